@@ -3,12 +3,18 @@
 synthetic RMAT graph, through the gmsx C-ABI on N GPUs of one node.
 
   python bench.py                       # N=1, RMAT scale-26 ef-16 (the graph BASELINE.json's metric is quoted on), 5 steps,
-                                        # 2 warm-ups; plus a parity record on scale 24 (configs[1], reference golden)
+                                        # 2 warm-ups: the headline figure only
+  python bench.py --full                # the same, plus every other record below (PMC traffic, side configs, CPU baselines, ...)
   python bench.py --scale 24            # configs[1] as the timed workload
+  python bench.py --dump-outputs DIR    # also write what the last timed step computed as DIR/*.npy (float64)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-At N=1 the same run appends the two other single-GPU perf configs of BASELINE.json as records of the JSON line:
+A plain run sets up (maps the graph from the --cache-dir cache, or generates and caches it), warms up, times the steps and prints the
+line; its roofline takes the traffic of an earlier --full run on the box or of profiles/hbm_traffic.json (same kernel build), measures none.
+`--prepare-only` generates the cache and exits (build() runs it on a host with a GPU).  Everything else runs only under --full:
+the live PMC passes and the read-stream ceiling of the roofline, a parity record on scale 24 (configs[1], reference golden), the CPU
+baselines, and at N=1 the two other single-GPU perf configs of BASELINE.json as records of the JSON line:
   config2_kclique4_s22   k = 4 cliques, RMAT scale-22 ef-16 (configs[2]); count asserted against the compiled reference's golden
   config3_bk             Bron–Kerbosch maximal cliques on the com-Orkut-shaped RMAT (|E| = 117 M, configs[3]); likewise
 each with kernel_ms (best of 3), roots/s, the lean upload time and beyond-L2 traffic from the same rocprofv3 PMC child mechanism.
@@ -373,8 +379,62 @@ def tc_s27_record(capi, args, algo, divisor, rank, t_start):
 
 # ---- rocprofv3 PMC passes, live --------------------------------------------------------------------------------------
 
+def default_cache_dir():
+    """GMSX_CACHE, else ~/.cache/gmsx: the graphs generated once (by build() on a host with a GPU, or by the first run) stay for the runs
+    that follow; the temp directory where the home directory cannot be written."""
+    if os.environ.get("GMSX_CACHE"):
+        return os.environ["GMSX_CACHE"]
+    home = os.path.expanduser("~")
+    if os.path.isdir(home) and os.access(home, os.W_OK):
+        return os.path.join(os.environ.get("XDG_CACHE_HOME") or os.path.join(home, ".cache"), "gmsx")
+    return os.path.join(tempfile.gettempdir(), f"gmsx_cache_{os.getuid()}")
+
+
 def sg_cache_path(args):
     return os.path.join(args.cache_dir, f"{args.generator}-{args.scale}-{args.degree}.sgx")  # mapped, not read: the ranks / PMC children share one page-cache copy
+
+
+def save_cache(csr, path):
+    """Writes the .sgx cache atomically (a reader never maps a half-written file)."""
+    fd, tmp = tempfile.mkstemp(prefix=".sg_", dir=os.path.dirname(path))
+    os.close(fd)
+    try:
+        csr.save_sgx(tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def prepare_input(args):
+    """--prepare-only: the timed graph into the cache, so that a run maps it instead of generating it (RMAT scale 26: ~30 s of host time on
+    16 cores, ~9 GB on disk).  Skipped when cached already or when the disk has no room for it; a run without the cache generates the graph."""
+    from gms_amd import capi
+    sg = sg_cache_path(args)
+    if os.path.exists(sg):
+        print(f"[bench] {sg} is cached already", file=sys.stderr)
+        return
+    os.makedirs(args.cache_dir, mode=0o700, exist_ok=True)
+    need = (8 + 4 * 2 * args.degree) << args.scale  # offsets + both directions of every generated edge: an upper bound of the file
+    free = shutil.disk_usage(args.cache_dir).free
+    if free < need + (2 << 30):
+        print(f"[bench] not caching {sg}: {free >> 30} GiB free, {need >> 30} GiB needed", file=sys.stderr)
+        return
+    capi.set_host_threads(host_cores())
+    t0 = time.perf_counter()
+    csr = capi.HostCSR.generate(args.generator, args.scale, args.degree, capi.RELABEL_AUTO)
+    save_cache(csr, sg)
+    print(f"[bench] cached {sg} ({os.path.getsize(sg) >> 20} MiB) in {time.perf_counter() - t0:.1f} s", file=sys.stderr)
+
+
+def dump_outputs(path, total, triangles):
+    """--dump-outputs: what the timed path returned in its last step, as float64 arrays (exact: the counts stay below 2^53)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, v in (("total_count", total), ("triangles", triangles)):
+        a = np.array([v], dtype=np.float64)
+        assert int(a[0]) == int(v), f"{name} = {v} is not exact in float64"
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 # the single-GPU perf configs of BASELINE.json besides the triangle count (configs[2], configs[3])
@@ -694,27 +754,40 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--scale", type=int, default=26, help="RMAT scale: 26 = the graph BASELINE.json's metric is quoted on; 24 = configs[1]")
-    ap.add_argument("--check-scale", type=int, default=24, help="N=1 only: extra untimed-setup pass on this scale, asserted against the "
+    ap.add_argument("--full", action="store_true", help="also everything beyond the headline figure: live PMC traffic passes, the read-stream ceiling, "
+                                                        "the configs[1] check, side records and CPU baselines (the options marked --full below)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last step computed "
+                                                                      "(the all-reduced count and the triangles) as DIR/<name>.npy, float64")
+    ap.add_argument("--prepare-only", action="store_true", help="generate the timed graph into --cache-dir (unless cached) and exit")
+    ap.add_argument("--check-scale", type=int, default=24, help="--full, N=1 only: extra untimed-setup pass on this scale, asserted against the "
                                                                "reference golden (configs[1]); 0 disables")
     ap.add_argument("--degree", type=int, default=16)
     ap.add_argument("--generator", default="kronecker")
     ap.add_argument("--algo", default="auto", choices=["auto", "oriented", "full"])
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="size of the CPU-baseline sample; 0 disables it")
-    ap.add_argument("--ref-scale", type=int, default=22, help="scale of the graph the compiled reference is timed on; 0 disables")
-    ap.add_argument("--cache-dir", default=os.environ.get("GMSX_CACHE") or os.path.join(tempfile.gettempdir(), f"gmsx_cache_{os.getuid()}"))
-    ap.add_argument("--pmc", type=int, default=1, help="N=1: collect HBM traffic with rocprofv3 PMC child passes in this run (0 = use profiles/hbm_traffic.json)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: size of the CPU-baseline sample; 0 disables it")
+    ap.add_argument("--ref-scale", type=int, default=22, help="--full: scale of the graph the compiled reference is timed on; 0 disables")
+    ap.add_argument("--cache-dir", default=default_cache_dir())
+    ap.add_argument("--pmc", type=int, default=1, help="--full, N=1: collect HBM traffic with rocprofv3 PMC child passes in this run (0 = use profiles/hbm_traffic.json)")
     ap.add_argument("--pmc-timeout", type=float, default=420.0)
-    ap.add_argument("--dump-traffic", default="", help="merge this run's PMC traffic table (all shard counts) into the given JSON file "
+    ap.add_argument("--dump-traffic", default="", help="--full: merge this run's PMC traffic table (all shard counts) into the given JSON file "
                                                        "(the committed fallback profiles/hbm_traffic.json is produced this way)")
-    ap.add_argument("--side", type=int, default=1, help="N=1: also run BASELINE configs[2] (k=4 cliques, scale 22) and configs[3] (Bron-Kerbosch, 117M-edge RMAT); 0 disables")
+    ap.add_argument("--side", type=int, default=1, help="--full, N=1: also run BASELINE configs[2] (k=4 cliques, scale 22) and configs[3] (Bron-Kerbosch, 117M-edge RMAT); 0 disables")
     ap.add_argument("--workload", default="tc", choices=["tc"] + sorted(WORKLOADS), help=argparse.SUPPRESS)
-    ap.add_argument("--big", type=int, default=1, help="N=1: also the two north-star-size records — kclique4_s26 (k = 4 on the headline graph, count == the reference's kClist golden) "
+    ap.add_argument("--big", type=int, default=1, help="--full, N=1: also the two north-star-size records — kclique4_s26 (k = 4 on the headline graph, count == the reference's kClist golden) "
                                                       "and tc_s27 (BASELINE configs[4]'s graph on ONE GPU: whole pass + its eight shards); 0 disables")
     ap.add_argument("--big-budget-s", type=float, default=330.0, help="tc_s27 (≈ 2 min of host-side graph generation) is skipped when the run is already older than this")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.pmc_child:
         return pmc_child(args)
+    if args.prepare_only:
+        return prepare_input(args)
+    if not args.full:  # a plain run: the headline figure only, no measurement beyond the timed steps
+        if args.dump_traffic:
+            ap.error("--dump-traffic records the PMC passes of a --full run")
+        args.pmc, args.side, args.big, args.cpu_seconds, args.check_scale = 0, 0, 0, 0.0, 0
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     from gms_amd import capi, dist
     rank, local_rank, world = dist.env_rank_world()
@@ -740,10 +813,7 @@ def main():
             csr = capi.HostCSR.generate(args.generator, args.scale, args.degree, capi.RELABEL_AUTO)
             if os.environ.get("GMSX_NO_CACHE") != "1" or world > 1:
                 try:
-                    fd, tmp = tempfile.mkstemp(prefix=".sg_", dir=args.cache_dir)
-                    os.close(fd)
-                    csr.save_sgx(tmp)
-                    os.replace(tmp, sg)
+                    save_cache(csr, sg)
                     if world > 1:  # rank 0 drops its private copy and maps the cache like the other ranks: ONE copy of the CSR in host memory
                         csr = None
                         csr = capi.HostCSR.load(sg, relabel=capi.RELABEL_NEVER)
@@ -806,7 +876,7 @@ def main():
     capi.set_stream(torch.cuda.current_stream().cuda_stream)
     info = capi.device_info()
     ceiling = None
-    if rank == 0 and not share:
+    if rank == 0 and not share and args.full:
         try:  # the box's own read-stream ceiling, before the graph takes the memory: 8 GiB swept 40 times, ~60 ms
             ceiling = capi.hbm_read_probe(8 << 30, 40)
             log(rank, f"read-only stream ceiling of this device: {ceiling:.0f} GB/s")
@@ -896,6 +966,8 @@ def main():
         parity = f"== reference golden ({golden_src or 'tests/golden/graphs.json'})"
     else:
         parity = "no reference golden at this size (self-consistency only: every step returned the same count)"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, totals[-1], totals[-1] // divisor)
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = m * args.steps / elapsed
@@ -1023,7 +1095,7 @@ def main():
         out["cpu_baseline"] = None
         try:
             with open(cpu_cache) as f:
-                out["cpu_baseline"] = dict(json.load(f), measured_by="the N=1 run of bench.py on this box (cached in --cache-dir); not re-timed at N>1")
+                out["cpu_baseline"] = dict(json.load(f), measured_by="the N=1 --full run of bench.py on this box (cached in --cache-dir); not re-timed by this run")
         except (OSError, ValueError):
             pass
     if rank == 0:

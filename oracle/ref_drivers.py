@@ -90,7 +90,7 @@ def build(name, workdir, lean, exe):
     # the reference's flags of record (CMakeLists.txt:10-11,32) with a portable -march; include dir of the driver for "verifier.h"
     cmd = ["g++", "-std=c++17", "-O2", "-march=x86-64-v3", "-fopenmp", "-w", "-DNOPAPIW"] + d["flags"] + \
           ["-I", os.path.join(ROOT, "include"), "-I", REF, "-I", os.path.dirname(os.path.join(REF, d["src"])), src, roaring,
-           "-L", LIBDIR, "-lgmsx", "-Wl,-rpath," + LIBDIR, "-Wl,-rpath,$ORIGIN/../../gms_amd/lib", "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
+           "-L", LIBDIR, "-lgmsx", "-Wl,-rpath," + LIBDIR, "-Wl,-rpath,$ORIGIN/../../../gms_amd/lib", "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
     subprocess.run(cmd, check=True)
     os.remove(src)  # patched reference text never stays on disk
 

@@ -55,7 +55,7 @@ def test_bench_eight_ranks_on_one_gpu(gpu, tmp_path):
     shard 0 of 8 on this kernel build.  UNMEASURED on real multi-GPU hardware: no 8-GPU node has been available to any round."""
     cache = str(tmp_path / "cache")
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "22", "--steps", "2", "--warmup", "1", "--cache-dir", cache, "--side", "0",
+    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--scale", "22", "--steps", "2", "--warmup", "1", "--cache-dir", cache, "--side", "0",
                          "--cpu-seconds", "0", "--check-scale", "0", "--big", "0"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r1.returncode == 0, r1.stderr[-3000:]
     one = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][0])

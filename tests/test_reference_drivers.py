@@ -17,7 +17,13 @@ import subprocess
 import pytest
 
 from conftest import ROOT  # noqa: F401
-from oracle.ref_drivers import DRIVERS, OUT, build, have_ref
+from oracle.ref_drivers import DRIVERS, LIBDIR, OUT, build, have_ref
+
+
+def _driver_env():
+    """The prebuilt drivers load this tree's libgmsx.so whatever their rpath says: oracle/_ref/ may have been built under another path or be
+    reached through a link, and $ORIGIN resolves to where the binary really lies."""
+    return dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(p for p in (LIBDIR, os.environ.get("LD_LIBRARY_PATH")) if p))
 
 
 @pytest.mark.parametrize("name", sorted(DRIVERS))
@@ -32,7 +38,7 @@ def test_real_driver_compiles_with_one_added_line(tmp_path, capi, name):
     os.makedirs(OUT, exist_ok=True)
     build(name, str(tmp_path), lean=True, exe=os.path.join(OUT, name))
     # no GPU here: the harness reaches FromCGraph, the upload is skipped, the first device call fails loudly (exit code -32 & 0xff)
-    r = subprocess.run([os.path.join(OUT, name), "-n", "1", "-g", "kronecker", "8"], capture_output=True, text=True)  # clipp: flags before the -g group
+    r = subprocess.run([os.path.join(OUT, name), "-n", "1", "-g", "kronecker", "8"], capture_output=True, text=True, env=_driver_env())  # clipp: flags before the -g group
     if "GraphExec buildTime" in r.stdout and r.returncode != 0:
         assert "no HIP device" in r.stderr, r.stderr
 
@@ -69,7 +75,7 @@ def test_real_driver_runs_on_device_under_reference_harness(gpu, name, args, nee
     exe = os.path.join(OUT, name)
     if not os.path.exists(exe):
         pytest.skip("oracle/_ref/drivers/%s not prebuilt (needs the reference tree at build time)" % name)
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=600, env=_driver_env())
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     for n in needles:
         assert n in r.stdout, r.stdout[-3000:]
