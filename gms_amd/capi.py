@@ -37,7 +37,7 @@ SYMBOLS = [
     "gmsx_graph_upload", "gmsx_graph_upload_csr", "gmsx_graph_upload_shard", "gmsx_graph_upload_csr_shard", "gmsx_graph_prepare", "gmsx_graph_tc_passes", "gmsx_graph_free", "gmsx_graph_num_nodes", "gmsx_graph_num_edges",
     "gmsx_graph_device_bytes", "gmsx_graph_max_out_degree",
     "gmsx_tc_total", "gmsx_tc_partial", "gmsx_tc_divisor", "gmsx_tc_stream_breakdown", "gmsx_tc_row_histogram", "gmsx_tc_comembership", "gmsx_tc_vertex_count2",
-    "gmsx_intersect_count_batch", "gmsx_set_op_batch", "gmsx_vertex_similarity_batch", "gmsx_kclique_count", "gmsx_kclique_partial", "gmsx_kclique_star_count", "gmsx_bk_count", "gmsx_bk_partial",
+    "gmsx_intersect_count_batch", "gmsx_set_op_batch", "gmsx_vertex_similarity_batch", "gmsx_kclique_count", "gmsx_kclique_partial", "gmsx_kclique_star_count", "gmsx_bk_count", "gmsx_bk_partial", "gmsx_bk_list",
     "gmsx_adg_rank", "gmsx_tc_ordering",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -50,6 +50,14 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class BkListInfo(C.Structure):
+    _fields_ = [("cliques", C.c_int64), ("members", C.c_int64), ("max_size", C.c_int32), ("size_hist", C.c_int64 * 65)]
+
+    def as_dict(self):
+        return {"cliques": int(self.cliques), "members": int(self.members), "max_size": int(self.max_size),
+                "size_hist": [int(x) for x in self.size_hist]}
 
 
 class GmsxError(RuntimeError):
@@ -126,6 +134,7 @@ def lib():
     L.gmsx_kclique_star_count.argtypes = [vp, C.c_int, u64p, u64p, sp]
     L.gmsx_bk_count.argtypes = [vp, C.c_void_p, u64p, sp]
     L.gmsx_bk_partial.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, u64p, sp]
+    L.gmsx_bk_list.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(BkListInfo), sp]
     L.gmsx_adg_rank.argtypes = [vp, C.c_double, C.c_int, _i32p, C.POINTER(C.c_int32), sp]
     L.gmsx_tc_ordering.argtypes = [vp, _i32p, sp]
     L.gmsx_comm_unique_id.argtypes = [C.c_char_p]
@@ -454,6 +463,35 @@ class DeviceGraph:
             rp = rank.ctypes.data_as(C.c_void_p)
         _check(lib().gmsx_bk_partial(self._h, rp, part, nparts, C.byref(out), C.byref(st)), "gmsx_bk_partial")
         return (int(out.value), st.as_dict()) if stats else int(out.value)
+
+    def bk_list_info(self, rank=None, part=0, nparts=1):
+        """gmsx_bk_list, sizing call: {cliques, members, max_size, size_hist[65]} of shard (part, nparts)."""
+        info = BkListInfo()
+        rp = None
+        if rank is not None:
+            rank = np.ascontiguousarray(rank, dtype=np.int32)
+            rp = rank.ctypes.data_as(C.c_void_p)
+        _check(lib().gmsx_bk_list(self._h, rp, part, nparts, None, None, 0, 0, C.byref(info), None), "gmsx_bk_list (sizing)")
+        return info.as_dict()
+
+    def bk_list(self, rank=None, part=0, nparts=1, stats=False):
+        """gmsx_bk_list: the maximal cliques of shard (part, nparts) as (offsets int64[n + 1], members int32[m]) — clique i is
+        members[offsets[i]:offsets[i + 1]], ascending caller ids.  The sizing call, then the fill into arrays of exactly that size."""
+        info, st = BkListInfo(), Stats()
+        rp = None
+        if rank is not None:
+            rank = np.ascontiguousarray(rank, dtype=np.int32)
+            rp = rank.ctypes.data_as(C.c_void_p)
+        _check(lib().gmsx_bk_list(self._h, rp, part, nparts, None, None, 0, 0, C.byref(info), C.byref(st)), "gmsx_bk_list (sizing)")
+        sizing = st.as_dict()
+        off = np.zeros(int(info.cliques) + 1, dtype=np.int64)
+        mem = np.zeros(max(int(info.members), 1), dtype=np.int32)
+        _check(lib().gmsx_bk_list(self._h, rp, part, nparts, off.ctypes.data_as(C.c_void_p), mem.ctypes.data_as(C.c_void_p), off.size,
+                                  int(info.members), C.byref(info), C.byref(st)), "gmsx_bk_list")
+        mem = mem[:int(info.members)]
+        if stats:
+            return off, mem, {"sizing": sizing, "fill": st.as_dict(), "info": info.as_dict()}
+        return off, mem
 
     def adg_rank(self, epsilon=0.001, rank_format=True, stats=False):
         """gmsx_adg_rank: (rank or order vector, number of peeling rounds)"""

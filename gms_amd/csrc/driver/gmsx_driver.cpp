@@ -12,6 +12,7 @@
 // Added:  --gpus N   one process per GPU (this binary FORKS its N ranks before it touches HIP and stays behind as their supervisor), every rank counts its
 //                    shard (gmsx_*_partial) and ONE u64 all-reduce over RCCL (gmsx_comm_allreduce_u64) replaces the OpenMP
 //                    reduction(+:total) of parallel/total.h:12.  --gpus 1 runs the same path with a 1-rank communicator.
+// Added:  bk --list FILE   the maximal cliques of the last trial (gmsx_bk_list, outside the timed trial), one per line, members ascending.
 // Usage:  gmsx_driver <tc|vertex|kclique|bk> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
@@ -42,6 +43,7 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     int scale = -1, deg = 16;
     int clique_size = 4;
     int gpus = 0;  // 0 = single process without a communicator
+    std::string list;  // bk --list FILE: the maximal cliques of the last trial, one per line (gmsx_bk_list)
     int error = 0;
 };
 
@@ -67,6 +69,7 @@ Args parse(int argc, char **argv) {
         else if (f == "-f" || f == "--file") { if (!need(1)) break; a.file = argv[++i]; }
         else if (f == "-g" || f == "--gen") { if (!need(2)) break; a.gen = argv[++i]; a.scale = std::atoi(argv[++i]); }
         else if (f == "--deg") { if (!need(1)) break; a.deg = std::atoi(argv[++i]); }
+        else if (f == "--list") { if (!need(1)) break; a.list = argv[++i]; }
         else if (f == "--gpus") { if (!need(1)) break; a.gpus = std::atoi(argv[++i]); if (a.gpus < 1 || a.gpus > 64) a.error = 100; }
         else if (f == "--opt") {  // --opt NAME=VALUE -> gmsx_set_option (limits, kernel variants, diagnostics: include/gmsx.h); unknown names are refused
             if (!need(1)) break;
@@ -86,12 +89,13 @@ Args parse(int argc, char **argv) {
     }
     if (!a.error && a.file.empty() && a.gen.empty()) a.error = 101;  // cli/cli.h:131-133
     if (!a.error && !a.gen.empty() && a.gen != "kronecker" && a.gen != "uniform") a.error = 100;
+    if (!a.error && !a.list.empty() && (a.kernel != "bk" || a.gpus > 1)) a.error = 100;  // one process writes the whole list
     return a;
 }
 
 void usage(const char *argv0) {
     std::printf("usage: %s <tc|vertex|kclique|bk> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
-                "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...]\n", argv0);
+                "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk: --list FILE]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -442,6 +446,23 @@ int main(int argc, char **argv) {
         PrintTime("Trial Time", trial);
         if (args.kernel == "tc") std::printf("triangles: %" PRIu64 "\n", result);
         if (args.kernel == "bk") std::printf("The Number of maximal clique counted: %" PRIu64 "\n", result);  // helper.h:120-133
+        if (args.kernel == "bk" && !args.list.empty() && it + 1 == args.trials) {  // outside the timed trial: the listing build's `sol`
+            const auto cliques = gmsx::maximal_cliques(g, order);
+            FILE *fo = std::fopen(args.list.c_str(), "w");
+            if (!fo) {
+                std::fprintf(stderr, "gmsx_driver: --list %s: cannot open\n", args.list.c_str());
+                return 2;
+            }
+            for (const auto &c : cliques) {
+                bool first = true;
+                for (auto v : c) {
+                    std::fprintf(fo, first ? "%d" : " %d", int(v));
+                    first = false;
+                }
+                std::fputc('\n', fo);
+            }
+            if (std::fclose(fo) != 0) return 2;
+        }
         if (args.verify && root) {  // rank 0 verifies; the others go on to the next trial's all-reduce and wait there
             t.Start();
             bool ok = true;

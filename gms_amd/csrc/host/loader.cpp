@@ -772,6 +772,8 @@ Option g_options[] = {
     {"BK_MAXC", "", false}, {"BK_ARENA_MB", "", false}, {"BK_GROUPS", "", false}, {"BK_SMALL_P", "", false}, {"BK_SMALL_P_GROUPS", "", false},
     {"BK_BUDGET", "", false}, {"BK_BUDGET0", "", false}, {"BK_RESUME_GRAB", "", false}, {"BK_SPLIT_BUILD", "", false}, {"BK_TINY_ROOTS", "", false},
     {"BK_TINY_BESIDE", "", false},
+    // Bron–Kerbosch listing (bk_list.hip)
+    {"BK_LIST_ARENA_MB", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

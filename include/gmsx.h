@@ -137,7 +137,8 @@ int gmsx_set_host_threads(int n);
  *                   KC_POOL_MB (the pool those pivots' matrices pass through, default min(what the call needs, 6144): smaller = more, shorter chunks)
  *   Bron–Kerbosch   BK_MAXC (widest start vertex of the register-resident search), BK_ARENA_MB, BK_BUDGET / BK_BUDGET0 (nodes before a
  *                   search is re-split), BK_GROUPS, BK_SMALL_P, BK_SMALL_P_GROUPS, BK_RESUME_GRAB, BK_SPLIT_BUILD, BK_TINY_ROOTS,
- *                   BK_TINY_BESIDE (kernel variants) */
+ *                   BK_TINY_BESIDE (kernel variants)
+ *   Bron–Kerbosch listing  BK_LIST_ARENA_MB (budget of the search slabs of one launch: smaller = more launches) */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -318,6 +319,36 @@ int gmsx_kclique_star_count(const gmsx_graph *g, int k, uint64_t *stars, uint64_
  * magnitude slower per node, same count — so no graph is refused for the width of a neighbourhood. */
 int gmsx_bk_count(const gmsx_graph *g, const int32_t *rank, uint64_t *maximal_cliques, gmsx_stats *stats);
 int gmsx_bk_partial(const gmsx_graph *g, const int32_t *rank, int part, int nparts, uint64_t *partial, gmsx_stats *stats);
+
+/* ---- Bron–Kerbosch maximal-clique LISTING: BkEppsteinPar::mceBench without -DBK_COUNT (eppsteinPAR.h:18-53, tomita.h:79-84 fill `sol`).
+ * The cliques listed are exactly the reference's: every maximal clique of the graph once, an isolated vertex v as {v}.  Members are the
+ * vertex ids of the uploaded CSR, strictly ascending inside each clique; clique i is members[offsets[i] .. offsets[i+1]), offsets[0] = 0.
+ * rank: validated exactly as by gmsx_bk_count (NULL, or a permutation of 0..n-1, else GMSX_ERR_INVALID); the set does not depend on it.
+ * Two calls:
+ *   sizing  offsets == NULL and members == NULL: only *info is filled (info is required on every call);
+ *   fill    offsets_capacity >= info.cliques + 1 and members_capacity >= info.members (members may be NULL if that is 0), else
+ *           GMSX_ERR_INVALID with *info holding the required sizes and neither buffer written.
+ * A fill call that follows the sizing call of the same handle and shard re-uses its first pass (one search instead of two).
+ * Order: the cliques of one start vertex are contiguous, start vertices in the device's degree order (decreasing (degree, id)); inside one
+ * start vertex the depth-first order of its search.  The same graph, upload flags, part and nparts give byte-identical arrays, in every
+ * process.
+ * Shards: start vertex v belongs to part shard_of(p) where p is v's position in that degree order and shard_of(p) = p mod nparts on even
+ * stripes p / nparts, nparts - 1 - (p mod nparts) on odd ones; a clique is listed by its member of the lowest position.  The shards of one
+ * nparts are disjoint and their union is the whole list; (0, 1) is the whole graph.  A shard can be listed (and freed) at a time, so an
+ * output larger than host memory can be streamed.
+ * Width: every start vertex runs the same memory-resident search (a global slab of Cadj | XT | levels per start vertex), so no graph that
+ * gmsx_bk_count accepts is refused for the width of a neighbourhood.  Test hook: option BK_LIST_ARENA_MB (budget of the slabs of one
+ * launch; smaller = more launches).  Errors inside a pass (a slab or output bound, a fill that disagrees with its sizing pass) are
+ * reported as GMSX_ERR_KERNEL; nothing is written out of bounds. */
+typedef struct {
+    int64_t cliques;        /* maximal cliques of this call's shard */
+    int64_t members;        /* sum of their sizes = entries `members` needs */
+    int32_t max_size;       /* largest clique listed (0 if none) */
+    int64_t size_hist[65];  /* [s] = cliques with s members for s < 64, [64] = 64 or more; [0] = 0 */
+} gmsx_bk_list_info;
+int gmsx_bk_list(const gmsx_graph *g, const int32_t *rank, int part, int nparts, int64_t *offsets /* info->cliques + 1 entries, host, or NULL */,
+                 int32_t *members /* info->members entries, host, or NULL */, int64_t offsets_capacity, int64_t members_capacity,
+                 gmsx_bk_list_info *info /* required */, gmsx_stats *stats);
 
 /* ---- vertex orderings that consume the path's operators ----
  * PpParallel::getDegeneracyOrderingApproxSGraph<boundary_function::averageDegree> (preprocessing/parallel/

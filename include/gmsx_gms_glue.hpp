@@ -12,6 +12,7 @@
 //   GMS::TriangleCount::Par::vertex_count2 / vertex_count2_once / Seq::vertex_count2     parallel/vertex.h:14-49, sequential/vertex.h:14-26
 //   CliqueCount<Set, SGraph, Set2>                                      gms/algorithms/set_based/k_clique_count/k_clique_count_set_based.h:19-31
 //   BkEppsteinPar::mceBench<SGraph>   (count builds only, see below)    gms/algorithms/set_based/maximal_clique_enum/parallel/eppsteinPAR.h:18-53
+//   BkEppsteinPar::mceBench<SGraph>   (listing builds, opt-in: GMSX_GLUE_BK_LIST, see below)
 //   PpParallel::getDegeneracyOrderingApproxSGraph<averageDegree, …>     gms/algorithms/preprocessing/parallel/degeneracy_approx_set.h:14-86
 //   PpParallel::triangleCountOrdering<SGraph>                           gms/algorithms/preprocessing/parallel/triangle_count.h:11-30
 // Everything not listed (Verify::*, BkTomita::mce, getDegreeOrdering, getDegeneracyOrderingMatula, …) keeps instantiating the
@@ -67,6 +68,29 @@ using HipSetRefGraph = gmsx::HipSetRefGraph;    // SetGraph<SortedSetRef> flavou
 #define GMSX_GLUE_BK(SGRAPH)
 #endif
 
+// OPT-IN listing route: a translation unit that defines GMSX_GLUE_BK_LIST before including this header, in a listing build (-DMINEBENCH_TEST),
+// gets mceBench<HipSetGraph> / <HipRoaringGraph> on the device — the maximal cliques themselves (gmsx_bk_list), members ascending; with BK_COUNT
+// as well, BK_CLIQUE_COUNTER is set to their number.  Without GMSX_GLUE_BK_LIST nothing changes (the listing builds above keep the host template).
+#if defined(GMSX_GLUE_BK_LIST) && defined(MINEBENCH_TEST)
+#define GMSX_GLUE_BK_LIST_ROUTED 1
+#ifdef BK_COUNT
+#define GMSX_GLUE_BK_LIST_COUNTER(n) (BK_CLIQUE_COUNTER = (n))
+#else
+#define GMSX_GLUE_BK_LIST_COUNTER(n) ((void)(n))
+#endif
+#define GMSX_GLUE_BK_LIST_SPEC(SGRAPH)                                                                                             \
+    namespace BkEppsteinPar {                                                                                                      \
+    template <> inline std::vector<SGRAPH::Set> mceBench<SGRAPH, SGRAPH::Set>(const SGRAPH &g, const pvector<NodeId> &ordering) { \
+        std::vector<SGRAPH::Set> sol = gmsx::maximal_cliques(g, ordering);                                                         \
+        GMSX_GLUE_BK_LIST_COUNTER(sol.size());                                                                                     \
+        return sol;                                                                                                                \
+    }                                                                                                                              \
+    }
+#else
+#define GMSX_GLUE_BK_LIST_ROUTED 0
+#define GMSX_GLUE_BK_LIST_SPEC(SGRAPH)
+#endif
+
 #define GMSX_GLUE_ADG(SGRAPH)                                                                                                      \
     namespace PpParallel {                                                                                                         \
     template <>                                                                                                                    \
@@ -93,6 +117,8 @@ GMSX_GLUE_TC(HipRoaringGraph)
 GMSX_GLUE_TC(HipSetRefGraph)
 GMSX_GLUE_BK(HipSetGraph)
 GMSX_GLUE_BK(HipRoaringGraph)
+GMSX_GLUE_BK_LIST_SPEC(HipSetGraph)
+GMSX_GLUE_BK_LIST_SPEC(HipRoaringGraph)
 GMSX_GLUE_ADG(HipSetGraph)
 GMSX_GLUE_ADG(HipRoaringGraph)
 GMSX_GLUE_KC(gmsx::SortedSpanSet, HipSetGraph, gmsx::SortedSpanSet)        // like <SortedSet, SortedSetGraph, SortedSet>         (k_clique_count_set_based.cc:42)
@@ -101,5 +127,6 @@ GMSX_GLUE_KC(gmsx::SortedSpanSet, HipSetRefGraph, gmsx::SortedSpanRef)     // li
 
 #undef GMSX_GLUE_TC
 #undef GMSX_GLUE_BK
+#undef GMSX_GLUE_BK_LIST_SPEC
 #undef GMSX_GLUE_ADG
 #undef GMSX_GLUE_KC

@@ -548,4 +548,35 @@ inline std::vector<S> set_op_batch(const HipGraphT<S> &g, const Ids &u, const Id
     return out;
 }
 
+// BkEppsteinPar::mceBench WITHOUT -DBK_COUNT (eppsteinPAR.h:18-53, tomita.h:79-84): the maximal cliques themselves, each an owning set of the
+// graph's own flavour (members ascending).  `rank` is validated like maximal_clique_count's and does not change the set.  One sizing call,
+// one fill (gmsx_bk_list); the order of the cliques is deterministic but otherwise unspecified, like the reference's parallel `sol`.
+template <class S>
+inline std::vector<S> maximal_cliques_shard(const HipGraphT<S> &g, const int32_t *rank, int part, int nparts) {
+    gmsx_bk_list_info info{};
+    detail::check(gmsx_bk_list(g.device(), rank, part, nparts, nullptr, nullptr, 0, 0, &info, nullptr), "gmsx_bk_list");
+    std::vector<int64_t> off(size_t(info.cliques) + 1, 0);
+    std::vector<int32_t> ids(size_t(info.members) + 1);
+    detail::check(gmsx_bk_list(g.device(), rank, part, nparts, off.data(), ids.data(), int64_t(off.size()), info.members, &info, nullptr), "gmsx_bk_list");
+    std::vector<S> out;
+    out.reserve(size_t(info.cliques));
+    for (int64_t i = 0; i < info.cliques; ++i) out.emplace_back(ids.data() + off[size_t(i)], size_t(off[size_t(i) + 1] - off[size_t(i)]));  // (owning copies)
+    return out;
+}
+template <class S>
+inline std::vector<S> maximal_cliques(const HipGraphT<S> &g) {
+    return maximal_cliques_shard(g, nullptr, 0, 1);
+}
+template <class S, class Ranking>
+inline std::vector<S> maximal_cliques(const HipGraphT<S> &g, const Ranking &rank) {
+    const auto *r = rank.data();
+    if constexpr (sizeof(*r) == sizeof(int32_t) && std::is_integral_v<std::remove_cv_t<std::remove_reference_t<decltype(*r)>>>) {
+        return maximal_cliques_shard(g, reinterpret_cast<const int32_t *>(r), 0, 1);
+    } else {
+        std::unique_ptr<int32_t[]> tmp(new int32_t[size_t(g.num_nodes())]);
+        for (int64_t i = 0; i < g.num_nodes(); ++i) tmp[size_t(i)] = int32_t(rank[size_t(i)]);
+        return maximal_cliques_shard(g, tmp.get(), 0, 1);
+    }
+}
+
 }  // namespace gmsx
