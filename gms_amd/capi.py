@@ -37,7 +37,7 @@ SYMBOLS = [
     "gmsx_graph_upload", "gmsx_graph_upload_csr", "gmsx_graph_upload_shard", "gmsx_graph_upload_csr_shard", "gmsx_graph_prepare", "gmsx_graph_tc_passes", "gmsx_graph_free", "gmsx_graph_num_nodes", "gmsx_graph_num_edges",
     "gmsx_graph_device_bytes", "gmsx_graph_max_out_degree",
     "gmsx_tc_total", "gmsx_tc_partial", "gmsx_tc_divisor", "gmsx_tc_stream_breakdown", "gmsx_tc_row_histogram", "gmsx_tc_comembership", "gmsx_tc_vertex_count2",
-    "gmsx_intersect_count_batch", "gmsx_set_op_batch", "gmsx_vertex_similarity_batch", "gmsx_kclique_count", "gmsx_kclique_partial", "gmsx_kclique_star_count", "gmsx_bk_count", "gmsx_bk_partial", "gmsx_bk_list",
+    "gmsx_intersect_count_batch", "gmsx_set_op_batch", "gmsx_vertex_similarity_batch", "gmsx_kclique_count", "gmsx_kclique_partial", "gmsx_kclique_star_count", "gmsx_kclique_star_list", "gmsx_bk_count", "gmsx_bk_partial", "gmsx_bk_list",
     "gmsx_adg_rank", "gmsx_tc_ordering",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -58,6 +58,16 @@ class BkListInfo(C.Structure):
     def as_dict(self):
         return {"cliques": int(self.cliques), "members": int(self.members), "max_size": int(self.max_size),
                 "size_hist": [int(x) for x in self.size_hist]}
+
+
+class KcliqueStarListInfo(C.Structure):
+    _fields_ = [("cliques", C.c_int64), ("star_members", C.c_int64), ("k", C.c_int32), ("max_star", C.c_int32)]
+
+    def as_dict(self):
+        return {"cliques": int(self.cliques), "star_members": int(self.star_members), "k": int(self.k), "max_star": int(self.max_star)}
+
+
+KCSTAR_DEFAULT, KCSTAR_CLIQUES_ONLY = 0, 1
 
 
 class GmsxError(RuntimeError):
@@ -132,6 +142,8 @@ def lib():
     L.gmsx_kclique_count.argtypes = [vp, C.c_int, u64p, u64p, sp]
     L.gmsx_kclique_partial.argtypes = [vp, C.c_int, C.c_int, C.c_int, u64p, sp]
     L.gmsx_kclique_star_count.argtypes = [vp, C.c_int, u64p, u64p, sp]
+    L.gmsx_kclique_star_list.argtypes = [vp, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                         C.POINTER(KcliqueStarListInfo), sp]
     L.gmsx_bk_count.argtypes = [vp, C.c_void_p, u64p, sp]
     L.gmsx_bk_partial.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, u64p, sp]
     L.gmsx_bk_list.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(BkListInfo), sp]
@@ -440,6 +452,40 @@ class DeviceGraph:
         _check(lib().gmsx_kclique_star_count(self._h, k, C.byref(stars), C.byref(mem) if members else None, C.byref(st)), "gmsx_kclique_star_count")
         r = (int(stars.value), int(mem.value) if members else None)
         return (r + (st.as_dict(),)) if stats else r
+
+    def kclique_star_list_info(self, k, cliques_only=False, part=0, nparts=1):
+        """gmsx_kclique_star_list, sizing call: {cliques, star_members, k, max_star} of shard (part, nparts)."""
+        info = KcliqueStarListInfo()
+        flags = KCSTAR_CLIQUES_ONLY if cliques_only else KCSTAR_DEFAULT
+        _check(lib().gmsx_kclique_star_list(self._h, k, flags, part, nparts, None, None, None, 0, 0, C.byref(info), None),
+               "gmsx_kclique_star_list (sizing)")
+        return info.as_dict()
+
+    def kclique_star_list(self, k, cliques_only=False, part=0, nparts=1, stats=False):
+        """gmsx_kclique_star_list: the (clique, star) pairs of shard (part, nparts) as (cliques int32[C, k], star_offsets int64[C + 1],
+        star_members int32[M]) — star i is star_members[star_offsets[i]:star_offsets[i + 1]]; all ids ascending caller ids.  With
+        cliques_only the last two are None (k-clique listing).  The sizing call, then the fill into arrays of exactly that size."""
+        info, st = KcliqueStarListInfo(), Stats()
+        flags = KCSTAR_CLIQUES_ONLY if cliques_only else KCSTAR_DEFAULT
+        _check(lib().gmsx_kclique_star_list(self._h, k, flags, part, nparts, None, None, None, 0, 0, C.byref(info), C.byref(st)),
+               "gmsx_kclique_star_list (sizing)")
+        sizing = st.as_dict()
+        nc, nm = int(info.cliques), int(info.star_members)
+        cl = np.zeros(max(nc * k, 1), dtype=np.int32)
+        soff = mem = None
+        if not cliques_only:
+            soff = np.zeros(nc + 1, dtype=np.int64)
+            mem = np.zeros(max(nm, 1), dtype=np.int32)
+        _check(lib().gmsx_kclique_star_list(self._h, k, flags, part, nparts, cl.ctypes.data_as(C.c_void_p),
+                                            None if cliques_only else soff.ctypes.data_as(C.c_void_p),
+                                            None if cliques_only else mem.ctypes.data_as(C.c_void_p), nc, nm, C.byref(info), C.byref(st)),
+               "gmsx_kclique_star_list")
+        cl = cl[:nc * k].reshape(nc, k)
+        if mem is not None:
+            mem = mem[:nm]
+        if stats:
+            return cl, soff, mem, {"sizing": sizing, "fill": st.as_dict(), "info": info.as_dict()}
+        return cl, soff, mem
 
     def kclique_partial(self, k, part, nparts, stats=False):
         out, st = C.c_uint64(0), Stats()

@@ -13,7 +13,10 @@
 //                    shard (gmsx_*_partial) and ONE u64 all-reduce over RCCL (gmsx_comm_allreduce_u64) replaces the OpenMP
 //                    reduction(+:total) of parallel/total.h:12.  --gpus 1 runs the same path with a 1-rank communicator.
 // Added:  bk --list FILE   the maximal cliques of the last trial (gmsx_bk_list, outside the timed trial), one per line, members ascending.
-// Usage:  gmsx_driver <tc|vertex|kclique|bk> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  kcstar -p clique-size=k [--list FILE]   KCliqueStar::Par::CliqueStarList (k_clique_star_list/parallel/recursive.h:19-43) on the device: prints the
+//                    reference's "total k-cliques: N" line (:34, N = the number of pairs); --list writes the pairs of the last trial (gmsx_kclique_star_list, outside
+//                    the timed trial), one per line: "c1 … ck | s1 …", clique and star ascending.  Not sharded (--gpus > 1 is refused).
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -89,13 +92,14 @@ Args parse(int argc, char **argv) {
     }
     if (!a.error && a.file.empty() && a.gen.empty()) a.error = 101;  // cli/cli.h:131-133
     if (!a.error && !a.gen.empty() && a.gen != "kronecker" && a.gen != "uniform") a.error = 100;
-    if (!a.error && !a.list.empty() && (a.kernel != "bk" || a.gpus > 1)) a.error = 100;  // one process writes the whole list
+    if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
+    if (!a.error && a.kernel == "kcstar" && a.gpus > 1) a.error = 100;
     return a;
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|bk> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
-                "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk: --list FILE]\n", argv0);
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+                "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -330,7 +334,7 @@ int launch_ranks(int gpus) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "bk") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -434,6 +438,13 @@ int main(int argc, char **argv) {
             result = reduce(part) * fact;  // the reference's value k!·C_k, mod 2^64 like size_t
             std::printf("total %d-cliques: %" PRIu64 "\n", args.clique_size, result);  // k_clique_count_set_based.h:29
             label = "HipSet HipSetGraph";
+        } else if (args.kernel == "kcstar") {  // the timed kernel is the listing's sizing pass: every pair is found, none is copied out
+            gmsx_kclique_star_list_info info{};
+            gmsx::detail::check(gmsx_kclique_star_list(g.device(), args.clique_size, GMSX_KCSTAR_DEFAULT, 0, 1, nullptr, nullptr, nullptr, 0, 0, &info, nullptr),
+                                "gmsx_kclique_star_list");
+            result = uint64_t(info.cliques);
+            std::printf("total %d-cliques: %" PRIu64 "\n", args.clique_size, result);  // k_clique_star_list/parallel/recursive.h:34
+            label = "kcstar-list-par-HipSetGraph";
         } else {
             uint64_t part = 0;
             gmsx::detail::check(gmsx_bk_partial(g.device(), order.data(), rank, nranks, &part, nullptr), "gmsx_bk_partial");
@@ -459,6 +470,21 @@ int main(int argc, char **argv) {
                     std::fprintf(fo, first ? "%d" : " %d", int(v));
                     first = false;
                 }
+                std::fputc('\n', fo);
+            }
+            if (std::fclose(fo) != 0) return 2;
+        }
+        if (args.kernel == "kcstar" && !args.list.empty() && it + 1 == args.trials) {  // outside the timed trial: the pairs themselves
+            const auto pairs = gmsx::clique_stars(g, int32_t(args.clique_size));
+            FILE *fo = std::fopen(args.list.c_str(), "w");
+            if (!fo) {
+                std::fprintf(stderr, "gmsx_driver: --list %s: cannot open\n", args.list.c_str());
+                return 2;
+            }
+            for (const auto &p : pairs) {
+                for (auto v : p[0]) std::fprintf(fo, "%d ", int(v));
+                std::fputc('|', fo);
+                for (auto v : p[1]) std::fprintf(fo, " %d", int(v));
                 std::fputc('\n', fo);
             }
             if (std::fclose(fo) != 0) return 2;
@@ -499,6 +525,10 @@ int main(int argc, char **argv) {
                     ok = ok && sum * fact == result;
                     how = "three-shard device recount (graph beyond the host-recount limit)";
                 }
+            } else if (args.kernel == "kcstar") {  // the number of pairs is C_k: the count kernels, a different formulation
+                uint64_t stars = 0;
+                ok = gmsx_kclique_star_count(g.device(), args.clique_size, &stars, nullptr, nullptr) == GMSX_OK && stars == result;
+                how = "k-clique count kernels (gmsx_kclique_star_count)";
             } else {
                 if (m <= kHostBkEdges) {  // maximal_clique_enum/verifier.h:41-49: recount with Tomita on the host
                     ok = host_bk(hg, order) == result;

@@ -774,6 +774,8 @@ Option g_options[] = {
     {"BK_TINY_BESIDE", "", false},
     // Bron–Kerbosch listing (bk_list.hip)
     {"BK_LIST_ARENA_MB", "", false},
+    // k-clique-star listing (kcstar_list.hip)
+    {"KCSTAR_SLAB_MB", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

@@ -138,7 +138,8 @@ int gmsx_set_host_threads(int n);
  *   Bron–Kerbosch   BK_MAXC (widest start vertex of the register-resident search), BK_ARENA_MB, BK_BUDGET / BK_BUDGET0 (nodes before a
  *                   search is re-split), BK_GROUPS, BK_SMALL_P, BK_SMALL_P_GROUPS, BK_RESUME_GRAB, BK_SPLIT_BUILD, BK_TINY_ROOTS,
  *                   BK_TINY_BESIDE (kernel variants)
- *   Bron–Kerbosch listing  BK_LIST_ARENA_MB (budget of the search slabs of one launch: smaller = more launches) */
+ *   Bron–Kerbosch listing  BK_LIST_ARENA_MB (budget of the search slabs of one launch: smaller = more launches)
+ *   k-clique-star listing  KCSTAR_SLAB_MB (budget of the level-set slabs of one launch: smaller = more launches) */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -303,8 +304,47 @@ int gmsx_kclique_partial(const gmsx_graph *g, int k, int part, int nparts, uint6
  * *stars = the number of (clique, star) pairs = C_k — what the reference prints as "total k-cliques" and what `output.size()` is;
  * *star_members = the total cardinality of the stars = (k+1)·C_{k+1}: every (k+1)-clique puts each of its members into the star of the
  * k-clique of the others (may be NULL: the (k+1)-clique pass is then skipped).  Both from the k-clique kernels above; the listing itself
- * is not produced on the device.  k = 1 … 63. */
+ * is gmsx_kclique_star_list below.  k = 1 … 63. */
 int gmsx_kclique_star_count(const gmsx_graph *g, int k, uint64_t *stars, uint64_t *star_members, gmsx_stats *stats);
+
+/* ---- k-clique-star LISTING: KCliqueStar::Par::CliqueStarList (k_clique_star_list/parallel/recursive.h:37-43 over sequential/recursive.h:31-71).
+ * One (clique, star) pair per k-clique of the graph: the k members, and the star — every vertex outside the clique that is adjacent to all
+ * k members in the full undirected graph.  k = 1 gives (v, N(v)) for every vertex, isolated ones included (an empty star).  The sum of the
+ * star sizes is (k+1)·C_(k+1), what gmsx_kclique_star_count reports.  With GMSX_KCSTAR_CLIQUES_ONLY the stars are not computed: k-clique
+ * listing (k = 3: triangle listing); the star pointers must then be NULL (else GMSX_ERR_INVALID) and info->star_members = max_star = 0.
+ * k = 1 … 63; k < 1 → GMSX_ERR_INVALID, k > 63 → GMSX_ERR_UNSUPPORTED.
+ * All ids are vertex ids of the uploaded CSR.  Row i of `cliques` (k ids) is clique i, strictly ascending; star i is
+ * star_members[star_offsets[i] .. star_offsets[i+1]), strictly ascending, star_offsets[0] = 0.
+ * Two calls:
+ *   sizing  all three arrays NULL: only *info is filled (info is required on every call);
+ *   fill    cliques_capacity >= info.cliques (in cliques) and star_capacity >= info.star_members (in ids; star_members may be NULL if that
+ *           is 0), else GMSX_ERR_INVALID with *info holding the required sizes and no buffer written.
+ * A fill call that follows the sizing call of the same handle, k, flags and shard re-uses its first pass (one search instead of two).
+ * Order: the PIVOT of a clique is its member that comes last in the device's degree order (decreasing (degree, id)).  The pairs of one
+ * pivot are contiguous, pivots in that degree order; inside a pivot by the member chosen first — the pivot's neighbours that come before it
+ * in the degree order, in ascending vertex id — then depth-first, every further member chosen in ascending vertex id among the common
+ * neighbours that come before the member chosen last.  The same graph, upload flags, k, flags, part and nparts give byte-identical
+ * arrays, in every process.
+ * Shards: a shard is a set of whole pivots.  Pivot v belongs to part shard_of(p) where p is v's position in that degree order and
+ * shard_of(p) = p mod nparts on even stripes p / nparts, nparts - 1 - (p mod nparts) on odd ones (the rule of gmsx_bk_list).  The parts of
+ * one nparts are disjoint and their union is the whole list; (0, 1) is the whole graph; other (part, nparts) → GMSX_ERR_INVALID.
+ * Width: every level set of a search is a list in a global slab, so no request is refused for the width of a neighbourhood.  The output of
+ * a call is assembled on the device first: one that does not fit there returns GMSX_ERR_DEVICE_MEM and the caller uses more shards.  Test
+ * hook: option KCSTAR_SLAB_MB.  Errors inside a pass (a slab or output bound, a fill that disagrees with its sizing pass) are reported as
+ * GMSX_ERR_KERNEL; nothing is written out of bounds.
+ * gmsx_stats: kernel_ms (the search passes), setup_ms (building the task list on the host), launches, units = tasks (pivot, first member). */
+enum { GMSX_KCSTAR_DEFAULT = 0, GMSX_KCSTAR_CLIQUES_ONLY = 1 };
+typedef struct {
+    int64_t cliques;       /* k-cliques of this shard = (clique, star) pairs */
+    int64_t star_members;  /* sum of the star sizes; 0 with CLIQUES_ONLY */
+    int32_t k;
+    int32_t max_star;      /* largest star listed; 0 with CLIQUES_ONLY */
+} gmsx_kclique_star_list_info;
+int gmsx_kclique_star_list(const gmsx_graph *g, int k, uint32_t flags, int part, int nparts,
+                           int32_t *cliques /* k * info->cliques ids, row i = clique i, host, or NULL */,
+                           int64_t *star_offsets /* info->cliques + 1, host, or NULL */, int32_t *star_members /* info->star_members, host, or NULL */,
+                           int64_t cliques_capacity /* in cliques */, int64_t star_capacity /* in ids */,
+                           gmsx_kclique_star_list_info *info /* required */, gmsx_stats *stats);
 
 /* ---- Bron–Kerbosch maximal-clique count: BkEppsteinPar::mceBench with -DBK_COUNT
  * (maximal_clique_enum/parallel/eppsteinPAR.h:18-53 over sequential/tomita.h:12-86).

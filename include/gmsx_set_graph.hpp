@@ -19,6 +19,7 @@
 //   gmsx::vertex_count2(g, out)          -> gmsx_tc_vertex_count2  (triangle_count/parallel/vertex.h:14-49)
 //   gmsx::clique_count(g, k)             -> gmsx_kclique_count     (k_clique_count_set_based.h:19-31)
 //   gmsx::clique_star_count(g, k)        -> gmsx_kclique_star_count (k_clique_star_list/parallel/recursive.h:19-35, count mode)
+//   gmsx::clique_stars(g, k) / cliques(g, k) -> gmsx_kclique_star_list (k_clique_star_list/parallel/recursive.h:37-43: the pairs themselves)
 //   gmsx::maximal_clique_count(g, rank)  -> gmsx_bk_count          (maximal_clique_enum/parallel/eppsteinPAR.h:18-53)
 //   gmsx::adg_rank(g, eps, out)          -> gmsx_adg_rank          (preprocessing/parallel/degeneracy_approx_set.h:14-86)
 //   gmsx::triangle_count_ordering(g,out) -> gmsx_tc_ordering       (preprocessing/parallel/triangle_count.h:11-30)
@@ -27,6 +28,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -486,7 +488,7 @@ inline size_t clique_count(const HipGraphT<S> &g, size_t k = 4) {
 }
 // KCliqueStar::Par::CliqueStar<SGraph, OutputMode::Count> (k_clique_star_list/parallel/recursive.h:19-35): the number of k-clique-stars —
 // what `output.size()` is in count mode — printed like the reference does (:33); *star_members (optional) = the total size of the stars a
-// listing would carry.  The listing itself (`CliqueStarList`) stays on the host: the generic template runs over the span sets.
+// listing would carry.  The listing itself (`CliqueStarList`) is gmsx::clique_stars below.
 template <class S>
 inline int64_t clique_star_count(const HipGraphT<S> &g, int32_t k, uint64_t *star_members = nullptr) {
     uint64_t stars = 0;
@@ -577,6 +579,45 @@ inline std::vector<S> maximal_cliques(const HipGraphT<S> &g, const Ranking &rank
         for (int64_t i = 0; i < g.num_nodes(); ++i) tmp[size_t(i)] = int32_t(rank[size_t(i)]);
         return maximal_cliques_shard(g, tmp.get(), 0, 1);
     }
+}
+
+// KCliqueStar::Par::CliqueStarList (k_clique_star_list/parallel/recursive.h:37-43): one {clique, star} pair per k-clique, each an owning
+// set of the graph's own flavour — the shape of the reference's ListOutput<Set, List, 2>, a vector of std::array<Set, 2>.  One sizing call,
+// one fill (gmsx_kclique_star_list); the order of the pairs is deterministic (gmsx.h) where the reference's parallel one is not.
+template <class S>
+inline std::vector<std::array<S, 2>> clique_stars_shard(const HipGraphT<S> &g, int32_t k, int part, int nparts) {
+    gmsx_kclique_star_list_info info{};
+    detail::check(gmsx_kclique_star_list(g.device(), int(k), GMSX_KCSTAR_DEFAULT, part, nparts, nullptr, nullptr, nullptr, 0, 0, &info, nullptr),
+                  "gmsx_kclique_star_list");
+    std::vector<int32_t> cl(size_t(info.cliques) * size_t(k) + 1), ids(size_t(info.star_members) + 1);
+    std::vector<int64_t> off(size_t(info.cliques) + 1, 0);
+    detail::check(gmsx_kclique_star_list(g.device(), int(k), GMSX_KCSTAR_DEFAULT, part, nparts, cl.data(), off.data(), ids.data(), info.cliques,
+                                         info.star_members, &info, nullptr),
+                  "gmsx_kclique_star_list");
+    std::vector<std::array<S, 2>> out;
+    out.reserve(size_t(info.cliques));
+    for (int64_t i = 0; i < info.cliques; ++i)  // (owning copies)
+        out.push_back({S(cl.data() + size_t(i) * size_t(k), size_t(k)), S(ids.data() + off[size_t(i)], size_t(off[size_t(i) + 1] - off[size_t(i)]))});
+    return out;
+}
+template <class S>
+inline std::vector<std::array<S, 2>> clique_stars(const HipGraphT<S> &g, int32_t k) {
+    return clique_stars_shard(g, k, 0, 1);
+}
+// … with the stars switched off (GMSX_KCSTAR_CLIQUES_ONLY): the k-cliques themselves, members ascending; k = 3 lists the triangles
+template <class S>
+inline std::vector<S> cliques(const HipGraphT<S> &g, int32_t k, int part = 0, int nparts = 1) {
+    gmsx_kclique_star_list_info info{};
+    detail::check(gmsx_kclique_star_list(g.device(), int(k), GMSX_KCSTAR_CLIQUES_ONLY, part, nparts, nullptr, nullptr, nullptr, 0, 0, &info, nullptr),
+                  "gmsx_kclique_star_list");
+    std::vector<int32_t> cl(size_t(info.cliques) * size_t(k) + 1);
+    detail::check(gmsx_kclique_star_list(g.device(), int(k), GMSX_KCSTAR_CLIQUES_ONLY, part, nparts, cl.data(), nullptr, nullptr, info.cliques, 0,
+                                         &info, nullptr),
+                  "gmsx_kclique_star_list");
+    std::vector<S> out;
+    out.reserve(size_t(info.cliques));
+    for (int64_t i = 0; i < info.cliques; ++i) out.emplace_back(cl.data() + size_t(i) * size_t(k), size_t(k));
+    return out;
 }
 
 }  // namespace gmsx
