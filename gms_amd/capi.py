@@ -38,7 +38,7 @@ SYMBOLS = [
     "gmsx_graph_device_bytes", "gmsx_graph_max_out_degree",
     "gmsx_tc_total", "gmsx_tc_partial", "gmsx_tc_divisor", "gmsx_tc_stream_breakdown", "gmsx_tc_row_histogram", "gmsx_tc_comembership", "gmsx_tc_vertex_count2",
     "gmsx_intersect_count_batch", "gmsx_set_op_batch", "gmsx_vertex_similarity_batch", "gmsx_kclique_count", "gmsx_kclique_partial", "gmsx_kclique_star_count", "gmsx_kclique_star_list", "gmsx_bk_count", "gmsx_bk_partial", "gmsx_bk_list",
-    "gmsx_adg_rank", "gmsx_tc_ordering",
+    "gmsx_adg_rank", "gmsx_tc_ordering", "gmsx_core_decomposition", "gmsx_degree_rank", "gmsx_order_quality",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
 
@@ -68,6 +68,24 @@ class KcliqueStarListInfo(C.Structure):
 
 
 KCSTAR_DEFAULT, KCSTAR_CLIQUES_ONLY = 0, 1
+
+
+class CoreInfo(C.Structure):
+    _fields_ = [("degeneracy", C.c_int32), ("levels", C.c_int32), ("rounds", C.c_int32), ("reserved", C.c_int32), ("top_core", C.c_int64)]
+
+    def as_dict(self):
+        return {"degeneracy": int(self.degeneracy), "levels": int(self.levels), "rounds": int(self.rounds), "top_core": int(self.top_core)}
+
+
+class OrderQualityInfo(C.Structure):
+    _fields_ = [("max_later", C.c_int32), ("core_number", C.c_int32), ("core_number_of_order", C.c_int32), ("reserved", C.c_int32),
+                ("faulty", C.c_int64), ("excess", C.c_int64), ("relative_error", C.c_double), ("fault_rate", C.c_double),
+                ("relative_mean_difference", C.c_double)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("max_later", "core_number", "core_number_of_order", "faulty", "excess")}
+        d.update({k: float(getattr(self, k)) for k in ("relative_error", "fault_rate", "relative_mean_difference")})
+        return d
 
 
 class GmsxError(RuntimeError):
@@ -149,6 +167,9 @@ def lib():
     L.gmsx_bk_list.argtypes = [vp, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(BkListInfo), sp]
     L.gmsx_adg_rank.argtypes = [vp, C.c_double, C.c_int, _i32p, C.POINTER(C.c_int32), sp]
     L.gmsx_tc_ordering.argtypes = [vp, _i32p, sp]
+    L.gmsx_core_decomposition.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CoreInfo), sp]
+    L.gmsx_degree_rank.argtypes = [vp, C.c_int, _i32p, sp]
+    L.gmsx_order_quality.argtypes = [vp, C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.POINTER(OrderQualityInfo), sp]
     L.gmsx_comm_unique_id.argtypes = [C.c_char_p]
     L.gmsx_comm_init.argtypes = [C.c_int, C.c_int, C.c_char_p, vpp]
     L.gmsx_comm_allreduce_u64.argtypes = [vp, u64p]
@@ -551,6 +572,41 @@ class DeviceGraph:
         _check(lib().gmsx_tc_ordering(self._h, out, C.byref(st)), "gmsx_tc_ordering")
         out = out[:self.num_nodes]
         return (out, st.as_dict()) if stats else out
+
+    def core_decomposition(self, order=True, rank_format=True, stats=False):
+        """gmsx_core_decomposition: (core numbers int32[n], exact degeneracy order as rank or order vector — None with order=False —,
+        {degeneracy, levels, rounds, top_core})."""
+        n = self.num_nodes
+        core, info, st = np.zeros(max(n, 1), dtype=np.int32), CoreInfo(), Stats()
+        ordv = np.zeros(max(n, 1), dtype=np.int32) if order else None
+        _check(lib().gmsx_core_decomposition(self._h, core.ctypes.data_as(C.c_void_p), ordv.ctypes.data_as(C.c_void_p) if order else None,
+                                             int(bool(rank_format)), C.byref(info), C.byref(st)), "gmsx_core_decomposition")
+        r = (core[:n], ordv[:n] if order else None, info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def degree_rank(self, rank_format=True, stats=False):
+        """gmsx_degree_rank: the vertices by ascending (degree, id) as a rank or an order vector."""
+        out, st = np.zeros(max(self.num_nodes, 1), dtype=np.int32), Stats()
+        _check(lib().gmsx_degree_rank(self._h, int(bool(rank_format)), out, C.byref(st)), "gmsx_degree_rank")
+        out = out[:self.num_nodes]
+        return (out, st.as_dict()) if stats else out
+
+    def order_quality(self, ordering, rank_format=True, core_number=None, later=False, stats=False):
+        """gmsx_order_quality: the info dict of `ordering` graded against core_number (None: the exact degeneracy, computed on the device);
+        with later=True (info, later int32[n])."""
+        n = self.num_nodes
+        ordering = np.ascontiguousarray(ordering, dtype=np.int32)
+        if ordering.size != n:
+            raise GmsxError(ERR_INVALID, "gmsx_order_quality (ordering must have n entries)")
+        lat = np.zeros(max(n, 1), dtype=np.int32) if later else None
+        info, st = OrderQualityInfo(), Stats()
+        op = ordering.ctypes.data_as(C.c_void_p) if n else np.zeros(1, np.int32).ctypes.data_as(C.c_void_p)
+        _check(lib().gmsx_order_quality(self._h, op, int(bool(rank_format)), -1 if core_number is None else int(core_number),
+                                        lat.ctypes.data_as(C.c_void_p) if later else None, C.byref(info), C.byref(st)), "gmsx_order_quality")
+        r = (info.as_dict(), lat[:n]) if later else (info.as_dict(),)
+        if stats:
+            r = r + (st.as_dict(),)
+        return r if len(r) > 1 else r[0]
 
     def free(self):
         if getattr(self, "_h", None):

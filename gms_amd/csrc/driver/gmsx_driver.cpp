@@ -13,6 +13,8 @@
 //                    shard (gmsx_*_partial) and ONE u64 all-reduce over RCCL (gmsx_comm_allreduce_u64) replaces the OpenMP
 //                    reduction(+:total) of parallel/total.h:12.  --gpus 1 runs the same path with a 1-rank communicator.
 // Added:  bk --list FILE   the maximal cliques of the last trial (gmsx_bk_list, outside the timed trial), one per line, members ascending.
+// Added:  bk --order adg|deg|dgr   which preprocessor the timed "Preprocess Time" runs and hands its rank to the search: gmsx_adg_rank (default; BK-GMS-ADG),
+//                    gmsx_degree_rank (BK-GMS-DEG) or the exact degeneracy order of gmsx_core_decomposition (BK-GMS-DGR).  The count does not depend on it.
 // Added:  kcstar -p clique-size=k [--list FILE]   KCliqueStar::Par::CliqueStarList (k_clique_star_list/parallel/recursive.h:19-43) on the device: prints the
 //                    reference's "total k-cliques: N" line (:34, N = the number of pairs); --list writes the pairs of the last trial (gmsx_kclique_star_list, outside
 //                    the timed trial), one per line: "c1 … ck | s1 …", clique and star ascending.  Not sharded (--gpus > 1 is refused).
@@ -47,6 +49,7 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     int clique_size = 4;
     int gpus = 0;  // 0 = single process without a communicator
     std::string list;  // bk --list FILE: the maximal cliques of the last trial, one per line (gmsx_bk_list)
+    std::string order; // bk --order adg|deg|dgr: the preprocessing step in front of the search (default adg)
     int error = 0;
 };
 
@@ -73,6 +76,7 @@ Args parse(int argc, char **argv) {
         else if (f == "-g" || f == "--gen") { if (!need(2)) break; a.gen = argv[++i]; a.scale = std::atoi(argv[++i]); }
         else if (f == "--deg") { if (!need(1)) break; a.deg = std::atoi(argv[++i]); }
         else if (f == "--list") { if (!need(1)) break; a.list = argv[++i]; }
+        else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; if (a.order != "adg" && a.order != "deg" && a.order != "dgr") a.error = 100; }
         else if (f == "--gpus") { if (!need(1)) break; a.gpus = std::atoi(argv[++i]); if (a.gpus < 1 || a.gpus > 64) a.error = 100; }
         else if (f == "--opt") {  // --opt NAME=VALUE -> gmsx_set_option (limits, kernel variants, diagnostics: include/gmsx.h); unknown names are refused
             if (!need(1)) break;
@@ -94,12 +98,13 @@ Args parse(int argc, char **argv) {
     if (!a.error && !a.gen.empty() && a.gen != "kronecker" && a.gen != "uniform") a.error = 100;
     if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
     if (!a.error && a.kernel == "kcstar" && a.gpus > 1) a.error = 100;
+    if (!a.error && !a.order.empty() && a.kernel != "bk") a.error = 100;  // only Bron–Kerbosch has a preprocessing step
     return a;
 }
 
 void usage(const char *argv0) {
     std::printf("usage: %s <tc|vertex|kclique|kcstar|bk> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
-                "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE]\n", argv0);
+                "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -415,9 +420,12 @@ int main(int argc, char **argv) {
         std::vector<int64_t> counts;
         std::vector<int32_t> order;
         double pp_time = -1;
-        if (args.kernel == "bk") {  // BenchmarkKernelBkPP: preprocess(rgraph, order) per trial (common/benchmark.h:163-170), ADG eps 0.001
+        if (args.kernel == "bk") {  // BenchmarkKernelBkPP: preprocess(rgraph, order) per trial (common/benchmark.h:163-170)
             t.Start();
-            gmsx::adg_rank(g, 0.001, order, true);
+            // the three preprocessors of maximal_clique_enum_bron_kerbosch.cc:36-56: BK-GMS-ADG (eps 0.001), BK-GMS-DEG, BK-GMS-DGR
+            if (args.order == "deg") gmsx::degree_order(g, order, true);
+            else if (args.order == "dgr") gmsx::degeneracy_order(g, order, true);
+            else gmsx::adg_rank(g, 0.001, order, true);
             t.Stop();
             pp_time = t.Seconds();
             PrintTime("Preprocess Time", pp_time);

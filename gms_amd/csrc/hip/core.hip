@@ -1,0 +1,676 @@
+// Exact k-core decomposition, the degree order and the quality of an order, on gfx950:
+//   gmsx_core_decomposition  the exact counterpart of PpSequential::getDegeneracyOrderingMatula (preprocessing/sequential/degeneracy_matula.h:13-66;
+//                            PpParallel's is the same serial loop behind a parallel degree pass) — BK-GMS-DGR of the Bron–Kerbosch driver
+//                            (maximal_clique_enum_bron_kerbosch.cc:50-56)
+//   gmsx_degree_rank         PpParallel::getDegreeOrdering (preprocessing/parallel/degree.h:15-61) — BK-GMS-DEG (:43-49)
+//   gmsx_order_quality       CoreNumberEvaluator::getCoreNumberOfOrder / evaluateCoreNrAccuracy (preprocessing/util/core_number_evaluator.h:73-139)
+//
+// THE PEEL.  Matula's loop removes ONE vertex per step — the minimum of (remaining degree, id) — and is serial by construction.  The core
+// numbers it implies (the running maximum of the removal degrees) do not depend on that sequence, and the level-synchronous peel yields them
+// in a few hundred rounds: k := the smallest remaining degree; then rounds until none applies — in a round every remaining vertex of
+// remaining degree <= k leaves at once (core number k, round = the running round index) and PUSHes a decrement to each neighbour, as
+// k_adg_push does: every CSR entry is touched once over the whole run.  deg[] alone carries the membership: deg[w] <= k <=> w has left, is
+// leaving or is queued for the next round, and the ONE decrement that takes deg[w] from k+1 to k (atomicSub returns k+1) queues w.  Which
+// vertices a round removes is a fact about the integers, not about the arrival order of the atomics; the order inside the queues is not, and
+// never reaches an output: the result is sorted by (round, id) at the end.
+//
+// COST SHAPE.  Hundreds of rounds, almost all of a handful of vertices: the fixed cost per round decides.  A round boundary is a kernel
+// boundary (k_core_round + k_core_round_long + k_core_advance, then the host reads 48 bytes) or — while the frontier holds at most
+// CORE_WG_FRONTIER vertices with at most kWgWorkMax CSR entries between them and no row above kWgRowMax — a __syncthreads() of k_core_tail, ONE workgroup that runs round after round until
+// the frontier empties (the level is done: the next k needs a sweep over all vertices) or outgrows the threshold.  No workgroup ever waits
+// for another one.  Rows are binned by length: a 16-lane group per vertex up to kLongRow entries, longer rows by all workgroups of
+// k_core_round_long (all threads of the workgroup in k_core_tail) together — no lane walks a long row alone.
+#include "device_graph.hpp"
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <vector>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+namespace gmsx {
+
+namespace {
+
+struct Dev {
+    void *p = nullptr;
+    ~Dev() { (void)hipFree(p); }
+    template <class T> T *as() { return static_cast<T *>(p); }
+};
+template <class T>
+int dalloc(Dev &d, int64_t count) {
+    if (hipMalloc(&d.p, size_t(std::max<int64_t>(count, 1)) * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        d.p = nullptr;
+        return GMSX_ERR_DEVICE_MEM;
+    }
+    return GMSX_OK;
+}
+
+// UNMEASURED: none of these bounds has a timing behind it yet (tools/core_probe.py is the measurement).  They follow the round
+// table of the peel on R-MAT graphs (almost every round removes fewer than 256 vertices) and the row shapes named there.
+constexpr int kGroup = 16;          // lanes per frontier vertex of a short row
+constexpr int kLongRow = 1024;      // longer rows are walked by many waves together
+constexpr int kWgRowMax = 32768;    // k_core_tail hands a frontier with a longer row back to the grid-wide kernels
+constexpr int kTailThreads = 1024;
+constexpr int kTailLong = 256;      // long rows one round of k_core_tail can park for its whole-workgroup phase; more: the round goes back to the grid
+constexpr int kWgWorkMax = 1 << 18; // CSR entries one round of k_core_tail may walk (256 per thread); more: the round goes back to the grid
+constexpr long long kWgFrontierDefault = 512;
+
+// control block of one peel (device, mirrored to the host after every step)
+struct CoreCtrl {
+    int32_t count;      // vertices in the current frontier
+    int32_t next;       // appended to the next one so far
+    int32_t round;      // index of the round the current frontier leaves in
+    int32_t k;          // current level
+    int32_t removed;    // vertices that have left in finished rounds
+    int32_t error;      // an append hit its bound
+    int32_t nlong;      // long rows parked by k_core_round for k_core_round_long
+    int32_t bail;       // k_core_tail met a round too heavy for one workgroup (row length, long rows, total entries): it belongs to the grid-wide kernels
+    int32_t min_deg;    // level sweep: smallest remaining degree
+    int32_t cur;        // which of the two frontier buffers is the current one
+    int32_t pad[2];
+};
+
+__device__ __forceinline__ int32_t load_now(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ void k_core_init(int64_t n, const int64_t *__restrict__ off, int32_t *__restrict__ deg, int32_t *__restrict__ round_of) {
+    const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (v < n) {
+        deg[v] = int32_t(off[v + 1] - off[v]);
+        round_of[v] = -1;
+    }
+}
+
+// level sweep, first half: ctrl->min_deg = min deg over the remaining vertices (deg > the level just finished)
+__global__ __launch_bounds__(256) void k_core_min(int64_t n, const int32_t *__restrict__ deg, int32_t k_done, CoreCtrl *__restrict__ ctrl) {
+    int32_t m = INT_MAX;
+    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < n; v += int64_t(gridDim.x) * blockDim.x) {
+        const int32_t d = deg[v];
+        if (d > k_done) m = min(m, d);
+    }
+    for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_down(m, o));
+    if ((threadIdx.x & 63) == 0 && m != INT_MAX) atomicMin(&ctrl->min_deg, m);
+}
+
+// … second half: the remaining vertices of that degree are the level's first frontier (one wave-aggregated append per wave)
+__global__ __launch_bounds__(256) void k_core_select(int64_t n, const int32_t *__restrict__ deg, int32_t k_done, CoreCtrl *__restrict__ ctrl,
+                                                     int32_t *__restrict__ frontier) {
+    const int lane = threadIdx.x & 63;
+    const int32_t k = ctrl->min_deg;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->k = k;  // (the others read min_deg, not k)
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    const int64_t end = ((n + 63) / 64) * 64;  // whole waves stay converged for the ballot
+    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride) {
+        bool take = false;
+        if (v < n) {
+            const int32_t d = deg[v];
+            take = d > k_done && d <= k;
+        }
+        const unsigned long long m = __ballot(take);
+        if (m == 0) continue;
+        int32_t base = 0;
+        if (lane == 0) base = atomicAdd(&ctrl->count, int32_t(__popcll(m)));
+        base = __shfl(base, 0);
+        if (take) {
+            const int64_t pos = int64_t(base) + __popcll(m & ((1ull << lane) - 1ull));
+            if (pos < n) frontier[pos] = int32_t(v);
+            else ctrl->error = 1;
+        }
+    }
+}
+
+// the PUSH of one frontier vertex's row part [j0, j1) by W lanes: a neighbour still above k loses one; the decrement that brings it to k queues it
+template <class Counter>
+__device__ __forceinline__ void core_walk(int64_t j0, int64_t j1, int64_t lane, int64_t width, int32_t k, const int32_t *__restrict__ adj,
+                                          int32_t *__restrict__ deg, int32_t *__restrict__ next, Counter *next_count, int64_t cap, int32_t *error) {
+    for (int64_t j = j0 + lane; j < j1; j += width) {
+        const int32_t w = adj[j];
+        if (load_now(&deg[w]) <= k) continue;  // has left, is leaving or is queued (deg only ever falls: a stale value costs an atomic, never the result)
+        if (atomicSub(&deg[w], 1) == k + 1) {
+            const int64_t pos = int64_t(atomicAdd(next_count, 1));
+            if (pos < cap) next[pos] = w;
+            else *error = 1;
+        }
+    }
+}
+
+// one round, grid-wide: a 16-lane group per frontier vertex; rows above kLongRow are parked for k_core_round_long
+__global__ __launch_bounds__(256) void k_core_round(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                    int32_t *__restrict__ deg, int32_t *__restrict__ round_of, int32_t *__restrict__ core,
+                                                    const int32_t *__restrict__ cur, int32_t *__restrict__ next, int32_t *__restrict__ longs,
+                                                    int64_t long_cap, CoreCtrl *__restrict__ ctrl) {
+    const int lane = threadIdx.x & (kGroup - 1);
+    const int64_t group0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / kGroup;
+    const int64_t groups = (int64_t(gridDim.x) * blockDim.x) / kGroup;
+    const int32_t count = ctrl->count, k = ctrl->k, round = ctrl->round;
+    for (int64_t i = group0; i < count; i += groups) {
+        const int32_t x = cur[i];
+        const int64_t j0 = off[x], j1 = off[x + 1];
+        if (lane == 0) {
+            round_of[x] = round;
+            core[x] = k;
+        }
+        if (j1 - j0 > kLongRow) {
+            if (lane == 0) {
+                const int64_t pos = int64_t(atomicAdd(&ctrl->nlong, 1));
+                if (pos < long_cap) longs[pos] = x;
+                else ctrl->error = 1;
+            }
+            continue;
+        }
+        core_walk(j0, j1, lane, kGroup, k, adj, deg, next, &ctrl->next, n, &ctrl->error);
+    }
+}
+
+// … its long rows: all workgroups walk each of them together
+__global__ __launch_bounds__(256) void k_core_round_long(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                         int32_t *__restrict__ deg, int32_t *__restrict__ next, const int32_t *__restrict__ longs,
+                                                         int64_t long_cap, CoreCtrl *__restrict__ ctrl) {
+    const int64_t nlong = min(int64_t(ctrl->nlong), long_cap);
+    const int32_t k = ctrl->k;
+    const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, threads = int64_t(gridDim.x) * blockDim.x;
+    for (int64_t i = 0; i < nlong; ++i) {
+        const int32_t x = longs[i];
+        core_walk(off[x], off[x + 1], tid, threads, k, adj, deg, next, &ctrl->next, n, &ctrl->error);
+    }
+}
+
+// … and the round boundary: the next frontier becomes the current one
+__global__ void k_core_advance(CoreCtrl *__restrict__ ctrl) {
+    ctrl->removed += ctrl->count;
+    ctrl->count = ctrl->next;
+    ctrl->next = 0;
+    ctrl->nlong = 0;
+    ctrl->round += 1;
+    ctrl->cur ^= 1;
+}
+
+// rounds inside ONE workgroup: the round boundary is a __syncthreads().  Runs while 0 < frontier <= wg_frontier; returns with the control
+// block describing the state it stopped in (frontier empty: level done; larger than wg_frontier, or ctrl->bail — a round too heavy for one workgroup —: the grid-wide kernels go on).
+// The two frontier buffers stay in global memory (they are bounds-checked against n there and may be handed back at any round), read with
+// loads that bypass the vector cache; the counters live in LDS.
+__global__ __launch_bounds__(kTailThreads) void k_core_tail(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                            int32_t *__restrict__ deg, int32_t *__restrict__ round_of, int32_t *__restrict__ core,
+                                                            int32_t *__restrict__ f0, int32_t *__restrict__ f1, int32_t wg_frontier,
+                                                            CoreCtrl *__restrict__ ctrl) {
+    __shared__ int32_t s_count, s_next, s_error, s_flag, s_nlong, s_nlong_seen;
+    __shared__ unsigned long long s_work;
+    __shared__ int32_t s_long[kTailLong];
+    const int tid = threadIdx.x, lane = tid & (kGroup - 1), group = tid / kGroup;
+    constexpr int groups = kTailThreads / kGroup;
+    const int32_t k = ctrl->k;
+    int32_t round = ctrl->round, removed = ctrl->removed, curi = ctrl->cur, bail = 0;
+    if (tid == 0) {
+        s_count = ctrl->count;
+        s_next = 0;
+        s_error = 0;
+        s_flag = 0;
+        s_nlong = 0;
+        s_nlong_seen = 0;
+        s_work = 0;
+    }
+    __syncthreads();
+    for (;;) {
+        const int32_t count = s_count;
+        if (count == 0 || count > wg_frontier) break;
+        const int32_t *cur = curi ? f1 : f0;
+        int32_t *next = curi ? f0 : f1;
+        // what the round would cost here: one workgroup takes it only if no row is above kWgRowMax, its long rows fit the list and all its
+        // rows together hold at most kWgWorkMax entries — else every other CU would idle behind this one
+        unsigned long long work = 0;
+        int32_t nl = 0;
+        for (int32_t i = tid; i < count; i += kTailThreads) {
+            const int32_t x = load_now(&cur[i]);
+            const int64_t len = off[x + 1] - off[x];
+            if (len > kWgRowMax) s_flag = 1;
+            if (len > kLongRow) ++nl;
+            work += (unsigned long long)len;
+        }
+        if (work) atomicAdd(&s_work, work);
+        if (nl) atomicAdd(&s_nlong_seen, nl);
+        __syncthreads();
+        if (s_flag || s_nlong_seen > kTailLong || s_work > (unsigned long long)kWgWorkMax) {
+            bail = 1;
+            break;
+        }
+        for (int32_t i = group; i < count; i += groups) {
+            const int32_t x = load_now(&cur[i]);
+            const int64_t j0 = off[x], j1 = off[x + 1];
+            if (lane == 0) {
+                round_of[x] = round;
+                core[x] = k;
+            }
+            if (j1 - j0 > kLongRow) {
+                if (lane == 0) {  // at most kTailLong of them: checked above
+                    const int32_t pos = atomicAdd(&s_nlong, 1);
+                    if (pos < kTailLong) s_long[pos] = x;
+                    else s_error = 1;
+                }
+                continue;
+            }
+            core_walk(j0, j1, lane, kGroup, k, adj, deg, next, &s_next, n, &s_error);
+        }
+        __syncthreads();
+        const int32_t nlong = min(s_nlong, kTailLong);
+        for (int32_t i = 0; i < nlong; ++i) {
+            const int32_t x = s_long[i];
+            core_walk(off[x], off[x + 1], tid, kTailThreads, k, adj, deg, next, &s_next, n, &s_error);
+        }
+        __syncthreads();
+        removed += count;
+        round += 1;
+        curi ^= 1;
+        if (tid == 0) {
+            s_count = s_error ? 0 : min(s_next, int32_t(min(n, int64_t(INT_MAX))));
+            s_next = 0;
+            s_nlong = 0;
+            s_nlong_seen = 0;
+            s_work = 0;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        ctrl->count = s_count;
+        ctrl->next = 0;
+        ctrl->nlong = 0;
+        ctrl->round = round;
+        ctrl->removed = removed;
+        ctrl->cur = curi;
+        ctrl->bail = bail;
+        if (s_error) ctrl->error = 1;
+    }
+}
+
+__global__ void k_core_keys(int64_t n, const int32_t *__restrict__ hi, unsigned long long *__restrict__ keys) {
+    const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (v < n) keys[v] = ((unsigned long long)uint32_t(hi[v]) << 32) | (unsigned long long)uint32_t(v);
+}
+__global__ void k_degree_keys(int64_t n, const int64_t *__restrict__ off, unsigned long long *__restrict__ keys) {
+    const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (v < n) keys[v] = ((unsigned long long)uint32_t(off[v + 1] - off[v]) << 32) | (unsigned long long)uint32_t(v);
+}
+__global__ void k_core_emit(int64_t n, const unsigned long long *__restrict__ sorted, int rank_format, int32_t *__restrict__ out) {
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const int32_t v = int32_t(uint32_t(sorted[i] & 0xffffffffull));
+        if (rank_format) out[v] = int32_t(i);
+        else out[i] = v;
+    }
+}
+
+int bits_for(uint64_t max_value) {
+    int b = 1;
+    while (b < 32 && (max_value >> b) != 0) ++b;
+    return b;
+}
+
+// sorts n keys (hi << 32 | id) whose high halves are <= max_hi and writes the rank or order vector they imply into d_out
+int sort_and_emit(int64_t n, Dev &d_keys, uint64_t max_hi, int rank_format, int32_t *d_out, hipStream_t s, int *launches) {
+    Dev d_sorted, d_tmp;
+    if (int rc = dalloc<unsigned long long>(d_sorted, n)) return rc;
+    const unsigned end_bit = 32u + unsigned(bits_for(max_hi));
+    size_t tmp_bytes = 0;
+    GMSX_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_keys.as<unsigned long long>(), d_sorted.as<unsigned long long>(), size_t(n), 0, end_bit, s));
+    if (int rc = dalloc<char>(d_tmp, int64_t(tmp_bytes))) return rc;
+    GMSX_HIP(rocprim::radix_sort_keys(d_tmp.p, tmp_bytes, d_keys.as<unsigned long long>(), d_sorted.as<unsigned long long>(), size_t(n), 0, end_bit, s));
+    hipLaunchKernelGGL(k_core_emit, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, n, d_sorted.as<unsigned long long>(), rank_format, d_out);
+    GMSX_HIP(hipStreamSynchronize(s));  // d_sorted / d_tmp are freed on return
+    *launches += 2;
+    return GMSX_OK;
+}
+
+// The peel.  On success d_core / d_round (n each, device) hold the core number and the round of every vertex.
+int core_peel(const gmsx_graph *g, Dev &d_core, Dev &d_round, gmsx_core_info *info, int *launches_out) {
+    Ctx &c = ctx();
+    hipStream_t s = c.stream;
+    const int64_t n = g->n;
+    const int64_t long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
+    Dev d_deg, d_f0, d_f1, d_long, d_ctrl;
+    if (int rc = dalloc<int32_t>(d_deg, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_core, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_round, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_f0, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_f1, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_long, long_cap)) return rc;
+    if (int rc = dalloc<CoreCtrl>(d_ctrl, 1)) return rc;
+    CoreCtrl *ctrl = d_ctrl.as<CoreCtrl>();
+    int32_t *deg = d_deg.as<int32_t>(), *core = d_core.as<int32_t>(), *round_of = d_round.as<int32_t>();
+    int32_t *f[2] = {d_f0.as<int32_t>(), d_f1.as<int32_t>()};
+    long long wg_frontier = opt_int("CORE_WG_FRONTIER", kWgFrontierDefault);  // test hook: 0 = every round a kernel boundary, large = every round it may take in k_core_tail
+    wg_frontier = std::max<long long>(0, std::min<long long>(wg_frontier, INT_MAX));
+
+    const int cus = c.compute_units > 0 ? c.compute_units : 256;
+    const unsigned tb = unsigned((n + 255) / 256);
+    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    const unsigned long_grid = unsigned(cus) * 4;
+    int launches = 1;
+    hipLaunchKernelGGL(k_core_init, dim3(tb), dim3(256), 0, s, n, g->off, deg, round_of);
+    CoreCtrl h;
+    std::memset(&h, 0, sizeof h);
+    GMSX_HIP(hipMemsetAsync(ctrl, 0, sizeof(CoreCtrl), s));
+    int32_t k_done = -1, levels = 0;
+    int64_t top_core = 0;
+    while (h.removed < n) {
+        // ---- the next level: k = smallest remaining degree, first frontier = the vertices that have it
+        GMSX_HIP(hipMemsetAsync(&ctrl->min_deg, 0x7f, sizeof(int32_t), s));
+        hipLaunchKernelGGL(k_core_min, dim3(sweep), dim3(256), 0, s, n, deg, k_done, ctrl);
+        hipLaunchKernelGGL(k_core_select, dim3(sweep), dim3(256), 0, s, n, deg, k_done, ctrl, f[h.cur]);
+        launches += 2;
+        GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        if (h.error || h.count <= 0 || h.count > n - h.removed || h.min_deg <= k_done || h.k != h.min_deg) return GMSX_ERR_KERNEL;
+        const int64_t removed_before = h.removed;
+        // ---- rounds of this level
+        while (h.count > 0) {
+            if (h.count <= wg_frontier && !h.bail) {
+                hipLaunchKernelGGL(k_core_tail, dim3(1), dim3(kTailThreads), 0, s, n, g->off, g->adj, deg, round_of, core, f[0], f[1],
+                                   int32_t(wg_frontier), ctrl);
+                launches += 1;
+            } else {
+                const unsigned rb = unsigned(std::min<int64_t>((int64_t(h.count) * kGroup + 255) / 256, int64_t(cus) * 32));
+                hipLaunchKernelGGL(k_core_round, dim3(rb), dim3(256), 0, s, n, g->off, g->adj, deg, round_of, core, f[h.cur], f[h.cur ^ 1],
+                                   d_long.as<int32_t>(), long_cap, ctrl);
+                hipLaunchKernelGGL(k_core_round_long, dim3(long_grid), dim3(256), 0, s, n, g->off, g->adj, deg, f[h.cur ^ 1], d_long.as<int32_t>(),
+                                   long_cap, ctrl);
+                hipLaunchKernelGGL(k_core_advance, dim3(1), dim3(1), 0, s, ctrl);
+                launches += 3;
+                if (h.bail) {
+                    h.bail = 0;
+                    GMSX_HIP(hipMemsetAsync(&ctrl->bail, 0, sizeof(int32_t), s));
+                }
+            }
+            const int32_t removed_was = h.removed, round_was = h.round;
+            GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
+            GMSX_HIP(hipStreamSynchronize(s));
+            if (h.error || h.count < 0 || h.removed > n || h.count > n - h.removed) return GMSX_ERR_KERNEL;
+            if (!h.bail && (h.removed <= removed_was || h.round <= round_was)) return GMSX_ERR_KERNEL;  // a step that made no progress
+        }
+        top_core = h.removed - removed_before;
+        k_done = h.k;
+        ++levels;
+    }
+    GMSX_HIP(hipGetLastError());
+    if (h.removed != n) return GMSX_ERR_KERNEL;
+    info->degeneracy = k_done;
+    info->levels = levels;
+    info->rounds = h.round;
+    info->reserved = 0;
+    info->top_core = top_core;
+    *launches_out = launches;
+    return GMSX_OK;
+}
+
+// ---- order quality ------------------------------------------------------------------------------------------------------------------
+
+// ordering -> rank[] (device) + validation: every entry in [0, n) and hit once
+__global__ void k_oq_rank(int64_t n, const int32_t *__restrict__ ordering, int rank_format, int32_t *__restrict__ rank, int32_t *__restrict__ seen,
+                          int32_t *__restrict__ bad) {
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t x = ordering[i];
+    if (x < 0 || int64_t(x) >= n) {
+        *bad = 1;
+        return;
+    }
+    if (atomicAdd(&seen[x], 1) != 0) *bad = 1;
+    if (!rank_format) rank[x] = int32_t(i);  // ordering[i] = i-th vertex
+}
+
+// later[v] = |{ w in N(v) : rank[w] > rank[v] }|: a 16-lane group per vertex, rows above kLongRow parked for k_oq_later_long
+__global__ __launch_bounds__(256) void k_oq_later(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                  const int32_t *__restrict__ rank, int32_t *__restrict__ later, int32_t *__restrict__ longs,
+                                                  int64_t long_cap, int32_t *__restrict__ ctl /* [0] long rows, [1] error */) {
+    const int lane = threadIdx.x & (kGroup - 1);
+    const int64_t group0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / kGroup;
+    const int64_t groups = (int64_t(gridDim.x) * blockDim.x) / kGroup;
+    const int64_t end = ((n + 3) / 4) * 4;  // the four groups of a wave stay together for the shuffles
+    for (int64_t v = group0; v < end; v += groups) {
+        int32_t cnt = 0;
+        if (v < n) {
+            const int64_t j0 = off[v], j1 = off[v + 1];
+            if (j1 - j0 > kLongRow) {
+                if (lane == 0) {
+                    later[v] = 0;
+                    const int64_t pos = int64_t(atomicAdd(&ctl[0], 1));
+                    if (pos < long_cap) longs[pos] = int32_t(v);
+                    else ctl[1] = 1;
+                }
+                cnt = -1;
+            } else {
+                const int32_t rv = rank[v];
+                for (int64_t j = j0 + lane; j < j1; j += kGroup) cnt += rank[adj[j]] > rv ? 1 : 0;
+            }
+        }
+        const bool parked = cnt < 0;
+        if (parked) cnt = 0;
+        for (int o = kGroup / 2; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, kGroup);
+        if (v < n && lane == 0 && !parked) later[v] = cnt;
+    }
+}
+__global__ __launch_bounds__(256) void k_oq_later_long(const int64_t *__restrict__ off, const int32_t *__restrict__ adj, const int32_t *__restrict__ rank,
+                                                       int32_t *__restrict__ later, const int32_t *__restrict__ longs, int64_t long_cap,
+                                                       const int32_t *__restrict__ ctl) {
+    const int64_t nlong = min(int64_t(ctl[0]), long_cap);
+    const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, threads = int64_t(gridDim.x) * blockDim.x;
+    for (int64_t i = 0; i < nlong; ++i) {
+        const int32_t v = longs[i];
+        const int32_t rv = rank[v];
+        const int64_t j0 = off[v], j1 = off[v + 1];
+        int32_t cnt = 0;
+        for (int64_t j = j0 + tid; j < j1; j += threads) cnt += rank[adj[j]] > rv ? 1 : 0;
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+        if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&later[v], cnt);
+    }
+}
+// acc[0] = max later, acc[1] = #(later > core_number), acc[2] = Σ (later - core_number) over those; core_number < 0: the maximum only
+__global__ __launch_bounds__(256) void k_oq_reduce(int64_t n, const int32_t *__restrict__ later, int32_t core_number, unsigned long long *__restrict__ acc) {
+    unsigned long long mx = 0, faulty = 0, excess = 0;
+    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < n; v += int64_t(gridDim.x) * blockDim.x) {
+        const int32_t l = later[v];
+        mx = max(mx, (unsigned long long)l);
+        if (core_number >= 0 && l > core_number) {
+            ++faulty;
+            excess += (unsigned long long)(l - core_number);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        mx = max(mx, (unsigned long long)__shfl_down((long long)mx, o));
+        faulty += __shfl_down(faulty, o);
+        excess += __shfl_down(excess, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (mx) atomicMax(&acc[0], mx);
+        if (faulty) atomicAdd(&acc[1], faulty);
+        if (excess) atomicAdd(&acc[2], excess);
+    }
+}
+
+}  // namespace
+}  // namespace gmsx
+
+using namespace gmsx;
+
+extern "C" {
+
+int gmsx_core_decomposition(const gmsx_graph *g, int32_t *core, int32_t *ordering, int rank_format, gmsx_core_info *info, gmsx_stats *stats) {
+    return gmsx::guard([&]() -> int {
+        if (!g || !info) return GMSX_ERR_INVALID;
+        if (int rc = ensure_init()) return rc;
+        Ctx &c = ctx();
+        hipStream_t s = c.stream;
+        const int64_t n = g->n;
+        gmsx_core_info res;
+        std::memset(&res, 0, sizeof res);
+        if (n == 0) {
+            *info = res;
+            if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0, 0};
+            return GMSX_OK;
+        }
+        Dev d_core, d_round, d_keys, d_out;
+        int launches = 0;
+        GMSX_HIP(hipEventRecord(c.ev[0], s));
+        if (int rc = core_peel(g, d_core, d_round, &res, &launches)) return rc;
+        if (ordering) {
+            if (int rc = dalloc<unsigned long long>(d_keys, n)) return rc;
+            if (int rc = dalloc<int32_t>(d_out, n)) return rc;
+            hipLaunchKernelGGL(k_core_keys, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, n, d_round.as<int32_t>(), d_keys.as<unsigned long long>());
+            launches += 1;
+            if (int rc = sort_and_emit(n, d_keys, uint64_t(res.rounds), rank_format ? 1 : 0, d_out.as<int32_t>(), s, &launches)) return rc;
+        }
+        GMSX_HIP(hipEventRecord(c.ev[1], s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        GMSX_HIP(hipGetLastError());
+        // the outputs are written only now, when nothing can fail but the copies themselves
+        std::vector<int32_t> h_core, h_ord;
+        if (core) {
+            h_core.resize(size_t(n));
+            GMSX_HIP(hipMemcpy(h_core.data(), d_core.p, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        if (ordering) {
+            h_ord.resize(size_t(n));
+            GMSX_HIP(hipMemcpy(h_ord.data(), d_out.p, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        float ms = 0.f;
+        GMSX_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+        if (core) std::memcpy(core, h_core.data(), size_t(n) * sizeof(int32_t));
+        if (ordering) std::memcpy(ordering, h_ord.data(), size_t(n) * sizeof(int32_t));
+        *info = res;
+        if (stats) *stats = gmsx_stats{double(ms), 0.0, uint64_t(n), 0, uint64_t(res.rounds), launches, 0, 0};
+        return GMSX_OK;
+    });
+}
+
+int gmsx_degree_rank(const gmsx_graph *g, int rank_format, int32_t *out, gmsx_stats *stats) {
+    return gmsx::guard([&]() -> int {
+        if (!g || !out) return GMSX_ERR_INVALID;
+        if (int rc = ensure_init()) return rc;
+        Ctx &c = ctx();
+        hipStream_t s = c.stream;
+        const int64_t n = g->n;
+        if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0, 0};
+        if (n == 0) return GMSX_OK;
+        Dev d_keys, d_out;
+        if (int rc = dalloc<unsigned long long>(d_keys, n)) return rc;
+        if (int rc = dalloc<int32_t>(d_out, n)) return rc;
+        int launches = 1;
+        GMSX_HIP(hipEventRecord(c.ev[0], s));
+        // compare_degree (degree.h:16-22): v before w iff (deg v, v) < (deg w, w) — a strict total order, so the sort has one result
+        hipLaunchKernelGGL(k_degree_keys, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, n, g->off, d_keys.as<unsigned long long>());
+        if (int rc = sort_and_emit(n, d_keys, 0x7fffffffull /* any degree */, rank_format ? 1 : 0, d_out.as<int32_t>(), s, &launches))
+            return rc;
+        GMSX_HIP(hipEventRecord(c.ev[1], s));
+        GMSX_HIP(hipMemcpyAsync(out, d_out.p, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        GMSX_HIP(hipGetLastError());
+        if (stats) {
+            float ms = 0.f;
+            GMSX_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+            *stats = gmsx_stats{double(ms), 0.0, uint64_t(n), 0, 0, launches, 0, 0};
+        }
+        return GMSX_OK;
+    });
+}
+
+int gmsx_order_quality(const gmsx_graph *g, const int32_t *ordering, int rank_format, int32_t core_number, int32_t *later,
+                       gmsx_order_quality_info *info, gmsx_stats *stats) {
+    return gmsx::guard([&]() -> int {
+        if (!g || !info || (g->n > 0 && !ordering)) return GMSX_ERR_INVALID;
+        if (int rc = ensure_init()) return rc;
+        Ctx &c = ctx();
+        hipStream_t s = c.stream;
+        const int64_t n = g->n;
+        gmsx_order_quality_info res;
+        std::memset(&res, 0, sizeof res);
+        if (n == 0) {
+            res.core_number = std::max<int32_t>(core_number, 0);
+            res.core_number_of_order = res.core_number;
+            *info = res;
+            if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0, 0};
+            return GMSX_OK;
+        }
+        const int cus = c.compute_units > 0 ? c.compute_units : 256;
+        const unsigned tb = unsigned((n + 255) / 256);
+        const int64_t long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
+        Dev d_in, d_rank, d_seen, d_later, d_long, d_ctl, d_acc;
+        if (int rc = dalloc<int32_t>(d_in, n)) return rc;
+        if (int rc = dalloc<int32_t>(d_seen, n)) return rc;
+        if (int rc = dalloc<int32_t>(d_later, n)) return rc;
+        if (int rc = dalloc<int32_t>(d_long, long_cap)) return rc;
+        if (int rc = dalloc<int32_t>(d_ctl, 4)) return rc;
+        if (int rc = dalloc<unsigned long long>(d_acc, 4)) return rc;
+        if (!rank_format)
+            if (int rc = dalloc<int32_t>(d_rank, n)) return rc;
+        GMSX_HIP(hipMemcpyAsync(d_in.p, ordering, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        GMSX_HIP(hipMemsetAsync(d_seen.p, 0, size_t(n) * sizeof(int32_t), s));
+        GMSX_HIP(hipMemsetAsync(d_ctl.p, 0, 4 * sizeof(int32_t), s));
+        GMSX_HIP(hipMemsetAsync(d_acc.p, 0, 4 * sizeof(unsigned long long), s));
+        GMSX_HIP(hipEventRecord(c.ev[0], s));
+        int32_t *rank = rank_format ? d_in.as<int32_t>() : d_rank.as<int32_t>();
+        // a permutation of 0..n-1, checked before anything reads rank[] as an index (the BK entry points refuse the same inputs)
+        hipLaunchKernelGGL(k_oq_rank, dim3(tb), dim3(256), 0, s, n, d_in.as<int32_t>(), rank_format ? 1 : 0, rank, d_seen.as<int32_t>(), d_ctl.as<int32_t>() + 2);
+        int32_t ctl[4] = {0, 0, 0, 0};
+        GMSX_HIP(hipMemcpyAsync(ctl, d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        if (ctl[2]) return GMSX_ERR_INVALID;  // n in-range entries, none hit twice: every value once
+        int launches = 3;
+        const unsigned lb = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
+        hipLaunchKernelGGL(k_oq_later, dim3(lb), dim3(256), 0, s, n, g->off, g->adj, rank, d_later.as<int32_t>(), d_long.as<int32_t>(), long_cap, d_ctl.as<int32_t>());
+        hipLaunchKernelGGL(k_oq_later_long, dim3(unsigned(cus) * 4), dim3(256), 0, s, g->off, g->adj, rank, d_later.as<int32_t>(), d_long.as<int32_t>(), long_cap,
+                           d_ctl.as<int32_t>());
+        GMSX_HIP(hipEventRecord(c.ev[1], s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        float ms = 0.f;
+        GMSX_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+        if (core_number < 0) {  // graded against the true degeneracy: the peel of gmsx_core_decomposition
+            Dev d_core, d_round;
+            gmsx_core_info ci;
+            int peel_launches = 0;
+            GMSX_HIP(hipEventRecord(c.ev[0], s));
+            if (int rc = core_peel(g, d_core, d_round, &ci, &peel_launches)) return rc;
+            GMSX_HIP(hipEventRecord(c.ev[1], s));
+            GMSX_HIP(hipStreamSynchronize(s));
+            float pms = 0.f;
+            GMSX_HIP(hipEventElapsedTime(&pms, c.ev[0], c.ev[1]));
+            ms += pms;
+            launches += peel_launches;
+            core_number = ci.degeneracy;
+        }
+        const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+        GMSX_HIP(hipEventRecord(c.ev[0], s));
+        hipLaunchKernelGGL(k_oq_reduce, dim3(sweep), dim3(256), 0, s, n, d_later.as<int32_t>(), core_number, d_acc.as<unsigned long long>());
+        GMSX_HIP(hipEventRecord(c.ev[1], s));
+        unsigned long long acc[4] = {0, 0, 0, 0};
+        GMSX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipMemcpyAsync(ctl, d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        GMSX_HIP(hipGetLastError());
+        if (ctl[1]) return GMSX_ERR_KERNEL;
+        float rms = 0.f;
+        GMSX_HIP(hipEventElapsedTime(&rms, c.ev[0], c.ev[1]));
+        std::vector<int32_t> h_later;
+        if (later) {
+            h_later.resize(size_t(n));
+            GMSX_HIP(hipMemcpy(h_later.data(), d_later.p, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        res.max_later = int32_t(acc[0]);
+        res.core_number = core_number;
+        res.core_number_of_order = std::max(core_number, res.max_later);
+        res.faulty = int64_t(acc[1]);
+        res.excess = int64_t(acc[2]);
+        if (core_number > 0) {
+            // core_number_evaluator.h:105-110, operand order as written there (size_t difference first, then the division by the double)
+            const size_t core_of_order = size_t(res.core_number_of_order), actual = size_t(core_number);
+            res.relative_error = (core_of_order - actual) / (double)actual;
+            res.fault_rate = (double)acc[1] / (double)n;
+            res.relative_mean_difference = (acc[1] == 0) ? 0 : ((double)acc[2] / (double)acc[1]) / (double)actual;
+        }
+        if (later) std::memcpy(later, h_later.data(), size_t(n) * sizeof(int32_t));
+        *info = res;
+        if (stats) *stats = gmsx_stats{double(ms + rms), 0.0, uint64_t(n), 0, 0, launches + 1, 0, 0};
+        return GMSX_OK;
+    });
+}
+
+}  // extern "C"

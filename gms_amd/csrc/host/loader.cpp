@@ -776,6 +776,8 @@ Option g_options[] = {
     {"BK_LIST_ARENA_MB", "", false},
     // k-clique-star listing (kcstar_list.hip)
     {"KCSTAR_SLAB_MB", "", false},
+    // core decomposition (core.hip)
+    {"CORE_WG_FRONTIER", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

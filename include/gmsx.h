@@ -139,7 +139,9 @@ int gmsx_set_host_threads(int n);
  *                   search is re-split), BK_GROUPS, BK_SMALL_P, BK_SMALL_P_GROUPS, BK_RESUME_GRAB, BK_SPLIT_BUILD, BK_TINY_ROOTS,
  *                   BK_TINY_BESIDE (kernel variants)
  *   Bron–Kerbosch listing  BK_LIST_ARENA_MB (budget of the search slabs of one launch: smaller = more launches)
- *   k-clique-star listing  KCSTAR_SLAB_MB (budget of the level-set slabs of one launch: smaller = more launches) */
+ *   k-clique-star listing  KCSTAR_SLAB_MB (budget of the level-set slabs of one launch: smaller = more launches)
+ *   core decomposition     CORE_WG_FRONTIER (largest frontier whose rounds run inside the one-workgroup kernel, default 512 — a first guess, not a
+ *                   tuned value; 0 = every round is a kernel boundary; test hook) */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -406,6 +408,58 @@ int gmsx_adg_rank(const gmsx_graph *g, double epsilon, int rank_format, int32_t 
  * parallel/vertex.h:42-46, so its own output depends on heap contents; this is the ordering by the well-defined counts, which
  * the reference produces with CountFn = Par::vertex_count2 — that instantiation is what the goldens were generated with.) */
 int gmsx_tc_ordering(const gmsx_graph *g, int32_t *ordering /* n, host */, gmsx_stats *stats);
+
+/* ---- exact k-core decomposition and an exact degeneracy order: the device counterpart of PpSequential::getDegeneracyOrderingMatula
+ * (preprocessing/sequential/degeneracy_matula.h:13-66; PpParallel::getDegeneracyOrderingMatula, parallel/degeneracy_matula.h, is the same serial
+ * loop behind a parallel degree pass) — "BK-GMS-DGR" of the Bron–Kerbosch driver (maximal_clique_enum_bron_kerbosch.cc:50-56).
+ * The peel: k = 0, every vertex remaining.  While vertices remain, k rises to the smallest remaining degree; then rounds repeat until none
+ * applies: in one round every remaining vertex whose remaining degree is <= k leaves at once — its core number is k, its round the running
+ * round index — and the remaining degrees of its still-remaining neighbours drop.  Isolated vertices leave in round 0 with core number 0.
+ * core[v] (n, host, or NULL) is unique for the graph: the running maximum of the removal degrees along the reference's Matula order, bit for bit;
+ * info->degeneracy = its maximum = CoreNumberEvaluator::getCoreNumberOfOrder of that order (core_number_evaluator.h:115-139).
+ * ordering (n, host, or NULL): the vertices by ascending (round, vertex id); rank_format as in gmsx_adg_rank (!= 0: ordering[v] = position of v,
+ * else ordering[i] = i-th vertex).  Every vertex has at most core[v] <= degeneracy neighbours after it, so this IS an exact degeneracy order: it
+ * passes DegeneracyOrderingVerifier::degegeneracyOrderingVerifier (preprocessing/verifiers/degeneracy_verifier.h:70-86) and, handed to
+ * Bron–Kerbosch as the rank, bounds every candidate set by the degeneracy.
+ * Ties: it is NOT Matula's own sequence.  That one takes, step by step, the minimum of (remaining degree, id) among the remaining vertices
+ * (:39-45, the first element of the lowest non-empty bucket) and is serial by construction; all exact degeneracy orders share the core
+ * numbers and the bound, and this one is the one a level-synchronous peel defines.  The same graph gives byte-identical core, ordering and
+ * info in every process and on every run (the arrival order of the atomics reaches no output).
+ * core and ordering may both be NULL: only *info is filled.  n = 0: GMSX_OK, *info zeroed.  NULL g or info: GMSX_ERR_INVALID.  A frontier that
+ * would overflow its buffer or a final count != n is reported as GMSX_ERR_KERNEL; nothing is written out of bounds.  Test hook: option
+ * CORE_WG_FRONTIER.  gmsx_stats: kernel_ms, launches, units = n, probes = rounds. */
+typedef struct {
+    int32_t degeneracy;   /* largest core number = the graph's degeneracy; 0 for an edgeless graph */
+    int32_t levels;       /* distinct core numbers that occur */
+    int32_t rounds;       /* peel rounds (definition above) */
+    int32_t reserved;
+    int64_t top_core;     /* vertices whose core number equals degeneracy */
+} gmsx_core_info;
+int gmsx_core_decomposition(const gmsx_graph *g, int32_t *core /* n, host, or NULL */, int32_t *ordering /* n, host, or NULL */, int rank_format,
+                            gmsx_core_info *info /* required */, gmsx_stats *stats);
+/* PpParallel::getDegreeOrdering (preprocessing/parallel/degree.h:15-61) — "BK-GMS-DEG" (maximal_clique_enum_bron_kerbosch.cc:43-49): the
+ * vertices by ASCENDING (degree, vertex id).  compare_degree (:16-22) is a strict total order, so the result is the reference's bit for bit in
+ * both formats (rank_format as in gmsx_adg_rank).  Not the device's internal degree order (that one is decreasing). */
+int gmsx_degree_rank(const gmsx_graph *g, int rank_format, int32_t *out /* n, host */, gmsx_stats *stats);
+/* CoreNumberEvaluator (preprocessing/util/core_number_evaluator.h): how good an order is as a degeneracy order.
+ * ordering: n entries (host), rank_format as in gmsx_adg_rank; it must be a permutation of 0..n-1 (checked on the device), else
+ * GMSX_ERR_INVALID and nothing is written.  core_number: the degeneracy to grade against; < 0 = computed here by the peel of
+ * gmsx_core_decomposition.  later (n, host, or NULL): per vertex the number of its neighbours that come after it.
+ * With core_number = 0 (an edgeless graph) the three doubles are 0.0 — the reference divides by zero there (:108-110).  n = 0: GMSX_OK, the
+ * integers 0 (core_number as passed, 0 if < 0), the doubles 0.0. */
+typedef struct {
+    int32_t max_later;            /* CoreNumberEvaluator::getCoreNumberOfOrder (:115-139): max over v of |{w in N(v): w after v}| */
+    int32_t core_number;          /* the degeneracy the order was graded against */
+    int32_t core_number_of_order; /* evaluateCoreNrAccuracy (:73-112): max(core_number, max_later) */
+    int32_t reserved;
+    int64_t faulty;               /* vertices with more than core_number neighbours after them (biggerThanCore) */
+    int64_t excess;               /* sum over those of (later - core_number) (difAcc, in 64 bits; the reference's unsigned int wraps above 2^32) */
+    double relative_error, fault_rate, relative_mean_difference; /* the reference's three expressions (:108-110), evaluated on the host from the integers above, operand order as written there */
+} gmsx_order_quality_info;
+int gmsx_order_quality(const gmsx_graph *g, const int32_t *ordering /* n, host */, int rank_format,
+                       int32_t core_number /* < 0: computed here by the peel of gmsx_core_decomposition */,
+                       int32_t *later /* n, host, or NULL: per-vertex count of neighbours after v */,
+                       gmsx_order_quality_info *info /* required */, gmsx_stats *stats);
 
 /* ---- the one collective of the path: the OpenMP reduction(+:total) of parallel/total.h:12,
  * k_clique_count_set_based.h:25 and the BK_CLIQUE_COUNTER atomic (tomita.h:76-77) across GPUs = ONE all-reduce of a u64 over

@@ -16,7 +16,9 @@
 //   PpParallel::getDegeneracyOrderingApproxSGraph<averageDegree, …>     gms/algorithms/preprocessing/parallel/degeneracy_approx_set.h:14-86
 //   PpParallel::triangleCountOrdering<SGraph>                           gms/algorithms/preprocessing/parallel/triangle_count.h:11-30
 // Everything not listed (Verify::*, BkTomita::mce, getDegreeOrdering, getDegeneracyOrderingMatula, …) keeps instantiating the
-// reference's generic templates over the gmsx host sets — that is what makes the harness's `-v` verifiers independent host
+// reference's generic templates over the gmsx host sets; the last two have device counterparts in the adaptor — gmsx::degree_order,
+// gmsx::degeneracy_order / gmsx::core_numbers, graded by gmsx::order_quality — that are not routed here (the exact order breaks ties
+// differently from Matula's own sequence).  The generic instantiation is what makes the harness's `-v` verifiers independent host
 // recounts (triangle_count/verifier.h:13-42, maximal_clique_enum/verifier.h:41-49).
 #pragma once
 

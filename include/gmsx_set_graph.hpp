@@ -23,6 +23,10 @@
 //   gmsx::maximal_clique_count(g, rank)  -> gmsx_bk_count          (maximal_clique_enum/parallel/eppsteinPAR.h:18-53)
 //   gmsx::adg_rank(g, eps, out)          -> gmsx_adg_rank          (preprocessing/parallel/degeneracy_approx_set.h:14-86)
 //   gmsx::triangle_count_ordering(g,out) -> gmsx_tc_ordering       (preprocessing/parallel/triangle_count.h:11-30)
+//   gmsx::core_numbers(g, out)           -> gmsx_core_decomposition (the core numbers behind preprocessing/sequential/degeneracy_matula.h:13-66; returns the degeneracy)
+//   gmsx::degeneracy_order(g, out)       -> gmsx_core_decomposition (an exact degeneracy order; not Matula's own tie sequence, gmsx.h)
+//   gmsx::degree_order(g, out)           -> gmsx_degree_rank       (preprocessing/parallel/degree.h:15-61)
+//   gmsx::order_quality(g, order)        -> gmsx_order_quality     (preprocessing/util/core_number_evaluator.h:73-139)
 // include/gmsx_gms_glue.hpp holds the explicit specialisations that route the reference's own function names to these
 // (INTEGRATION.md §2).  Header-only; link with -lgmsx.
 #pragma once
@@ -530,6 +534,46 @@ inline void triangle_count_ordering(const HipGraphT<S> &g, Output &ordering) {
     ordering.resize(size_t(g.num_nodes()));
     static_assert(sizeof(*ordering.data()) == sizeof(int32_t), "orderings are NodeId = int32 vectors");
     detail::check(gmsx_tc_ordering(g.device(), reinterpret_cast<int32_t *>(ordering.data()), nullptr), "gmsx_tc_ordering");
+}
+// The core numbers of all vertices (the running maximum of the removal degrees along PpSequential::getDegeneracyOrderingMatula's order,
+// degeneracy_matula.h:13-66); returns the degeneracy.  `info` (optional) receives levels, rounds and the size of the top core.
+template <class S, class Output>
+inline int32_t core_numbers(const HipGraphT<S> &g, Output &core, gmsx_core_info *info = nullptr) {
+    core.resize(size_t(g.num_nodes()));
+    static_assert(sizeof(*core.data()) == sizeof(int32_t), "core numbers are NodeId = int32 vectors");
+    gmsx_core_info ci{};
+    detail::check(gmsx_core_decomposition(g.device(), reinterpret_cast<int32_t *>(core.data()), nullptr, 1, &ci, nullptr), "gmsx_core_decomposition");
+    if (info) *info = ci;
+    return ci.degeneracy;
+}
+// An EXACT degeneracy order — what getDegeneracyOrderingMatula<SGraph, useRankFormat> is for: every vertex has at most degeneracy
+// neighbours after it.  The vertices by (peel round, id), not Matula's own sequence (gmsx.h); returns the degeneracy.
+template <class S, class Output>
+inline int32_t degeneracy_order(const HipGraphT<S> &g, Output &res, bool rank_format = true) {
+    res.resize(size_t(g.num_nodes()));
+    static_assert(sizeof(*res.data()) == sizeof(int32_t), "orderings are NodeId = int32 vectors");
+    gmsx_core_info ci{};
+    detail::check(gmsx_core_decomposition(g.device(), nullptr, reinterpret_cast<int32_t *>(res.data()), rank_format ? 1 : 0, &ci, nullptr),
+                  "gmsx_core_decomposition");
+    return ci.degeneracy;
+}
+// PpParallel::getDegreeOrdering<AnyGraph, useRankFormat> (preprocessing/parallel/degree.h:15-61): ascending (degree, id), bit-identical
+template <class S, class Output>
+inline void degree_order(const HipGraphT<S> &g, Output &res, bool rank_format = true) {
+    res.resize(size_t(g.num_nodes()));
+    static_assert(sizeof(*res.data()) == sizeof(int32_t), "orderings are NodeId = int32 vectors");
+    detail::check(gmsx_degree_rank(g.device(), rank_format ? 1 : 0, reinterpret_cast<int32_t *>(res.data()), nullptr), "gmsx_degree_rank");
+}
+// CoreNumberEvaluator::evaluateCoreNrAccuracy<useRankFormat> (core_number_evaluator.h:73-112, :141-154 when core_number < 0: graded against
+// the exact degeneracy, computed on the device) — info.max_later is getCoreNumberOfOrder (:115-139)
+template <class S, class Input>
+inline gmsx_order_quality_info order_quality(const HipGraphT<S> &g, const Input &order, bool rank_format = true, int32_t core_number = -1) {
+    static_assert(sizeof(*order.data()) == sizeof(int32_t), "orderings are NodeId = int32 vectors");
+    gmsx_order_quality_info qi{};
+    if (int64_t(order.size()) != g.num_nodes()) detail::check(GMSX_ERR_INVALID, "gmsx_order_quality");
+    detail::check(gmsx_order_quality(g.device(), reinterpret_cast<const int32_t *>(order.data()), rank_format ? 1 : 0, core_number, nullptr, &qi, nullptr),
+                  "gmsx_order_quality");
+    return qi;
 }
 
 // Set::intersect / Set::difference of whole neighbourhoods for a BATCH of vertex pairs on the device (sorted_set.h:160-197): result i =
