@@ -9,20 +9,14 @@
 // u in P ∪ Xc, ties to the lowest local index.  In addition the chosen local indices R are kept, one word per level; at a leaf
 // (P, Xc, Xf all empty) the wave maps {v} ∪ R through N+(r) and oldid to the caller's ids, ranks them by count and stores them ascending.
 //
-// One wave per start vertex; every structure of a search lives in its own slab of a global arena (Cadj | XT | levels | R), so no width is
-// refused.  Start vertices run in launches whose slabs fit the arena budget (GMSX_BK_LIST_ARENA_MB, a test hook, shrinks it).
-// Two passes over one deterministic task list (the shard's start vertices in rank-id order, i.e. by decreasing degree):
-//   FILL = false  per task: cliques, member total; per call: size histogram and largest clique
-//   scan          rocPRIM exclusive scans give every task its base in the offsets and member arrays
-//   FILL = true   the identical search again, every clique written at its task's base + a running offset
-// Nothing that shapes the search depends on timing (pivot ties by index, DFS order by index), so pass 2 meets the cliques of pass 1 in the
-// same order; a task that would write more or other than pass 1 counted sets a flag instead (GMSX_ERR_KERNEL), it never writes past its span.
-#include "device_graph.hpp"
+// One wave per start vertex; every structure of a search lives in its own slab of a global arena (Cadj | XT | levels | R).  The task list is
+// the shard's start vertices in rank-id order, i.e. by decreasing degree; the two passes over it (count: cliques and member total per task,
+// size histogram and largest clique per call; scan; fill), the launches that fit the arena budget (test hook BK_LIST_ARENA_MB) and the
+// pass-1 cache are the scaffold of two_pass_list.hpp.  Nothing that shapes the search depends on timing (pivot ties by index, DFS order by
+// index), which is what that scheme asks of a kernel.
+#include "two_pass_list.hpp"
 
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
-#include <new>
 #include <vector>
 
 namespace gmsx {
@@ -44,12 +38,6 @@ __host__ __device__ inline unsigned long long bkl_need(long long c, long long x)
 }
 
 __device__ __forceinline__ void bkl_flag(unsigned long long *acc, unsigned long long f) { atomicOr(&acc[kListFlags], f); }
-
-// the wave's writes to its slab visible to the other lanes of the wave (readers: this wave only)
-__device__ __forceinline__ void bkl_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ unsigned long long bkl_max64(unsigned long long k) {
     for (int m = 32; m >= 1; m >>= 1) {
@@ -178,14 +166,14 @@ __global__ __launch_bounds__(64) void k_bk_list(const int64_t *__restrict__ off,
                         if (lane < s) out_mem[pos + rk] = id;
                     } else {
                         for (long long i = lane; i < s; i += 64) ids[i] = uint32_t(i == 0 ? o : oldid[cand[Rst[i - 1]]]);
-                        bkl_sync();
+                        wave_slab_sync();
                         for (long long i = lane; i < s; i += 64) {
                             const int32_t me = int32_t(ids[i]);
                             long long rk = 0;
                             for (long long j = 0; j < s; ++j) rk += int32_t(ids[j]) < me ? 1 : 0;
                             out_mem[pos + rk] = me;
                         }
-                        bkl_sync();
+                        wave_slab_sync();
                     }
                 }
             }
@@ -239,7 +227,7 @@ __global__ __launch_bounds__(64) void k_bk_list(const int64_t *__restrict__ off,
             return;
         }
         for (long long i = lane; i < c * (cw + xw); i += 64) Cadj[i] = 0u;  // Cadj and XT are contiguous
-        bkl_sync();
+        wave_slab_sync();
         // ---- Cadj | XT: every neighbour's oriented row, up to rank id r (nothing at or above r is a candidate); a lane per row
         for (long long jj = lane; jj < c + x; jj += 64) {
             const bool is_c = jj < c;
@@ -282,7 +270,7 @@ __global__ __launch_bounds__(64) void k_bk_list(const int64_t *__restrict__ off,
             }
             for (long long i = lane; i < xw; i += 64) Xf[i] = (i < xw - 1 || (x & 31) == 0) ? ~0u : ((1u << (x & 31)) - 1u);
             if (lane == 0) Rst[0] = 0xFFFFFFFFu;
-            bkl_sync();
+            wave_slab_sync();
             bkl_pivot(P, Xc, L + 2 * cw, Cadj, c, cw, lane);
         }
         long long d = 0;
@@ -325,7 +313,7 @@ __global__ __launch_bounds__(64) void k_bk_list(const int64_t *__restrict__ off,
                 anyX |= xf != 0u;
             }
             const bool wP = __ballot(anyP) != 0ull, wX = __ballot(anyX) != 0ull;
-            bkl_sync();
+            wave_slab_sync();
             if (!wP) {
                 if (!wX) emit(d + 2);
                 continue;
@@ -333,7 +321,7 @@ __global__ __launch_bounds__(64) void k_bk_list(const int64_t *__restrict__ off,
             ++d;
             if (lane == 0) Rst[d] = 0xFFFFFFFFu;
             bkl_pivot(Pn, Xcn, Pn + 2 * cw, Cadj, c, cw, lane);
-            bkl_sync();
+            wave_slab_sync();
         }
     }
 
@@ -351,101 +339,29 @@ __global__ __launch_bounds__(64) void k_bk_list(const int64_t *__restrict__ off,
     }
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-};
-
-// Pass 1 of the last (graph, shard): a fill call that follows its sizing call re-uses it instead of searching a third time.  Keyed on the
-// handle and its device arrays; a stale entry can only make pass 2 disagree with it, which is reported (GMSX_ERR_KERNEL), never written.
-struct ListPass1 {
-    const gmsx_graph *g = nullptr;
-    const int64_t *off = nullptr;
-    const int32_t *adj = nullptr;
-    int64_t n = -1, nnz = -1;
-    int part = -1, nparts = -1;
-    int64_t n_tasks = 0;
-    std::vector<int64_t> soff;  // slab offsets (words), n_tasks + 1
-    DevBuf task_r, slab_off, cbase, mbase;
+struct BkListPass1 : ListPass1 {  // task[0]: the start vertices' rank ids
     gmsx_bk_list_info info{};
-    bool valid = false;
-    void clear() {
-        valid = false;
-        g = nullptr;
-        soff.clear();
-        soff.shrink_to_fit();
-        task_r.reset();
-        slab_off.reset();
-        cbase.reset();
-        mbase.reset();
-    }
 };
-ListPass1 &pass1_cache() {
-    static ListPass1 c;
+BkListPass1 &pass1_cache() {
+    static BkListPass1 c;
     return c;
 }
-
-// launches of one pass: consecutive tasks whose slabs fit the arena
-struct Launch {
-    int64_t t0, t1;
-};
-std::vector<Launch> plan_launches(const std::vector<int64_t> &soff, int64_t n_tasks, unsigned long long budget_words, unsigned long long *arena_words) {
-    std::vector<Launch> out;
-    unsigned long long widest = 0;
-    for (int64_t t0 = 0; t0 < n_tasks;) {
-        int64_t t1 = t0 + 1;
-        while (t1 < n_tasks && (unsigned long long)(soff[size_t(t1 + 1)] - soff[size_t(t0)]) <= budget_words) ++t1;
-        widest = std::max<unsigned long long>(widest, (unsigned long long)(soff[size_t(t1)] - soff[size_t(t0)]));
-        out.push_back({t0, t1});
-        t0 = t1;
-    }
-    *arena_words = widest;
-    return out;
-}
+constexpr ListArena kArena{8ull << 30, "BK_LIST_ARENA_MB", kNoTaskCap};  // the option is a test hook: a small arena splits a small graph into many launches
 
 template <bool FILL>
 int run_pass(const gmsx_graph *g, const ListPass1 &p1, int64_t *cnt, int64_t *mem, int64_t *out_off, int32_t *out_mem, int64_t off_cap,
              int64_t mem_cap, unsigned long long *acc, int *launches) {
-    hipStream_t s = ctx().stream;
-    size_t free_b = 0, total_b = 0;
-    GMSX_HIP(hipMemGetInfo(&free_b, &total_b));
-    unsigned long long budget_words = std::min<unsigned long long>(free_b / 4, 8ull << 30) / 4;
-    const long long mb = opt_int("BK_LIST_ARENA_MB", 0);  // test hook: a small arena splits a small graph into many launches
-    if (mb >= 1) budget_words = std::min<unsigned long long>(budget_words, ((unsigned long long)mb << 20) / 4);
-    unsigned long long arena_words = 0;
-    const std::vector<Launch> plan = plan_launches(p1.soff, p1.n_tasks, std::max<unsigned long long>(budget_words, 4), &arena_words);
-    if (plan.empty()) return GMSX_OK;
-    DevBuf arena;
-    GMSX_HIP(hipMalloc(&arena.p, size_t(arena_words) * 4 + 64));
-    for (const Launch &l : plan) {
-        hipLaunchKernelGGL((k_bk_list<FILL>), dim3(unsigned(l.t1 - l.t0)), dim3(64), 0, s, g->off, g->adj, g->newid, g->oldid, g->hoff, g->hadj,
-                           g->toff, g->tadj, g->dplus, static_cast<const int32_t *>(p1.task_r.p), static_cast<const int64_t *>(p1.slab_off.p), l.t0,
-                           l.t1, static_cast<uint32_t *>(arena.p), arena_words, cnt, mem, static_cast<const int64_t *>(p1.cbase.p),
-                           static_cast<const int64_t *>(p1.mbase.p), out_off, out_mem, off_cap, mem_cap, acc);
-        GMSX_HIP(hipGetLastError());
-        ++*launches;
-    }
-    GMSX_HIP(hipStreamSynchronize(s));
-    return GMSX_OK;
+    return run_list_pass(p1, kArena, FILL ? 2 : 0, launches, [&](const Launch &l, void *arena, unsigned long long arena_words) {
+        hipLaunchKernelGGL((k_bk_list<FILL>), dim3(unsigned(l.t1 - l.t0)), dim3(64), 0, ctx().stream, g->off, g->adj, g->newid, g->oldid, g->hoff,
+                           g->hadj, g->toff, g->tadj, g->dplus, p1.task[0].as<const int32_t>(), p1.slab_off.as<const int64_t>(), l.t0, l.t1,
+                           static_cast<uint32_t *>(arena), arena_words, cnt, mem, p1.cbase.as<const int64_t>(), p1.mbase.as<const int64_t>(), out_off,
+                           out_mem, off_cap, mem_cap, acc);
+    });
 }
 
-int flags_status(unsigned long long f) { return f ? GMSX_ERR_KERNEL : GMSX_OK; }
-
-// pass 1 of (g, part, nparts) into the cache
-int bk_list_pass1(const gmsx_graph *g, int part, int nparts, double *ms, int *launches) {
-    ListPass1 &p1 = pass1_cache();
-    p1.clear();
-    Ctx &cx = ctx();
-    hipStream_t s = cx.stream;
+// pass 1 of (g, part, nparts) into the cleared p1
+int bk_list_pass1(const gmsx_graph *g, int part, int nparts, BkListPass1 &p1, double *ms, int *launches) {
+    hipStream_t s = ctx().stream;
     const int64_t n = g->n;
     // ---- task list: the shard's start vertices that yield a clique or a search, by rank id (decreasing degree: heavy first)
     std::vector<int32_t> dplus(static_cast<size_t>(n)), oldid(static_cast<size_t>(n));
@@ -467,38 +383,18 @@ int bk_list_pass1(const gmsx_graph *g, int part, int nparts, double *ms, int *la
         task_r.push_back(int32_t(r));
         p1.soff.push_back(p1.soff.back() + int64_t(bkl_need(c, x)));
     }
-    const int64_t nt = int64_t(task_r.size());
-    p1.n_tasks = nt;
-    GMSX_HIP(hipMalloc(&p1.task_r.p, size_t(nt > 0 ? nt : 1) * 4));
-    GMSX_HIP(hipMalloc(&p1.slab_off.p, size_t(nt + 1) * 8));
-    GMSX_HIP(hipMalloc(&p1.cbase.p, size_t(nt + 1) * 8));
-    GMSX_HIP(hipMalloc(&p1.mbase.p, size_t(nt + 1) * 8));
-    if (nt > 0) GMSX_HIP(hipMemcpyAsync(p1.task_r.p, task_r.data(), size_t(nt) * 4, hipMemcpyHostToDevice, s));
-    GMSX_HIP(hipMemcpyAsync(p1.slab_off.p, p1.soff.data(), size_t(nt + 1) * 8, hipMemcpyHostToDevice, s));
+    const std::vector<int32_t> *tasks[] = {&task_r};
+    if (int rc = upload_tasks(p1, tasks, 1, s)) return rc;
+    const int64_t nt = p1.n_tasks;
     DevBuf cnt, mem, acc;
-    GMSX_HIP(hipMalloc(&cnt.p, size_t(nt + 1) * 8));
-    GMSX_HIP(hipMalloc(&mem.p, size_t(nt + 1) * 8));
-    GMSX_HIP(hipMalloc(&acc.p, size_t(kListAcc) * 8));
-    GMSX_HIP(hipMemsetAsync(cnt.p, 0, size_t(nt + 1) * 8, s));
-    GMSX_HIP(hipMemsetAsync(mem.p, 0, size_t(nt + 1) * 8, s));
-    GMSX_HIP(hipMemsetAsync(acc.p, 0, size_t(kListAcc) * 8, s));
-    GMSX_HIP(hipEventRecord(cx.ev[0], s));
-    if (int rc = run_pass<false>(g, p1, static_cast<int64_t *>(cnt.p), static_cast<int64_t *>(mem.p), nullptr, nullptr, 0, 0,
-                                 static_cast<unsigned long long *>(acc.p), launches))
-        return rc;
-    GMSX_HIP(hipEventRecord(cx.ev[1], s));
-    if (int rc = exclusive_scan_i64(static_cast<const int64_t *>(cnt.p), static_cast<int64_t *>(p1.cbase.p), nt + 1, s)) return rc;
-    if (int rc = exclusive_scan_i64(static_cast<const int64_t *>(mem.p), static_cast<int64_t *>(p1.mbase.p), nt + 1, s)) return rc;
+    if (int rc = alloc_zeroed(cnt, size_t(nt + 1) * 8, s)) return rc;
+    if (int rc = alloc_zeroed(mem, size_t(nt + 1) * 8, s)) return rc;
+    if (int rc = alloc_zeroed(acc, size_t(kListAcc) * 8, s)) return rc;
+    if (int rc = run_pass<false>(g, p1, cnt.as<int64_t>(), mem.as<int64_t>(), nullptr, nullptr, 0, 0, acc.as<unsigned long long>(), launches)) return rc;
     unsigned long long host[kListAcc];
     int64_t tot[2] = {0, 0};
-    GMSX_HIP(hipMemcpyAsync(host, acc.p, sizeof(host), hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipMemcpyAsync(&tot[0], static_cast<int64_t *>(p1.cbase.p) + nt, 8, hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipMemcpyAsync(&tot[1], static_cast<int64_t *>(p1.mbase.p) + nt, 8, hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipStreamSynchronize(s));
-    float f_ms = 0.f;
-    GMSX_HIP(hipEventElapsedTime(&f_ms, cx.ev[0], cx.ev[1]));
-    *ms = double(f_ms);
-    if (int rc = flags_status(host[kListFlags])) return rc;
+    if (int rc = finish_count_pass(p1, cnt, mem, acc, host, kListAcc, tot, 0, ms)) return rc;
+    if (host[kListFlags]) return GMSX_ERR_KERNEL;
     gmsx_bk_list_info info{};
     info.cliques = tot[0];
     info.members = tot[1];
@@ -506,33 +402,17 @@ int bk_list_pass1(const gmsx_graph *g, int part, int nparts, double *ms, int *la
     for (int b = 0; b < kListBins; ++b) info.size_hist[b] = int64_t(host[b]);
     info.size_hist[0] = 0;
     p1.info = info;
-    p1.g = g;
-    p1.off = g->off;
-    p1.adj = g->adj;
-    p1.n = g->n;
-    p1.nnz = g->nnz;
-    p1.part = part;
-    p1.nparts = nparts;
-    p1.valid = true;
     return GMSX_OK;
 }
 
 int bk_list(const gmsx_graph *g, int part, int nparts, int64_t *offsets, int32_t *members, int64_t offsets_capacity, int64_t members_capacity,
             gmsx_bk_list_info *info, gmsx_stats *st) {
-    Ctx &cx = ctx();
-    hipStream_t s = cx.stream;
-    ListPass1 &p1 = pass1_cache();
+    hipStream_t s = ctx().stream;
+    BkListPass1 &p1 = pass1_cache();
     const bool sizing = offsets == nullptr && members == nullptr;
     double ms1 = 0.0, ms2 = 0.0;
     int launches = 0;
-    const bool hit = p1.valid && p1.g == g && p1.off == g->off && p1.adj == g->adj && p1.n == g->n && p1.nnz == g->nnz && p1.part == part &&
-                     p1.nparts == nparts;
-    if (!hit || sizing) {  // a sizing call always searches (it is what a caller times); a fill call re-uses its pass 1
-        if (int rc = bk_list_pass1(g, part, nparts, &ms1, &launches)) {
-            p1.clear();
-            return rc;
-        }
-    }
+    if (int rc = ensure_pass1(p1, ListKey(g, part, nparts), sizing, [&] { return bk_list_pass1(g, part, nparts, p1, &ms1, &launches); })) return rc;
     *info = p1.info;
     if (!sizing) {
         const int64_t nc = p1.info.cliques, nm = p1.info.members;
@@ -540,21 +420,13 @@ int bk_list(const gmsx_graph *g, int part, int nparts, int64_t *offsets, int32_t
         DevBuf d_off, d_mem, acc;
         GMSX_HIP(hipMalloc(&d_off.p, size_t(nc + 1) * 8));
         GMSX_HIP(hipMalloc(&d_mem.p, size_t(nm > 0 ? nm : 1) * 4));
-        GMSX_HIP(hipMalloc(&acc.p, size_t(kListAcc) * 8));
-        GMSX_HIP(hipMemsetAsync(acc.p, 0, size_t(kListAcc) * 8, s));
-        GMSX_HIP(hipMemcpyAsync(static_cast<int64_t *>(d_off.p) + nc, &nm, 8, hipMemcpyHostToDevice, s));
-        GMSX_HIP(hipEventRecord(cx.ev[2], s));
-        if (int rc = run_pass<true>(g, p1, nullptr, nullptr, static_cast<int64_t *>(d_off.p), static_cast<int32_t *>(d_mem.p), nc, nm,
-                                    static_cast<unsigned long long *>(acc.p), &launches))
+        if (int rc = alloc_zeroed(acc, size_t(kListAcc) * 8, s)) return rc;
+        GMSX_HIP(hipMemcpyAsync(d_off.as<int64_t>() + nc, &nm, 8, hipMemcpyHostToDevice, s));
+        if (int rc = run_pass<true>(g, p1, nullptr, nullptr, d_off.as<int64_t>(), d_mem.as<int32_t>(), nc, nm, acc.as<unsigned long long>(), &launches))
             return rc;
-        GMSX_HIP(hipEventRecord(cx.ev[3], s));
         unsigned long long host[kListAcc];
-        GMSX_HIP(hipMemcpyAsync(host, acc.p, sizeof(host), hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipStreamSynchronize(s));
-        float f_ms = 0.f;
-        GMSX_HIP(hipEventElapsedTime(&f_ms, cx.ev[2], cx.ev[3]));
-        ms2 = double(f_ms);
-        if (int rc = flags_status(host[kListFlags])) return rc;
+        if (int rc = finish_fill_pass(acc, host, kListAcc, 2, &ms2)) return rc;
+        if (host[kListFlags]) return GMSX_ERR_KERNEL;
         // the caller's buffers are written only now, on success
         GMSX_HIP(hipMemcpyAsync(offsets, d_off.p, size_t(nc + 1) * 8, hipMemcpyDeviceToHost, s));
         if (nm > 0) GMSX_HIP(hipMemcpyAsync(members, d_mem.p, size_t(nm) * 4, hipMemcpyDeviceToHost, s));

@@ -20,6 +20,7 @@
 // the frontier empties (the level is done: the next k needs a sweep over all vertices) or outgrows the threshold.  No workgroup ever waits
 // for another one.  Rows are binned by length: a 16-lane group per vertex up to kLongRow entries, longer rows by all workgroups of
 // k_core_round_long (all threads of the workgroup in k_core_tail) together — no lane walks a long row alone.
+#include "device_buffer.hpp"
 #include "device_graph.hpp"
 
 #include <algorithm>
@@ -32,21 +33,6 @@
 namespace gmsx {
 
 namespace {
-
-struct Dev {
-    void *p = nullptr;
-    ~Dev() { (void)hipFree(p); }
-    template <class T> T *as() { return static_cast<T *>(p); }
-};
-template <class T>
-int dalloc(Dev &d, int64_t count) {
-    if (hipMalloc(&d.p, size_t(std::max<int64_t>(count, 1)) * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        d.p = nullptr;
-        return GMSX_ERR_DEVICE_MEM;
-    }
-    return GMSX_OK;
-}
 
 // UNMEASURED: none of these bounds has a timing behind it yet (tools/core_probe.py is the measurement).  They follow the round
 // table of the peel on R-MAT graphs (almost every round removes fewer than 256 vertices) and the row shapes named there.
@@ -307,8 +293,8 @@ int bits_for(uint64_t max_value) {
 }
 
 // sorts n keys (hi << 32 | id) whose high halves are <= max_hi and writes the rank or order vector they imply into d_out
-int sort_and_emit(int64_t n, Dev &d_keys, uint64_t max_hi, int rank_format, int32_t *d_out, hipStream_t s, int *launches) {
-    Dev d_sorted, d_tmp;
+int sort_and_emit(int64_t n, DevBuf &d_keys, uint64_t max_hi, int rank_format, int32_t *d_out, hipStream_t s, int *launches) {
+    DevBuf d_sorted, d_tmp;
     if (int rc = dalloc<unsigned long long>(d_sorted, n)) return rc;
     const unsigned end_bit = 32u + unsigned(bits_for(max_hi));
     size_t tmp_bytes = 0;
@@ -322,12 +308,12 @@ int sort_and_emit(int64_t n, Dev &d_keys, uint64_t max_hi, int rank_format, int3
 }
 
 // The peel.  On success d_core / d_round (n each, device) hold the core number and the round of every vertex.
-int core_peel(const gmsx_graph *g, Dev &d_core, Dev &d_round, gmsx_core_info *info, int *launches_out) {
+int core_peel(const gmsx_graph *g, DevBuf &d_core, DevBuf &d_round, gmsx_core_info *info, int *launches_out) {
     Ctx &c = ctx();
     hipStream_t s = c.stream;
     const int64_t n = g->n;
     const int64_t long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
-    Dev d_deg, d_f0, d_f1, d_long, d_ctrl;
+    DevBuf d_deg, d_f0, d_f1, d_long, d_ctrl;
     if (int rc = dalloc<int32_t>(d_deg, n)) return rc;
     if (int rc = dalloc<int32_t>(d_core, n)) return rc;
     if (int rc = dalloc<int32_t>(d_round, n)) return rc;
@@ -508,7 +494,7 @@ int gmsx_core_decomposition(const gmsx_graph *g, int32_t *core, int32_t *orderin
             if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0, 0};
             return GMSX_OK;
         }
-        Dev d_core, d_round, d_keys, d_out;
+        DevBuf d_core, d_round, d_keys, d_out;
         int launches = 0;
         GMSX_HIP(hipEventRecord(c.ev[0], s));
         if (int rc = core_peel(g, d_core, d_round, &res, &launches)) return rc;
@@ -551,7 +537,7 @@ int gmsx_degree_rank(const gmsx_graph *g, int rank_format, int32_t *out, gmsx_st
         const int64_t n = g->n;
         if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0, 0};
         if (n == 0) return GMSX_OK;
-        Dev d_keys, d_out;
+        DevBuf d_keys, d_out;
         if (int rc = dalloc<unsigned long long>(d_keys, n)) return rc;
         if (int rc = dalloc<int32_t>(d_out, n)) return rc;
         int launches = 1;
@@ -593,7 +579,7 @@ int gmsx_order_quality(const gmsx_graph *g, const int32_t *ordering, int rank_fo
         const int cus = c.compute_units > 0 ? c.compute_units : 256;
         const unsigned tb = unsigned((n + 255) / 256);
         const int64_t long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
-        Dev d_in, d_rank, d_seen, d_later, d_long, d_ctl, d_acc;
+        DevBuf d_in, d_rank, d_seen, d_later, d_long, d_ctl, d_acc;
         if (int rc = dalloc<int32_t>(d_in, n)) return rc;
         if (int rc = dalloc<int32_t>(d_seen, n)) return rc;
         if (int rc = dalloc<int32_t>(d_later, n)) return rc;
@@ -624,7 +610,7 @@ int gmsx_order_quality(const gmsx_graph *g, const int32_t *ordering, int rank_fo
         float ms = 0.f;
         GMSX_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
         if (core_number < 0) {  // graded against the true degeneracy: the peel of gmsx_core_decomposition
-            Dev d_core, d_round;
+            DevBuf d_core, d_round;
             gmsx_core_info ci;
             int peel_launches = 0;
             GMSX_HIP(hipEventRecord(c.ev[0], s));

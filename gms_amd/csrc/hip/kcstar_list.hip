@@ -13,16 +13,12 @@
 // every clique is met exactly once.  Members are never in their own rows, so T_(k-1) is exactly the star, ascending: pass 1 counts it,
 // pass 2 stores it where it belongs.  With CLIQUES_ONLY nothing but candidates is carried (the rank filter is applied when a list is
 // built) and the last level is not built: every element of T_(k-2) closes a clique.  A branch stops when fewer candidates remain than
-// members are still needed.  T_1 … T_(k-2) live in the task's slab of a global arena (k - 2 lists of d(u) ids), so no width is refused;
-// tasks run in launches whose slabs fit the budget (option KCSTAR_SLAB_MB, a test hook, shrinks it).  The per-level search state (position,
-// candidate mask, list size, chosen member) is spread over the lanes: lane j holds level j (k <= 63).
-// Two passes over one deterministic task list (the shard's pivots in rank-id order, each pivot's first members in ascending caller id):
-//   FILL = false  per task: cliques and star ids; per call: the largest star (integer atomicMax)
-//   scan          rocPRIM exclusive scans give every task its base in the clique rows and in the star array
-//   FILL = true   the identical search again, every pair written at its task's base + a running offset
-// Nothing that shapes the search depends on timing, so pass 2 meets the pairs of pass 1 in the same order; a task that would write more or
-// other than pass 1 counted raises a flag instead (GMSX_ERR_KERNEL), it never writes past its span.
-#include "device_graph.hpp"
+// members are still needed.  T_1 … T_(k-2) live in the task's slab of a global arena (k - 2 lists of d(u) ids).  The per-level search state
+// (position, candidate mask, list size, chosen member) is spread over the lanes: lane j holds level j (k <= 63).
+// The task list is the shard's pivots in rank-id order, each pivot's first members in ascending caller id; the two passes over it (count:
+// cliques and star ids per task, the largest star per call by integer atomicMax; scan; fill), the launches that fit the slab budget (test
+// hook KCSTAR_SLAB_MB) and the pass-1 cache are the scaffold of two_pass_list.hpp.  Nothing that shapes the search depends on timing.
+#include "two_pass_list.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -35,15 +31,8 @@ namespace {
 constexpr int kWavesPerBlock = 4;
 constexpr int kAccMax = 0, kAccFlags = 1, kAccWords = 2;
 constexpr unsigned long long kFlagSlab = 1, kFlagOut = 2, kFlagMismatch = 4;
-constexpr int64_t kMaxTasksPerLaunch = int64_t(1) << 24;
 
 __device__ __forceinline__ void kcs_flag(unsigned long long *acc, unsigned long long f) { atomicOr(&acc[kAccFlags], f); }
-
-// the wave's writes to its slab visible to the other lanes of the wave (readers: this wave only)
-__device__ __forceinline__ void kcs_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ unsigned long long kcs_shfl64(unsigned long long v, int j) {
     const unsigned lo = unsigned(__shfl(int(unsigned(v)), j));
@@ -215,7 +204,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_kcstar_list(
             failed = true;
             return false;
         }
-        kcs_sync();
+        wave_slab_sync();
         if (nc < (long long)(k - (d + 1))) return false;  // fewer candidates than members still needed
         if (lane == d) {
             memb = x;
@@ -295,104 +284,31 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_kcstar_list(
     }
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-};
-
-// Pass 1 of the last (graph, k, flags, shard): a fill call that follows its sizing call re-uses it instead of searching a third time.  Keyed
-// on the handle and its device arrays; a stale entry can only make pass 2 disagree with it, which is reported (GMSX_ERR_KERNEL), never written.
-struct StarPass1 {
-    const gmsx_graph *g = nullptr;
-    const int64_t *off = nullptr;
-    const int32_t *adj = nullptr;
-    int64_t n = -1, nnz = -1;
-    int k = 0, part = -1, nparts = -1;
-    uint32_t flags = 0;
-    int64_t n_tasks = 0;
-    std::vector<int64_t> soff;  // slab offsets (words), n_tasks + 1
-    DevBuf task_a, task_b, slab_off, cbase, mbase;
+struct StarPass1 : ListPass1 {  // task[0]: pivots, task[1]: first members (caller ids; -1 for k = 1)
     gmsx_kclique_star_list_info info{};
-    bool valid = false;
-    void clear() {
-        valid = false;
-        g = nullptr;
-        soff.clear();
-        soff.shrink_to_fit();
-        task_a.reset();
-        task_b.reset();
-        slab_off.reset();
-        cbase.reset();
-        mbase.reset();
-    }
 };
 StarPass1 &pass1_cache() {
     static StarPass1 c;
     return c;
 }
-
-// launches of one pass: consecutive tasks whose slabs fit the arena
-struct Launch {
-    int64_t t0, t1;
-};
-std::vector<Launch> plan_launches(const std::vector<int64_t> &soff, int64_t n_tasks, unsigned long long budget_words, unsigned long long *arena_words) {
-    std::vector<Launch> out;
-    unsigned long long widest = 0;
-    for (int64_t t0 = 0; t0 < n_tasks;) {
-        int64_t t1 = t0 + 1;
-        while (t1 < n_tasks && t1 - t0 < kMaxTasksPerLaunch && (unsigned long long)(soff[size_t(t1 + 1)] - soff[size_t(t0)]) <= budget_words) ++t1;
-        widest = std::max<unsigned long long>(widest, (unsigned long long)(soff[size_t(t1)] - soff[size_t(t0)]));
-        out.push_back({t0, t1});
-        t0 = t1;
-    }
-    *arena_words = widest;
-    return out;
-}
+constexpr ListArena kArena{4ull << 30, "KCSTAR_SLAB_MB", int64_t(1) << 24};  // the option is a test hook: a small budget splits a small graph into many launches
 
 template <bool FILL>
-int run_pass(const gmsx_graph *g, const StarPass1 &p1, int64_t *cnt, int64_t *mem, int32_t *out_cl, int64_t *out_soff, int32_t *out_star,
-             int64_t cl_cap, int64_t star_cap, unsigned long long *acc, int *launches) {
-    hipStream_t s = ctx().stream;
-    size_t free_b = 0, total_b = 0;
-    GMSX_HIP(hipMemGetInfo(&free_b, &total_b));
-    unsigned long long budget_words = std::min<unsigned long long>(free_b / 4, 4ull << 30) / 4;
-    const long long mb = opt_int("KCSTAR_SLAB_MB", 0);  // test hook: a small budget splits a small graph into many launches
-    if (mb >= 1) budget_words = std::min<unsigned long long>(budget_words, ((unsigned long long)mb << 20) / 4);
-    unsigned long long arena_words = 0;
-    const std::vector<Launch> plan = plan_launches(p1.soff, p1.n_tasks, std::max<unsigned long long>(budget_words, 4), &arena_words);
-    if (plan.empty()) return GMSX_OK;
-    DevBuf arena;
-    GMSX_HIP(hipMalloc(&arena.p, size_t(arena_words) * 4 + 64));
-    const int only = (p1.flags & GMSX_KCSTAR_CLIQUES_ONLY) ? 1 : 0;
-    for (const Launch &l : plan) {
+int run_pass(const gmsx_graph *g, const ListPass1 &p1, int k, uint32_t flags, int64_t *cnt, int64_t *mem, int32_t *out_cl, int64_t *out_soff,
+             int32_t *out_star, int64_t cl_cap, int64_t star_cap, unsigned long long *acc, int *launches) {
+    const int only = (flags & GMSX_KCSTAR_CLIQUES_ONLY) ? 1 : 0;
+    return run_list_pass(p1, kArena, FILL ? 2 : 0, launches, [&](const Launch &l, void *arena, unsigned long long arena_words) {
         const unsigned blocks = unsigned((l.t1 - l.t0 + kWavesPerBlock - 1) / kWavesPerBlock);
-        hipLaunchKernelGGL((k_kcstar_list<FILL>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, s, g->off, g->adj, g->newid,
-                           static_cast<const int32_t *>(p1.task_a.p), static_cast<const int32_t *>(p1.task_b.p),
-                           static_cast<const int64_t *>(p1.slab_off.p), l.t0, l.t1, static_cast<int32_t *>(arena.p), arena_words, p1.k, only, cnt, mem,
-                           static_cast<const int64_t *>(p1.cbase.p), static_cast<const int64_t *>(p1.mbase.p), out_cl, out_soff, out_star, cl_cap,
-                           star_cap, acc);
-        GMSX_HIP(hipGetLastError());
-        ++*launches;
-    }
-    GMSX_HIP(hipStreamSynchronize(s));
-    return GMSX_OK;
+        hipLaunchKernelGGL((k_kcstar_list<FILL>), dim3(blocks), dim3(64 * kWavesPerBlock), 0, ctx().stream, g->off, g->adj, g->newid,
+                           p1.task[0].as<const int32_t>(), p1.task[1].as<const int32_t>(), p1.slab_off.as<const int64_t>(), l.t0, l.t1,
+                           static_cast<int32_t *>(arena), arena_words, k, only, cnt, mem, p1.cbase.as<const int64_t>(), p1.mbase.as<const int64_t>(),
+                           out_cl, out_soff, out_star, cl_cap, star_cap, acc);
+    });
 }
 
-// pass 1 of (g, k, flags, part, nparts) into the cache
-int kcstar_pass1(const gmsx_graph *g, int k, uint32_t flags, int part, int nparts, double *ms, double *setup_ms, int *launches) {
-    StarPass1 &p1 = pass1_cache();
-    p1.clear();
-    Ctx &cx = ctx();
-    hipStream_t s = cx.stream;
+// pass 1 of (g, k, flags, part, nparts) into the cleared p1
+int kcstar_pass1(const gmsx_graph *g, int k, uint32_t flags, int part, int nparts, StarPass1 &p1, double *ms, double *setup_ms, int *launches) {
+    hipStream_t s = ctx().stream;
     const int64_t n = g->n, nnz = g->nnz;
     const auto h0 = std::chrono::steady_clock::now();
     // ---- task list: the shard's pivots by rank id (decreasing degree), each pivot's first members — its neighbours of a lower rank id — in
@@ -428,45 +344,21 @@ int kcstar_pass1(const gmsx_graph *g, int k, uint32_t flags, int part, int npart
             p1.soff.push_back(p1.soff.back() + need);
         }
     }
-    const int64_t nt = int64_t(task_a.size());
-    p1.n_tasks = nt;
-    p1.k = k;
-    p1.flags = flags;
-    GMSX_HIP(hipMalloc(&p1.task_a.p, size_t(nt > 0 ? nt : 1) * 4));
-    GMSX_HIP(hipMalloc(&p1.task_b.p, size_t(nt > 0 ? nt : 1) * 4));
-    GMSX_HIP(hipMalloc(&p1.slab_off.p, size_t(nt + 1) * 8));
-    GMSX_HIP(hipMalloc(&p1.cbase.p, size_t(nt + 1) * 8));
-    GMSX_HIP(hipMalloc(&p1.mbase.p, size_t(nt + 1) * 8));
-    if (nt > 0) {
-        GMSX_HIP(hipMemcpyAsync(p1.task_a.p, task_a.data(), size_t(nt) * 4, hipMemcpyHostToDevice, s));
-        GMSX_HIP(hipMemcpyAsync(p1.task_b.p, task_b.data(), size_t(nt) * 4, hipMemcpyHostToDevice, s));
-    }
-    GMSX_HIP(hipMemcpyAsync(p1.slab_off.p, p1.soff.data(), size_t(nt + 1) * 8, hipMemcpyHostToDevice, s));
+    const std::vector<int32_t> *tasks[] = {&task_a, &task_b};
+    if (int rc = upload_tasks(p1, tasks, 2, s)) return rc;
+    const int64_t nt = p1.n_tasks;
     DevBuf cnt, mem, acc;
-    GMSX_HIP(hipMalloc(&cnt.p, size_t(nt + 1) * 8));
-    GMSX_HIP(hipMalloc(&mem.p, size_t(nt + 1) * 8));
-    GMSX_HIP(hipMalloc(&acc.p, size_t(kAccWords) * 8));
-    GMSX_HIP(hipMemsetAsync(cnt.p, 0, size_t(nt + 1) * 8, s));
-    GMSX_HIP(hipMemsetAsync(mem.p, 0, size_t(nt + 1) * 8, s));
-    GMSX_HIP(hipMemsetAsync(acc.p, 0, size_t(kAccWords) * 8, s));
+    if (int rc = alloc_zeroed(cnt, size_t(nt + 1) * 8, s)) return rc;
+    if (int rc = alloc_zeroed(mem, size_t(nt + 1) * 8, s)) return rc;
+    if (int rc = alloc_zeroed(acc, size_t(kAccWords) * 8, s)) return rc;
     GMSX_HIP(hipStreamSynchronize(s));
     *setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
-    GMSX_HIP(hipEventRecord(cx.ev[0], s));
-    if (int rc = run_pass<false>(g, p1, static_cast<int64_t *>(cnt.p), static_cast<int64_t *>(mem.p), nullptr, nullptr, nullptr, 0, 0,
-                                 static_cast<unsigned long long *>(acc.p), launches))
+    if (int rc = run_pass<false>(g, p1, k, flags, cnt.as<int64_t>(), mem.as<int64_t>(), nullptr, nullptr, nullptr, 0, 0, acc.as<unsigned long long>(),
+                                 launches))
         return rc;
-    GMSX_HIP(hipEventRecord(cx.ev[1], s));
-    if (int rc = exclusive_scan_i64(static_cast<const int64_t *>(cnt.p), static_cast<int64_t *>(p1.cbase.p), nt + 1, s)) return rc;
-    if (int rc = exclusive_scan_i64(static_cast<const int64_t *>(mem.p), static_cast<int64_t *>(p1.mbase.p), nt + 1, s)) return rc;
     unsigned long long host[kAccWords];
     int64_t tot[2] = {0, 0};
-    GMSX_HIP(hipMemcpyAsync(host, acc.p, sizeof(host), hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipMemcpyAsync(&tot[0], static_cast<int64_t *>(p1.cbase.p) + nt, 8, hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipMemcpyAsync(&tot[1], static_cast<int64_t *>(p1.mbase.p) + nt, 8, hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipStreamSynchronize(s));
-    float f_ms = 0.f;
-    GMSX_HIP(hipEventElapsedTime(&f_ms, cx.ev[0], cx.ev[1]));
-    *ms = double(f_ms);
+    if (int rc = finish_count_pass(p1, cnt, mem, acc, host, kAccWords, tot, 0, ms)) return rc;
     if (host[kAccFlags]) return GMSX_ERR_KERNEL;
     gmsx_kclique_star_list_info info{};
     info.cliques = tot[0];
@@ -474,34 +366,20 @@ int kcstar_pass1(const gmsx_graph *g, int k, uint32_t flags, int part, int npart
     info.k = k;
     info.max_star = int32_t(host[kAccMax]);
     p1.info = info;
-    p1.g = g;
-    p1.off = g->off;
-    p1.adj = g->adj;
-    p1.n = g->n;
-    p1.nnz = g->nnz;
-    p1.part = part;
-    p1.nparts = nparts;
-    p1.valid = true;
     return GMSX_OK;
 }
 
 int kcstar_list(const gmsx_graph *g, int k, uint32_t flags, int part, int nparts, int32_t *cliques, int64_t *star_offsets, int32_t *star_members,
                 int64_t cliques_capacity, int64_t star_capacity, gmsx_kclique_star_list_info *info, gmsx_stats *st) {
-    Ctx &cx = ctx();
-    hipStream_t s = cx.stream;
+    hipStream_t s = ctx().stream;
     StarPass1 &p1 = pass1_cache();
     const bool only = (flags & GMSX_KCSTAR_CLIQUES_ONLY) != 0;
     const bool sizing = cliques == nullptr && star_offsets == nullptr && star_members == nullptr;
     double ms1 = 0.0, ms2 = 0.0, setup = 0.0;
     int launches = 0;
-    const bool hit = p1.valid && p1.g == g && p1.off == g->off && p1.adj == g->adj && p1.n == g->n && p1.nnz == g->nnz && p1.k == k &&
-                     p1.flags == flags && p1.part == part && p1.nparts == nparts;
-    if (!hit || sizing) {  // a sizing call always searches (it is what a caller times); a fill call re-uses its pass 1
-        if (int rc = kcstar_pass1(g, k, flags, part, nparts, &ms1, &setup, &launches)) {
-            p1.clear();
-            return rc;
-        }
-    }
+    if (int rc = ensure_pass1(p1, ListKey(g, part, nparts, k, flags), sizing,
+                              [&] { return kcstar_pass1(g, k, flags, part, nparts, p1, &ms1, &setup, &launches); }))
+        return rc;
     *info = p1.info;
     if (!sizing) {
         const int64_t nc = p1.info.cliques, nm = p1.info.star_members;
@@ -511,20 +389,13 @@ int kcstar_list(const gmsx_graph *g, int k, uint32_t flags, int part, int nparts
         GMSX_HIP(hipMalloc(&d_cl.p, size_t(nc > 0 ? nc : 1) * size_t(k) * 4));
         GMSX_HIP(hipMalloc(&d_soff.p, size_t(nc + 1) * 8));
         GMSX_HIP(hipMalloc(&d_star.p, size_t(nm > 0 ? nm : 1) * 4));
-        GMSX_HIP(hipMalloc(&acc.p, size_t(kAccWords) * 8));
-        GMSX_HIP(hipMemsetAsync(acc.p, 0, size_t(kAccWords) * 8, s));
-        GMSX_HIP(hipMemcpyAsync(static_cast<int64_t *>(d_soff.p) + nc, &nm, 8, hipMemcpyHostToDevice, s));
-        GMSX_HIP(hipEventRecord(cx.ev[2], s));
-        if (int rc = run_pass<true>(g, p1, nullptr, nullptr, static_cast<int32_t *>(d_cl.p), static_cast<int64_t *>(d_soff.p),
-                                    static_cast<int32_t *>(d_star.p), nc, nm, static_cast<unsigned long long *>(acc.p), &launches))
+        if (int rc = alloc_zeroed(acc, size_t(kAccWords) * 8, s)) return rc;
+        GMSX_HIP(hipMemcpyAsync(d_soff.as<int64_t>() + nc, &nm, 8, hipMemcpyHostToDevice, s));
+        if (int rc = run_pass<true>(g, p1, k, flags, nullptr, nullptr, d_cl.as<int32_t>(), d_soff.as<int64_t>(), d_star.as<int32_t>(), nc, nm,
+                                    acc.as<unsigned long long>(), &launches))
             return rc;
-        GMSX_HIP(hipEventRecord(cx.ev[3], s));
         unsigned long long host[kAccWords];
-        GMSX_HIP(hipMemcpyAsync(host, acc.p, sizeof(host), hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipStreamSynchronize(s));
-        float f_ms = 0.f;
-        GMSX_HIP(hipEventElapsedTime(&f_ms, cx.ev[2], cx.ev[3]));
-        ms2 = double(f_ms);
+        if (int rc = finish_fill_pass(acc, host, kAccWords, 2, &ms2)) return rc;
         if (host[kAccFlags]) return GMSX_ERR_KERNEL;
         // the caller's buffers are written only now, on success
         if (nc > 0) GMSX_HIP(hipMemcpyAsync(cliques, d_cl.p, size_t(nc) * size_t(k) * 4, hipMemcpyDeviceToHost, s));

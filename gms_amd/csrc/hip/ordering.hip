@@ -12,6 +12,7 @@
 // two integers go to the host, which evaluates the reference's double expression for the border bit for bit; one
 // select kernel that stamps the round into state[] and emits (deg << 32 | id) keys; a rocPRIM radix sort of the batch
 // (ties: vertex id — the reference leaves them to __gnu_parallel); one push kernel.
+#include "device_buffer.hpp"
 #include "device_graph.hpp"
 
 #include <algorithm>
@@ -23,21 +24,6 @@
 namespace gmsx {
 
 namespace {
-
-struct Dev {
-    void *p = nullptr;
-    ~Dev() { (void)hipFree(p); }
-    template <class T> T *as() { return static_cast<T *>(p); }
-};
-template <class T>
-int dalloc(Dev &d, int64_t count) {
-    if (hipMalloc(&d.p, size_t(std::max<int64_t>(count, 1)) * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        d.p = nullptr;
-        return GMSX_ERR_DEVICE_MEM;
-    }
-    return GMSX_OK;
-}
 
 __global__ void k_adg_init(int64_t n, const int64_t *__restrict__ off, int32_t *__restrict__ deg, int32_t *__restrict__ state) {
     const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -138,7 +124,7 @@ int gmsx_adg_rank(const gmsx_graph *g, double epsilon, int rank_format, int32_t 
         if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0};
         if (rounds_out) *rounds_out = 0;
         if (n == 0) return GMSX_OK;
-        Dev d_deg, d_state, d_keys, d_sorted, d_out, d_acc, d_tmp;
+        DevBuf d_deg, d_state, d_keys, d_sorted, d_out, d_acc, d_tmp;
         if (int rc = dalloc<int32_t>(d_deg, n)) return rc;
         if (int rc = dalloc<int32_t>(d_state, n)) return rc;
         if (int rc = dalloc<unsigned long long>(d_keys, n)) return rc;
@@ -204,7 +190,7 @@ int gmsx_tc_ordering(const gmsx_graph *g, int32_t *ordering, gmsx_stats *stats) 
         const int64_t n = g->n;
         if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0};
         if (n == 0) return GMSX_OK;
-        Dev d_counts, d_counts_sorted, d_ids, d_ids_sorted, d_tmp;
+        DevBuf d_counts, d_counts_sorted, d_ids, d_ids_sorted, d_tmp;
         if (int rc = dalloc<unsigned long long>(d_counts, n)) return rc;
         if (int rc = dalloc<unsigned long long>(d_counts_sorted, n)) return rc;
         if (int rc = dalloc<int32_t>(d_ids, n)) return rc;

@@ -9,11 +9,10 @@
 // longer row (wave-cooperative binary search; both rows are sorted), matches are counted with ballot + popcount.
 // This is the work-efficient form of the reference's two-pointer merge (Σ min(d_u,d_v)·log max(d_u,d_v) probes instead
 // of Σ (d_u+d_v) merge steps); rows stay in L2/MALL because CSR rows are re-used across the pairs of a hub.
+#include "device_buffer.hpp"
 #include "device_graph.hpp"
 
 #include <algorithm>
-
-#include <rocprim/device/device_scan.hpp>
 
 namespace gmsx {
 
@@ -223,9 +222,9 @@ static int run_edge_pairs(const gmsx_graph *g, int mode, int part, int nparts, u
                           gmsx_stats *st) {
     Ctx &c = ctx();
     hipStream_t s = c.stream;
-    unsigned long long *acc = nullptr;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&acc), sizeof(unsigned long long) * (64 * 16 + 1)));
-    struct Guard { void *p; ~Guard() { (void)hipFree(p); } } guard{acc};
+    DevBuf acc_buf;
+    GMSX_HIP(hipMalloc(&acc_buf.p, sizeof(unsigned long long) * (64 * 16 + 1)));
+    unsigned long long *acc = acc_buf.as<unsigned long long>();
     GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * (64 * 16 + 1), s));
     // contiguous entry ranges; entries are shuffled across hubs well enough by the row order for a first cut
     const int64_t first = g->nnz / nparts * part + std::min<int64_t>(part, g->nnz % nparts);
@@ -272,6 +271,30 @@ int tc_vertex_counts_device(const gmsx_graph *g, unsigned long long *d_counts, g
     return rc;
 }
 
+namespace {
+
+// What the pair-batch entry points start with (after allocating their outputs): u / v on the device, the flag word zeroed, ev[0] recorded;
+// blocks = the grid of a one-wave-per-pair kernel.
+struct PairBatch {
+    DevBuf u, v, flags;
+    int64_t blocks = 0;
+    int begin(int64_t n_pairs, const int32_t *hu, const int32_t *hv) {
+        Ctx &c = ctx();
+        hipStream_t s = c.stream;
+        GMSX_HIP(hipMalloc(&u.p, size_t(n_pairs) * 4));
+        GMSX_HIP(hipMalloc(&v.p, size_t(n_pairs) * 4));
+        GMSX_HIP(hipMalloc(&flags.p, 8));
+        GMSX_HIP(hipMemcpyAsync(u.p, hu, size_t(n_pairs) * 4, hipMemcpyHostToDevice, s));
+        GMSX_HIP(hipMemcpyAsync(v.p, hv, size_t(n_pairs) * 4, hipMemcpyHostToDevice, s));
+        GMSX_HIP(hipMemsetAsync(flags.p, 0, 8, s));
+        GMSX_HIP(hipEventRecord(c.ev[0], s));
+        blocks = std::min<int64_t>((n_pairs + 3) / 4, int64_t(c.compute_units > 0 ? c.compute_units : 256) * 32);
+        return GMSX_OK;
+    }
+};
+
+}  // namespace
+
 }  // namespace gmsx
 
 using namespace gmsx;
@@ -283,12 +306,11 @@ int gmsx_tc_vertex_count2(const gmsx_graph *g, int64_t *counts, gmsx_stats *stat
         if (!g || !counts) return GMSX_ERR_INVALID;
         if (int rc = ensure_init()) return rc;
         hipStream_t s = ctx().stream;
-        unsigned long long *d_counts = nullptr;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&d_counts), sizeof(unsigned long long) * size_t(std::max<int64_t>(g->n, 1))));
-        struct Guard { void *p; ~Guard() { (void)hipFree(p); } } guard{d_counts};
-        GMSX_HIP(hipMemsetAsync(d_counts, 0, sizeof(unsigned long long) * size_t(std::max<int64_t>(g->n, 1)), s));
-        if (int rc = tc_vertex_counts_device(g, d_counts, stats)) return rc;
-        if (g->n > 0) GMSX_HIP(hipMemcpy(counts, d_counts, sizeof(int64_t) * size_t(g->n), hipMemcpyDeviceToHost));
+        DevBuf d_counts;
+        GMSX_HIP(hipMalloc(&d_counts.p, sizeof(unsigned long long) * size_t(std::max<int64_t>(g->n, 1))));
+        GMSX_HIP(hipMemsetAsync(d_counts.p, 0, sizeof(unsigned long long) * size_t(std::max<int64_t>(g->n, 1)), s));
+        if (int rc = tc_vertex_counts_device(g, d_counts.as<unsigned long long>(), stats)) return rc;
+        if (g->n > 0) GMSX_HIP(hipMemcpy(counts, d_counts.p, sizeof(int64_t) * size_t(g->n), hipMemcpyDeviceToHost));
         return GMSX_OK;
     });
 }
@@ -305,25 +327,17 @@ int gmsx_vertex_similarity_batch(const gmsx_graph *g, int metric, int64_t n_pair
         }
         Ctx &c = ctx();
         hipStream_t s = c.stream;
-        int32_t *du = nullptr, *dv = nullptr;
-        double *dout = nullptr;
-        unsigned long long *flags = nullptr;
-        struct Guard { void *p = nullptr; ~Guard() { (void)hipFree(p); } } g1, g2, g3, g4;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&du), size_t(n_pairs) * 4)); g1.p = du;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&dv), size_t(n_pairs) * 4)); g2.p = dv;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&dout), size_t(n_pairs) * 8)); g3.p = dout;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&flags), 8)); g4.p = flags;
-        GMSX_HIP(hipMemcpyAsync(du, u, size_t(n_pairs) * 4, hipMemcpyHostToDevice, s));
-        GMSX_HIP(hipMemcpyAsync(dv, v, size_t(n_pairs) * 4, hipMemcpyHostToDevice, s));
-        GMSX_HIP(hipMemsetAsync(flags, 0, 8, s));
-        GMSX_HIP(hipEventRecord(c.ev[0], s));
-        const int64_t blocks = std::min<int64_t>((n_pairs + 3) / 4, int64_t(c.compute_units > 0 ? c.compute_units : 256) * 32);
-        hipLaunchKernelGGL(k_pair_similarity, dim3(unsigned(blocks)), dim3(256), 0, s, g->off, g->adj, g->n, metric, n_pairs, du, dv, dout, flags);
+        DevBuf dout;
+        PairBatch b;
+        GMSX_HIP(hipMalloc(&dout.p, size_t(n_pairs) * 8));
+        if (int rc = b.begin(n_pairs, u, v)) return rc;
+        hipLaunchKernelGGL(k_pair_similarity, dim3(unsigned(b.blocks)), dim3(256), 0, s, g->off, g->adj, g->n, metric, n_pairs, b.u.as<int32_t>(),
+                           b.v.as<int32_t>(), dout.as<double>(), b.flags.as<unsigned long long>());
         GMSX_HIP(hipEventRecord(c.ev[1], s));
         GMSX_HIP(hipGetLastError());
         unsigned long long bad = 0;
-        GMSX_HIP(hipMemcpyAsync(out, dout, size_t(n_pairs) * 8, hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipMemcpyAsync(&bad, flags, 8, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipMemcpyAsync(out, dout.p, size_t(n_pairs) * 8, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipMemcpyAsync(&bad, b.flags.p, 8, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
         if (stats) {
             float ms = 0.f;
@@ -345,25 +359,17 @@ int gmsx_intersect_count_batch(const gmsx_graph *g, int64_t n_pairs, const int32
         }
         Ctx &c = ctx();
         hipStream_t s = c.stream;
-        int32_t *du = nullptr, *dv = nullptr;
-        uint32_t *dout = nullptr;
-        unsigned long long *flags = nullptr;
-        struct Guard { void *p = nullptr; ~Guard() { (void)hipFree(p); } } g1, g2, g3, g4;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&du), size_t(n_pairs) * 4)); g1.p = du;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&dv), size_t(n_pairs) * 4)); g2.p = dv;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&dout), size_t(n_pairs) * 4)); g3.p = dout;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&flags), 8)); g4.p = flags;
-        GMSX_HIP(hipMemcpyAsync(du, u, size_t(n_pairs) * 4, hipMemcpyHostToDevice, s));
-        GMSX_HIP(hipMemcpyAsync(dv, v, size_t(n_pairs) * 4, hipMemcpyHostToDevice, s));
-        GMSX_HIP(hipMemsetAsync(flags, 0, 8, s));
-        GMSX_HIP(hipEventRecord(c.ev[0], s));
-        const int64_t blocks = std::min<int64_t>((n_pairs + 3) / 4, int64_t(c.compute_units > 0 ? c.compute_units : 256) * 32);
-        hipLaunchKernelGGL(k_pair_batch, dim3(unsigned(blocks)), dim3(256), 0, s, g->off, g->adj, g->n, n_pairs, du, dv, dout, flags);
+        DevBuf dout;
+        PairBatch b;
+        GMSX_HIP(hipMalloc(&dout.p, size_t(n_pairs) * 4));
+        if (int rc = b.begin(n_pairs, u, v)) return rc;
+        hipLaunchKernelGGL(k_pair_batch, dim3(unsigned(b.blocks)), dim3(256), 0, s, g->off, g->adj, g->n, n_pairs, b.u.as<int32_t>(), b.v.as<int32_t>(),
+                           dout.as<uint32_t>(), b.flags.as<unsigned long long>());
         GMSX_HIP(hipEventRecord(c.ev[1], s));
         GMSX_HIP(hipGetLastError());
         unsigned long long bad = 0;
-        GMSX_HIP(hipMemcpyAsync(out, dout, size_t(n_pairs) * 4, hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipMemcpyAsync(&bad, flags, 8, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipMemcpyAsync(out, dout.p, size_t(n_pairs) * 4, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipMemcpyAsync(&bad, b.flags.p, 8, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
         if (stats) {
             float ms = 0.f;
@@ -387,47 +393,37 @@ int gmsx_set_op_batch(const gmsx_graph *g, int op, int64_t n_pairs, const int32_
         }
         Ctx &c = ctx();
         hipStream_t s = c.stream;
-        int32_t *du = nullptr, *dv = nullptr, *dout = nullptr;
-        uint32_t *dcnt = nullptr;
-        int64_t *dsz = nullptr, *doff = nullptr;
-        unsigned long long *flags = nullptr;
-        void *tmp = nullptr;
-        struct Guard { void *p = nullptr; ~Guard() { (void)hipFree(p); } } g1, g2, g3, g4, g5, g6, g7, g8;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&du), size_t(n_pairs) * 4)); g1.p = du;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&dv), size_t(n_pairs) * 4)); g2.p = dv;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&dcnt), size_t(n_pairs) * 4)); g3.p = dcnt;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&dsz), size_t(n_pairs + 1) * 8)); g4.p = dsz;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&doff), size_t(n_pairs + 1) * 8)); g5.p = doff;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&flags), 8)); g6.p = flags;
-        GMSX_HIP(hipMemcpyAsync(du, u, size_t(n_pairs) * 4, hipMemcpyHostToDevice, s));
-        GMSX_HIP(hipMemcpyAsync(dv, v, size_t(n_pairs) * 4, hipMemcpyHostToDevice, s));
-        GMSX_HIP(hipMemsetAsync(flags, 0, 8, s));
-        GMSX_HIP(hipEventRecord(c.ev[0], s));
-        const int64_t blocks = std::min<int64_t>((n_pairs + 3) / 4, int64_t(c.compute_units > 0 ? c.compute_units : 256) * 32);
-        hipLaunchKernelGGL(k_pair_batch, dim3(unsigned(blocks)), dim3(256), 0, s, g->off, g->adj, g->n, n_pairs, du, dv, dcnt, flags);
-        hipLaunchKernelGGL(k_pair_sizes, dim3(unsigned(n_pairs / 256 + 1)), dim3(256), 0, s, g->off, g->n, n_pairs, du, dv, dcnt, op == GMSX_SETOP_DIFFERENCE ? 1 : 0, dsz);
-        size_t tb = 0;
-        GMSX_HIP(rocprim::exclusive_scan(nullptr, tb, dsz, doff, int64_t(0), size_t(n_pairs + 1), rocprim::plus<int64_t>(), s));
-        GMSX_HIP(hipMalloc(&tmp, tb ? tb : 8)); g7.p = tmp;
-        GMSX_HIP(rocprim::exclusive_scan(tmp, tb, dsz, doff, int64_t(0), size_t(n_pairs + 1), rocprim::plus<int64_t>(), s));
+        DevBuf dcnt, dsz, doff, dout;
+        PairBatch b;
+        GMSX_HIP(hipMalloc(&dcnt.p, size_t(n_pairs) * 4));
+        GMSX_HIP(hipMalloc(&dsz.p, size_t(n_pairs + 1) * 8));
+        GMSX_HIP(hipMalloc(&doff.p, size_t(n_pairs + 1) * 8));
+        if (int rc = b.begin(n_pairs, u, v)) return rc;
+        const int32_t *du = b.u.as<int32_t>(), *dv = b.v.as<int32_t>();
+        const int64_t blocks = b.blocks;
+        hipLaunchKernelGGL(k_pair_batch, dim3(unsigned(blocks)), dim3(256), 0, s, g->off, g->adj, g->n, n_pairs, du, dv, dcnt.as<uint32_t>(),
+                           b.flags.as<unsigned long long>());
+        hipLaunchKernelGGL(k_pair_sizes, dim3(unsigned(n_pairs / 256 + 1)), dim3(256), 0, s, g->off, g->n, n_pairs, du, dv, dcnt.as<const uint32_t>(),
+                           op == GMSX_SETOP_DIFFERENCE ? 1 : 0, dsz.as<int64_t>());
+        if (int rc = exclusive_scan_i64(dsz.as<const int64_t>(), doff.as<int64_t>(), n_pairs + 1, s)) return rc;
         unsigned long long bad = 0;
-        GMSX_HIP(hipMemcpyAsync(out_offsets, doff, size_t(n_pairs + 1) * 8, hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipMemcpyAsync(&bad, flags, 8, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipMemcpyAsync(out_offsets, doff.p, size_t(n_pairs + 1) * 8, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipMemcpyAsync(&bad, b.flags.p, 8, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
         if (bad) return GMSX_ERR_INVALID;  // a vertex id outside [0, n)
         const int64_t total = out_offsets[n_pairs];
         int launches = 3;
         if (out_ids && total > out_capacity) return GMSX_ERR_INVALID;  // the offsets say how much room the result needs
         if (out_ids && total > 0) {
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&dout), size_t(total) * 4)); g8.p = dout;
+            GMSX_HIP(hipMalloc(&dout.p, size_t(total) * 4));
             if (op == GMSX_SETOP_DIFFERENCE)
-                hipLaunchKernelGGL(k_pair_fill<true>, dim3(unsigned(blocks)), dim3(256), 0, s, g->off, g->adj, g->n, n_pairs, du, dv, doff, dout);
+                hipLaunchKernelGGL(k_pair_fill<true>, dim3(unsigned(blocks)), dim3(256), 0, s, g->off, g->adj, g->n, n_pairs, du, dv, doff.as<const int64_t>(), dout.as<int32_t>());
             else
-                hipLaunchKernelGGL(k_pair_fill<false>, dim3(unsigned(blocks)), dim3(256), 0, s, g->off, g->adj, g->n, n_pairs, du, dv, doff, dout);
+                hipLaunchKernelGGL(k_pair_fill<false>, dim3(unsigned(blocks)), dim3(256), 0, s, g->off, g->adj, g->n, n_pairs, du, dv, doff.as<const int64_t>(), dout.as<int32_t>());
             ++launches;
             GMSX_HIP(hipEventRecord(c.ev[1], s));
             GMSX_HIP(hipGetLastError());
-            GMSX_HIP(hipMemcpyAsync(out_ids, dout, size_t(total) * 4, hipMemcpyDeviceToHost, s));
+            GMSX_HIP(hipMemcpyAsync(out_ids, dout.p, size_t(total) * 4, hipMemcpyDeviceToHost, s));
             GMSX_HIP(hipStreamSynchronize(s));
         } else {
             GMSX_HIP(hipEventRecord(c.ev[1], s));

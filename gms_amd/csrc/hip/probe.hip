@@ -2,6 +2,7 @@
 // against (`frac_of_measured_stream_ceiling`), next to the 8 TB/s specification peak.  A buffer far larger than the 256 MB Infinity Cache is read
 // with 16-byte loads, four independent ones in flight per lane, in the in-order sweep of a grid-stride loop (the access pattern of the counting
 // kernels' row streams at their best); the time is taken with HIP events on the library's stream.  Diagnostic only: no reference counterpart.
+#include "device_buffer.hpp"
 #include "device_graph.hpp"
 
 namespace gmsx {
@@ -35,19 +36,18 @@ extern "C" int gmsx_hbm_read_probe(int64_t bytes, int iterations, double *gbps) 
         Ctx &c = ctx();
         hipStream_t s = c.stream;
         const int64_t n16 = bytes / 16;
-        uint4 *buf = nullptr;
-        unsigned long long *sink = nullptr;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&buf), size_t(n16) * 16));
-        struct Free { void *p; ~Free() { (void)hipFree(p); } } f0{buf};
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&sink), 8));
-        Free f1{sink};
-        GMSX_HIP(hipMemsetAsync(buf, 0, size_t(n16) * 16, s));
+        DevBuf d_buf, d_sink;
+        GMSX_HIP(hipMalloc(&d_buf.p, size_t(n16) * 16));
+        GMSX_HIP(hipMalloc(&d_sink.p, 8));
+        const u32x4 *buf = d_buf.as<const u32x4>();
+        unsigned long long *sink = d_sink.as<unsigned long long>();
+        GMSX_HIP(hipMemsetAsync(d_buf.p, 0, size_t(n16) * 16, s));
         GMSX_HIP(hipMemsetAsync(sink, 0, 8, s));
         const int cus = c.compute_units > 0 ? c.compute_units : 256;
         const dim3 grid(unsigned(cus * 4)), block(512);  // 2048 lanes per CU = every wave slot, four 16-byte loads each in flight
-        hipLaunchKernelGGL(k_read_probe, grid, block, 0, s, reinterpret_cast<const u32x4 *>(buf), n16, sink);  // warm-up (code object, TLB)
+        hipLaunchKernelGGL(k_read_probe, grid, block, 0, s, buf, n16, sink);  // warm-up (code object, TLB)
         GMSX_HIP(hipEventRecord(c.ev[0], s));
-        for (int it = 0; it < iterations; ++it) hipLaunchKernelGGL(k_read_probe, grid, block, 0, s, reinterpret_cast<const u32x4 *>(buf), n16, sink);
+        for (int it = 0; it < iterations; ++it) hipLaunchKernelGGL(k_read_probe, grid, block, 0, s, buf, n16, sink);
         GMSX_HIP(hipEventRecord(c.ev[1], s));
         GMSX_HIP(hipEventSynchronize(c.ev[1]));
         GMSX_HIP(hipGetLastError());
