@@ -39,6 +39,7 @@ SYMBOLS = [
     "gmsx_tc_total", "gmsx_tc_partial", "gmsx_tc_divisor", "gmsx_tc_stream_breakdown", "gmsx_tc_row_histogram", "gmsx_tc_comembership", "gmsx_tc_vertex_count2",
     "gmsx_intersect_count_batch", "gmsx_set_op_batch", "gmsx_vertex_similarity_batch", "gmsx_kclique_count", "gmsx_kclique_partial", "gmsx_kclique_star_count", "gmsx_kclique_star_list", "gmsx_bk_count", "gmsx_bk_partial", "gmsx_bk_list",
     "gmsx_adg_rank", "gmsx_tc_ordering", "gmsx_core_decomposition", "gmsx_degree_rank", "gmsx_order_quality",
+    "gmsx_link_prediction", "gmsx_link_prediction_precision",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
 
@@ -86,6 +87,27 @@ class OrderQualityInfo(C.Structure):
         d = {k: int(getattr(self, k)) for k in ("max_later", "core_number", "core_number_of_order", "faulty", "excess")}
         d.update({k: float(getattr(self, k)) for k in ("relative_error", "fault_rate", "relative_mean_difference")})
         return d
+
+
+class LinkPredictionInfo(C.Structure):
+    _fields_ = [("found", C.c_int64), ("scored", C.c_int64), ("positive", C.c_int64), ("chunks", C.c_int32), ("classes", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("found", "scored", "positive", "chunks", "classes")}
+
+
+LP_CLASS_ONE, LP_CLASS_POS, LP_CLASS_ZERO, LP_CLASS_ALL = 1, 2, 4, 8
+SIM_METRICS = {"jaccard": 0, "overlap": 1, "adamic_adar": 2, "resource": 3, "common": 4, "total": 5, "prefatt": 6}
+
+
+def merge_link_predictions(parts, q):
+    """Merges link_prediction outputs (u, v, scores[, info]) of the shards of one (graph, metric, q) under the rule of gmsx.h — decreasing
+    score, ties by ascending (u, v) — truncates to q and returns (u, v, scores) worst first: the whole graph's output, byte for byte."""
+    u = np.concatenate([np.asarray(p[0], dtype=np.int32) for p in parts]) if parts else np.zeros(0, np.int32)
+    v = np.concatenate([np.asarray(p[1], dtype=np.int32) for p in parts]) if parts else np.zeros(0, np.int32)
+    s = np.concatenate([np.asarray(p[2], dtype=np.float64) for p in parts]) if parts else np.zeros(0, np.float64)
+    order = np.lexsort((v, u, -s))[:max(int(q), 0)][::-1]
+    return u[order], v[order], s[order]
 
 
 class GmsxError(RuntimeError):
@@ -170,6 +192,10 @@ def lib():
     L.gmsx_core_decomposition.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CoreInfo), sp]
     L.gmsx_degree_rank.argtypes = [vp, C.c_int, _i32p, sp]
     L.gmsx_order_quality.argtypes = [vp, C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.POINTER(OrderQualityInfo), sp]
+    L.gmsx_link_prediction.argtypes = [vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                       C.POINTER(LinkPredictionInfo), sp]
+    L.gmsx_link_prediction_precision.argtypes = [vp, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_double), sp]
     L.gmsx_comm_unique_id.argtypes = [C.c_char_p]
     L.gmsx_comm_init.argtypes = [C.c_int, C.c_int, C.c_char_p, vpp]
     L.gmsx_comm_allreduce_u64.argtypes = [vp, u64p]
@@ -607,6 +633,35 @@ class DeviceGraph:
         if stats:
             r = r + (st.as_dict(),)
         return r if len(r) > 1 else r[0]
+
+    def link_prediction(self, metric, q, part=0, nparts=1, stats=False):
+        """gmsx_link_prediction: the q best-scoring non-edges under `metric` (a SIM_* value or one of SIM_METRICS' names), worst first:
+        (u int32[found], v int32[found], scores float64[found], info dict)."""
+        metric = SIM_METRICS.get(metric, metric) if isinstance(metric, str) else int(metric)
+        q = int(q)
+        if q > (1 << 27):  # the library's limit (gmsx.h): refused here, before q slots are allocated for nothing
+            raise GmsxError(ERR_UNSUPPORTED, "gmsx_link_prediction (q > 2^27)")
+        cap = max(q, 1)  # (q < 1 is refused by the library)
+        u, v, sc = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.float64)
+        info, st = LinkPredictionInfo(), Stats()
+        _check(lib().gmsx_link_prediction(self._h, metric, q, int(part), int(nparts), u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p),
+                                          sc.ctypes.data_as(C.c_void_p), cap, C.byref(info), C.byref(st)), "gmsx_link_prediction")
+        f = int(info.found)
+        r = (u[:f].copy(), v[:f].copy(), sc[:f].copy(), info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def link_prediction_precision(self, u, v, stats=False):
+        """gmsx_link_prediction_precision with this graph as g_test: {true_positives, true_count, precision, recall} of the predicted list."""
+        u, v = np.ascontiguousarray(u, dtype=np.int32), np.ascontiguousarray(v, dtype=np.int32)
+        if u.size != v.size:
+            raise GmsxError(ERR_INVALID, "gmsx_link_prediction_precision (u and v must have the same length)")
+        tp, tc, pr, rc, st = C.c_int64(0), C.c_int64(0), C.c_double(0.0), C.c_double(0.0), Stats()
+        pu = u.ctypes.data_as(C.c_void_p) if u.size else None
+        pv = v.ctypes.data_as(C.c_void_p) if v.size else None
+        _check(lib().gmsx_link_prediction_precision(self._h, int(u.size), pu, pv, C.byref(tp), C.byref(tc), C.byref(pr), C.byref(rc), C.byref(st)),
+               "gmsx_link_prediction_precision")
+        r = {"true_positives": int(tp.value), "true_count": int(tc.value), "precision": float(pr.value), "recall": float(rc.value)}
+        return (r, st.as_dict()) if stats else r
 
     def free(self):
         if getattr(self, "_h", None):

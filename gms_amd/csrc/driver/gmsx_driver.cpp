@@ -15,6 +15,10 @@
 // Added:  bk --list FILE   the maximal cliques of the last trial (gmsx_bk_list, outside the timed trial), one per line, members ascending.
 // Added:  bk --order adg|deg|dgr   which preprocessor the timed "Preprocess Time" runs and hands its rank to the search: gmsx_adg_rank (default; BK-GMS-ADG),
 //                    gmsx_degree_rank (BK-GMS-DEG) or the exact degeneracy order of gmsx_core_decomposition (BK-GMS-DGR).  The count does not depend on it.
+// Added:  lp --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N [--list FILE]   GMS::LinkPrediction::link_prediction_similarity<Metric>
+//                    (set_based/link_prediction/link_prediction.h:42-101) on the device (gmsx_link_prediction): the N best-scoring non-edges; N defaults to m / 4, the
+//                    choice of the reference's bench_ranking (link_prediction.cc:36).  --list writes the result of the last trial in the reference's shape, padding
+//                    included, one "u v score" line per entry, worst first, the score as a hex float.  Not sharded (--gpus > 1 is refused).
 // Added:  kcstar -p clique-size=k [--list FILE]   KCliqueStar::Par::CliqueStarList (k_clique_star_list/parallel/recursive.h:19-43) on the device: prints the
 //                    reference's "total k-cliques: N" line (:34, N = the number of pairs); --list writes the pairs of the last trial (gmsx_kclique_star_list, outside
 //                    the timed trial), one per line: "c1 … ck | s1 …", clique and star ascending.  Not sharded (--gpus > 1 is refused).
@@ -49,6 +53,8 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     int clique_size = 4;
     int gpus = 0;  // 0 = single process without a communicator
     std::string list;  // bk --list FILE: the maximal cliques of the last trial, one per line (gmsx_bk_list)
+    std::string metric = "jaccard";  // lp --metric
+    int64_t q = 0;     // lp -q N (0: m / 4)
     std::string order; // bk --order adg|deg|dgr: the preprocessing step in front of the search (default adg)
     int error = 0;
 };
@@ -61,6 +67,13 @@ struct Timer {  // gapbs/timer.h:18-47
 };
 void PrintTime(const std::string &s, double sec) { std::printf("%-21s%3.5lf\n", (s + ":").c_str(), sec); }          // gapbs/util.h:31-33
 void PrintLabel(const std::string &l, const std::string &v) { std::printf("%-21s%7s\n", (l + ":").c_str(), v.c_str()); }  // util.h:27-29
+
+int lp_metric(const std::string &name) {
+    static const char *names[] = {"jaccard", "overlap", "adamic_adar", "resource", "common", "total", "prefatt"};  // the GMSX_SIM_* order
+    for (int i = 0; i < 7; ++i)
+        if (name == names[i]) return i;
+    return -1;
+}
 
 Args parse(int argc, char **argv) {
     Args a;
@@ -76,6 +89,8 @@ Args parse(int argc, char **argv) {
         else if (f == "-g" || f == "--gen") { if (!need(2)) break; a.gen = argv[++i]; a.scale = std::atoi(argv[++i]); }
         else if (f == "--deg") { if (!need(1)) break; a.deg = std::atoi(argv[++i]); }
         else if (f == "--list") { if (!need(1)) break; a.list = argv[++i]; }
+        else if (f == "--metric") { if (!need(1)) break; a.metric = argv[++i]; }
+        else if (f == "-q") { if (!need(1)) break; a.q = std::atoll(argv[++i]); if (a.q < 1) a.error = 100; }
         else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; if (a.order != "adg" && a.order != "deg" && a.order != "dgr") a.error = 100; }
         else if (f == "--gpus") { if (!need(1)) break; a.gpus = std::atoi(argv[++i]); if (a.gpus < 1 || a.gpus > 64) a.error = 100; }
         else if (f == "--opt") {  // --opt NAME=VALUE -> gmsx_set_option (limits, kernel variants, diagnostics: include/gmsx.h); unknown names are refused
@@ -96,15 +111,17 @@ Args parse(int argc, char **argv) {
     }
     if (!a.error && a.file.empty() && a.gen.empty()) a.error = 101;  // cli/cli.h:131-133
     if (!a.error && !a.gen.empty() && a.gen != "kronecker" && a.gen != "uniform") a.error = 100;
-    if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
-    if (!a.error && a.kernel == "kcstar" && a.gpus > 1) a.error = 100;
+    if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
+    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp") && a.gpus > 1) a.error = 100;
+    if (!a.error && a.kernel == "lp" && lp_metric(a.metric) < 0) a.error = 100;
     if (!a.error && !a.order.empty() && a.kernel != "bk") a.error = 100;  // only Bron–Kerbosch has a preprocessing step
     return a;
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
-                "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr]\n", argv0);
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+                "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
+                "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -339,7 +356,7 @@ int launch_ranks(int gpus) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -419,6 +436,7 @@ int main(int argc, char **argv) {
         uint64_t result = 0;
         std::vector<int64_t> counts;
         std::vector<int32_t> order;
+        gmsx::ScoredEdges lp_result;
         double pp_time = -1;
         if (args.kernel == "bk") {  // BenchmarkKernelBkPP: preprocess(rgraph, order) per trial (common/benchmark.h:163-170)
             t.Start();
@@ -446,6 +464,12 @@ int main(int argc, char **argv) {
             result = reduce(part) * fact;  // the reference's value k!·C_k, mod 2^64 like size_t
             std::printf("total %d-cliques: %" PRIu64 "\n", args.clique_size, result);  // k_clique_count_set_based.h:29
             label = "HipSet HipSetGraph";
+        } else if (args.kernel == "lp") {
+            const int64_t q = args.q > 0 ? args.q : std::max<int64_t>(1, m / 4);
+            lp_result = gmsx::link_prediction(g, lp_metric(args.metric), q);
+            result = uint64_t(lp_result.found);
+            std::printf("predicted links: %" PRIu64 " of %" PRId64 " requested (%s)\n", result, q, args.metric.c_str());
+            label = "link-prediction-HipSetGraph";
         } else if (args.kernel == "kcstar") {  // the timed kernel is the listing's sizing pass: every pair is found, none is copied out
             gmsx_kclique_star_list_info info{};
             gmsx::detail::check(gmsx_kclique_star_list(g.device(), args.clique_size, GMSX_KCSTAR_DEFAULT, 0, 1, nullptr, nullptr, nullptr, 0, 0, &info, nullptr),
@@ -480,6 +504,16 @@ int main(int argc, char **argv) {
                 }
                 std::fputc('\n', fo);
             }
+            if (std::fclose(fo) != 0) return 2;
+        }
+        if (args.kernel == "lp" && !args.list.empty() && it + 1 == args.trials) {  // the reference's shape, padding included, worst first
+            FILE *fo = std::fopen(args.list.c_str(), "w");
+            if (!fo) {
+                std::fprintf(stderr, "gmsx_driver: --list %s: cannot open\n", args.list.c_str());
+                return 2;
+            }
+            for (size_t i = 0; i < lp_result.scores.size(); ++i)
+                std::fprintf(fo, "%d %d %a\n", int(lp_result.edges[i].first), int(lp_result.edges[i].second), lp_result.scores[i]);
             if (std::fclose(fo) != 0) return 2;
         }
         if (args.kernel == "kcstar" && !args.list.empty() && it + 1 == args.trials) {  // outside the timed trial: the pairs themselves
@@ -533,6 +567,13 @@ int main(int argc, char **argv) {
                     ok = ok && sum * fact == result;
                     how = "three-shard device recount (graph beyond the host-recount limit)";
                 }
+            } else if (args.kernel == "lp") {  // a different decomposition of the device run: three shards merged under the rule must give the same entries
+                const int64_t q = args.q > 0 ? args.q : std::max<int64_t>(1, m / 4);
+                std::vector<gmsx::ScoredEdges> parts;
+                for (int p = 0; p < 3; ++p) parts.push_back(gmsx::link_prediction_shard(g, lp_metric(args.metric), q, p, 3));
+                const gmsx::ScoredEdges merged = gmsx::merge_link_predictions(parts, q);
+                ok = merged.edges == lp_result.edges && merged.scores == lp_result.scores;
+                how = "three-shard device recount, merged";
             } else if (args.kernel == "kcstar") {  // the number of pairs is C_k: the count kernels, a different formulation
                 uint64_t stars = 0;
                 ok = gmsx_kclique_star_count(g.device(), args.clique_size, &stars, nullptr, nullptr) == GMSX_OK && stars == result;

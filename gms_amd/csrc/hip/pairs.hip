@@ -11,35 +11,11 @@
 // of Σ (d_u+d_v) merge steps); rows stay in L2/MALL because CSR rows are re-used across the pairs of a hub.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
+#include "pair_similarity.hpp"  // wave_intersect_count, wave_pair_similarity
 
 #include <algorithm>
 
 namespace gmsx {
-
-// |A ∩ B| for two ascending rows; wave-uniform arguments; returns the wave-uniform count
-__device__ __forceinline__ uint32_t wave_intersect_count(const int32_t *__restrict__ a, int64_t la, const int32_t *__restrict__ b,
-                                                         int64_t lb, int lane) {
-    if (la > lb) {  // stream the shorter, search the longer
-        const int32_t *t = a; a = b; b = t;
-        const int64_t tl = la; la = lb; lb = tl;
-    }
-    uint32_t cnt = 0;
-    for (int64_t base = 0; base < la; base += 64) {
-        const int64_t i = base + lane;
-        bool hit = false;
-        if (i < la) {
-            const int32_t x = a[i];
-            int64_t lo = 0, hi = lb;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (b[mid] < x) lo = mid + 1; else hi = mid;
-            }
-            hit = lo < lb && b[lo] == x;
-        }
-        cnt += uint32_t(__popcll(__ballot(hit)));
-    }
-    return cnt;
-}
 
 // out[i] = |N(u[i]) ∩ N(v[i])|
 __global__ __launch_bounds__(256) void k_pair_batch(const int64_t *__restrict__ off, const int32_t *__restrict__ adj, int64_t n,
@@ -118,8 +94,7 @@ __global__ void k_pair_sizes(const int64_t *__restrict__ off, int64_t n, int64_t
     sizes[p] = !ok ? 0 : diff ? (off[u + 1] - off[u]) - int64_t(cnt[p]) : int64_t(cnt[p]);
 }
 
-// Vertex similarity (vertex_similarity/vertex_similarity.h:30-222): one wave per pair.  Count-based metrics reuse
-// wave_intersect_count; Adamic-Adar / resource allocation add a per-common-neighbour term while intersecting.
+// Vertex similarity (vertex_similarity/vertex_similarity.h:30-222): one wave per pair, the score itself in pair_similarity.hpp.
 __global__ __launch_bounds__(256) void k_pair_similarity(const int64_t *__restrict__ off, const int32_t *__restrict__ adj, int64_t n,
                                                          int metric, int64_t n_pairs, const int32_t *__restrict__ pu,
                                                          const int32_t *__restrict__ pv, double *__restrict__ out,
@@ -136,43 +111,7 @@ __global__ __launch_bounds__(256) void k_pair_similarity(const int64_t *__restri
             }
             continue;
         }
-        const int32_t *a = adj + off[u], *b = adj + off[v];
-        int64_t la = off[u + 1] - off[u], lb = off[v + 1] - off[v];
-        const double ca = double(la), cb = double(lb);
-        double r;
-        if (metric == GMSX_SIM_ADAMIC_ADAR || metric == GMSX_SIM_RESOURCE) {
-            if (la > lb) {
-                const int32_t *t = a; a = b; b = t;
-                const int64_t tl = la; la = lb; lb = tl;
-            }
-            double sum = 0.0;
-            for (int64_t base = 0; base < la; base += 64) {
-                const int64_t i = base + lane;
-                if (i < la) {
-                    const int32_t x = a[i];
-                    int64_t lo = 0, hi = lb;
-                    while (lo < hi) {
-                        const int64_t mid = (lo + hi) >> 1;
-                        if (b[mid] < x) lo = mid + 1; else hi = mid;
-                    }
-                    if (lo < lb && b[lo] == x) {
-                        const double deg = double(off[x + 1] - off[x]);
-                        sum += metric == GMSX_SIM_ADAMIC_ADAR ? 1.0 / log(deg) : 1.0 / deg;
-                    }
-                }
-            }
-            for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s);
-            r = sum;
-        } else {
-            const double cnt = double(wave_intersect_count(a, la, b, lb, lane));
-            switch (metric) {
-                case GMSX_SIM_JACCARD: r = (la == 0 && lb == 0) ? 1.0 : cnt / (ca + cb + cnt); break;   // sic, vertex_similarity.h:31-36
-                case GMSX_SIM_OVERLAP: r = cnt / (ca < cb ? ca : cb); break;                              // :66-68
-                case GMSX_SIM_COMMON_NEIGHBORS: r = cnt; break;                                           // :139-143
-                case GMSX_SIM_TOTAL_NEIGHBORS: r = ca + cb - cnt; break;                                  // union_count, :155-159
-                default: r = ca * cb; break;                                                              // :171-174
-            }
-        }
+        const double r = wave_pair_similarity(off, adj, metric, u, v, lane);
         if (lane == 0) out[p] = r;
     }
 }

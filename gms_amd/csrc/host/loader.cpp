@@ -778,6 +778,8 @@ Option g_options[] = {
     {"KCSTAR_SLAB_MB", "", false},
     // core decomposition (core.hip)
     {"CORE_WG_FRONTIER", "", false},
+    // link prediction (linkpred.hip)
+    {"LP_LDS_MAXN", "", false}, {"LP_SLAB_MB", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

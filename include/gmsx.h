@@ -141,7 +141,10 @@ int gmsx_set_host_threads(int n);
  *   Bron–Kerbosch listing  BK_LIST_ARENA_MB (budget of the search slabs of one launch: smaller = more launches)
  *   k-clique-star listing  KCSTAR_SLAB_MB (budget of the level-set slabs of one launch: smaller = more launches)
  *   core decomposition     CORE_WG_FRONTIER (largest frontier whose rounds run inside the one-workgroup kernel, default 512 — a first guess, not a
- *                   tuned value; 0 = every round is a kernel boundary; test hook) */
+ *                   tuned value; 0 = every round is a kernel boundary; test hook)
+ *   link prediction        LP_LDS_MAXN (largest n whose per-source bitmaps live in LDS, default and maximum 131072 — a first guess; 0 = every
+ *                   bitmap in the workgroup's global slab; test hook), LP_SLAB_MB (budget of the candidates of one chunk: smaller = more chunks;
+ *                   test hook) */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -460,6 +463,52 @@ int gmsx_order_quality(const gmsx_graph *g, const int32_t *ordering /* n, host *
                        int32_t core_number /* < 0: computed here by the peel of gmsx_core_decomposition */,
                        int32_t *later /* n, host, or NULL: per-vertex count of neighbours after v */,
                        gmsx_order_quality_info *info /* required */, gmsx_stats *stats);
+
+/* ---- link prediction: GMS::LinkPrediction::link_prediction_similarity<Metric> (set_based/link_prediction/link_prediction.h:42-101), the q
+ * best-scoring NON-edges of the graph under one of the GMSX_SIM_* metrics, and the precision / recall step of the reference's bench_ranking
+ * (link_prediction.cc:30-49).  The reference walks all pairs u < v in lexicographic order, skips edges and inserts each score into an ascending
+ * array of q slots with a strict `>`; that is exactly this rule:
+ *   candidates  the non-edges u < v whose score is not NaN (Overlap is 0/0 when an endpoint is isolated, vertex_similarity.h:64-66: never inserted)
+ *   order       decreasing score, ties by ascending (u, v)
+ *   result      the first min(q, candidates) of that order, returned in REVERSE: index 0 is the worst entry kept, the last index the best.
+ * Scores are those of gmsx_vertex_similarity_batch, bit for bit (one device function computes both), including the reference's Jaccard
+ * c/(|A|+|B|+c), which is 1.0 when both rows are empty.  u, v, scores (host, `capacity` entries each) receive info->found = min(q, candidates)
+ * entries; one call does everything, there is no sizing call.  The reference leaves q - found leading entries (-1.0, edge (0,0)) when fewer than
+ * q candidates exist and returns exactly one such entry when none does: the C call returns the real entries only, gmsx::link_prediction
+ * (gmsx_set_graph.hpp) reproduces the padding.
+ * Classes: for Jaccard, Overlap, Adamic-Adar, Resource and CommonNeighbors a non-edge is ONE (Jaccard only: both endpoints isolated, 1.0), POS (at
+ * least one common neighbour, score > 0; every such Jaccard score is <= 1/3) or ZERO (no common neighbour, exactly 0.0; Overlap: both endpoints
+ * non-isolated); the order is ONE, POS, ZERO, and inside ONE and ZERO purely lexicographic.  Only POS pairs — found by two-hop marking per
+ * source vertex — are scored and sorted; ZERO is generated in order, chunk by chunk, until q is reached.  TotalNeighbors and PrefAttachment rank
+ * every non-edge (one class, ALL).
+ * Cost: the ALL class, and a ZERO fill that cannot stop early (q above the POS pairs plus most ZERO pairs), cost O(n^2) scores / pairs, as the
+ * reference does; the ALL class returns GMSX_ERR_UNSUPPORTED for n > 131072.  q > 2^27 returns GMSX_ERR_UNSUPPORTED.
+ * Shards: a shard owns the sources u with u mod nparts == part; (0, 1) is the whole graph.  Merging the shards' outputs under the rule and
+ * truncating to q gives the whole graph's output byte for byte (capi.merge_link_predictions, gmsx::merge_link_predictions).
+ * The same graph, metric, q and shard give byte-identical arrays in every process: the arrival order of atomics reaches no output (the
+ * two-hop bitmaps are set by idempotent ORs, candidates leave them in ascending v, and equal scores are ordered by one STABLE sort).
+ * Errors: q < 1, an unknown metric, a NULL g, info or output array, capacity < min(q, 2^62), part / nparts outside 0 <= part < nparts →
+ * GMSX_ERR_INVALID, nothing written.  A bounds violation or a fill that disagrees with its count pass → GMSX_ERR_KERNEL; nothing is written
+ * out of bounds and the caller's arrays are written only after the device flag word was read as zero.  n = 0 or 1: GMSX_OK, found = 0.
+ * Test hooks: options LP_LDS_MAXN, LP_SLAB_MB.  gmsx_stats: kernel_ms (the device span of the call), launches, units = scored. */
+typedef struct {
+    int64_t found;        /* entries written: min(q, candidates) */
+    int64_t scored;       /* pairs whose score was computed */
+    int64_t positive;     /* POS pairs of this shard (five common-neighbour metrics); -1 where the ALL class ran */
+    int32_t chunks;       /* launches-of-sources the call was cut into: the POS / ALL and ZERO chunks that were filled (0 when ONE alone filled q) */
+    int32_t classes;      /* bit 0 ONE, 1 POS, 2 ZERO, 3 ALL: which classes contributed to the output */
+} gmsx_link_prediction_info;
+int gmsx_link_prediction(const gmsx_graph *g, int metric /* GMSX_SIM_* */, int64_t q, int part, int nparts,
+                         int32_t *u /* capacity */, int32_t *v /* capacity */, double *scores /* capacity */,
+                         int64_t capacity, gmsx_link_prediction_info *info /* required */, gmsx_stats *stats);
+/* score_link_prediction_precision (evaluation.h:99-124): g_test's undirected edges against a predicted list u[i], v[i] (host, n_pred entries).
+ * (u, v) and (v, u) are the same edge; duplicates in the list count once, as EdgeSet.contains over g_test's edges implies.  *true_positives =
+ * the edges of g_test that occur in the list, *true_count = the edges of g_test, *precision = tp / n_pred, *recall = tp / true_count: plain
+ * double divisions on the host; where a denominator is 0 the reference divides by zero — 0.0 here.  Every output pointer may be NULL.
+ * A pair with u == v or an id outside [0, n) → GMSX_ERR_INVALID.  n_pred = 0 is allowed. */
+int gmsx_link_prediction_precision(const gmsx_graph *g_test, int64_t n_pred, const int32_t *u, const int32_t *v,
+                                   int64_t *true_positives, int64_t *true_count, double *precision, double *recall,
+                                   gmsx_stats *stats);
 
 /* ---- the one collective of the path: the OpenMP reduction(+:total) of parallel/total.h:12,
  * k_clique_count_set_based.h:25 and the BK_CLIQUE_COUNTER atomic (tomita.h:76-77) across GPUs = ONE all-reduce of a u64 over

@@ -27,12 +27,15 @@
 //   gmsx::degeneracy_order(g, out)       -> gmsx_core_decomposition (an exact degeneracy order; not Matula's own tie sequence, gmsx.h)
 //   gmsx::degree_order(g, out)           -> gmsx_degree_rank       (preprocessing/parallel/degree.h:15-61)
 //   gmsx::order_quality(g, order)        -> gmsx_order_quality     (preprocessing/util/core_number_evaluator.h:73-139)
+//   gmsx::link_prediction(g, metric, q)  -> gmsx_link_prediction   (set_based/link_prediction/link_prediction.h:42-101; the reference's padding reproduced)
+//   gmsx::link_prediction_precision(g_test, edges) -> gmsx_link_prediction_precision (set_based/link_prediction/evaluation.h:99-124)
 // include/gmsx_gms_glue.hpp holds the explicit specialisations that route the reference's own function names to these
 // (INTEGRATION.md §2).  Header-only; link with -lgmsx.
 #pragma once
 
 #include <algorithm>
 #include <array>
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -662,6 +665,82 @@ inline std::vector<S> cliques(const HipGraphT<S> &g, int32_t k, int part = 0, in
     out.reserve(size_t(info.cliques));
     for (int64_t i = 0; i < info.cliques; ++i) out.emplace_back(cl.data() + size_t(i) * size_t(k), size_t(k));
     return out;
+}
+
+// GMS::LinkPrediction::link_prediction_similarity<Metric> (link_prediction/link_prediction.h:42-101) in the reference's shape: the q best
+// non-edges and their scores, ascending (index 0 the worst kept), WITH the reference's padding — q - found leading entries (-1.0, edge (0,0))
+// when fewer than q candidates exist, exactly one such entry when none does.  metric: a GMSX_SIM_* value.
+struct ScoredEdges {
+    std::vector<std::pair<int32_t, int32_t>> edges;  // UndirectedEdge: first < second
+    std::vector<double> scores;
+    int64_t found = 0;  // the real entries: the last `found` of both vectors
+};
+template <class S>
+inline ScoredEdges link_prediction_shard(const HipGraphT<S> &g, int metric, int64_t q, int part, int nparts, gmsx_link_prediction_info *info = nullptr) {
+    if (q > (int64_t(1) << 27)) detail::check(GMSX_ERR_UNSUPPORTED, "gmsx_link_prediction (q > 2^27)");  // the library's limit: no q slots allocated for nothing
+    const int64_t room = q >= 1 ? q : 1;  // (q < 1 is refused by the library)
+    std::vector<int32_t> u(static_cast<size_t>(room)), v(static_cast<size_t>(room));
+    std::vector<double> sc(static_cast<size_t>(room));
+    gmsx_link_prediction_info li{};
+    detail::check(gmsx_link_prediction(g.device(), metric, q, part, nparts, u.data(), v.data(), sc.data(), room, &li, nullptr), "gmsx_link_prediction");
+    if (info) *info = li;
+    ScoredEdges out;
+    out.found = li.found;
+    const int64_t pad = li.found > 0 ? q - li.found : 1;
+    out.edges.assign(size_t(pad), std::pair<int32_t, int32_t>(0, 0));
+    out.scores.assign(size_t(pad), -1.0);
+    for (int64_t i = 0; i < li.found; ++i) {
+        out.edges.emplace_back(u[size_t(i)], v[size_t(i)]);
+        out.scores.push_back(sc[size_t(i)]);
+    }
+    return out;
+}
+template <class S>
+inline ScoredEdges link_prediction(const HipGraphT<S> &g, int metric, int64_t q, gmsx_link_prediction_info *info = nullptr) {
+    return link_prediction_shard(g, metric, q, 0, 1, info);
+}
+// The shards of one (graph, metric, q) merged under the rule of gmsx.h — decreasing score, ties by ascending (u, v) —, truncated to q and padded
+// as the reference pads: the whole graph's result, entry for entry.
+inline ScoredEdges merge_link_predictions(const std::vector<ScoredEdges> &parts, int64_t q) {
+    struct E {
+        double s;
+        int32_t u, v;
+    };
+    std::vector<E> all;
+    for (const ScoredEdges &p : parts)
+        for (size_t i = p.scores.size() - size_t(p.found); i < p.scores.size(); ++i) all.push_back(E{p.scores[i], p.edges[i].first, p.edges[i].second});
+    std::sort(all.begin(), all.end(), [](const E &a, const E &b) { return a.s != b.s ? a.s > b.s : a.u != b.u ? a.u < b.u : a.v < b.v; });
+    if (int64_t(all.size()) > q) all.resize(size_t(std::max<int64_t>(q, 0)));
+    ScoredEdges out;
+    out.found = int64_t(all.size());
+    const int64_t pad = out.found > 0 ? q - out.found : 1;
+    out.edges.assign(size_t(pad), std::pair<int32_t, int32_t>(0, 0));
+    out.scores.assign(size_t(pad), -1.0);
+    for (size_t i = all.size(); i-- > 0;) {
+        out.edges.emplace_back(all[i].u, all[i].v);
+        out.scores.push_back(all[i].s);
+    }
+    return out;
+}
+// score_link_prediction_precision (link_prediction/evaluation.h:99-124): g_test's undirected edges against a predicted list
+struct LinkPredictionScore {
+    double precision = 0.0, recall = 0.0;
+    int64_t true_positives = 0, true_count = 0;
+};
+template <class S, class Edges>
+inline LinkPredictionScore link_prediction_precision(const HipGraphT<S> &g_test, const Edges &predicted) {
+    std::vector<int32_t> u, v;
+    u.reserve(predicted.size());
+    v.reserve(predicted.size());
+    for (const auto &e : predicted) {
+        u.push_back(int32_t(e.first));
+        v.push_back(int32_t(e.second));
+    }
+    LinkPredictionScore sc;
+    detail::check(gmsx_link_prediction_precision(g_test.device(), int64_t(u.size()), u.data(), v.data(), &sc.true_positives, &sc.true_count, &sc.precision,
+                                                 &sc.recall, nullptr),
+                  "gmsx_link_prediction_precision");
+    return sc;
 }
 
 }  // namespace gmsx
