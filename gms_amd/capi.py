@@ -39,6 +39,7 @@ SYMBOLS = [
     "gmsx_tc_total", "gmsx_tc_partial", "gmsx_tc_divisor", "gmsx_tc_stream_breakdown", "gmsx_tc_row_histogram", "gmsx_tc_comembership", "gmsx_tc_vertex_count2",
     "gmsx_intersect_count_batch", "gmsx_set_op_batch", "gmsx_vertex_similarity_batch", "gmsx_kclique_count", "gmsx_kclique_partial", "gmsx_kclique_star_count", "gmsx_kclique_star_list", "gmsx_bk_count", "gmsx_bk_partial", "gmsx_bk_list",
     "gmsx_adg_rank", "gmsx_tc_ordering", "gmsx_core_decomposition", "gmsx_degree_rank", "gmsx_order_quality",
+    "gmsx_coloring_jp", "gmsx_coloring_verify",
     "gmsx_link_prediction", "gmsx_link_prediction_precision",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -87,6 +88,24 @@ class OrderQualityInfo(C.Structure):
         d = {k: int(getattr(self, k)) for k in ("max_later", "core_number", "core_number_of_order", "faulty", "excess")}
         d.update({k: float(getattr(self, k)) for k in ("relative_error", "fault_rate", "relative_mean_difference")})
         return d
+
+
+class ColoringInfo(C.Structure):
+    _fields_ = [("colors", C.c_int32), ("rounds", C.c_int32), ("max_pred", C.c_int32), ("reserved", C.c_int32), ("first_round", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("colors", "rounds", "max_pred", "first_round")}
+
+
+class ColoringCheck(C.Structure):
+    _fields_ = [("conflicts", C.c_int64), ("invalid", C.c_int64), ("max_color", C.c_int32), ("distinct", C.c_int32), ("max_degree", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("conflicts", "invalid", "max_color", "distinct", "max_degree")}
+
+
+COLOR_HEURISTICS = ("id", "ff", "lf", "sl", "adg")
 
 
 class LinkPredictionInfo(C.Structure):
@@ -192,6 +211,8 @@ def lib():
     L.gmsx_core_decomposition.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CoreInfo), sp]
     L.gmsx_degree_rank.argtypes = [vp, C.c_int, _i32p, sp]
     L.gmsx_order_quality.argtypes = [vp, C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.POINTER(OrderQualityInfo), sp]
+    L.gmsx_coloring_jp.argtypes = [vp, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ColoringInfo), sp]
+    L.gmsx_coloring_verify.argtypes = [vp, C.c_void_p, C.POINTER(ColoringCheck), sp]
     L.gmsx_link_prediction.argtypes = [vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.POINTER(LinkPredictionInfo), sp]
     L.gmsx_link_prediction_precision.argtypes = [vp, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -633,6 +654,56 @@ class DeviceGraph:
         if stats:
             r = r + (st.as_dict(),)
         return r if len(r) > 1 else r[0]
+
+    def coloring_jp(self, ordering=None, rank_format=True, want_rounds=False, stats=False):
+        """gmsx_coloring_jp: (coloring int32[n], {colors, rounds, max_pred, first_round}) — Jones–Plassmann under `ordering` (a rank or an order
+        vector; the vertex of the highest position is coloured first; None = order[v] = v); with want_rounds=True (coloring, round_of, info)."""
+        n = self.num_nodes
+        op = None
+        if ordering is not None:
+            ordering = np.ascontiguousarray(ordering, dtype=np.int32)
+            if ordering.size != n:
+                raise GmsxError(ERR_INVALID, "gmsx_coloring_jp (ordering must have n entries)")
+            op = ordering.ctypes.data_as(C.c_void_p) if n else None
+        col = np.zeros(max(n, 1), dtype=np.int32)
+        rnd = np.zeros(max(n, 1), dtype=np.int32) if want_rounds else None
+        info, st = ColoringInfo(), Stats()
+        _check(lib().gmsx_coloring_jp(self._h, op, int(bool(rank_format)), col.ctypes.data_as(C.c_void_p),
+                                      rnd.ctypes.data_as(C.c_void_p) if want_rounds else None, C.byref(info), C.byref(st)), "gmsx_coloring_jp")
+        r = (col[:n], rnd[:n], info.as_dict()) if want_rounds else (col[:n], info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def coloring_verify(self, coloring, stats=False):
+        """gmsx_coloring_verify: {conflicts, invalid, max_color, distinct, max_degree} of a colouring (int32[n]); GCVerifierMaxColor(g, c, m) is
+        invalid == 0 and conflicts == 0 and max_color <= m."""
+        coloring = np.ascontiguousarray(coloring, dtype=np.int32)
+        if coloring.size != self.num_nodes:
+            raise GmsxError(ERR_INVALID, "gmsx_coloring_verify (coloring must have n entries)")
+        out, st = ColoringCheck(), Stats()
+        _check(lib().gmsx_coloring_verify(self._h, coloring.ctypes.data_as(C.c_void_p) if coloring.size else None, C.byref(out), C.byref(st)),
+               "gmsx_coloring_verify")
+        return (out.as_dict(), st.as_dict()) if stats else out.as_dict()
+
+    def color_order(self, heuristic, epsilon=0.001):
+        """The rank vector of a colouring heuristic, composed from the existing producers (rank format; None for "id"): "ff" = n-1-v (first-fit in
+        id order, graph_coloring_naive_sequential), "lf" = gmsx_degree_rank (largest first), "sl" = gmsx_core_decomposition's order (smallest last),
+        "adg" = gmsx_adg_rank(epsilon)."""
+        n = self.num_nodes
+        if heuristic == "id":
+            return None
+        if heuristic == "ff":
+            return np.arange(n - 1, -1, -1, dtype=np.int32)
+        if heuristic == "lf":
+            return self.degree_rank(rank_format=True)
+        if heuristic == "sl":
+            return self.core_decomposition(order=True, rank_format=True)[1]
+        if heuristic == "adg":
+            return self.adg_rank(epsilon, rank_format=True)[0]
+        raise GmsxError(ERR_INVALID, f"color (heuristic must be one of {COLOR_HEURISTICS})")
+
+    def color(self, heuristic, epsilon=0.001):
+        """Jones–Plassmann under one of COLOR_HEURISTICS: (coloring int32[n], info dict)."""
+        return self.coloring_jp(self.color_order(heuristic, epsilon), rank_format=True)
 
     def link_prediction(self, metric, q, part=0, nparts=1, stats=False):
         """gmsx_link_prediction: the q best-scoring non-edges under `metric` (a SIM_* value or one of SIM_METRICS' names), worst first:

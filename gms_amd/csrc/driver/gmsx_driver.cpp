@@ -22,7 +22,12 @@
 // Added:  kcstar -p clique-size=k [--list FILE]   KCliqueStar::Par::CliqueStarList (k_clique_star_list/parallel/recursive.h:19-43) on the device: prints the
 //                    reference's "total k-cliques: N" line (:34, N = the number of pairs); --list writes the pairs of the last trial (gmsx_kclique_star_list, outside
 //                    the timed trial), one per line: "c1 … ck | s1 …", clique and star ascending.  Not sharded (--gpus > 1 is refused).
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  color [--order id|ff|lf|sl|adg] [--eps e]   GMS::Coloring::JonesV3::graph_coloring_jones (non_set_based/coloring/coloring_jones_v3.h:38-68) on the device
+//                    (gmsx_coloring_jp) with the trial loop and the labels of benchmarkGraphColoringWithReordering (coloring.cc:82-129): per trial "Preprocess Time"
+//                    (the order: id = getSimpleIdOrdering, the reference's; ff = n-1-v; lf = gmsx_degree_rank; sl = gmsx_core_decomposition; adg = gmsx_adg_rank(eps)),
+//                    "Trial Time", "Colors" and with -v "Verification" (gmsx_coloring_verify read as GCVerifierMaxColor), then the three averages.  A colouring is
+//                    global: not sharded (--gpus > 1 is refused).
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -55,7 +60,8 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     std::string list;  // bk --list FILE: the maximal cliques of the last trial, one per line (gmsx_bk_list)
     std::string metric = "jaccard";  // lp --metric
     int64_t q = 0;     // lp -q N (0: m / 4)
-    std::string order; // bk --order adg|deg|dgr: the preprocessing step in front of the search (default adg)
+    std::string order; // bk --order adg|deg|dgr: the preprocessing step in front of the search (default adg); color --order id|ff|lf|sl|adg (default id)
+    double eps = 0.001; // color --eps: epsilon of --order adg
     int error = 0;
 };
 
@@ -91,7 +97,8 @@ Args parse(int argc, char **argv) {
         else if (f == "--list") { if (!need(1)) break; a.list = argv[++i]; }
         else if (f == "--metric") { if (!need(1)) break; a.metric = argv[++i]; }
         else if (f == "-q") { if (!need(1)) break; a.q = std::atoll(argv[++i]); if (a.q < 1) a.error = 100; }
-        else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; if (a.order != "adg" && a.order != "deg" && a.order != "dgr") a.error = 100; }
+        else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; }
+        else if (f == "--eps") { if (!need(1)) break; a.eps = std::atof(argv[++i]); }
         else if (f == "--gpus") { if (!need(1)) break; a.gpus = std::atoi(argv[++i]); if (a.gpus < 1 || a.gpus > 64) a.error = 100; }
         else if (f == "--opt") {  // --opt NAME=VALUE -> gmsx_set_option (limits, kernel variants, diagnostics: include/gmsx.h); unknown names are refused
             if (!need(1)) break;
@@ -114,14 +121,19 @@ Args parse(int argc, char **argv) {
     if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
     if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp") && a.gpus > 1) a.error = 100;
     if (!a.error && a.kernel == "lp" && lp_metric(a.metric) < 0) a.error = 100;
-    if (!a.error && !a.order.empty() && a.kernel != "bk") a.error = 100;  // only Bron–Kerbosch has a preprocessing step
+    if (!a.error && !a.order.empty() && a.kernel != "bk" && a.kernel != "color") a.error = 100;  // only Bron–Kerbosch and the colouring have a preprocessing step
+    if (!a.error && !a.order.empty() && a.kernel == "bk" && a.order != "adg" && a.order != "deg" && a.order != "dgr") a.error = 100;
+    if (!a.error && a.kernel == "color") {
+        const std::string &o = a.order;
+        if ((!o.empty() && o != "id" && o != "ff" && o != "lf" && o != "sl" && o != "adg") || a.gpus > 1) a.error = 100;
+    }
     return a;
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
-                "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE]\n", argv0);
+                "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -351,12 +363,48 @@ int launch_ranks(int gpus) {
     return worst;
 }
 
+// benchmarkGraphColoringWithReordering (coloring.cc:82-129) around gmsx::coloring: its labels, its three averages
+int run_color(const Args &args, const gmsx::HipSetGraph &g) {
+    const std::string heuristic = args.order.empty() ? "id" : args.order;
+    double total_seconds = 0, pp_total_seconds = 0;
+    int64_t total_colors = 0;
+    Timer t;
+    for (int64_t it = 0; it < args.trials; ++it) {
+        t.Start();
+        std::vector<int32_t> order;
+        const bool has_order = gmsx::coloring_order(g, heuristic.c_str(), args.eps, order);
+        t.Stop();
+        PrintTime("Preprocess Time", t.Seconds());
+        pp_total_seconds += t.Seconds();
+        t.Start();
+        gmsx_coloring_info info{};
+        const std::vector<int32_t> coloring = has_order ? gmsx::coloring(g, order, true, &info) : gmsx::coloring(g, heuristic.c_str(), args.eps, &info);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        const gmsx_coloring_check chk = gmsx::coloring_check(g, coloring);
+        const int n_col = int(chk.distinct);  // uniqueColorsCount (coloring_common.h:205-209)
+        total_colors += n_col;
+        PrintLabel("Colors", std::to_string(n_col));
+        if (args.verify) {  // GCVerifierMaxColor(g, coloring, nCol) (coloring_common.h:102-122)
+            const bool ok = chk.invalid == 0 && chk.conflicts == 0 && chk.max_color <= n_col && info.colors == n_col;
+            PrintLabel("Verification", ok ? "PASS" : "FAIL");
+        }
+        std::cout << "@@@ coloring jones_v3 pp:" << heuristic << std::endl;
+    }
+    const double trials = double(args.trials > 0 ? args.trials : 1);
+    PrintTime("Average Time", total_seconds / trials);
+    PrintTime("Average pp Time", pp_total_seconds / trials);
+    PrintTime("Average colors", double(total_colors) / trials);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -429,6 +477,12 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
+    if (args.kernel == "color") {
+        const int rc_color = run_color(args, g);
+        if (comm) gmsx_comm_finalize(comm);
+        gmsx_csr_free(csr);
+        return rc_color;
+    }
 
     std::string label;
     double total = 0;

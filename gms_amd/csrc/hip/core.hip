@@ -22,6 +22,7 @@
 // k_core_round_long (all threads of the workgroup in k_core_tail) together — no lane walks a long row alone.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
+#include "order_rank.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -36,8 +37,7 @@ namespace {
 
 // UNMEASURED: none of these bounds has a timing behind it yet (tools/core_probe.py is the measurement).  They follow the round
 // table of the peel on R-MAT graphs (almost every round removes fewer than 256 vertices) and the row shapes named there.
-constexpr int kGroup = 16;          // lanes per frontier vertex of a short row
-constexpr int kLongRow = 1024;      // longer rows are walked by many waves together
+// (kGroup = 16 lanes per frontier vertex of a short row and kLongRow = 1024, above which a row is walked by many waves together: order_rank.hpp)
 constexpr int kWgRowMax = 32768;    // k_core_tail hands a frontier with a longer row back to the grid-wide kernels
 constexpr int kTailThreads = 1024;
 constexpr int kTailLong = 256;      // long rows one round of k_core_tail can park for its whole-workgroup phase; more: the round goes back to the grid
@@ -390,66 +390,8 @@ int core_peel(const gmsx_graph *g, DevBuf &d_core, DevBuf &d_round, gmsx_core_in
 
 // ---- order quality ------------------------------------------------------------------------------------------------------------------
 
-// ordering -> rank[] (device) + validation: every entry in [0, n) and hit once
-__global__ void k_oq_rank(int64_t n, const int32_t *__restrict__ ordering, int rank_format, int32_t *__restrict__ rank, int32_t *__restrict__ seen,
-                          int32_t *__restrict__ bad) {
-    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t x = ordering[i];
-    if (x < 0 || int64_t(x) >= n) {
-        *bad = 1;
-        return;
-    }
-    if (atomicAdd(&seen[x], 1) != 0) *bad = 1;
-    if (!rank_format) rank[x] = int32_t(i);  // ordering[i] = i-th vertex
-}
+// ordering -> rank[] with its validation (k_oq_rank) and later[] (k_oq_later / k_oq_later_long): order_rank.hpp, shared with coloring.hip
 
-// later[v] = |{ w in N(v) : rank[w] > rank[v] }|: a 16-lane group per vertex, rows above kLongRow parked for k_oq_later_long
-__global__ __launch_bounds__(256) void k_oq_later(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                  const int32_t *__restrict__ rank, int32_t *__restrict__ later, int32_t *__restrict__ longs,
-                                                  int64_t long_cap, int32_t *__restrict__ ctl /* [0] long rows, [1] error */) {
-    const int lane = threadIdx.x & (kGroup - 1);
-    const int64_t group0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / kGroup;
-    const int64_t groups = (int64_t(gridDim.x) * blockDim.x) / kGroup;
-    const int64_t end = ((n + 3) / 4) * 4;  // the four groups of a wave stay together for the shuffles
-    for (int64_t v = group0; v < end; v += groups) {
-        int32_t cnt = 0;
-        if (v < n) {
-            const int64_t j0 = off[v], j1 = off[v + 1];
-            if (j1 - j0 > kLongRow) {
-                if (lane == 0) {
-                    later[v] = 0;
-                    const int64_t pos = int64_t(atomicAdd(&ctl[0], 1));
-                    if (pos < long_cap) longs[pos] = int32_t(v);
-                    else ctl[1] = 1;
-                }
-                cnt = -1;
-            } else {
-                const int32_t rv = rank[v];
-                for (int64_t j = j0 + lane; j < j1; j += kGroup) cnt += rank[adj[j]] > rv ? 1 : 0;
-            }
-        }
-        const bool parked = cnt < 0;
-        if (parked) cnt = 0;
-        for (int o = kGroup / 2; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, kGroup);
-        if (v < n && lane == 0 && !parked) later[v] = cnt;
-    }
-}
-__global__ __launch_bounds__(256) void k_oq_later_long(const int64_t *__restrict__ off, const int32_t *__restrict__ adj, const int32_t *__restrict__ rank,
-                                                       int32_t *__restrict__ later, const int32_t *__restrict__ longs, int64_t long_cap,
-                                                       const int32_t *__restrict__ ctl) {
-    const int64_t nlong = min(int64_t(ctl[0]), long_cap);
-    const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, threads = int64_t(gridDim.x) * blockDim.x;
-    for (int64_t i = 0; i < nlong; ++i) {
-        const int32_t v = longs[i];
-        const int32_t rv = rank[v];
-        const int64_t j0 = off[v], j1 = off[v + 1];
-        int32_t cnt = 0;
-        for (int64_t j = j0 + tid; j < j1; j += threads) cnt += rank[adj[j]] > rv ? 1 : 0;
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
-        if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&later[v], cnt);
-    }
-}
 // acc[0] = max later, acc[1] = #(later > core_number), acc[2] = Σ (later - core_number) over those; core_number < 0: the maximum only
 __global__ __launch_bounds__(256) void k_oq_reduce(int64_t n, const int32_t *__restrict__ later, int32_t core_number, unsigned long long *__restrict__ acc) {
     unsigned long long mx = 0, faulty = 0, excess = 0;

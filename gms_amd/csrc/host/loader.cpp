@@ -778,6 +778,8 @@ Option g_options[] = {
     {"KCSTAR_SLAB_MB", "", false},
     // core decomposition (core.hip)
     {"CORE_WG_FRONTIER", "", false},
+    // graph colouring (coloring.hip)
+    {"COLOR_WG_FRONTIER", "", false},
     // link prediction (linkpred.hip)
     {"LP_LDS_MAXN", "", false}, {"LP_SLAB_MB", "", false},
 };

@@ -142,6 +142,8 @@ int gmsx_set_host_threads(int n);
  *   k-clique-star listing  KCSTAR_SLAB_MB (budget of the level-set slabs of one launch: smaller = more launches)
  *   core decomposition     CORE_WG_FRONTIER (largest frontier whose rounds run inside the one-workgroup kernel, default 512 — a first guess, not a
  *                   tuned value; 0 = every round is a kernel boundary; test hook)
+ *   graph colouring        COLOR_WG_FRONTIER (the same for the rounds of gmsx_coloring_jp: largest frontier whose rounds run inside its one-workgroup
+ *                   kernel, default 512 — a first guess; 0 = every round is a kernel boundary; test hook)
  *   link prediction        LP_LDS_MAXN (largest n whose per-source bitmaps live in LDS, default and maximum 131072 — a first guess; 0 = every
  *                   bitmap in the workgroup's global slab; test hook), LP_SLAB_MB (budget of the candidates of one chunk: smaller = more chunks;
  *                   test hook) */
@@ -463,6 +465,48 @@ int gmsx_order_quality(const gmsx_graph *g, const int32_t *ordering /* n, host *
                        int32_t core_number /* < 0: computed here by the peel of gmsx_core_decomposition */,
                        int32_t *later /* n, host, or NULL: per-vertex count of neighbours after v */,
                        gmsx_order_quality_info *info /* required */, gmsx_stats *stats);
+
+/* ---- graph colouring: GMS::Coloring::JonesV3::graph_coloring_jones (non_set_based/coloring/coloring_jones_v3.h:38-68), Jones–Plassmann under a
+ * caller-given priority — what benchmarkGraphColoringWithReordering times (coloring.cc:82-129, :149).  u is a PREDECESSOR of v iff u is a neighbour
+ * of v and order[u] > order[v] (:52); a vertex takes the smallest colour >= 1 that none of its predecessors holds (:12-21).  The result is a
+ * function of (graph, order): the greedy colouring of the vertices taken by DESCENDING order[], the reference's array element for element at
+ * every thread count.
+ * ordering (n, host, or NULL): rank_format as in gmsx_adg_rank (!= 0: ordering[v] = position of v, else ordering[i] = i-th vertex).  The vertex of
+ * the HIGHEST position is coloured first.  That is the convention of the rank producers here: gmsx_degree_rank gives largest-first (LF),
+ * gmsx_core_decomposition's order smallest-last (SL: at most core[v] predecessors per vertex, so at most degeneracy + 1 colours), gmsx_adg_rank the
+ * approximate SL.  NULL = order[v] = v, PpSequential::getSimpleIdOrdering, what coloring.cc:25-30 hands to JonesV3; order[v] = n-1-v gives
+ * graph_coloring_naive_sequential (coloring_sequential.h:17-42), first-fit in id order.  ordering must be a permutation of 0..n-1 (checked on
+ * the device), else GMSX_ERR_INVALID and nothing is written: the reference mis-colours on ties.
+ * coloring (n, host, or NULL): coloring[v] in 1..info->colors.  round_of (n, host, or NULL): the Jones–Plassmann round of v — 0 without
+ * predecessors, else 1 + the maximum over its predecessors (its depth in the priority DAG).
+ * All outputs are a fact about (graph, permutation): byte-identical in every process and on every run (the arrival order of the atomics reaches
+ * no output).  n = 0: GMSX_OK, *info zeroed.  NULL g or info: GMSX_ERR_INVALID.  A frontier that would overflow its buffer or a final coloured
+ * count != n is reported as GMSX_ERR_KERNEL; nothing is written out of bounds and the caller's arrays are written only after success.
+ * Width: the forbidden colours of a vertex are a bitmap in LDS for rows of up to 1024 entries and in a global slab beyond, so no graph is
+ * refused for a wide neighbourhood.  A colouring is global: the call is single-GPU only, there are no shards.
+ * Test hook: option COLOR_WG_FRONTIER.  gmsx_stats: kernel_ms, launches, units = n, probes = rounds. */
+typedef struct {
+    int32_t colors;      /* largest colour used = number of colours (greedy leaves no gap in 1..colors); 0 for n = 0 */
+    int32_t rounds;      /* Jones–Plassmann rounds = vertices on the longest path of the priority DAG; 0 for n = 0 */
+    int32_t max_pred;    /* most predecessors of any vertex (= gmsx_order_quality's max_later for this order); colors <= max_pred + 1 */
+    int32_t reserved;
+    int64_t first_round; /* vertices without a predecessor (the size of round 0) */
+} gmsx_coloring_info;
+int gmsx_coloring_jp(const gmsx_graph *g, const int32_t *ordering /* n, host, or NULL */, int rank_format,
+                     int32_t *coloring /* n, host, or NULL */, int32_t *round_of /* n, host, or NULL */,
+                     gmsx_coloring_info *info /* required */, gmsx_stats *stats);
+/* The reference's verifiers (coloring_common.h) as integers over any colouring (n, host):
+ *   GCVerifierMaxColor(g, c, m) (:102-122)   <=>  invalid == 0 && conflicts == 0 && max_color <= m
+ *   GCVerifierDeltaPlusOne (:125-157)        <=>  the same with m = max_degree + 1
+ * One difference: a NEGATIVE colour counts as invalid here and passes the range test of GCVerifierMaxColor (c == 0 || c > maxColor, :109); no
+ * reference algorithm produces one.  n = 0: GMSX_OK, *out zeroed.  NULL g, out or (n > 0) coloring: GMSX_ERR_INVALID. */
+typedef struct {
+    int64_t conflicts;   /* undirected edges {u,v} with coloring[u] == coloring[v] */
+    int64_t invalid;     /* vertices with coloring[v] < 1 */
+    int32_t max_color, distinct;   /* distinct = the reference's uniqueColorsCount (coloring_common.h:205-209) */
+    int32_t max_degree, reserved;
+} gmsx_coloring_check;
+int gmsx_coloring_verify(const gmsx_graph *g, const int32_t *coloring /* n, host */, gmsx_coloring_check *out /* required */, gmsx_stats *stats);
 
 /* ---- link prediction: GMS::LinkPrediction::link_prediction_similarity<Metric> (set_based/link_prediction/link_prediction.h:42-101), the q
  * best-scoring NON-edges of the graph under one of the GMSX_SIM_* metrics, and the precision / recall step of the reference's bench_ranking

@@ -27,6 +27,8 @@
 //   gmsx::degeneracy_order(g, out)       -> gmsx_core_decomposition (an exact degeneracy order; not Matula's own tie sequence, gmsx.h)
 //   gmsx::degree_order(g, out)           -> gmsx_degree_rank       (preprocessing/parallel/degree.h:15-61)
 //   gmsx::order_quality(g, order)        -> gmsx_order_quality     (preprocessing/util/core_number_evaluator.h:73-139)
+//   gmsx::coloring(g, order) / coloring(g, "sl") -> gmsx_coloring_jp (non_set_based/coloring/coloring_jones_v3.h:38-68: Jones–Plassmann under a priority)
+//   gmsx::coloring_check(g, coloring)    -> gmsx_coloring_verify   (non_set_based/coloring/coloring_common.h:102-157, 205-209: the verifiers as integers)
 //   gmsx::link_prediction(g, metric, q)  -> gmsx_link_prediction   (set_based/link_prediction/link_prediction.h:42-101; the reference's padding reproduced)
 //   gmsx::link_prediction_precision(g_test, edges) -> gmsx_link_prediction_precision (set_based/link_prediction/evaluation.h:99-124)
 // include/gmsx_gms_glue.hpp holds the explicit specialisations that route the reference's own function names to these
@@ -42,6 +44,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <memory>
+#include <string>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -577,6 +580,63 @@ inline gmsx_order_quality_info order_quality(const HipGraphT<S> &g, const Input 
     detail::check(gmsx_order_quality(g.device(), reinterpret_cast<const int32_t *>(order.data()), rank_format ? 1 : 0, core_number, nullptr, &qi, nullptr),
                   "gmsx_order_quality");
     return qi;
+}
+
+// JonesV3::graph_coloring_jones(g, coloring, order) (coloring_jones_v3.h:38-68): the colouring (1..info->colors) under `order` — rank format
+// (order[v] = position of v) is the reference's own; the vertex of the highest position is coloured first.
+template <class S, class Input>
+inline std::vector<int32_t> coloring(const HipGraphT<S> &g, const Input &order, bool rank_format = true, gmsx_coloring_info *info = nullptr) {
+    static_assert(sizeof(*order.data()) == sizeof(int32_t), "orderings are NodeId = int32 vectors");
+    if (int64_t(order.size()) != g.num_nodes()) detail::check(GMSX_ERR_INVALID, "gmsx_coloring_jp");
+    std::vector<int32_t> res(size_t(g.num_nodes()));
+    gmsx_coloring_info ci{};
+    detail::check(gmsx_coloring_jp(g.device(), g.num_nodes() ? reinterpret_cast<const int32_t *>(order.data()) : nullptr, rank_format ? 1 : 0, res.data(), nullptr,
+                                   &ci, nullptr), "gmsx_coloring_jp");
+    if (info) *info = ci;
+    return res;
+}
+// The rank vector of a colouring heuristic, composed from the existing producers: "ff" = n-1-v (graph_coloring_naive_sequential's first-fit,
+// coloring_sequential.h:17-42), "lf" = degree_order (largest first), "sl" = degeneracy_order (smallest last), "adg" = adg_rank(epsilon).
+// Returns false for "id" (order[v] = v, getSimpleIdOrdering: gmsx_coloring_jp's NULL) and leaves `order` empty; an unknown name exits.
+template <class S>
+inline bool coloring_order(const HipGraphT<S> &g, const char *heuristic, double epsilon, std::vector<int32_t> &order) {
+    const std::string h = heuristic ? heuristic : "";
+    order.clear();
+    if (h == "id") return false;
+    if (h == "ff") {
+        order.resize(size_t(g.num_nodes()));
+        for (size_t v = 0; v < order.size(); ++v) order[v] = int32_t(order.size() - 1 - v);
+    } else if (h == "lf") {
+        degree_order(g, order, true);
+    } else if (h == "sl") {
+        degeneracy_order(g, order, true);
+    } else if (h == "adg") {
+        adg_rank(g, epsilon, order, true);
+    } else {
+        detail::check(GMSX_ERR_INVALID, "gmsx::coloring (heuristic: id, ff, lf, sl or adg)");
+    }
+    return true;
+}
+template <class S>
+inline std::vector<int32_t> coloring(const HipGraphT<S> &g, const char *heuristic, double epsilon = 0.001, gmsx_coloring_info *info = nullptr) {
+    std::vector<int32_t> order;
+    if (coloring_order(g, heuristic, epsilon, order)) return coloring(g, order, true, info);
+    std::vector<int32_t> res(size_t(g.num_nodes()));
+    gmsx_coloring_info ci{};
+    detail::check(gmsx_coloring_jp(g.device(), nullptr, 1, res.data(), nullptr, &ci, nullptr), "gmsx_coloring_jp");
+    if (info) *info = ci;
+    return res;
+}
+// GCVerifierMaxColor(g, c, m) (coloring_common.h:102-122) is invalid == 0 && conflicts == 0 && max_color <= m; GCVerifierDeltaPlusOne (:125-157)
+// the same with m = max_degree + 1; distinct is uniqueColorsCount (:205-209)
+template <class S, class Input>
+inline gmsx_coloring_check coloring_check(const HipGraphT<S> &g, const Input &coloring) {
+    static_assert(sizeof(*coloring.data()) == sizeof(int32_t), "colourings are int32 vectors");
+    gmsx_coloring_check out{};
+    if (int64_t(coloring.size()) != g.num_nodes()) detail::check(GMSX_ERR_INVALID, "gmsx_coloring_verify");
+    detail::check(gmsx_coloring_verify(g.device(), g.num_nodes() ? reinterpret_cast<const int32_t *>(coloring.data()) : nullptr, &out, nullptr),
+                  "gmsx_coloring_verify");
+    return out;
 }
 
 // Set::intersect / Set::difference of whole neighbourhoods for a BATCH of vertex pairs on the device (sorted_set.h:160-197): result i =
