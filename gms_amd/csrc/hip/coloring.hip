@@ -13,14 +13,14 @@
 // it and is dropped).  No rank[] gather in the rounds; every CSR entry is touched once per endpoint over the whole run.  Which vertices a
 // round colours, and with what, is a fact about the integers; the order inside the queues and the slab offsets are not, and reach no output.
 //
-// COST SHAPE.  That of the peel in core.hip — hundreds to thousands of rounds, most of them tiny — and its solutions: a round boundary is a
-// kernel boundary (k_color_round + k_color_round_long + k_color_pick_advance, then the host reads the control block) or, while the frontier holds at
-// most COLOR_WG_FRONTIER vertices that are light enough, a __syncthreads() of k_color_tail, ONE workgroup that runs round after round.  No
-// workgroup ever waits for another one.  Rows are binned as there: a 16-lane group per vertex up to kLongRow entries with its bitmap in
-// LDS; longer rows by all workgroups together (all threads of the workgroup in k_color_tail) with the bitmap in a zeroed global slab, so
-// no graph is refused for a wide neighbourhood.
+// COST SHAPE.  That of the peel in core.hip — hundreds to thousands of rounds, most of them tiny — and its solution: the rounds are those of the
+// frontier engine (frontier_rounds.hpp: the row binning, the one-workgroup tail under COLOR_WG_FRONTIER and its hand-back rule); this file
+// supplies the per-vertex work (ColorJp), the setup and the final checks.  A short row keeps its bitmap in the group's LDS words; a long row is
+// parked with a piece of a zeroed global slab (its note) and takes its colour at the round boundary, so no graph is refused for a wide
+// neighbourhood.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
+#include "frontier_rounds.hpp"
 #include "order_rank.hpp"
 
 #include <algorithm>
@@ -32,48 +32,24 @@ namespace gmsx {
 
 namespace {
 
-// UNMEASURED: none of these bounds has a timing behind it yet (tools/coloring_probe.py is the measurement).  They are
-// core.hip's, for the same reasons; kGroup and kLongRow are shared with it (order_rank.hpp).
 constexpr int kBitWords = kLongRow / 32 + 1;  // bitmap of a short row: colours 1..p+1, p <= kLongRow
-constexpr int kWgRowMax = 32768;              // k_color_tail hands a frontier with a longer row back to the grid-wide kernels
-constexpr int kTailThreads = 1024;
-constexpr int kTailLong = 256;                // long rows one round of k_color_tail can park; more: the round goes back to the grid
-constexpr int kWgWorkMax = 1 << 18;           // CSR entries one round of k_color_tail may walk; more: the round goes back to the grid
-constexpr long long kWgFrontierDefault = 512;
 
-// control block of one run (device, mirrored to the host after every step)
-struct ColorCtrl {
-    int32_t count;      // vertices in the current frontier
-    int32_t next;       // appended to the next one so far
-    int32_t round;      // index of the round the current frontier is coloured in
-    int32_t colored;    // vertices coloured in finished rounds
-    int32_t error;      // an append, the slab or a first-free search hit its bound
-    int32_t nlong;      // long rows parked by k_color_round
-    int32_t bail;       // k_color_tail met a round too heavy for one workgroup
-    int32_t cur;        // which of the two frontier buffers is the current one
-    int32_t colors;     // largest colour given so far
-    int32_t max_pred;   // most predecessors of any vertex
+// control block of one run: the engine's, plus what the colours need
+struct ColorCtrl : FrontierCtrl {  // (done = vertices coloured in finished rounds; error: also the slab or a first-free search hit its bound)
+    int32_t colors;                // largest colour given so far
+    int32_t max_pred;              // most predecessors of any vertex
     unsigned long long slab_used;  // words of the slab handed to long rows so far (every vertex is parked at most once)
 };
 
-__device__ __forceinline__ int32_t load_now(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint32_t load_now(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void store_now(int32_t *p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // the lanes of a wave run in program order: this only keeps the compiler from moving LDS accesses across the phases of a group
 __device__ __forceinline__ void group_phase() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
 
-__global__ void k_color_iota(int64_t n, int32_t *__restrict__ rank) {
-    const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (v < n) rank[v] = int32_t(v);  // getSimpleIdOrdering: what coloring.cc:25-30 hands to JonesV3
-}
-
 // pred[v] = cnt[v] (the counters fall, the bitmap widths stay), max_pred, and the first frontier: cnt == 0 (one wave-aggregated append per wave)
 __global__ __launch_bounds__(256) void k_color_select(int64_t n, const int32_t *__restrict__ cnt, int32_t *__restrict__ pred, ColorCtrl *__restrict__ ctrl,
                                                       int32_t *__restrict__ frontier) {
-    const int lane = threadIdx.x & 63;
     const int64_t stride = int64_t(gridDim.x) * blockDim.x;
     const int64_t end = ((n + 63) / 64) * 64;  // whole waves stay converged for the ballot
     int32_t mx = 0;
@@ -85,317 +61,110 @@ __global__ __launch_bounds__(256) void k_color_select(int64_t n, const int32_t *
             mx = max(mx, p);
             take = p == 0;
         }
-        const unsigned long long m = __ballot(take);
-        if (m == 0) continue;
-        int32_t base = 0;
-        if (lane == 0) base = atomicAdd(&ctrl->count, int32_t(__popcll(m)));
-        base = __shfl(base, 0);
-        if (take) {
-            const int64_t pos = int64_t(base) + __popcll(m & ((1ull << lane) - 1ull));
-            if (pos < n) frontier[pos] = int32_t(v);
-            else ctrl->error = 1;
-        }
+        wave_append(take, int32_t(v), frontier, &ctrl->count, n, &ctrl->error);
     }
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_down(mx, o));
-    if (lane == 0 && mx) atomicMax(&ctrl->max_pred, mx);
-}
-
-// a successor of the frontier vertex: its counter drops, and the decrement that brings it to 0 queues it
-template <class Counter>
-__device__ __forceinline__ void release_successor(int32_t w, int32_t *__restrict__ cnt, int32_t *__restrict__ next, Counter *next_count, int64_t cap,
-                                                  int32_t *error) {
-    if (atomicSub(&cnt[w], 1) == 1) {
-        const int64_t pos = int64_t(atomicAdd(next_count, 1));
-        if (pos < cap) next[pos] = w;
-        else *error = 1;
-    }
-}
-
-// one SHORT row [j0, j1) of frontier vertex x by the kGroup lanes of a group, forbidden bitmap `bits` (kBitWords words of LDS, the group's own):
-// returns x's colour (every lane of the group), 0 if the search found none (cannot happen: at most p of the p + 1 bits are set)
-template <class Counter>
-__device__ __forceinline__ int32_t color_short_row(int64_t j0, int64_t j1, int32_t p, int lane, uint32_t *bits, const int32_t *__restrict__ adj,
-                                                   const int32_t *__restrict__ color, int32_t *__restrict__ cnt, int32_t *__restrict__ next,
-                                                   Counter *next_count, int64_t cap, int32_t *error) {
-    const int words = min(p / 32 + 1, kBitWords);  // bits 0..p = colours 1..p+1
-    for (int w = lane; w < words; w += kGroup) bits[w] = 0;
-    group_phase();
-    for (int64_t j = j0 + lane; j < j1; j += kGroup) {
-        const int32_t w = adj[j];
-        const int32_t c = load_now(&color[w]);
-        if (c != 0) {
-            const int32_t b = c - 1;
-            if (b >= 0 && b <= p && (b >> 5) < words) atomicOr(&bits[b >> 5], 1u << (b & 31));
-        } else {
-            release_successor(w, cnt, next, next_count, cap, error);
-        }
-    }
-    group_phase();
-    int32_t best = INT_MAX;
-    for (int w = lane; w < words; w += kGroup) {
-        const uint32_t free = ~bits[w];
-        if (free) best = min(best, w * 32 + __ffs(free) - 1);
-    }
-    for (int o = kGroup / 2; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o, kGroup));
-    group_phase();  // (the next vertex of this group zeroes the same words)
-    return best <= p ? best + 1 : 0;
-}
-
-// the part of one LONG row that `threads` threads walk together: the bitmap is slab[0 .. p/32], zeroed, set by idempotent ORs
-template <class Counter>
-__device__ __forceinline__ void color_long_walk(int64_t j0, int64_t j1, int32_t p, int64_t tid, int64_t threads, uint32_t *__restrict__ slab,
-                                                const int32_t *__restrict__ adj, const int32_t *__restrict__ color, int32_t *__restrict__ cnt,
-                                                int32_t *__restrict__ next, Counter *next_count, int64_t cap, int32_t *error) {
-    for (int64_t j = j0 + tid; j < j1; j += threads) {
-        const int32_t w = adj[j];
-        const int32_t c = load_now(&color[w]);
-        if (c != 0) {
-            const int32_t b = c - 1;
-            if (b >= 0 && b <= p) {
-                const uint32_t bit = 1u << (b & 31);
-                if (!(load_now(&slab[b >> 5]) & bit)) atomicOr(&slab[b >> 5], bit);  // (a stale read costs an atomic, never the result)
-            }
-        } else {
-            release_successor(w, cnt, next, next_count, cap, error);
-        }
-    }
+    if ((threadIdx.x & 63) == 0 && mx) atomicMax(&ctrl->max_pred, mx);
 }
 
 // first zero bit of slab[0 .. p/32] by all threads of the workgroup (every thread must call it); 0-based, INT_MAX if none
-__device__ __forceinline__ int32_t first_free_long(const uint32_t *__restrict__ slab, int32_t p, int tid, int threads, int32_t *s_best) {
-    if (tid == 0) *s_best = INT_MAX;
+__device__ __forceinline__ int32_t first_free_long(const uint32_t *__restrict__ slab, int32_t p, int tid, int threads) {
+    __shared__ int32_t s_best;
+    if (tid == 0) s_best = INT_MAX;
     __syncthreads();
     const int32_t words = p / 32 + 1;
     for (int32_t w = tid; w < words; w += threads) {
         const uint32_t free = ~load_now(&slab[w]);
         if (free) {
-            atomicMin(s_best, w * 32 + __ffs(free) - 1);
+            atomicMin(&s_best, w * 32 + __ffs(free) - 1);
             break;  // (this thread's later words are higher)
         }
     }
     __syncthreads();
-    const int32_t best = *s_best;
+    const int32_t best = s_best;
     __syncthreads();
     return best;
 }
 
-// one round, grid-wide: a 16-lane group per frontier vertex; rows above kLongRow are parked for k_color_round_long, each with its piece of the slab
-__global__ __launch_bounds__(256) void k_color_round(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                     const int32_t *__restrict__ pred, int32_t *__restrict__ color, int32_t *__restrict__ round_of,
-                                                     int32_t *__restrict__ cnt, const int32_t *__restrict__ cur, int32_t *__restrict__ next,
-                                                     int32_t *__restrict__ longs, unsigned long long *__restrict__ long_slab, int64_t long_cap,
-                                                     unsigned long long slab_cap, ColorCtrl *__restrict__ ctrl) {
-    __shared__ uint32_t s_bits[256 / kGroup][kBitWords];
-    const int lane = threadIdx.x & (kGroup - 1);
-    uint32_t *bits = s_bits[threadIdx.x / kGroup];
-    const int64_t group0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / kGroup;
-    const int64_t groups = (int64_t(gridDim.x) * blockDim.x) / kGroup;
-    const int32_t count = ctrl->count, round = ctrl->round;
-    int32_t top = 0;
-    for (int64_t i = group0; i < count; i += groups) {  // (a group is on its own from here: its shuffles and its bitmap stay inside it)
-        const int32_t x = cur[i];
-        const int64_t j0 = off[x], j1 = off[x + 1];
+// Jones–Plassmann as a policy of the engine: one pass over the row of frontier vertex x marks the colours of its predecessors and releases its
+// successors; then x takes the first free colour
+struct ColorJp {
+    static constexpr int kGroupWords = kBitWords;
+    static constexpr bool kNotes = true;  // a parked row's note = where its bitmap starts in the slab
+    int64_t n;
+    const int64_t *off;
+    const int32_t *adj, *pred;
+    int32_t *color, *round_of, *cnt;
+    uint32_t *slab;
+    unsigned long long slab_cap, *slab_used;  // (slab_used, colors: the words of the control block)
+    int32_t *colors;
+    int32_t top;  // largest colour this thread gave (the kernel argument is every thread's own copy)
+
+    __device__ __forceinline__ void give(int32_t x, int32_t c, int32_t round, int32_t *error) {
+        if (c == 0) *error = 1;
+        store_now(&color[x], c);
+        round_of[x] = round;
+        top = max(top, c);
+    }
+    // row entry w: a colour is a predecessor's, and is marked by `mark`; 0 is a successor — its counter drops, and the decrement that brings it
+    // to 0 queues it
+    template <class Mark>
+    __device__ __forceinline__ void visit(int32_t w, int32_t p, const NextQueue &q, Mark mark) const {
+        const int32_t c = load_now(&color[w]);
+        if (c != 0) {
+            if (c - 1 >= 0 && c - 1 <= p) mark(c - 1);
+        } else if (atomicSub(&cnt[w], 1) == 1) {
+            q.push(w);
+        }
+    }
+    // SHORT row: the forbidden bitmap in `bits` (kBitWords words of LDS, the group's own); cannot find none: at most p of the p + 1 bits are set
+    __device__ __forceinline__ void short_row(int32_t x, int64_t j0, int64_t j1, int lane, int32_t round, uint32_t *bits, const NextQueue &q) {
         const int32_t p = pred[x];
-        if (j1 - j0 > kLongRow) {
-            if (lane == 0) {
-                const unsigned long long words = (unsigned long long)(p / 32 + 1);
-                const int64_t pos = int64_t(atomicAdd(&ctrl->nlong, 1));
-                const unsigned long long at = atomicAdd(&ctrl->slab_used, words);
-                if (pos < long_cap && at + words <= slab_cap) {
-                    longs[pos] = x;
-                    long_slab[pos] = at;
-                } else {
-                    ctrl->error = 1;
-                }
-            }
-            continue;
+        const int words = min(p / 32 + 1, kBitWords);  // bits 0..p = colours 1..p+1
+        for (int w = lane; w < words; w += kGroup) bits[w] = 0;
+        group_phase();
+        for (int64_t j = j0 + lane; j < j1; j += kGroup)
+            visit(adj[j], p, q, [&](int32_t b) {
+                if ((b >> 5) < words) atomicOr(&bits[b >> 5], 1u << (b & 31));
+            });
+        group_phase();
+        int32_t best = INT_MAX;
+        for (int w = lane; w < words; w += kGroup) {
+            const uint32_t free = ~bits[w];
+            if (free) best = min(best, w * 32 + __ffs(free) - 1);
         }
-        const int32_t c = color_short_row(j0, j1, p, lane, bits, adj, color, cnt, next, &ctrl->next, n, &ctrl->error);
-        if (lane == 0) {
-            if (c == 0) ctrl->error = 1;
-            store_now(&color[x], c);
-            round_of[x] = round;
-            top = max(top, c);
-        }
+        for (int o = kGroup / 2; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o, kGroup));
+        group_phase();  // (the next vertex of this group zeroes the same words)
+        if (lane == 0) give(x, best <= p ? best + 1 : 0, round, q.error);
     }
-    if (top) atomicMax(&ctrl->colors, top);
-}
-
-// … its long rows: all workgroups walk each of them together
-__global__ __launch_bounds__(256) void k_color_round_long(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                          const int32_t *__restrict__ pred, const int32_t *__restrict__ color,
-                                                          int32_t *__restrict__ cnt, int32_t *__restrict__ next, const int32_t *__restrict__ longs,
-                                                          const unsigned long long *__restrict__ long_slab, int64_t long_cap,
-                                                          uint32_t *__restrict__ slab, ColorCtrl *__restrict__ ctrl) {
-    if (ctrl->error) return;  // (a parked row without its piece of the slab)
-    const int64_t nlong = min(int64_t(ctrl->nlong), long_cap);
-    const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, threads = int64_t(gridDim.x) * blockDim.x;
-    for (int64_t i = 0; i < nlong; ++i) {
-        const int32_t x = longs[i];
-        color_long_walk(off[x], off[x + 1], pred[x], tid, threads, slab + long_slab[i], adj, color, cnt, next, &ctrl->next, n, &ctrl->error);
+    // LONG row: its piece of the slab, pred/32 + 1 zeroed words …
+    __device__ __forceinline__ void park(int32_t x, int32_t, unsigned long long *notes, int64_t pos, int32_t *error) const {
+        const unsigned long long words = (unsigned long long)(pred[x] / 32 + 1);
+        const unsigned long long at = atomicAdd(slab_used, words);
+        if (at + words <= slab_cap) notes[pos] = at;
+        else *error = 1;
     }
-}
-
-// … their colours (ONE workgroup: the bitmaps are complete only behind the kernel boundary), and the round boundary: the next frontier becomes
-// the current one
-__global__ __launch_bounds__(kTailThreads) void k_color_pick_advance(const int32_t *__restrict__ pred, int32_t *__restrict__ color,
-                                                                     int32_t *__restrict__ round_of, const int32_t *__restrict__ longs,
-                                                                     const unsigned long long *__restrict__ long_slab, int64_t long_cap,
-                                                                     const uint32_t *__restrict__ slab, ColorCtrl *__restrict__ ctrl) {
-    __shared__ int32_t s_best;
-    const int tid = threadIdx.x;
-    const int64_t nlong = ctrl->error ? 0 : min(int64_t(ctrl->nlong), long_cap);
-    const int32_t round = ctrl->round;
-    int32_t top = 0, bad = 0;
-    for (int64_t i = 0; i < nlong; ++i) {
-        const int32_t x = longs[i];
+    // … set by idempotent ORs of many threads together …
+    __device__ __forceinline__ void long_walk(int32_t x, unsigned long long note, int64_t tid, int64_t threads, const NextQueue &q) const {
+        uint32_t *bits = slab + note;
         const int32_t p = pred[x];
-        const int32_t best = first_free_long(slab + long_slab[i], p, tid, kTailThreads, &s_best);
-        if (tid == 0) {
-            if (best > p) bad = 1;
-            const int32_t c = best > p ? 0 : best + 1;
-            store_now(&color[x], c);
-            round_of[x] = round;
-            top = max(top, c);
-        }
+        const int64_t j1 = off[x + 1];
+        for (int64_t j = off[x] + tid; j < j1; j += threads)
+            visit(adj[j], p, q, [&](int32_t b) {
+                const uint32_t bit = 1u << (b & 31);
+                if (!(load_now(&bits[b >> 5]) & bit)) atomicOr(&bits[b >> 5], bit);  // (a stale read costs an atomic, never the result)
+            });
     }
-    if (tid == 0) {
-        if (bad) ctrl->error = 1;
-        if (top > ctrl->colors) ctrl->colors = top;  // (the only workgroup of the only kernel that runs now)
-        ctrl->colored += ctrl->count;
-        ctrl->count = ctrl->next;
-        ctrl->next = 0;
-        ctrl->nlong = 0;
-        ctrl->round += 1;
-        ctrl->cur ^= 1;
+    // … and searched when they are complete
+    __device__ __forceinline__ void settle(int32_t x, unsigned long long note, int32_t round, int tid, int32_t *error) {
+        const int32_t p = pred[x];
+        const int32_t best = first_free_long(slab + note, p, tid, kTailThreads);
+        if (tid == 0) give(x, best > p ? 0 : best + 1, round, error);
     }
-}
-
-// rounds inside ONE workgroup: the round boundary is a __syncthreads().  Runs while 0 < frontier <= wg_frontier; returns with the control block
-// describing the state it stopped in (frontier empty: done; larger than wg_frontier, or ctrl->bail — a round too heavy for one workgroup —:
-// the grid-wide kernels go on).  color[], cnt[], the slab and the two frontier buffers stay in global memory and are read with loads that
-// bypass the vector cache; the counters and the short rows' bitmaps live in LDS.
-__global__ __launch_bounds__(kTailThreads) void k_color_tail(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                             const int32_t *__restrict__ pred, int32_t *__restrict__ color,
-                                                             int32_t *__restrict__ round_of, int32_t *__restrict__ cnt, int32_t *__restrict__ f0,
-                                                             int32_t *__restrict__ f1, uint32_t *__restrict__ slab, unsigned long long slab_cap,
-                                                             int32_t wg_frontier, ColorCtrl *__restrict__ ctrl) {
-    __shared__ int32_t s_count, s_next, s_error, s_flag, s_nlong, s_nlong_seen, s_best, s_top;
-    __shared__ unsigned long long s_work;
-    __shared__ int32_t s_long[kTailLong];
-    __shared__ unsigned long long s_long_slab[kTailLong];
-    __shared__ uint32_t s_bits[kTailThreads / kGroup][kBitWords];
-    const int tid = threadIdx.x, lane = tid & (kGroup - 1), group = tid / kGroup;
-    constexpr int groups = kTailThreads / kGroup;
-    uint32_t *bits = s_bits[group];
-    int32_t round = ctrl->round, colored = ctrl->colored, curi = ctrl->cur, bail = 0;
-    if (tid == 0) {
-        s_count = ctrl->count;
-        s_next = 0;
-        s_error = 0;
-        s_flag = 0;
-        s_nlong = 0;
-        s_nlong_seen = 0;
-        s_work = 0;
-        s_top = 0;
+    __device__ __forceinline__ void finish() const {
+        if (top) atomicMax(colors, top);
     }
-    __syncthreads();
-    for (;;) {
-        const int32_t count = s_count;
-        if (count == 0 || count > wg_frontier) break;
-        const int32_t *cur = curi ? f1 : f0;
-        int32_t *next = curi ? f0 : f1;
-        // what the round would cost here (core.hip's rule): one workgroup takes it only if no row is above kWgRowMax, its long rows fit the
-        // list and all its rows together hold at most kWgWorkMax entries — else every other CU would idle behind this one
-        unsigned long long work = 0;
-        int32_t nl = 0;
-        for (int32_t i = tid; i < count; i += kTailThreads) {
-            const int32_t x = load_now(&cur[i]);
-            const int64_t len = off[x + 1] - off[x];
-            if (len > kWgRowMax) s_flag = 1;
-            if (len > kLongRow) ++nl;
-            work += (unsigned long long)len;
-        }
-        if (work) atomicAdd(&s_work, work);
-        if (nl) atomicAdd(&s_nlong_seen, nl);
-        __syncthreads();
-        if (s_flag || s_nlong_seen > kTailLong || s_work > (unsigned long long)kWgWorkMax) {
-            bail = 1;
-            break;
-        }
-        int32_t top = 0;
-        for (int32_t i = group; i < count; i += groups) {
-            const int32_t x = load_now(&cur[i]);
-            const int64_t j0 = off[x], j1 = off[x + 1];
-            const int32_t p = pred[x];
-            if (j1 - j0 > kLongRow) {
-                if (lane == 0) {  // at most kTailLong of them: checked above
-                    const unsigned long long words = (unsigned long long)(p / 32 + 1);
-                    const int32_t pos = atomicAdd(&s_nlong, 1);
-                    const unsigned long long at = atomicAdd(&ctrl->slab_used, words);
-                    if (pos < kTailLong && at + words <= slab_cap) {
-                        s_long[pos] = x;
-                        s_long_slab[pos] = at;
-                    } else {
-                        s_error = 1;
-                    }
-                }
-                continue;
-            }
-            const int32_t c = color_short_row(j0, j1, p, lane, bits, adj, color, cnt, next, &s_next, n, &s_error);
-            if (lane == 0) {
-                if (c == 0) s_error = 1;
-                store_now(&color[x], c);
-                round_of[x] = round;
-                top = max(top, c);
-            }
-        }
-        if (top) atomicMax(&s_top, top);
-        __syncthreads();
-        const int32_t nlong = s_error ? 0 : min(s_nlong, kTailLong);
-        __syncthreads();  // every thread has read s_error before the walk may set it: the loops below hold barriers, their trip count must be uniform
-        for (int32_t i = 0; i < nlong; ++i) {
-            const int32_t x = s_long[i];
-            color_long_walk(off[x], off[x + 1], pred[x], tid, kTailThreads, slab + s_long_slab[i], adj, color, cnt, next, &s_next, n, &s_error);
-        }
-        __syncthreads();
-        for (int32_t i = 0; i < nlong; ++i) {
-            const int32_t x = s_long[i];
-            const int32_t p = pred[x];
-            const int32_t best = first_free_long(slab + s_long_slab[i], p, tid, kTailThreads, &s_best);
-            if (tid == 0) {
-                if (best > p) s_error = 1;
-                const int32_t c = best > p ? 0 : best + 1;
-                store_now(&color[x], c);
-                round_of[x] = round;
-                if (c > s_top) s_top = c;
-            }
-        }
-        __syncthreads();
-        colored += count;
-        round += 1;
-        curi ^= 1;
-        if (tid == 0) {
-            s_count = s_error ? 0 : min(s_next, int32_t(min(n, int64_t(INT_MAX))));
-            s_next = 0;
-            s_nlong = 0;
-            s_nlong_seen = 0;
-            s_work = 0;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        ctrl->count = s_count;
-        ctrl->next = 0;
-        ctrl->nlong = 0;
-        ctrl->round = round;
-        ctrl->colored = colored;
-        ctrl->cur = curi;
-        ctrl->bail = bail;
-        if (s_top > ctrl->colors) ctrl->colors = s_top;
-        if (s_error) ctrl->error = 1;
-    }
-}
+};
 
 // ---- verify -------------------------------------------------------------------------------------------------------------------------
 
@@ -425,9 +194,7 @@ __global__ __launch_bounds__(256) void k_cv_rows(int64_t n, const int64_t *__res
         }
         if (j1 - j0 > kLongRow) {
             if (lane == 0) {
-                const int64_t pos = int64_t(atomicAdd(&ctl[0], 1));
-                if (pos < long_cap) longs[pos] = int32_t(v);
-                else ctl[1] = 1;
+                append_checked(longs, &ctl[0], long_cap, int32_t(v), &ctl[1]);
             }
             continue;
         }
@@ -516,8 +283,9 @@ int gmsx_coloring_jp(const gmsx_graph *g, const int32_t *ordering, int rank_form
         ColorCtrl *ctrl = d_ctrl.as<ColorCtrl>();
         int32_t *rank = own_rank ? d_rank.as<int32_t>() : d_in.as<int32_t>();
         int32_t *cnt = d_cnt.as<int32_t>(), *pred = d_pred.as<int32_t>(), *color = d_color.as<int32_t>(), *rnd = d_round.as<int32_t>();
-        int32_t *f[2] = {d_f0.as<int32_t>(), d_f1.as<int32_t>()};
         uint32_t *slab = d_slab.as<uint32_t>();
+        const FrontierBufs bufs{{d_f0.as<int32_t>(), d_f1.as<int32_t>()}, d_long.as<int32_t>(), d_long_slab.as<unsigned long long>(), long_cap};
+        const ColorJp jp{n, g->off, g->adj, pred, color, rnd, cnt, slab, slab_cap, &ctrl->slab_used, &ctrl->colors, 0};
         long long wg_frontier = opt_int("COLOR_WG_FRONTIER", kWgFrontierDefault);  // test hook: 0 = every round a kernel boundary
         wg_frontier = std::max<long long>(0, std::min<long long>(wg_frontier, INT_MAX));
 
@@ -538,7 +306,7 @@ int gmsx_coloring_jp(const gmsx_graph *g, const int32_t *ordering, int rank_form
             GMSX_HIP(hipStreamSynchronize(s));
             if (ctl[2]) return GMSX_ERR_INVALID;
         } else {
-            hipLaunchKernelGGL(k_color_iota, dim3(tb), dim3(256), 0, s, n, rank);
+            hipLaunchKernelGGL(k_iota, dim3(tb), dim3(256), 0, s, n, rank);  // getSimpleIdOrdering: what coloring.cc:25-30 hands to JonesV3
         }
         const unsigned lb = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
         const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
@@ -546,7 +314,7 @@ int gmsx_coloring_jp(const gmsx_graph *g, const int32_t *ordering, int rank_form
         hipLaunchKernelGGL(k_oq_later, dim3(lb), dim3(256), 0, s, n, g->off, g->adj, rank, cnt, d_long.as<int32_t>(), long_cap, d_ctl.as<int32_t>());
         hipLaunchKernelGGL(k_oq_later_long, dim3(long_grid), dim3(256), 0, s, g->off, g->adj, rank, cnt, d_long.as<int32_t>(), long_cap,
                            d_ctl.as<int32_t>());
-        hipLaunchKernelGGL(k_color_select, dim3(sweep), dim3(256), 0, s, n, cnt, pred, ctrl, f[0]);
+        hipLaunchKernelGGL(k_color_select, dim3(sweep), dim3(256), 0, s, n, cnt, pred, ctrl, bufs.f[0]);
         launches += 4;
         ColorCtrl h;
         std::memset(&h, 0, sizeof h);
@@ -557,35 +325,11 @@ int gmsx_coloring_jp(const gmsx_graph *g, const int32_t *ordering, int rank_form
         if (ctl[1] || h.error || h.count <= 0 || h.count > n) return GMSX_ERR_KERNEL;  // (a permutation has a maximum: the first frontier is not empty)
         res.first_round = h.count;
         res.max_pred = h.max_pred;
-        while (h.count > 0) {
-            if (h.count <= wg_frontier && !h.bail) {
-                hipLaunchKernelGGL(k_color_tail, dim3(1), dim3(kTailThreads), 0, s, n, g->off, g->adj, pred, color, rnd, cnt, f[0], f[1], slab, slab_cap,
-                                   int32_t(wg_frontier), ctrl);
-                launches += 1;
-            } else {
-                const unsigned rb = unsigned(std::min<int64_t>((int64_t(h.count) * kGroup + 255) / 256, int64_t(cus) * 32));
-                hipLaunchKernelGGL(k_color_round, dim3(rb), dim3(256), 0, s, n, g->off, g->adj, pred, color, rnd, cnt, f[h.cur], f[h.cur ^ 1],
-                                   d_long.as<int32_t>(), d_long_slab.as<unsigned long long>(), long_cap, slab_cap, ctrl);
-                hipLaunchKernelGGL(k_color_round_long, dim3(long_grid), dim3(256), 0, s, n, g->off, g->adj, pred, color, cnt, f[h.cur ^ 1],
-                                   d_long.as<int32_t>(), d_long_slab.as<unsigned long long>(), long_cap, slab, ctrl);
-                hipLaunchKernelGGL(k_color_pick_advance, dim3(1), dim3(kTailThreads), 0, s, pred, color, rnd, d_long.as<int32_t>(),
-                                   d_long_slab.as<unsigned long long>(), long_cap, slab, ctrl);
-                launches += 3;
-                if (h.bail) {
-                    h.bail = 0;
-                    GMSX_HIP(hipMemsetAsync(&ctrl->bail, 0, sizeof(int32_t), s));
-                }
-            }
-            const int32_t colored_was = h.colored, round_was = h.round;
-            GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
-            GMSX_HIP(hipStreamSynchronize(s));
-            if (h.error || h.count < 0 || h.colored > n || h.count > n - h.colored) return GMSX_ERR_KERNEL;
-            if (!h.bail && (h.colored <= colored_was || h.round <= round_was)) return GMSX_ERR_KERNEL;  // a step that made no progress
-        }
+        if (int rc = run_frontier_rounds(jp, bufs, ctrl, h, wg_frontier, &launches)) return rc;
         GMSX_HIP(hipEventRecord(c.ev[1], s));
         GMSX_HIP(hipStreamSynchronize(s));
         GMSX_HIP(hipGetLastError());
-        if (h.colored != n || h.colors < 1 || h.colors > h.max_pred + 1 || h.slab_used > slab_cap) return GMSX_ERR_KERNEL;
+        if (h.done != n || h.colors < 1 || h.colors > h.max_pred + 1 || h.slab_used > slab_cap) return GMSX_ERR_KERNEL;
         res.colors = h.colors;
         res.rounds = h.round;
         // the outputs are written only now, when nothing can fail but the copies themselves

@@ -14,14 +14,12 @@
 // vertices a round removes is a fact about the integers, not about the arrival order of the atomics; the order inside the queues is not, and
 // never reaches an output: the result is sorted by (round, id) at the end.
 //
-// COST SHAPE.  Hundreds of rounds, almost all of a handful of vertices: the fixed cost per round decides.  A round boundary is a kernel
-// boundary (k_core_round + k_core_round_long + k_core_advance, then the host reads 48 bytes) or — while the frontier holds at most
-// CORE_WG_FRONTIER vertices with at most kWgWorkMax CSR entries between them and no row above kWgRowMax — a __syncthreads() of k_core_tail, ONE workgroup that runs round after round until
-// the frontier empties (the level is done: the next k needs a sweep over all vertices) or outgrows the threshold.  No workgroup ever waits
-// for another one.  Rows are binned by length: a 16-lane group per vertex up to kLongRow entries, longer rows by all workgroups of
-// k_core_round_long (all threads of the workgroup in k_core_tail) together — no lane walks a long row alone.
+// COST SHAPE.  Hundreds of rounds, almost all of a handful of vertices: the fixed cost per round decides.  The rounds are those of the frontier
+// engine (frontier_rounds.hpp: the row binning, the one-workgroup tail under CORE_WG_FRONTIER and its hand-back rule); this file supplies the
+// per-vertex work (CorePeel), the level sweep and the final checks.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
+#include "frontier_rounds.hpp"
 #include "order_rank.hpp"
 
 #include <algorithm>
@@ -35,31 +33,11 @@ namespace gmsx {
 
 namespace {
 
-// UNMEASURED: none of these bounds has a timing behind it yet (tools/core_probe.py is the measurement).  They follow the round
-// table of the peel on R-MAT graphs (almost every round removes fewer than 256 vertices) and the row shapes named there.
-// (kGroup = 16 lanes per frontier vertex of a short row and kLongRow = 1024, above which a row is walked by many waves together: order_rank.hpp)
-constexpr int kWgRowMax = 32768;    // k_core_tail hands a frontier with a longer row back to the grid-wide kernels
-constexpr int kTailThreads = 1024;
-constexpr int kTailLong = 256;      // long rows one round of k_core_tail can park for its whole-workgroup phase; more: the round goes back to the grid
-constexpr int kWgWorkMax = 1 << 18; // CSR entries one round of k_core_tail may walk (256 per thread); more: the round goes back to the grid
-constexpr long long kWgFrontierDefault = 512;
-
-// control block of one peel (device, mirrored to the host after every step)
-struct CoreCtrl {
-    int32_t count;      // vertices in the current frontier
-    int32_t next;       // appended to the next one so far
-    int32_t round;      // index of the round the current frontier leaves in
-    int32_t k;          // current level
-    int32_t removed;    // vertices that have left in finished rounds
-    int32_t error;      // an append hit its bound
-    int32_t nlong;      // long rows parked by k_core_round for k_core_round_long
-    int32_t bail;       // k_core_tail met a round too heavy for one workgroup (row length, long rows, total entries): it belongs to the grid-wide kernels
-    int32_t min_deg;    // level sweep: smallest remaining degree
-    int32_t cur;        // which of the two frontier buffers is the current one
-    int32_t pad[2];
+// control block of one peel: the engine's, plus the level
+struct CoreCtrl : FrontierCtrl {  // (done = vertices that have left in finished rounds)
+    int32_t k;        // current level
+    int32_t min_deg;  // level sweep: smallest remaining degree
 };
-
-__device__ __forceinline__ int32_t load_now(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ void k_core_init(int64_t n, const int64_t *__restrict__ off, int32_t *__restrict__ deg, int32_t *__restrict__ round_of) {
     const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -83,7 +61,6 @@ __global__ __launch_bounds__(256) void k_core_min(int64_t n, const int32_t *__re
 // … second half: the remaining vertices of that degree are the level's first frontier (one wave-aggregated append per wave)
 __global__ __launch_bounds__(256) void k_core_select(int64_t n, const int32_t *__restrict__ deg, int32_t k_done, CoreCtrl *__restrict__ ctrl,
                                                      int32_t *__restrict__ frontier) {
-    const int lane = threadIdx.x & 63;
     const int32_t k = ctrl->min_deg;
     if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->k = k;  // (the others read min_deg, not k)
     const int64_t stride = int64_t(gridDim.x) * blockDim.x;
@@ -94,180 +71,42 @@ __global__ __launch_bounds__(256) void k_core_select(int64_t n, const int32_t *_
             const int32_t d = deg[v];
             take = d > k_done && d <= k;
         }
-        const unsigned long long m = __ballot(take);
-        if (m == 0) continue;
-        int32_t base = 0;
-        if (lane == 0) base = atomicAdd(&ctrl->count, int32_t(__popcll(m)));
-        base = __shfl(base, 0);
-        if (take) {
-            const int64_t pos = int64_t(base) + __popcll(m & ((1ull << lane) - 1ull));
-            if (pos < n) frontier[pos] = int32_t(v);
-            else ctrl->error = 1;
-        }
+        wave_append(take, int32_t(v), frontier, &ctrl->count, n, &ctrl->error);
     }
 }
 
-// the PUSH of one frontier vertex's row part [j0, j1) by W lanes: a neighbour still above k loses one; the decrement that brings it to k queues it
-template <class Counter>
-__device__ __forceinline__ void core_walk(int64_t j0, int64_t j1, int64_t lane, int64_t width, int32_t k, const int32_t *__restrict__ adj,
-                                          int32_t *__restrict__ deg, int32_t *__restrict__ next, Counter *next_count, int64_t cap, int32_t *error) {
-    for (int64_t j = j0 + lane; j < j1; j += width) {
-        const int32_t w = adj[j];
-        if (load_now(&deg[w]) <= k) continue;  // has left, is leaving or is queued (deg only ever falls: a stale value costs an atomic, never the result)
-        if (atomicSub(&deg[w], 1) == k + 1) {
-            const int64_t pos = int64_t(atomicAdd(next_count, 1));
-            if (pos < cap) next[pos] = w;
-            else *error = 1;
-        }
-    }
-}
+// the peel as a policy of the engine: a frontier vertex leaves (core number k, this round) and PUSHes a decrement along its row
+struct CorePeel {
+    static constexpr int kGroupWords = 0;
+    static constexpr bool kNotes = false;
+    int64_t n;
+    const int64_t *off;
+    const int32_t *adj;
+    int32_t *deg, *round_of, *core;
+    int32_t k;  // the level (the host sets it from the control block it read)
 
-// one round, grid-wide: a 16-lane group per frontier vertex; rows above kLongRow are parked for k_core_round_long
-__global__ __launch_bounds__(256) void k_core_round(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                    int32_t *__restrict__ deg, int32_t *__restrict__ round_of, int32_t *__restrict__ core,
-                                                    const int32_t *__restrict__ cur, int32_t *__restrict__ next, int32_t *__restrict__ longs,
-                                                    int64_t long_cap, CoreCtrl *__restrict__ ctrl) {
-    const int lane = threadIdx.x & (kGroup - 1);
-    const int64_t group0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / kGroup;
-    const int64_t groups = (int64_t(gridDim.x) * blockDim.x) / kGroup;
-    const int32_t count = ctrl->count, k = ctrl->k, round = ctrl->round;
-    for (int64_t i = group0; i < count; i += groups) {
-        const int32_t x = cur[i];
-        const int64_t j0 = off[x], j1 = off[x + 1];
-        if (lane == 0) {
-            round_of[x] = round;
-            core[x] = k;
-        }
-        if (j1 - j0 > kLongRow) {
-            if (lane == 0) {
-                const int64_t pos = int64_t(atomicAdd(&ctrl->nlong, 1));
-                if (pos < long_cap) longs[pos] = x;
-                else ctrl->error = 1;
-            }
-            continue;
-        }
-        core_walk(j0, j1, lane, kGroup, k, adj, deg, next, &ctrl->next, n, &ctrl->error);
+    __device__ __forceinline__ void leave(int32_t x, int32_t round) const {
+        round_of[x] = round;
+        core[x] = k;
     }
-}
-
-// … its long rows: all workgroups walk each of them together
-__global__ __launch_bounds__(256) void k_core_round_long(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                         int32_t *__restrict__ deg, int32_t *__restrict__ next, const int32_t *__restrict__ longs,
-                                                         int64_t long_cap, CoreCtrl *__restrict__ ctrl) {
-    const int64_t nlong = min(int64_t(ctrl->nlong), long_cap);
-    const int32_t k = ctrl->k;
-    const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, threads = int64_t(gridDim.x) * blockDim.x;
-    for (int64_t i = 0; i < nlong; ++i) {
-        const int32_t x = longs[i];
-        core_walk(off[x], off[x + 1], tid, threads, k, adj, deg, next, &ctrl->next, n, &ctrl->error);
+    // row part [j0, j1) by `width` lanes: a neighbour still above k loses one; the decrement that brings it to k queues it
+    __device__ __forceinline__ void walk(int64_t j0, int64_t j1, int64_t lane, int64_t width, const NextQueue &q) const {
+        for (int64_t j = j0 + lane; j < j1; j += width) {
+            const int32_t w = adj[j];
+            if (load_now(&deg[w]) <= k) continue;  // has left, is leaving or is queued (deg only ever falls: a stale value costs an atomic, never the result)
+            if (atomicSub(&deg[w], 1) == k + 1) q.push(w);
+        }
     }
-}
-
-// … and the round boundary: the next frontier becomes the current one
-__global__ void k_core_advance(CoreCtrl *__restrict__ ctrl) {
-    ctrl->removed += ctrl->count;
-    ctrl->count = ctrl->next;
-    ctrl->next = 0;
-    ctrl->nlong = 0;
-    ctrl->round += 1;
-    ctrl->cur ^= 1;
-}
-
-// rounds inside ONE workgroup: the round boundary is a __syncthreads().  Runs while 0 < frontier <= wg_frontier; returns with the control
-// block describing the state it stopped in (frontier empty: level done; larger than wg_frontier, or ctrl->bail — a round too heavy for one workgroup —: the grid-wide kernels go on).
-// The two frontier buffers stay in global memory (they are bounds-checked against n there and may be handed back at any round), read with
-// loads that bypass the vector cache; the counters live in LDS.
-__global__ __launch_bounds__(kTailThreads) void k_core_tail(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                            int32_t *__restrict__ deg, int32_t *__restrict__ round_of, int32_t *__restrict__ core,
-                                                            int32_t *__restrict__ f0, int32_t *__restrict__ f1, int32_t wg_frontier,
-                                                            CoreCtrl *__restrict__ ctrl) {
-    __shared__ int32_t s_count, s_next, s_error, s_flag, s_nlong, s_nlong_seen;
-    __shared__ unsigned long long s_work;
-    __shared__ int32_t s_long[kTailLong];
-    const int tid = threadIdx.x, lane = tid & (kGroup - 1), group = tid / kGroup;
-    constexpr int groups = kTailThreads / kGroup;
-    const int32_t k = ctrl->k;
-    int32_t round = ctrl->round, removed = ctrl->removed, curi = ctrl->cur, bail = 0;
-    if (tid == 0) {
-        s_count = ctrl->count;
-        s_next = 0;
-        s_error = 0;
-        s_flag = 0;
-        s_nlong = 0;
-        s_nlong_seen = 0;
-        s_work = 0;
+    __device__ __forceinline__ void short_row(int32_t x, int64_t j0, int64_t j1, int lane, int32_t round, uint32_t *, const NextQueue &q) const {
+        if (lane == 0) leave(x, round);
+        walk(j0, j1, lane, kGroup, q);
     }
-    __syncthreads();
-    for (;;) {
-        const int32_t count = s_count;
-        if (count == 0 || count > wg_frontier) break;
-        const int32_t *cur = curi ? f1 : f0;
-        int32_t *next = curi ? f0 : f1;
-        // what the round would cost here: one workgroup takes it only if no row is above kWgRowMax, its long rows fit the list and all its
-        // rows together hold at most kWgWorkMax entries — else every other CU would idle behind this one
-        unsigned long long work = 0;
-        int32_t nl = 0;
-        for (int32_t i = tid; i < count; i += kTailThreads) {
-            const int32_t x = load_now(&cur[i]);
-            const int64_t len = off[x + 1] - off[x];
-            if (len > kWgRowMax) s_flag = 1;
-            if (len > kLongRow) ++nl;
-            work += (unsigned long long)len;
-        }
-        if (work) atomicAdd(&s_work, work);
-        if (nl) atomicAdd(&s_nlong_seen, nl);
-        __syncthreads();
-        if (s_flag || s_nlong_seen > kTailLong || s_work > (unsigned long long)kWgWorkMax) {
-            bail = 1;
-            break;
-        }
-        for (int32_t i = group; i < count; i += groups) {
-            const int32_t x = load_now(&cur[i]);
-            const int64_t j0 = off[x], j1 = off[x + 1];
-            if (lane == 0) {
-                round_of[x] = round;
-                core[x] = k;
-            }
-            if (j1 - j0 > kLongRow) {
-                if (lane == 0) {  // at most kTailLong of them: checked above
-                    const int32_t pos = atomicAdd(&s_nlong, 1);
-                    if (pos < kTailLong) s_long[pos] = x;
-                    else s_error = 1;
-                }
-                continue;
-            }
-            core_walk(j0, j1, lane, kGroup, k, adj, deg, next, &s_next, n, &s_error);
-        }
-        __syncthreads();
-        const int32_t nlong = min(s_nlong, kTailLong);
-        for (int32_t i = 0; i < nlong; ++i) {
-            const int32_t x = s_long[i];
-            core_walk(off[x], off[x + 1], tid, kTailThreads, k, adj, deg, next, &s_next, n, &s_error);
-        }
-        __syncthreads();
-        removed += count;
-        round += 1;
-        curi ^= 1;
-        if (tid == 0) {
-            s_count = s_error ? 0 : min(s_next, int32_t(min(n, int64_t(INT_MAX))));
-            s_next = 0;
-            s_nlong = 0;
-            s_nlong_seen = 0;
-            s_work = 0;
-        }
-        __syncthreads();
+    __device__ __forceinline__ void park(int32_t x, int32_t round, unsigned long long *, int64_t, int32_t *) const { leave(x, round); }
+    __device__ __forceinline__ void long_walk(int32_t x, unsigned long long, int64_t tid, int64_t threads, const NextQueue &q) const {
+        walk(off[x], off[x + 1], tid, threads, q);
     }
-    if (tid == 0) {
-        ctrl->count = s_count;
-        ctrl->next = 0;
-        ctrl->nlong = 0;
-        ctrl->round = round;
-        ctrl->removed = removed;
-        ctrl->cur = curi;
-        ctrl->bail = bail;
-        if (s_error) ctrl->error = 1;
-    }
-}
+    __device__ __forceinline__ void finish() const {}
+};
 
 __global__ void k_core_keys(int64_t n, const int32_t *__restrict__ hi, unsigned long long *__restrict__ keys) {
     const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -322,63 +161,41 @@ int core_peel(const gmsx_graph *g, DevBuf &d_core, DevBuf &d_round, gmsx_core_in
     if (int rc = dalloc<int32_t>(d_long, long_cap)) return rc;
     if (int rc = dalloc<CoreCtrl>(d_ctrl, 1)) return rc;
     CoreCtrl *ctrl = d_ctrl.as<CoreCtrl>();
-    int32_t *deg = d_deg.as<int32_t>(), *core = d_core.as<int32_t>(), *round_of = d_round.as<int32_t>();
-    int32_t *f[2] = {d_f0.as<int32_t>(), d_f1.as<int32_t>()};
-    long long wg_frontier = opt_int("CORE_WG_FRONTIER", kWgFrontierDefault);  // test hook: 0 = every round a kernel boundary, large = every round it may take in k_core_tail
+    int32_t *deg = d_deg.as<int32_t>();
+    const FrontierBufs bufs{{d_f0.as<int32_t>(), d_f1.as<int32_t>()}, d_long.as<int32_t>(), nullptr, long_cap};
+    CorePeel peel{n, g->off, g->adj, deg, d_round.as<int32_t>(), d_core.as<int32_t>(), 0};
+    long long wg_frontier = opt_int("CORE_WG_FRONTIER", kWgFrontierDefault);  // test hook: 0 = every round a kernel boundary, large = every round the tail may take
     wg_frontier = std::max<long long>(0, std::min<long long>(wg_frontier, INT_MAX));
 
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
     const unsigned tb = unsigned((n + 255) / 256);
     const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
-    const unsigned long_grid = unsigned(cus) * 4;
     int launches = 1;
-    hipLaunchKernelGGL(k_core_init, dim3(tb), dim3(256), 0, s, n, g->off, deg, round_of);
+    hipLaunchKernelGGL(k_core_init, dim3(tb), dim3(256), 0, s, n, g->off, deg, peel.round_of);
     CoreCtrl h;
     std::memset(&h, 0, sizeof h);
     GMSX_HIP(hipMemsetAsync(ctrl, 0, sizeof(CoreCtrl), s));
     int32_t k_done = -1, levels = 0;
     int64_t top_core = 0;
-    while (h.removed < n) {
+    while (h.done < n) {
         // ---- the next level: k = smallest remaining degree, first frontier = the vertices that have it
         GMSX_HIP(hipMemsetAsync(&ctrl->min_deg, 0x7f, sizeof(int32_t), s));
         hipLaunchKernelGGL(k_core_min, dim3(sweep), dim3(256), 0, s, n, deg, k_done, ctrl);
-        hipLaunchKernelGGL(k_core_select, dim3(sweep), dim3(256), 0, s, n, deg, k_done, ctrl, f[h.cur]);
+        hipLaunchKernelGGL(k_core_select, dim3(sweep), dim3(256), 0, s, n, deg, k_done, ctrl, bufs.f[h.cur]);
         launches += 2;
         GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
-        if (h.error || h.count <= 0 || h.count > n - h.removed || h.min_deg <= k_done || h.k != h.min_deg) return GMSX_ERR_KERNEL;
-        const int64_t removed_before = h.removed;
+        if (h.error || h.count <= 0 || h.count > n - h.done || h.min_deg <= k_done || h.k != h.min_deg) return GMSX_ERR_KERNEL;
+        const int64_t removed_before = h.done;
         // ---- rounds of this level
-        while (h.count > 0) {
-            if (h.count <= wg_frontier && !h.bail) {
-                hipLaunchKernelGGL(k_core_tail, dim3(1), dim3(kTailThreads), 0, s, n, g->off, g->adj, deg, round_of, core, f[0], f[1],
-                                   int32_t(wg_frontier), ctrl);
-                launches += 1;
-            } else {
-                const unsigned rb = unsigned(std::min<int64_t>((int64_t(h.count) * kGroup + 255) / 256, int64_t(cus) * 32));
-                hipLaunchKernelGGL(k_core_round, dim3(rb), dim3(256), 0, s, n, g->off, g->adj, deg, round_of, core, f[h.cur], f[h.cur ^ 1],
-                                   d_long.as<int32_t>(), long_cap, ctrl);
-                hipLaunchKernelGGL(k_core_round_long, dim3(long_grid), dim3(256), 0, s, n, g->off, g->adj, deg, f[h.cur ^ 1], d_long.as<int32_t>(),
-                                   long_cap, ctrl);
-                hipLaunchKernelGGL(k_core_advance, dim3(1), dim3(1), 0, s, ctrl);
-                launches += 3;
-                if (h.bail) {
-                    h.bail = 0;
-                    GMSX_HIP(hipMemsetAsync(&ctrl->bail, 0, sizeof(int32_t), s));
-                }
-            }
-            const int32_t removed_was = h.removed, round_was = h.round;
-            GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
-            GMSX_HIP(hipStreamSynchronize(s));
-            if (h.error || h.count < 0 || h.removed > n || h.count > n - h.removed) return GMSX_ERR_KERNEL;
-            if (!h.bail && (h.removed <= removed_was || h.round <= round_was)) return GMSX_ERR_KERNEL;  // a step that made no progress
-        }
-        top_core = h.removed - removed_before;
+        peel.k = h.k;
+        if (int rc = run_frontier_rounds(peel, bufs, ctrl, h, wg_frontier, &launches)) return rc;
+        top_core = h.done - removed_before;
         k_done = h.k;
         ++levels;
     }
     GMSX_HIP(hipGetLastError());
-    if (h.removed != n) return GMSX_ERR_KERNEL;
+    if (h.done != n) return GMSX_ERR_KERNEL;
     info->degeneracy = k_done;
     info->levels = levels;
     info->rounds = h.round;

@@ -1,18 +1,12 @@
 // An order as the kernels consume it — rank[] on the device, validated — and later[v] = |{ w in N(v) : rank[w] > rank[v] }|: shared by
 // gmsx_order_quality (core.hip: the count IS the grade) and gmsx_coloring_jp (coloring.hip: the count is the predecessor counter of
-// Jones–Plassmann).  Also the row binning both translation units use: a kGroup-lane group per row up to kLongRow entries, longer rows
-// parked and walked by all workgroups together — no lane walks a long row alone.
+// Jones–Plassmann).  later[] is counted over ALL vertices with the row binning of frontier_rounds.hpp: a kGroup-lane group per row up to
+// kLongRow entries, longer rows parked and walked by all workgroups together.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "frontier_rounds.hpp"
 
 namespace gmsx {
 namespace {
-
-// UNMEASURED: they follow the row shapes of the R-MAT graphs, no timing is behind them yet.
-constexpr int kGroup = 16;      // lanes per vertex of a short row
-constexpr int kLongRow = 1024;  // longer rows are walked by many waves together
 
 // ordering -> rank[] (device) + validation: every entry in [0, n) and hit once
 __global__ void k_oq_rank(int64_t n, const int32_t *__restrict__ ordering, int rank_format, int32_t *__restrict__ rank, int32_t *__restrict__ seen,
@@ -43,9 +37,7 @@ __global__ __launch_bounds__(256) void k_oq_later(int64_t n, const int64_t *__re
             if (j1 - j0 > kLongRow) {
                 if (lane == 0) {
                     later[v] = 0;
-                    const int64_t pos = int64_t(atomicAdd(&ctl[0], 1));
-                    if (pos < long_cap) longs[pos] = int32_t(v);
-                    else ctl[1] = 1;
+                    append_checked(longs, &ctl[0], long_cap, int32_t(v), &ctl[1]);
                 }
                 cnt = -1;
             } else {

@@ -14,6 +14,7 @@
 // (ties: vertex id — the reference leaves them to __gnu_parallel); one push kernel.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
+#include "frontier_rounds.hpp"  // k_iota
 
 #include <algorithm>
 #include <cstring>
@@ -100,11 +101,6 @@ __global__ __launch_bounds__(256) void k_adg_push(int64_t batch, const unsigned 
             if (state[w] < 0) atomicSub(&deg[w], 1);  // w is still in the graph after this round: it loses neighbour x
         }
     }
-}
-
-__global__ void k_iota(int64_t n, int32_t *__restrict__ ids) {
-    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i < n) ids[i] = int32_t(i);
 }
 
 }  // namespace

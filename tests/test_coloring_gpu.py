@@ -6,6 +6,8 @@
   composition  color("sl") stays within degeneracy + 1 and verifies clean; color("lf") / color("ff") are the goldens of those orders
   shapes       cliques at the word boundaries of the bitmap, a clique of long rows, a star from both ends, a path of 4 096 rounds, a crown
                graph under two orders, an edgeless graph, the empty graph — closed-form answers
+  hand-back    small frontiers too heavy for the one-workgroup kernel (more long rows than it parks, more entries than it may walk, one row above
+               its bound) and a golden graph at a threshold of 3: the same bytes at every COLOR_WG_FRONTIER
   errors       a non-permutation and a NULL info are GMSX_ERR_INVALID and write nothing
   verify       clean on a device colouring; planted conflicts and a zeroed entry are counted exactly
   determinism  the same bytes on a second call and in a fresh process"""
@@ -23,7 +25,7 @@ from test_coloring_golden_cpu import COL, COL_ARR, ORDERS, golden_rank, jp_golde
 from test_core_golden_cpu import CORE, golden_csr
 
 pytestmark = pytest.mark.gpu
-WG_NONE = 0
+WG_NONE, WG_ALL = 0, 2 ** 31 - 1
 HUB_LIMIT_64 = 64 << 8
 
 
@@ -202,6 +204,56 @@ def test_edgeless_and_empty(gpu):
     assert col.size == 0 and rnd.size == 0 and info == {"colors": 0, "rounds": 0, "max_pred": 0, "first_round": 0}
     assert g.coloring_jp(np.zeros(0, np.int32))[1] == info
     assert g.coloring_verify(np.zeros(0, np.int32)) == {"conflicts": 0, "invalid": 0, "max_color": 0, "distinct": 0, "max_degree": 0}
+    g.free()
+
+
+# ---- 3a. the hand-back between the one-workgroup kernel and the grid-wide ones -----------------------------------------------------------
+def every_threshold(gpu, g, rank):
+    """both_ends, plus a tiny COLOR_WG_FRONTIER and one that leaves every round it may take to the one-workgroup kernel: the same bytes"""
+    col, rnd, info = both_ends(gpu, g, rank)
+    for wg in (3, WG_ALL):
+        with gpu.options(COLOR_WG_FRONTIER=wg):
+            col2, rnd2, info2 = g.coloring_jp(rank, want_rounds=True)
+        assert col2.tobytes() == col.tobytes() and rnd2.tobytes() == rnd.tobytes() and info2 == info, wg
+    return col, rnd, info
+
+
+@pytest.mark.parametrize("hubs,leaves", [(300, 1100),   # one frontier of 300 long rows: more than the one-workgroup kernel parks
+                                         (450, 600)])   # short rows, 270 000 entries in one frontier: above its work bound
+def test_independent_hubs_go_back_to_the_grid(gpu, hubs, leaves):
+    n = hubs + hubs * leaves  # hub h = vertex h; its private leaves follow the hubs
+    leaf = np.arange(hubs, n, dtype=np.int64)
+    csr = edges_to_csr(gpu, np.stack([(leaf - hubs) // leaves, leaf], axis=1), n=n)
+    g = gpu.DeviceGraph.from_csr(csr)
+    col, rnd, info = every_threshold(gpu, g, None)  # the id order colours the highest ids, the leaves, first
+    assert np.all(col[hubs:] == 1) and np.all(rnd[hubs:] == 0) and np.all(col[:hubs] == 2) and np.all(rnd[:hubs] == 1)
+    assert info == {"colors": 2, "rounds": 2, "max_pred": leaves, "first_round": hubs * leaves}
+    col, rnd, info = every_threshold(gpu, g, np.arange(n - 1, -1, -1, dtype=np.int32))  # reversed: the hubs first
+    assert np.all(col[:hubs] == 1) and np.all(rnd[:hubs] == 0) and np.all(col[hubs:] == 2) and np.all(rnd[hubs:] == 1)
+    assert info == {"colors": 2, "rounds": 2, "max_pred": 1, "first_round": hubs}
+    g.free()
+
+
+def test_star_of_40000_from_both_ends(gpu):
+    leaves = 40000  # one row above the one-workgroup kernel's row bound, alone in its frontier
+    csr = edges_to_csr(gpu, np.stack([np.zeros(leaves, dtype=np.int64), np.arange(1, leaves + 1)], axis=1), n=leaves + 1)
+    g = gpu.DeviceGraph.from_csr(csr)
+    col, rnd, info = every_threshold(gpu, g, np.arange(leaves, -1, -1, dtype=np.int32))  # the hub first
+    assert col[0] == 1 and np.all(col[1:] == 2) and rnd[0] == 0 and np.all(rnd[1:] == 1)
+    assert info == {"colors": 2, "rounds": 2, "max_pred": 1, "first_round": 1}
+    col, rnd, info = every_threshold(gpu, g, None)  # the hub last: 40 000 predecessors of colour 1
+    assert col[0] == 2 and np.all(col[1:] == 1) and rnd[0] == 1 and np.all(rnd[1:] == 0)
+    assert info == {"colors": 2, "rounds": 2, "max_pred": leaves, "first_round": leaves}
+    g.free()
+
+
+def test_golden_graph_at_every_threshold(gpu):
+    key = "kronecker_12_16"  # at 3 the run switches between the one-workgroup kernel and the grid-wide ones many times
+    g = gpu.DeviceGraph.from_csr(golden_csr(gpu, key))
+    col, rnd, info = every_threshold(gpu, g, golden_rank(key, "degree"))
+    rec = COL[key]["orders"]["degree"]
+    assert col.tobytes() == COL_ARR["color_degree_" + key].tobytes() and info == {f: rec[f] for f in ("colors", "rounds", "max_pred", "first_round")}
+    assert np.array_equal(rnd, jp_golden(gpu, key, "degree")[1])
     g.free()
 
 
