@@ -446,9 +446,9 @@ class DeviceGraph:
     BREAKDOWN = ["hub_rows_list", "hub_rows_bitset", "hub_rows_delta", "tail_rows_list", "tail_rows_delta", "entries", "pivot_containers",
                  "of_which_inline_rows", "light_streamed_hub_rows", "light_streamed_tail_rows", "light_pivot_lists_and_descriptors",
                  "count_entries", "count_inline_entries", "count_work_items", "count_light_streamed_members",
-                 "reserved15", "reserved16", "reserved17", "reserved18", "reserved19", "reserved20"]
+                 "core_matrix", "core_k", "reserved17", "reserved18", "reserved19", "reserved20"]
     BREAKDOWN_BYTES = ("hub_rows_list", "hub_rows_bitset", "hub_rows_delta", "tail_rows_list", "tail_rows_delta", "entries", "pivot_containers",
-                       "light_streamed_hub_rows", "light_streamed_tail_rows", "light_pivot_lists_and_descriptors")  # these add up to stats.stream_bytes
+                       "light_streamed_hub_rows", "light_streamed_tail_rows", "light_pivot_lists_and_descriptors", "core_matrix")  # these add up to stats.stream_bytes
 
     def tc_stream_breakdown(self):
         out = np.zeros(21, dtype=np.uint64)

@@ -20,6 +20,8 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "../host/gmsx_internal.hpp"
+#include "../host/tc_core_plan.hpp"
+#include "kc4_mfma.hpp"  // kc4m_stride: the row stride Kc4mBlock reads
 
 namespace gmsx {
 
@@ -446,6 +448,42 @@ __global__ __launch_bounds__(256) void k_dense_fill(int32_t limit, const int64_t
         }
     }
 }
+// ---- the dense core (device_graph.hpp: core_bits) -------------------------------------------------------------------------------------
+// Row i of the K x WS-word matrix = the ids of N+(i), all of them hub ids below i.  A wave per row; the matrix is zeroed before.
+__global__ __launch_bounds__(256) void k_core_fill(int32_t K, int WS, const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj,
+                                                   uint32_t *__restrict__ bits) {
+    const int lane = threadIdx.x & 63;
+    const int32_t wave0 = int32_t((int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6);
+    const int32_t nwaves = int32_t((int64_t(gridDim.x) * blockDim.x) >> 6);
+    for (int32_t i = wave0; i < K; i += nwaves)
+        for (int64_t j = hoff[i] + lane; j < hoff[i + 1]; j += 64) {
+            const uint32_t id = hadj[j];
+            if (id < uint32_t(i)) atomicOr(&bits[size_t(i) * size_t(WS) + (id >> 5)], 1u << (id & 31u));  // (0xFFFF = row padding)
+        }
+}
+// GMSX_TC_CORE = -1: what the streamed path would read for the edges of the pivots below `cap`, in 16-byte units per bucket of 1 024 pivots —
+// the input of choose_tc_core (host/tc_core_plan.hpp).  An ESTIMATE from the degrees alone (the stream rows do not exist yet when K is needed):
+// the edge to member i of u (i members of u lie below it) streams the shorter of the two sides, v's row or u's row cut at v, in its
+// cheaper form — a 16-bit list (8 ids per unit) or a bitset over [0, v) (128 ids per unit).  The byte-delta form is not modelled.
+__global__ __launch_bounds__(256) void k_core_units(int32_t cap, const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj,
+                                                    const int32_t *__restrict__ dplus, unsigned long long *__restrict__ bucket) {
+    const int lane = threadIdx.x & 63;
+    const int32_t wave0 = int32_t((int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6);
+    const int32_t nwaves = int32_t((int64_t(gridDim.x) * blockDim.x) >> 6);
+    for (int32_t u = wave0; u < cap; u += nwaves) {
+        const int64_t hb = hoff[u];
+        const int hl = int(hoff[u + 1] - hb);
+        unsigned long long units = 0;
+        for (int i = lane; i < hl; i += 64) {
+            const uint32_t v = hadj[hb + i];
+            if (v >= uint32_t(u)) continue;  // row padding
+            const uint32_t ids = uint32_t(min(i, dplus[v]));
+            units += min((ids + 7u) / 8u, (v + 127u) / 128u);
+        }
+        for (int s = 32; s > 0; s >>= 1) units += __shfl_down(units, s);
+        if (lane == 0 && units) atomicAdd(&bucket[u / kTcCoreBucket], units);
+    }
+}
 // tsplit[u] = number of tail targets of u below `limit` (tail rows are ascending when rows_sorted; otherwise a plain count,
 // which the kernels then do not use as a position)
 __global__ __launch_bounds__(256) void k_tail_split(int64_t n, const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj, int32_t limit,
@@ -508,7 +546,7 @@ __device__ __forceinline__ bool takes_inline(int32_t v, int32_t inline_limit, co
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_inline_rows(int64_t first, int64_t end, const int32_t *__restrict__ order, const int64_t *__restrict__ hoff,
                                                      const uint16_t *__restrict__ hadj, const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj,
-                                                     const int32_t *__restrict__ dplus, int32_t inline_limit, int inline_first, const int32_t *__restrict__ opos, int nparts, int part,
+                                                     const int32_t *__restrict__ dplus, int32_t inline_limit, int inline_first, int32_t core, const int32_t *__restrict__ opos, int nparts, int part,
                                                      unsigned long long *__restrict__ cnt_h,
                                                      unsigned long long *__restrict__ cnt_t, const int64_t *__restrict__ ihoff,
                                                      const int64_t *__restrict__ itoff, int64_t base_h, uint16_t *__restrict__ pool_h, int64_t base_t,
@@ -518,6 +556,7 @@ __global__ __launch_bounds__(256) void k_inline_rows(int64_t first, int64_t end,
     const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
     for (int64_t pos = first + wave0; pos < end; pos += nwaves) {
         const int32_t u = order[pos];
+        if (u < core) continue;  // a core pivot (k_tc_core): none of its edges is handed over
         const int64_t hb = hoff[u], tb = toff[u];
         // a heavy pivot takes part with its first inline_first members only (the low lanes of its combined list); a light one with all
         const int first_u = dplus[u] >= kHeavy ? inline_first : kInlineFirstMax;
@@ -638,7 +677,7 @@ __global__ void k_list_sizes(int64_t n_recv, uint32_t *__restrict__ cnt, int64_t
 
 // ---- light edges (device_graph.hpp): thread per light pivot (positions [first, end) of `order`) ----------------------------------------
 __global__ void k_ledge_count(int64_t first, int64_t end, const int32_t *__restrict__ order, const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj,
-                              const int32_t *__restrict__ tsplit, const int32_t *__restrict__ dplus, int64_t *__restrict__ cnt) {
+                              const int32_t *__restrict__ tsplit, const int32_t *__restrict__ dplus, int32_t core, int64_t *__restrict__ cnt) {
     const int64_t pos = first + int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (pos > end) return;
     int64_t c = 0;
@@ -646,16 +685,18 @@ __global__ void k_ledge_count(int64_t first, int64_t end, const int32_t *__restr
         const int32_t u = order[pos];
         const int64_t tb = toff[u];
         const int tl = int(toff[u + 1] - tb);
-        for (int i = tsplit[u]; i < tl; ++i) c += dplus[tadj[tb + i]] < kHeavy ? 1 : 0;
+        if (u >= core)  // (a core pivot's edges are k_tc_core's)
+            for (int i = tsplit[u]; i < tl; ++i) c += dplus[tadj[tb + i]] < kHeavy ? 1 : 0;
     }
     cnt[pos - first] = c;
 }
 __global__ void k_ledge_fill(int64_t first, int64_t end, const int32_t *__restrict__ order, const int64_t *__restrict__ hoff, const int64_t *__restrict__ toff,
                              const int32_t *__restrict__ tadj, const int32_t *__restrict__ tsplit, const int32_t *__restrict__ dplus,
-                             const int64_t *__restrict__ ebeg, int nparts, int part, uint4 *__restrict__ ledge) {
+                             int32_t core, const int64_t *__restrict__ ebeg, int nparts, int part, uint4 *__restrict__ ledge) {
     const int64_t pos = first + int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (pos >= end) return;
     const int32_t u = order[pos];
+    if (u < core) return;
     const int64_t hb = hoff[u], tb = toff[u];
     const int tl = int(toff[u + 1] - tb);
     const unsigned long long hu = (unsigned long long)hb | ((unsigned long long)(hoff[u + 1] - hb) << 40);
@@ -729,7 +770,7 @@ __global__ __launch_bounds__(256) void k_task_lists(int64_t n_heavy, const int32
                                                     uint32_t *__restrict__ cnt, uint32_t *__restrict__ cur, const int64_t *__restrict__ hbeg,
                                                     const int64_t *__restrict__ tbeg, TaskList htask, TaskList ttask,
                                                     int32_t *__restrict__ tunits, unsigned long long *__restrict__ reversed, const uint32_t *__restrict__ spool,
-                                                    const uint32_t *__restrict__ tpool, int32_t inline_limit, int inline_first, int nparts, int part, TcClasses cc) {
+                                                    const uint32_t *__restrict__ tpool, int32_t inline_limit, int inline_first, int32_t core, int nparts, int part, TcClasses cc) {
     const int kClasses = cc.count();
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
@@ -737,6 +778,7 @@ __global__ __launch_bounds__(256) void k_task_lists(int64_t n_heavy, const int32
     unsigned long long rev = 0;
     for (int64_t pos = wave0; pos < n_heavy; pos += nwaves) {  // the heavy pivots are the first n_heavy of `order`: receiver index = pos
         const int32_t u = order[pos];
+        if (u < core) continue;  // a core pivot keeps no edge and hands none over (k_tc_core); it still receives the rows of pivots >= core
         const int64_t hb = hoff[u], tb = toff[u];
         const int hl = int(hoff[u + 1] - hb), tl = int(toff[u + 1] - tb);
         const unsigned long long du_s = srow[u], du_s2 = srow2[u], du_t = trow[u];  // du_s2 != 0: hybrid row — du_s is the prefix bitmap, du_s2 the ids behind it
@@ -892,7 +934,8 @@ static void free_tc(gmsx_graph *g) {
         p = nullptr;
     };
     drop(g->tsplit); drop(g->srow); drop(g->srow2); drop(g->ksplit); drop(g->spool); drop(g->trow); drop(g->htask.lo); drop(g->htask.hi); drop(g->ttask.lo); drop(g->ttask.hi); drop(g->hitem); drop(g->titem); drop(g->tunits);
-    drop(g->ledge); drop(g->tpool); drop(g->shard_hitem); drop(g->shard_titem);
+    drop(g->ledge); drop(g->tpool); drop(g->shard_hitem); drop(g->shard_titem); drop(g->core_bits);
+    g->tc_core = 0;
     g->shard_idx_part = g->shard_idx_nparts = -1;
     g->device_bytes -= g->tc_bytes;
     g->tc_bytes = 0;
@@ -931,6 +974,7 @@ static void free_graph(gmsx_graph *g) {
     (void)hipFree(g->shard_hitem);
     (void)hipFree(g->shard_titem);
     (void)hipFree(g->ledge);
+    (void)hipFree(g->core_bits);
     (void)hipFree(g->tpool);
     (void)hipFree(g->dplus);
     (void)hipFree(g->order);
@@ -1301,6 +1345,40 @@ static int build_tc_sets(gmsx_graph *g) {
     if (int rc = dmalloc(&opos, n + 1, nullptr)) return rc;
     DevGuard g_opos{opos};
     if (n > 0) hipLaunchKernelGGL(k_opos, dim3(tb), dim3(256), 0, s, n, g->order, opos);
+    // 4b'. THE CORE (device_graph.hpp).  GMSX_TC_CORE: 0 = none, N > 0 = the rank ids below N, -1 = choose_tc_core on the estimate of
+    //      k_core_units; always clamped to the hub ids, n and kTcCoreCap; unset = kTcCoreDefault (host/tc_core_plan.hpp, with the measurements
+    //      behind it).  The same K on every shard and in every pass: it depends on the graph alone.
+    {
+        long long want = kTcCoreDefault;
+        if (const char *e = opt("TC_CORE")) want = std::atoll(e);
+        g->tc_core = 0;
+        if (want > 0) g->tc_core = tc_core_clamp(want, hub_limit, n);
+        else if (want < 0) {
+            const int cap = tc_core_clamp(kTcCoreCap, hub_limit, n) / kTcCoreBucket * kTcCoreBucket;
+            if (cap > 0) {
+                const int nbk = cap / kTcCoreBucket;
+                unsigned long long *bucket = nullptr;
+                if (int rc = dmalloc(&bucket, nbk, nullptr)) return rc;
+                DevGuard g_b{bucket};
+                GMSX_HIP(hipMemsetAsync(bucket, 0, size_t(nbk) * sizeof(unsigned long long), s));
+                hipLaunchKernelGGL(k_core_units, dim3(grid_for_waves(cap)), dim3(256), 0, s, cap, g->hoff, g->hadj, g->dplus, bucket);
+                std::vector<uint64_t> h(size_t(nbk), 0);
+                static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "bucket words");
+                GMSX_HIP(hipMemcpyAsync(h.data(), bucket, size_t(nbk) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+                GMSX_HIP(hipStreamSynchronize(s));
+                g->tc_core = choose_tc_core(h, cap);
+            }
+        }
+        if (g->tc_core > 0) {
+            const int32_t K = g->tc_core;
+            const int WS = kc4m_stride(K);
+            const int64_t words = int64_t(K) * WS + 8;
+            if (int rc = dmalloc(&g->core_bits, words, g)) return rc;
+            GMSX_HIP(hipMemsetAsync(g->core_bits, 0, size_t(words) * sizeof(uint32_t), s));
+            hipLaunchKernelGGL(k_core_fill, dim3(grid_for_waves(K)), dim3(256), 0, s, K, WS, g->hoff, g->hadj, g->core_bits);
+        }
+    }
+    pt.mark("core matrix");
     // 4c. INLINE LIMIT.  A light pivot u (2 <= d+ < 64) hands the edge (u,v) over to v whenever v is a pivot of the workgroup kernel
     //     anyway (d+ >= 64) or a popular target (rank id < inline_limit): the members of u below v — the only ids of N+(u) that can
     //     be in N+(v) — are copied into v's INLINE ROWS, two more stream rows of v (16-bit hub ids / 32-bit tail ids, list form) that
@@ -1352,7 +1430,7 @@ static int build_tc_sets(gmsx_graph *g) {
         GMSX_HIP(hipMemsetAsync(inl_t, 0, size_t(n + 1) * sizeof(unsigned long long), s));
         if (n_work > 0)
             hipLaunchKernelGGL(k_inline_rows<false>, dim3(grid_for_waves(n_work)), dim3(256), 0, s, int64_t(0), n_work, g->order, g->hoff, g->hadj,
-                               g->toff, g->tadj, g->dplus, g->inline_limit, g->inline_first, opos, g->shard_nparts, g->shard_part, inl_h, inl_t, ihoff, itoff, int64_t(0), static_cast<uint16_t *>(nullptr),
+                               g->toff, g->tadj, g->dplus, g->inline_limit, g->inline_first, g->tc_core, opos, g->shard_nparts, g->shard_part, inl_h, inl_t, ihoff, itoff, int64_t(0), static_cast<uint16_t *>(nullptr),
                                int64_t(0), static_cast<int32_t *>(nullptr));
         int64_t *uh = nullptr, *ut = nullptr;
         if (int rc = dmalloc(&uh, n + 1, nullptr)) return rc;
@@ -1478,7 +1556,7 @@ static int build_tc_sets(gmsx_graph *g) {
         GMSX_HIP(hipMemsetAsync(inl_h, 0, size_t(n + 1) * sizeof(unsigned long long), s));  // now the fill cursors
         GMSX_HIP(hipMemsetAsync(inl_t, 0, size_t(n + 1) * sizeof(unsigned long long), s));
         hipLaunchKernelGGL(k_inline_rows<true>, dim3(grid_for_waves(n_work)), dim3(256), 0, s, int64_t(0), n_work, g->order, g->hoff, g->hadj, g->toff,
-                           g->tadj, g->dplus, g->inline_limit, g->inline_first, opos, g->shard_nparts, g->shard_part, inl_h, inl_t, ihoff, itoff, inline_h_base, reinterpret_cast<uint16_t *>(g->spool),
+                           g->tadj, g->dplus, g->inline_limit, g->inline_first, g->tc_core, opos, g->shard_nparts, g->shard_part, inl_h, inl_t, ihoff, itoff, inline_h_base, reinterpret_cast<uint16_t *>(g->spool),
                            inline_t_base, reinterpret_cast<int32_t *>(g->tpool));
     }
     pt.mark("inline rows fill");
@@ -1495,7 +1573,7 @@ static int build_tc_sets(gmsx_graph *g) {
             DevGuard g_ec{ecnt};
             if (int rc = dmalloc(&ebeg, nl + 1, nullptr)) return rc;
             DevGuard g_eb{ebeg};
-            hipLaunchKernelGGL(k_ledge_count, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->toff, g->tadj, g->tsplit, g->dplus, ecnt);
+            hipLaunchKernelGGL(k_ledge_count, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->toff, g->tadj, g->tsplit, g->dplus, g->tc_core, ecnt);
             if (int rc = exclusive_scan_i64(ecnt, ebeg, nl + 1, s)) return rc;
             GMSX_HIP(hipMemcpy(&g->ledge_total, ebeg + nl, sizeof(int64_t), hipMemcpyDeviceToHost));
             const int np = g->shard_nparts > 1 ? g->shard_nparts : 1, pp = g->shard_nparts > 1 ? g->shard_part : 0;
@@ -1504,7 +1582,7 @@ static int build_tc_sets(gmsx_graph *g) {
                 g->n_ledge = np <= 1 ? g->ledge_total : full + (((full & 1) ? np - 1 - pp : pp) < rem ? 1 : 0);
             }
             if (int rc = dmalloc(&g->ledge, 2 * g->n_ledge + 2, g)) return rc;
-            hipLaunchKernelGGL(k_ledge_fill, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->hoff, g->toff, g->tadj, g->tsplit, g->dplus, ebeg,
+            hipLaunchKernelGGL(k_ledge_fill, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->hoff, g->toff, g->tadj, g->tsplit, g->dplus, g->tc_core, ebeg,
                                np, pp, g->ledge);
             GMSX_HIP(hipStreamSynchronize(s));
         }
@@ -1580,7 +1658,7 @@ static int build_tc_sets(gmsx_graph *g) {
         if (n_heavy > 0)
             hipLaunchKernelGGL(k_task_lists<false>, dim3(grid), dim3(256), 0, s, n_heavy, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->srow, g->srow2, g->ksplit, g->trow,
                                two_sided, opos, cnt, cur, hbeg, tbeg, TaskList{}, TaskList{}, g->tunits,
-                               totals + 2, g->spool, g->tpool, g->inline_limit, g->inline_first, g->shard_nparts, g->shard_part, cc);
+                               totals + 2, g->spool, g->tpool, g->inline_limit, g->inline_first, g->tc_core, g->shard_nparts, g->shard_part, cc);
         pt.mark("task lists count");
         // class offsets, list offsets
         hipLaunchKernelGGL(k_list_sizes, dim3(unsigned(n_recv / 256 + 1)), dim3(256), 0, s, n_recv, cnt, hcnt, tcnt, cc);
@@ -1605,7 +1683,7 @@ static int build_tc_sets(gmsx_graph *g) {
                                inline_t_base, cnt, cur, hbeg, tbeg, g->htask, g->ttask, totals, cc);
         if (n_heavy > 0)
             hipLaunchKernelGGL(k_task_lists<true>, dim3(grid), dim3(256), 0, s, n_heavy, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->srow, g->srow2, g->ksplit, g->trow,
-                               two_sided, opos, cnt, cur, hbeg, tbeg, g->htask, g->ttask, g->tunits, totals + 2, g->spool, g->tpool, g->inline_limit, g->inline_first, g->shard_nparts, g->shard_part, cc);
+                               two_sided, opos, cnt, cur, hbeg, tbeg, g->htask, g->ttask, g->tunits, totals + 2, g->spool, g->tpool, g->inline_limit, g->inline_first, g->tc_core, g->shard_nparts, g->shard_part, cc);
         pt.mark("task lists fill");
         // work items
         const int hub_phases = cc.hub_phases();

@@ -137,6 +137,14 @@ struct gmsx_graph {
     // independent.  Edge e of the (deterministic) list belongs to shard shard_of(e, nparts) — the pivots' rule; a sharded upload keeps its own at slot e / nparts.
     uint4 *ledge = nullptr;
     int64_t n_ledge = 0, ledge_total = 0;
+    // CORE (k_tc_core, tc.hip): the oriented edges (u, v) with rank id u < tc_core.  v and all of N+(v) lie below u, so the sum of their
+    // intersect_counts is Σ_ij L_ij (L Lᵀ)_ij on the strictly lower-triangular tc_core x tc_core bit matrix L of those rows — a masked bit-GEMM
+    // on the matrix cores (kc4_mfma.hpp) instead of streamed rows.  Such an edge has no task entry, no inline copy and no light-edge record.
+    // core_bits: tc_core rows of kc4m_stride(tc_core) words, row i = the ids of N+(i), zero beyond its last bit; whole on every shard.
+    uint32_t *core_bits = nullptr;
+    int32_t tc_core = 0;                 // 0 = no core (GMSX_TC_CORE)
+    mutable int core_bytes_k = -1, core_bytes_part = -1, core_bytes_nparts = -1;  // memo of tc_core_bytes() for the last (K, part, nparts)
+    mutable uint64_t core_bytes = 0;
     // HOT WINDOWS (round 4): the hub-entry list of a receiver is laid out phase by phase — first the entries whose stream row starts in
     // window 0 of the pool ([0, tc_window_units) 16-byte units: the rows of the biggest hubs, the most often streamed bytes of the graph),
     // then window 1 … and last everything else — and the work items of phase 0 of ALL receivers come first, then phase 1 …: while a phase

@@ -29,9 +29,16 @@
 //      for the few that pass, a table probe; hits are counted per lane, reduced per workgroup, added to one of 64 spread u64
 //      accumulators (one atomic per workgroup);
 //   4. k_tc_light — the edges between two light vertices that no work item covers: one 16-lane group per edge, all-pairs in registers.
-//   The three kernels run side by side on three streams (hub items: bandwidth + VALU; tail items: short rows; light pivots: latency).
-// No MFMA: integer/indexing work bounded by row streaming (HBM) and VALU issue of the decode + probe sequence.
+//   5. k_tc_core (GMSX_TC_CORE; host/tc_core_plan.hpp holds the default and the rule) — the edges whose pivot-side endpoint has a rank id below K: they and everything they can match lie
+//      inside the top K x K corner of the oriented adjacency matrix, where an RMAT graph is dense, so their sum is the masked bit-GEMM
+//      Σ_ij L_ij (L Lᵀ)_ij on the matrix cores (kc4_mfma.hpp: fp4 MFMA, f32 sums of ones, exact).  Those edges have no entry, no inline copy and
+//      no light-edge record: what the items stream shrinks by their rows.
+//   The kernels run one after the other on the launch stream (the item kernels are bound by the same memory system: side by side they
+//   took the sum of their times).  Everything but the core is integer / indexing work bounded by row streaming (HBM) and
+//   the VALU issue of the decode + probe sequence.
 #include "device_graph.hpp"
+#include "kc4_mfma.hpp"
+#include "../host/tc_core_plan.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -801,6 +808,49 @@ __global__ __launch_bounds__(256) void k_tc_light(const uint16_t *__restrict__ h
     block_add(total, red, lane, wave, tid, acc);
 }
 
+// ---------------------------------------------------------------------------------------------
+// THE CORE (device_graph.hpp: core_bits).  One wave per 64 x 64 block (bi >= bj) of the K x K matrix, Kc4mBlock<2>::run as k_kc4_mfma uses it:
+// 1 024 threads, four waves per SIMD.  The blocks are dealt out STATICALLY — no ticket, no global atomic — from the cost-descending sequence of
+// host/tc_core_plan.hpp (highest bj first), of which this call's shard takes every nparts-th block.  The shard's blocks are cut into chunks
+// of Q = 16 x (workgroups per XCD) consecutive blocks, one per wave of an XCD; round j hands the chunks 8 j … 8 j + 7 to the eight XCDs
+// (blockIdx mod 8 labels the XCD; odd rounds in reverse, so that no XCD always gets the dearer chunk).  What an XCD works on at any time is one
+// chunk: a few neighbouring bj, whose J rows stay in its L2 while the I rows pass through.  A wrong guess about the XCDs costs speed, never the count.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_tc_core(const uint32_t *__restrict__ bits, int WS, int K, int nb, int nblk, int part, int nparts,
+                                                  unsigned long long *__restrict__ acc) {
+    __shared__ unsigned long long red[16];
+    // the lane id from the exec mask (v_mbcnt), formed anew for every block and for the final sum: carried across Kc4mBlock::run, which takes all 128
+    // registers of a wave at four per SIMD, the thread id and what is derived from it were spilled
+    auto lane_id = [] { return int(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u))); };
+    const int wave = uni32(int(threadIdx.x) >> 6);
+    const int x = blockIdx.x & 7, y = blockIdx.x >> 3, Y = int(gridDim.x) >> 3;  // gridDim.x is a multiple of 8 (host)
+    const int Q = 16 * Y, q = y * 16 + wave;
+    const int ns = (nblk - part + nparts - 1) / nparts;  // blocks of this shard (nblk <= 131 328: every index below fits 32 bits)
+    uint32_t cnt = 0;  // per lane <= 64 K = 2^21 per block, and a launch has >= 128 waves for <= 131 328 blocks: below 2^31
+    for (int j = 0;; ++j) {
+        const int sidx = (8 * j + ((j & 1) ? 7 - x : x)) * Q + q;
+        if (sidx >= ns) break;  // (every index of the later rounds is larger still)
+        const int t = sidx * nparts + part;
+        int c = int((__builtin_sqrtf(8.0f * float(t) + 1.0f) - 1.0f) * 0.5f);
+        while (c * (c + 1) / 2 > t) --c;
+        while ((c + 1) * (c + 2) / 2 <= t) ++c;
+        const int bj = nb - 1 - c, bi = bj + (t - c * (c + 1) / 2);
+        int lane = lane_id();
+        asm volatile("" : "+v"(lane));  // (not hoisted out of the loop)
+        cnt += Kc4mBlock<2>::run(bits, WS, K, bi, bj, lane);
+    }
+    const int lane = lane_id();
+    unsigned long long total = cnt;
+    for (int sft = 32; sft > 0; sft >>= 1) total += __shfl_down(total, sft);
+    if (lane == 0) red[wave] = total;
+    __syncthreads();
+    if (wave == 0 && lane == 0) {
+        unsigned long long t = 0;
+        for (int w = 0; w < 16; ++w) t += red[w];
+        if (t) atomicAdd(&acc[(blockIdx.x & (kAccSlots - 1)) * kAccStride], t);
+    }
+}
+
 // units / probes / algorithmic stream bytes of a shard (untimed bookkeeping for gmsx_stats).  out[2] follows what the count kernels
 // read, byte for byte, assuming no on-chip reuse:
 //   light pivot u (2 <= d+ < 64; k_tc_stats, wave per pivot position): per far light member v (rank id >= inline_limit, d+ < 64) the
@@ -808,13 +858,14 @@ __global__ __launch_bounds__(256) void k_tc_light(const uint16_t *__restrict__ h
 //   work item (k_tc_item_stats, wave per item): the pivot's container (hub part for a hub item, tail part for a tail item) once; per
 //       entry 6 bytes of descriptor and the stream row it describes (whole 16-byte units) — members' rows, cut rows and inline chunks alike.
 // out[0] = oriented edges counted by the shard: every edge of a light or idle pivot at the pivot, the edges a heavy pivot handed to its
-// first members over inline at the pivot, every other edge of a heavy pivot where its entries live (tunits, written by the build);
+// first members over inline at the pivot, every other edge of a heavy pivot where its entries live (tunits, written by the build), every
+// edge of a core pivot (rank id < core: k_tc_core counts it, nothing streams it) at the pivot, beside the entries it received;
 // out[1] = id slots probed (per unit: 8 list, 14 byte-delta, 10 gap-12, 4 bitset words; 4 / 6 tail ids).  A shard = the pivots at the
 // positions of `order` that shard_of() gives it.
 __global__ __launch_bounds__(256) void k_tc_stats(const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj,
                                                   const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj,
                                                   const int32_t *__restrict__ dplus, const int32_t *__restrict__ order,
-                                                  const int32_t *__restrict__ tunits, int32_t inline_limit, int inline_first, int64_t end, int nparts, int part,
+                                                  const int32_t *__restrict__ tunits, int32_t inline_limit, int inline_first, int32_t core, int64_t end, int nparts, int part,
                                                   unsigned long long *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
@@ -826,6 +877,10 @@ __global__ __launch_bounds__(256) void k_tc_stats(const int64_t *__restrict__ ho
         const int du = dplus[u];
         if (du >= kHeavy) {  // forward + reverse edges whose entries live here (the heavy pivots are the first of `order`) …
             if (lane == 0) units += (unsigned long long)tunits[pos];
+            if (u < core) {  // a core pivot: all its own edges, none of them inline
+                if (lane == 0) units += (unsigned long long)du;
+                continue;
+            }
             // … and the edges to its first members that went inline (no entry anywhere)
             const int hl = min(int(hoff[u + 1] - hoff[u]), inline_first), tl = min(int(toff[u + 1] - toff[u]), inline_first - hl);
             int32_t v = -1;
@@ -838,7 +893,7 @@ __global__ __launch_bounds__(256) void k_tc_stats(const int64_t *__restrict__ ho
         }
         const int hl = int(hoff[u + 1] - hoff[u]);
         if (lane == 0) units += (unsigned long long)du;
-        if (du < 2) continue;
+        if (du < 2 || u < core) continue;
         for (int64_t j = toff[u] + lane; j < toff[u + 1]; j += 64) {
             const int32_t v = tadj[j];
             if (v < inline_limit || dplus[v] >= kHeavy) continue;  // handed over: the ids are in v's inline rows, counted with its items
@@ -901,12 +956,14 @@ __global__ __launch_bounds__(256) void k_tc_item_stats(const int64_t *__restrict
 //   out[8..9]  light edges (k_tc_light): hub / tail parts of the far light members' rows
 //   out[10]    light edges: the 32-byte records + the pivots' own hub / tail parts (once per edge)
 //   out[11..14] counts: entries, inline entries, work items, light edges
-//   out[15..20] reserved (0)
+//   out[15]    the core (k_tc_core): per 64 x 64 block the fragment bytes of its 2 x 64 rows and its mask words, no reuse assumed (host)
+//   out[16]    K, the rank ids below which an edge belongs to the core (0 = none)
+//   out[17..20] reserved (0)
 __global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict__ hoff, const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj,
                                                       const int32_t *__restrict__ dplus, const int32_t *__restrict__ order,
                                                       const TaskList htask, const gmsx_tc_item *__restrict__ hitem, int64_t hitems,
                                                       const TaskList ttask, const gmsx_tc_item *__restrict__ titem, int64_t titems,
-                                                      int32_t inline_limit, int64_t first_light, int64_t end_light,
+                                                      int32_t inline_limit, int32_t core, int64_t first_light, int64_t end_light,
                                                       unsigned long long *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
@@ -934,6 +991,7 @@ __global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict_
     }
     for (int64_t pos = first_light + wave0; pos < end_light; pos += nwaves) {
         const int32_t u = order[pos];
+        if (u < core) continue;
         const int64_t tb0 = toff[u], te = toff[u + 1];
         const unsigned long long hl = (unsigned long long)(hoff[u + 1] - hoff[u]);
         for (int64_t j = tb0 + lane; j < te; j += 64) {
@@ -1063,11 +1121,22 @@ __global__ __launch_bounds__(256) void k_tc_row_hist(const int64_t *__restrict__
         if (h[i]) atomicAdd(&out[i], h[i]);
 }
 
-static int tc_one(const gmsx_graph *g, int part, int nparts, uint64_t *partial, gmsx_stats *st);
+// (cpart, cnparts): the share of the core's blocks this call counts — cnparts = 0: none (a later pass of a call that walks several)
+static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnparts, uint64_t *partial, gmsx_stats *st);
+static uint64_t core_bytes_of(const gmsx_graph *g, int part, int nparts) {
+    if (g->tc_core <= 0 || nparts < 1) return 0;
+    if (!(g->core_bytes_k == g->tc_core && g->core_bytes_part == part && g->core_bytes_nparts == nparts)) {
+        g->core_bytes = tc_core_bytes(g->tc_core, part, nparts);
+        g->core_bytes_k = g->tc_core;
+        g->core_bytes_part = part;
+        g->core_bytes_nparts = nparts;
+    }
+    return g->core_bytes;
+}
 
 static int tc_oriented(const gmsx_graph *g, int part, int nparts, uint64_t *partial, gmsx_stats *st) {
     if (int rc = ensure_tc(g)) return rc;  // first call on a graph uploaded without GMSX_UPLOAD_FOR_TC: builds the task lists (untimed)
-    if (g->tc_passes == 1) return tc_one(g, part, nparts, partial, st);
+    if (g->tc_passes == 1) return tc_one(g, part, nparts, part, nparts, partial, st);
     // FALLBACK (device_graph.hpp, tc_passes): the containers of all pivots did not fit.  A whole-graph call walks the passes — shard p of
     // tc_passes resident at a time, rebuilt between the passes (untimed like every build; kernel_ms is the sum of the passes' kernels); a
     // sharded call builds exactly its shard.
@@ -1094,7 +1163,7 @@ static int tc_oriented(const gmsx_graph *g, int part, int nparts, uint64_t *part
                 if (rc) break;
                 uint64_t pp = 0;
                 gmsx_stats sp{};
-                rc = tc_one(g, sub, nparts * J, &pp, st ? &sp : nullptr);
+                rc = tc_one(g, sub, nparts * J, part, a == 0 ? nparts : 0, &pp, st ? &sp : nullptr);  // the core with the first sub-shard only
                 total += pp;
                 sum.kernel_ms += sp.kernel_ms;
                 sum.setup_ms += sp.setup_ms;
@@ -1116,7 +1185,7 @@ static int tc_oriented(const gmsx_graph *g, int part, int nparts, uint64_t *part
         if (int rc = ensure_tc_shard(g, p, g->tc_passes)) return rc;
         uint64_t pp = 0;
         gmsx_stats sp{};
-        if (int rc = tc_one(g, p, g->tc_passes, &pp, st ? &sp : nullptr)) return rc;
+        if (int rc = tc_one(g, p, g->tc_passes, 0, p == 0 ? 1 : 0, &pp, st ? &sp : nullptr)) return rc;  // the core in the first pass only
         total += pp;
         sum.kernel_ms += sp.kernel_ms;
         sum.setup_ms += sp.setup_ms;
@@ -1133,7 +1202,7 @@ static int tc_oriented(const gmsx_graph *g, int part, int nparts, uint64_t *part
     return GMSX_OK;
 }
 
-static int tc_one(const gmsx_graph *g, int part, int nparts, uint64_t *partial, gmsx_stats *st) {
+static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnparts, uint64_t *partial, gmsx_stats *st) {
     // a sharded call on a FULL upload launches the work items of its shard only (compacted index lists, cached per (part, nparts)); a sharded
     // upload holds nothing but its own items
     const bool use_idx = nparts > 1 && g->shard_nparts == 1;
@@ -1200,6 +1269,16 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, uint64_t *partial, 
         GMSX_HIP(hipStreamWaitEvent(c.side[1], c.ev_fork, 0));
         join.armed[1] = true;
     }
+    const bool run_core = g->tc_core > 0 && cnparts > 0 && !only;
+    if (run_core) {
+        const int K = g->tc_core, nb = (K + 63) / 64, nblk = int(tc_core_blocks(K));
+        const int64_t ns = (int64_t(nblk) - cpart + cnparts - 1) / cnparts;
+        if (ns > 0) {  // one workgroup of 16 waves per CU at the most, a multiple of 8 workgroups
+            const int64_t wgs = std::max<int64_t>(8, std::min<int64_t>(cus / 8 * 8, ((ns + 15) / 16 + 7) / 8 * 8));
+            hipLaunchKernelGGL(k_tc_core, dim3(unsigned(wgs)), dim3(1024), 0, s, g->core_bits, kc4m_stride(K), K, nb, nblk, cpart, cnparts, acc);
+            ++launches;
+        }
+    }
     if (persist) {
         const int wgs_env = [] { const char *e = opt("TC_ITEM_WGS"); return e ? std::atoi(e) : 0; }();  // workgroups per CU (0: what the kernel is compiled for)
         auto grid = [&](int64_t n, int wgs) {
@@ -1244,7 +1323,7 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, uint64_t *partial, 
         if (g->n > 0) {
             const int64_t blocks = std::min<int64_t>((g->n + 3) / 4, cap_blocks);
             hipLaunchKernelGGL(k_tc_stats, dim3(unsigned(blocks)), dim3(256), 0, s, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->order,
-                               g->tunits, g->inline_limit, g->inline_first, g->n, nparts, part, acc + kAccSlots * kAccStride);
+                               g->tunits, g->inline_limit, g->inline_first, g->tc_core, g->n, nparts, part, acc + kAccSlots * kAccStride);
         }
         if (g->hitems > 0)
             hipLaunchKernelGGL(k_tc_item_stats, dim3(unsigned(std::min<int64_t>((g->hitems + 3) / 4, cap_blocks))), dim3(256), 0, s, g->hoff, 2, 0, g->htask, g->hitem,
@@ -1277,7 +1356,7 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, uint64_t *partial, 
         st->alg_elements = nparts == 1 ? g->alg_elements : 0;
         st->launches = launches;
         st->reserved = 0;
-        st->stream_bytes = g->stats_bytes;
+        st->stream_bytes = g->stats_bytes + (run_core ? core_bytes_of(g, cpart, cnparts) : 0);
     }
     return GMSX_OK;
 }
@@ -1307,12 +1386,14 @@ int gmsx_tc_stream_breakdown(const gmsx_graph *g, uint64_t *out21) {
         GMSX_HIP(hipMemsetAsync(acc, 0, 21 * 8, s));
         const int cus = ctx().compute_units > 0 ? ctx().compute_units : 256;
         hipLaunchKernelGGL(k_tc_breakdown, dim3(unsigned(cus * 16)), dim3(256), 0, s, g->hoff, g->toff, g->tadj, g->dplus, g->order, g->htask,
-                           g->hitem, g->hitems, g->ttask, g->titem, g->titems, g->inline_limit, n_block, n_work, acc);
+                           g->hitem, g->hitems, g->ttask, g->titem, g->titems, g->inline_limit, g->tc_core, n_block, n_work, acc);
         GMSX_HIP(hipMemcpyAsync(out21, acc, 21 * 8, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
         GMSX_HIP(hipGetLastError());
         out21[7] = uint64_t(g->inline_units) * 16ull;                         // the build's figures: the entries do not say what they name
         out21[12] = uint64_t(g->inline_hentries + g->inline_tentries);
+        out21[15] = core_bytes_of(g, 0, 1);
+        out21[16] = uint64_t(g->tc_core);
         return GMSX_OK;
     });
 }

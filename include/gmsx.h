@@ -127,7 +127,10 @@ int gmsx_set_host_threads(int n);
  *                   TC_DELTA / TC_DELTA_PCT / TC_GAP12 / TC_HYBRID / TC_TAIL_DELTA (which container forms the stream rows may take),
  *                   TC_HOT_WINDOWS / TC_HOT_KB / TC_HOT_MIN (L2-window phases of the hub lists), TC_TEST_MAX_UNITS (pretend the task-list
  *                   fields are this narrow), TC_KEEP_ROWS (keep the per-vertex row descriptors for gmsx_tc_row_histogram), TC_OVERLAP,
- *                   TC_PERSIST, TC_ITEM_WGS (launch shapes)
+ *                   TC_PERSIST, TC_ITEM_WGS (launch shapes), TC_CORE (the dense core, read when the containers are built: the oriented edges
+ *                   whose pivot-side endpoint has a rank id below K are counted as one masked bit-GEMM on the matrix cores instead of being
+ *                   streamed; -1 = K chosen from the graph, a multiple of 1024 or 0 (the default), 0 = no core, N > 0 = K = N; always clamped
+ *                   to min(hub ids, n, 32768))
  *   k-clique        KC_MAXD (widest pivot of the bit-matrix kernels), KC_SLAB_MB (budget of the global slabs), KC_STREAMS, KC_PIPE_ALL,
  *                   KC_STREAM_BUILD (BUILD variants), KC_REVERSE (0 = every member row streamed forward: no reverse rows; like KC_REV_* read when the lists of a graph are built, i.e. at its first k-clique call), KC_REV_MIN (edges a hub
  *                   receiver must get to take them, default 64), KC_REV_FACTOR (10 x how much cheaper in bytes the reverse side must be; default 0: every hub edge whose receiver qualifies), KC_REV_GW (8 / 16 lanes per record in the receivers' kernels),
@@ -162,7 +165,8 @@ typedef struct gmsx_stats {
     uint64_t units;            /* work units processed: intersect_count calls (edges) / root vertices */
     uint64_t alg_elements;     /* Σ(d_u+d_v) over the units of this call, 0 if n/a */
     uint64_t probes;           /* TC: id slots the oriented kernels probe (8 per list unit, 14 per byte-delta unit, 4 words per bitset
-                                * unit, 4 / 6 per tail unit); BK: resume rounds; else 0 */
+                                * unit, 4 / 6 per tail unit) — the bit products of the dense core (TC_CORE) are NOT counted; BK: resume rounds;
+                                * else 0 */
     int32_t launches;          /* number of kernel launches inside kernel_ms */
     int32_t reserved;
     uint64_t stream_bytes;     /* TC (oriented): algorithmic bytes of THIS formulation per call — every pivot's own containers once, plus
@@ -252,7 +256,9 @@ int gmsx_tc_divisor(int algo); /* 1 for ORIENTED/AUTO, 3 for FULL */
  * list, 16-bit delta); out[5]: the entries themselves; out[6]: the pivots' own containers, once per work item; out[7]: the part of
  * out[0] + out[3] that is inline rows (ids handed over by light pivots); out[8..10]: the light-pivot kernel — hub rows, tail rows of
  * the far light members it streams, and its own lists + descriptors; out[11..14]: counts — entries, inline entries, work items,
- * members streamed by the light-pivot kernel; out[15..20]: 0.  out[0..6] + out[8..10] = stream_bytes.  21 values, host. */
+ * members streamed by the light-pivot kernel; out[15]: the dense core (TC_CORE) — per 64 x 64 block the fragment bytes of its 2 x 64 rows
+ * and its mask words, no reuse assumed; out[16]: K of the core (0 = none); out[17..20]: 0.  out[0..6] + out[8..10] + out[15] = stream_bytes.
+ * 21 values, host. */
 int gmsx_tc_stream_breakdown(const gmsx_graph *g, uint64_t *out21);
 /* Diagnostics: the stream rows named by the work items' entries as a histogram over row length in 16-byte units — out[(cls*24 +
  * bin)*2] rows, [+1] units; cls 0..4 = hub rows as list / bitset / byte-delta, tail rows as list / delta; bin = 1 … 16 units exactly,
