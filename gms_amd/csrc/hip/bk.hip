@@ -15,18 +15,19 @@
 // the others are BUILT by workgroups — k_bk_block, a piece of 2048 row jobs of a start vertex per work item, Cadj | XT straight into an arena
 // — and leave a root record.  Rounds >= 1 (k_bk_resume): one wave per record runs the recursion with an explicit stack in a global slab and,
 // past its node budget, re-splits what is left into records for the next round.
+#include "device_buffer.hpp"
 #include "device_graph.hpp"
+#include "rank_check.hpp"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 namespace gmsx {
 
@@ -2122,398 +2123,409 @@ static int64_t part_count(int64_t first, int64_t end, int nparts, int part) {
     return span <= 0 ? 0 : (span + nparts - 1) / nparts;
 }
 
-static int bk_partial(const gmsx_graph *g, int part, int nparts, uint64_t *out, gmsx_stats *st) {
-    Ctx &c = ctx();
-    hipStream_t s = c.stream;
-    const int64_t n = g->n;
-    struct Guard { void *p = nullptr; ~Guard() { (void)hipFree(p); } } g_acc, g_ki, g_ko, g_vi, g_vo, g_tmp, g_arena, g_pool0, g_pool1, g_dir0, g_dir1;
-    unsigned long long *acc = nullptr;
-    // control words after the 64 spread accumulators: [0] isolated vertices [1] giant tasks [2] queue [3] arena head [4] pool head [5] directory count
-    // [6] stack words of k_bk_resume [7..9] slab words of a 16- / 8- / 4-lane search [10] build queue [11] LDS-task queue [12..14] k_bk_resume4's queues [16..20] layout maxima
-    constexpr int kCtl = 64 * 16;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&acc), sizeof(unsigned long long) * (kCtl + 32)));
-    g_acc.p = acc;
-    GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * (kCtl + 32), s));
-    if (n == 0) {
-        *out = 0;
-        if (st) *st = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0};
+// per start vertex of a range of the task order: arena words, record words and k_bk_block pieces (k_bk_layout) and their exclusive sums, count + 1 entries each
+struct BkLayout {
+    DevBuf mem[6];
+    int64_t *need_a = nullptr, *need_r = nullptr, *need_p = nullptr, *aoff = nullptr, *roff = nullptr, *poff = nullptr;
+    int alloc(int64_t count, bool with_poff) {
+        int64_t **const ptr[6] = {&need_a, &need_r, &need_p, &aoff, &roff, &poff};
+        for (int i = 0; i < (with_poff ? 6 : 5); ++i) {
+            GMSX_HIP(hipMalloc(&mem[i].p, size_t(count + 1) * 8));
+            *ptr[i] = mem[i].as<int64_t>();
+        }
         return GMSX_OK;
     }
-    // ---- tasks: slab requirement per start vertex, heavy first (untimed setup, like the reference's preprocessing step)
-    unsigned long long *k_in = nullptr, *k_out = nullptr;
-    int32_t *v_in = nullptr, *v_out = nullptr;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&k_in), size_t(n) * 8)); g_ki.p = k_in;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&k_out), size_t(n) * 8)); g_ko.p = k_out;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&v_in), size_t(n) * 4)); g_vi.p = v_in;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&v_out), size_t(n) * 4)); g_vo.p = v_out;
-    GMSX_HIP(hipEventRecord(c.ev[0], s));
-    int max_c = kBkMaxCand;
-    if (const char *e = opt("BK_MAXC")) {  // test hook: a lower width limit sends more start vertices through the memory-resident search
-        const int v = std::atoi(e);
-        if (v >= 1 && v < kBkMaxCand) max_c = v;
-    }
-    const unsigned long long giant_cap = (unsigned long long)std::min<int64_t>(n, int64_t(1) << 20);
-    int32_t *giant = nullptr;
-    Guard g_giant;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&giant), size_t(giant_cap) * 4));
-    g_giant.p = giant;
-    hipLaunchKernelGGL(k_bk_tasks, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, n, g->off, g->oldid, g->dplus, k_in, v_in, max_c, giant, giant_cap,
-                       acc + kCtl);
-    size_t tmp_bytes = 0;
-    GMSX_HIP(rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, size_t(n), 0, 64, s));
-    void *tmp = nullptr;
-    GMSX_HIP(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 8));
-    g_tmp.p = tmp;
-    GMSX_HIP(rocprim::radix_sort_pairs_desc(tmp, tmp_bytes, k_in, k_out, v_in, v_out, size_t(n), 0, 64, s));
-    std::unique_ptr<unsigned long long[]> words_mem(new (std::nothrow) unsigned long long[static_cast<size_t>(n > 0 ? n : 1)]);  // 1 GB at scale 27
-    if (!words_mem) return GMSX_ERR_NOMEM;
-    unsigned long long *const words = words_mem.get();
-    unsigned long long head[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    GMSX_HIP(hipMemcpyAsync(words, k_out, size_t(n) * 8, hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipMemcpyAsync(head, acc + kCtl, sizeof(head), hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipStreamSynchronize(s));
-    const int64_t n_giant = int64_t(head[1]);    // start vertices beyond the register-resident width: memory-resident search after the rounds
-    const unsigned long long giant_slab_w = (head[2] + 3ull) & ~3ull;
-    if (n_giant > int64_t(giant_cap)) return GMSX_ERR_UNSUPPORTED;  // more than a million of them
-    const int64_t n_wide = int64_t(head[7]);     // tasks with more than 2048 candidates: sorted first (kWideTask), WPL = 2 / 4 / 8 kernels
-    const int widest = std::min(g->max_dplus, max_c);  // candidates of a start vertex = its d+
-    const int wpl_wide = widest <= 4096 ? 2 : widest <= 8192 ? 4 : 8;
-    for (int64_t i = 0; i < n_wide; ++i) words[size_t(i)] &= ~kWideTask;
-    GMSX_HIP(hipMemsetAsync(acc + kCtl + 7, 0, 8, s));  // ([7] held the number of wide tasks until here)
+};
 
-    // ---- arena + record pools of the load balancer
+// One count call (gmsx_bk_partial): its state, and its phases in the order run() goes through them.  Every device buffer is a DevBuf of the call,
+// allocated as GMSX_HIP(hipMalloc(&d.p, bytes)) — out of memory is GMSX_ERR_DEVICE_MEM, any other failure GMSX_ERR_KERNEL — and freed when the call is over.
+struct BkCall {
+    const gmsx_graph *const g;
+    const int part, nparts;
+    Ctx &c = ctx();
+    const hipStream_t s = c.stream;
+    const int64_t n = g->n;
     const int cu = c.compute_units > 0 ? c.compute_units : 256;
-    size_t free_b = 0, total_b = 0;
-    GMSX_HIP(hipMemGetInfo(&free_b, &total_b));
-    const unsigned long long budget_bytes = std::min<unsigned long long>(free_b / 4, 16ull << 30);
-    BkShared sh{};
-    // the arena (Cadj | XT of the start vertices of a chunk + of the LDS-slab searches that split) is sized by NEED once the layout of the
-    // start vertices is known — a fixed 48 GB allocation per call cost seconds of first-touch time now and then
-    unsigned long long arena_hard_cap = std::min<unsigned long long>(free_b / 4, 48ull << 30) / 4;
-    if (const char *e = opt("BK_ARENA_MB")) {  // test hook: a small arena makes small graphs build their roots in several chunks
-        const long v = std::atol(e);
-        if (v >= 1) arena_hard_cap = std::min<unsigned long long>(arena_hard_cap, ((unsigned long long)v << 20) / 4);
-    }
-    auto alloc_arena = [&](unsigned long long want_words) -> int {
-        sh.arena_cap = std::min(arena_hard_cap, std::max<unsigned long long>(want_words, (256ull << 20) / 4));
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&sh.arena), sh.arena_cap * 4 + 64));  // + 64: 16-byte loads may run 12 bytes past a row
-        g_arena.p = sh.arena;
-        return GMSX_OK;
-    };
     // 1 = records with at most 512 candidates are searched four to a wave (k_bk_resume4, default); 0 = every record by k_bk_resume (round 4)
-    const bool use_groups = [] { const char *e = opt("BK_GROUPS"); return !e || std::atoi(e) != 0; }();
-    sh.pool_cap = std::min<unsigned long long>(free_b / 16, 2ull << 30) / 4;
-    sh.dir_cap = 8ull << 20;
-    uint32_t *pools[2] = {nullptr, nullptr};
-    unsigned long long *dirs[2] = {nullptr, nullptr};
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&pools[0]), sh.pool_cap * 4 + 64)); g_pool0.p = pools[0];  // + 64: 16-byte loads may run 12 bytes past a record
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&pools[1]), sh.pool_cap * 4 + 64)); g_pool1.p = pools[1];
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&dirs[0]), sh.dir_cap * 8)); g_dir0.p = dirs[0];
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&dirs[1]), sh.dir_cap * 8)); g_dir1.p = dirs[1];
-    unsigned long long *queue = acc + kCtl + 2, *gqueue = acc + kCtl + 12;  // tickets of k_bk_resume / k_bk_resume4
-    sh.arena_head = acc + kCtl + 3;
-    sh.pool_head = acc + kCtl + 4;
-    sh.dir_count = acc + kCtl + 5;
-    sh.max_stack = acc + kCtl + 6;
-    // nodes before a search is re-split.  Round 3 swept 128 … 8192 on the config-4 graph and Kronecker scale 14 and took 512; with round 4's build
-    // pipeline the configs[3] graph takes 248.6 / 209.5 / 203.1 / 200.0 / 204.0 ms at 256 / 512 / 1024 / 2048 / 4096, RMAT 18 ef 64 (a = .45)
-    // 275.9 -> 260.1 ms at 2048, the sparse graphs (one round) are indifferent
-    sh.budget = 2048;
-    sh.small_p = [] { const char *e = opt("BK_SMALL_P"); return e ? std::atoi(e) : 6; }();  // swept on the configs[3] graph: 0 (off) 316 ms, 2 304, 3 ~300, 4 295, 6 293, 8 295, 16 303
-    sh.small_p_groups = [] { const char *e = opt("BK_SMALL_P_GROUPS"); return e ? std::atoi(e) : 12; }();
-    sh.bmoff = g->bmoff;
-    sh.bmpool = g->bmpool;
-    sh.dense_limit = g->dense_limit;
-    if (const char *e = opt("BK_BUDGET")) {  // tuning knob: nodes a search may visit before it is re-split
-        const long v = std::atol(e);
-        if (v >= 16 && v <= (1l << 30)) sh.budget = unsigned(v);
-    }
-    unsigned budget0 = sh.budget;  // round 0 (start vertices: build + first stretch of the search)
-    if (const char *e = opt("BK_BUDGET0")) {
-        const long v = std::atol(e);
-        if (v >= 16 && v <= (1l << 30)) budget0 = unsigned(v);
-    }
-    const unsigned budget_resume = sh.budget;
-    sh.budget = budget0;
-    int cur = 0;
-    sh.pool = pools[cur];
-    sh.dir = dirs[cur];
-    GMSX_HIP(hipMemsetAsync(sh.dir, 0xff, sh.dir_cap * 8, s));
+    const bool use_groups = opt_int("BK_GROUPS", 1) != 0;
+    const int64_t resume_grab = std::max<long long>(1, opt_int("BK_RESUME_GRAB", 1));  // measured on configs[3]: 8 costs 4 ms (the records of a round differ in cost; their queue is not the limit)
     // 2 (default): k_bk_block, a workgroup per start vertex, rows streamed against an LDS bitmap; 1: k_bk_build, a wave per start vertex with
     // the hash-map build of k_bk_wave; 0: round 2's combined build + search bins
-    const int64_t resume_grab = [] { const char *e = opt("BK_RESUME_GRAB"); return e ? std::max(1, std::atoi(e)) : 1; }();  // measured on configs[3]: 8 costs 4 ms (the records of a round differ in cost; their queue is not the limit)
-    const int split_build = [] { const char *e = opt("BK_SPLIT_BUILD"); return e ? std::atoi(e) : 2; }();
-    int64_t n_tasks = 0;
-    while (n_tasks < n && words[size_t(n_tasks)] > 0) ++n_tasks;
-    int64_t n_glob = 0;  // tasks beyond an LDS slab: sorted first (the wide ones, > 2048 candidates, at the very front)
-    while (n_glob < n_tasks && (n_glob < n_wide || words[size_t(n_glob)] > (unsigned long long)kLdsSlabWords)) ++n_glob;
-    // LAYOUT of the start vertices that get their own build kernel (arena and record offsets by prefix sums) and the arena itself: setup like
-    // the task sort above — allocations of gigabytes now and then stall for a second, they are not part of the kernels' time
-    const int64_t cnt_glob = split_build ? part_count(0, n_glob, nparts, part) : 0;
-    int64_t need_total = 0;  // arena words of the start vertices built by k_bk_block
-    const int64_t cnt_tiny = part_count(n_glob, n_tasks, nparts, part);
-    const bool tiny_roots = use_groups && split_build >= 2 && cnt_glob > 0 && [] { const char *e = opt("BK_TINY_ROOTS"); return e && std::atoi(e) != 0; }();
-    int64_t *t_need_a = nullptr, *t_need_r = nullptr, *t_need_p = nullptr, *t_aoff = nullptr, *t_roff = nullptr, tiny_a = 0, tiny_r = 0;
-    Guard g_tna, g_tnr, g_tnp, g_tao, g_tro;
-    int64_t *need_a = nullptr, *need_r = nullptr, *aoff = nullptr, *roff = nullptr, *d_end = nullptr, *need_p = nullptr, *poff = nullptr;
-    unsigned long long *pieces = nullptr;
-    Guard g_na, g_nr, g_ao, g_ro, g_de, g_map, g_np, g_po, g_pc;
-    unsigned long long *maxima = acc + kCtl + 16;  // [0] stack words, [1] global map words, [2..4] slab words of a 16- / 8- / 4-lane search
+    const int split_build = int(opt_int("BK_SPLIT_BUILD", 2));
+    // the LDS-slab tasks: 1 (default) beside the build of the first chunk, 0 one after the other (profiling), 2 beside the FIRST RESUME ROUND (what they
+    // split off joins that round's output)
+    const int tiny_mode = int(opt_int("BK_TINY_BESIDE", 1));
+    const bool verbose = opt("BK_VERBOSE") != nullptr;
+    static constexpr int kGroupWavesPerCu = 4 * GMSX_BK_GROUP_WAVES;
+
+    // control words after the 64 spread accumulators: [0] isolated vertices [1] giant tasks [2] queue [3] arena head [4] pool head [5] directory count
+    // [6] stack words of k_bk_resume [7..9] slab words of a 16- / 8- / 4-lane search [10] build queue [11] LDS-task queue [12..14] k_bk_resume4's queues [16..20] layout maxima
+    static constexpr int kCtl = 64 * 16;
+    DevBuf d_acc;
+    unsigned long long *acc = nullptr;
+    unsigned long long *ctl(int i) const { return acc + kCtl + i; }
+    unsigned long long *queue() const { return ctl(2); }    // tickets of k_bk_resume (and of the bins without a build kernel)
+    unsigned long long *gqueue() const { return ctl(12); }  // … of k_bk_resume4
+    unsigned long long *maxima() const { return ctl(16); }  // [0] stack words, [1] global map words, [2..4] slab words of a 16- / 8- / 4-lane search
+
+    // tasks()
+    DevBuf d_kin, d_kout, d_vin, d_vout, d_giant, d_sort_tmp;
+    int32_t *v_out = nullptr, *giant = nullptr;    // start vertices, heavy first | those beyond the register-resident width
+    std::unique_ptr<unsigned long long[]> words;   // slab requirement per task, in task order (1 GB at scale 27)
+    int64_t n_giant = 0, n_wide = 0, n_tasks = 0, n_glob = 0;
+    unsigned long long giant_slab_w = 0;
+    int widest = 0, wpl_wide = 1;
+    // make_pools()
+    size_t free_b = 0;
+    unsigned long long budget_bytes = 0, arena_hard_cap = 0;
+    BkShared sh{};
+    DevBuf d_arena, d_pool[2], d_dir[2];
+    uint32_t *pools[2] = {nullptr, nullptr};
+    unsigned long long *dirs[2] = {nullptr, nullptr};
+    unsigned budget_resume = 0;
+    int cur = 0;
+    // layout()
+    int64_t cnt_glob = 0, cnt_tiny = 0, need_total = 0, tiny_a = 0, tiny_r = 0, build_waves = 0;
+    bool tiny_roots = false;
+    BkLayout lay, tlay;  // of the start vertices with a build kernel | of the LDS-slab tasks (BK_TINY_ROOTS)
+    DevBuf d_end, d_pieces, d_map;
     unsigned long long mx[5] = {0, 0, 0, 0, 0}, map_words = 0;  // [0] stack words of k_bk_resume, [1] global map words, [2..4] slab words of a 16- / 8- / 4-lane search
-    int64_t build_waves = 0;
-    uint32_t *map_scratch = nullptr;
-    if (cnt_glob > 0) {
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&need_a), size_t(cnt_glob + 1) * 8)); g_na.p = need_a;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&need_r), size_t(cnt_glob + 1) * 8)); g_nr.p = need_r;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&aoff), size_t(cnt_glob + 1) * 8)); g_ao.p = aoff;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&roff), size_t(cnt_glob + 1) * 8)); g_ro.p = roff;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&d_end), 8)); g_de.p = d_end;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&need_p), size_t(cnt_glob + 1) * 8)); g_np.p = need_p;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&poff), size_t(cnt_glob + 1) * 8)); g_po.p = poff;
-        GMSX_HIP(hipMemsetAsync(maxima, 0, 40, s));
-        hipLaunchKernelGGL(k_bk_layout, dim3(unsigned(cnt_glob / 256 + 1)), dim3(256), 0, s, int64_t(0), cnt_glob, nparts, part, v_out, g->off, g->oldid, g->dplus,
-                           split_build >= 2 ? 1 : 0, need_a, need_r, need_p, maxima);
-        {
-            size_t scan_bytes = 0;
-            GMSX_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, need_a, aoff, int64_t(0), size_t(cnt_glob + 1), rocprim::plus<int64_t>(), s));
-            void *scan_tmp = nullptr;
-            GMSX_HIP(hipMalloc(&scan_tmp, scan_bytes ? scan_bytes : 8));
-            Guard g_scan;
-            g_scan.p = scan_tmp;
-            GMSX_HIP(rocprim::exclusive_scan(scan_tmp, scan_bytes, need_a, aoff, int64_t(0), size_t(cnt_glob + 1), rocprim::plus<int64_t>(), s));
-            GMSX_HIP(rocprim::exclusive_scan(scan_tmp, scan_bytes, need_r, roff, int64_t(0), size_t(cnt_glob + 1), rocprim::plus<int64_t>(), s));
-            GMSX_HIP(rocprim::exclusive_scan(scan_tmp, scan_bytes, need_p, poff, int64_t(0), size_t(cnt_glob + 1), rocprim::plus<int64_t>(), s));
-            GMSX_HIP(hipStreamSynchronize(s));
-        }
-        if (split_build >= 2) {  // the work items of k_bk_block
-            int64_t n_pieces = 0;
-            GMSX_HIP(hipMemcpy(&n_pieces, poff + cnt_glob, 8, hipMemcpyDeviceToHost));
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&pieces), size_t(n_pieces + 1) * 8)); g_pc.p = pieces;
-            hipLaunchKernelGGL(k_bk_pieces, dim3(unsigned(cnt_glob / 256 + 1)), dim3(256), 0, s, cnt_glob, poff, pieces);
-        }
-        // GMSX_BK_TINY_ROOTS=1 (off by default): the LDS-slab tasks are BUILT by k_bk_wave<true> and SEARCHED by k_bk_resume4 — they leave Cadj | XT in the arena
-        // and a root record in the pool, at offsets from the same kind of layout scans (their x = in-neighbours only: the wave build compacts them).  Measured
-        // on configs[3]: round 0 62 -> 55 ms (the build alone beside k_bk_block), round 1 32.8 -> 48.8 ms (1.65 M searches of ~33 nodes: a record fetch and a
-        // root pivot each) — 156 against 147.4 ms: their search in LDS, hidden beside the build, is the cheaper place
-        if (tiny_roots && cnt_tiny > 0) {
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&t_need_a), size_t(cnt_tiny + 1) * 8)); g_tna.p = t_need_a;
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&t_need_r), size_t(cnt_tiny + 1) * 8)); g_tnr.p = t_need_r;
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&t_need_p), size_t(cnt_tiny + 1) * 8)); g_tnp.p = t_need_p;
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&t_aoff), size_t(cnt_tiny + 1) * 8)); g_tao.p = t_aoff;
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&t_roff), size_t(cnt_tiny + 1) * 8)); g_tro.p = t_roff;
-            hipLaunchKernelGGL(k_bk_layout, dim3(unsigned(cnt_tiny / 256 + 1)), dim3(256), 0, s, n_glob, cnt_tiny, nparts, part, v_out, g->off, g->oldid, g->dplus, 0,
-                               t_need_a, t_need_r, t_need_p, maxima);
-            size_t scan_bytes = 0;
-            GMSX_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, t_need_a, t_aoff, int64_t(0), size_t(cnt_tiny + 1), rocprim::plus<int64_t>(), s));
-            void *scan_tmp = nullptr;
-            GMSX_HIP(hipMalloc(&scan_tmp, scan_bytes ? scan_bytes : 8));
-            Guard g_scan;
-            g_scan.p = scan_tmp;
-            GMSX_HIP(rocprim::exclusive_scan(scan_tmp, scan_bytes, t_need_a, t_aoff, int64_t(0), size_t(cnt_tiny + 1), rocprim::plus<int64_t>(), s));
-            GMSX_HIP(rocprim::exclusive_scan(scan_tmp, scan_bytes, t_need_r, t_roff, int64_t(0), size_t(cnt_tiny + 1), rocprim::plus<int64_t>(), s));
-            GMSX_HIP(hipStreamSynchronize(s));
-            GMSX_HIP(hipMemcpy(&tiny_a, t_aoff + cnt_tiny, 8, hipMemcpyDeviceToHost));
-            GMSX_HIP(hipMemcpy(&tiny_r, t_roff + cnt_tiny, 8, hipMemcpyDeviceToHost));
-        }
-        GMSX_HIP(hipMemcpy(mx, maxima, sizeof(mx), hipMemcpyDeviceToHost));
-        GMSX_HIP(hipMemcpy(&need_total, aoff + cnt_glob, 8, hipMemcpyDeviceToHost));
-        // the roots may take 3/4 of the arena (below): everything in one chunk when the device allows, + room for the LDS-slab searches that split
-        if (int rc = alloc_arena((unsigned long long)need_total / 3 * 4 + (unsigned long long)tiny_a + (512ull << 20) / 4)) return rc;
-        if (opt("BK_VERBOSE"))
-            std::fprintf(stderr, "[gmsx bk] start vertices %lld: %lld built in the arena (%lld words), %lld in LDS slabs\n", (long long)n_tasks, (long long)cnt_glob,
-                         (long long)need_total, (long long)(n_tasks - n_glob));
-        map_words = split_build >= 2 ? 0ull : (mx[1] + 3ull) & ~3ull;
-        build_waves = std::min<int64_t>(cnt_glob, int64_t(cu) * 24);
-        if (map_words > 0) {
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&map_scratch), size_t(build_waves) * map_words * 4));
-            g_map.p = map_scratch;
-        }
-    }
-    // the stack slabs of the resume kernel (grow-only, reused by every round): for the root round their size is known from the layout
-    Guard g_rslab, g_gslab;
+    DevBuf d_rslab, d_gslab;  // the stack slabs of the resume kernels (grow-only, reused by every round)
     size_t resume_cap = 0, group_cap = 0;
-    const bool any_wide_records = !use_groups || widest > kBkGroupMaxC;  // k_bk_resume has records to search
-    if (cnt_glob > 0 && mx[0] > 0 && any_wide_records) {
-        const unsigned long long slab_bytes = ((mx[0] + 3ull) & ~3ull) * 4ull;
-        if (slab_bytes <= budget_bytes) {
-            const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({cnt_glob, int64_t(cu) * 24, int64_t(budget_bytes / slab_bytes)}));
-            resume_cap = size_t(waves) * slab_bytes;
-            GMSX_HIP(hipMalloc(&g_rslab.p, resume_cap));
-        }
-    }
-    const int group_waves_per_cu = 4 * GMSX_BK_GROUP_WAVES;
-    // words of a wave's slab area in k_bk_resume4: 4 searches of 16 lanes, 8 of 8 or 16 of 4, whichever class needs most
-    auto group_wave_words = [](unsigned long long w16, unsigned long long w8, unsigned long long w4) {
-        return std::max({4ull * ((w16 + 3ull) & ~3ull), 8ull * ((w8 + 3ull) & ~3ull), 16ull * ((w4 + 3ull) & ~3ull)});
-    };
-    if (cnt_glob > 0 && (mx[2] | mx[3] | mx[4]) != 0 && use_groups) {
-        const unsigned long long slab_bytes = group_wave_words(mx[2], mx[3], mx[4]) * 4ull;
-        if (slab_bytes <= budget_bytes) {
-            const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({(cnt_glob + (tiny_roots ? cnt_tiny : 0) + 3) / 4, int64_t(cu) * group_waves_per_cu, int64_t(budget_bytes / slab_bytes)}));
-            group_cap = size_t(waves) * slab_bytes;
-            GMSX_HIP(hipMalloc(&g_gslab.p, group_cap));
-        }
-    }
-    GMSX_HIP(hipStreamSynchronize(s));
-    GMSX_HIP(hipEventRecord(c.ev[1], s));
-
-    // ---- round 0.  Start vertices whose structures fit an LDS slab (<= kLdsSlabWords): one wave builds and searches (k_bk_wave<true>).
-    //      The others (GMSX_BK_SPLIT_BUILD=0 restores round 2's one-kernel bins): k_bk_build writes Cadj | XT into the arena and a root
-    //      record per start vertex, in chunks that fit the arena and the record pool; the resume rounds below search them.
-    int launches = 0;
-    // ---- rounds >= 1: resume the split searches (and search the root records of k_bk_build) until no record is left
-    int rounds = 0;
-    // GMSX_BK_TINY_BESIDE=2: the LDS-slab tasks run beside the FIRST RESUME ROUND (what they split off joins that round's output) instead of beside the
-    // build: hooks called around the launch of a round's kernels, and before the next round reads the counters
-    std::function<int()> round_pre, round_post, round_join;
-    auto run_rounds = [&]() -> int {
-    while (true) {
-        if (round_join) {
-            if (int rc = round_join()) return rc;
-            round_join = nullptr;
-        }
-        unsigned long long ctl[6] = {0, 0, 0, 0, 0, 0};  // pool_head, dir_count, max_stack, slab words of a 16- / 8- / 4-lane search
-        GMSX_HIP(hipMemcpyAsync(ctl, sh.pool_head, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipStreamSynchronize(s));
-        // a wave whose allocation overshot a capacity kept its search: only fully written records are below the caps
-        const unsigned long long n_rec = std::min(ctl[1], sh.dir_cap);
-        if (n_rec == 0) break;
-        const unsigned long long stack_w = (ctl[2] + 3ull) & ~3ull, group_w = group_wave_words(ctl[3], ctl[4], ctl[5]);
-        const uint32_t *pool_in = pools[cur];
-        const unsigned long long *dir_in = dirs[cur];
-        cur ^= 1;
-        sh.pool = pools[cur];
-        sh.dir = dirs[cur];
-        GMSX_HIP(hipMemsetAsync(queue, 0, 8, s));
-        GMSX_HIP(hipMemsetAsync(gqueue, 0, 24, s));
-        GMSX_HIP(hipMemsetAsync(sh.pool_head, 0, 6 * sizeof(unsigned long long), s));
-        GMSX_HIP(hipMemsetAsync(sh.dir, 0xff, sh.dir_cap * 8, s));
-        // few records left: split sooner so that the idle waves get work (the tail rounds are latency-, not throughput-bound)
-        const int64_t full = int64_t(cu) * 24 * 2;
-        sh.budget = int64_t(n_rec) >= full ? budget_resume : unsigned(std::max<int64_t>(128, int64_t(budget_resume) * int64_t(n_rec) / full));
-        // records per queue ticket (GMSX_BK_RESUME_GRAB, default 1: eight cost 4 ms on configs[3] — the records of a round differ in cost, their queue is not the limit)
-        const unsigned grab = unsigned(std::max<int64_t>(1, std::min<int64_t>(resume_grab, int64_t(n_rec) / (int64_t(cu) * 24 * 16))));
-        if (round_pre) {
-            if (int rc = round_pre()) return rc;
-            round_pre = nullptr;
-        }
-        if (use_groups && group_w > 0) {  // records with at most 512 candidates: four searches per wave
-            const unsigned long long slab_bytes = group_w * 4ull;
-            if (slab_bytes > budget_bytes) return GMSX_ERR_DEVICE_MEM;
-            const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({int64_t((n_rec + 3) / 4), int64_t(cu) * group_waves_per_cu, int64_t(budget_bytes / slab_bytes)}));
-            if (size_t(waves) * slab_bytes > group_cap) {  // grow-only, reused by every round
-                (void)hipFree(g_gslab.p);
-                g_gslab.p = nullptr;
-                group_cap = size_t(waves) * slab_bytes;
-                GMSX_HIP(hipMalloc(&g_gslab.p, group_cap));
-            }
-            if (opt("BK_VERBOSE"))
-                std::fprintf(stderr, "[gmsx bk] round %d: %llu records (%llu pool words), %lld waves of 4 / 8 / 16 searches, %llu slab words each, budget %u\n", rounds + 1,
-                             n_rec, ctl[0], (long long)waves, group_w, sh.budget);
-            hipLaunchKernelGGL(k_bk_resume4, dim3(unsigned(waves)), dim3(64), 0, s, pool_in, dir_in, n_rec, gqueue, grab, static_cast<uint32_t *>(g_gslab.p), group_w,
-                               (ctl[3] + 3ull) & ~3ull, (ctl[4] + 3ull) & ~3ull, (ctl[5] + 3ull) & ~3ull, acc, sh);
-            ++launches;
-        }
-        if (!use_groups || widest > kBkGroupMaxC) {  // the others (every record with GMSX_BK_GROUPS=0): one search per wave
-            const int min_c = use_groups ? kBkGroupMaxC + 1 : 0;
-            const unsigned long long slab_bytes = std::max<unsigned long long>(stack_w * 4ull, 16);
-            if (slab_bytes > budget_bytes) return GMSX_ERR_DEVICE_MEM;
-            const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({int64_t(n_rec), int64_t(cu) * 24, int64_t(budget_bytes / slab_bytes)}));
-            if (size_t(waves) * slab_bytes > resume_cap) {  // grow-only stack slabs, reused by every round
-                (void)hipFree(g_rslab.p);
-                g_rslab.p = nullptr;
-                resume_cap = size_t(waves) * slab_bytes;
-                GMSX_HIP(hipMalloc(&g_rslab.p, resume_cap));
-            }
-            if (opt("BK_VERBOSE"))
-                std::fprintf(stderr, "[gmsx bk] round %d: %llu records (%llu pool words), %lld waves, stack %llu words, budget %u\n", rounds + 1, n_rec, ctl[0],
-                             (long long)waves, stack_w, sh.budget);
-            if (n_wide > 0 && wpl_wide == 2)  // records of wide tasks may be anywhere in the pool
-                hipLaunchKernelGGL(k_bk_resume<2>, dim3(unsigned(waves)), dim3(64), 0, s, pool_in, dir_in, n_rec, queue, grab,
-                                   static_cast<uint32_t *>(g_rslab.p), stack_w, acc, sh, min_c);
-            else if (n_wide > 0 && wpl_wide == 4)
-                hipLaunchKernelGGL(k_bk_resume<4>, dim3(unsigned(waves)), dim3(64), 0, s, pool_in, dir_in, n_rec, queue, grab,
-                                   static_cast<uint32_t *>(g_rslab.p), stack_w, acc, sh, min_c);
-            else if (n_wide > 0)
-                hipLaunchKernelGGL(k_bk_resume<8>, dim3(unsigned(waves)), dim3(64), 0, s, pool_in, dir_in, n_rec, queue, grab,
-                                   static_cast<uint32_t *>(g_rslab.p), stack_w, acc, sh, min_c);
-            else
-                hipLaunchKernelGGL(k_bk_resume<1>, dim3(unsigned(waves)), dim3(64), 0, s, pool_in, dir_in, n_rec, queue, grab,
-                                   static_cast<uint32_t *>(g_rslab.p), stack_w, acc, sh, min_c);
-            ++launches;
-        }
-        if (round_post) {
-            if (int rc = round_post()) return rc;
-            round_post = nullptr;
-        }
-        if (++rounds > 100000) return GMSX_ERR_KERNEL;
-    }
-    return GMSX_OK;
-    };
-
-    // the LDS-slab tasks: their own queue word; `beside` = on a side stream next to the build kernel that was just launched on s (the build
-    // streams rows at 8 workgroups per CU, the tiny searches live in LDS: each leaves what the other needs), joined before the rounds
-    unsigned long long *tqueue = acc + kCtl + 11;
-    bool tiny_beside = false;
-    struct TinyJoin {  // every way out joins the side stream again (error returns free buffers the kernel beside may still use)
-        Ctx &c;
-        hipStream_t s;
-        bool &armed;
-        ~TinyJoin() {
-            if (armed && hipEventRecord(c.ev_join[0], c.side[0]) == hipSuccess) {
-                (void)hipStreamWaitEvent(s, c.ev_join[0], 0);
-                (void)hipStreamSynchronize(s);
-            }
-        }
-    } tiny_join{c, s, tiny_beside};
+    // the rounds
+    int launches = 0, rounds = 0;
+    bool tiny_beside = false;  // a kernel of the LDS-slab tasks is running on the side stream
+    bool tiny_pending = false;  // BK_TINY_BESIDE = 2: the LDS-slab tasks wait for the first resume round
     unsigned long long emit_abase = 0, emit_rbase = 0, emit_dbase = 0;
     bool emit = false;  // set by the first chunk when the LDS-slab tasks' roots fit behind its own
-    auto launch_tiny = [&](int64_t lo, int64_t hi, bool beside) -> int {
-        const int64_t cnt = part_count(lo, hi, nparts, part);
-        if (cnt <= 0) return GMSX_OK;
-        GMSX_HIP(hipMemsetAsync(tqueue, 0, 8, s));
+
+    BkCall(const gmsx_graph *g_, int part_, int nparts_) : g(g_), part(part_), nparts(nparts_) {}
+    ~BkCall() {  // every way out joins the side stream again (error returns free buffers the kernel beside may still use)
+        if (tiny_beside && hipEventRecord(c.ev_join[0], c.side[0]) == hipSuccess) {
+            (void)hipStreamWaitEvent(s, c.ev_join[0], 0);
+            (void)hipStreamSynchronize(s);
+        }
+    }
+
+    int run(uint64_t *out, gmsx_stats *st) {
+        GMSX_HIP(hipMalloc(&d_acc.p, sizeof(unsigned long long) * (kCtl + 32)));
+        acc = d_acc.as<unsigned long long>();
+        GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * (kCtl + 32), s));
+        if (n == 0) {
+            *out = 0;
+            if (st) *st = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0};
+            return GMSX_OK;
+        }
+        // untimed setup (ev[0] .. ev[1]), like the reference's preprocessing step
+        if (int rc = tasks()) return rc;
+        if (int rc = make_pools()) return rc;
+        if (int rc = layout()) return rc;
+        GMSX_HIP(hipStreamSynchronize(s));
+        GMSX_HIP(hipEventRecord(c.ev[1], s));
+        if (int rc = split_build ? built_roots() : bins()) return rc;
+        if (int rc = giant_tail()) return rc;
+        GMSX_HIP(hipEventRecord(c.ev[2], s));
+        GMSX_HIP(hipGetLastError());
+        return result(out, st);
+    }
+
+    // ---- tasks: slab requirement per start vertex, heavy first
+    int tasks() {
+        GMSX_HIP(hipMalloc(&d_kin.p, size_t(n) * 8));
+        GMSX_HIP(hipMalloc(&d_kout.p, size_t(n) * 8));
+        GMSX_HIP(hipMalloc(&d_vin.p, size_t(n) * 4));
+        GMSX_HIP(hipMalloc(&d_vout.p, size_t(n) * 4));
+        unsigned long long *const k_in = d_kin.as<unsigned long long>(), *const k_out = d_kout.as<unsigned long long>();
+        int32_t *const v_in = d_vin.as<int32_t>();
+        v_out = d_vout.as<int32_t>();
+        GMSX_HIP(hipEventRecord(c.ev[0], s));
+        const long long maxc_opt = opt_int("BK_MAXC", kBkMaxCand);  // test hook: a lower width limit sends more start vertices through the memory-resident search
+        const int max_c = maxc_opt >= 1 && maxc_opt < kBkMaxCand ? int(maxc_opt) : kBkMaxCand;
+        const unsigned long long giant_cap = (unsigned long long)std::min<int64_t>(n, int64_t(1) << 20);
+        GMSX_HIP(hipMalloc(&d_giant.p, size_t(giant_cap) * 4));
+        giant = d_giant.as<int32_t>();
+        hipLaunchKernelGGL(k_bk_tasks, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, n, g->off, g->oldid, g->dplus, k_in, v_in, max_c, giant, giant_cap, ctl(0));
+        size_t tmp_bytes = 0;
+        GMSX_HIP(rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, size_t(n), 0, 64, s));
+        GMSX_HIP(hipMalloc(&d_sort_tmp.p, tmp_bytes ? tmp_bytes : 8));
+        GMSX_HIP(rocprim::radix_sort_pairs_desc(d_sort_tmp.p, tmp_bytes, k_in, k_out, v_in, v_out, size_t(n), 0, 64, s));
+        words.reset(new (std::nothrow) unsigned long long[static_cast<size_t>(n)]);
+        if (!words) return GMSX_ERR_NOMEM;
+        unsigned long long head[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        GMSX_HIP(hipMemcpyAsync(words.get(), k_out, size_t(n) * 8, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipMemcpyAsync(head, ctl(0), sizeof(head), hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        n_giant = int64_t(head[1]);    // start vertices beyond the register-resident width: memory-resident search after the rounds
+        giant_slab_w = (head[2] + 3ull) & ~3ull;
+        if (n_giant > int64_t(giant_cap)) return GMSX_ERR_UNSUPPORTED;  // more than a million of them
+        n_wide = int64_t(head[7]);     // tasks with more than 2048 candidates: sorted first (kWideTask), WPL = 2 / 4 / 8 kernels
+        widest = std::min(g->max_dplus, max_c);  // candidates of a start vertex = its d+
+        wpl_wide = widest <= 4096 ? 2 : widest <= 8192 ? 4 : 8;
+        for (int64_t i = 0; i < n_wide; ++i) words[size_t(i)] &= ~kWideTask;
+        GMSX_HIP(hipMemsetAsync(ctl(7), 0, 8, s));  // ([7] held the number of wide tasks until here)
+        while (n_tasks < n && words[size_t(n_tasks)] > 0) ++n_tasks;
+        // tasks beyond an LDS slab: sorted first (the wide ones, > 2048 candidates, at the very front)
+        while (n_glob < n_tasks && (n_glob < n_wide || words[size_t(n_glob)] > (unsigned long long)kLdsSlabWords)) ++n_glob;
+        return GMSX_OK;
+    }
+
+    // ---- record pools of the load balancer, the limits of its arena, the node budgets
+    int make_pools() {
+        size_t total_b = 0;
+        GMSX_HIP(hipMemGetInfo(&free_b, &total_b));
+        budget_bytes = std::min<unsigned long long>(free_b / 4, 16ull << 30);
+        // the arena (Cadj | XT of the start vertices of a chunk + of the LDS-slab searches that split) is sized by NEED once the layout of the
+        // start vertices is known — a fixed 48 GB allocation per call cost seconds of first-touch time now and then
+        arena_hard_cap = std::min<unsigned long long>(free_b / 4, 48ull << 30) / 4;
+        const long long arena_mb = opt_int("BK_ARENA_MB", 0);  // test hook: a small arena makes small graphs build their roots in several chunks
+        if (arena_mb >= 1) arena_hard_cap = std::min<unsigned long long>(arena_hard_cap, ((unsigned long long)arena_mb << 20) / 4);
+        sh.pool_cap = std::min<unsigned long long>(free_b / 16, 2ull << 30) / 4;
+        sh.dir_cap = 8ull << 20;
+        for (int i = 0; i < 2; ++i) {
+            GMSX_HIP(hipMalloc(&d_pool[i].p, sh.pool_cap * 4 + 64));  // + 64: 16-byte loads may run 12 bytes past a record
+            pools[i] = d_pool[i].as<uint32_t>();
+        }
+        for (int i = 0; i < 2; ++i) {
+            GMSX_HIP(hipMalloc(&d_dir[i].p, sh.dir_cap * 8));
+            dirs[i] = d_dir[i].as<unsigned long long>();
+        }
+        sh.arena_head = ctl(3);
+        sh.pool_head = ctl(4);
+        sh.dir_count = ctl(5);
+        sh.max_stack = ctl(6);
+        sh.small_p = int(opt_int("BK_SMALL_P", 6));  // swept on the configs[3] graph: 0 (off) 316 ms, 2 304, 3 ~300, 4 295, 6 293, 8 295, 16 303
+        sh.small_p_groups = int(opt_int("BK_SMALL_P_GROUPS", 12));
+        sh.bmoff = g->bmoff;
+        sh.bmpool = g->bmpool;
+        sh.dense_limit = g->dense_limit;
+        // nodes before a search is re-split.  Round 3 swept 128 … 8192 on the config-4 graph and Kronecker scale 14 and took 512; with round 4's build
+        // pipeline the configs[3] graph takes 248.6 / 209.5 / 203.1 / 200.0 / 204.0 ms at 256 / 512 / 1024 / 2048 / 4096, RMAT 18 ef 64 (a = .45)
+        // 275.9 -> 260.1 ms at 2048, the sparse graphs (one round) are indifferent
+        auto budget_opt = [](const char *name, unsigned dflt) {
+            const long long v = opt_int(name, dflt);
+            return v >= 16 && v <= (1ll << 30) ? unsigned(v) : dflt;
+        };
+        budget_resume = budget_opt("BK_BUDGET", 2048);           // tuning knob: nodes a search may visit before it is re-split
+        sh.budget = budget_opt("BK_BUDGET0", budget_resume);     // round 0 (start vertices: build + first stretch of the search)
+        sh.pool = pools[cur];
+        sh.dir = dirs[cur];
+        GMSX_HIP(hipMemsetAsync(sh.dir, 0xff, sh.dir_cap * 8, s));
+        return GMSX_OK;
+    }
+    int alloc_arena(unsigned long long want_words) {
+        sh.arena_cap = std::min(arena_hard_cap, std::max<unsigned long long>(want_words, (256ull << 20) / 4));
+        GMSX_HIP(hipMalloc(&d_arena.p, sh.arena_cap * 4 + 64));  // + 64: 16-byte loads may run 12 bytes past a row
+        sh.arena = d_arena.as<uint32_t>();
+        return GMSX_OK;
+    }
+
+    // k_bk_layout over `count` start vertices from position `first` of the task order, then the exclusive sums of what it left
+    int lay_out(BkLayout &l, int64_t first, int64_t count, int pieces_mode, bool with_pieces) {
+        if (int rc = l.alloc(count, with_pieces)) return rc;
+        hipLaunchKernelGGL(k_bk_layout, dim3(unsigned(count / 256 + 1)), dim3(256), 0, s, first, count, nparts, part, v_out, g->off, g->oldid, g->dplus, pieces_mode,
+                           l.need_a, l.need_r, l.need_p, maxima());
+        if (int rc = exclusive_scan_i64(l.need_a, l.aoff, count + 1, s)) return rc;
+        if (int rc = exclusive_scan_i64(l.need_r, l.roff, count + 1, s)) return rc;
+        return with_pieces ? exclusive_scan_i64(l.need_p, l.poff, count + 1, s) : GMSX_OK;
+    }
+    // words of a wave's slab area in k_bk_resume4: 4 searches of 16 lanes, 8 of 8 or 16 of 4, whichever class needs most
+    static unsigned long long group_wave_words(unsigned long long w16, unsigned long long w8, unsigned long long w4) {
+        return std::max({4ull * ((w16 + 3ull) & ~3ull), 8ull * ((w8 + 3ull) & ~3ull), 16ull * ((w4 + 3ull) & ~3ull)});
+    }
+
+    // ---- LAYOUT of the start vertices that get their own build kernel (arena and record offsets by prefix sums) and the arena itself: setup like
+    //      the task sort above — allocations of gigabytes now and then stall for a second, they are not part of the kernels' time
+    int layout() {
+        cnt_glob = split_build ? part_count(0, n_glob, nparts, part) : 0;
+        cnt_tiny = part_count(n_glob, n_tasks, nparts, part);
+        tiny_roots = use_groups && split_build >= 2 && cnt_glob > 0 && opt_on("BK_TINY_ROOTS");
+        if (cnt_glob > 0) {
+            GMSX_HIP(hipMalloc(&d_end.p, 8));
+            GMSX_HIP(hipMemsetAsync(maxima(), 0, 40, s));
+            if (int rc = lay_out(lay, 0, cnt_glob, split_build >= 2 ? 1 : 0, true)) return rc;
+            if (split_build >= 2) {  // the work items of k_bk_block
+                int64_t n_pieces = 0;
+                GMSX_HIP(hipMemcpy(&n_pieces, lay.poff + cnt_glob, 8, hipMemcpyDeviceToHost));
+                GMSX_HIP(hipMalloc(&d_pieces.p, size_t(n_pieces + 1) * 8));
+                hipLaunchKernelGGL(k_bk_pieces, dim3(unsigned(cnt_glob / 256 + 1)), dim3(256), 0, s, cnt_glob, lay.poff, d_pieces.as<unsigned long long>());
+            }
+            // GMSX_BK_TINY_ROOTS=1 (off by default): the LDS-slab tasks are BUILT by k_bk_wave<true> and SEARCHED by k_bk_resume4 — they leave Cadj | XT in the arena
+            // and a root record in the pool, at offsets from the same kind of layout scans (their x = in-neighbours only: the wave build compacts them).  Measured
+            // on configs[3]: round 0 62 -> 55 ms (the build alone beside k_bk_block), round 1 32.8 -> 48.8 ms (1.65 M searches of ~33 nodes: a record fetch and a
+            // root pivot each) — 156 against 147.4 ms: their search in LDS, hidden beside the build, is the cheaper place
+            if (tiny_roots && cnt_tiny > 0) {
+                if (int rc = lay_out(tlay, n_glob, cnt_tiny, 0, false)) return rc;
+                GMSX_HIP(hipMemcpy(&tiny_a, tlay.aoff + cnt_tiny, 8, hipMemcpyDeviceToHost));
+                GMSX_HIP(hipMemcpy(&tiny_r, tlay.roff + cnt_tiny, 8, hipMemcpyDeviceToHost));
+            }
+            GMSX_HIP(hipMemcpy(mx, maxima(), sizeof(mx), hipMemcpyDeviceToHost));
+            GMSX_HIP(hipMemcpy(&need_total, lay.aoff + cnt_glob, 8, hipMemcpyDeviceToHost));
+            // the roots may take 3/4 of the arena (below): everything in one chunk when the device allows, + room for the LDS-slab searches that split
+            if (int rc = alloc_arena((unsigned long long)need_total / 3 * 4 + (unsigned long long)tiny_a + (512ull << 20) / 4)) return rc;
+            if (verbose)
+                std::fprintf(stderr, "[gmsx bk] start vertices %lld: %lld built in the arena (%lld words), %lld in LDS slabs\n", (long long)n_tasks, (long long)cnt_glob,
+                             (long long)need_total, (long long)(n_tasks - n_glob));
+            map_words = split_build >= 2 ? 0ull : (mx[1] + 3ull) & ~3ull;
+            build_waves = std::min<int64_t>(cnt_glob, int64_t(cu) * 24);
+            if (map_words > 0) GMSX_HIP(hipMalloc(&d_map.p, size_t(build_waves) * map_words * 4));
+        }
+        // the stack slabs of the resume kernels: for the root round their size is known from the layout
+        const bool any_wide_records = !use_groups || widest > kBkGroupMaxC;  // k_bk_resume has records to search
+        if (cnt_glob > 0 && mx[0] > 0 && any_wide_records) {
+            const unsigned long long slab_bytes = ((mx[0] + 3ull) & ~3ull) * 4ull;
+            if (slab_bytes <= budget_bytes) {
+                const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({cnt_glob, int64_t(cu) * 24, int64_t(budget_bytes / slab_bytes)}));
+                resume_cap = size_t(waves) * slab_bytes;
+                GMSX_HIP(hipMalloc(&d_rslab.p, resume_cap));
+            }
+        }
+        if (cnt_glob > 0 && (mx[2] | mx[3] | mx[4]) != 0 && use_groups) {
+            const unsigned long long slab_bytes = group_wave_words(mx[2], mx[3], mx[4]) * 4ull;
+            if (slab_bytes <= budget_bytes) {
+                const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({(cnt_glob + (tiny_roots ? cnt_tiny : 0) + 3) / 4, int64_t(cu) * kGroupWavesPerCu, int64_t(budget_bytes / slab_bytes)}));
+                group_cap = size_t(waves) * slab_bytes;
+                GMSX_HIP(hipMalloc(&d_gslab.p, group_cap));
+            }
+        }
+        return GMSX_OK;
+    }
+
+    // ---- rounds >= 1: resume the split searches (and search the root records of the build kernels) until no record is left
+    int run_rounds() {
+        while (true) {
+            if (int rc = join_tiny()) return rc;  // (BK_TINY_BESIDE = 2: before the next round reads the counters)
+            unsigned long long rd[6] = {0, 0, 0, 0, 0, 0};  // pool_head, dir_count, max_stack, slab words of a 16- / 8- / 4-lane search
+            GMSX_HIP(hipMemcpyAsync(rd, sh.pool_head, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+            GMSX_HIP(hipStreamSynchronize(s));
+            // a wave whose allocation overshot a capacity kept its search: only fully written records are below the caps
+            const unsigned long long n_rec = std::min(rd[1], sh.dir_cap);
+            if (n_rec == 0) break;
+            const unsigned long long stack_w = (rd[2] + 3ull) & ~3ull, group_w = group_wave_words(rd[3], rd[4], rd[5]);
+            const uint32_t *pool_in = pools[cur];
+            const unsigned long long *dir_in = dirs[cur];
+            cur ^= 1;
+            sh.pool = pools[cur];
+            sh.dir = dirs[cur];
+            GMSX_HIP(hipMemsetAsync(queue(), 0, 8, s));
+            GMSX_HIP(hipMemsetAsync(gqueue(), 0, 24, s));
+            GMSX_HIP(hipMemsetAsync(sh.pool_head, 0, 6 * sizeof(unsigned long long), s));
+            GMSX_HIP(hipMemsetAsync(sh.dir, 0xff, sh.dir_cap * 8, s));
+            // few records left: split sooner so that the idle waves get work (the tail rounds are latency-, not throughput-bound)
+            const int64_t full = int64_t(cu) * 24 * 2;
+            sh.budget = int64_t(n_rec) >= full ? budget_resume : unsigned(std::max<int64_t>(128, int64_t(budget_resume) * int64_t(n_rec) / full));
+            // records per queue ticket (GMSX_BK_RESUME_GRAB, default 1: eight cost 4 ms on configs[3] — the records of a round differ in cost, their queue is not the limit)
+            const unsigned grab = unsigned(std::max<int64_t>(1, std::min<int64_t>(resume_grab, int64_t(n_rec) / (int64_t(cu) * 24 * 16))));
+            const bool tiny_now = tiny_pending;  // the LDS-slab tasks run beside this round's kernels: fork here, launch behind them
+            tiny_pending = false;
+            if (tiny_now) {
+                GMSX_HIP(hipMemsetAsync(ctl(11), 0, 8, s));
+                GMSX_HIP(hipEventRecord(c.ev_fork, s));
+            }
+            if (use_groups && group_w > 0) {  // records with at most 512 candidates: four searches per wave
+                const unsigned long long slab_bytes = group_w * 4ull;
+                if (slab_bytes > budget_bytes) return GMSX_ERR_DEVICE_MEM;
+                const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({int64_t((n_rec + 3) / 4), int64_t(cu) * kGroupWavesPerCu, int64_t(budget_bytes / slab_bytes)}));
+                if (size_t(waves) * slab_bytes > group_cap) {  // grow-only, reused by every round
+                    d_gslab.reset();
+                    group_cap = size_t(waves) * slab_bytes;
+                    GMSX_HIP(hipMalloc(&d_gslab.p, group_cap));
+                }
+                if (verbose)
+                    std::fprintf(stderr, "[gmsx bk] round %d: %llu records (%llu pool words), %lld waves of 4 / 8 / 16 searches, %llu slab words each, budget %u\n", rounds + 1,
+                                 n_rec, rd[0], (long long)waves, group_w, sh.budget);
+                hipLaunchKernelGGL(k_bk_resume4, dim3(unsigned(waves)), dim3(64), 0, s, pool_in, dir_in, n_rec, gqueue(), grab, d_gslab.as<uint32_t>(), group_w,
+                                   (rd[3] + 3ull) & ~3ull, (rd[4] + 3ull) & ~3ull, (rd[5] + 3ull) & ~3ull, acc, sh);
+                ++launches;
+            }
+            if (!use_groups || widest > kBkGroupMaxC) {  // the others (every record with GMSX_BK_GROUPS=0): one search per wave
+                const int min_c = use_groups ? kBkGroupMaxC + 1 : 0;
+                const unsigned long long slab_bytes = std::max<unsigned long long>(stack_w * 4ull, 16);
+                if (slab_bytes > budget_bytes) return GMSX_ERR_DEVICE_MEM;
+                const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({int64_t(n_rec), int64_t(cu) * 24, int64_t(budget_bytes / slab_bytes)}));
+                if (size_t(waves) * slab_bytes > resume_cap) {  // grow-only stack slabs, reused by every round
+                    d_rslab.reset();
+                    resume_cap = size_t(waves) * slab_bytes;
+                    GMSX_HIP(hipMalloc(&d_rslab.p, resume_cap));
+                }
+                if (verbose)
+                    std::fprintf(stderr, "[gmsx bk] round %d: %llu records (%llu pool words), %lld waves, stack %llu words, budget %u\n", rounds + 1, n_rec, rd[0],
+                                 (long long)waves, stack_w, sh.budget);
+                auto resume = [&](auto kern) {
+                    hipLaunchKernelGGL(kern, dim3(unsigned(waves)), dim3(64), 0, s, pool_in, dir_in, n_rec, queue(), grab, d_rslab.as<uint32_t>(), stack_w, acc, sh, min_c);
+                };
+                if (n_wide <= 0) resume(k_bk_resume<1>);
+                else if (wpl_wide == 2) resume(k_bk_resume<2>);  // records of wide tasks may be anywhere in the pool
+                else if (wpl_wide == 4) resume(k_bk_resume<4>);
+                else resume(k_bk_resume<8>);
+                ++launches;
+            }
+            if (tiny_now) {
+                GMSX_HIP(hipStreamWaitEvent(c.side[0], c.ev_fork, 0));
+                launch_wave_lds(c.side[0], queue_tiny(), n_glob, n_tasks);
+                tiny_beside = true;
+            }
+            if (++rounds > 100000) return GMSX_ERR_KERNEL;
+        }
+        return GMSX_OK;
+    }
+
+    // k_bk_wave<true>: a wave builds and searches a start vertex in its LDS slab, tasks [lo, hi) of the order
+    void launch_wave_lds(hipStream_t st, unsigned long long *q, int64_t lo, int64_t hi) {
+        const int64_t waves = std::min<int64_t>(part_count(lo, hi, nparts, part), int64_t(cu) * 16);
+        hipLaunchKernelGGL((k_bk_wave<true, 1>), dim3(unsigned(waves)), dim3(64), 0, st, g->off, g->adj, g->newid, g->oldid, g->hoff, g->hadj, g->toff, g->tadj,
+                           g->dplus, v_out, lo, hi, nparts, part, q, static_cast<uint32_t *>(nullptr), 0ull, acc, sh,
+                           emit ? tlay.aoff : static_cast<const int64_t *>(nullptr), emit ? tlay.roff : static_cast<const int64_t *>(nullptr), emit_abase, emit_rbase, emit_dbase);
+        ++launches;
+    }
+    unsigned long long *queue_tiny() const { return ctl(11); }
+    bool have_side() const { return c.side[0] && c.ev_fork && c.ev_join[0]; }
+    // the LDS-slab tasks: their own queue word; `beside` = on a side stream next to the build kernel that is launched on s right after (the build
+    // streams rows at 8 workgroups per CU, the tiny searches live in LDS: each leaves what the other needs), joined before the rounds
+    int launch_tiny(bool beside) {
+        if (part_count(n_glob, n_tasks, nparts, part) <= 0) return GMSX_OK;
+        GMSX_HIP(hipMemsetAsync(queue_tiny(), 0, 8, s));
         hipStream_t st = s;
-        if (beside && c.side[0] && c.ev_fork && c.ev_join[0]) {
+        if (beside && have_side()) {
             st = c.side[0];
             GMSX_HIP(hipEventRecord(c.ev_fork, s));
             GMSX_HIP(hipStreamWaitEvent(st, c.ev_fork, 0));
         }
-        const int64_t waves = std::min<int64_t>(cnt, int64_t(cu) * 16);
-        hipLaunchKernelGGL((k_bk_wave<true, 1>), dim3(unsigned(waves)), dim3(64), 0, st, g->off, g->adj, g->newid, g->oldid, g->hoff, g->hadj, g->toff, g->tadj,
-                           g->dplus, v_out, lo, hi, nparts, part, tqueue, static_cast<uint32_t *>(nullptr), 0ull, acc, sh,
-                           emit ? t_aoff : static_cast<const int64_t *>(nullptr), emit ? t_roff : static_cast<const int64_t *>(nullptr), emit_abase, emit_rbase, emit_dbase);
-        ++launches;
+        launch_wave_lds(st, queue_tiny(), n_glob, n_tasks);
         tiny_beside = st != s;
         return GMSX_OK;
-    };
-    auto join_tiny = [&]() -> int {  // after the kernel that runs beside it was launched on s
+    }
+    int join_tiny() {  // after the kernel that runs beside it was launched on s
         if (tiny_beside) {
             tiny_beside = false;
             GMSX_HIP(hipEventRecord(c.ev_join[0], c.side[0]));
             GMSX_HIP(hipStreamWaitEvent(s, c.ev_join[0], 0));
         }
         return GMSX_OK;
-    };
-    if (split_build) {
+    }
+
+    // ---- round 0.  Start vertices whose structures fit an LDS slab (<= kLdsSlabWords): one wave builds and searches (k_bk_wave<true>).
+    //      The others: k_bk_block (k_bk_build) writes Cadj | XT into the arena and a root record per start vertex, in chunks that fit the
+    //      arena and the record pool; the resume rounds search them.
+    int built_roots() {
         bool tiny_done = false;
         if (cnt_glob > 0) {
-            unsigned long long *bqueue = acc + kCtl + 10;
+            unsigned long long *bqueue = ctl(10);
+            int64_t *const d_q1 = d_end.as<int64_t>();
             // the roots may take at most 3/4 of the arena and half of the pool: searches of the LDS-slab tasks that split need room too
             const int64_t a_cap = int64_t(sh.arena_cap / 4 * 3), r_cap = int64_t(sh.pool_cap / 2), max_tasks = int64_t(sh.dir_cap / 2);
             for (int64_t q0 = 0; q0 < cnt_glob;) {
-                hipLaunchKernelGGL(k_bk_chunk_end, dim3(1), dim3(1), 0, s, q0, cnt_glob, aoff, roff, a_cap, r_cap, max_tasks, d_end);
+                hipLaunchKernelGGL(k_bk_chunk_end, dim3(1), dim3(1), 0, s, q0, cnt_glob, lay.aoff, lay.roff, a_cap, r_cap, max_tasks, d_q1);
                 int64_t q1 = 0, span[4] = {0, 0, 0, 0};
-                GMSX_HIP(hipMemcpyAsync(&q1, d_end, 8, hipMemcpyDeviceToHost, s));
+                GMSX_HIP(hipMemcpyAsync(&q1, d_q1, 8, hipMemcpyDeviceToHost, s));
                 GMSX_HIP(hipStreamSynchronize(s));
-                GMSX_HIP(hipMemcpy(&span[0], aoff + q0, 8, hipMemcpyDeviceToHost));
-                GMSX_HIP(hipMemcpy(&span[1], aoff + q1, 8, hipMemcpyDeviceToHost));
-                GMSX_HIP(hipMemcpy(&span[2], roff + q0, 8, hipMemcpyDeviceToHost));
-                GMSX_HIP(hipMemcpy(&span[3], roff + q1, 8, hipMemcpyDeviceToHost));
+                GMSX_HIP(hipMemcpy(&span[0], lay.aoff + q0, 8, hipMemcpyDeviceToHost));
+                GMSX_HIP(hipMemcpy(&span[1], lay.aoff + q1, 8, hipMemcpyDeviceToHost));
+                GMSX_HIP(hipMemcpy(&span[2], lay.roff + q0, 8, hipMemcpyDeviceToHost));
+                GMSX_HIP(hipMemcpy(&span[3], lay.roff + q1, 8, hipMemcpyDeviceToHost));
                 if (uint64_t(span[1] - span[0]) > sh.arena_cap || uint64_t(span[3] - span[2]) > sh.pool_cap) return GMSX_ERR_DEVICE_MEM;  // one start vertex beyond the arena
                 // pool_head / dir_count / max_stack as if the roots had been split off by an earlier round; arena_head behind their structures
                 unsigned long long ctl0[6] = {(unsigned long long)(span[3] - span[2]), (unsigned long long)(q1 - q0), mx[0], mx[2], mx[3], mx[4]};
                 unsigned long long ah = (unsigned long long)(span[1] - span[0]);
-                const int tiny_mode = [] { const char *e = opt("BK_TINY_BESIDE"); return e ? std::atoi(e) : 1; }();
                 if (!tiny_done && tiny_roots && cnt_tiny > 0 && tiny_mode != 2 && ah + (unsigned long long)tiny_a + (64ull << 20) / 4 <= sh.arena_cap &&
                     ctl0[0] + (unsigned long long)tiny_r <= sh.pool_cap / 4 * 3 && ctl0[1] + (unsigned long long)cnt_tiny <= sh.dir_cap) {
                     emit = true;  // the LDS-slab tasks' structures and root records go behind this chunk's: round 1 searches both
@@ -2531,39 +2543,23 @@ static int bk_partial(const gmsx_graph *g, int part, int nparts, uint64_t *out, 
                 int64_t pspan[2] = {0, 0};
                 if (split_build >= 2) {  // Cadj | XT of the chunk start empty: the pieces of a start vertex only OR into them
                     GMSX_HIP(hipMemsetAsync(sh.arena, 0, size_t(zero_words) * 4, s));
-                    GMSX_HIP(hipMemcpyAsync(&pspan[0], poff + q0, 8, hipMemcpyDeviceToHost, s));
-                    GMSX_HIP(hipMemcpyAsync(&pspan[1], poff + q1, 8, hipMemcpyDeviceToHost, s));
+                    GMSX_HIP(hipMemcpyAsync(&pspan[0], lay.poff + q0, 8, hipMemcpyDeviceToHost, s));
+                    GMSX_HIP(hipMemcpyAsync(&pspan[1], lay.poff + q1, 8, hipMemcpyDeviceToHost, s));
                 }
                 GMSX_HIP(hipStreamSynchronize(s));  // ctl0 / ah / pspan are stack variables
                 if (!tiny_done) {  // the LDS-slab tasks run beside the first chunk's build; what they split off joins its records
-                    const int beside = [] { const char *e = opt("BK_TINY_BESIDE"); return e ? std::atoi(e) : 1; }();  // 0: one after the other (profiling)
-                    if (beside == 2 && c.side[0] && c.ev_fork && c.ev_join[0] && part_count(n_glob, n_tasks, nparts, part) > 0) {
-                        round_pre = [&]() -> int {
-                            GMSX_HIP(hipMemsetAsync(tqueue, 0, 8, s));
-                            GMSX_HIP(hipEventRecord(c.ev_fork, s));
-                            return GMSX_OK;
-                        };
-                        round_post = [&]() -> int {
-                            const int64_t cnt = part_count(n_glob, n_tasks, nparts, part);
-                            GMSX_HIP(hipStreamWaitEvent(c.side[0], c.ev_fork, 0));
-                            const int64_t waves = std::min<int64_t>(cnt, int64_t(cu) * 16);
-                            hipLaunchKernelGGL((k_bk_wave<true, 1>), dim3(unsigned(waves)), dim3(64), 0, c.side[0], g->off, g->adj, g->newid, g->oldid, g->hoff, g->hadj, g->toff,
-                                               g->tadj, g->dplus, v_out, n_glob, n_tasks, nparts, part, tqueue, static_cast<uint32_t *>(nullptr), 0ull, acc, sh);
-                            ++launches;
-                            tiny_beside = true;
-                            round_join = [&]() -> int { return join_tiny(); };
-                            return GMSX_OK;
-                        };
-                    } else if (int rc = launch_tiny(n_glob, n_tasks, beside != 0)) return rc;
+                    if (tiny_mode == 2 && have_side() && cnt_tiny > 0)
+                        tiny_pending = true;
+                    else if (int rc = launch_tiny(tiny_mode != 0)) return rc;
                     tiny_done = true;
                 }
                 if (split_build >= 2)
                     hipLaunchKernelGGL(k_bk_block, dim3(unsigned(std::min<int64_t>(pspan[1] - pspan[0], int64_t(cu) * 8))), dim3(256), 0, s, g->off, g->adj, g->newid,
-                                       g->oldid, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, v_out, int64_t(0), nparts, part, q0, pieces, pspan[0], pspan[1], aoff, roff,
-                                       bqueue, sh);
+                                       g->oldid, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, v_out, int64_t(0), nparts, part, q0, d_pieces.as<unsigned long long>(), pspan[0],
+                                       pspan[1], lay.aoff, lay.roff, bqueue, sh);
                 else
                     hipLaunchKernelGGL(k_bk_build, dim3(unsigned(std::min<int64_t>(q1 - q0, build_waves))), dim3(64), 0, s, g->off, g->adj, g->newid, g->oldid, g->hoff,
-                                       g->hadj, g->toff, g->tadj, g->dplus, v_out, int64_t(0), nparts, part, q0, q1, aoff, roff, bqueue, map_scratch, map_words, sh);
+                                       g->hadj, g->toff, g->tadj, g->dplus, v_out, int64_t(0), nparts, part, q0, q1, lay.aoff, lay.roff, bqueue, d_map.as<uint32_t>(), map_words, sh);
                 ++launches;
                 if (int rc = join_tiny()) return rc;
                 if (int rc = run_rounds()) return rc;
@@ -2579,10 +2575,15 @@ static int bk_partial(const gmsx_graph *g, int part, int nparts, uint64_t *out, 
         if (!tiny_done) {
             if (!sh.arena)
                 if (int rc = alloc_arena(std::min<unsigned long long>(free_b / 8, 8ull << 30) / 4)) return rc;
-            if (int rc = launch_tiny(n_glob, n_tasks, false)) return rc;
+            if (int rc = launch_tiny(false)) return rc;
             if (int rc = run_rounds()) return rc;
         }
-    } else {
+        return GMSX_OK;
+    }
+
+    // ---- round 0 with GMSX_BK_SPLIT_BUILD=0, round 2's one-kernel bins: every start vertex is built and searched by one wave, the LDS-slab
+    //      tasks in one launch, the others in bins of similar slab width; what splits is searched by the resume rounds
+    int bins() {
         if (int rc = alloc_arena(std::min<unsigned long long>(free_b / 8, 8ull << 30) / 4)) return rc;
         int64_t lo = 0;
         while (lo < n_tasks) {
@@ -2594,136 +2595,127 @@ static int bk_partial(const gmsx_graph *g, int part, int nparts, uint64_t *out, 
             while (hi < bin_end && (lds || words[size_t(hi)] * 4 > top)) ++hi;
             const int64_t cnt = part_count(lo, hi, nparts, part);
             if (cnt > 0) {
-                GMSX_HIP(hipMemsetAsync(queue, 0, 8, s));
+                GMSX_HIP(hipMemsetAsync(queue(), 0, 8, s));
                 if (lds) {
-                    const int64_t waves = std::min<int64_t>(cnt, int64_t(cu) * 16);
-                    hipLaunchKernelGGL((k_bk_wave<true, 1>), dim3(unsigned(waves)), dim3(64), 0, s, g->off, g->adj, g->newid, g->oldid, g->hoff,
-                                       g->hadj, g->toff, g->tadj, g->dplus, v_out, lo, hi, nparts, part, queue,
-                                       static_cast<uint32_t *>(nullptr), 0ull, acc, sh);
+                    launch_wave_lds(s, queue(), lo, hi);
                 } else {
                     const unsigned long long slab_w = (top + 3ull) & ~3ull;  // 16-byte aligned slabs (64-bit map slots)
                     const unsigned long long slab_bytes = slab_w * 4ull;
                     if (slab_bytes > budget_bytes) return GMSX_ERR_DEVICE_MEM;
                     const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({cnt, int64_t(cu) * 16, int64_t(budget_bytes / slab_bytes)}));
-                    uint32_t *slabs = nullptr;
-                    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&slabs), size_t(waves) * slab_bytes));
-                    Guard g_slabs;  // freed on every path out of this bin, error returns included
-                    g_slabs.p = slabs;
-                    if (wide && wpl_wide == 2)
-                        hipLaunchKernelGGL((k_bk_wave<false, 2>), dim3(unsigned(waves)), dim3(64), 0, s, g->off, g->adj, g->newid, g->oldid,
-                                           g->hoff, g->hadj, g->toff, g->tadj, g->dplus, v_out, lo, hi, nparts, part, queue, slabs, slab_w, acc, sh);
-                    else if (wide && wpl_wide == 4)
-                        hipLaunchKernelGGL((k_bk_wave<false, 4>), dim3(unsigned(waves)), dim3(64), 0, s, g->off, g->adj, g->newid, g->oldid,
-                                           g->hoff, g->hadj, g->toff, g->tadj, g->dplus, v_out, lo, hi, nparts, part, queue, slabs, slab_w, acc, sh);
-                    else if (wide)
-                        hipLaunchKernelGGL((k_bk_wave<false, 8>), dim3(unsigned(waves)), dim3(64), 0, s, g->off, g->adj, g->newid, g->oldid,
-                                           g->hoff, g->hadj, g->toff, g->tadj, g->dplus, v_out, lo, hi, nparts, part, queue, slabs, slab_w, acc, sh);
-                    else
-                        hipLaunchKernelGGL((k_bk_wave<false, 1>), dim3(unsigned(waves)), dim3(64), 0, s, g->off, g->adj, g->newid, g->oldid,
-                                           g->hoff, g->hadj, g->toff, g->tadj, g->dplus, v_out, lo, hi, nparts, part, queue, slabs, slab_w, acc, sh);
+                    DevBuf d_slabs;  // freed on every path out of this bin, error returns included
+                    GMSX_HIP(hipMalloc(&d_slabs.p, size_t(waves) * slab_bytes));
+                    auto wave = [&](auto kern) {
+                        hipLaunchKernelGGL(kern, dim3(unsigned(waves)), dim3(64), 0, s, g->off, g->adj, g->newid, g->oldid, g->hoff, g->hadj, g->toff, g->tadj, g->dplus,
+                                           v_out, lo, hi, nparts, part, queue(), d_slabs.as<uint32_t>(), slab_w, acc, sh, static_cast<const int64_t *>(nullptr),
+                                           static_cast<const int64_t *>(nullptr), 0ull, 0ull, 0ull);
+                    };
+                    if (!wide) wave(k_bk_wave<false, 1>);
+                    else if (wpl_wide == 2) wave(k_bk_wave<false, 2>);
+                    else if (wpl_wide == 4) wave(k_bk_wave<false, 4>);
+                    else wave(k_bk_wave<false, 8>);
                     GMSX_HIP(hipStreamSynchronize(s));
+                    ++launches;
                 }
-                ++launches;
             }
             lo = hi;
         }
-        if (int rc = run_rounds()) return rc;
+        return run_rounds();
     }
+
     // ---- start vertices too wide for the register-resident search: one wave each, the whole search in its global slab
-    if (n_giant > 0) {
+    int giant_tail() {
         const int64_t cnt = part_count(0, n_giant, nparts, part);
-        if (cnt > 0) {
-            {   // the list was appended with atomics: sort it, so that every rank shards the same sequence
-                int32_t *sorted = nullptr;
-                GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&sorted), size_t(n_giant) * 4));
-                Guard g_sorted;
-                g_sorted.p = sorted;
-                size_t sort_bytes = 0;
-                GMSX_HIP(rocprim::radix_sort_keys(nullptr, sort_bytes, giant, sorted, size_t(n_giant), 0, 32, s));
-                void *sort_tmp = nullptr;
-                GMSX_HIP(hipMalloc(&sort_tmp, sort_bytes ? sort_bytes : 8));
-                Guard g_st;
-                g_st.p = sort_tmp;
-                GMSX_HIP(rocprim::radix_sort_keys(sort_tmp, sort_bytes, giant, sorted, size_t(n_giant), 0, 32, s));
-                GMSX_HIP(hipMemcpyAsync(giant, sorted, size_t(n_giant) * 4, hipMemcpyDeviceToDevice, s));
+        if (cnt <= 0) return GMSX_OK;
+        {   // the list was appended with atomics: sort it, so that every rank shards the same sequence
+            DevBuf d_sorted, d_tmp;
+            GMSX_HIP(hipMalloc(&d_sorted.p, size_t(n_giant) * 4));
+            int32_t *const sorted = d_sorted.as<int32_t>();
+            size_t sort_bytes = 0;
+            GMSX_HIP(rocprim::radix_sort_keys(nullptr, sort_bytes, giant, sorted, size_t(n_giant), 0, 32, s));
+            GMSX_HIP(hipMalloc(&d_tmp.p, sort_bytes ? sort_bytes : 8));
+            GMSX_HIP(rocprim::radix_sort_keys(d_tmp.p, sort_bytes, giant, sorted, size_t(n_giant), 0, 32, s));
+            GMSX_HIP(hipMemcpyAsync(giant, sorted, size_t(n_giant) * 4, hipMemcpyDeviceToDevice, s));
+            GMSX_HIP(hipStreamSynchronize(s));
+        }
+        const unsigned long long slab_bytes = giant_slab_w * 4ull;
+        if (slab_bytes > budget_bytes) return GMSX_ERR_DEVICE_MEM;
+        const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({cnt, int64_t(cu) * 8, int64_t(budget_bytes / slab_bytes)}));
+        DevBuf d_slabs;
+        GMSX_HIP(hipMalloc(&d_slabs.p, size_t(waves) * slab_bytes));
+        GMSX_HIP(hipMemsetAsync(queue(), 0, 8, s));
+        hipLaunchKernelGGL((k_bk_wave<false, 0>), dim3(unsigned(waves)), dim3(64), 0, s, g->off, g->adj, g->newid, g->oldid, g->hoff, g->hadj,
+                           g->toff, g->tadj, g->dplus, giant, int64_t(0), n_giant, nparts, part, queue(), d_slabs.as<uint32_t>(), giant_slab_w, acc, sh);
+        GMSX_HIP(hipStreamSynchronize(s));
+        ++launches;
+        return GMSX_OK;
+    }
+
+    // ---- the shard's count and the call's statistics
+    int result(uint64_t *out, gmsx_stats *st) {
+        unsigned long long host[kCtl + 32];
+        GMSX_HIP(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        unsigned long long total = 0;
+        for (int i = 0; i < 64; ++i) total += host[i * 16];
+#ifdef GMSX_BK_STATS
+        {
+            unsigned long long nodes = 0, zero = 0;
+            (void)hipMemcpyFromSymbol(&nodes, HIP_SYMBOL(g_bk_nodes), 8);
+            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bk_nodes), &zero, 8);
+            std::fprintf(stderr, "[gmsx bk] search nodes %llu, maximal cliques %llu\n", nodes, total);
+            unsigned long long hist[32], zeros[32] = {};
+            (void)hipMemcpyFromSymbol(hist, HIP_SYMBOL(g_bk_hist), sizeof(hist));
+            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bk_hist), zeros, sizeof(zeros));
+            std::fprintf(stderr, "[gmsx bk] entered nodes by c <= 32/64/128/256/512/1024/2048/more:");
+            for (int i = 0; i < 8; ++i) std::fprintf(stderr, " %llu", hist[i]);
+            std::fprintf(stderr, "\n[gmsx bk] entered nodes by |P| = 0 / 1 / 2-6 / 7-16 / 17-32 / 33-64 / 65-256 / more:");
+            for (int i = 8; i < 16; ++i) std::fprintf(stderr, " %llu", hist[i]);
+            std::fprintf(stderr, "\n[gmsx bk] entered with Xf %llu, one-candidate nodes %llu, branch steps %llu, leaf fast paths %llu, one-candidate children %llu, pushes %llu (Xf words %llu), "
+                         "pivot-scored nodes %llu (sum |P u Xc| %llu), deepest level %llu\n", hist[16], hist[25], hist[17], hist[18], hist[19], hist[20], hist[24], hist[21], hist[22], hist[23]);
+            {
+                unsigned long long gs[20], gz[20] = {};
+                (void)hipMemcpyFromSymbol(gs, HIP_SYMBOL(g_bkg_stat), sizeof(gs));
+                (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bkg_stat), gz, sizeof(gz));
+                std::fprintf(stderr, "[gmsx bk] k_bk_resume4: trips %llu (with a fetch %llu, a memory walk of Xf %llu, pivot scoring %llu); group steps PIVOT %llu PIVOT+BRANCH %llu BRANCH %llu "
+                             "CHILD1 %llu POP %llu, idle group-trips %llu; pushes %llu, of them without a saved level %llu\n",
+                             gs[0], gs[1], gs[2], gs[3], gs[4], gs[5], gs[6], gs[7], gs[8], gs[9], gs[10], gs[11]);
+            }
+            std::fprintf(stderr, "[gmsx bk] Xf checks of the fast paths %llu (%llu words), non-zero words of the pushed child Xf %llu; wave cycles: search %llu, of them Xf loops %llu, pivot scoring %llu\n",
+                         hist[26], hist[27], hist[31], hist[29], hist[28], hist[30]);
+        }
+        for (int b = 0; b < 7; ++b) {
+            unsigned long long nrec = 0, xws = 0;
+            for (int i = 0; i < 64; ++i) { nrec += host[i * 16 + 1 + b]; xws += host[i * 16 + 8 + b]; }
+            std::fprintf(stderr, "[gmsx bk] resumed records with c <= %d: %llu, mean Xf words %.1f\n", b < 6 ? 32 << b : 1 << 30, nrec, nrec ? double(xws) / double(nrec) : 0.0);
+        }
+#endif
+        if (part == 0) total += host[kCtl];  // isolated vertices, counted once
+        *out = total;
+        if (st) {
+            float ms_setup = 0.f, ms = 0.f;
+            GMSX_HIP(hipEventElapsedTime(&ms_setup, c.ev[0], c.ev[1]));
+            GMSX_HIP(hipEventElapsedTime(&ms, c.ev[1], c.ev[2]));
+            // ALGORITHMIC bytes of this formulation (no cache assumed), outside the timed region: the rows the builds walk + Cadj | XT of the start vertices
+            // built in the arena, written once + one Cadj row (cw words) per search-tree node — the operand of the reference's cand.intersect(N(q))
+            unsigned long long node_words = 0;
+            for (int i = 0; i < 64; ++i) node_words += host[i * 16 + 15];
+            unsigned long long build_bytes = 0;
+            if (n_tasks > 0) {
+                GMSX_HIP(hipMemsetAsync(acc + kCtl + 30, 0, 8, s));
+                hipLaunchKernelGGL(k_stat_bk_bytes, dim3(unsigned(cu * 8)), dim3(256), 0, s, n_tasks, nparts, part, v_out, g->off, g->adj, g->newid, g->oldid, g->hoff, g->toff,
+                                   acc + kCtl + 30);
+                GMSX_HIP(hipMemcpyAsync(&build_bytes, acc + kCtl + 30, 8, hipMemcpyDeviceToHost, s));
                 GMSX_HIP(hipStreamSynchronize(s));
             }
-            const unsigned long long slab_bytes = giant_slab_w * 4ull;
-            if (slab_bytes > budget_bytes) return GMSX_ERR_DEVICE_MEM;
-            const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({cnt, int64_t(cu) * 8, int64_t(budget_bytes / slab_bytes)}));
-            uint32_t *slabs = nullptr;
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&slabs), size_t(waves) * slab_bytes));
-            Guard g_slabs;
-            g_slabs.p = slabs;
-            GMSX_HIP(hipMemsetAsync(queue, 0, 8, s));
-            hipLaunchKernelGGL((k_bk_wave<false, 0>), dim3(unsigned(waves)), dim3(64), 0, s, g->off, g->adj, g->newid, g->oldid, g->hoff, g->hadj,
-                               g->toff, g->tadj, g->dplus, giant, int64_t(0), n_giant, nparts, part, queue, slabs, giant_slab_w, acc, sh);
-            GMSX_HIP(hipStreamSynchronize(s));
-            ++launches;
+            const uint64_t alg = uint64_t(build_bytes) + 4ull * uint64_t(need_total) + 4ull * uint64_t(node_words);
+            *st = gmsx_stats{double(ms), double(ms_setup), uint64_t(part_count(0, n, nparts, part)), 0, uint64_t(rounds), launches, 0, alg};
         }
+        return GMSX_OK;
     }
-    GMSX_HIP(hipEventRecord(c.ev[2], s));
-    GMSX_HIP(hipGetLastError());
-    unsigned long long host[kCtl + 32];
-    GMSX_HIP(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipStreamSynchronize(s));
-    unsigned long long total = 0;
-    for (int i = 0; i < 64; ++i) total += host[i * 16];
-#ifdef GMSX_BK_STATS
-    {
-        unsigned long long nodes = 0, zero = 0;
-        (void)hipMemcpyFromSymbol(&nodes, HIP_SYMBOL(g_bk_nodes), 8);
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bk_nodes), &zero, 8);
-        std::fprintf(stderr, "[gmsx bk] search nodes %llu, maximal cliques %llu\n", nodes, total);
-        unsigned long long hist[32], zeros[32] = {};
-        (void)hipMemcpyFromSymbol(hist, HIP_SYMBOL(g_bk_hist), sizeof(hist));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bk_hist), zeros, sizeof(zeros));
-        std::fprintf(stderr, "[gmsx bk] entered nodes by c <= 32/64/128/256/512/1024/2048/more:");
-        for (int i = 0; i < 8; ++i) std::fprintf(stderr, " %llu", hist[i]);
-        std::fprintf(stderr, "\n[gmsx bk] entered nodes by |P| = 0 / 1 / 2-6 / 7-16 / 17-32 / 33-64 / 65-256 / more:");
-        for (int i = 8; i < 16; ++i) std::fprintf(stderr, " %llu", hist[i]);
-        std::fprintf(stderr, "\n[gmsx bk] entered with Xf %llu, one-candidate nodes %llu, branch steps %llu, leaf fast paths %llu, one-candidate children %llu, pushes %llu (Xf words %llu), "
-                     "pivot-scored nodes %llu (sum |P u Xc| %llu), deepest level %llu\n", hist[16], hist[25], hist[17], hist[18], hist[19], hist[20], hist[24], hist[21], hist[22], hist[23]);
-        {
-            unsigned long long gs[20], gz[20] = {};
-            (void)hipMemcpyFromSymbol(gs, HIP_SYMBOL(g_bkg_stat), sizeof(gs));
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bkg_stat), gz, sizeof(gz));
-            std::fprintf(stderr, "[gmsx bk] k_bk_resume4: trips %llu (with a fetch %llu, a memory walk of Xf %llu, pivot scoring %llu); group steps PIVOT %llu PIVOT+BRANCH %llu BRANCH %llu "
-                         "CHILD1 %llu POP %llu, idle group-trips %llu; pushes %llu, of them without a saved level %llu\n",
-                         gs[0], gs[1], gs[2], gs[3], gs[4], gs[5], gs[6], gs[7], gs[8], gs[9], gs[10], gs[11]);
-        }
-        std::fprintf(stderr, "[gmsx bk] Xf checks of the fast paths %llu (%llu words), non-zero words of the pushed child Xf %llu; wave cycles: search %llu, of them Xf loops %llu, pivot scoring %llu\n",
-                     hist[26], hist[27], hist[31], hist[29], hist[28], hist[30]);
-    }
-    for (int b = 0; b < 7; ++b) {
-        unsigned long long nrec = 0, xws = 0;
-        for (int i = 0; i < 64; ++i) { nrec += host[i * 16 + 1 + b]; xws += host[i * 16 + 8 + b]; }
-        std::fprintf(stderr, "[gmsx bk] resumed records with c <= %d: %llu, mean Xf words %.1f\n", b < 6 ? 32 << b : 1 << 30, nrec, nrec ? double(xws) / double(nrec) : 0.0);
-    }
-#endif
-    if (part == 0) total += host[kCtl];  // isolated vertices, counted once
-    *out = total;
-    if (st) {
-        float ms_setup = 0.f, ms = 0.f;
-        GMSX_HIP(hipEventElapsedTime(&ms_setup, c.ev[0], c.ev[1]));
-        GMSX_HIP(hipEventElapsedTime(&ms, c.ev[1], c.ev[2]));
-        // ALGORITHMIC bytes of this formulation (no cache assumed), outside the timed region: the rows the builds walk + Cadj | XT of the start vertices
-        // built in the arena, written once + one Cadj row (cw words) per search-tree node — the operand of the reference's cand.intersect(N(q))
-        unsigned long long node_words = 0;
-        for (int i = 0; i < 64; ++i) node_words += host[i * 16 + 15];
-        unsigned long long build_bytes = 0;
-        if (n_tasks > 0) {
-            GMSX_HIP(hipMemsetAsync(acc + kCtl + 30, 0, 8, s));
-            hipLaunchKernelGGL(k_stat_bk_bytes, dim3(unsigned(cu * 8)), dim3(256), 0, s, n_tasks, nparts, part, v_out, g->off, g->adj, g->newid, g->oldid, g->hoff, g->toff,
-                               acc + kCtl + 30);
-            GMSX_HIP(hipMemcpyAsync(&build_bytes, acc + kCtl + 30, 8, hipMemcpyDeviceToHost, s));
-            GMSX_HIP(hipStreamSynchronize(s));
-        }
-        const uint64_t alg = uint64_t(build_bytes) + 4ull * uint64_t(need_total) + 4ull * uint64_t(node_words);
-        *st = gmsx_stats{double(ms), double(ms_setup), uint64_t(part_count(0, n, nparts, part)), 0, uint64_t(rounds), launches, 0, alg};
-    }
-    return GMSX_OK;
-}
+};
+
+static int bk_partial(const gmsx_graph *g, int part, int nparts, uint64_t *out, gmsx_stats *st) { return BkCall(g, part, nparts).run(out, st); }
 
 }  // namespace gmsx
 
@@ -2734,28 +2726,8 @@ extern "C" {
 int gmsx_bk_partial(const gmsx_graph *g, const int32_t *rank, int part, int nparts, uint64_t *partial, gmsx_stats *stats) {
     return gmsx::guard([&]() -> int {
         if (!g || !partial || nparts < 1 || part < 0 || part >= nparts) return GMSX_ERR_INVALID;
-        // `rank` is what the reference's drivers hand from the preprocessing step to mceBench(graph, ordering).  The number of
-        // maximal cliques does not depend on it and the device splits by its own degree rank, so it is validated
-        // (a permutation of 0..n-1, as every rank-format ordering is) and otherwise not needed.
-        // No exception may cross the C ABI: the scratch bitmap is a nothrow allocation.  Validated on EVERY call (an O(n) pass next to an
-        // enumeration): a memo keyed on the pointer would accept an array that was changed, or another one at the same address.
-        if (rank) {
-            const int64_t n = g->n;
-            const size_t words = size_t((n + 63) / 64 + 1);
-            uint64_t *seen = new (std::nothrow) uint64_t[words]();
-            if (!seen) return GMSX_ERR_NOMEM;
-            bool ok = true;
-            for (int64_t i = 0; i < n && ok; ++i) {
-                const int64_t r = rank[i];
-                if (r < 0 || r >= n) { ok = false; break; }
-                uint64_t &w = seen[size_t(r >> 6)];
-                const uint64_t bit = 1ull << (r & 63);
-                if (w & bit) ok = false;
-                w |= bit;
-            }
-            delete[] seen;
-            if (!ok) return GMSX_ERR_INVALID;
-        }
+        if (rank)  // the count does not depend on it: validated (rank_check.hpp) and otherwise not needed
+            if (int rc = check_rank_permutation(rank, g->n)) return rc;
         if (int rc = ensure_init()) return rc;
         return bk_partial(g, part, nparts, partial, stats);
     });

@@ -14,6 +14,7 @@
 // size histogram and largest clique per call; scan; fill), the launches that fit the arena budget (test hook BK_LIST_ARENA_MB) and the
 // pass-1 cache are the scaffold of two_pass_list.hpp.  Nothing that shapes the search depends on timing (pivot ties by index, DFS order by
 // index), which is what that scheme asks of a kernel.
+#include "rank_check.hpp"
 #include "two_pass_list.hpp"
 
 #include <algorithm>
@@ -448,18 +449,8 @@ int gmsx_bk_list(const gmsx_graph *g, const int32_t *rank, int part, int nparts,
                  int64_t members_capacity, gmsx_bk_list_info *info, gmsx_stats *stats) {
     return gmsx::guard([&]() -> int {
         if (!g || !info || nparts < 1 || part < 0 || part >= nparts || offsets_capacity < 0 || members_capacity < 0) return GMSX_ERR_INVALID;
-        if (rank) {  // validated exactly as gmsx_bk_partial does: a permutation of 0..n-1; the set of maximal cliques does not depend on it
-            const int64_t n = g->n;
-            std::vector<uint64_t> seen(size_t((n + 63) / 64 + 1), 0);
-            for (int64_t i = 0; i < n; ++i) {
-                const int64_t r = rank[i];
-                if (r < 0 || r >= n) return GMSX_ERR_INVALID;
-                uint64_t &w = seen[size_t(r >> 6)];
-                const uint64_t bit = 1ull << (r & 63);
-                if (w & bit) return GMSX_ERR_INVALID;
-                w |= bit;
-            }
-        }
+        if (rank)  // validated as gmsx_bk_partial does; the set of maximal cliques does not depend on it
+            if (int rc = check_rank_permutation(rank, g->n)) return rc;
         if (int rc = ensure_init()) return rc;
         return bk_list(g, part, nparts, offsets, members, offsets_capacity, members_capacity, info, stats);
     });

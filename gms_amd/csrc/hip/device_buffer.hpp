@@ -27,6 +27,11 @@ struct DevBuf {
         p = nullptr;
     }
     template <class T> T *as() const { return static_cast<T *>(p); }
+    template <class T> T *release() {  // hands the allocation to a longer-lived owner (the graph)
+        T *q = as<T>();
+        p = nullptr;
+        return q;
+    }
 };
 
 // `count` elements of T (at least one) into the empty d.  Any failure is GMSX_ERR_DEVICE_MEM and leaves no sticky error behind; a site that

@@ -14,6 +14,7 @@
 //   2. COUNT: recursive set intersection on bit rows: cand' = cand & rows[j] (bitmap AND), popcount at the last
 //      level — the reference's `isect.intersect(N(vi))` recursion with sets as d-bit vectors.  k = 4 on wide matrices
 //      runs wave-cooperatively with one neighbour j per lane (kc4_row), slab matrices band by band through LDS.
+#include "device_buffer.hpp"
 #include "device_graph.hpp"
 #include "kc4_mfma.hpp"
 #if defined(GMSX_KC_NO_TAIL_MEMBERS) && !defined(GMSX_DEV_HOOKS)  // (the A/B switches of device_graph.hpp's list + this round's: development builds only)
@@ -1669,9 +1670,8 @@ static int launch_generic(const gmsx_graph *g, int k, int64_t first, int64_t end
         const long long v = std::atoll(e);
         if (v >= 1) budget_ints = int64_t(v) * (1 << 20) / 4;
     }
-    int32_t *slab = nullptr;
+    DevBuf slab;
     int64_t slab_ints = 0;
-    struct Guard { int32_t *&p; ~Guard() { (void)hipFree(p); } } guard{slab};
     for (int64_t lo = first; lo < end;) {
         const int64_t left = part_count(lo, end, nparts, part);
         if (left <= 0) break;
@@ -1690,14 +1690,13 @@ static int launch_generic(const gmsx_graph *g, int k, int64_t first, int64_t end
         const int64_t need = pivots * blocks_x * per_block;
         if (need > slab_ints) {
             GMSX_HIP(hipStreamSynchronize(s));  // earlier chunks still read the old slab
-            (void)hipFree(slab);
-            slab = nullptr;
+            slab.reset();
             slab_ints = 0;
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&slab), size_t(need) * 4));
+            GMSX_HIP(hipMalloc(&slab.p, size_t(need) * 4));
             slab_ints = need;
         }
         hipLaunchKernelGGL(k_kc_generic, dim3(unsigned(blocks_x), unsigned(pivots)), dim3(256), 0, s, g->hoff, g->hadj, g->toff, g->tadj, g->bmoff,
-                           g->bmpool, g->bitset_limit, g->dense_limit, g->dplus, g->order, lo, hi, nparts, part, k, slab, stride, acc, g->oldid, vcounts);
+                           g->bmpool, g->bitset_limit, g->dense_limit, g->dplus, g->order, lo, hi, nparts, part, k, slab.as<int32_t>(), stride, acc, g->oldid, vcounts);
         ++*launches;
         GMSX_HIP(hipGetLastError());
         lo = hi;
@@ -2093,17 +2092,14 @@ static int ensure_kc_reverse(const gmsx_graph *g, int max_d) {
     GMSX_HIP(hipStreamSynchronize(s));
     if (hub_total <= 0) return GMSX_OK;
     const int32_t H = g->dense_limit;
-    struct Dev { void *p = nullptr; ~Dev() { (void)hipFree(p); } };
-    Dev d_rel, d_rcnt, d_words, d_aoff, d_roff, d_ioff, d_rec, d_item;
-    Dev d_relt, d_rcntt, d_sizes, d_rect, d_itemt;  // tail receivers (option KC_REV_TAIL = 0: none)
-    auto fail = [&](int rc) { return rc; };
-    if (hipMalloc(&d_rel.p, size_t(hub_total) * 4) != hipSuccess || hipMalloc(&d_rcnt.p, size_t(H + 1) * 4 * 2) != hipSuccess ||
-        hipMalloc(&d_words.p, size_t(g->n + 1) * 8) != hipSuccess || hipMalloc(&d_aoff.p, size_t(g->n + 1) * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(GMSX_OK);  // no room for the lists: the forward BUILD needs none
-    }
-    uint32_t *rel = static_cast<uint32_t *>(d_rel.p), *rcnt = static_cast<uint32_t *>(d_rcnt.p), *rcur = rcnt + (H + 1);
-    int64_t *words = static_cast<int64_t *>(d_words.p), *aoff = static_cast<int64_t *>(d_aoff.p);
+    // what leaves this function early is freed; what the graph keeps is handed over at the end (release).  A failed allocation is no error
+    // here: no room for the lists, the forward BUILD needs none
+    DevBuf d_rel, d_rcnt, d_words, d_aoff, d_roff, d_ioff, d_rec, d_item, d_arena;
+    DevBuf d_relt, d_rcntt, d_sizes, d_rect, d_itemt;  // tail receivers (option KC_REV_TAIL = 0: none)
+    if (dalloc<uint32_t>(d_rel, hub_total) || dalloc<uint32_t>(d_rcnt, int64_t(H + 1) * 2) || dalloc<int64_t>(d_words, g->n + 1) || dalloc<int64_t>(d_aoff, g->n + 1))
+        return GMSX_OK;
+    uint32_t *rel = d_rel.as<uint32_t>(), *rcnt = d_rcnt.as<uint32_t>(), *rcur = rcnt + (H + 1);
+    int64_t *words = d_words.as<int64_t>(), *aoff = d_aoff.as<int64_t>();
     GMSX_HIP(hipMemsetAsync(rel, 0xff, size_t(hub_total) * 4, s));
     GMSX_HIP(hipMemsetAsync(rcnt, 0, size_t(H + 1) * 8, s));
     GMSX_HIP(hipMemsetAsync(words, 0, size_t(g->n + 1) * 8, s));
@@ -2117,16 +2113,14 @@ static int ensure_kc_reverse(const gmsx_graph *g, int max_d) {
     KcrTail tl{g->toff, g->tadj, H, int(std::max<long long>(1, opt_int("KC_REV_TAIL_MIN", 256))), nullptr, nullptr, nullptr, nullptr, nullptr, n_piv};
     const bool want_tail = nt > 0 && tail_total > 0 && !(opt("KC_REV_TAIL") && std::atoi(opt("KC_REV_TAIL")) == 0);
     if (want_tail) {
-        if (hipMalloc(&d_relt.p, size_t(tail_total) * 4) == hipSuccess && hipMalloc(&d_rcntt.p, size_t(nt) * 4 * 2) == hipSuccess) {
-            tl.relt = static_cast<uint32_t *>(d_relt.p);
-            tl.rcnt = static_cast<uint32_t *>(d_rcntt.p);
+        if (!dalloc<uint32_t>(d_relt, tail_total) && !dalloc<uint32_t>(d_rcntt, nt * 2)) {  // (no room: the tail members stay forward)
+            tl.relt = d_relt.as<uint32_t>();
+            tl.rcnt = d_rcntt.as<uint32_t>();
             tl.rcur = tl.rcnt + nt;
             GMSX_HIP(hipMemsetAsync(tl.relt, 0xff, size_t(tail_total) * 4, s));
             GMSX_HIP(hipMemsetAsync(tl.rcnt, 0, size_t(nt) * 8, s));
             if (int rc = count_dplus_ge(g, 2, &tl.n_all)) return rc;  // … the tail members of the narrow pivots too (k_kc_small)
             tl.n_all = std::max(tl.n_all, n_piv);
-        } else {
-            (void)hipGetLastError();  // no room: the tail members stay forward
         }
     }
     // (option: 10 x how much cheaper in BYTES the reverse side must be.  Default 1 — handed over unless it moves ten times the bytes — since the matrix-core count:
@@ -2160,11 +2154,8 @@ static int ensure_kc_reverse(const gmsx_graph *g, int max_d) {
     int64_t recs_t = 0, items_t = 0;
     int64_t *rofft = nullptr, *iofft = nullptr;
     if (tl.rcnt) {
-        if (hipMalloc(&d_sizes.p, size_t(nt + 1) * 8 * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return GMSX_OK;
-        }
-        int64_t *sz_r = static_cast<int64_t *>(d_sizes.p), *sz_i = sz_r + (nt + 1);
+        if (dalloc<int64_t>(d_sizes, (nt + 1) * 4)) return GMSX_OK;
+        int64_t *sz_r = d_sizes.as<int64_t>(), *sz_i = sz_r + (nt + 1);
         rofft = sz_i + (nt + 1);
         iofft = rofft + (nt + 1);
         hipLaunchKernelGGL(k_kcr_tail_sizes, dim3(unsigned((nt + 1 + 255) / 256)), dim3(256), 0, s, nt, tl.rcnt, tl.min_edges, sz_r, sz_i);
@@ -2177,44 +2168,32 @@ static int ensure_kc_reverse(const gmsx_graph *g, int max_d) {
         tl.roff = rofft;
     }
     if (recs + recs_t == 0 || arena_words <= 0 || arena_words >= (int64_t(1) << 36)) return GMSX_OK;  // nothing worth handing over (small or flat graphs)
-    if (hipMalloc(&d_roff.p, size_t(H + 1) * 8) != hipSuccess || hipMalloc(&d_ioff.p, size_t(H + 1) * 8) != hipSuccess ||
-        hipMalloc(&d_rec.p, size_t(std::max<int64_t>(recs, 1)) * sizeof(ulonglong2)) != hipSuccess ||
-        hipMalloc(&d_item.p, size_t(std::max<int64_t>(items, 1)) * sizeof(uint4)) != hipSuccess ||
-        hipMalloc(&d_rect.p, size_t(std::max<int64_t>(recs_t, 1)) * 2 * sizeof(ulonglong2)) != hipSuccess ||
-        hipMalloc(&d_itemt.p, size_t(std::max<int64_t>(items_t, 1)) * sizeof(uint4)) != hipSuccess) {
-        (void)hipGetLastError();
+    if (dalloc<int64_t>(d_roff, H + 1) || dalloc<int64_t>(d_ioff, H + 1) || dalloc<ulonglong2>(d_rec, recs) || dalloc<uint4>(d_item, items) ||
+        dalloc<ulonglong2>(d_rect, std::max<int64_t>(recs_t, 1) * 2) || dalloc<uint4>(d_itemt, items_t) || dalloc<uint32_t>(d_arena, arena_words + 16))
         return GMSX_OK;
-    }
-    tl.rec = static_cast<ulonglong2 *>(d_rect.p);
-    uint32_t *arena = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&arena), size_t(arena_words) * 4 + 64) != hipSuccess) {
-        (void)hipGetLastError();
-        return GMSX_OK;
-    }
-    Dev d_arena;
-    d_arena.p = arena;
-    int64_t *roff = static_cast<int64_t *>(d_roff.p), *ioff = static_cast<int64_t *>(d_ioff.p);
+    tl.rec = d_rect.as<ulonglong2>();
+    int64_t *roff = d_roff.as<int64_t>(), *ioff = d_ioff.as<int64_t>();
     GMSX_HIP(hipMemcpyAsync(roff, h_roff.data(), size_t(H + 1) * 8, hipMemcpyHostToDevice, s));
     GMSX_HIP(hipMemcpyAsync(ioff, h_ioff.data(), size_t(H + 1) * 8, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_kcr_edges<2>, dim3(blocks), dim3(256), 0, s, n_piv, g->order, g->hoff, g->hadj, g->dense_limit, min_edges, factor10, rel, rcnt, words, aoff, roff, rcur,
-                       static_cast<ulonglong2 *>(d_rec.p), tl);
-    hipLaunchKernelGGL(k_kcr_items, dim3(unsigned((H + 255) / 256)), dim3(256), 0, s, int64_t(H), roff, ioff, static_cast<uint4 *>(d_item.p), int32_t(0));
+                       d_rec.as<ulonglong2>(), tl);
+    hipLaunchKernelGGL(k_kcr_items, dim3(unsigned((H + 255) / 256)), dim3(256), 0, s, int64_t(H), roff, ioff, d_item.as<uint4>(), int32_t(0));
     if (tl.rcnt && items_t > 0)
-        hipLaunchKernelGGL(k_kcr_items, dim3(unsigned((nt + 255) / 256)), dim3(256), 0, s, nt, rofft, iofft, static_cast<uint4 *>(d_itemt.p), int32_t(H));
+        hipLaunchKernelGGL(k_kcr_items, dim3(unsigned((nt + 255) / 256)), dim3(256), 0, s, nt, rofft, iofft, d_itemt.as<uint4>(), int32_t(H));
     GMSX_HIP(hipGetLastError());
     GMSX_HIP(hipStreamSynchronize(s));
     if (tl.rcnt && recs_t > 0) {
-        g->kc_relt = tl.relt; d_relt.p = nullptr;
-        g->kc_rect = tl.rec; d_rect.p = nullptr;
-        g->kc_itemt = static_cast<uint4 *>(d_itemt.p); d_itemt.p = nullptr;
+        g->kc_relt = d_relt.release<uint32_t>();
+        g->kc_rect = d_rect.release<ulonglong2>();
+        g->kc_itemt = d_itemt.release<uint4>();
         g->kc_recst = recs_t;
         g->kc_itemst = items_t;
     }
-    g->kc_rel = rel; d_rel.p = nullptr;
-    g->kc_aoff = aoff; d_aoff.p = nullptr;
-    g->kc_arena = arena; d_arena.p = nullptr;
-    g->kc_rec = static_cast<ulonglong2 *>(d_rec.p); d_rec.p = nullptr;
-    g->kc_item = static_cast<uint4 *>(d_item.p); d_item.p = nullptr;
+    g->kc_rel = d_rel.release<uint32_t>();
+    g->kc_aoff = d_aoff.release<int64_t>();
+    g->kc_arena = d_arena.release<uint32_t>();
+    g->kc_rec = d_rec.release<ulonglong2>();
+    g->kc_item = d_item.release<uint4>();
     g->kc_recs = recs;
     g->kc_items = items;
     g->kc_arena_words = arena_words;
@@ -2326,7 +2305,7 @@ static bool kc_mfma_enabled() {
 }
 
 template <int LV, bool VTX = false>
-static int launch_all(const gmsx_graph *g, int part, int nparts, unsigned long long *acc, int *launches, uint32_t **slab_out,
+static int launch_all(const gmsx_graph *g, int part, int nparts, unsigned long long *acc, int *launches, DevBuf &slab,
                       unsigned long long *vcounts = nullptr) {
     Ctx &c = ctx();
     hipStream_t s = c.stream;
@@ -2554,9 +2533,8 @@ static int launch_all(const gmsx_graph *g, int part, int nparts, unsigned long l
         if (l_cnt[b] > 0) slab_bytes[b] = size_t(l_blocks[b]) * l_dmax[b] * (l_dmax[b] / 32 + 1) * sizeof(uint32_t);
     }
     if (slab_bytes[0] + slab_bytes[1] + slab_bytes[2] > 0) {
-        uint32_t *slabs = nullptr;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&slabs), std::max({slab_bytes[0], slab_bytes[1], slab_bytes[2]})));  // the launches run back to back
-        *slab_out = slabs;
+        GMSX_HIP(hipMalloc(&slab.p, std::max({slab_bytes[0], slab_bytes[1], slab_bytes[2]})));  // the launches run back to back
+        uint32_t *slabs = slab.as<uint32_t>();
         static bool l_attr[kMaxK + 1] = {false};
         if (!l_attr[VTX ? kMaxK : LV]) {
             GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<LV, 1, true, VTX>), hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
@@ -2714,29 +2692,27 @@ static int kclique_partial(const gmsx_graph *g, int k, int part, int nparts, uin
     if (k <= kMaxK && g->rows_sorted)
         if (int rc0 = ensure_kc_reverse(g, 8192)) return rc0;
     const double setup_ms = rev_was_there ? 0.0 : g->kc_rev_build_ms;
-    unsigned long long *acc = nullptr;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&acc), sizeof(unsigned long long) * kAccSlots * kAccStride));
-    struct Guard { void *p; ~Guard() { (void)hipFree(p); } } guard{acc};
-    uint32_t *slabs = nullptr;
+    DevBuf d_acc, slabs;  // (slabs: the global-slab bins of launch_all, freed when the call is over)
+    GMSX_HIP(hipMalloc(&d_acc.p, sizeof(unsigned long long) * kAccSlots * kAccStride));
+    unsigned long long *acc = d_acc.as<unsigned long long>();
     GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * kAccSlots * kAccStride, s));
     GMSX_HIP(hipEventRecord(c.ev[0], s));
     int launches = 0, rc = GMSX_OK;
     switch (k) {
-        case 3: rc = launch_all<1>(g, part, nparts, acc, &launches, &slabs); break;
-        case 4: rc = launch_all<2>(g, part, nparts, acc, &launches, &slabs); break;
-        case 5: rc = launch_all<3>(g, part, nparts, acc, &launches, &slabs); break;
-        case 6: rc = launch_all<4>(g, part, nparts, acc, &launches, &slabs); break;
-        case 7: rc = launch_all<5>(g, part, nparts, acc, &launches, &slabs); break;
-        case 8: rc = launch_all<6>(g, part, nparts, acc, &launches, &slabs); break;
-        case 9: rc = launch_all<7>(g, part, nparts, acc, &launches, &slabs); break;
-        case 10: rc = launch_all<8>(g, part, nparts, acc, &launches, &slabs); break;
+        case 3: rc = launch_all<1>(g, part, nparts, acc, &launches, slabs); break;
+        case 4: rc = launch_all<2>(g, part, nparts, acc, &launches, slabs); break;
+        case 5: rc = launch_all<3>(g, part, nparts, acc, &launches, slabs); break;
+        case 6: rc = launch_all<4>(g, part, nparts, acc, &launches, slabs); break;
+        case 7: rc = launch_all<5>(g, part, nparts, acc, &launches, slabs); break;
+        case 8: rc = launch_all<6>(g, part, nparts, acc, &launches, slabs); break;
+        case 9: rc = launch_all<7>(g, part, nparts, acc, &launches, slabs); break;
+        case 10: rc = launch_all<8>(g, part, nparts, acc, &launches, slabs); break;
         default: {  // k > kMaxK: every pivot that can head a k-clique (d+ >= k-1) through the generic list recursion
             int64_t n_min = 0;
             rc = g->rows_sorted ? count_dplus_ge(g, k - 1, &n_min) : GMSX_ERR_UNSUPPORTED;
             if (!rc) rc = launch_generic(g, k, 0, n_min, part, nparts, acc, &launches);
         }
     }
-    Guard slab_guard{slabs};
     if (rc) return rc;
     GMSX_HIP(hipEventRecord(c.ev[1], s));
     GMSX_HIP(hipGetLastError());
@@ -2768,17 +2744,15 @@ static int kclique_partial(const gmsx_graph *g, int k, int part, int nparts, uin
 int kclique_vertex_counts(const gmsx_graph *g, unsigned long long *d_counts, gmsx_stats *st) {
     Ctx &c = ctx();
     hipStream_t s = c.stream;
-    unsigned long long *acc = nullptr;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&acc), sizeof(unsigned long long) * kAccSlots * kAccStride));
-    struct Guard { void *p; ~Guard() { (void)hipFree(p); } } guard{acc};
-    uint32_t *slabs = nullptr;
+    DevBuf d_acc, slabs;  // (slabs: the global-slab bins of launch_all, freed when the call is over)
+    GMSX_HIP(hipMalloc(&d_acc.p, sizeof(unsigned long long) * kAccSlots * kAccStride));
+    unsigned long long *acc = d_acc.as<unsigned long long>();
     if (g->rows_sorted)
         if (int rc0 = ensure_kc_reverse(g, 8192)) return rc0;
     GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * kAccSlots * kAccStride, s));
     GMSX_HIP(hipEventRecord(c.ev[0], s));
     int launches = 0;
-    const int rc = launch_all<1, true>(g, 0, 1, acc, &launches, &slabs, d_counts);
-    Guard slab_guard{slabs};
+    const int rc = launch_all<1, true>(g, 0, 1, acc, &launches, slabs, d_counts);
     if (rc) return rc;
     GMSX_HIP(hipEventRecord(c.ev[1], s));
     GMSX_HIP(hipGetLastError());

@@ -18,11 +18,12 @@ csr = capi.HostCSR.generate_rmat(scale, ef, 0.45, 0.22, 0.22)
 g = capi.DeviceGraph.from_csr(csr, flags=capi.UPLOAD_TRUSTED)
 for knobs in (({},) if default_only else ({}, {"BK_SPLIT_BUILD": "1"}, {"BK_SPLIT_BUILD": "0"}, {})):
     capi.set_option("BK_SPLIT_BUILD", knobs.get("BK_SPLIT_BUILD"))
-    ms = []
+    ms, setup = [], []
     for _ in range(3):
         total, st = g.bk_count(stats=True)
         ms.append(round(st["kernel_ms"], 1))
+        setup.append(round(st["setup_ms"], 1))
     gold = GOLD.get("rmat-%d-%d-a45-b22-c22" % (scale, ef), {}).get("bk")
-    print(json.dumps({"graph": [scale, ef], "m": csr.num_edges, "knobs": knobs, "maximal_cliques": total, "golden_ok": (total == gold) if gold else None, "kernel_ms": ms,
+    print(json.dumps({"graph": [scale, ef], "m": csr.num_edges, "knobs": knobs, "maximal_cliques": total, "golden_ok": (total == gold) if gold else None, "kernel_ms": ms, "setup_ms": setup,
                       "rounds": st["probes"], "launches": st["launches"]}), flush=True)
 capi.set_option("BK_SPLIT_BUILD", None)
