@@ -6,6 +6,7 @@ point returns GMSX_ERR_NO_DEVICE without a GPU.
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -40,6 +41,7 @@ SYMBOLS = [
     "gmsx_intersect_count_batch", "gmsx_set_op_batch", "gmsx_vertex_similarity_batch", "gmsx_kclique_count", "gmsx_kclique_partial", "gmsx_kclique_star_count", "gmsx_kclique_star_list", "gmsx_bk_count", "gmsx_bk_partial", "gmsx_bk_list",
     "gmsx_adg_rank", "gmsx_tc_ordering", "gmsx_core_decomposition", "gmsx_degree_rank", "gmsx_order_quality",
     "gmsx_coloring_jp", "gmsx_coloring_verify",
+    "gmsx_edge_support", "gmsx_truss_decomposition",
     "gmsx_link_prediction", "gmsx_link_prediction_precision",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -106,6 +108,14 @@ class ColoringCheck(C.Structure):
 
 
 COLOR_HEURISTICS = ("id", "ff", "lf", "sl", "adg")
+
+
+class TrussInfo(C.Structure):
+    _fields_ = [("max_truss", C.c_int32), ("levels", C.c_int32), ("rounds", C.c_int32), ("max_support", C.c_int32), ("top_edges", C.c_int64),
+                ("triangles", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("max_truss", "levels", "rounds", "max_support", "top_edges", "triangles")}
 
 
 class LinkPredictionInfo(C.Structure):
@@ -213,6 +223,8 @@ def lib():
     L.gmsx_order_quality.argtypes = [vp, C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.POINTER(OrderQualityInfo), sp]
     L.gmsx_coloring_jp.argtypes = [vp, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(ColoringInfo), sp]
     L.gmsx_coloring_verify.argtypes = [vp, C.c_void_p, C.POINTER(ColoringCheck), sp]
+    L.gmsx_edge_support.argtypes = [vp, C.c_void_p, u64p, sp]
+    L.gmsx_truss_decomposition.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(TrussInfo), sp]
     L.gmsx_link_prediction.argtypes = [vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                        C.POINTER(LinkPredictionInfo), sp]
     L.gmsx_link_prediction_precision.argtypes = [vp, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -411,7 +423,9 @@ class DeviceGraph:
         h = C.c_void_p()
         _check(lib().gmsx_graph_upload(off.size - 1, off, neigh if neigh.size else np.zeros(1, np.int32), flags, C.byref(h)),
                "gmsx_graph_upload")
-        return cls(h)
+        g = cls(h)
+        g._host = (weakref.ref(off), weakref.ref(neigh))  # what ktruss_edges(k) filters; weak: the handle keeps no host copy alive
+        return g
 
     @classmethod
     def from_csr(cls, csr, flags=UPLOAD_DEFAULT, shard=None):
@@ -421,7 +435,9 @@ class DeviceGraph:
             _check(lib().gmsx_graph_upload_csr(csr._h, flags, C.byref(h)), "gmsx_graph_upload_csr")
         else:
             _check(lib().gmsx_graph_upload_csr_shard(csr._h, flags, int(shard[0]), int(shard[1]), C.byref(h)), "gmsx_graph_upload_csr_shard")
-        return cls(h)
+        g = cls(h)
+        g._host = (weakref.ref(csr),)
+        return g
 
     num_nodes = property(lambda self: lib().gmsx_graph_num_nodes(self._h))
     num_edges = property(lambda self: lib().gmsx_graph_num_edges(self._h))
@@ -704,6 +720,50 @@ class DeviceGraph:
     def color(self, heuristic, epsilon=0.001):
         """Jones–Plassmann under one of COLOR_HEURISTICS: (coloring int32[n], info dict)."""
         return self.coloring_jp(self.color_order(heuristic, epsilon), rank_format=True)
+
+    def edge_support(self, stats=False):
+        """gmsx_edge_support: (support int32[nnz] — |N(u) ∩ N(v)| per arc of the uploaded CSR, both arcs of an edge alike —, triangles)."""
+        nnz = 2 * self.num_edges
+        sup, tri, st = np.zeros(max(nnz, 1), dtype=np.int32), C.c_uint64(0), Stats()
+        _check(lib().gmsx_edge_support(self._h, sup.ctypes.data_as(C.c_void_p), C.byref(tri), C.byref(st)), "gmsx_edge_support")
+        r = (sup[:nnz], int(tri.value))
+        return (r + (st.as_dict(),)) if stats else r
+
+    def truss_decomposition(self, rounds=False, stats=False):
+        """gmsx_truss_decomposition: (truss int32[nnz] per arc of the uploaded CSR, {max_truss, levels, rounds, max_support, top_edges,
+        triangles}); with rounds=True (truss, round_of, info)."""
+        nnz = 2 * self.num_edges
+        tr = np.zeros(max(nnz, 1), dtype=np.int32)
+        rnd = np.zeros(max(nnz, 1), dtype=np.int32) if rounds else None
+        info, st = TrussInfo(), Stats()
+        _check(lib().gmsx_truss_decomposition(self._h, tr.ctypes.data_as(C.c_void_p), rnd.ctypes.data_as(C.c_void_p) if rounds else None,
+                                              C.byref(info), C.byref(st)), "gmsx_truss_decomposition")
+        r = (tr[:nnz], rnd[:nnz], info.as_dict()) if rounds else (tr[:nnz], info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def _host_csr(self):
+        """(off, neigh) of the CSR this graph was uploaded from, while the caller still holds it (the handle keeps only weak references)"""
+        refs = [r() for r in getattr(self, "_host", ())]
+        if len(refs) == 1 and refs[0] is not None and getattr(refs[0], "_h", None):
+            return refs[0].offsets(), refs[0].neighbors()
+        if len(refs) == 2 and refs[0] is not None and refs[1] is not None:
+            return refs[0], refs[1]
+        raise GmsxError(ERR_INVALID, "ktruss_edges (the uploaded CSR is gone from the host: pass off and neigh)")
+
+    def ktruss_edges(self, k, off=None, neigh=None, truss=None):
+        """The k-truss as an edge list: (u, v) int32 arrays of the u < v edges with truss >= k, in CSR order.  A host-side filter of
+        truss_decomposition (or of `truss`, a per-arc array it returned earlier) over the CSR the graph was uploaded from: the handle keeps no
+        host copy, so ktruss_edges(k) works while the caller still holds that CSR, and off / neigh hand its arrays over otherwise."""
+        if off is None or neigh is None:
+            off, neigh = self._host_csr()
+        off, neigh = np.asarray(off, dtype=np.int64), np.asarray(neigh, dtype=np.int32)
+        if truss is None:
+            truss = self.truss_decomposition()[0]
+        if off.size != self.num_nodes + 1 or neigh.size != truss.size or (off.size and int(off[-1]) != neigh.size):
+            raise GmsxError(ERR_INVALID, "ktruss_edges (off / neigh must be the uploaded CSR)")
+        src = np.repeat(np.arange(off.size - 1, dtype=np.int32), np.diff(off))
+        keep = (src < neigh) & (truss >= int(k))
+        return src[keep], neigh[keep]
 
     def link_prediction(self, metric, q, part=0, nparts=1, stats=False):
         """gmsx_link_prediction: the q best-scoring non-edges under `metric` (a SIM_* value or one of SIM_METRICS' names), worst first:

@@ -27,7 +27,10 @@
 //                    (the order: id = getSimpleIdOrdering, the reference's; ff = n-1-v; lf = gmsx_degree_rank; sl = gmsx_core_decomposition; adg = gmsx_adg_rank(eps)),
 //                    "Trial Time", "Colors" and with -v "Verification" (gmsx_coloring_verify read as GCVerifierMaxColor), then the three averages.  A colouring is
 //                    global: not sharded (--gpus > 1 is refused).
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  truss      the k-truss decomposition on the device (gmsx_truss_decomposition; no reference driver) with the usual trial loop: per trial "Trial Time",
+//                    "Max Truss", "Levels", "Rounds", "Triangles" and with -v "Verification" (the triangles against gmsx_tc_total), after the last trial the
+//                    trussness histogram ("truss k: edges"), then "Average Time".  Single GPU: not sharded (--gpus > 1 is refused).
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -119,7 +122,7 @@ Args parse(int argc, char **argv) {
     if (!a.error && a.file.empty() && a.gen.empty()) a.error = 101;  // cli/cli.h:131-133
     if (!a.error && !a.gen.empty() && a.gen != "kronecker" && a.gen != "uniform") a.error = 100;
     if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
-    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp") && a.gpus > 1) a.error = 100;
+    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss") && a.gpus > 1) a.error = 100;
     if (!a.error && a.kernel == "lp" && lp_metric(a.metric) < 0) a.error = 100;
     if (!a.error && !a.order.empty() && a.kernel != "bk" && a.kernel != "color") a.error = 100;  // only Bron–Kerbosch and the colouring have a preprocessing step
     if (!a.error && !a.order.empty() && a.kernel == "bk" && a.order != "adg" && a.order != "deg" && a.order != "dgr") a.error = 100;
@@ -131,7 +134,7 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
                 "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e]\n", argv0);
 }
@@ -399,12 +402,41 @@ int run_color(const Args &args, const gmsx::HipSetGraph &g) {
     return 0;
 }
 
+// the k-truss decomposition (gmsx::truss_numbers) under the usual trial loop
+int run_truss(const Args &args, const gmsx::HipSetGraph &g) {
+    double total_seconds = 0;
+    Timer t;
+    std::vector<int32_t> truss;
+    gmsx_truss_info info{};
+    for (int64_t it = 0; it < args.trials; ++it) {
+        t.Start();
+        gmsx::truss_numbers(g, truss, &info);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        PrintLabel("Max Truss", std::to_string(info.max_truss));
+        PrintLabel("Levels", std::to_string(info.levels));
+        PrintLabel("Rounds", std::to_string(info.rounds));
+        PrintLabel("Triangles", std::to_string(info.triangles));
+        if (args.verify) PrintLabel("Verification", uint64_t(info.triangles) == uint64_t(gmsx::count_total(g)) ? "PASS" : "FAIL");
+        std::cout << "@@@ truss decomposition" << std::endl;
+    }
+    std::vector<int64_t> hist(size_t(info.max_truss) + 1, 0);
+    for (int64_t u = 0; u < g.num_nodes() && !truss.empty(); ++u)  // (-n 0: no trial has filled truss)
+        for (int64_t j = g.offsets()[u]; j < g.offsets()[u + 1]; ++j)
+            if (u < g.neighbors()[j]) ++hist[size_t(truss[size_t(j)])];
+    for (size_t k = 0; k < hist.size(); ++k)
+        if (hist[k]) std::printf("truss %zu: %lld\n", k, (long long)hist[k]);
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -477,11 +509,11 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color") {
-        const int rc_color = run_color(args, g);
+    if (args.kernel == "color" || args.kernel == "truss") {
+        const int rc_run = args.kernel == "color" ? run_color(args, g) : run_truss(args, g);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);
-        return rc_color;
+        return rc_run;
     }
 
     std::string label;

@@ -780,6 +780,8 @@ Option g_options[] = {
     {"CORE_WG_FRONTIER", "", false},
     // graph colouring (coloring.hip)
     {"COLOR_WG_FRONTIER", "", false},
+    // truss decomposition (truss.hip)
+    {"TRUSS_WG_FRONTIER", "", false},
     // link prediction (linkpred.hip)
     {"LP_LDS_MAXN", "", false}, {"LP_SLAB_MB", "", false},
 };

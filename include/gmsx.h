@@ -147,6 +147,8 @@ int gmsx_set_host_threads(int n);
  *                   tuned value; 0 = every round is a kernel boundary; test hook)
  *   graph colouring        COLOR_WG_FRONTIER (the same for the rounds of gmsx_coloring_jp: largest frontier whose rounds run inside its one-workgroup
  *                   kernel, default 512 — a first guess; 0 = every round is a kernel boundary; test hook)
+ *   truss decomposition    TRUSS_WG_FRONTIER (the same for the rounds of gmsx_truss_decomposition, whose frontier holds edges: default 0 = every
+ *                   round is a kernel boundary, which measured faster than the one-workgroup kernel at every size; test hook)
  *   link prediction        LP_LDS_MAXN (largest n whose per-source bitmaps live in LDS, default and maximum 131072 — a first guess; 0 = every
  *                   bitmap in the workgroup's global slab; test hook), LP_SLAB_MB (budget of the candidates of one chunk: smaller = more chunks;
  *                   test hook) */
@@ -513,6 +515,37 @@ typedef struct {
     int32_t max_degree, reserved;
 } gmsx_coloring_check;
 int gmsx_coloring_verify(const gmsx_graph *g, const int32_t *coloring /* n, host */, gmsx_coloring_check *out /* required */, gmsx_stats *stats);
+
+/* ---- per-edge triangle support and the exact k-truss decomposition: the edge counterpart of gmsx_tc_vertex_count2 and gmsx_core_decomposition.
+ * No reference counterpart (the k-truss is the member of the k-core / k-clique / k-clique-star / k-truss family the reference lists and does not
+ * build); both are one Set::intersect_count per edge, and the peel below is the k-core peel one level up.
+ * SUPPORT.  support(e) of an undirected edge e = {u, v} is |N(u) ∩ N(v)| on the full rows: the number of triangles through e.
+ * THE PEEL.  l = 0, every edge remaining.  While edges remain, l rises to the smallest remaining support; then rounds repeat until none
+ * applies: in one round every remaining edge whose remaining support is <= l leaves at once — its trussness is l + 2, its round the running
+ * round index.  A triangle is destroyed if all three of its edges were remaining at the start of the round and at least one of them leaves;
+ * the remaining support of each of its edges that does not leave in this round drops by one — once per triangle, however many of its edges
+ * leave.  truss(e) is therefore the largest k such that e lies in a subgraph whose every edge is in at least k - 2 triangles of that subgraph
+ * ({e : truss(e) >= k} is the k-truss); every edge has truss >= 2.
+ * Per-arc outputs (nnz, host) are parallel to the uploaded CSR's neigh: entry j belongs to arc j, and the two arcs of an edge carry the same
+ * value.  support, truss, round_of, rounds and levels are facts about the graph: byte-identical in every process and on every run (the arrival
+ * order of the atomics reaches no output).  The caller's arrays are written only after success.
+ * n = 0 or no edge: GMSX_OK, *info zeroed (*triangles = 0).  NULL g, NULL info, or NULL support with nnz > 0: GMSX_ERR_INVALID, nothing written.
+ * m >= 2^31: GMSX_ERR_UNSUPPORTED — edge ids are 32 bits (no test reaches this branch: such a graph does not fit a test).  A CSR that is not
+ * symmetric and loop-free (possible only under GMSX_UPLOAD_TRUSTED), a frontier that would overflow its buffer or a final count != m is reported
+ * as GMSX_ERR_KERNEL; nothing is written out of bounds.  Both calls are single-GPU only, there are no shards (a sharded upload gives the same bytes).
+ * Test hook: option TRUSS_WG_FRONTIER.  gmsx_stats of gmsx_truss_decomposition: kernel_ms (the peel), setup_ms (edge numbering and support),
+ * launches, units = m, probes = rounds; of gmsx_edge_support: kernel_ms (edge numbering and support), launches, units = m. */
+typedef struct {
+    int32_t max_truss;    /* largest trussness; 0 for a graph without edges, 2 for a triangle-free one */
+    int32_t levels;       /* distinct trussness values that occur */
+    int32_t rounds;       /* peel rounds (definition above) */
+    int32_t max_support;
+    int64_t top_edges;    /* undirected edges with truss == max_truss */
+    int64_t triangles;    /* (sum of support over undirected edges) / 3 */
+} gmsx_truss_info;
+int gmsx_edge_support(const gmsx_graph *g, int32_t *support /* nnz, host */, uint64_t *triangles /* may be NULL */, gmsx_stats *stats);
+int gmsx_truss_decomposition(const gmsx_graph *g, int32_t *truss /* nnz, host, or NULL */, int32_t *round_of /* nnz, host, or NULL */,
+                             gmsx_truss_info *info /* required */, gmsx_stats *stats);
 
 /* ---- link prediction: GMS::LinkPrediction::link_prediction_similarity<Metric> (set_based/link_prediction/link_prediction.h:42-101), the q
  * best-scoring NON-edges of the graph under one of the GMSX_SIM_* metrics, and the precision / recall step of the reference's bench_ranking

@@ -29,6 +29,9 @@
 //   gmsx::order_quality(g, order)        -> gmsx_order_quality     (preprocessing/util/core_number_evaluator.h:73-139)
 //   gmsx::coloring(g, order) / coloring(g, "sl") -> gmsx_coloring_jp (non_set_based/coloring/coloring_jones_v3.h:38-68: Jones–Plassmann under a priority)
 //   gmsx::coloring_check(g, coloring)    -> gmsx_coloring_verify   (non_set_based/coloring/coloring_common.h:102-157, 205-209: the verifiers as integers)
+//   gmsx::edge_support(g, out)           -> gmsx_edge_support      (per arc |N(u) ∩ N(v)|: one Set::intersect_count per edge; no reference driver; returns the triangles)
+//   gmsx::truss_numbers(g, out)          -> gmsx_truss_decomposition (the trussness per arc; returns the largest)
+//   gmsx::ktruss_edges(g, k)             -> gmsx_truss_decomposition (the u < v edges of the k-truss, a host-side filter)
 //   gmsx::link_prediction(g, metric, q)  -> gmsx_link_prediction   (set_based/link_prediction/link_prediction.h:42-101; the reference's padding reproduced)
 //   gmsx::link_prediction_precision(g_test, edges) -> gmsx_link_prediction_precision (set_based/link_prediction/evaluation.h:99-124)
 // include/gmsx_gms_glue.hpp holds the explicit specialisations that route the reference's own function names to these
@@ -580,6 +583,41 @@ inline gmsx_order_quality_info order_quality(const HipGraphT<S> &g, const Input 
     detail::check(gmsx_order_quality(g.device(), reinterpret_cast<const int32_t *>(order.data()), rank_format ? 1 : 0, core_number, nullptr, &qi, nullptr),
                   "gmsx_order_quality");
     return qi;
+}
+
+// support[j] = |N(u) ∩ N(v)| of arc j = (u -> v) of the graph's CSR — the triangles through that edge, both arcs of an edge alike (gmsx.h);
+// returns the number of triangles.
+template <class S, class Output>
+inline uint64_t edge_support(const HipGraphT<S> &g, Output &support) {
+    const int64_t nnz = g.num_nodes() ? g.offsets()[g.num_nodes()] : 0;
+    support.resize(size_t(nnz));
+    static_assert(sizeof(*support.data()) == sizeof(int32_t), "supports are int32 vectors");
+    uint64_t triangles = 0;
+    detail::check(gmsx_edge_support(g.device(), reinterpret_cast<int32_t *>(support.data()), &triangles, nullptr), "gmsx_edge_support");
+    return triangles;
+}
+// truss[j] = trussness of the edge of arc j (gmsx.h: the level-synchronous peel; unique for the graph); returns the largest.  `info` (optional)
+// receives levels, rounds, the largest support, the size of the top truss and the triangles.
+template <class S, class Output>
+inline int32_t truss_numbers(const HipGraphT<S> &g, Output &truss, gmsx_truss_info *info = nullptr) {
+    const int64_t nnz = g.num_nodes() ? g.offsets()[g.num_nodes()] : 0;
+    truss.resize(size_t(nnz));
+    static_assert(sizeof(*truss.data()) == sizeof(int32_t), "truss numbers are int32 vectors");
+    gmsx_truss_info ti{};
+    detail::check(gmsx_truss_decomposition(g.device(), reinterpret_cast<int32_t *>(truss.data()), nullptr, &ti, nullptr), "gmsx_truss_decomposition");
+    if (info) *info = ti;
+    return ti.max_truss;
+}
+// The k-truss as an edge list: the u < v edges with trussness >= k, in CSR order.
+template <class S>
+inline std::vector<std::pair<int32_t, int32_t>> ktruss_edges(const HipGraphT<S> &g, int32_t k) {
+    std::vector<int32_t> truss;
+    truss_numbers(g, truss);
+    std::vector<std::pair<int32_t, int32_t>> res;
+    for (int64_t u = 0; u < g.num_nodes(); ++u)
+        for (int64_t j = g.offsets()[u]; j < g.offsets()[u + 1]; ++j)
+            if (u < g.neighbors()[j] && truss[size_t(j)] >= k) res.emplace_back(int32_t(u), int32_t(g.neighbors()[j]));
+    return res;
 }
 
 // JonesV3::graph_coloring_jones(g, coloring, order) (coloring_jones_v3.h:38-68): the colouring (1..info->colors) under `order` — rank format
