@@ -716,6 +716,88 @@ __global__ void k_ledge_fill(int64_t first, int64_t end, const int32_t *__restri
     }
 }
 
+// ---- packed light edges (device_graph.hpp: lpack): the enumeration of k_ledge_count / k_ledge_fill once more, class by class -------------
+// cnt is class-major — cnt[c * nl + p] = edges of class c of the pivot at position first + p — so that ONE exclusive scan gives every
+// (class, pivot) the index of its first block in the whole list: class after class, inside a class pivot after pivot, no atomics.
+__global__ void k_lpack_count(int64_t first, int64_t end, const int32_t *__restrict__ order, const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj,
+                              const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj, const int32_t *__restrict__ tsplit, const int32_t *__restrict__ dplus,
+                              int32_t core, int64_t *__restrict__ cnt) {
+    const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, nl = end - first;
+    if (p >= nl) return;
+    int64_t c[kLightClasses];
+#pragma unroll
+    for (int k = 0; k < kLightClasses; ++k) c[k] = 0;
+    const int32_t u = order[first + p];
+    if (u >= core) {  // (a core pivot's edges are k_tc_core's)
+        const int64_t tb = toff[u];
+        const int tl = int(toff[u + 1] - tb), ah = light_hub_ids(hoff, hadj, u);
+        for (int i = tsplit[u]; i < tl; ++i) {
+            const int32_t v = tadj[tb + i];
+            if (dplus[v] >= kHeavy) continue;
+            const int cls = light_class(ah, i, light_hub_ids(hoff, hadj, v), int(toff[v + 1] - toff[v]));
+#pragma unroll
+            for (int k = 0; k < kLightClasses; ++k) c[k] += cls == k ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kLightClasses; ++k) cnt[int64_t(k) * nl + p] = c[k];
+}
+struct LpackPlan {
+    int64_t class_beg[kLightClasses];  // index of the first block of a class in the whole list (the scan's value at (c, pivot 0))
+    int64_t unit_base[kLightClasses];  // first 16-byte unit of the class in lpack
+};
+// eight 16-bit ids / four 32-bit ids of a row part from position 8 q / 4 q on, the filler behind its end
+__device__ __forceinline__ uint4 lpack_hub_unit(const uint16_t *__restrict__ row, int len, int q) {
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = 8 * q + 2 * j;
+        const uint32_t lo = i < len ? row[i] : 0xFFFFu, hi = i + 1 < len ? row[i + 1] : 0xFFFFu;
+        w[j] = lo | (hi << 16);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ uint4 lpack_tail_unit(const int32_t *__restrict__ row, int len, int q, uint32_t filler) {
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = 4 * q + j < len ? uint32_t(row[4 * q + j]) : filler;
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__global__ void k_lpack_fill(int64_t first, int64_t end, const int32_t *__restrict__ order, const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj,
+                             const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj, const int32_t *__restrict__ tsplit, const int32_t *__restrict__ dplus,
+                             int32_t core, const int64_t *__restrict__ beg, const LpackPlan plan, int nparts, int part, uint4 *__restrict__ lpack) {
+    const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, nl = end - first;
+    if (p >= nl) return;
+    const int32_t u = order[first + p];
+    if (u < core) return;
+    int64_t next[kLightClasses];  // index inside its class of this pivot's next block of that class
+#pragma unroll
+    for (int k = 0; k < kLightClasses; ++k) next[k] = beg[int64_t(k) * nl + p] - plan.class_beg[k];
+    const int64_t hb = hoff[u], tb = toff[u];
+    const int tl = int(toff[u + 1] - tb), ah = light_hub_ids(hoff, hadj, u);
+    for (int i = tsplit[u]; i < tl; ++i) {
+        const int32_t v = tadj[tb + i];
+        if (dplus[v] >= kHeavy) continue;
+        const int64_t hv = hoff[v], tv = toff[v];
+        const int bh = light_hub_ids(hoff, hadj, v), bt = int(toff[v + 1] - tv);
+        const int cls = light_class(ah, i, bh, bt);
+        int64_t k = 0, base = 0;
+#pragma unroll
+        for (int c = 0; c < kLightClasses; ++c)
+            if (cls == c) {
+                k = next[c]++;
+                base = plan.unit_base[c];
+            }
+        if (nparts > 1 && shard_of(k, nparts) != part) continue;  // (every stripe of nparts consecutive blocks has one member per shard: slot k / nparts)
+        const LightShape sh = light_shape(cls);
+        uint4 *blk = lpack + base + (nparts <= 1 ? k : k / nparts) * sh.stride();
+        for (int q = 0; q < sh.ah; ++q) *blk++ = lpack_hub_unit(hadj + hb, ah, q);
+        for (int q = 0; q < sh.at; ++q) *blk++ = lpack_tail_unit(tadj + tb, i, q, 0xFFFFFFFFu);  // the tail ids of u in front of v
+        for (int q = 0; q < sh.bh; ++q) *blk++ = lpack_hub_unit(hadj + hv, bh, q);
+        for (int q = 0; q < sh.bt; ++q) *blk++ = lpack_tail_unit(tadj + tv, bt, q, 0xFFFFFFFEu);
+    }
+}
+
 // ---- task lists of the heavy pivots (device_graph.hpp) -------------------------------------------------------------------------
 // The rule, evaluated once per oriented edge (u,v), u heavy: the edge is handed to v ("reverse") iff v is heavy too and the part of u's
 // rows that v has to stream (cut at v's id) is strictly fewer 16-byte units than what u would stream of v's; otherwise u keeps it.
@@ -934,7 +1016,7 @@ static void free_tc(gmsx_graph *g) {
         p = nullptr;
     };
     drop(g->tsplit); drop(g->srow); drop(g->srow2); drop(g->ksplit); drop(g->spool); drop(g->trow); drop(g->htask.lo); drop(g->htask.hi); drop(g->ttask.lo); drop(g->ttask.hi); drop(g->hitem); drop(g->titem); drop(g->tunits);
-    drop(g->ledge); drop(g->tpool); drop(g->shard_hitem); drop(g->shard_titem); drop(g->core_bits);
+    drop(g->ledge); drop(g->lpack); drop(g->tpool); drop(g->shard_hitem); drop(g->shard_titem); drop(g->core_bits);
     g->tc_core = 0;
     g->shard_idx_part = g->shard_idx_nparts = -1;
     g->device_bytes -= g->tc_bytes;
@@ -942,6 +1024,7 @@ static void free_tc(gmsx_graph *g) {
     g->tc_ready = false;
     g->htask_entries = g->ttask_entries = g->hitems = g->titems = g->inline_hentries = g->inline_tentries = 0;
     g->n_ledge = g->ledge_total = 0;
+    for (int c = 0; c < 8; ++c) g->lpack_base[c] = g->lpack_n[c] = g->lpack_total[c] = 0;
     g->task_reverse = g->inline_units = g->spool_units = g->tpool_units = 0;
     g->stats_part = g->stats_nparts = -1;
 }
@@ -974,6 +1057,7 @@ static void free_graph(gmsx_graph *g) {
     (void)hipFree(g->shard_hitem);
     (void)hipFree(g->shard_titem);
     (void)hipFree(g->ledge);
+    (void)hipFree(g->lpack);
     (void)hipFree(g->core_bits);
     (void)hipFree(g->tpool);
     (void)hipFree(g->dplus);
@@ -1567,7 +1651,47 @@ static int build_tc_sets(gmsx_graph *g) {
     {
         const int64_t nl = n_work - n_heavy;
         g->n_ledge = g->ledge_total = 0;
-        if (nl > 0) {
+        g->light_packed = opt_int("TC_LIGHT_PACKED", 1) != 0;  // 0 (A/B): the 32-byte pointer records and k_tc_light
+        for (int c = 0; c < 8; ++c) g->lpack_base[c] = g->lpack_n[c] = g->lpack_total[c] = 0;
+        if (nl > 0 && g->light_packed) {
+            int64_t *ecnt = nullptr, *ebeg = nullptr;
+            const int64_t cells = int64_t(kLightClasses) * nl;
+            if (int rc = dmalloc(&ecnt, cells + 1, nullptr)) return rc;
+            DevGuard g_ec{ecnt};
+            if (int rc = dmalloc(&ebeg, cells + 1, nullptr)) return rc;
+            DevGuard g_eb{ebeg};
+            GMSX_HIP(hipMemsetAsync(ecnt + cells, 0, sizeof(int64_t), s));
+            hipLaunchKernelGGL(k_lpack_count, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->tsplit, g->dplus,
+                               g->tc_core, ecnt);
+            if (int rc = exclusive_scan_i64(ecnt, ebeg, cells + 1, s)) return rc;
+            const int np = g->shard_nparts > 1 ? g->shard_nparts : 1, pp = g->shard_nparts > 1 ? g->shard_part : 0;
+            LpackPlan plan{};
+            int64_t units = 0;
+            for (int c = 0; c < kLightClasses; ++c) {
+                int64_t b[2] = {0, 0};  // the scan at (c, first pivot) and at (c + 1, first pivot) = behind the class
+                GMSX_HIP(hipMemcpy(&b[0], ebeg + int64_t(c) * nl, sizeof(int64_t), hipMemcpyDeviceToHost));
+                GMSX_HIP(hipMemcpy(&b[1], ebeg + int64_t(c + 1) * nl, sizeof(int64_t), hipMemcpyDeviceToHost));
+                const int64_t total = b[1] - b[0], full = total / np, rem = total % np;  // whole stripes of np blocks + this shard's share of the partial one
+                plan.class_beg[c] = b[0];
+                plan.unit_base[c] = units;
+                g->lpack_total[c] = total;
+                g->lpack_n[c] = np <= 1 ? total : full + (((full & 1) ? np - 1 - pp : pp) < rem ? 1 : 0);
+                g->lpack_base[c] = units;
+                units += g->lpack_n[c] * light_shape(c).stride();
+                g->ledge_total += total;
+                g->n_ledge += g->lpack_n[c];
+            }
+            if (opt("MEM_TRACE"))
+                for (int c = 0; c < kLightClasses; ++c) {
+                    const LightShape k = light_shape(c);
+                    std::fprintf(stderr, "gmsx light class %d (ids <= %d / %d / %d / %d, %d units): %lld blocks\n", c, 8 * k.ah, 4 * k.at, 8 * k.bh, 4 * k.bt, k.stride(),
+                                 (long long)g->lpack_total[c]);
+                }
+            if (int rc = dmalloc(&g->lpack, units + 1, g)) return rc;
+            hipLaunchKernelGGL(k_lpack_fill, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->tsplit, g->dplus,
+                               g->tc_core, ebeg, plan, np, pp, g->lpack);
+            GMSX_HIP(hipStreamSynchronize(s));
+        } else if (nl > 0) {
             int64_t *ecnt = nullptr, *ebeg = nullptr;
             if (int rc = dmalloc(&ecnt, nl + 1, nullptr)) return rc;
             DevGuard g_ec{ecnt};

@@ -137,6 +137,20 @@ struct gmsx_graph {
     // independent.  Edge e of the (deterministic) list belongs to shard shard_of(e, nparts) — the pivots' rule; a sharded upload keeps its own at slot e / nparts.
     uint4 *ledge = nullptr;
     int64_t n_ledge = 0, ledge_total = 0;
+    // PACKED LIGHT EDGES (GMSX_TC_LIGHT_PACKED=1, the default; k_tc_lpack): the same edges in the same order, but every edge as one BLOCK of
+    // whole 16-byte units that holds the ids themselves — u's hub ids, u's tail ids in front of v, v's hub ids, v's tail ids (16-bit / 32-bit
+    // values, the 0xFFFF row padding dropped) — instead of four pointers into hadj / tadj: a gather behind a pointer costs a 128-byte line
+    // for a few dozen bytes of ids, a block is streamed.  Each of the four parts is padded to the capacity its SIZE CLASS gives it (gmsx::LightShape,
+    // chosen from the four lengths alone), so a class is a plain array — block k at lpack + lpack_base[c] + k * stride — and every block of
+    // a class has the same compare shape.  Fillers: 0xFFFF in both hub parts (never an id; u's side is masked by value), 0xFFFFFFFF in u's
+    // tail part, 0xFFFFFFFE in v's (rank ids are < 2^31).  A block carries no header: the fillers make the lengths redundant.  Within a class
+    // the blocks follow the enumeration order of `ledge` (count per pivot and class -> scan -> fill: no atomics); block k of a class belongs
+    // to shard shard_of(k, nparts), a sharded upload keeps its own at slot k / nparts.  With the option on `ledge` is not built.
+    uint4 *lpack = nullptr;
+    int64_t lpack_base[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // first unit of class c
+    int64_t lpack_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // blocks of class c held here
+    int64_t lpack_total[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // … in the whole list (= lpack_n unless this is a sharded upload)
+    bool light_packed = false;
     // CORE (k_tc_core, tc.hip): the oriented edges (u, v) with rank id u < tc_core.  v and all of N+(v) lie below u, so the sum of their
     // intersect_counts is Σ_ij L_ij (L Lᵀ)_ij on the strictly lower-triangular tc_core x tc_core bit matrix L of those rows — a masked bit-GEMM
     // on the matrix cores (kc4_mfma.hpp) instead of streamed rows.  Such an edge has no task entry, no inline copy and no light-edge record.
@@ -272,6 +286,38 @@ __host__ __device__ inline int shard_of(int64_t pos, int nparts) {
 }
 static constexpr int kHeavy = 64;        // d+ from which a pivot runs on the workgroup kernel
 static constexpr int kDeltaIds = 14;  // ids per full 16-byte delta unit  // size of gmsx_graph::acc in u64
+
+// SIZE CLASSES of the packed light edges (gmsx_graph::lpack).  A shape gives the capacity of the four parts of a block in 16-byte units
+// (8 hub ids or 4 tail ids each): u's hub ids, u's tail ids in front of v, v's hub ids, v's tail ids.  The class of an edge is the first
+// shape all four lengths fit; the shapes ascend by stride.  A light vertex has d+ < kHeavy = 64 ids in both parts together, so the last
+// shape (64 ids per part) holds every edge: a block is at most 48 units = 768 bytes.  The five shapes in front of it were chosen on the
+// length histograms of RMAT scale 26 and 24 (profiles/tc_light/README.md: greedily, each the shape that takes most units off both graphs):
+// the far light members' rows are mostly TAIL ids — 24 to 40 of them —, so v's tail capacity is what separates the classes.
+struct LightShape {
+    int ah, at, bh, bt;
+    __host__ __device__ constexpr int stride() const { return ah + at + bh + bt; }
+};
+static constexpr int kLightClasses = 6;
+static_assert(kLightClasses <= 8, "gmsx_graph::lpack_base");
+__host__ __device__ constexpr LightShape light_shape(int c) {
+    return c == 0 ? LightShape{2, 3, 2, 4} : c == 1 ? LightShape{1, 2, 5, 8} : c == 2 ? LightShape{2, 4, 5, 9} : c == 3 ? LightShape{3, 8, 4, 9}
+         : c == 4 ? LightShape{6, 8, 6, 10} : LightShape{8, 16, 8, 16};
+}
+static_assert(kHeavy <= 8 * light_shape(kLightClasses - 1).ah && kHeavy <= 4 * light_shape(kLightClasses - 1).at &&
+              kHeavy <= 8 * light_shape(kLightClasses - 1).bh && kHeavy <= 4 * light_shape(kLightClasses - 1).bt, "the last class must hold every light row");
+static constexpr int kLightMaxUnits = light_shape(kLightClasses - 1).stride();
+__host__ __device__ inline int light_class(int ah, int at, int bh, int bt) {  // lengths in ids (hub lengths without the row padding)
+    for (int c = 0; c < kLightClasses - 1; ++c) {
+        const LightShape k = light_shape(c);
+        if (ah <= 8 * k.ah && at <= 4 * k.at && bh <= 8 * k.bh && bt <= 4 * k.bt) return c;
+    }
+    return kLightClasses - 1;
+}
+// ids of the hub part of v's row without the 0xFFFF row padding (which sorts last)
+__device__ __forceinline__ int light_hub_ids(const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj, int32_t v) {
+    const int64_t b = hoff[v], e = hoff[v + 1];
+    return int(e - b) - ((e > b && hadj[e - 1] == 0xFFFFu) ? 1 : 0);
+}
 
 // words of the bitset container of hub rank id v (covers ids [0, v)), rounded to 16 bytes
 __host__ __device__ inline int64_t bitset_words(int32_t v) { return ((int64_t(v) + 31) / 32 + 3) & ~int64_t(3); }

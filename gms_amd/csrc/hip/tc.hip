@@ -28,7 +28,8 @@
 //   3. every streamed hub id is one LDS word read + bit test (no collisions, no branches); a tail id is one filter-bit test and,
 //      for the few that pass, a table probe; hits are counted per lane, reduced per workgroup, added to one of 64 spread u64
 //      accumulators (one atomic per workgroup);
-//   4. k_tc_light — the edges between two light vertices that no work item covers: one 16-lane group per edge, all-pairs in registers.
+//   4. k_tc_lpack — the edges between two light vertices that no work item covers: one 16-lane group per edge, the ids of both rows streamed
+//      as one packed block per edge, compared by binary search in LDS (GMSX_TC_LIGHT_PACKED=0: k_tc_light, pointer records and all-pairs in registers).
 //   5. k_tc_core (GMSX_TC_CORE; host/tc_core_plan.hpp holds the default and the rule) — the edges whose pivot-side endpoint has a rank id below K: they and everything they can match lie
 //      inside the top K x K corner of the oriented adjacency matrix, where an RMAT graph is dense, so their sum is the masked bit-GEMM
 //      Σ_ij L_ij (L Lᵀ)_ij on the matrix cores (kc4_mfma.hpp: fp4 MFMA, f32 sums of ones, exact).  Those edges have no entry, no inline copy and
@@ -809,7 +810,85 @@ __global__ __launch_bounds__(256) void k_tc_light(const uint16_t *__restrict__ h
 }
 
 // ---------------------------------------------------------------------------------------------
-// THE CORE (device_graph.hpp: core_bits).  One wave per 64 x 64 block (bi >= bj) of the K x K matrix, Kc4mBlock<2>::run as k_kc4_mfma uses it:
+// PACKED LIGHT EDGES (device_graph.hpp: lpack; GMSX_TC_LIGHT_PACKED=1).  The same edges, one 16-lane group per edge, but the ids arrive as
+// the edge's own block — 16-byte loads from class base + index x stride, no pointer, no clamp per part — and the compare is a SEARCH, not
+// all-pairs: the group copies the block as it is into its slice of LDS (one 16-byte write per lane and step), every lane takes the ids of u
+// interleaved (id i in lane i & 15) and runs a branch-free binary search for each over v's part, which the class pads to its capacity:
+// ceil(log2(size)) + 1 dependent LDS reads at about three vector instructions each, independent of how many ids v has.  One launch per class
+// (C), so the four groups of a wave agree on the shape and every loop below has compile-time bounds.  A group lives inside one wave and
+// the LDS queue of a wave is in order: no s_barrier, only compiler fences between the writes and the reads.  The next edge's block is in
+// flight while this one is searched.  Hub ids compare as 16-bit values, tail ids as 32-bit ones; fillers: device_graph.hpp.
+// ---------------------------------------------------------------------------------------------
+// Is `a` in the ascending array b[0 … N)?  The window [pos, pos + len) keeps the first element >= a (or the last element if there is
+// none) and halves until one candidate is left.
+template <int N, class T>
+__device__ __forceinline__ bool lds_has(const T *b, uint32_t a) {
+    uint32_t pos = 0;
+#pragma unroll
+    for (int len = N; len > 1; len -= len / 2) pos += uint32_t(b[pos + len / 2 - 1]) < a ? uint32_t(len / 2) : 0u;
+    return uint32_t(b[pos]) == a;
+}
+__device__ __forceinline__ void wave_lds_fence() {  // LDS written by one lane of the wave is read by another: keep the compiler from reordering
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <int C>
+__global__ __launch_bounds__(256) void k_tc_lpack(const uint4 *__restrict__ blocks, int nparts, int part, int64_t count, unsigned long long *__restrict__ acc) {
+    constexpr LightShape K = light_shape(C);
+    constexpr int S = K.stride(), STEPS = (S + 15) / 16;
+    constexpr int AH = 8 * K.ah, AT = 4 * K.at, BH = 8 * K.bh, BT = 4 * K.bt;  // capacities in ids
+    constexpr int RAH = (AH + 15) / 16, RAT = (AT + 15) / 16;                  // registers of u's ids per lane
+    static_assert(2 * RAH <= STEPS * 16 && K.ah + 4 * RAT <= STEPS * 16, "a lane past the end of a part of u reads inside the group's slice");
+    __shared__ uint4 slab[16 * STEPS * 16];
+    __shared__ unsigned long long red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sub = lane & 15;
+    uint4 *mine = slab + (tid >> 4) * (STEPS * 16);
+    const uint16_t *ah = reinterpret_cast<const uint16_t *>(mine), *bh = reinterpret_cast<const uint16_t *>(mine + K.ah + K.at);
+    const uint32_t *at = reinterpret_cast<const uint32_t *>(mine + K.ah), *bt = reinterpret_cast<const uint32_t *>(mine + K.ah + K.at + K.bh);
+    const int64_t ngroups = int64_t(gridDim.x) * 16, g0 = int64_t(blockIdx.x) * 16 + (tid >> 4);
+    const int64_t trips = (count + ngroups - 1) / ngroups;  // the same for every group; a group without an edge searches block 0 and drops the result
+    struct Units {
+        uint4 u[STEPS];
+    };
+    auto load = [&](int64_t t) -> Units {
+        const int64_t k = g0 + t * ngroups;
+        const int64_t kk = k < count ? k : 0;  // (count > 0 here)
+        const int64_t e = nparts <= 1 ? kk : kk * nparts + ((kk & 1) ? nparts - 1 - part : part);
+        const uint4 *blk = blocks + e * S;
+        Units r;
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) r.u[s] = blk[min(sub + 16 * s, S - 1)];  // (lanes past the block repeat its last unit: nothing reads their slot)
+        return r;
+    };
+    unsigned long long total = 0;
+    if (trips > 0) {
+        Units cur = load(0);
+        for (int64_t t = 0; t < trips; ++t) {
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) mine[16 * s + sub] = cur.u[s];
+            wave_lds_fence();
+            cur = load(t + 1);
+            uint32_t c = 0;
+#pragma unroll
+            for (int r = 0; r < RAH; ++r) {  // (a lane past the part reads what lies behind it and drops the answer)
+                const uint32_t a = ah[sub + 16 * r];
+                c += (lds_has<BH>(bh, a) && a != 0xFFFFu && (16 * (r + 1) <= AH || sub + 16 * r < AH)) ? 1u : 0u;  // 0xFFFF = filler on both sides
+            }
+#pragma unroll
+            for (int r = 0; r < RAT; ++r) {
+                const uint32_t a = (16 * (r + 1) <= AT || sub + 16 * r < AT) ? at[sub + 16 * r] : 0xFFFFFFFFu;
+                c += lds_has<BT>(bt, a) ? 1u : 0u;
+            }
+            wave_lds_fence();
+            total += g0 + t * ngroups < count ? c : 0u;
+        }
+    }
+    block_add(total, red, lane, wave, tid, acc);
+}
+
+// ---------------------------------------------------------------------------------------------
+// THE CORE (device_graph.hpp: core_bits). One wave per 64 x 64 block (bi >= bj) of the K x K matrix, Kc4mBlock<2>::run as k_kc4_mfma uses it:
 // 1 024 threads, four waves per SIMD.  The blocks are dealt out STATICALLY — no ticket, no global atomic — from the cost-descending sequence of
 // host/tc_core_plan.hpp (highest bj first), of which this call's shard takes every nparts-th block.  The shard's blocks are cut into chunks
 // of Q = 16 x (workgroups per XCD) consecutive blocks, one per wave of an XCD; round j hands the chunks 8 j … 8 j + 7 to the eight XCDs
@@ -865,7 +944,7 @@ __global__ __launch_bounds__(1024) void k_tc_core(const uint32_t *__restrict__ b
 __global__ __launch_bounds__(256) void k_tc_stats(const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj,
                                                   const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj,
                                                   const int32_t *__restrict__ dplus, const int32_t *__restrict__ order,
-                                                  const int32_t *__restrict__ tunits, int32_t inline_limit, int inline_first, int32_t core, int64_t end, int nparts, int part,
+                                                  const int32_t *__restrict__ tunits, int32_t inline_limit, int inline_first, int32_t core, int packed, int64_t end, int nparts, int part,
                                                   unsigned long long *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
@@ -894,12 +973,15 @@ __global__ __launch_bounds__(256) void k_tc_stats(const int64_t *__restrict__ ho
         const int hl = int(hoff[u + 1] - hoff[u]);
         if (lane == 0) units += (unsigned long long)du;
         if (du < 2 || u < core) continue;
+        const int ah = packed ? light_hub_ids(hoff, hadj, u) : 0;
         for (int64_t j = toff[u] + lane; j < toff[u + 1]; j += 64) {
             const int32_t v = tadj[j];
             if (v < inline_limit || dplus[v] >= kHeavy) continue;  // handed over: the ids are in v's inline rows, counted with its items
-            // a light edge (k_tc_light): its 32-byte record, both parts of u's row (the tail part up to v) and of v's row
             const unsigned long long hv = (unsigned long long)(hoff[v + 1] - hoff[v]), tv = (unsigned long long)(toff[v + 1] - toff[v]);
-            bytes += 32ull + 2ull * hl + 4ull * (unsigned long long)(j - toff[u]) + 2ull * hv + 4ull * tv;
+            // a light edge, packed (k_tc_lpack): its block, padding included …
+            if (packed) bytes += 16ull * (unsigned long long)light_shape(light_class(ah, int(j - toff[u]), light_hub_ids(hoff, hadj, v), int(tv))).stride();
+            // … or behind pointers (k_tc_light): its 32-byte record, both parts of u's row (the tail part up to v) and of v's row
+            else bytes += 32ull + 2ull * hl + 4ull * (unsigned long long)(j - toff[u]) + 2ull * hv + 4ull * tv;
             probes += hv + tv;  // v's ids, each compared with u's
         }
     }
@@ -953,17 +1035,18 @@ __global__ __launch_bounds__(256) void k_tc_item_stats(const int64_t *__restrict
 //   out[3..4]  tail stream rows named by the entries (32-bit list, 16-bit delta)
 //   out[5]     the entries themselves (6 bytes each)          out[6]  the pivots' own containers (hub part per hub item, tail part per tail item)
 //   out[7]     of out[0] + out[3]: inline rows (ids handed over by light pivots; filled in by the host from the build's figures)
-//   out[8..9]  light edges (k_tc_light): hub / tail parts of the far light members' rows
-//   out[10]    light edges: the 32-byte records + the pivots' own hub / tail parts (once per edge)
+//   out[8..9]  light edges (k_tc_light): hub / tail parts of the far light members' rows; packed (k_tc_lpack): the hub / tail units of the
+//              edges' blocks, both rows and the padding of their class included
+//   out[10]    light edges: the 32-byte records + the pivots' own hub / tail parts (once per edge); packed: 0 (a block has no header)
 //   out[11..14] counts: entries, inline entries, work items, light edges
 //   out[15]    the core (k_tc_core): per 64 x 64 block the fragment bytes of its 2 x 64 rows and its mask words, no reuse assumed (host)
 //   out[16]    K, the rank ids below which an edge belongs to the core (0 = none)
 //   out[17..20] reserved (0)
-__global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict__ hoff, const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj,
+__global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj, const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj,
                                                       const int32_t *__restrict__ dplus, const int32_t *__restrict__ order,
                                                       const TaskList htask, const gmsx_tc_item *__restrict__ hitem, int64_t hitems,
                                                       const TaskList ttask, const gmsx_tc_item *__restrict__ titem, int64_t titems,
-                                                      int32_t inline_limit, int32_t core, int64_t first_light, int64_t end_light,
+                                                      int32_t inline_limit, int32_t core, int packed, int64_t first_light, int64_t end_light,
                                                       unsigned long long *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
@@ -994,13 +1077,20 @@ __global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict_
         if (u < core) continue;
         const int64_t tb0 = toff[u], te = toff[u + 1];
         const unsigned long long hl = (unsigned long long)(hoff[u + 1] - hoff[u]);
+        const int ah = packed ? light_hub_ids(hoff, hadj, u) : 0;
         for (int64_t j = tb0 + lane; j < te; j += 64) {
             const int32_t v = tadj[j];
             if (v < inline_limit || dplus[v] >= kHeavy) continue;
+            c[14] += 1;
+            if (packed) {  // the block of the edge (k_tc_lpack): no record, the hub / tail units of both rows with their padding
+                const LightShape k = light_shape(light_class(ah, int(j - tb0), light_hub_ids(hoff, hadj, v), int(toff[v + 1] - toff[v])));
+                c[8] += 16ull * (unsigned long long)(k.ah + k.bh);
+                c[9] += 16ull * (unsigned long long)(k.at + k.bt);
+                continue;
+            }
             c[8] += 2ull * (unsigned long long)(hoff[v + 1] - hoff[v]);
             c[9] += 4ull * (unsigned long long)(toff[v + 1] - toff[v]);
             c[10] += 32ull + 2ull * hl + 4ull * (unsigned long long)(j - tb0);
-            c[14] += 1;
         }
     }
     for (int k = 0; k < 15; ++k) {
@@ -1235,12 +1325,15 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
     const bool run_light = !only || std::strcmp(only, "light") == 0;
     // the light edges of this call: a full upload holds every edge (shard = shard_of(e, nparts)), a sharded one its own, densely
     const bool strided = nparts > 1 && g->shard_nparts == 1;
-    const int64_t cnt_light = [&]() -> int64_t {
+    auto light_share = [&](int64_t held) -> int64_t {  // of a list of `held` edges (or blocks of one class)
         if (!run_light) return 0;
-        if (!strided) return g->n_ledge;
-        const int64_t full = g->n_ledge / nparts, rem = g->n_ledge % nparts;  // whole stripes + the members of the last, partial one
+        if (!strided) return held;
+        const int64_t full = held / nparts, rem = held % nparts;  // whole stripes + the members of the last, partial one
         return full + (((full & 1) ? nparts - 1 - part : part) < rem ? 1 : 0);
-    }();
+    };
+    int64_t cnt_class[kLightClasses], cnt_light = 0;  // packed light edges (gmsx_graph::lpack): every class is a list of its own
+    for (int k = 0; k < kLightClasses; ++k) cnt_light += cnt_class[k] = g->light_packed ? light_share(g->lpack_n[k]) : 0;
+    if (!g->light_packed) cnt_light = light_share(g->n_ledge);
     // LAUNCH PLAN (round 4).  k_tc_items — one persistent launch over the hub and the tail items — then k_tc_light, both on the launch stream.
     // GMSX_TC_OVERLAP=1 puts k_tc_light on a side stream behind the item kernel (its workgroups need no LDS and start wherever a persistent
     // workgroup has left): measured 72.0-72.4 ms against 71.3-71.6 one after the other at scale 26 — the items kernel is bound by memory and
@@ -1303,7 +1396,22 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
             ++launches;
         }
     }
-    if (cnt_light > 0) {
+    if (g->light_packed) {  // one launch per non-empty class
+        auto launch = [&](auto kernel, int k) {
+            if (cnt_class[k] <= 0) return;
+            const int64_t blocks = std::min<int64_t>((cnt_class[k] + 15) / 16, int64_t(cus) * 8);
+            hipLaunchKernelGGL(kernel, dim3(unsigned(blocks)), dim3(256), 0, side_light ? c.side[1] : s, g->lpack + g->lpack_base[k], strided ? nparts : 1, strided ? part : 0,
+                               cnt_class[k], acc);
+            ++launches;
+        };
+        static_assert(kLightClasses == 6, "one instance per class");
+        launch(k_tc_lpack<0>, 0);
+        launch(k_tc_lpack<1>, 1);
+        launch(k_tc_lpack<2>, 2);
+        launch(k_tc_lpack<3>, 3);
+        launch(k_tc_lpack<4>, 4);
+        launch(k_tc_lpack<5>, 5);
+    } else if (cnt_light > 0) {
         const int64_t blocks = std::min<int64_t>((cnt_light + 15) / 16, int64_t(cus) * 8);
         hipLaunchKernelGGL(k_tc_light, dim3(unsigned(blocks)), dim3(256), 0, side_light ? c.side[1] : s, g->hadj, g->tadj, g->ledge, strided ? nparts : 1,
                            strided ? part : 0, cnt_light, acc);
@@ -1323,7 +1431,7 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
         if (g->n > 0) {
             const int64_t blocks = std::min<int64_t>((g->n + 3) / 4, cap_blocks);
             hipLaunchKernelGGL(k_tc_stats, dim3(unsigned(blocks)), dim3(256), 0, s, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->order,
-                               g->tunits, g->inline_limit, g->inline_first, g->tc_core, g->n, nparts, part, acc + kAccSlots * kAccStride);
+                               g->tunits, g->inline_limit, g->inline_first, g->tc_core, g->light_packed ? 1 : 0, g->n, nparts, part, acc + kAccSlots * kAccStride);
         }
         if (g->hitems > 0)
             hipLaunchKernelGGL(k_tc_item_stats, dim3(unsigned(std::min<int64_t>((g->hitems + 3) / 4, cap_blocks))), dim3(256), 0, s, g->hoff, 2, 0, g->htask, g->hitem,
@@ -1385,8 +1493,8 @@ int gmsx_tc_stream_breakdown(const gmsx_graph *g, uint64_t *out21) {
         struct Guard { void *p; ~Guard() { (void)hipFree(p); } } g1{acc};
         GMSX_HIP(hipMemsetAsync(acc, 0, 21 * 8, s));
         const int cus = ctx().compute_units > 0 ? ctx().compute_units : 256;
-        hipLaunchKernelGGL(k_tc_breakdown, dim3(unsigned(cus * 16)), dim3(256), 0, s, g->hoff, g->toff, g->tadj, g->dplus, g->order, g->htask,
-                           g->hitem, g->hitems, g->ttask, g->titem, g->titems, g->inline_limit, g->tc_core, n_block, n_work, acc);
+        hipLaunchKernelGGL(k_tc_breakdown, dim3(unsigned(cus * 16)), dim3(256), 0, s, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->order, g->htask,
+                           g->hitem, g->hitems, g->ttask, g->titem, g->titems, g->inline_limit, g->tc_core, g->light_packed ? 1 : 0, n_block, n_work, acc);
         GMSX_HIP(hipMemcpyAsync(out21, acc, 21 * 8, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
         GMSX_HIP(hipGetLastError());

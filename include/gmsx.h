@@ -130,7 +130,9 @@ int gmsx_set_host_threads(int n);
  *                   TC_PERSIST, TC_ITEM_WGS (launch shapes), TC_CORE (the dense core, read when the containers are built: the oriented edges
  *                   whose pivot-side endpoint has a rank id below K are counted as one masked bit-GEMM on the matrix cores instead of being
  *                   streamed; -1 = K chosen from the graph, a multiple of 1024 or 0 (the default), 0 = no core, N > 0 = K = N; always clamped
- *                   to min(hub ids, n, 32768))
+ *                   to min(hub ids, n, 32768)), TC_LIGHT_PACKED (read when the containers are built: 1, the default = the edges between two
+ *                   light vertices as packed blocks of ids, streamed and compared by search; 0 = as 32-byte pointer records, gathered and
+ *                   compared all-pairs)
  *   k-clique        KC_MAXD (widest pivot of the bit-matrix kernels), KC_SLAB_MB (budget of the global slabs), KC_STREAMS, KC_PIPE_ALL,
  *                   KC_STREAM_BUILD (BUILD variants), KC_REVERSE (0 = every member row streamed forward: no reverse rows; like KC_REV_* read when the lists of a graph are built, i.e. at its first k-clique call), KC_REV_MIN (edges a hub
  *                   receiver must get to take them, default 64), KC_REV_FACTOR (10 x how much cheaper in bytes the reverse side must be; default 0: every hub edge whose receiver qualifies), KC_REV_GW (8 / 16 lanes per record in the receivers' kernels),
