@@ -12,11 +12,12 @@
 //      bit-matrix  rows[i] = N+(v_i) ∩ N+(u)  (d x d bits, strictly lower triangular; in LDS up to d = 1024, else in a
 //      global slab built through an LDS row stage);
 //   2. COUNT: recursive set intersection on bit rows: cand' = cand & rows[j] (bitmap AND), popcount at the last
-//      level — the reference's `isect.intersect(N(vi))` recursion with sets as d-bit vectors.  k = 4 on wide matrices
-//      runs wave-cooperatively with one neighbour j per lane (kc4_row), slab matrices band by band through LDS.
+//      level — the reference's `isect.intersect(N(vi))` recursion with sets as d-bit vectors.  k = 4 counts an LDS matrix by
+//      pair lists (kc4_count_pairs), a slab matrix band by band through LDS (kc4_row_list), or leaves it to the matrix cores.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
 #include "kc4_mfma.hpp"
+#include "kc_bin_plan.hpp"
 #if defined(GMSX_KC_NO_TAIL_MEMBERS) && !defined(GMSX_DEV_HOOKS)  // (the A/B switches of device_graph.hpp's list + this round's: development builds only)
 #error "A/B switches need -DGMSX_DEV_HOOKS (tools/ab_lib.sh sets it)"
 #endif
@@ -32,6 +33,7 @@ namespace gmsx {
 static constexpr int kAccSlots = 64;
 static constexpr int kAccStride = 16;
 static constexpr int kMaxK = 10;
+static_assert(kKcBitmapWords == kBitmapWords, "kc_bin_plan.hpp sizes the LDS of the kernels below");
 
 // ---- id -> local index map of the wave kernel (open-addressing fallback of its bucket set; keys -1 = empty) ----
 __device__ __forceinline__ uint32_t kc_hash(int32_t w, int shift) { return (uint32_t(w) * 0x9E3779B1u) >> shift; }
@@ -62,10 +64,7 @@ struct KcExport {
 // every word that can hold a column below i, and word j >> 5 of row j exists for the pair loops — at word offset Σ_{t<i} ((t >> 5) + 1).  Half the
 // LDS of the rectangular layout: two 1024-thread workgroups per CU up to d+ = 960, and a matrix in LDS (pair-list count) instead of a global slab
 // (row-band count) up to d+ = 1472.
-__device__ __host__ __forceinline__ uint32_t kc_tri_off(int i) {
-    const int q = i >> 5, r = i & 31;
-    return uint32_t((q + 1) * (16 * q + r));
-}
+__device__ __host__ __forceinline__ uint32_t kc_tri_off(int i) { return kc_tri_words(i); }
 // a finished row of `nwords` words from the arena into the (zeroed) matrix row, by the 16 lanes of a group
 __device__ __forceinline__ void kc_copy_row(const uint32_t *__restrict__ src, int nwords, uint32_t *orow, int sub) {
     for (int t = sub; t < nwords; t += 16) orow[t] = src[t];
@@ -119,9 +118,6 @@ __device__ __forceinline__ kc_u4u kc_load8(const uint16_t *row, int j, int l) {
 // A ring of kKcDepth loads per lane, refilled before the oldest one is probed; the loads are UNCONDITIONAL (an index past the row is
 // clamped to its last pair: in bounds, probed never) so that the waits are counted — under a branch every wait is vmcnt(0) and the
 // group has ONE load in flight: long member rows (the pivots of the big bins have members of d+ up to 3000) were a chain of round trips.
-#ifndef GMSX_KC_STREAM_DEPTH
-#define GMSX_KC_STREAM_DEPTH 2  // steps in flight per lane of the step-stream BUILD (mode 2)
-#endif
 #ifndef GMSX_KC_DEPTH
 #define GMSX_KC_DEPTH 2  // (measured, k = 4 at scale 22 / 24: depth 2 22.6 / 143.4 ms, depth 3 24.9 / 154.5, depth 4 25.1 / 155.2 — the registers of a deeper ring cost a wave per SIMD, and the BUILD waits on its LDS probes, not on the row loads)
 #endif
@@ -376,97 +372,6 @@ __device__ __forceinline__ void kc_build_member(const int64_t *__restrict__ hoff
     }
 }
 
-// ---- the BUILD as ONE STREAM OF STEPS per 16-lane group (round 5; mode 2 of k_kc_block) ---------------------------------------------------
-// Member by member (mode 0) a group pays, per member, the chain member id -> extents -> first units of the row before it streams it; from scale 24 on
-// the oriented containers no longer sit in the Infinity Cache and every link is an HBM round trip: the BUILD of k = 4 at scale 26 moved its 1.6 TB of
-// member rows at 2.1 TB/s.  Here, as in the triangle kernels' StepStream (tc.hip): the extents of up to 256 members are fetched by
-// 256 threads AT ONCE into LDS descriptors, and a group then walks its members' rows as one stream of steps (16 consecutive 16-byte units, one per
-// lane) with D steps in flight per lane ACROSS member boundaries — every load unconditional (a lane without a unit in the step re-reads the row's last
-// unit, a group past its last member the fallback address) so that the waits are counted.  A member's row = its hub part (bitset words or 16-bit list)
-// followed by its tail part (32-bit ids); a step carries its member's index, the probe reads what else it needs from the descriptor.
-struct __attribute__((aligned(16))) KcDesc {
-    unsigned long long ph, pt;  // byte addresses of the hub part (list or bitset container) and of the tail part
-    uint32_t hu, tu;            // 16-byte units of the two parts; bit 31 of hu: the hub part is a bitset container
-    uint32_t hl, tl;            // ids of the list / tail part (the last unit of a part is cut there)
-};
-template <int D>
-struct KcStream {
-    static constexpr int S = D == 1 ? 2 : D;
-    const KcDesc *desc;
-    const char *fallback;
-    int hi, sub, G;
-    int e, units, hu, last, lim, j;
-    const char *ph, *pt;
-    int pending;
-    kc_u4u p[S];
-    int pj[S], pe[S];
-    __device__ __forceinline__ void open_row() {
-        if (e < hi) {
-            const KcDesc d = desc[e];
-            ph = reinterpret_cast<const char *>(d.ph);
-            pt = reinterpret_cast<const char *>(d.pt);
-            hu = int(d.hu & 0x7fffffffu);
-            units = hu + int(d.tu);
-        } else {
-            ph = pt = fallback;
-            hu = units = 0;
-        }
-        last = max(units - 1, 0);
-        lim = units + sub;
-        j = sub;
-    }
-    __device__ __forceinline__ void issue(int k) {
-        const int jj = min(j, last);
-        const char *a = jj < hu ? ph + 16 * size_t(jj) : pt + 16 * size_t(jj - hu);
-        p[k] = *reinterpret_cast<const kc_u4u *>(units > 0 ? a : fallback);
-        pj[k] = j < units ? j : -1;
-        pe[k] = e;
-        pending += e < hi ? 1 : 0;
-        j += 16;
-        if (j >= lim) {  // the member's row is through (uniform per group): the group's next member
-            e += G;
-            open_row();
-        }
-    }
-    __device__ __forceinline__ void start(const KcDesc *d, const void *fb, int n, int tid, int nthreads) {
-        desc = d;
-        fallback = static_cast<const char *>(fb);
-        hi = n;
-        sub = tid & 15;
-        G = nthreads >> 4;
-        e = tid >> 4;
-        pending = 0;
-        open_row();
-#pragma unroll
-        for (int k = 0; k < S - (D == 1 ? 1 : 0); ++k) issue(k);
-    }
-    template <class Probe>
-    __device__ __forceinline__ void run(Probe probe) {
-        if constexpr (D == 1) {
-            while (pending > 0) {
-                pending -= 1;
-                issue(1);
-                if (pj[0] >= 0) probe(p[0], pj[0], pe[0]);
-                if (!(pending > 0)) break;
-                pending -= 1;
-                issue(0);
-                if (pj[1] >= 0) probe(p[1], pj[1], pe[1]);
-            }
-        } else {
-            while (pending > 0) {
-#pragma unroll
-                for (int k = 0; k < D; ++k) {
-                    const kc_u4u pc = p[k];
-                    const int jc = pj[k], ec = pe[k];
-                    pending -= 1;
-                    issue(k);
-                    if (jc >= 0) probe(pc, jc, ec);
-                }
-            }
-        }
-    }
-};
-
 // ---- counting ------------------------------------------------------------------------------------------------
 // Per-lane recursion for local graphs of <= 32 vertices (one 32-bit word per set).  Number of LV-cliques inside cand.
 template <int LV>
@@ -588,70 +493,14 @@ __device__ __forceinline__ uint32_t kc4_and_popc(uint32_t wl, const uint32_t *rj
     return acc + acc1;
 }
 
-// k = 4 count of one matrix row i, wave-cooperative:  Σ_{j ∈ rows[i], j in the band} popc(rows[i] & rows[j]).
-// The lanes take the SET BITS j of row i (64 neighbours per chunk, found through a popcount prefix over the row's
-// words: lane t holds word t), so every lane walks words 0..j>>5 of its own row j — neighbouring lanes have
-// neighbouring j, i.e. the same trip count, and rows[i][q] is a wave-uniform v_readlane (no LDS read).  `band` holds
-// the rows of the vertices j0, j0+1, … (stride BS words, zero above the diagonal) in LDS; only the words [jw0, jw1)
-// of row i (the band's columns) are enumerated.
-template <int WPL>
-__device__ __forceinline__ unsigned long long kc4_row(const uint32_t (&wt)[WPL], const uint32_t *band, int BS, int j0, int jw0, int jw1, int lane) {
-    unsigned long long total = 0;
-#pragma unroll
-    for (int h = 0; h < WPL; ++h) {
-        const int t_me = lane + 64 * h;
-        const uint32_t w = (t_me >= jw0 && t_me < jw1) ? wt[h] : 0u;
-        const int pc = __popc(w);
-        int P = pc;  // inclusive prefix over the lanes
-        for (int sft = 1; sft < 64; sft <<= 1) {
-            const int o = __shfl_up(P, sft);
-            if (lane >= sft) P += o;
-        }
-        const int nb = __builtin_amdgcn_readlane(P, 63);
-        const int ex_me = P - pc;
-        for (int c0 = 0; c0 < nb; c0 += 64) {
-            const bool act = c0 + lane < nb;
-            const int rr = act ? c0 + lane : nb - 1;
-            int L = 0;  // number of lanes whose prefix is <= rr = the lane holding my neighbour's word
-#pragma unroll
-            for (int sft = 32; sft > 0; sft >>= 1)
-                if (__shfl(P, L + sft - 1) <= rr) L += sft;
-            uint32_t word = uint32_t(__shfl(int(w), L));
-            int k = rr - __shfl(ex_me, L);  // k-th set bit of word (0-based)
-            int pos = 0;
-#pragma unroll
-            for (int sft = 16; sft > 0; sft >>= 1) {
-                const int c = __popc((word >> pos) & ((1u << sft) - 1u));
-                if (k >= c) {
-                    k -= c;
-                    pos += sft;
-                }
-            }
-            const int tj = L + 64 * h;
-            const int j = (tj << 5) + pos;
-            const int tmax = __builtin_amdgcn_readlane(tj, min(63, nb - c0 - 1));  // ranks ascend with the lane: the last active lane has the largest word index
-            const uint32_t *rj = band + size_t(j - j0) * BS;
-            uint32_t acc = 0;
-#ifdef GMSX_KC_NO_INNER  // A/B build (wrong counts): the k = 4 count without its AND + popcount loops (what finding the neighbours alone takes)
-            acc = uint32_t(rj[0] & 1u) + uint32_t(tmax);
-#else
-#pragma unroll
-            for (int g = 0; g < WPL; ++g)
-                if (tmax >= 64 * g) acc += kc4_and_popc(wt[g], rj + 64 * g, min(tmax - 64 * g, 63) + 1);
-#endif
-            if (act) total += acc;
-        }
-    }
-    return total;
-}
-
-// … the same sum with the neighbours of the row found WITHOUT the 64-lane shuffle scan, the six-step search and the five-step select (round 5, the
-// slab matrices: 0.16 s of the 0.39 s their bins took at scale 26 were those, 0.12 s the AND + popcount loops): only the band's column words
-// [jw0, jw1) of row i can hold neighbours, so the lanes that hold them write their set bits j - j0 into the wave's LDS list behind a DPP prefix sum,
-// and lane r of a chunk reads entry r.  (Tried and dropped: the lanes on the WORDS of the two rows, the neighbours walked by scalar code — no scan,
-// no list, one ds_read_b32 + v_and + v_bcnt per neighbour: 2.5 times SLOWER, 0.92 s for the slab bins: one LDS round trip per neighbour and wave
-// instead of 64 neighbours in flight.)
-static constexpr int kKcRowList = 256;  // entries of a wave's neighbour list (2 bytes each)
+// k = 4 count of one matrix row i, wave-cooperative:  Σ_{j ∈ rows[i], j in the band} popc(rows[i] & rows[j]).  The lanes take the SET BITS j of row i, 64
+// neighbours per chunk, so every lane walks words 0..j>>5 of its own row j — neighbouring lanes have neighbouring j, i.e. the same trip count, and
+// rows[i][q] is a wave-uniform v_readlane (no LDS read).  `band` holds the rows of the vertices j0, j0+1, … (stride BS words, zero above the diagonal)
+// in LDS.  Only the band's column words [jw0, jw1) of row i (lane t holds word t) can hold neighbours, so the lanes that hold them write their set
+// bits j - j0 into the wave's LDS list (kKcRowList entries) behind a DPP prefix sum, and lane r of a chunk reads entry r — a 64-lane shuffle scan,
+// a six-step search and a five-step select per row instead were 0.16 s of the 0.39 s the slab bins took at scale 26, the AND + popcount loops 0.12 s.
+// (Tried and dropped: the lanes on the WORDS of the two rows, the neighbours walked by scalar code — no scan, no list, one ds_read_b32 + v_and + v_bcnt
+// per neighbour: 2.5 times SLOWER, 0.92 s for the slab bins: one LDS round trip per neighbour and wave instead of 64 neighbours in flight.)
 template <int WPL>
 __device__ __forceinline__ unsigned long long kc4_row_list(const uint32_t (&wt)[WPL], const uint32_t *band, int BS, int j0, int jw0, int jw1, int lane,
                                                            unsigned short *wbuf, int cap) {
@@ -1035,7 +884,7 @@ __global__ __launch_bounds__(256) void k_kc_small(const int64_t *__restrict__ ho
 // LDS layout: LDS variants — static [bm: 2048 u32][pre: 2048 u16][filter: 1024 u32] at LDS address 0, dynamic [rows][col][fwd]; slab variants — static filter,
 // dynamic [bm: 2048 u32] [pre: 2048 u16] [row stage: nwaves*4*W u32]
 // ---------------------------------------------------------------------------------------------
-template <int LV, int WPL, bool GLOBAL_ROWS, bool VTX, int PIPE = GLOBAL_ROWS ? 1 : 0 /* the BUILD: 0 member by member, 1 three-stage member pipeline, 2 step stream */,
+template <int LV, int WPL, bool GLOBAL_ROWS, bool VTX, int PIPE = GLOBAL_ROWS ? 1 : 0 /* the BUILD: 0 member by member, 1 three-stage member pipeline */,
           bool TRI = false /* LDS matrix stored triangularly (kc_tri_off; k = 4 only) */,
           bool EXPORT = false /* BUILD only: the finished matrix leaves for the pool (KcExport), k_kc4_mfma counts it */>
 __global__ __launch_bounds__(1024) void k_kc_block(const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj,
@@ -1058,22 +907,17 @@ __global__ __launch_bounds__(1024) void k_kc_block(const int64_t *__restrict__ h
     __shared__ __attribute__((aligned(16))) uint32_t kc_fixed[kStaticWords];
     uint32_t *fltw = GLOBAL_ROWS ? kc_fixed : kc_fixed + kBitmapWords + kBitmapWords / 2;  // the pivot's tail members, one bit per (id mod 32 x words): kc_tail_find
     const KcFilter flt{fltw, uint32_t(kKcFilterWords - 1)};
-#ifdef GMSX_KC_NO_PAIRS  // A/B build: round 4's k = 4 counts (kc4_row for wide matrices, one lane per matrix word for the others)
-    constexpr bool kc4_pairs_enabled = false;
-#else
-    constexpr bool kc4_pairs_enabled = !GLOBAL_ROWS;
-#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nthreads = int(blockDim.x), nwaves = nthreads >> 6;  // 256 … 1024 threads: big LDS bit-matrices leave one workgroup per CU
     // WS = row stride in words: W for the wave-cooperative recursion (lane = word index), W + 1 for the lane-per-pair
     // k = 4 count (random rows per lane: an odd stride spreads them over the LDS banks)
-    static_assert(!TRI || (LV == 2 && !GLOBAL_ROWS && !VTX && PIPE != 2), "the triangular layout serves the k = 4 count on LDS matrices");
+    static_assert(!TRI || (LV == 2 && !GLOBAL_ROWS && !VTX), "the triangular layout serves the k = 4 count on LDS matrices");
     const size_t mat_words = TRI ? size_t(kc_tri_off(dmax)) : size_t(dmax) * WS;  // words of the LDS matrix of this bin
     static_assert(!EXPORT || (LV == 2 && !VTX && (GLOBAL_ROWS || TRI) && PIPE == 1), "the variants whose k = 4 count can run on the matrix cores");
     constexpr bool kCanExport = EXPORT, exporting = EXPORT;  // (compile-time: the BUILD-only kernels carry none of the count phases' registers)
     uint32_t *rows = GLOBAL_ROWS ? slabs + size_t(blockIdx.x) * size_t(dmax) * size_t(WS) : smem;
     uint32_t *bm = GLOBAL_ROWS ? smem : kc_fixed;
-    // dynamic LDS of the LDS-matrix variants: [rows: mat_words][column counters (VTX)][forward list / step-stream descriptors]
+    // dynamic LDS of the LDS-matrix variants: [rows: mat_words][column counters (VTX)][forward list]
     auto rowp = [&](int i) -> uint32_t * { return TRI ? rows + kc_tri_off(i) : rows + size_t(i) * WS; };
     unsigned short *pre = reinterpret_cast<unsigned short *>(bm + kBitmapWords);
 
@@ -1140,7 +984,7 @@ __global__ __launch_bounds__(1024) void k_kc_block(const int64_t *__restrict__ h
         // EXPORT (the matrix leaves for the pool): rows that lie in the arena never pass through LDS or the stage — they are copied arena -> pool in bulk below
         // (slab variant: here; LDS variant: by the copy-out) — and BOTH variants walk the forward list only.  (With every hub edge handed to its receiver the
         // slab BUILD spent 40 ms at scale 26 copying finished rows four per wave and trip through its stage.)
-        constexpr bool kUseFwd = (!GLOBAL_ROWS && PIPE != 2) || EXPORT;
+        constexpr bool kUseFwd = !GLOBAL_ROWS || EXPORT;
         unsigned short *fwd = GLOBAL_ROWS ? reinterpret_cast<unsigned short *>(reinterpret_cast<uint32_t *>(pre + kBitmapWords) + size_t(nwaves) * 4 * W)  // (slab: behind the stage)
                                           : reinterpret_cast<unsigned short *>(smem + mat_words + (VTX ? dmax : 0));
         int nfwd = d;
@@ -1195,55 +1039,7 @@ __global__ __launch_bounds__(1024) void k_kc_block(const int64_t *__restrict__ h
         {
             const int grp = lane >> 4, sub = lane & 15;
             uint32_t *stage = GLOBAL_ROWS ? reinterpret_cast<uint32_t *>(pre + kBitmapWords) + size_t(wave) * 4 * W : nullptr;
-            if constexpr (PIPE == 2) {
-                // ---- mode 2: descriptors of up to 256 members at a time, then one step stream per group (KcStream above) ----
-                KcDesc *desc = reinterpret_cast<KcDesc *>(smem + size_t(dmax) * WS + (VTX ? dmax : 0));
-                for (int base = 0; base < d; base += 256) {
-                    const int nb = min(256, d - base);
-                    if (tid < nb) {
-                        const int i = base + tid;
-                        const bool is_hub = i < hc;
-                        const int32_t v = is_hub ? int32_t(hub_list[i]) : tail_list[i - hc];
-                        const uint32_t r = relat(i);
-                        const bool skip = r != kKcRelForward || i == 0;  // the row comes from the arena (copied here, by this one thread: the step stream is not the default BUILD) or is empty
-                        if (r != kKcRelForward)
-                            for (int t = 0; t < ((i + 31) >> 5); ++t) rows[size_t(i) * WS + t] = arow[r + t];
-                        const KcExt e = kc_load_ext(hoff, toff, bmoff, dense_limit, skip ? 0 : v);
-                        const bool bs = kc_use_bitset(skip ? 0 : v, is_hub, dense_limit, e.hl);
-                        KcDesc dd;
-                        dd.ph = bs ? reinterpret_cast<unsigned long long>(bmpool + e.bo) : reinterpret_cast<unsigned long long>(hadj + e.hb);
-                        dd.pt = reinterpret_cast<unsigned long long>(tadj + e.tb);
-                        dd.hu = bs ? (uint32_t(bitset_words(v) / 4) | 0x80000000u) : (hc > 0 ? uint32_t((e.hl + 7) / 8) : 0u);
-                        dd.tu = (!is_hub && tc > 0) ? uint32_t((e.tl + 3) / 4) : 0u;
-                        if (skip) dd.hu = dd.tu = 0u;
-                        dd.hl = uint32_t(e.hl);
-                        dd.tl = uint32_t(e.tl);
-                        desc[tid] = dd;
-                    }
-                    __syncthreads();
-                    KcStream<GMSX_KC_STREAM_DEPTH> st;
-                    st.start(desc, hadj, nb, tid, nthreads);
-                    st.run([&](kc_u4u pu, int ju, int eu) {
-                        const KcDesc dd = desc[eu];
-                        uint32_t *orow = rows + size_t(base + eu) * WS;
-                        const int hu = int(dd.hu & 0x7fffffffu);
-                        if (ju < hu) {
-                            if (dd.hu & 0x80000000u) kc_and4(make_uint4(pu.x, pu.y, pu.z, pu.w), *reinterpret_cast<const uint4 *>(bm + 4 * ju), 4 * ju, pre, orow);
-                            else kc_probe8(bm, pre, orow, kc_cut8(pu, int(dd.hl) - 8 * ju));
-                        } else {
-                            const int t0 = 4 * (ju - hu), nt = int(dd.tl) - t0;  // 1 … 4 ids of this unit are the row's
-                            const int32_t ids[4] = {int32_t(pu.x), int32_t(pu.y), int32_t(pu.z), int32_t(pu.w)};
-#pragma unroll
-                            for (int q4 = 0; q4 < 4; ++q4)
-                                if (q4 < nt) {
-                                    const int t = kc_tail_find(flt, tail_list, tc, ids[q4]);
-                                    if (t >= 0) atomicOr(&orow[(hc + t) >> 5], 1u << ((hc + t) & 31));
-                                }
-                        }
-                    });
-                    __syncthreads();  // the descriptors are rewritten by the next batch
-                }
-            } else if constexpr (PIPE == 1) {
+            if constexpr (PIPE == 1) {
                 const int istep = nwaves * 4;
                 // member i of the pivot: its rank id (an index past the row: vertex 0 — loaded, never used)
                 auto member = [&](int i) -> int32_t { return i < hc ? int32_t(hub_list[i]) : tail_list[i < d ? i - hc : 0]; };
@@ -1453,11 +1249,7 @@ __global__ __launch_bounds__(1024) void k_kc_block(const int64_t *__restrict__ h
                         cnt += any;
                         continue;
 #endif
-#ifdef GMSX_KC_SLAB_ROW_SCAN  // A/B build: rounds 1-4's neighbour search (shuffle scan + binary search + select)
-                        cnt += kc4_row<WPL>(wt, band, BS, j0, jw0, jw1, lane);
-#else
                         cnt += kc4_row_list<WPL>(wt, band, BS, j0, jw0, jw1, lane, wlist, kKcRowList);
-#endif
                     }
                 }
             }
@@ -1475,22 +1267,14 @@ __global__ __launch_bounds__(1024) void k_kc_block(const int64_t *__restrict__ h
                 if constexpr (WPL > 1) cand[1] = 64 + lane < W ? rows[size_t(i) * WS + 64 + lane] : 0u;
                 cnt += wave_cliques<LV, WPL>(rows, WS, cand, lane);
             }
-        } else if (LV == 2 && kc4_pairs_enabled) {
+        } else if (LV == 2) {
             // k = 4 on an LDS matrix: pair lists in the dead bitmap / prefix area (12 KB), a share per wave (kc4_count_pairs)
             uint32_t *wbuf = bm + size_t(wave) * size_t((kBitmapWords + kBitmapWords / 2) / nwaves);
             cnt += kc4_count_pairs<TRI>(rows, WS, d, W, wbuf, (kBitmapWords + kBitmapWords / 2) / nwaves, &wave_tot[0], lane);
-        } else if (LV == 2 && W >= 22) {
-            // k = 4, wide matrix in LDS: a single band (the whole matrix), one row per wave and trip.  (Below ~700 vertices
-            // the per-row prefix / select overhead of kc4_row exceeds what its divergence-free inner loop saves.)
-            for (int i = 1 + wave; i < d; i += nwaves) {
-                uint32_t wt[1];
-                wt[0] = lane < W ? rows[size_t(i) * WS + lane] : 0u;
-                cnt += kc4_row<1>(wt, rows, WS, 0, 0, W, lane);
-            }
         } else {
-            // k = 4 on narrower matrices, and narrow rows at k >= 5: one LANE per matrix word (i, w): it walks the set bits j of its word and enumerates the cliques below
+            // narrow rows at k >= 5: one LANE per matrix word (i, w): it walks the set bits j of its word and enumerates the cliques below
             // the path (i, j) by ANDing the path's rows word by word — the reference's isect.intersect(N(vi)) recursion
-            // (k = 4: Σ_i Σ_{j ∈ rows[i]} popc(rows[i] & rows[j])).  Odd row stride: no LDS bank conflicts.
+            // Odd row stride: no LDS bank conflicts.
             const int words = d * W;
             for (int cell = tid; cell < words; cell += nthreads) {
                 const int i = cell / W, w = cell - i * W;
@@ -1863,7 +1647,7 @@ __global__ void k_kcr_items(int64_t H, const int64_t *__restrict__ roff, const i
 // Which shard a pivot belongs to: the pivots' kernels stride over the positions of THEIR BIN — position lo + q * nparts + part of the d+ order, lo = where the
 // bin starts (launch_all) — so the rule needs the bins' starts: lo[] ascending, 0 for "not yet reached".
 struct KcBins {
-    static constexpr int kN = 16;
+    static constexpr int kN = kKcMaxBins;
     int64_t lo[kN];  // unused slots: 0
     __device__ __forceinline__ int part_of(int64_t pos, int nparts) const {
         int64_t l = 0;
@@ -1880,7 +1664,7 @@ struct KcBins {
 // compiler evaluated KcBins::part_of (sixteen 64-bit compares and selects) for EVERY record ahead of `nparts <= 1 ||` — half the vector instructions of the
 // single-GPU kernel.  (Its run time did not move: 72.7 against 75 ms at scale 26 — the pass waits on memory, 77 % of its wave cycles, and what it pulls
 // through the fabric, ≈ 200 M KB of FETCH_SIZE per call, is the bandwidth of the box: every added load made it slower, every removed instruction left it as it was.)
-template <int GW /* lanes per record: 16, or 8 = twice the records in flight per wave (most prefixes fit one step of 64 ids) */, bool SHARDED>
+template <int GW /* lanes per record (8 — twice the records in flight per wave — measured slower: DESIGN_HISTORY_r5.md) */, bool SHARDED>
 __global__ __launch_bounds__(256) void k_kc_reverse(const uint4 *__restrict__ items, int64_t n_items, const ulonglong2 *__restrict__ rec, const int64_t *__restrict__ bmoff,
                                                     const uint32_t *__restrict__ bmpool, const uint16_t *__restrict__ hadj, uint32_t *__restrict__ arena, int nparts,
                                                     int part, KcBins bins, unsigned int *__restrict__ queue) {
@@ -2074,7 +1858,7 @@ __global__ __launch_bounds__(256) void k_kc_reverse_tail(const uint4 *__restrict
 }
 
 // builds the lists above for the graph (once); leaves kc_rel == nullptr when no receiver qualifies or the option KC_REVERSE = 0 says no
-static int ensure_kc_reverse(const gmsx_graph *g, int max_d) {
+static int ensure_kc_reverse(const gmsx_graph *g) {
     if (g->kc_rev_tried) return GMSX_OK;
     g->kc_rev_tried = true;
     if (const char *e = opt("KC_REVERSE"); e && std::atoi(e) == 0) return GMSX_OK;
@@ -2084,9 +1868,7 @@ static int ensure_kc_reverse(const gmsx_graph *g, int max_d) {
     const auto t_begin = std::chrono::steady_clock::now();
     int64_t n_piv = 0, hub_total = 0;
     if (int rc = count_dplus_ge(g, kRevMinD, &n_piv)) return rc;
-    int64_t n_over = 0;
-    if (int rc = count_dplus_ge(g, max_d + 1, &n_over)) return rc;  // (pivots beyond the bit-matrix kernels take part too: harmless, their lists are never read)
-    (void)n_over;
+    // (pivots beyond the bit-matrix kernels take part too: harmless, their lists are never read)
     if (n_piv <= 0) return GMSX_OK;
     GMSX_HIP(hipMemcpyAsync(&hub_total, g->hoff + g->n, 8, hipMemcpyDeviceToHost, s));
     GMSX_HIP(hipStreamSynchronize(s));
@@ -2214,41 +1996,26 @@ static int launch_kc_reverse(const gmsx_graph *g, int part, int nparts, const Kc
     const int cu = c.compute_units > 0 ? c.compute_units : 256;
     const unsigned blocks = unsigned(std::min<int64_t>(g->kc_items, int64_t(cu) * 8));
     if (g->kc_items > 0) {
-        const bool gw8 = opt("KC_REV_GW") && std::atoi(opt("KC_REV_GW")) == 8;  // (hub receivers: 16 lanes per record — 8: 84 against 71 ms at scale 26; option for A/B)
         auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, g->kc_item, g->kc_items, g->kc_rec, g->bmoff, g->bmpool, g->hadj, g->kc_arena, nparts, part, bins, queue); };
-        if (nparts > 1) { if (gw8) go(k_kc_reverse<8, true>); else go(k_kc_reverse<16, true>); }
-        else { if (gw8) go(k_kc_reverse<8, false>); else go(k_kc_reverse<16, false>); }
+        if (nparts > 1) go(k_kc_reverse<16, true>);
+        else go(k_kc_reverse<16, false>);
         ++*launches;
     }
     if (g->kc_relt && g->kc_itemst > 0) {
         const unsigned blocks_t = unsigned(std::min<int64_t>(g->kc_itemst, int64_t(cu) * 8));
-        const bool gw8 = opt("KC_REV_GW") && std::atoi(opt("KC_REV_GW")) == 8;  // (8 lanes per record: 94 against ~105 ms alone at scale 26, but 433 against 425 ms for the call — the passes overlap)
         auto go = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(blocks_t), dim3(256), 0, s, g->kc_itemt, g->kc_itemst, g->kc_rect, g->hoff, g->hadj, g->toff, g->tadj, g->kc_arena, nparts, part, bins, queue + 1);
         };
-        if (nparts > 1) { if (gw8) go(k_kc_reverse_tail<8, true>); else go(k_kc_reverse_tail<16, true>); }
-        else { if (gw8) go(k_kc_reverse_tail<8, false>); else go(k_kc_reverse_tail<16, false>); }
+        if (nparts > 1) go(k_kc_reverse_tail<16, true>);
+        else go(k_kc_reverse_tail<16, false>);
         ++*launches;
     }
     return GMSX_OK;
 }
 
-// widths of the two triangular LDS bins (k = 4): the matrix of d+ <= 1472 and its bitmap / prefix / forward list fill one CU's LDS (153.6 of the 155 KB a
-// launch may ask for); two matrices of d+ <= 960 fit it together (2 x 78.0 KB with the static 4.3 KB each)
-// dynamic LDS the LDS-matrix variants may ask for: the CU's 160 KB minus their 16.2 KB of static LDS (bitmap + prefix counts + tail filter + reduction slots)
-static constexpr int kKcLdsDynMax = 143 * 1024;
-static constexpr int kKcTriTop = 1472, kKcTriTwo = 960;  // (multiples of 32: W = dmax / 32 words)
 static bool kc_tri_enabled() {
-    const char *e = opt("KC_TRI");  // option: 0 = rectangular LDS matrices up to 1024 and the slab beyond, as in rounds 1-5 (A/B)
+    const char *e = opt("KC_TRI");  // option: 0 = rectangular LDS matrices up to 1024 and the slab beyond (A/B)
     return !(e && std::atoi(e) == 0);
-}
-static bool stream_build_default(const gmsx_graph *g) {
-    (void)g;
-    return false;
-}
-static bool pipe_all_default(const gmsx_graph *g) {
-    (void)g;
-    return false;
 }
 
 // The pool the exporting BUILD kernels leave their matrices in (KcExport) — allocated at the first k = 4 call and kept (option KC_POOL_MB, default 6 144: a
@@ -2304,333 +2071,267 @@ static bool kc_mfma_enabled() {
     return !(e && std::atoi(e) == 0);
 }
 
-template <int LV, bool VTX = false>
-static int launch_all(const gmsx_graph *g, int part, int nparts, unsigned long long *acc, int *launches, DevBuf &slab,
-                      unsigned long long *vcounts = nullptr) {
-    Ctx &c = ctx();
-    hipStream_t s = c.stream;
-    const int k = LV + 2;
-    int64_t over = 0, n_min = 0;
-    constexpr int kMaxD = (LV <= 2) ? 8192 : 4096;  // widest bit rows: four words per lane for k = 3, 4 and the per-vertex counts, two for k >= 5
-    int max_d = kMaxD;
-    if (const char *e = opt("KC_MAXD")) {  // test hook: a lower limit sends more pivots through the generic path
-        const int v = std::atoi(e);
-        if (v >= 1 && v < kMaxD) max_d = v;
-    }
-    if (int rc = count_dplus_ge(g, max_d + 1, &over)) return rc;
-    if (!g->rows_sorted) return GMSX_ERR_UNSUPPORTED;  // > 2^32 container entries: rows were not sorted at upload
-    if (over > 0) {
-        // pivots wider than the bit-matrix kernels hold: the generic list recursion takes positions [0, over) of the d+ order — with the per-vertex
-        // counts too (round 6: gmsx_tc_vertex_count2 used to leave the whole graph to one full-row intersect per CSR entry as soon as ONE pivot was
-        // wider than 8192; now only the wide pivots themselves take the slow path)
-        if (int rc = launch_generic(g, k, 0, over, part, nparts, acc, launches, VTX ? vcounts : nullptr)) return rc;
-    }
-    if (int rc = count_dplus_ge(g, std::max(k - 1, 1), &n_min)) return rc;
-    const int cu = c.compute_units > 0 ? c.compute_units : 256;
-    // positions [lo, hi) in the d+-sorted order of the pivots with a < d+ <= b, cut at the smallest useful d+
-    auto range = [&](int a, int b, int64_t *lo, int64_t *hi) -> int {
-        if (int rc = count_dplus_ge(g, b + 1, lo)) return rc;
-        if (int rc = count_dplus_ge(g, a + 1, hi)) return rc;
-        *hi = std::min(*hi, n_min);
-        *lo = std::max(*lo, over);  // positions [0, over) went through the generic path
-        *hi = std::max(*hi, *lo);
-        return GMSX_OK;
-    };
-
-    // Two streams: the wide bins (slab, 1024, 704: one or two workgroups per CU, LDS-bound occupancy) on the caller's
-    // stream, the narrow bins and the wave kernel on a side stream — their small workgroups fill the wave slots and the
-    // LDS the wide ones leave free.  All kernels add into the same accumulators; the side stream is joined below.
-    // FOUR streams (round 3; two before): the bins differ in workgroup size and LDS footprint (one workgroup per CU for the 1024-wide
-    // matrices … sixteen for the narrow ones), each leaves wave slots and LDS the others can use, and a bin's last workgroups no longer hold
-    // up the next bin of the same stream.  GMSX_KC_STREAMS=1 … 4 (A/B).
-    constexpr int kSides = 4;  // three for the bins (round robin with the launch stream), the last for the wave kernel of d+ <= 32
-    static hipStream_t sides[kSides] = {nullptr, nullptr, nullptr, nullptr};
-    static hipEvent_t ev_fork = nullptr, ev_joins[kSides] = {nullptr, nullptr, nullptr, nullptr};
-    if (!sides[0]) {
+// The side streams, the fork / join / reverse events and the kernels whose dynamic-LDS limit is raised: one set per process, whatever k is counted.
+struct KcSide {
+    static constexpr int kSides = 4;  // three for the bins (round robin with the launch stream), the last for the wave kernel of d+ <= 32
+    hipStream_t sides[kSides] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev_fork = nullptr, ev_joins[kSides] = {nullptr, nullptr, nullptr, nullptr}, ev_rev = nullptr;
+    std::vector<const void *> raised;
+    int init() {
+        if (ev_rev) return GMSX_OK;
         for (int i = 0; i < kSides; ++i) {
             GMSX_HIP(hipStreamCreateWithFlags(&sides[i], hipStreamNonBlocking));
             GMSX_HIP(hipEventCreateWithFlags(&ev_joins[i], hipEventDisableTiming));
         }
         GMSX_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+        GMSX_HIP(hipEventCreateWithFlags(&ev_rev, hipEventDisableTiming));
+        return GMSX_OK;
     }
+    int raise_lds(const void *kern, int bytes) {  // once per kernel
+        if (std::find(raised.begin(), raised.end(), kern) != raised.end()) return GMSX_OK;
+        GMSX_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        raised.push_back(kern);
+        return GMSX_OK;
+    }
+    // every way out of a call joins the side streams again — error returns included, so that no later call on the launch stream can overtake kernels
+    // still running beside it
+    struct Join {
+        KcSide &sd;
+        hipStream_t main;
+        bool armed = true;
+        ~Join() {
+            if (!armed) return;
+            for (int i = 0; i < kSides; ++i)
+                if (hipEventRecord(sd.ev_joins[i], sd.sides[i]) == hipSuccess) (void)hipStreamWaitEvent(main, sd.ev_joins[i], 0);
+        }
+    };
+};
+static KcSide g_kc_side;
+
+// one launch of a pivots' kernel: the pivots at positions first + q * nparts + part < end of the d+ order, q = 0, 1, … — a bin of the plan or a chunk of it
+struct KcLaunch {
+    const gmsx_graph *g;
+    const KcBin *bin;
+    const KcShape *shape;  // bin->count, or bin->build with `ex` set
+    hipStream_t stream;
+    unsigned blocks;
+    int64_t first, end;
+    int nparts, part;
+    uint32_t *slabs;
+    unsigned long long *acc, *vcounts;
+    KcRev rv;
+    KcExport ex;
+};
+using KcLaunchFn = int (*)(const KcLaunch &);
+
+// the part of the driver that knows LV = k - 2 and VTX at compile time: which kernel a bin runs
+template <int LV, bool VTX>
+static int launch_bin(const KcLaunch &a) {
+    const gmsx_graph *g = a.g;
+    const KcBin &b = *a.bin;
+    if (b.kind == KcKind::Wave) {
+        hipLaunchKernelGGL((k_kc_small<LV, VTX>), dim3(a.blocks), dim3(a.shape->threads), 0, a.stream, g->hoff, g->hadj, g->toff, g->tadj, g->bmoff, g->bmpool, g->order, a.first,
+                           a.end, a.nparts, a.part, a.acc, g->oldid, a.vcounts, a.rv);
+        return GMSX_OK;
+    }
+    auto go = [&](auto kern) -> int {
+        if (int rc = g_kc_side.raise_lds(reinterpret_cast<const void *>(kern), b.kind == KcKind::Slab ? kKcSlabLdsMax : kKcLdsDynMax)) return rc;
+        hipLaunchKernelGGL(kern, dim3(a.blocks), dim3(a.shape->threads), a.shape->lds, a.stream, g->hoff, g->hadj, g->toff, g->tadj, g->bmoff, g->bmpool, g->dense_limit, g->order,
+                           a.first, a.end, a.nparts, a.part, b.dmax, b.W, a.shape->WS, a.shape->WT, a.slabs, a.acc, g->oldid, a.vcounts, a.rv, a.ex);
+        return GMSX_OK;
+    };
+    if constexpr (LV == 2 && !VTX) {
+        if (a.ex.pool)  // BUILD only: the matrix leaves for the pool
+            return b.kind == KcKind::LdsTri ? go(k_kc_block<2, 1, false, false, 1, true, true>)
+                   : b.wpl == 1             ? go(k_kc_block<2, 1, true, false, 1, false, true>)
+                   : b.wpl == 2             ? go(k_kc_block<2, 2, true, false, 1, false, true>)
+                                            : go(k_kc_block<2, 4, true, false, 1, false, true>);
+        if (b.kind == KcKind::LdsTri) return go(k_kc_block<2, 1, false, false, 1, true>);
+    }
+    if (b.kind == KcKind::Slab) {
+        if (b.wpl == 4) {
+            if constexpr (LV <= 2) return go(k_kc_block<LV, 4, true, VTX>);
+            return GMSX_ERR_KERNEL;  // (k >= 5 stops at d+ = 4096)
+        }
+        return b.wpl == 2 ? go(k_kc_block<LV, 2, true, VTX>) : go(k_kc_block<LV, 1, true, VTX>);
+    }
+    if (b.kind != KcKind::Lds) return GMSX_ERR_KERNEL;  // (the triangular layout serves the k = 4 count only)
+    // one 1024-thread workgroup or two per CU: four waves per SIMD whatever the registers — the pipelined BUILD pays there; the narrower bins build member by member
+    return a.shape->threads == 1024 ? go(k_kc_block<LV, 1, false, VTX, 1>) : go(k_kc_block<LV, 1, false, VTX, 0>);
+}
+
+// a bin of the plan in this call: its positions [lo, hi) of the d+ order, this shard's pivots among them, and whether its matrices went to the pool
+struct KcResolved {
+    KcBin bin;
+    int64_t lo, hi, cnt;
+    bool exported;
+};
+
+// The pivots' kernels of one call.  `launch` = launch_bin<k - 2, vtx>.  *slab_from: the narrowest pivots whose matrix goes through global memory (a slab or the
+// pool) are wider than this — what k_stat_kc_bytes accounts for.
+static int launch_all(const gmsx_graph *g, int k, bool vtx, KcLaunchFn launch, int part, int nparts, unsigned long long *acc, int *launches, DevBuf &slab,
+                      unsigned long long *vcounts, int *slab_from) {
+    Ctx &c = ctx();
+    hipStream_t s = c.stream;
+    int64_t over = 0, n_min = 0;
+    int max_d = k <= 4 ? 8192 : 4096;  // widest bit rows: four words per lane for k = 3, 4 and the per-vertex counts, two for k >= 5
+    if (const char *e = opt("KC_MAXD")) {  // test hook: a lower limit sends more pivots through the generic path
+        const int v = std::atoi(e);
+        if (v >= 1 && v < max_d) max_d = v;
+    }
+    if (int rc = count_dplus_ge(g, max_d + 1, &over)) return rc;
+    if (!g->rows_sorted) return GMSX_ERR_UNSUPPORTED;  // > 2^32 container entries: rows were not sorted at upload
+    if (over > 0) {
+        // pivots wider than the bit-matrix kernels hold: the generic list recursion takes positions [0, over) of the d+ order — with the per-vertex
+        // counts too, so that only the wide pivots themselves take the slow path
+        if (int rc = launch_generic(g, k, 0, over, part, nparts, acc, launches, vcounts)) return rc;
+    }
+    if (int rc = count_dplus_ge(g, std::max(k - 1, 1), &n_min)) return rc;
+    const int cu = c.compute_units > 0 ? c.compute_units : 256;
+    // the bins of this call and where each lies in the d+ order: [lo, hi), cut at the smallest useful d+ (n_min).  A bin starts where the one above it ends,
+    // the first one behind the generic path's positions; the shards of a bin are strides of ITS positions, so the receivers' pass gets the starts too.
+    const bool tri = k == 4 && !vtx && kc_tri_enabled();
+    std::vector<KcResolved> bins;
+    KcBins starts;
+    for (int64_t &x : starts.lo) x = 0;
+    {
+        const std::vector<KcBin> plan = kc_bin_plan(k, vtx, tri, max_d);
+        if (plan.size() > size_t(KcBins::kN)) return GMSX_ERR_KERNEL;
+        int64_t lo = over;
+        for (const KcBin &b : plan) {
+            int64_t below = 0;
+            if (int rc = count_dplus_ge(g, b.from + 1, &below)) return rc;
+            const int64_t hi = std::max(std::min(below, n_min), lo);
+            starts.lo[bins.size()] = lo;
+            bins.push_back({b, lo, hi, part_count(lo, hi, nparts, part), false});
+            lo = below;
+        }
+    }
+
+    // The bins differ in workgroup size and LDS footprint (one workgroup per CU for the 1024-wide matrices … sixteen for the narrow ones): each leaves wave
+    // slots and LDS the others can use, and on streams of their own a bin's last workgroups do not hold up the next bin.  All kernels add into the same
+    // accumulators.  KC_STREAMS = 1 … 4 (A/B).
+    constexpr int kSides = KcSide::kSides;
+    KcSide &sd = g_kc_side;
+    if (int rc = sd.init()) return rc;
+    hipStream_t *sides = sd.sides;
     const int n_streams = [] { const char *e = opt("KC_STREAMS"); const int v = e ? std::atoi(e) : 4; return v < 1 ? 1 : v > 4 ? 4 : v; }();
-    GMSX_HIP(hipEventRecord(ev_fork, s));
-    for (int i = 0; i < kSides; ++i) GMSX_HIP(hipStreamWaitEvent(sides[i], ev_fork, 0));
+    GMSX_HIP(hipEventRecord(sd.ev_fork, s));
+    for (int i = 0; i < kSides; ++i) GMSX_HIP(hipStreamWaitEvent(sides[i], sd.ev_fork, 0));
+    KcSide::Join join{sd, s};
     hipStream_t side = n_streams > 1 ? sides[0] : s;
     // The receivers' pass (the rows the pivots copy instead of streaming their member) and the wave kernel of d+ <= 32 — which reads none of those rows —
     // start TOGETHER, each on a side stream of its own: both are latency-bound (60 - 70 % of their wave cycles waiting, 9 / 6 KB of LDS per workgroup),
     // so they share the CUs instead of queueing (28.5 + 58 ms one after the other at scale 26).  Every other bin waits for the rows (ev_rev).
-    static hipEvent_t ev_rev = nullptr;
-    if (!ev_rev) GMSX_HIP(hipEventCreateWithFlags(&ev_rev, hipEventDisableTiming));
     hipStream_t rev_stream = n_streams > 1 ? sides[kSides - 2] : s, small_stream = n_streams > 1 ? sides[kSides - 1] : s;
-    // the bins of this call: slab widths (each from half its width on), then the LDS-matrix widths, each from the next one on — and, for the receivers'
-    // pass, where each starts in the d+ order (`range` below): the shards of a bin are strides of ITS positions
-    // k = 4 (count only): the LDS matrices of 512 < d+ <= 1472 are stored TRIANGULARLY (kc_tri_off) — two 1024-thread workgroups per CU up to 960, and
-    // the pivots of 1024 < d+ <= 1472 (most of what used to be the first slab bin) count by pair lists in LDS instead of row bands over a global slab
-    const bool tri = LV == 2 && !VTX && kc_tri_enabled();
-    const int l_dmax[3] = {4096, 2048, 8192}, l_from[3] = {2048, tri ? kKcTriTop : 1024, 4096};  // slab bins: (from, dmax]
-    const int m_rect[] = {1024, 704, 640, 512, 384, 256, 192, 128, 96, 64, 32}, m_tri[] = {kKcTriTop, kKcTriTwo, 512, 384, 256, 192, 128, 96, 64, 32};
-    const int *m_dmax = tri ? m_tri : m_rect;  // LDS bins: (next entry, entry]; the last entry = lower end of the last bin
-    const int n_m = tri ? int(sizeof(m_tri) / sizeof(int)) : int(sizeof(m_rect) / sizeof(int));
-    KcBins bins;
-    {
-        int nb = 0;
-        for (int64_t &x : bins.lo) x = 0;
-        auto add = [&](int width) -> int {
-            int64_t lo = 0;
-            if (int rc = count_dplus_ge(g, width + 1, &lo)) return rc;
-            if (nb < KcBins::kN) bins.lo[nb++] = std::max(lo, over);
-            return GMSX_OK;
-        };
-        for (int w : l_dmax)
-            if (int rc = add(w)) return rc;
-        for (int b = 0; b < n_m; ++b)
-            if (int rc = add(m_dmax[b])) return rc;
-    }
     // (Measured and dropped: the tail receivers' pass on a stream of its own beside the hub receivers' — 425 … 442 against 421 ms at scale 26.)
-    if (int rc = launch_kc_reverse(g, part, nparts, bins, acc, launches, rev_stream)) return rc;
+    if (int rc = launch_kc_reverse(g, part, nparts, starts, acc, launches, rev_stream)) return rc;
     const KcRev rv{g->kc_rel, g->kc_aoff, g->kc_arena, g->kc_relt};
     if (g->kc_rel && (g->kc_items > 0 || g->kc_itemst > 0) && n_streams > 1) {
-        GMSX_HIP(hipEventRecord(ev_rev, rev_stream));
-        GMSX_HIP(hipStreamWaitEvent(s, ev_rev, 0));
-        for (int i = 0; i + 2 < kSides; ++i) GMSX_HIP(hipStreamWaitEvent(sides[i], ev_rev, 0));
-        if (g->kc_relt) GMSX_HIP(hipStreamWaitEvent(small_stream, ev_rev, 0));  // (the wave kernel reads its tail members' rows from the arena too)
+        GMSX_HIP(hipEventRecord(sd.ev_rev, rev_stream));
+        GMSX_HIP(hipStreamWaitEvent(s, sd.ev_rev, 0));
+        for (int i = 0; i + 2 < kSides; ++i) GMSX_HIP(hipStreamWaitEvent(sides[i], sd.ev_rev, 0));
+        if (g->kc_relt) GMSX_HIP(hipStreamWaitEvent(small_stream, sd.ev_rev, 0));  // (the wave kernel reads its tail members' rows from the arena too)
     }
     int next_stream = 0;
     auto pick = [&]() -> hipStream_t {  // round robin over the launch stream and the side streams in use
         const int i = next_stream++ % n_streams;
         return i == 0 ? s : sides[i - 1];
     };
-    // every way out of this function joins the side streams again — error returns included, so that no later call on the launch
-    // stream can overtake kernels still running beside it
-    struct Join {
-        hipStream_t main;
-        hipStream_t *sides;
-        hipEvent_t *evs;
-        bool armed = true;
-        ~Join() {
-            if (!armed) return;
-            for (int i = 0; i < kSides; ++i)
-                if (hipEventRecord(evs[i], sides[i]) == hipSuccess) (void)hipStreamWaitEvent(main, evs[i], 0);
-        }
-    } join{s, sides, ev_joins};
-    // S: k-1 <= d+ <= 32 — launched first, beside the receivers' pass (see above)
-    {
-        int64_t lo = 0, hi = 0;
-        if (int rc = range(0, 32, &lo, &hi)) return rc;
-        const int64_t cnt = part_count(lo, hi, nparts, part);
-        if (cnt > 0) {
-            const int64_t blocks = std::min<int64_t>((cnt + 3) / 4, int64_t(cu) * 32);
-            hipLaunchKernelGGL((k_kc_small<LV, VTX>), dim3(unsigned(blocks)), dim3(256), 0, small_stream, g->hoff, g->hadj, g->toff, g->tadj, g->bmoff, g->bmpool,
-                               g->order, lo, hi, nparts, part, acc, g->oldid, vcounts, rv);
-            ++*launches;
-        }
-    }
+    const KcExport no_export{nullptr, nullptr, 0ull};
+    auto run = [&](const KcResolved &r, const KcShape &shape, hipStream_t st, int64_t blocks, int64_t first, int64_t end, uint32_t *slabs, const KcExport &ex) -> int {
+        return launch(KcLaunch{g, &r.bin, &shape, st, unsigned(blocks), first, end, nparts, part, slabs, acc, vcounts, rv, ex});
+    };
     const bool timing = opt("TIMING") != nullptr;  // the bins' pivot counts on stderr
-    // k = 4 on the MATRIX CORES (round 6): the bins of d+ > 512 BUILD their matrices into a pool — chunk by chunk, a pool region and a stream per chunk in
-    // turn — and each chunk's count is one k_kc4_mfma launch behind its BUILD on the same stream (kc4_mfma.hpp): the BUILD of the next chunk (rows streamed
-    // from HBM: latency and bandwidth) runs beside the count of this one (matrix cores and VALU, operands from the L2).
-    bool exported_slab[3] = {false, false, false}, exported_tri = false;
-    if constexpr (LV == 2 && !VTX) {
-        // (a graph without a pivot wider than 512 allocates nothing)
-        size_t needed = 0;
-        if (kc_mfma_enabled()) {
-            const int froms[5] = {4096, 2048, tri ? kKcTriTop : 1024, kKcTriTwo, 512}, tos[5] = {8192, 4096, 2048, kKcTriTop, kKcTriTwo};
-            for (int b = 0; b < (tri ? 5 : 3); ++b) {
-                int64_t lo = 0, hi = 0;
-                if (int rc = range(froms[b], tos[b], &lo, &hi)) return rc;
-                needed += size_t(part_count(lo, hi, nparts, part)) * (size_t(tos[b]) * size_t(kc4m_stride(tos[b])) + kKcSlotPad) * 4;
-            }
-        }
-        if (needed > 0) {
+    // S: k-1 <= d+ <= 32 — launched first, beside the receivers' pass (see above)
+    if (const KcResolved &r = bins.back(); r.bin.kind == KcKind::Wave && r.cnt > 0) {
+        if (int rc = run(r, r.bin.count, small_stream, std::min<int64_t>((r.cnt + 3) / 4, int64_t(cu) * 32), r.lo, r.hi, nullptr, no_export)) return rc;
+        ++*launches;
+    }
+    // k = 4 on the MATRIX CORES: the bins that can BUILD their matrices into a pool — chunk by chunk, a pool region and a stream per chunk in turn — and each
+    // chunk's count is one k_kc4_mfma launch behind its BUILD on the same stream (kc4_mfma.hpp): the BUILD of the next chunk (rows streamed from HBM: latency
+    // and bandwidth) runs beside the count of this one (matrix cores and VALU, operands from the L2).
+    if (kc_mfma_enabled()) {
+        auto slot_words_of = [](const KcBin &b) { return size_t(b.dmax) * size_t(kc4m_stride(b.dmax)) + kKcSlotPad; };
+        size_t needed = 0;  // (a graph without a pivot in those bins allocates nothing)
+        for (const KcResolved &r : bins)
+            if (r.bin.can_export) needed += size_t(r.cnt) * slot_words_of(r.bin) * 4;
+        if (needed > 0)
             if (int rc = ensure_kc_pool(needed + (size_t(1) << 20))) return rc;
-            KcPool &pool = kc_pool();
-            const int n_regions = std::min(n_streams, kKcPoolRegions);
-            const size_t region_words = pool.bytes / 4 / size_t(n_regions) & ~size_t(63);
-            static bool x_attr = false;
-            if (!x_attr) {
-                GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<2, 1, true, false, 1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-                GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<2, 2, true, false, 1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-                GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<2, 4, true, false, 1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-                GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<2, 1, false, false, 1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kKcLdsDynMax));
-                x_attr = true;
-            }
-            int chunk_seq = 0;
-            // one bin (from, dmax]: slab variant WPL = 1 / 2 / 4 (dmax 2048 / 4096 / 8192) or the triangular LDS variant (WPL = 0)
-            auto export_bin = [&](int from, int dmax, int wpl, bool *done) -> int {
-                *done = false;
-                if (!pool.base) return GMSX_OK;
-                const size_t slot_words = size_t(dmax) * size_t(kc4m_stride(dmax)) + kKcSlotPad;
-                const int64_t cap = std::min<int64_t>(int64_t(region_words / slot_words), kKcChunkMax);
-                if (cap < 1) return GMSX_OK;  // the pool cannot hold one matrix of this bin: it keeps its in-kernel count
-                int64_t lo = 0, hi = 0;
-                if (int rc = range(from, dmax, &lo, &hi)) return rc;
-                const int64_t cnt = part_count(lo, hi, nparts, part);
-                *done = true;
-                if (timing && cnt > 0) std::fprintf(stderr, "[gmsx kclique] matrix-core bin d+ <= %d: %lld pivots, %lld per chunk\n", dmax, (long long)cnt, (long long)cap);
-                const int W = dmax / 32;
-                for (int64_t q0 = 0; q0 < cnt; q0 += cap) {
-                    const int64_t nq = std::min(cap, cnt - q0);
-                    const int r = chunk_seq++ % n_regions;
-                    hipStream_t st = r == 0 ? s : sides[r - 1];
-                    const KcExport ex{pool.base + size_t(r) * region_words, pool.dpool + size_t(r) * kKcChunkMax, (unsigned long long)slot_words};
-                    const int64_t first = lo + q0 * nparts, end = std::min(hi, lo + (q0 + nq) * nparts);
-                    if (wpl > 0) {
-                        constexpr int slab_threads = 1024;
-                        const size_t lds = size_t(kBitmapWords) * 4 + size_t(kBitmapWords) * 2 + size_t(slab_threads / 64) * 4 * W * 4 +  // bitmap + prefix + row stage
-                                           ((size_t(dmax) * 2 + 15) & ~size_t(15));                                                            // + the forward list
-                        const unsigned blocks = unsigned(std::min<int64_t>(nq, int64_t(cu)));  // (128 registers x 1024 threads: one workgroup per CU)
-                        if (wpl == 1)
-                            hipLaunchKernelGGL((k_kc_block<2, 1, true, false, 1, false, true>), dim3(blocks), dim3(slab_threads), lds, st, g->hoff, g->hadj, g->toff, g->tadj, g->bmoff, g->bmpool,
-                                               g->dense_limit, g->order, first, end, nparts, part, dmax, W, W, 0, static_cast<uint32_t *>(nullptr), acc, g->oldid, vcounts, rv, ex);
-                        else if (wpl == 2)
-                            hipLaunchKernelGGL((k_kc_block<2, 2, true, false, 1, false, true>), dim3(blocks), dim3(slab_threads), lds, st, g->hoff, g->hadj, g->toff, g->tadj, g->bmoff, g->bmpool,
-                                               g->dense_limit, g->order, first, end, nparts, part, dmax, W, W, 0, static_cast<uint32_t *>(nullptr), acc, g->oldid, vcounts, rv, ex);
-                        else
-                            hipLaunchKernelGGL((k_kc_block<2, 4, true, false, 1, false, true>), dim3(blocks), dim3(slab_threads), lds, st, g->hoff, g->hadj, g->toff, g->tadj, g->bmoff, g->bmpool,
-                                               g->dense_limit, g->order, first, end, nparts, part, dmax, W, W, 0, static_cast<uint32_t *>(nullptr), acc, g->oldid, vcounts, rv, ex);
-                    } else {
-                        const size_t lds = size_t(kc_tri_off(dmax)) * 4 + ((size_t(dmax) * 2 + 15) & ~size_t(15));
-                        const unsigned blocks = unsigned(std::min<int64_t>(nq, int64_t(cu) * 64));
-                        constexpr int tri_threads = 1024;
-                        hipLaunchKernelGGL((k_kc_block<2, 1, false, false, 1, true, true>), dim3(blocks), dim3(tri_threads), lds, st, g->hoff, g->hadj, g->toff, g->tadj, g->bmoff,
-                                           g->bmpool, g->dense_limit, g->order, first, end, nparts, part, dmax, W, W | 1, 0, static_cast<uint32_t *>(nullptr), acc, g->oldid,
-                                           vcounts, rv, ex);
-                    }
-                    // teams of G workgroups of one XCD per matrix (kc4_mfma.hpp): the wider the matrices, the more of an XCD's CUs share one — measured on 1 024
-                    // matrices of d+ = 600 / 1 200 / 1 800 / 3 000: G = 1 / 2 / 4 / 8 are the fastest (0.092 / 0.220 / 0.717 / 1.46 ms; G = 1: 0.092 / 0.244 / 0.822 / 1.87)
-                    const int G = dmax <= kKcTriTwo ? 1 : dmax <= kKcTriTop ? 2 : dmax <= 2048 ? 4 : 8;
-                    const unsigned cgrid = unsigned(std::max(cu / (8 * G), 1) * 8 * G);  // (a multiple of 8 G; teams beyond the chunk's matrices leave at once)
-                    // (Measured at scale 26 and dropped: 256- / 512-thread count workgroups, two or four per CU, with 512- / 768-thread BUILD workgroups beside them, so
-                    //  that a count wave per SIMD fits next to the BUILD's — 504 … 545 against 489 ms: the two kernels slow each other more than the overlap gains.)
-                    hipLaunchKernelGGL((k_kc4_mfma<2, 1024>), dim3(cgrid), dim3(1024), 0, st, ex.pool, slot_words, ex.dpool, int(nq), G, acc, kAccSlots, kAccStride);
-                    *launches += 2;
-                }
-                return GMSX_OK;
-            };
-            if (int rc = export_bin(4096, 8192, 4, &exported_slab[2])) return rc;
-            if (int rc = export_bin(2048, 4096, 2, &exported_slab[0])) return rc;
-            if (int rc = export_bin(tri ? kKcTriTop : 1024, 2048, 1, &exported_slab[1])) return rc;
-            if (tri) {
-                bool a = false, b = false;
-                if (int rc = export_bin(kKcTriTwo, kKcTriTop, 0, &a)) return rc;
-                if (int rc = export_bin(512, kKcTriTwo, 0, &b)) return rc;
-                exported_tri = a && b;
-                if (a != b) return GMSX_ERR_KERNEL;  // (both bins have slots of at most 283 KB: a pool that holds one holds the other)
+        KcPool &pool = kc_pool();
+        const int n_regions = std::min(n_streams, kKcPoolRegions);
+        const size_t region_words = pool.bytes / 4 / size_t(n_regions) & ~size_t(63);
+        int chunk_seq = 0;
+        for (KcResolved &r : bins) {
+            if (!r.bin.can_export || !pool.base) continue;
+            const size_t slot_words = slot_words_of(r.bin);
+            const int64_t cap = std::min<int64_t>(int64_t(region_words / slot_words), kKcChunkMax);
+            if (cap < 1) continue;  // the pool cannot hold one matrix of this bin: it keeps its in-kernel count
+            r.exported = true;
+            const int dmax = r.bin.dmax;
+            if (timing && r.cnt > 0) std::fprintf(stderr, "[gmsx kclique] matrix-core bin d+ <= %d: %lld pivots, %lld per chunk\n", dmax, (long long)r.cnt, (long long)cap);
+            for (int64_t q0 = 0; q0 < r.cnt; q0 += cap) {
+                const int64_t nq = std::min(cap, r.cnt - q0);
+                const int reg = chunk_seq++ % n_regions;
+                hipStream_t st = reg == 0 ? s : sides[reg - 1];
+                const KcExport ex{pool.base + size_t(reg) * region_words, pool.dpool + size_t(reg) * kKcChunkMax, (unsigned long long)slot_words};
+                // (a slab BUILD: one workgroup per CU)
+                const int64_t blocks = std::min<int64_t>(nq, r.bin.kind == KcKind::Slab ? int64_t(cu) : int64_t(cu) * 64);
+                if (int rc = run(r, r.bin.build, st, blocks, r.lo + q0 * nparts, std::min(r.hi, r.lo + (q0 + nq) * nparts), nullptr, ex)) return rc;
+                // teams of G workgroups of one XCD per matrix (kc4_mfma.hpp): the wider the matrices, the more of an XCD's CUs share one — measured on 1 024
+                // matrices of d+ = 600 / 1 200 / 1 800 / 3 000: G = 1 / 2 / 4 / 8 are the fastest (0.092 / 0.220 / 0.717 / 1.46 ms; G = 1: 0.092 / 0.244 / 0.822 / 1.87)
+                const int G = dmax <= kKcTriTwo ? 1 : dmax <= kKcTriTop ? 2 : dmax <= 2048 ? 4 : 8;
+                const unsigned cgrid = unsigned(std::max(cu / (8 * G), 1) * 8 * G);  // (a multiple of 8 G; teams beyond the chunk's matrices leave at once)
+                // (Measured at scale 26 and dropped: 256- / 512-thread count workgroups, two or four per CU, with 512- / 768-thread BUILD workgroups beside them, so
+                //  that a count wave per SIMD fits next to the BUILD's — 504 … 545 against 489 ms: the two kernels slow each other more than the overlap gains.)
+                hipLaunchKernelGGL((k_kc4_mfma<2, 1024>), dim3(cgrid), dim3(1024), 0, st, ex.pool, slot_words, ex.dpool, int(nq), G, acc, kAccSlots, kAccStride);
+                *launches += 2;
             }
         }
     }
-    // L: 1024 < d+ <= 4096 (8192 for k <= 4), bit-matrix in a global slab per workgroup; one launch per row width (one / two / four words per lane)
-    constexpr int NL = (LV <= 2) ? 3 : 2;
-    size_t slab_bytes[3] = {0, 0, 0};
-    int64_t l_lo[3], l_hi[3], l_cnt[3] = {0, 0, 0}, l_blocks[3];
-    for (int b = 0; b < NL; ++b) {
-        if (exported_slab[b]) continue;
-        if (int rc = range(l_from[b], l_dmax[b], &l_lo[b], &l_hi[b])) return rc;
-        l_cnt[b] = part_count(l_lo[b], l_hi[b], nparts, part);
-        l_blocks[b] = std::min<int64_t>(l_cnt[b], cu);  // one workgroup per CU: the LDS tile / stage fills it
-        if (timing && l_cnt[b] > 0) std::fprintf(stderr, "[gmsx kclique] slab bin d+ <= %d: %lld pivots\n", l_dmax[b], (long long)l_cnt[b]);
-        if (l_cnt[b] > 0) slab_bytes[b] = size_t(l_blocks[b]) * l_dmax[b] * (l_dmax[b] / 32 + 1) * sizeof(uint32_t);
-    }
-    if (slab_bytes[0] + slab_bytes[1] + slab_bytes[2] > 0) {
-        GMSX_HIP(hipMalloc(&slab.p, std::max({slab_bytes[0], slab_bytes[1], slab_bytes[2]})));  // the launches run back to back
-        uint32_t *slabs = slab.as<uint32_t>();
-        static bool l_attr[kMaxK + 1] = {false};
-        if (!l_attr[VTX ? kMaxK : LV]) {
-            GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<LV, 1, true, VTX>), hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-            GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<LV, 2, true, VTX>), hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-            if constexpr (LV <= 2)
-                GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<LV, 4, true, VTX>), hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-            l_attr[VTX ? kMaxK : LV] = true;
+    *slab_from = INT32_MAX;
+    for (const KcResolved &r : bins)
+        if (r.bin.kind == KcKind::Slab || r.exported) *slab_from = std::min(*slab_from, r.bin.from);
+    // L: the slab bins that count in their kernel — bit-matrix in a global slab per workgroup, one workgroup per CU (the LDS band / stage fills it).  They run
+    // back to back on the launch stream and share one slab; the (4096, 8192] bin, which rarely has a pivot, goes behind the other two.
+    // (Tried: the other cut of a slab matrix — a CHUNK of 16 / 8 column words of every row in LDS and one lane per pair (i, j) as on the LDS matrices, pairs
+    //  enumerated from the slab into per-wave lists: bit-exact, and SLOWER — 270.7 against 249.5 ms for the d+ <= 2048 bin, 171.6 against 98.7 for d+ <= 4096
+    //  at scale 26 (profiles/r06/kc26_slab_chunks.txt).  The slab matrices are dense enough that the count is the AND + popcount words themselves, and a
+    //  lane-per-pair loop reads BOTH rows from LDS for every word where the band loop holds row i in registers.)
+    {
+        std::vector<const KcResolved *> todo;
+        size_t slab_bytes = 0;
+        for (const KcResolved &r : bins) {
+            if (r.bin.kind != KcKind::Slab || r.exported || r.cnt <= 0) continue;
+            if (timing) std::fprintf(stderr, "[gmsx kclique] slab bin d+ <= %d: %lld pivots\n", r.bin.dmax, (long long)r.cnt);
+            slab_bytes = std::max(slab_bytes, size_t(std::min<int64_t>(r.cnt, cu)) * r.bin.dmax * r.bin.count.WS * sizeof(uint32_t));
+            todo.push_back(&r);
         }
-        for (int b = 0; b < NL; ++b) {
-            if (l_cnt[b] <= 0) continue;
-            const int dmax = l_dmax[b], W = dmax / 32, WS = W + 1;
-            const int threads = LV == 2 ? 1024 : 512;
-            // (Round 6 tried the other cut of a slab matrix — a CHUNK of 16 / 8 column words of every row in LDS and one lane per pair (i, j) as on the LDS
-            //  matrices, pairs enumerated from the slab into per-wave lists: bit-exact, and SLOWER — 270.7 against 249.5 ms for the d+ <= 2048 bin, 171.6 against
-            //  98.7 for d+ <= 4096 at scale 26 (profiles/r06/kc26_slab_chunks.txt).  The slab matrices are dense enough that the count is the AND + popcount
-            //  words themselves, and a lane-per-pair loop reads BOTH rows from LDS for every word where the band loop below holds row i in registers.)
-            const int WT = dmax == 8192 ? 128 : dmax == 4096 ? 288 : 576;  // k = 4 row band: WT rows x (W+1) words of LDS (multiple of 32)
-            size_t lds = size_t(kBitmapWords) * 4 + size_t(kBitmapWords) * 2 + size_t(threads / 64) * 4 * W * 4;  // bitmap + prefix + row stage
-            if (LV == 2) lds = std::max(lds, size_t(WT) * (W + 1) * 4 + size_t(threads / 64) * kKcRowList * sizeof(unsigned short));  // + the waves' neighbour lists (kc4_row_list)
-            if (VTX) lds += size_t(dmax) * 4;  // column counters
-            if (b == 2) {
-                if constexpr (LV <= 2)
-                    hipLaunchKernelGGL((k_kc_block<LV, 4, true, VTX>), dim3(unsigned(l_blocks[b])), dim3(threads), lds, s, g->hoff, g->hadj, g->toff, g->tadj,
-                                       g->bmoff, g->bmpool, g->dense_limit, g->order, l_lo[b], l_hi[b], nparts, part, dmax, W, WS, WT, slabs, acc, g->oldid, vcounts, rv, KcExport{nullptr, nullptr, 0ull});
-            } else if (b == 0)
-                hipLaunchKernelGGL((k_kc_block<LV, 2, true, VTX>), dim3(unsigned(l_blocks[b])), dim3(threads), lds, s, g->hoff, g->hadj, g->toff, g->tadj,
-                                   g->bmoff, g->bmpool, g->dense_limit, g->order, l_lo[b], l_hi[b], nparts, part, dmax, W, WS, WT, slabs, acc, g->oldid, vcounts, rv, KcExport{nullptr, nullptr, 0ull});
-            else
-                hipLaunchKernelGGL((k_kc_block<LV, 1, true, VTX>), dim3(unsigned(l_blocks[b])), dim3(threads), lds, s, g->hoff, g->hadj, g->toff, g->tadj,
-                                   g->bmoff, g->bmpool, g->dense_limit, g->order, l_lo[b], l_hi[b], nparts, part, dmax, W, WS, WT, slabs, acc, g->oldid, vcounts, rv, KcExport{nullptr, nullptr, 0ull});
-            ++*launches;
+        if (!todo.empty()) {
+            if (todo.front()->bin.wpl == 4) std::rotate(todo.begin(), todo.begin() + 1, todo.end());
+            GMSX_HIP(hipMalloc(&slab.p, slab_bytes));
+            for (const KcResolved *r : todo) {
+                if (int rc = run(*r, r->bin.count, s, std::min<int64_t>(r->cnt, cu), r->lo, r->hi, slab.as<uint32_t>(), no_export)) return rc;
+                ++*launches;
+            }
         }
     }
-    // M: 32 < d+ <= 1024, bit-matrix in LDS; one launch per bin — the bins are cut where another workgroup fits a CU
-    static bool attr_set[kMaxK + 1] = {false};
-    if (!attr_set[VTX ? kMaxK : LV]) {
-        GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<LV, 1, false, VTX, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, kKcLdsDynMax));
-        if constexpr (LV == 2 && !VTX)
-            GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<LV, 1, false, VTX, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kKcLdsDynMax));
-        GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<LV, 1, false, VTX, 0>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kKcLdsDynMax));
-        GMSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_kc_block<LV, 1, false, VTX, 1>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, kKcLdsDynMax));
-        attr_set[VTX ? kMaxK : LV] = true;
-    }
-    // the pipelined BUILD (member id -> extents -> first units, three members deep) in the narrower bins too: GMSX_KC_PIPE_ALL = 1 always, 0 never, unset =
-    // when the oriented containers outgrow the 256 MB Infinity Cache (a member's row then costs HBM round trips, not cache hits — see DESIGN.md §5.2)
-    const bool pipe_all = [&] {
-        if (const char *e = opt("KC_PIPE_ALL")) return std::atoi(e) != 0;
-        return pipe_all_default(g);
-    }();
-    // the step-stream BUILD (mode 2): GMSX_KC_STREAM_BUILD = 1 always, 0 never, unset = by graph size (stream_build_default)
-    const bool stream_build = [&] {
-        if (const char *e = opt("KC_STREAM_BUILD")) return std::atoi(e) != 0;
-        return stream_build_default(g);
-    }();
-    for (int b = 0; b + 1 < n_m; ++b) {
-        const int dmax = m_dmax[b], W = dmax / 32, WS = W | 1;  // odd stride: rows of one column spread over the LDS banks
-        const bool tri_bin = tri && dmax > 512;
-        if (tri_bin && exported_tri) continue;
-        int64_t lo = 0, hi = 0;
-        if (int rc = range(m_dmax[b + 1], dmax, &lo, &hi)) return rc;
-        const int64_t cnt = part_count(lo, hi, nparts, part);
-        if (timing && cnt > 0) std::fprintf(stderr, "[gmsx kclique] LDS bin d+ <= %d: %lld pivots\n", dmax, (long long)cnt);
-        if (cnt > 0) {
-            // (the bitmap, the prefix counts and the tail filter — 16 KB — are static LDS of the LDS-matrix variants)
-            const size_t lds = (tri_bin ? size_t(kc_tri_off(dmax)) : size_t(dmax) * WS) * 4 + (VTX ? size_t(dmax) * 4 : 0) +
-                               ((size_t(dmax) * 2 + 15) & ~size_t(15));  // + the list of the members streamed forward (2 bytes each; no bin loses a workgroup per CU to it)
-            const int64_t blocks = std::min<int64_t>(cnt, int64_t(cu) * 64);
-            const int threads = dmax >= 640 ? 1024 : dmax >= 384 ? 512 : 256;  // (d+ <= 640: TWO 1024-thread workgroups fit a CU — 53.8 KB of matrix each)
-            // (one 1024-thread workgroup per CU from d+ = 513 on: four waves per SIMD whatever the registers — the pipelined BUILD pays there)
-            // (the step-stream BUILD adds 256 descriptors to the dynamic LDS: where they no longer fit beside the matrix and the 4 KB static filter —
-            // the d+ <= 1024 bin with per-vertex counts — the bin keeps its default BUILD instead of failing its launch: ADVICE r5)
-            if (tri_bin) {
-                if constexpr (LV == 2 && !VTX)
-                    hipLaunchKernelGGL((k_kc_block<LV, 1, false, VTX, 1, true>), dim3(unsigned(blocks)), dim3(1024), lds, n_streams > 2 ? pick() : s, g->hoff, g->hadj,
-                                       g->toff, g->tadj, g->bmoff, g->bmpool, g->dense_limit, g->order, lo, hi, nparts, part, dmax, W, WS, 0, static_cast<uint32_t *>(nullptr), acc, g->oldid, vcounts, rv, KcExport{nullptr, nullptr, 0ull});
-            } else if (stream_build && lds + 256 * sizeof(KcDesc) <= size_t(kKcLdsDynMax))
-                hipLaunchKernelGGL((k_kc_block<LV, 1, false, VTX, 2>), dim3(unsigned(blocks)), dim3(threads), lds + 256 * sizeof(KcDesc), n_streams > 2 ? pick() : (dmax >= 704 ? s : side), g->hoff, g->hadj,
-                                   g->toff, g->tadj, g->bmoff, g->bmpool, g->dense_limit, g->order, lo, hi, nparts, part, dmax, W, WS, 0, static_cast<uint32_t *>(nullptr), acc, g->oldid, vcounts, rv, KcExport{nullptr, nullptr, 0ull});
-            else if (threads == 1024 || pipe_all)
-                hipLaunchKernelGGL((k_kc_block<LV, 1, false, VTX, 1>), dim3(unsigned(blocks)), dim3(threads), lds, n_streams > 2 ? pick() : (dmax >= 704 ? s : side), g->hoff, g->hadj,
-                                   g->toff, g->tadj, g->bmoff, g->bmpool, g->dense_limit, g->order, lo, hi, nparts, part, dmax, W, WS, 0, static_cast<uint32_t *>(nullptr), acc, g->oldid, vcounts, rv, KcExport{nullptr, nullptr, 0ull});
-            else
-                hipLaunchKernelGGL((k_kc_block<LV, 1, false, VTX, 0>), dim3(unsigned(blocks)), dim3(threads), lds, n_streams > 2 ? pick() : (dmax >= 704 ? s : side), g->hoff, g->hadj,
-                                   g->toff, g->tadj, g->bmoff, g->bmpool, g->dense_limit, g->order, lo, hi, nparts, part, dmax, W, WS, 0, static_cast<uint32_t *>(nullptr), acc, g->oldid, vcounts, rv, KcExport{nullptr, nullptr, 0ull});
-            ++*launches;
-        }
+    // M: bit-matrix in LDS; one launch per bin
+    for (const KcResolved &r : bins) {
+        if ((r.bin.kind != KcKind::Lds && r.bin.kind != KcKind::LdsTri) || r.exported || r.cnt <= 0) continue;
+        if (timing) std::fprintf(stderr, "[gmsx kclique] LDS bin d+ <= %d: %lld pivots\n", r.bin.dmax, (long long)r.cnt);
+        hipStream_t st = n_streams > 2 ? pick() : (r.bin.dmax >= 704 ? s : side);
+        if (int rc = run(r, r.bin.count, st, std::min<int64_t>(r.cnt, int64_t(cu) * 64), r.lo, r.hi, nullptr, no_export)) return rc;
+        ++*launches;
     }
     join.armed = false;
     for (int i = 0; i < kSides; ++i) {
-        GMSX_HIP(hipEventRecord(ev_joins[i], sides[i]));
-        GMSX_HIP(hipStreamWaitEvent(s, ev_joins[i], 0));
+        GMSX_HIP(hipEventRecord(sd.ev_joins[i], sides[i]));
+        GMSX_HIP(hipStreamWaitEvent(s, sd.ev_joins[i], 0));
     }
     return GMSX_OK;
 }
+
 
 // gmsx_stats.stream_bytes of a k-clique call: the ALGORITHMIC bytes of this formulation, no cache assumed — per pivot u of the shard (d+ >= k - 1; position in
 // the d+ order ≡ part mod nparts) its own containers once and, per member v, the containers of N+(v) the BUILD reads: the hub part as bitset words or
@@ -2677,6 +2378,34 @@ __global__ __launch_bounds__(256) void k_stat_kc_bytes(int64_t n_min, int nparts
     if (lane == 0 && b) atomicAdd(out, b);
 }
 
+// What a count call owns, and its frame: the zeroed accumulator block, the timed region between the context's two events, the sum read back.
+struct KcCall {
+    DevBuf d_acc, slabs;  // (slabs: the global-slab bins of launch_all, freed when the call is over)
+    unsigned long long *acc = nullptr;
+    int launches = 0;
+    int begin(Ctx &c) {
+        GMSX_HIP(hipMalloc(&d_acc.p, sizeof(unsigned long long) * kAccSlots * kAccStride));
+        acc = d_acc.as<unsigned long long>();
+        GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * kAccSlots * kAccStride, c.stream));
+        GMSX_HIP(hipEventRecord(c.ev[0], c.stream));
+        return GMSX_OK;
+    }
+    int end(Ctx &c, unsigned long long *total, float *ms) {
+        GMSX_HIP(hipEventRecord(c.ev[1], c.stream));
+        GMSX_HIP(hipGetLastError());
+        unsigned long long host[kAccSlots * kAccStride];
+        GMSX_HIP(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, c.stream));
+        GMSX_HIP(hipStreamSynchronize(c.stream));
+        *total = 0;
+        for (int i = 0; i < kAccSlots; ++i) *total += host[i * kAccStride];
+        GMSX_HIP(hipEventElapsedTime(ms, c.ev[0], c.ev[1]));
+        return GMSX_OK;
+    }
+};
+
+static const KcLaunchFn kc_launcher[kMaxK - 2] = {launch_bin<1, false>, launch_bin<2, false>, launch_bin<3, false>, launch_bin<4, false>,
+                                                  launch_bin<5, false>, launch_bin<6, false>, launch_bin<7, false>, launch_bin<8, false>};  // k = 3 … kMaxK
+
 static int kclique_partial(const gmsx_graph *g, int k, int part, int nparts, uint64_t *out, gmsx_stats *st) {
     Ctx &c = ctx();
     hipStream_t s = c.stream;
@@ -2690,52 +2419,35 @@ static int kclique_partial(const gmsx_graph *g, int k, int part, int nparts, uin
     // container like the triangle-count task lists; the reference's harness likewise times its SetGraph build apart, k_clique_count_set_based.h:22)
     const bool rev_was_there = g->kc_rev_tried;
     if (k <= kMaxK && g->rows_sorted)
-        if (int rc0 = ensure_kc_reverse(g, 8192)) return rc0;
+        if (int rc0 = ensure_kc_reverse(g)) return rc0;
     const double setup_ms = rev_was_there ? 0.0 : g->kc_rev_build_ms;
-    DevBuf d_acc, slabs;  // (slabs: the global-slab bins of launch_all, freed when the call is over)
-    GMSX_HIP(hipMalloc(&d_acc.p, sizeof(unsigned long long) * kAccSlots * kAccStride));
-    unsigned long long *acc = d_acc.as<unsigned long long>();
-    GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * kAccSlots * kAccStride, s));
-    GMSX_HIP(hipEventRecord(c.ev[0], s));
-    int launches = 0, rc = GMSX_OK;
-    switch (k) {
-        case 3: rc = launch_all<1>(g, part, nparts, acc, &launches, slabs); break;
-        case 4: rc = launch_all<2>(g, part, nparts, acc, &launches, slabs); break;
-        case 5: rc = launch_all<3>(g, part, nparts, acc, &launches, slabs); break;
-        case 6: rc = launch_all<4>(g, part, nparts, acc, &launches, slabs); break;
-        case 7: rc = launch_all<5>(g, part, nparts, acc, &launches, slabs); break;
-        case 8: rc = launch_all<6>(g, part, nparts, acc, &launches, slabs); break;
-        case 9: rc = launch_all<7>(g, part, nparts, acc, &launches, slabs); break;
-        case 10: rc = launch_all<8>(g, part, nparts, acc, &launches, slabs); break;
-        default: {  // k > kMaxK: every pivot that can head a k-clique (d+ >= k-1) through the generic list recursion
-            int64_t n_min = 0;
-            rc = g->rows_sorted ? count_dplus_ge(g, k - 1, &n_min) : GMSX_ERR_UNSUPPORTED;
-            if (!rc) rc = launch_generic(g, k, 0, n_min, part, nparts, acc, &launches);
-        }
+    KcCall call;
+    if (int rc = call.begin(c)) return rc;
+    int slab_from = kKcLdsTop;
+    if (k <= kMaxK) {
+        if (int rc = launch_all(g, k, false, kc_launcher[k - 3], part, nparts, call.acc, &call.launches, call.slabs, nullptr, &slab_from)) return rc;
+    } else {  // every pivot that can head a k-clique (d+ >= k-1) through the generic list recursion
+        int64_t n_min = 0;
+        if (!g->rows_sorted) return GMSX_ERR_UNSUPPORTED;
+        if (int rc = count_dplus_ge(g, k - 1, &n_min)) return rc;
+        if (int rc = launch_generic(g, k, 0, n_min, part, nparts, call.acc, &call.launches)) return rc;
     }
-    if (rc) return rc;
-    GMSX_HIP(hipEventRecord(c.ev[1], s));
-    GMSX_HIP(hipGetLastError());
-    unsigned long long host[kAccSlots * kAccStride];
-    GMSX_HIP(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipStreamSynchronize(s));
     unsigned long long total = 0;
-    for (int i = 0; i < kAccSlots; ++i) total += host[i * kAccStride];
+    float ms = 0.f;
+    if (int rc = call.end(c, &total, &ms)) return rc;
     *out = total;
     if (st) {
-        float ms = 0.f;
-        GMSX_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
         unsigned long long alg = 0;  // outside the timed region
         int64_t n_min = 0;
         if (g->rows_sorted && count_dplus_ge(g, std::max(k - 1, 1), &n_min) == GMSX_OK && n_min > 0) {
-            GMSX_HIP(hipMemsetAsync(acc, 0, 8, s));
+            GMSX_HIP(hipMemsetAsync(call.acc, 0, 8, s));
             const int cu = c.compute_units > 0 ? c.compute_units : 256;
             hipLaunchKernelGGL(k_stat_kc_bytes, dim3(unsigned(cu * 8)), dim3(256), 0, s, n_min, nparts, part, g->order, g->dplus, g->hoff, g->hadj, g->toff, g->tadj,
-                               g->dense_limit, g->kc_rel, g->kc_relt, (k == 4 && kc_tri_enabled()) ? ((kc_mfma_enabled() && kc_pool().base) ? 512 : kKcTriTop) : 1024, acc);
-            GMSX_HIP(hipMemcpyAsync(&alg, acc, 8, hipMemcpyDeviceToHost, s));
+                               g->dense_limit, g->kc_rel, g->kc_relt, slab_from, call.acc);
+            GMSX_HIP(hipMemcpyAsync(&alg, call.acc, 8, hipMemcpyDeviceToHost, s));
             GMSX_HIP(hipStreamSynchronize(s));
         }
-        *st = gmsx_stats{double(ms), setup_ms, uint64_t(part_count(0, g->n, nparts, part)), 0, 0, launches, 0, uint64_t(alg)};
+        *st = gmsx_stats{double(ms), setup_ms, uint64_t(part_count(0, g->n, nparts, part)), 0, 0, call.launches, 0, uint64_t(alg)};
     }
     return GMSX_OK;
 }
@@ -2743,29 +2455,16 @@ static int kclique_partial(const gmsx_graph *g, int k, int part, int nparts, uin
 // per-vertex counts through the k = 3 machinery (used by gmsx_tc_vertex_count2): vcounts is indexed by ORIGINAL vertex id
 int kclique_vertex_counts(const gmsx_graph *g, unsigned long long *d_counts, gmsx_stats *st) {
     Ctx &c = ctx();
-    hipStream_t s = c.stream;
-    DevBuf d_acc, slabs;  // (slabs: the global-slab bins of launch_all, freed when the call is over)
-    GMSX_HIP(hipMalloc(&d_acc.p, sizeof(unsigned long long) * kAccSlots * kAccStride));
-    unsigned long long *acc = d_acc.as<unsigned long long>();
     if (g->rows_sorted)
-        if (int rc0 = ensure_kc_reverse(g, 8192)) return rc0;
-    GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * kAccSlots * kAccStride, s));
-    GMSX_HIP(hipEventRecord(c.ev[0], s));
-    int launches = 0;
-    const int rc = launch_all<1, true>(g, 0, 1, acc, &launches, slabs, d_counts);
-    if (rc) return rc;
-    GMSX_HIP(hipEventRecord(c.ev[1], s));
-    GMSX_HIP(hipGetLastError());
-    unsigned long long host[kAccSlots * kAccStride];
-    GMSX_HIP(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
-    GMSX_HIP(hipStreamSynchronize(s));
-    if (st) {
-        unsigned long long total = 0;
-        for (int i = 0; i < kAccSlots; ++i) total += host[i * kAccStride];
-        float ms = 0.f;
-        GMSX_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
-        *st = gmsx_stats{double(ms), 0.0, uint64_t(g->n), total, 0, launches, 0};  // probes = triangles met
-    }
+        if (int rc0 = ensure_kc_reverse(g)) return rc0;
+    KcCall call;
+    if (int rc = call.begin(c)) return rc;
+    int slab_from = 0;
+    if (int rc = launch_all(g, 3, true, launch_bin<1, true>, 0, 1, call.acc, &call.launches, call.slabs, d_counts, &slab_from)) return rc;
+    unsigned long long total = 0;
+    float ms = 0.f;
+    if (int rc = call.end(c, &total, &ms)) return rc;
+    if (st) *st = gmsx_stats{double(ms), 0.0, uint64_t(g->n), total, 0, call.launches, 0};  // probes = triangles met
     return GMSX_OK;
 }
 

@@ -94,6 +94,11 @@ def test_options_api(capi):
     with pytest.raises(capi.GmsxError) as ei:
         capi.set_option("NO_SUCH_OPTION", 1)
     assert ei.value.status == capi.ERR_INVALID
+    for gone in ("KC_STREAM_BUILD", "KC_PIPE_ALL", "KC_REV_GW"):   # k-clique variants that were deleted together with their option
+        assert gone not in names
+        with pytest.raises(capi.GmsxError) as ei:
+            capi.set_option(gone, 1)
+        assert ei.value.status == capi.ERR_INVALID, gone
     with pytest.raises(capi.GmsxError):
         capi.set_option("BK_MAXC", "9" * 40)   # longer than a value may be
     with capi.options(BK_MAXC=64, KC_MAXD=8):

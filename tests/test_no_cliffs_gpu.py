@@ -39,10 +39,14 @@ def cliques_of(oracle, csr, k):
     return ordered // math.factorial(k)
 
 
-@pytest.mark.parametrize("a,ks", [(4200, (5, 6)), (8300, (3, 4))])
-def test_kclique_beyond_the_bit_matrix_width(gpu, oracle, a, ks):
+@pytest.mark.parametrize("a,eh,ks", [
+    pytest.param(4200, 3 * 4200, (5, 6), id="4200-ks0"), pytest.param(8300, 3 * 8300, (3, 4), id="8300-ks1"),
+    # a + 1 pivots of d+ = a in the (1024, 2048] and the (2048, 4096] slab bin over an H dense enough to hold 4- and 5-cliques (3 951 / 6 and
+    # 12 299 / 16 of them): the k >= 5 slab kernels held to a non-trivial count (with eh = 3 a, H has next to no 4-clique)
+    pytest.param(1500, 40 * 1500, (5, 6), id="1500-dense"), pytest.param(3000, 60 * 3000, (5, 6), id="3000-dense")])
+def test_kclique_beyond_the_bit_matrix_width(gpu, oracle, a, eh, ks):
     b = a + 1
-    csr, hcsr = kab_plus_h(gpu, oracle, a, b, 3 * a, seed=a)
+    csr, hcsr = kab_plus_h(gpu, oracle, a, b, eh, seed=a)
     g = gpu.DeviceGraph.from_csr(csr)
     assert g.max_out_degree >= a
     for k in ks:
