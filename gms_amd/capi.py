@@ -43,6 +43,7 @@ SYMBOLS = [
     "gmsx_coloring_jp", "gmsx_coloring_verify",
     "gmsx_edge_support", "gmsx_truss_decomposition",
     "gmsx_link_prediction", "gmsx_link_prediction_precision",
+    "gmsx_subgraph_order", "gmsx_subgraph_match",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
 
@@ -139,6 +140,57 @@ def merge_link_predictions(parts, q):
     return u[order], v[order], s[order]
 
 
+class SubgraphInfo(C.Structure):
+    _fields_ = [("embeddings", C.c_int64), ("tasks", C.c_int64), ("k", C.c_int32), ("reserved", C.c_int32), ("order", C.c_int32 * 32)]
+
+    def as_dict(self):
+        return {"embeddings": int(self.embeddings), "tasks": int(self.tasks), "k": int(self.k), "order": [int(x) for x in self.order[:max(int(self.k), 0)]]}
+
+
+SGM_INDUCED, SGM_MONO, SGM_FIRST = 0, 1, 2
+
+
+def pattern_arrays(pattern):
+    """(offsets int64[k + 1], neigh int32[nnz]) of a pattern given as a HostCSR, an (offsets, neigh) pair or an edge list (pairs; symmetrized,
+    k = the largest id + 1).  A pair of arrays is handed on as it is: the library validates it."""
+    if isinstance(pattern, HostCSR):
+        return np.array(pattern.offsets(), dtype=np.int64), np.array(pattern.neighbors(), dtype=np.int32)
+    # (two arrays that are not two edges: offsets of 2 entries are k = 1, whose neigh is empty)
+    if isinstance(pattern, tuple) and len(pattern) == 2 and np.ndim(pattern[0]) == 1 and np.ndim(pattern[1]) == 1 and \
+            not (len(pattern[0]) == 2 and len(pattern[1]) == 2):
+        return np.ascontiguousarray(pattern[0], dtype=np.int64), np.ascontiguousarray(pattern[1], dtype=np.int32)
+    e = np.asarray(pattern, dtype=np.int64).reshape(-1, 2)
+    k = int(e.max()) + 1 if e.size else 1
+    a = np.zeros((k, k), dtype=bool)
+    a[e[:, 0], e[:, 1]] = True
+    a[e[:, 1], e[:, 0]] = True
+    off = np.concatenate([[0], np.cumsum(a.sum(axis=1))]).astype(np.int64)
+    return off, np.nonzero(a)[1].astype(np.int32)
+
+
+def _pattern_args(pattern):
+    off, neigh = pattern_arrays(pattern)
+    return off, neigh, int(off.size - 1), off.ctypes.data_as(C.c_void_p), (neigh if neigh.size else np.zeros(1, np.int32)).ctypes.data_as(C.c_void_p)
+
+
+def subgraph_order(pattern):
+    """gmsx_subgraph_order: the matching order pi of a pattern (int32[k]); host only."""
+    off, neigh, k, po, pn = _pattern_args(pattern)
+    order = np.zeros(max(k, 1), dtype=np.int32)
+    _check(lib().gmsx_subgraph_order(k, po, pn, order.ctypes.data_as(C.c_void_p)), "gmsx_subgraph_order")
+    return order[:k]
+
+
+def merge_subgraph_matches(parts, order):
+    """The row-wise merge of the shard lists of one (graph, pattern, flags): rows by ascending (f(pi_0), .., f(pi_(k-1))), the whole list byte
+    for byte.  parts: (E_i, k) int32 arrays; order: the matching order pi."""
+    order = [int(x) for x in order]
+    rows = np.concatenate([np.asarray(p, dtype=np.int32).reshape(-1, len(order)) for p in parts]) if parts else np.zeros((0, len(order)), np.int32)
+    if rows.shape[0] == 0:
+        return rows
+    return np.ascontiguousarray(rows[np.lexsort([rows[:, p] for p in reversed(order)])])
+
+
 class GmsxError(RuntimeError):
     def __init__(self, status, what):
         self.status = status
@@ -229,6 +281,9 @@ def lib():
                                        C.POINTER(LinkPredictionInfo), sp]
     L.gmsx_link_prediction_precision.argtypes = [vp, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                  C.POINTER(C.c_double), C.POINTER(C.c_double), sp]
+    L.gmsx_subgraph_order.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gmsx_subgraph_match.argtypes = [vp, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                      C.POINTER(SubgraphInfo), sp]
     L.gmsx_comm_unique_id.argtypes = [C.c_char_p]
     L.gmsx_comm_init.argtypes = [C.c_int, C.c_int, C.c_char_p, vpp]
     L.gmsx_comm_allreduce_u64.argtypes = [vp, u64p]
@@ -793,6 +848,41 @@ class DeviceGraph:
                "gmsx_link_prediction_precision")
         r = {"true_positives": int(tp.value), "true_count": int(tc.value), "precision": float(pr.value), "recall": float(rc.value)}
         return (r, st.as_dict()) if stats else r
+
+    def subgraph_match_info(self, pattern, induced=True, first=False, part=0, nparts=1, stats=False):
+        """gmsx_subgraph_match with maps = NULL: {embeddings, tasks, k, order} of shard (part, nparts) — the count, or with first=True the
+        existence answer (embeddings 0 or 1)."""
+        off, neigh, k, po, pn = _pattern_args(pattern)
+        flags = (0 if induced else SGM_MONO) | (SGM_FIRST if first else 0)
+        info, st = SubgraphInfo(), Stats()
+        _check(lib().gmsx_subgraph_match(self._h, k, po, pn, flags, int(part), int(nparts), None, 0, C.byref(info), C.byref(st)),
+               "gmsx_subgraph_match (sizing)")
+        return (info.as_dict(), st.as_dict()) if stats else info.as_dict()
+
+    def subgraph_match(self, pattern, induced=True, first=False, part=0, nparts=1, stats=False):
+        """gmsx_subgraph_match: the embeddings of `pattern` (a HostCSR, an (offsets, neigh) pair or an edge list) in shard (part, nparts) as an
+        (E, k) int32 array — row i is embedding i, column p the image of pattern vertex p; rows ascending in the matching order.  induced=False:
+        GMSX_SGM_MONO.  first=True: GMSX_SGM_FIRST, one call, E is 0 or 1.  Otherwise the sizing call, then the fill into an array of exactly
+        that size."""
+        off, neigh, k, po, pn = _pattern_args(pattern)
+        flags = (0 if induced else SGM_MONO) | (SGM_FIRST if first else 0)
+        info, st = SubgraphInfo(), Stats()
+        sizing = None
+        if first:
+            ne = 1
+        else:
+            _check(lib().gmsx_subgraph_match(self._h, k, po, pn, flags, int(part), int(nparts), None, 0, C.byref(info), C.byref(st)),
+                   "gmsx_subgraph_match (sizing)")
+            sizing = st.as_dict()
+            ne = int(info.embeddings)
+        maps = np.zeros(max(ne * k, 1), dtype=np.int32)
+        _check(lib().gmsx_subgraph_match(self._h, k, po, pn, flags, int(part), int(nparts), maps.ctypes.data_as(C.c_void_p), ne, C.byref(info),
+                                         C.byref(st)), "gmsx_subgraph_match")
+        ne = int(info.embeddings)
+        maps = maps[:ne * k].reshape(ne, k)
+        if stats:
+            return maps, {"sizing": sizing, "fill": st.as_dict(), "info": info.as_dict()}
+        return maps
 
     def free(self):
         if getattr(self, "_h", None):

@@ -30,7 +30,15 @@
 // Added:  truss      the k-truss decomposition on the device (gmsx_truss_decomposition; no reference driver) with the usual trial loop: per trial "Trial Time",
 //                    "Max Truss", "Levels", "Rounds", "Triangles" and with -v "Verification" (the triangles against gmsx_tc_total), after the last trial the
 //                    trussness histogram ("truss k: edges"), then "Average Time".  Single GPU: not sharded (--gpus > 1 is refused).
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  sgi -p pattern-file=FILE [--mono] [--list FILE]   the reference's subgraph-isomorphism drivers (non_set_based/subgraphiso/vf2/sequential/
+//                    subgraphiso_vf2_sequential.cpp, its -p pattern-file of util/command_line.hpp:42) on the device (gmsx_subgraph_match): per trial the FIRST
+//                    embedding ("isomorphism: t:p ..." — target vertex : pattern vertex, by ascending target vertex, the pairs of Result::isomorphism — or the
+//                    reference's "No isomorphisms were found"), with -v "Verification" the way subgraphisomorphismVerification checks it
+//                    (util/subgraphiso_verification.hpp:11-78), then the "@@@" line.  Target and pattern are loaded WITHOUT relabelling: the reference's driver
+//                    builds both with Builder::MakeGraph and never relabels (subgraphiso_vf2_parallel.cpp:25-32), so its ids are the file's.  --mono: the
+//                    non-induced mode; --list writes every embedding (outside the timed trials), one row per line, column p = the image of pattern vertex p.
+//                    Not sharded (--gpus > 1 is refused).
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -65,6 +73,8 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     int64_t q = 0;     // lp -q N (0: m / 4)
     std::string order; // bk --order adg|deg|dgr: the preprocessing step in front of the search (default adg); color --order id|ff|lf|sl|adg (default id)
     double eps = 0.001; // color --eps: epsilon of --order adg
+    std::string pattern_file;  // sgi -p pattern-file=FILE
+    bool mono = false;         // sgi --mono
     int error = 0;
 };
 
@@ -101,6 +111,7 @@ Args parse(int argc, char **argv) {
         else if (f == "--metric") { if (!need(1)) break; a.metric = argv[++i]; }
         else if (f == "-q") { if (!need(1)) break; a.q = std::atoll(argv[++i]); if (a.q < 1) a.error = 100; }
         else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; }
+        else if (f == "--mono") a.mono = true;
         else if (f == "--eps") { if (!need(1)) break; a.eps = std::atof(argv[++i]); }
         else if (f == "--gpus") { if (!need(1)) break; a.gpus = std::atoi(argv[++i]); if (a.gpus < 1 || a.gpus > 64) a.error = 100; }
         else if (f == "--opt") {  // --opt NAME=VALUE -> gmsx_set_option (limits, kernel variants, diagnostics: include/gmsx.h); unknown names are refused
@@ -116,13 +127,15 @@ Args parse(int argc, char **argv) {
             const std::string kv = argv[++i];
             if (kv.rfind("clique-size=", 0) == 0) a.clique_size = std::atoi(kv.c_str() + 12);
             else if (kv.rfind("cs=", 0) == 0) a.clique_size = std::atoi(kv.c_str() + 3);
+            else if (kv.rfind("pattern-file=", 0) == 0) a.pattern_file = kv.substr(13);
             else a.error = 100;
         } else a.error = 100;
     }
     if (!a.error && a.file.empty() && a.gen.empty()) a.error = 101;  // cli/cli.h:131-133
     if (!a.error && !a.gen.empty() && a.gen != "kronecker" && a.gen != "uniform") a.error = 100;
-    if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
-    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss") && a.gpus > 1) a.error = 100;
+    if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp" && a.kernel != "sgi") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
+    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss" || a.kernel == "sgi") && a.gpus > 1) a.error = 100;
+    if (!a.error && ((a.kernel == "sgi") != !a.pattern_file.empty() || (a.mono && a.kernel != "sgi"))) a.error = 100;  // util/command_line.hpp:22: the pattern is required
     if (!a.error && a.kernel == "lp" && lp_metric(a.metric) < 0) a.error = 100;
     if (!a.error && !a.order.empty() && a.kernel != "bk" && a.kernel != "color") a.error = 100;  // only Bron–Kerbosch and the colouring have a preprocessing step
     if (!a.error && !a.order.empty() && a.kernel == "bk" && a.order != "adg" && a.order != "deg" && a.order != "dgr") a.error = 100;
@@ -134,9 +147,9 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
-                "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e]\n", argv0);
+                "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -431,12 +444,68 @@ int run_truss(const Args &args, const gmsx::HipSetGraph &g) {
     return 0;
 }
 
+// subgraph matching: the reference's VF2 drivers (subgraphiso_vf2_sequential.cpp:33-51) over gmsx::subgraph_isomorphisms
+int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
+    gmsx_csr *pc = nullptr;
+    const int rc = gmsx_csr_load(args.pattern_file.c_str(), 1, GMSX_RELABEL_NEVER, &pc);
+    if (rc != GMSX_OK) {
+        std::printf("could not load the pattern: %s\n", gmsx_strerror(rc));
+        return 2;
+    }
+    const int32_t k = int32_t(gmsx_csr_num_nodes(pc));
+    const int64_t *po = gmsx_csr_offsets(pc);
+    const int32_t *pn = gmsx_csr_neighbors(pc);
+    const uint32_t mode = args.mono ? GMSX_SGM_MONO : GMSX_SGM_INDUCED;
+    double total_seconds = 0;
+    Timer t;
+    for (int64_t it = 0; it < args.trials; ++it) {
+        t.Start();
+        const std::vector<int32_t> row = gmsx::subgraph_isomorphisms(g, k, po, pn, mode | GMSX_SGM_FIRST);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        if (row.empty()) {
+            std::cout << "No isomorphisms were found" << std::endl;
+        } else {  // Result::isomorphism: target vertex -> pattern vertex, in key order
+            std::vector<std::pair<int32_t, int32_t>> pairs;
+            for (int32_t p = 0; p < k; ++p) pairs.push_back({row[size_t(p)], p});
+            std::sort(pairs.begin(), pairs.end());
+            std::cout << "isomorphism:";
+            for (const auto &pr : pairs) std::cout << " " << pr.first << ":" << pr.second;
+            std::cout << std::endl;
+        }
+        if (args.verify) {  // subgraphisomorphismVerification: every pattern edge a mapped target edge, and (induced) nothing else among the images
+            bool ok = true;
+            for (int32_t a = 0; a < k && !row.empty(); ++a)
+                for (int32_t b = 0; b < k; ++b) {
+                    if (a == b) continue;
+                    const bool pe = std::binary_search(pn + po[a], pn + po[a + 1], b);
+                    const bool te = std::binary_search(hg.row(row[size_t(a)]), hg.row(row[size_t(a)]) + hg.deg(row[size_t(a)]), row[size_t(b)]);
+                    if (row[size_t(a)] == row[size_t(b)] || (pe && !te) || (!args.mono && te && !pe)) ok = false;
+                }
+            PrintLabel("Verification", ok ? "PASS" : "FAIL");
+        }
+        std::cout << "@@@ vf2 " << (args.mono ? "non-induced" : "induced") << std::endl;
+    }
+    if (!args.list.empty()) {  // outside the timed trials: every embedding
+        const std::vector<int32_t> rows = gmsx::subgraph_isomorphisms(g, k, po, pn, mode);
+        std::FILE *f = std::fopen(args.list.c_str(), "w");
+        if (!f) { std::printf("could not write %s\n", args.list.c_str()); gmsx_csr_free(pc); return 2; }
+        for (size_t i = 0; i < rows.size(); ++i) std::fprintf(f, "%d%c", rows[i], (i + 1) % size_t(k) == 0 ? '\n' : ' ');
+        std::fclose(f);
+        std::printf("wrote %zu embeddings to %s\n", rows.size() / size_t(k), args.list.c_str());
+    }
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    gmsx_csr_free(pc);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -455,8 +524,9 @@ int main(int argc, char **argv) {
     gmsx_csr *csr = nullptr;
     t.Start();
     int rc;
-    if (!args.file.empty()) rc = gmsx_csr_load(args.file.c_str(), 1, GMSX_RELABEL_AUTO, &csr);
-    else rc = gmsx_csr_generate(args.gen == "uniform" ? GMSX_GEN_UNIFORM : GMSX_GEN_KRONECKER, args.scale, args.deg, GMSX_RELABEL_AUTO,
+    const int relabel = args.kernel == "sgi" ? GMSX_RELABEL_NEVER : GMSX_RELABEL_AUTO;  // the reference's subgraph drivers never relabel
+    if (!args.file.empty()) rc = gmsx_csr_load(args.file.c_str(), 1, relabel, &csr);
+    else rc = gmsx_csr_generate(args.gen == "uniform" ? GMSX_GEN_UNIFORM : GMSX_GEN_KRONECKER, args.scale, args.deg, relabel,
                                 int(args.threads), &csr);
     t.Stop();
     if (rc != GMSX_OK) {
@@ -509,8 +579,8 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss") {
-        const int rc_run = args.kernel == "color" ? run_color(args, g) : run_truss(args, g);
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi") {
+        const int rc_run = args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : run_sgi(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);
         return rc_run;

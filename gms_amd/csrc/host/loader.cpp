@@ -784,6 +784,8 @@ Option g_options[] = {
     {"TRUSS_WG_FRONTIER", "", false},
     // link prediction (linkpred.hip)
     {"LP_LDS_MAXN", "", false}, {"LP_SLAB_MB", "", false},
+    // subgraph matching (subgraph.hip)
+    {"SGM_LAUNCH_TASKS", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

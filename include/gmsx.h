@@ -153,7 +153,9 @@ int gmsx_set_host_threads(int n);
  *                   round is a kernel boundary, which measured faster than the one-workgroup kernel at every size; test hook)
  *   link prediction        LP_LDS_MAXN (largest n whose per-source bitmaps live in LDS, default and maximum 131072 — a first guess; 0 = every
  *                   bitmap in the workgroup's global slab; test hook), LP_SLAB_MB (budget of the candidates of one chunk: smaller = more chunks;
- *                   test hook) */
+ *                   test hook)
+ *   subgraph matching      SGM_LAUNCH_TASKS (tasks per launch of gmsx_subgraph_match, default 2^24 for a listing and 2^16 with GMSX_SGM_FIRST —
+ *                   both first guesses, not tuned values; a small value splits a small graph into many launches; test hook) */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -594,6 +596,58 @@ int gmsx_link_prediction(const gmsx_graph *g, int metric /* GMSX_SIM_* */, int64
 int gmsx_link_prediction_precision(const gmsx_graph *g_test, int64_t n_pred, const int32_t *u, const int32_t *v,
                                    int64_t *true_positives, int64_t *true_count, double *precision, double *recall,
                                    gmsx_stats *stats);
+
+/* ---- subgraph matching: GMS::SubGraphIso::VF2 (non_set_based/subgraphiso/vf2/sequential/vf2.hpp:53-81 with the candidate rule of
+ * vf2/util/candidateGeneration.hpp:12-56 and the feasibility rules of vf2/util/feasibilityRules.hpp:48-92), and the enumeration the reference's
+ * drivers stop short of: EVERY embedding of a small connected pattern P into the uploaded graph G, as rows of one array.
+ * Pattern: a symmetric CSR over k vertices — int64 p_offsets[k + 1], int32 p_neigh[p_offsets[k]], rows strictly ascending, loop-free, the arc set
+ * equal to its transpose — validated on the host on every call: a violation (an id outside [0, k) included) → GMSX_ERR_NOT_CANONICAL.
+ * 1 <= k <= 32: k < 1 or a NULL array → GMSX_ERR_INVALID, k > 32 → GMSX_ERR_UNSUPPORTED.  The pattern must be connected; a disconnected one →
+ * GMSX_ERR_UNSUPPORTED (its candidate sets are not subsets of a row).  No vertex or edge labels.
+ * Embedding: an injective f : V(P) → V(G).  INDUCED (the default; what VF2 decides, feasibilityRules.hpp:48-92): {a, b} ∈ E(P) <=> {f(a), f(b)} ∈
+ * E(G).  GMSX_SGM_MONO: only => is required — the non-induced mode of the reference's verifier (util/subgraphiso_verification.hpp:11-78,
+ * isInducedIsomorphism = false).  Every embedding is listed, so one subgraph copy appears |Aut(P)| times; there is no symmetry breaking.
+ * Matching order pi: pi_0 = 0, pi_(i+1) = the smallest pattern vertex adjacent to {pi_0 .. pi_i}; every pi_i, i >= 1, has an earlier neighbour.
+ * It is the order the reference's candidate rule walks a connected pattern in; info->order and gmsx_subgraph_order (host only, no device needed;
+ * the same status codes as above) return it.
+ * Output: row i of `maps` (k ids) is embedding i, column p holds f(p) — indexed by pattern vertex id, not by position in pi; all ids are vertex
+ * ids of the uploaded CSR.  Rows are in ascending lexicographic order of (f(pi_0), f(pi_1), .., f(pi_(k-1))).  In INDUCED mode row 0 is the
+ * reference's sequential VF2 result (Result::isomorphism), element for element: its depth-first search takes the pattern vertices in the order
+ * pi and the target vertices ascending and stops at the first embedding it meets (vf2.hpp:53-81).  (The reference's parallel driver returns
+ * whichever embedding its tasks meet first; only its existence answer is a fact about the input.)  The same graph, pattern, flags and shard
+ * give byte-identical arrays in every process.
+ * Two calls, as gmsx_kclique_star_list:
+ *   sizing  maps == NULL: only *info is filled (info is required on every call); it always searches;
+ *   fill    capacity >= info.embeddings (in embeddings), else GMSX_ERR_INVALID with *info holding the need and nothing written.
+ * A fill call that follows the sizing call of the same handle, pattern (the arrays are compared in full), flags and shard re-uses its first
+ * pass.  The output is assembled on the device first: one that does not fit there returns GMSX_ERR_DEVICE_MEM and the caller uses more shards.
+ * GMSX_SGM_FIRST (combinable with MONO): the reference driver's question — is there one, and which.  One call, no sizing: info.embeddings is 0
+ * or 1; with maps != NULL capacity >= 1 is required and the one row written is row 0 of the full list; maps == NULL answers existence only.  The
+ * search stops early: a task that meets its first embedding records its task index by an atomic minimum and ends, every task quits once a lower
+ * task has recorded one, and the host launches ascending ranges of tasks and stops after the first launch that found one.  Timing decides only
+ * how much abandoned work is done, never the result.
+ * Shards: an embedding belongs to part shard_of(f(pi_0)) — the rule of gmsx_kclique_star_list applied to the vertex id of the first image.  The
+ * parts of one nparts are disjoint and their row-wise merge in the list order is the whole list; (0, 1) is the whole graph; other (part, nparts)
+ * → GMSX_ERR_INVALID.
+ * Width: the candidates of a level are computed 64 ids at a time straight from one row of the CSR and never stored, so no request is refused for
+ * the width of a neighbourhood.  Test hook: option SGM_LAUNCH_TASKS (tasks per launch; the defaults, 2^24 and 2^16 with FIRST, are first guesses,
+ * not tuned values).
+ * Errors: unknown flag bits, a NULL g or info, a negative capacity → GMSX_ERR_INVALID.  A fill that disagrees with its count pass, or an output
+ * bound → GMSX_ERR_KERNEL; nothing is written out of bounds and the caller's array is written only after the device flag word was read as zero.
+ * n = 0 or k > n: GMSX_OK with 0 embeddings.
+ * gmsx_stats: kernel_ms (the search passes), setup_ms (building the task list on the host), launches, units = tasks — the arcs (f(pi_0), f(pi_1))
+ * that pass the degree filters d(f(p)) >= deg_P(p); k = 1: the vertices. */
+enum { GMSX_SGM_INDUCED = 0, GMSX_SGM_MONO = 1, GMSX_SGM_FIRST = 2 };
+typedef struct {
+    int64_t embeddings;   /* of this call's shard; with FIRST: 0 or 1 */
+    int64_t tasks;
+    int32_t k, reserved;
+    int32_t order[32];    /* the matching order pi (pattern vertex ids), k entries, the rest -1 */
+} gmsx_subgraph_info;
+int gmsx_subgraph_order(int32_t k, const int64_t *p_offsets, const int32_t *p_neigh, int32_t *order /* k */);
+int gmsx_subgraph_match(const gmsx_graph *g, int32_t k, const int64_t *p_offsets, const int32_t *p_neigh, uint32_t flags, int part, int nparts,
+                        int32_t *maps /* k * capacity ids, row i = embedding i, host, or NULL */, int64_t capacity /* in embeddings */,
+                        gmsx_subgraph_info *info /* required */, gmsx_stats *stats);
 
 /* ---- the one collective of the path: the OpenMP reduction(+:total) of parallel/total.h:12,
  * k_clique_count_set_based.h:25 and the BK_CLIQUE_COUNTER atomic (tomita.h:76-77) across GPUs = ONE all-reduce of a u64 over

@@ -34,6 +34,8 @@
 //   gmsx::ktruss_edges(g, k)             -> gmsx_truss_decomposition (the u < v edges of the k-truss, a host-side filter)
 //   gmsx::link_prediction(g, metric, q)  -> gmsx_link_prediction   (set_based/link_prediction/link_prediction.h:42-101; the reference's padding reproduced)
 //   gmsx::link_prediction_precision(g_test, edges) -> gmsx_link_prediction_precision (set_based/link_prediction/evaluation.h:99-124)
+//   gmsx::subgraph_isomorphisms(g, pattern, flags) -> gmsx_subgraph_match (every embedding of a small connected pattern, induced or not; no reference driver lists them)
+//   gmsx::subgraph_isomorphism(g, pattern) -> gmsx_subgraph_match, GMSX_SGM_FIRST (non_set_based/subgraphiso/vf2/sequential/vf2.hpp:39-81: the one mapping, target -> pattern)
 // include/gmsx_gms_glue.hpp holds the explicit specialisations that route the reference's own function names to these
 // (INTEGRATION.md §2).  Header-only; link with -lgmsx.
 #pragma once
@@ -46,6 +48,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <map>
 #include <memory>
 #include <string>
 #include <type_traits>
@@ -839,6 +842,44 @@ inline LinkPredictionScore link_prediction_precision(const HipGraphT<S> &g_test,
                                                  &sc.recall, nullptr),
                   "gmsx_link_prediction_precision");
     return sc;
+}
+
+// Subgraph matching (gmsx_subgraph_match): every embedding of a small connected pattern, row i = embedding i, column p = the image of pattern
+// vertex p, E * k ids in the list order of gmsx.h.  The pattern is anything with num_nodes(), offsets() and neighbors() — a HipGraphT of any
+// flavour (only its host arrays are read) — or the raw arrays, which need no graph object at all.  flags: GMSX_SGM_*; with
+// GMSX_SGM_FIRST the one call of that mode (0 or 1 row).  *info (may be NULL): count, tasks and the matching order.
+template <class S>
+inline std::vector<int32_t> subgraph_isomorphisms(const HipGraphT<S> &g, int32_t k, const int64_t *p_offsets, const int32_t *p_neigh,
+                                                  uint32_t flags = GMSX_SGM_INDUCED, int part = 0, int nparts = 1, gmsx_subgraph_info *info = nullptr) {
+    gmsx_subgraph_info local{};
+    gmsx_subgraph_info &inf = info ? *info : local;
+    const int32_t none = 0;
+    if (!p_neigh) p_neigh = &none;  // (k = 1: an empty array)
+    if (flags & GMSX_SGM_FIRST) {
+        inf.embeddings = 1;
+    } else {
+        detail::check(gmsx_subgraph_match(g.device(), k, p_offsets, p_neigh, flags, part, nparts, nullptr, 0, &inf, nullptr), "gmsx_subgraph_match");
+    }
+    std::vector<int32_t> maps(size_t(inf.embeddings) * size_t(k > 0 ? k : 0) + 1);
+    detail::check(gmsx_subgraph_match(g.device(), k, p_offsets, p_neigh, flags, part, nparts, maps.data(), inf.embeddings, &inf, nullptr),
+                  "gmsx_subgraph_match");
+    maps.resize(size_t(inf.embeddings) * size_t(k));
+    return maps;
+}
+template <class S, class Pattern>
+inline std::vector<int32_t> subgraph_isomorphisms(const HipGraphT<S> &g, const Pattern &pattern, uint32_t flags = GMSX_SGM_INDUCED, int part = 0,
+                                                  int nparts = 1, gmsx_subgraph_info *info = nullptr) {
+    return subgraph_isomorphisms(g, int32_t(pattern.num_nodes()), pattern.offsets(), pattern.neighbors(), flags, part, nparts, info);
+}
+// GMS::SubGraphIso::VF2::run (non_set_based/subgraphiso/vf2/sequential/vf2.hpp:39-51) in the shape of its Result::isomorphism (util/result.hpp:15,
+// filled by State::SaveToResult, vf2/util/vf2State.hpp:153-156): key = target vertex, value = pattern vertex; empty if there is no induced
+// embedding.  The pairs are the reference's sequential result, element for element (GMSX_SGM_FIRST).
+template <class S, class Pattern>
+inline std::map<int, int> subgraph_isomorphism(const HipGraphT<S> &g, const Pattern &pattern, uint32_t flags = GMSX_SGM_INDUCED) {
+    const std::vector<int32_t> row = subgraph_isomorphisms(g, pattern, flags | GMSX_SGM_FIRST);
+    std::map<int, int> out;
+    for (size_t p = 0; p < row.size(); ++p) out[int(row[p])] = int(p);
+    return out;
 }
 
 }  // namespace gmsx
