@@ -44,6 +44,7 @@ SYMBOLS = [
     "gmsx_edge_support", "gmsx_truss_decomposition",
     "gmsx_link_prediction", "gmsx_link_prediction_precision",
     "gmsx_subgraph_order", "gmsx_subgraph_match",
+    "gmsx_connected_components", "gmsx_jarvis_patrick",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
 
@@ -124,6 +125,23 @@ class LinkPredictionInfo(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k in ("found", "scored", "positive", "chunks", "classes")}
+
+
+class ComponentsInfo(C.Structure):
+    _fields_ = [("components", C.c_int64), ("singletons", C.c_int64), ("largest", C.c_int64), ("kept_edges", C.c_int64),
+                ("largest_label", C.c_int32), ("passes", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("components", "singletons", "largest", "kept_edges", "largest_label", "passes")}
+
+
+def clusters(label):
+    """The vertex ids of every component of a label array (connected_components, jarvis_patrick): a list of ascending int32 arrays, ordered
+    by label."""
+    label = np.asarray(label)
+    order = np.argsort(label, kind="stable")
+    cuts = np.flatnonzero(np.diff(label[order])) + 1
+    return [part.astype(np.int32) for part in np.split(order, cuts)] if label.size else []
 
 
 LP_CLASS_ONE, LP_CLASS_POS, LP_CLASS_ZERO, LP_CLASS_ALL = 1, 2, 4, 8
@@ -284,6 +302,8 @@ def lib():
     L.gmsx_subgraph_order.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.gmsx_subgraph_match.argtypes = [vp, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                       C.POINTER(SubgraphInfo), sp]
+    L.gmsx_connected_components.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(ComponentsInfo), sp]
+    L.gmsx_jarvis_patrick.argtypes = [vp, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(ComponentsInfo), sp]
     L.gmsx_comm_unique_id.argtypes = [C.c_char_p]
     L.gmsx_comm_init.argtypes = [C.c_int, C.c_int, C.c_char_p, vpp]
     L.gmsx_comm_allreduce_u64.argtypes = [vp, u64p]
@@ -883,6 +903,37 @@ class DeviceGraph:
         if stats:
             return maps, {"sizing": sizing, "fill": st.as_dict(), "info": info.as_dict()}
         return maps
+
+    def connected_components(self, arc_keep=None, stats=False):
+        """gmsx_connected_components: (label int32[n] — the smallest vertex id of every vertex's component —, {components, singletons, largest,
+        kept_edges, largest_label, passes}).  arc_keep: nnz bytes parallel to the uploaded CSR's neigh; an edge is kept if either arc's byte is
+        non-zero; None = every edge."""
+        n, nnz = self.num_nodes, 2 * self.num_edges
+        keep = None
+        if arc_keep is not None:
+            keep = np.ascontiguousarray(arc_keep, dtype=np.uint8)
+            if keep.size != nnz:
+                raise GmsxError(ERR_INVALID, "gmsx_connected_components (arc_keep must have one byte per arc)")
+            if nnz == 0:
+                keep = np.zeros(1, dtype=np.uint8)
+        label, info, st = np.zeros(max(n, 1), dtype=np.int32), ComponentsInfo(), Stats()
+        _check(lib().gmsx_connected_components(self._h, keep.ctypes.data_as(C.c_void_p) if keep is not None else None,
+                                               label.ctypes.data_as(C.c_void_p), C.byref(info), C.byref(st)), "gmsx_connected_components")
+        r = (label[:n], info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def jarvis_patrick(self, metric, threshold, want_mask=False, stats=False):
+        """gmsx_jarvis_patrick: (label, info) of the components over the edges whose endpoints score >= threshold under `metric` (a GMSX_SIM_*
+        value or a name of SIM / SIM_METRICS); with want_mask=True (label, info, mask uint8[nnz]), the kept arcs."""
+        if isinstance(metric, str):
+            metric = self.SIM[metric] if metric in self.SIM else SIM_METRICS[metric]
+        n, nnz = self.num_nodes, 2 * self.num_edges
+        label, info, st = np.zeros(max(n, 1), dtype=np.int32), ComponentsInfo(), Stats()
+        mask = np.zeros(max(nnz, 1), dtype=np.uint8) if want_mask else None
+        _check(lib().gmsx_jarvis_patrick(self._h, int(metric), float(threshold), label.ctypes.data_as(C.c_void_p),
+                                         mask.ctypes.data_as(C.c_void_p) if want_mask else None, C.byref(info), C.byref(st)), "gmsx_jarvis_patrick")
+        r = (label[:n], info.as_dict()) + ((mask[:nnz],) if want_mask else ())
+        return (r + (st.as_dict(),)) if stats else r
 
     def free(self):
         if getattr(self, "_h", None):

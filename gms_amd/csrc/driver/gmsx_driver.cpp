@@ -38,7 +38,14 @@
 //                    builds both with Builder::MakeGraph and never relabels (subgraphiso_vf2_parallel.cpp:25-32), so its ids are the file's.  --mono: the
 //                    non-induced mode; --list writes every embedding (outside the timed trials), one row per line, column p = the image of pattern vertex p.
 //                    Not sharded (--gpus > 1 is refused).
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  cc         the reference's connected-components driver (representations/graphs/log_graph/cc.cc:141-149: ShiloachVishkin, PrintCompStats, CCVerifier) on the
+//                    device (gmsx_connected_components) with the usual trial loop: per trial "Trial Time", "Components" and with -v "Verification" — this driver's
+//                    own BFS per label over the host CSR, the way CCVerifier checks (cc.cc:98-138), which also holds every label to the smallest id of its
+//                    component —, then the "@@@" line; after the last trial PrintCompStats' facts (cc.cc:75-91): the five largest components as label:size
+//                    and the number of components.  A component is global: not sharded (--gpus > 1 is refused).
+// Added:  jp --metric NAME --threshold X   Jarvis–Patrick clustering on the device (gmsx_jarvis_patrick; no reference driver; NAME as for lp): the same
+//                    loop and output plus "Kept Edges"; -v runs the BFS over the kept arcs the call returns and checks that they are symmetric.
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -46,6 +53,7 @@
 #include <algorithm>
 #include <cerrno>
 #include <chrono>
+#include <cmath>
 #include <csignal>
 #include <cinttypes>
 #include <cstdio>
@@ -75,6 +83,7 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     double eps = 0.001; // color --eps: epsilon of --order adg
     std::string pattern_file;  // sgi -p pattern-file=FILE
     bool mono = false;         // sgi --mono
+    double threshold = std::nan("");  // jp --threshold X
     int error = 0;
 };
 
@@ -112,6 +121,7 @@ Args parse(int argc, char **argv) {
         else if (f == "-q") { if (!need(1)) break; a.q = std::atoll(argv[++i]); if (a.q < 1) a.error = 100; }
         else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; }
         else if (f == "--mono") a.mono = true;
+        else if (f == "--threshold") { if (!need(1)) break; a.threshold = std::atof(argv[++i]); }
         else if (f == "--eps") { if (!need(1)) break; a.eps = std::atof(argv[++i]); }
         else if (f == "--gpus") { if (!need(1)) break; a.gpus = std::atoi(argv[++i]); if (a.gpus < 1 || a.gpus > 64) a.error = 100; }
         else if (f == "--opt") {  // --opt NAME=VALUE -> gmsx_set_option (limits, kernel variants, diagnostics: include/gmsx.h); unknown names are refused
@@ -134,9 +144,10 @@ Args parse(int argc, char **argv) {
     if (!a.error && a.file.empty() && a.gen.empty()) a.error = 101;  // cli/cli.h:131-133
     if (!a.error && !a.gen.empty() && a.gen != "kronecker" && a.gen != "uniform") a.error = 100;
     if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp" && a.kernel != "sgi") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
-    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss" || a.kernel == "sgi") && a.gpus > 1) a.error = 100;
+    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss" || a.kernel == "sgi" || a.kernel == "cc" || a.kernel == "jp") && a.gpus > 1) a.error = 100;
+    if (!a.error && ((a.kernel == "jp") != !std::isnan(a.threshold))) a.error = 100;  // the threshold is required, and only there
     if (!a.error && ((a.kernel == "sgi") != !a.pattern_file.empty() || (a.mono && a.kernel != "sgi"))) a.error = 100;  // util/command_line.hpp:22: the pattern is required
-    if (!a.error && a.kernel == "lp" && lp_metric(a.metric) < 0) a.error = 100;
+    if (!a.error && (a.kernel == "lp" || a.kernel == "jp") && lp_metric(a.metric) < 0) a.error = 100;
     if (!a.error && !a.order.empty() && a.kernel != "bk" && a.kernel != "color") a.error = 100;  // only Bron–Kerbosch and the colouring have a preprocessing step
     if (!a.error && !a.order.empty() && a.kernel == "bk" && a.order != "adg" && a.order != "deg" && a.order != "dgr") a.error = 100;
     if (!a.error && a.kernel == "color") {
@@ -147,9 +158,10 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
-                "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE]\n", argv0);
+                "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE] "
+                "[jp: --metric NAME --threshold X]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -444,6 +456,85 @@ int run_truss(const Args &args, const gmsx::HipSetGraph &g) {
     return 0;
 }
 
+// CCVerifier's check (cc.cc:98-138) as this driver's own loop: a BFS over the kept arcs (keep == nullptr: all) from the first unvisited vertex,
+// which must carry its own id as label; everything it reaches must carry that label too.  Holds the labels to the smallest id of every component.
+bool verify_components(const HostGraph &hg, const std::vector<int32_t> &comp, const uint8_t *keep) {
+    if (int64_t(comp.size()) != hg.n) return false;
+    std::vector<char> visited(size_t(hg.n), 0);
+    std::vector<int32_t> frontier;
+    frontier.reserve(size_t(hg.n));
+    if (keep)  // an edge is kept if either arc is: the output of gmsx_jarvis_patrick marks both
+        for (int64_t u = 0; u < hg.n; ++u)
+            for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j) {
+                const int32_t v = hg.adj[j];
+                const int32_t *b = hg.adj + hg.off[v], *e = hg.adj + hg.off[v + 1], *p = std::lower_bound(b, e, int32_t(u));
+                if (p == e || *p != u || (keep[j] != 0) != (keep[p - hg.adj] != 0)) return false;
+            }
+    for (int64_t s = 0; s < hg.n; ++s) {
+        if (visited[size_t(s)]) continue;
+        if (comp[size_t(s)] != s) return false;
+        frontier.clear();
+        frontier.push_back(int32_t(s));
+        visited[size_t(s)] = 1;
+        for (size_t at = 0; at < frontier.size(); ++at) {
+            const int32_t u = frontier[at];
+            for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j) {
+                if (keep && !keep[j]) continue;
+                const int32_t v = hg.adj[j];
+                if (comp[size_t(v)] != s) return false;
+                if (!visited[size_t(v)]) {
+                    visited[size_t(v)] = 1;
+                    frontier.push_back(v);
+                }
+            }
+        }
+    }
+    return true;
+}
+
+// connected components (cc) and Jarvis–Patrick clustering (jp) under the usual trial loop, with PrintCompStats' facts (cc.cc:75-91) at the end
+int run_components(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
+    const bool jp = args.kernel == "jp";
+    double total_seconds = 0;
+    Timer t;
+    std::vector<int32_t> comp(size_t(hg.n) + 1);
+    std::vector<uint8_t> keep;
+    if (jp && args.verify) keep.resize(size_t(hg.off[hg.n]) + 1);
+    gmsx_components_info info{};
+    for (int64_t it = 0; it < args.trials; ++it) {
+        t.Start();
+        if (jp)
+            gmsx::detail::check(gmsx_jarvis_patrick(g.device(), lp_metric(args.metric), args.threshold, comp.data(), keep.empty() ? nullptr : keep.data(), &info, nullptr),
+                                "gmsx_jarvis_patrick");
+        else gmsx::detail::check(gmsx_connected_components(g.device(), nullptr, comp.data(), &info, nullptr), "gmsx_connected_components");
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        PrintLabel("Components", std::to_string(info.components));
+        if (jp) PrintLabel("Kept Edges", std::to_string(info.kept_edges));
+        if (args.verify) {
+            std::vector<int32_t> labels(comp.begin(), comp.begin() + hg.n);
+            PrintLabel("Verification", verify_components(hg, labels, keep.empty() ? nullptr : keep.data()) ? "PASS" : "FAIL");
+        }
+        if (jp) std::cout << "@@@ jarvis-patrick " << args.metric << " " << args.threshold << std::endl;
+        else std::cout << "@@@ connected components" << std::endl;
+    }
+    if (args.trials > 0) {
+        std::vector<int64_t> size(size_t(hg.n) + 1, 0);
+        for (int64_t v = 0; v < hg.n; ++v) ++size[size_t(comp[size_t(v)])];
+        std::vector<std::pair<int64_t, int32_t>> top;  // (-size, label): ascending = largest first, ties by the smaller label
+        for (int64_t v = 0; v < hg.n; ++v)
+            if (size[size_t(v)]) top.emplace_back(-size[size_t(v)], int32_t(v));
+        const size_t k = std::min<size_t>(5, top.size());
+        std::partial_sort(top.begin(), top.begin() + k, top.end());
+        std::cout << std::endl << k << " biggest clusters" << std::endl;
+        for (size_t i = 0; i < k; ++i) std::cout << top[i].second << ":" << -top[i].first << std::endl;
+        std::cout << "There are " << top.size() << " components" << std::endl;
+    }
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
 // subgraph matching: the reference's VF2 drivers (subgraphiso_vf2_sequential.cpp:33-51) over gmsx::subgraph_isomorphisms
 int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
     gmsx_csr *pc = nullptr;
@@ -505,7 +596,7 @@ int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -579,8 +670,9 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi") {
-        const int rc_run = args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : run_sgi(args, g, hg);
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp") {
+        const int rc_run = args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
+                                                                                                                                        : run_components(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);
         return rc_run;

@@ -1,0 +1,543 @@
+// Connected components and Jarvis–Patrick clustering on gfx950: one device union-find over the vertices of the uploaded CSR.
+//   gmsx_connected_components   label[v] = smallest vertex id of v's component, over every edge or over the arcs a caller's byte mask keeps
+//                               (the reference's ShiloachVishkin, representations/graphs/log_graph/cc.cc:40-72, converges to the same labels)
+//   gmsx_jarvis_patrick         the same over the edges {u, v} with metric(N(u), N(v)) >= threshold; no reference counterpart
+// The definitions are those of include/gmsx.h.
+//
+// THE UNION-FIND.  parent[n] (int32, a DevBuf of the call; the handle is not touched), parent[v] = v at the start.  THE ONE RULE: a root is
+// only ever hooked under a SMALLER vertex id — link(u, v) walks to both roots and, where they differ, does atomicCAS(&parent[larger], larger,
+// smaller) at device scope; when the CAS fails (the larger root was hooked meanwhile) it walks again from the two roots it held.  So
+//   - parents only decrease, and every value parent[x] ever holds is an ancestor-or-self of x in every later state (a stale read is still an
+//     ancestor: correctness never depends on freshness);
+//   - the root of a finished tree is the smallest id of its component;
+//   - after a full flatten label[v] is the smallest vertex id of v's component: a fact about the edge set, independent of the arrival order of
+//     the atomics.
+// MEMORY MODEL.  The L2s of the eight XCDs are not coherent for plain loads inside one kernel, and a plain load may be served from a CU's L1 for
+// good.  Every read of parent inside a walk or a retry loop is a relaxed agent-scope atomic load (load_now), every compression write an
+// atomicMin (linking kernels, where other threads hook and compress the same word) or a relaxed agent-scope store (flatten kernels, where a
+// word has one writer).  No loop spins on a cached value, and NO LOOP IS UNBOUNDED: a walk strictly descends, so it takes fewer than n steps; a
+// retry follows a failed CAS, i.e. a root that stopped being one, which happens fewer than n times to the roots one link holds.  Both loops
+// carry the cap n + 64, and exceeding it (memory that is not a parent array any more) raises the call's flag word: GMSX_ERR_KERNEL.
+//
+// WORK DISTRIBUTION over CSR rows (k_cc_link, one template over the edge source and the lanes per row): one lane per row below kCcShortRow
+// entries, a 16-lane group per row below CC_WAVE_ROW, a wave per row below CC_WG_ROW, a whole workgroup per row from there on (a hub of 10^5 to
+// 10^6 entries is not one wave's job).  The three upper bins are vertex lists a classify kernel fills once per call (their order is the arrival
+// order of atomics and reaches no output).  The bin edges are options and first guesses, not tuned values.
+//
+// THE GIANT COMPONENT (Afforest's sampling; whole-graph call only).  Pass A links the first CC_SAMPLE neighbours of every vertex, a flatten
+// follows, one workgroup reads the labels of 1024 seeded vertex ids and picks the most frequent label L (ties: the smaller), and pass B links the
+// remaining neighbours of every vertex whose label is not L: the CSR is symmetric, so an edge from inside L to outside L is seen from its outside
+// endpoint.  L changes how much work is skipped, never the result.  With an arc mask the kept arcs need not be visible from both sides, so pass
+// B covers every vertex; Jarvis–Patrick is one pass over the edges.
+//
+// JARVIS–PATRICK (k_cc_jp).  Wave w of W takes the arcs w, w + W, w + 2 W, … — consecutive arcs of a hub's row, the dear ones, go to different
+// waves, as the pairs of gmsx_vertex_similarity_batch do — 64 at a time: lane t finds the source of its arc by a binary search in off, then the
+// wave works through the `u < v` arcs among them one after the other.  Such an arc is one wave_pair_similarity (pair_similarity.hpp, unchanged: the bits of
+// gmsx_vertex_similarity_batch); score >= threshold (false for NaN) marks the arc for the lane that resolved it, and after the 64 arcs every lane
+// links the endpoints of its own kept arc (up to 64 walks overlap instead of queueing on lane 0) and, where the caller asked for the mask,
+// writes 1 to both arcs' bytes — the twin by a binary search of u in row v.  No score array and no edge list exist.  Every edge gets one wave:
+// the workgroup-per-long-edge variant of truss.hip's support pass is not built here.
+//
+// FLATTEN (k_cc_flatten): every vertex walks up to kCcJump steps and stores where it got; a round in which every walk reached a root changes
+// nothing afterwards.  The host reads the flag between launches (a path of 2^20 vertices hooked into one chain needs four rounds).
+// INFO (k_cc_sizes, k_cc_info): size[label[v]] by atomicAdd, one add per distinct label of a wave (in the giant component that is one add per
+// wave); then per root: components, singletons, and the largest component as the maximum of size << 32 | ~label, i.e. ties go to the smaller label.
+#include "device_buffer.hpp"
+#include "device_graph.hpp"
+#include "frontier_rounds.hpp"  // load_now, store_now, wave_append, kGroup
+#include "pair_similarity.hpp"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+namespace gmsx {
+
+namespace {
+
+constexpr int kCcShortRow = 16;    // rows below this: one lane
+constexpr int kCcJump = 64;        // steps of one flatten walk
+constexpr int kCcSamples = 1024;   // vertex ids the giant-component vote reads
+constexpr int kCcFlattenMax = 64;  // flatten rounds before the call gives up (every round divides the depth by kCcJump)
+constexpr long long kCcSampleDefault = 2, kCcWaveRowDefault = 256, kCcWgRowDefault = 4096;  // first guesses (gmsx.h, OPTIONS)
+
+// the call's small device block, zeroed per call and read once
+struct CcAcc {
+    int32_t error;   // the flag word: a cap was exceeded, an append hit its bound, an arc has no twin
+    int32_t again;   // flatten: a walk ended below its root
+    int32_t giant;   // the label pass B skips, -1 = none
+    int32_t nlist[3];  // vertices in the group / wave / workgroup list
+    int32_t pad[2];
+    unsigned long long examined;  // arcs the linking kernels looked at (Jarvis–Patrick: edges scored)
+    unsigned long long kept;      // undirected edges the components are taken over
+    unsigned long long comps, singles;
+    unsigned long long best;      // size << 32 | ~label of the largest component
+};
+
+// root of x; compresses by halving on the way (atomicMin: other threads hook and compress the same words, and parents only decrease)
+__device__ __forceinline__ int32_t cc_find(int32_t *__restrict__ parent, int32_t x, uint32_t cap, int32_t *error) {
+    int32_t p = load_now(&parent[x]);
+    for (uint32_t it = 0; p != x; ++it) {
+        if (it > cap) {
+            *error = 1;
+            return x;
+        }
+        const int32_t gp = load_now(&parent[p]);
+        if (gp != p) atomicMin(&parent[x], gp);
+        x = p;
+        p = gp;
+    }
+    return x;
+}
+
+// the one rule: the larger root goes under the smaller one, or the walk starts again from the two roots just read
+__device__ __forceinline__ void cc_link(int32_t *__restrict__ parent, int32_t u, int32_t v, uint32_t cap, int32_t *error) {
+    int32_t ru = cc_find(parent, u, cap, error), rv = cc_find(parent, v, cap, error);
+    for (uint32_t it = 0; ru != rv; ++it) {
+        if (it > cap) {
+            *error = 1;
+            return;
+        }
+        const int32_t hi = max(ru, rv), lo = min(ru, rv);
+        if (atomicCAS(&parent[hi], hi, lo) == hi) return;
+        ru = cc_find(parent, hi, cap, error);
+        rv = cc_find(parent, lo, cap, error);
+    }
+}
+
+// edge sources of the row kernels
+struct SrcAll {
+    __device__ __forceinline__ bool keep(int64_t) const { return true; }
+};
+struct SrcMask {
+    const uint8_t *mask;
+    __device__ __forceinline__ bool keep(int64_t j) const { return mask[j] != 0; }
+};
+
+__global__ void k_cc_init(int64_t n, int32_t *__restrict__ parent, int32_t *__restrict__ size) {
+    const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (v < n) {
+        parent[v] = int32_t(v);
+        size[v] = 0;
+    }
+}
+
+// the three lists of the rows that get more than a lane (whole waves stay converged for the ballots)
+__global__ __launch_bounds__(256) void k_cc_classify(int64_t n, const int64_t *__restrict__ off, int64_t short_row, int64_t wave_row, int64_t wg_row,
+                                                     int32_t *__restrict__ lg, int32_t *__restrict__ lw, int32_t *__restrict__ lb, int64_t cap_g,
+                                                     int64_t cap_w, int64_t cap_b, CcAcc *__restrict__ acc) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    const int64_t end = ((n + 63) / 64) * 64;
+    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride) {
+        const int64_t d = v < n ? off[v + 1] - off[v] : -1;
+        wave_append(d >= short_row && d < wave_row, int32_t(v), lg, &acc->nlist[0], cap_g, &acc->error);
+        wave_append(d >= wave_row && d < wg_row, int32_t(v), lw, &acc->nlist[1], cap_w, &acc->error);
+        wave_append(d >= wg_row, int32_t(v), lb, &acc->nlist[2], cap_b, &acc->error);
+    }
+}
+
+// Links the arcs at positions [lo, min(degree, hi)) of its rows that the source keeps: WIDTH lanes per row.  list == nullptr: the rows are the
+// vertices 0 .. n - 1 whose degree is below dmax; else list[0 .. *count).  A row whose label is `giant` (acc->giant when use_giant) is skipped.
+template <class Src, int WIDTH>
+__global__ __launch_bounds__(256) void k_cc_link(Src src, int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                 const int32_t *__restrict__ list, int which, int64_t list_cap, int64_t dmax, int64_t lo, int64_t hi,
+                                                 int use_giant, int32_t *__restrict__ parent, CcAcc *__restrict__ acc) {
+    const int lane = threadIdx.x & (WIDTH - 1);
+    const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
+    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
+    const int64_t rows = list ? min(int64_t(acc->nlist[which]), list_cap) : n;
+    const int32_t giant = use_giant ? acc->giant : -1;
+    const uint32_t cap = uint32_t(min(n + 64, int64_t(INT_MAX)));
+    unsigned long long examined = 0;
+    for (int64_t i = row0; i < rows; i += rows_step) {
+        const int32_t v = list ? list[i] : int32_t(i);
+        const int64_t j0 = off[v], d = off[v + 1] - j0;
+        if (d >= dmax || d <= lo) continue;
+        if (giant >= 0 && load_now(&parent[v]) == giant) continue;
+        const int64_t j1 = j0 + min(d, hi);
+        for (int64_t j = j0 + lo + lane; j < j1; j += WIDTH) {
+            ++examined;
+            if (src.keep(j)) cc_link(parent, v, adj[j], cap, &acc->error);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) examined += __shfl_down(examined, o);
+    if ((threadIdx.x & 63) == 0 && examined) atomicAdd(&acc->examined, examined);
+}
+
+// position of x in the ascending row [lo, hi) of adj, or -1
+__device__ __forceinline__ int64_t cc_find_in_row(const int32_t *__restrict__ adj, int64_t lo, int64_t hi, int32_t x) {
+    const int64_t end = hi;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (adj[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return (lo < end && adj[lo] == x) ? lo : -1;
+}
+
+// Jarvis–Patrick: wave w takes the arcs w, w + W, …, 64 at a time (a lane resolves the source of each); one score per `u < v` arc, the kept
+// ones linked (and marked on both arcs when mask != nullptr).  amdgpu_waves_per_eu(8, 8): the score loop is latency-bound and lives on resident
+// waves; left alone the compiler takes 69 VGPRs = 7 waves per SIMD, held to 8 it takes 64 and spills nothing.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cc_jp(int64_t n, int64_t nnz, const int64_t *__restrict__ off,
+                                                                                          const int32_t *__restrict__ adj, int metric, double threshold,
+                                                                                          int32_t *__restrict__ parent, uint8_t *__restrict__ mask,
+                                                                                          CcAcc *__restrict__ acc) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave0 = uni64((int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6);
+    const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
+    const uint32_t cap = uint32_t(min(n + 64, int64_t(INT_MAX)));
+    unsigned long long scored = 0, kept = 0;  // (lane 0's are the wave's)
+    for (int64_t k0 = 0; wave0 + k0 * nwaves < nnz; k0 += 64) {
+        // lane t resolves arc wave0 + (k0 + t) nwaves: its source is the last u with off[u] <= j (off[n] = nnz > j, so u <= n - 1)
+        const int64_t mine = wave0 + (k0 + lane) * nwaves;
+        int32_t mu = -1, mv = -1;
+        if (mine < nnz) {
+            int64_t lo = 0, hi = n - 1;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi + 1) >> 1;
+                if (off[mid] <= mine) lo = mid;
+                else hi = mid - 1;
+            }
+            mv = adj[mine];
+            if (int64_t(mv) > lo) mu = int32_t(lo);  // the edge is taken from its endpoint of the smaller id
+        }
+        // … the wave scores the `u < v` arcs among them one after the other …
+        bool keep = false;
+        for (unsigned long long todo = __ballot(mu >= 0); todo; todo &= todo - 1) {
+            const int t = __ffsll((long long)todo) - 1;
+            // (left in vector registers, as the pair batch has them: pinned to scalar registers — row bounds by scalar loads — the same
+            // kernel measured 14 % slower)
+            const int32_t u = __shfl(mu, t), v = __shfl(mv, t);
+            const double score = wave_pair_similarity(off, adj, metric, u, v, lane);
+            ++scored;
+            if (score >= threshold && lane == t) keep = true;  // (a NaN score is never kept)
+        }
+        // … and every lane links the endpoints of its own arc, if that was kept: the walks of up to 64 links overlap instead of queueing on one lane
+        kept += (unsigned long long)__popcll(__ballot(keep));
+        if (keep) {
+            cc_link(parent, mu, mv, cap, &acc->error);
+            if (mask) {
+                const int64_t twin = cc_find_in_row(adj, off[mv], off[mv + 1], mu);
+                if (twin < 0) acc->error = 1;
+                else {
+                    mask[mine] = 1;
+                    mask[twin] = 1;
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        if (scored) atomicAdd(&acc->examined, scored);
+        if (kept) atomicAdd(&acc->kept, kept);
+    }
+}
+
+// kept edges of a caller's mask, each once: a `u < v` arc with its byte set, or a `u > v` arc with its byte set whose twin's byte is zero.
+// A kGroup-lane group per row.
+__global__ __launch_bounds__(256) void k_cc_mask_edges(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                       const uint8_t *__restrict__ mask, CcAcc *__restrict__ acc) {
+    const int lane = threadIdx.x & (kGroup - 1);
+    const int64_t group0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / kGroup;
+    const int64_t groups = (int64_t(gridDim.x) * blockDim.x) / kGroup;
+    unsigned long long kept = 0;
+    for (int64_t u = group0; u < n; u += groups)
+        for (int64_t j = off[u] + lane; j < off[u + 1]; j += kGroup) {
+            if (!mask[j]) continue;
+            const int32_t v = adj[j];
+            if (int64_t(v) > u) {
+                ++kept;
+            } else {
+                const int64_t twin = cc_find_in_row(adj, off[v], off[v + 1], int32_t(u));
+                if (twin < 0) acc->error = 1;
+                else if (!mask[twin]) ++kept;
+            }
+        }
+    for (int o = 32; o > 0; o >>= 1) kept += __shfl_down(kept, o);
+    if ((threadIdx.x & 63) == 0 && kept) atomicAdd(&acc->kept, kept);
+}
+
+// one flatten round: parent[v] = where a walk of at most kCcJump steps got; acc->again when one ended below its root.  Nothing hooks while
+// this runs and parent[v] has one writer, so the roots are fixed and a relaxed agent-scope store is enough.
+__global__ __launch_bounds__(256) void k_cc_flatten(int64_t n, int32_t *__restrict__ parent, CcAcc *__restrict__ acc) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    bool again = false;
+    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < n; v += stride) {
+        const int32_t p0 = load_now(&parent[v]);
+        int32_t x = p0, p = load_now(&parent[x]);
+        for (int it = 0; p != x && it < kCcJump; ++it) {
+            x = p;
+            p = load_now(&parent[x]);
+        }
+        if (p != x) again = true;
+        if (x != p0) store_now(&parent[v], x);
+    }
+    if (__ballot(again) && (threadIdx.x & 63) == 0) store_now(&acc->again, 1);
+}
+
+// the giant-component vote: the labels of kCcSamples seeded vertex ids, the most frequent one (ties: the smaller label) into acc->giant.
+// One workgroup of kCcSamples threads; 4 KB + 128 B of LDS.
+__global__ __launch_bounds__(kCcSamples) void k_cc_vote(int64_t n, const int32_t *__restrict__ parent, CcAcc *__restrict__ acc) {
+    __shared__ int32_t s_label[kCcSamples];
+    __shared__ unsigned long long s_best[kCcSamples / 64];
+    const int t = threadIdx.x;
+    unsigned long long h = (unsigned long long)(t + 1) * 0x9E3779B97F4A7C15ull;  // the seeded set: a fixed hash of the slot
+    h ^= h >> 29;
+    h *= 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 32;
+    const int32_t mine = parent[int64_t(h % (unsigned long long)n)];
+    s_label[t] = mine;
+    __syncthreads();
+    uint32_t c = 0;
+    for (int i = 0; i < kCcSamples; ++i) c += s_label[i] == mine;
+    unsigned long long key = ((unsigned long long)c << 32) | (0xffffffffu - uint32_t(mine));
+    for (int o = 32; o > 0; o >>= 1) key = max(key, __shfl_down(key, o));
+    if ((t & 63) == 0) s_best[t >> 6] = key;
+    __syncthreads();
+    if (t == 0) {
+        for (int i = 1; i < kCcSamples / 64; ++i) key = max(key, s_best[i]);
+        acc->giant = int32_t(0xffffffffu - uint32_t(key));
+    }
+}
+
+// size[label[v]] += 1, one add per distinct label of a wave
+__global__ __launch_bounds__(256) void k_cc_sizes(int64_t n, const int32_t *__restrict__ label, int32_t *__restrict__ size) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    const int64_t end = ((n + 63) / 64) * 64;
+    const int lane = threadIdx.x & 63;
+    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride) {
+        const int32_t l = v < n ? label[v] : -1;
+        unsigned long long todo = __ballot(l >= 0);
+        while (todo) {  // at most 64 turns: every turn retires the lanes of one label
+            const int first = __ffsll((long long)todo) - 1;
+            const int32_t l0 = __shfl(l, first);
+            const unsigned long long same = __ballot(l == l0) & todo;
+            if (lane == first) atomicAdd(&size[l0], int32_t(__popcll(same)));
+            todo &= ~same;
+        }
+    }
+}
+
+// per root: components, singletons, the largest component (ties: the smaller label).  A label that is no root raises the flag.
+__global__ __launch_bounds__(256) void k_cc_info(int64_t n, const int32_t *__restrict__ label, const int32_t *__restrict__ size, CcAcc *__restrict__ acc) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    unsigned long long comps = 0, singles = 0, best = 0;
+    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < n; v += stride) {
+        const int32_t l = label[v];
+        if (l < 0 || l > v || label[l] != l) acc->error = 1;
+        if (l != v) continue;
+        const uint32_t s = uint32_t(size[v]);
+        ++comps;
+        singles += s == 1;
+        best = max(best, ((unsigned long long)s << 32) | (0xffffffffu - uint32_t(v)));
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        comps += __shfl_down(comps, o);
+        singles += __shfl_down(singles, o);
+        best = max(best, __shfl_down(best, o));
+    }
+    if ((threadIdx.x & 63) == 0 && comps) {
+        atomicAdd(&acc->comps, comps);
+        if (singles) atomicAdd(&acc->singles, singles);
+        atomicMax(&acc->best, best);
+    }
+}
+
+enum { kSrcAll = 0, kSrcMask = 1, kSrcJp = 2 };
+
+struct CcLists {
+    DevBuf g, w, b;
+    int64_t cap_g = 0, cap_w = 0, cap_b = 0;
+    int64_t short_row = 0;
+};
+
+// one pass of the row kernels over the positions [lo, hi) of every row: the lane bin over all vertices, the three lists above it
+template <class Src>
+void link_rows(const Src &src, const gmsx_graph *g, const CcLists &l, int64_t lo, int64_t hi, int use_giant, int32_t *parent, CcAcc *acc, int cus,
+               hipStream_t s, int *launches) {
+    const int64_t n = g->n;
+    const unsigned lanes = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    hipLaunchKernelGGL((k_cc_link<Src, 1>), dim3(lanes), dim3(256), 0, s, src, n, g->off, g->adj, (const int32_t *)nullptr, 0, int64_t(0), l.short_row, lo,
+                       hi, use_giant, parent, acc);
+    const unsigned grid = unsigned(cus) * 8;
+    hipLaunchKernelGGL((k_cc_link<Src, kGroup>), dim3(grid), dim3(256), 0, s, src, n, g->off, g->adj, l.g.as<const int32_t>(), 0, l.cap_g,
+                       int64_t(INT64_MAX), lo, hi, use_giant, parent, acc);
+    hipLaunchKernelGGL((k_cc_link<Src, 64>), dim3(grid), dim3(256), 0, s, src, n, g->off, g->adj, l.w.as<const int32_t>(), 1, l.cap_w, int64_t(INT64_MAX),
+                       lo, hi, use_giant, parent, acc);
+    hipLaunchKernelGGL((k_cc_link<Src, 256>), dim3(grid), dim3(256), 0, s, src, n, g->off, g->adj, l.b.as<const int32_t>(), 2, l.cap_b, int64_t(INT64_MAX),
+                       lo, hi, use_giant, parent, acc);
+    *launches += 4;
+}
+
+// pointer jumping until a round changes nothing; the flag is read between launches
+int flatten(int64_t n, int32_t *parent, CcAcc *acc, int cus, hipStream_t s, int *launches, int32_t *rounds) {
+    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    for (int r = 1; r <= kCcFlattenMax; ++r) {
+        GMSX_HIP(hipMemsetAsync(&acc->again, 0, sizeof(int32_t), s));
+        hipLaunchKernelGGL(k_cc_flatten, dim3(sweep), dim3(256), 0, s, n, parent, acc);
+        ++*launches;
+        int32_t flags[2] = {0, 0};  // error, again
+        GMSX_HIP(hipMemcpyAsync(flags, acc, sizeof flags, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        if (flags[0]) return GMSX_ERR_KERNEL;
+        if (!flags[1]) {
+            if (rounds) *rounds = r;
+            return GMSX_OK;
+        }
+    }
+    return GMSX_ERR_KERNEL;
+}
+
+// Both entry points.  mask_in (host, nnz) for kSrcMask; mask_out (host, nnz, or null) for kSrcJp.
+int components(const gmsx_graph *g, int source, const uint8_t *mask_in, int metric, double threshold, int32_t *label, uint8_t *mask_out,
+               gmsx_components_info *info, gmsx_stats *stats) {
+    gmsx_components_info res;
+    std::memset(&res, 0, sizeof res);
+    if (g->n == 0) {
+        *info = res;
+        if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0, 0};
+        return GMSX_OK;
+    }
+    Ctx &c = ctx();
+    hipStream_t s = c.stream;
+    const int64_t n = g->n, nnz = g->nnz;
+    const int cus = c.compute_units > 0 ? c.compute_units : 256;
+    // test hooks, first guesses
+    const int64_t sample = std::max<long long>(0, std::min<long long>(opt_int("CC_SAMPLE", kCcSampleDefault), INT_MAX));
+    const int64_t wave_row = std::max<long long>(1, std::min<long long>(opt_int("CC_WAVE_ROW", kCcWaveRowDefault), INT_MAX));
+    const int64_t wg_row = std::max<long long>(wave_row, std::min<long long>(opt_int("CC_WG_ROW", kCcWgRowDefault), INT_MAX));
+    CcLists l;
+    l.short_row = std::min<int64_t>(kCcShortRow, wave_row);
+    l.cap_g = std::min<int64_t>(n, nnz / l.short_row + 1);
+    l.cap_w = std::min<int64_t>(n, nnz / wave_row + 1);
+    l.cap_b = std::min<int64_t>(n, nnz / wg_row + 1);
+    DevBuf d_parent, d_size, d_acc, d_mask;
+    const bool dev_mask = source == kSrcMask || (source == kSrcJp && mask_out);
+    // ---- setup: the buffers and the caller's mask
+    GMSX_HIP(hipEventRecord(c.ev[0], s));
+    if (int rc = dalloc<int32_t>(d_parent, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_size, n)) return rc;
+    if (int rc = dalloc<CcAcc>(d_acc, 1)) return rc;
+    if (source != kSrcJp) {
+        if (int rc = dalloc<int32_t>(l.g, l.cap_g)) return rc;
+        if (int rc = dalloc<int32_t>(l.w, l.cap_w)) return rc;
+        if (int rc = dalloc<int32_t>(l.b, l.cap_b)) return rc;
+    }
+    if (dev_mask)
+        if (int rc = dalloc<uint8_t>(d_mask, nnz)) return rc;
+    CcAcc *acc = d_acc.as<CcAcc>();
+    int32_t *parent = d_parent.as<int32_t>();
+    GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(CcAcc), s));
+    GMSX_HIP(hipMemsetAsync(&acc->giant, 0xff, sizeof(int32_t), s));
+    if (source == kSrcMask && nnz > 0) GMSX_HIP(hipMemcpyAsync(d_mask.p, mask_in, size_t(nnz), hipMemcpyHostToDevice, s));
+    if (source == kSrcJp && mask_out && nnz > 0) GMSX_HIP(hipMemsetAsync(d_mask.p, 0, size_t(nnz), s));
+    // ---- linking and flatten
+    GMSX_HIP(hipEventRecord(c.ev[1], s));
+    int launches = 0;
+    const unsigned per_vertex = unsigned((n + 255) / 256);
+    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    hipLaunchKernelGGL(k_cc_init, dim3(per_vertex), dim3(256), 0, s, n, parent, d_size.as<int32_t>());
+    ++launches;
+    if (source == kSrcJp) {
+        if (nnz > 0) {
+            const unsigned blocks = unsigned(std::min<int64_t>((nnz + 7) / 8, int64_t(cus) * 32));  // a wave per edge while the grid lasts: the pair batch's shape
+            hipLaunchKernelGGL(k_cc_jp, dim3(blocks), dim3(256), 0, s, n, nnz, g->off, g->adj, metric, threshold, parent, mask_out ? d_mask.as<uint8_t>() : nullptr,
+                               acc);
+            ++launches;
+        }
+    } else if (nnz > 0) {
+        hipLaunchKernelGGL(k_cc_classify, dim3(sweep), dim3(256), 0, s, n, g->off, l.short_row, wave_row, wg_row, l.g.as<int32_t>(), l.w.as<int32_t>(),
+                           l.b.as<int32_t>(), l.cap_g, l.cap_w, l.cap_b, acc);
+        ++launches;
+        const SrcMask masked{d_mask.as<const uint8_t>()};
+        int use_giant = 0;
+        if (sample > 0) {  // pass A: the first `sample` entries of every row, a lane per row
+            if (source == kSrcAll)
+                hipLaunchKernelGGL((k_cc_link<SrcAll, 1>), dim3(sweep), dim3(256), 0, s, SrcAll{}, n, g->off, g->adj, (const int32_t *)nullptr, 0, int64_t(0),
+                                   int64_t(INT64_MAX), int64_t(0), sample, 0, parent, acc);
+            else
+                hipLaunchKernelGGL((k_cc_link<SrcMask, 1>), dim3(sweep), dim3(256), 0, s, masked, n, g->off, g->adj, (const int32_t *)nullptr, 0, int64_t(0),
+                                   int64_t(INT64_MAX), int64_t(0), sample, 0, parent, acc);
+            ++launches;
+            if (source == kSrcAll) {  // the skip is valid only where every kept edge is visible from both sides
+                if (int rc = flatten(n, parent, acc, cus, s, &launches, nullptr)) return rc;
+                hipLaunchKernelGGL(k_cc_vote, dim3(1), dim3(kCcSamples), 0, s, n, parent, acc);
+                ++launches;
+                use_giant = 1;
+            }
+        }
+        if (source == kSrcAll) link_rows(SrcAll{}, g, l, sample, int64_t(INT64_MAX), use_giant, parent, acc, cus, s, &launches);
+        else link_rows(masked, g, l, sample, int64_t(INT64_MAX), 0, parent, acc, cus, s, &launches);
+    }
+    int32_t passes = 0;
+    if (int rc = flatten(n, parent, acc, cus, s, &launches, &passes)) return rc;
+    // ---- the info reduction
+    GMSX_HIP(hipEventRecord(c.ev[2], s));
+    hipLaunchKernelGGL(k_cc_sizes, dim3(sweep), dim3(256), 0, s, n, parent, d_size.as<int32_t>());
+    hipLaunchKernelGGL(k_cc_info, dim3(sweep), dim3(256), 0, s, n, parent, d_size.as<int32_t>(), acc);
+    if (source == kSrcMask && nnz > 0) {
+        const unsigned groups = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
+        hipLaunchKernelGGL(k_cc_mask_edges, dim3(groups), dim3(256), 0, s, n, g->off, g->adj, d_mask.as<const uint8_t>(), acc);
+    }
+    CcAcc h;
+    GMSX_HIP(hipMemcpyAsync(&h, acc, sizeof h, hipMemcpyDeviceToHost, s));
+    GMSX_HIP(hipEventRecord(c.ev[3], s));
+    GMSX_HIP(hipStreamSynchronize(s));
+    GMSX_HIP(hipGetLastError());
+    if (h.error || h.comps < 1 || h.comps > (unsigned long long)n || (h.best >> 32) < 1) return GMSX_ERR_KERNEL;
+    res.components = int64_t(h.comps);
+    res.singletons = int64_t(h.singles);
+    res.largest = int64_t(h.best >> 32);
+    res.largest_label = int32_t(0xffffffffu - uint32_t(h.best));
+    res.kept_edges = source == kSrcAll ? nnz / 2 : int64_t(h.kept);
+    res.passes = passes;
+    // the flag word was read as zero: the caller's arrays are written now, through host staging
+    std::vector<int32_t> h_label;
+    std::vector<uint8_t> h_mask;
+    if (label) {
+        h_label.resize(size_t(n));
+        GMSX_HIP(hipMemcpyAsync(h_label.data(), parent, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    if (source == kSrcJp && mask_out && nnz > 0) {
+        h_mask.resize(size_t(nnz));
+        GMSX_HIP(hipMemcpyAsync(h_mask.data(), d_mask.p, size_t(nnz), hipMemcpyDeviceToHost, s));
+    }
+    GMSX_HIP(hipStreamSynchronize(s));
+    float up_ms = 0.f, ms = 0.f, info_ms = 0.f;
+    GMSX_HIP(hipEventElapsedTime(&up_ms, c.ev[0], c.ev[1]));
+    GMSX_HIP(hipEventElapsedTime(&ms, c.ev[1], c.ev[2]));
+    GMSX_HIP(hipEventElapsedTime(&info_ms, c.ev[2], c.ev[3]));
+    if (label) std::memcpy(label, h_label.data(), size_t(n) * sizeof(int32_t));
+    if (!h_mask.empty()) std::memcpy(mask_out, h_mask.data(), size_t(nnz));
+    *info = res;
+    if (stats)
+        *stats = gmsx_stats{double(ms), double(up_ms) + double(info_ms), uint64_t(h.examined), source == kSrcJp ? g->alg_elements : 0, 0, launches, 0, 0};
+    return GMSX_OK;
+}
+
+}  // namespace
+}  // namespace gmsx
+
+using namespace gmsx;
+
+extern "C" {
+
+int gmsx_connected_components(const gmsx_graph *g, const uint8_t *arc_keep, int32_t *label, gmsx_components_info *info, gmsx_stats *stats) {
+    return gmsx::guard([&]() -> int {
+        if (!g || !info) return GMSX_ERR_INVALID;
+        if (int rc = ensure_init()) return rc;  // (before the handle is read: without a device there is no valid one)
+        return components(g, arc_keep ? kSrcMask : kSrcAll, arc_keep, 0, 0.0, label, nullptr, info, stats);
+    });
+}
+
+int gmsx_jarvis_patrick(const gmsx_graph *g, int metric, double threshold, int32_t *label, uint8_t *arc_keep, gmsx_components_info *info,
+                        gmsx_stats *stats) {
+    return gmsx::guard([&]() -> int {
+        if (!g || !info || metric < GMSX_SIM_JACCARD || metric > GMSX_SIM_PREF_ATTACHMENT || std::isnan(threshold)) return GMSX_ERR_INVALID;
+        if (int rc = ensure_init()) return rc;
+        return components(g, kSrcJp, nullptr, metric, threshold, label, arc_keep, info, stats);
+    });
+}
+
+}  // extern "C"

@@ -786,6 +786,8 @@ Option g_options[] = {
     {"LP_LDS_MAXN", "", false}, {"LP_SLAB_MB", "", false},
     // subgraph matching (subgraph.hip)
     {"SGM_LAUNCH_TASKS", "", false},
+    // connected components (components.hip)
+    {"CC_SAMPLE", "", false}, {"CC_WAVE_ROW", "", false}, {"CC_WG_ROW", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

@@ -155,7 +155,11 @@ int gmsx_set_host_threads(int n);
  *                   bitmap in the workgroup's global slab; test hook), LP_SLAB_MB (budget of the candidates of one chunk: smaller = more chunks;
  *                   test hook)
  *   subgraph matching      SGM_LAUNCH_TASKS (tasks per launch of gmsx_subgraph_match, default 2^24 for a listing and 2^16 with GMSX_SGM_FIRST —
- *                   both first guesses, not tuned values; a small value splits a small graph into many launches; test hook) */
+ *                   both first guesses, not tuned values; a small value splits a small graph into many launches; test hook)
+ *   connected components   CC_SAMPLE (neighbours of every vertex linked in the first pass of gmsx_connected_components, before the giant component
+ *                   is picked and skipped; default 2; 0 = no sampling pass: one pass covers every vertex and neighbour), CC_WAVE_ROW / CC_WG_ROW
+ *                   (smallest row that gets a wave / a whole workgroup in the linking kernels, defaults 256 / 4096) — all three first guesses,
+ *                   not tuned values; test hooks */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -648,6 +652,45 @@ int gmsx_subgraph_order(int32_t k, const int64_t *p_offsets, const int32_t *p_ne
 int gmsx_subgraph_match(const gmsx_graph *g, int32_t k, const int64_t *p_offsets, const int32_t *p_neigh, uint32_t flags, int part, int nparts,
                         int32_t *maps /* k * capacity ids, row i = embedding i, host, or NULL */, int64_t capacity /* in embeddings */,
                         gmsx_subgraph_info *info /* required */, gmsx_stats *stats);
+
+/* ---- connected components and Jarvis–Patrick clustering: one device union-find over the vertices of the uploaded CSR.
+ * gmsx_connected_components is ShiloachVishkin (gms/representations/graphs/log_graph/cc.cc:40-72): label[v] is the smallest vertex id of v's
+ * component, which is what the reference's hooking of larger labels under smaller ones converges to; so label[v] <= v and
+ * label[label[v]] == label[v].  gmsx_jarvis_patrick has no reference counterpart (like the k-truss it is the member of the family the suite
+ * describes and does not build): keep an edge {u, v} iff metric(N(u), N(v)) >= threshold on the full rows; the clusters are the connected
+ * components of what is kept.
+ * arc_keep AS AN INPUT (gmsx_connected_components; NULL = every edge): nnz bytes parallel to the uploaded CSR's neigh, like the per-arc arrays of
+ * gmsx_truss_decomposition.  An edge is kept if the byte of at least one of its two arcs is non-zero, so a symmetric mask (truss >= k) and a
+ * one-sided one both mean what they look like.  info->kept_edges counts each kept edge once (an arc u -> v with u > v counts only if the byte of
+ * v -> u is zero).
+ * arc_keep AS AN OUTPUT (gmsx_jarvis_patrick; may be NULL): symmetric, 0 or 1.  Fed back into gmsx_connected_components it gives the same labels
+ * and info, byte for byte.
+ * Scores are those of gmsx_vertex_similarity_batch, bit for bit (one device function computes both); a NaN score (Overlap of an isolated
+ * endpoint cannot occur on an edge, but the rule stands) is never kept.  All seven GMSX_SIM_* metrics are accepted; GMSX_SIM_COMMON_NEIGHBORS
+ * with an integer threshold k is the classical "share at least k neighbours".  Note that the reference's Jaccard, c / (|A| + |B| + c), never
+ * exceeds 1/3.
+ * label, every field of info except passes, and the output mask are facts about the graph: byte-identical in every process and on every run (the
+ * arrival order of the atomics reaches no output).  The caller's arrays are written only after the device flag word was read as zero.
+ * n = 0: GMSX_OK, *info zeroed.  A graph without edges or a mask of zeros: n singletons.  NULL g or info, an unknown metric or a NaN threshold:
+ * GMSX_ERR_INVALID, nothing written.  Every walk and retry loop of the kernels is capped (n + 64 steps); a cap that is exceeded, a list that
+ * would overflow or an arc without its twin (possible only under GMSX_UPLOAD_TRUSTED) is reported as GMSX_ERR_KERNEL, and nothing is written
+ * out of bounds.  Single GPU, no shards — a component is global; a sharded upload gives the same bytes.
+ * Test hooks: options CC_SAMPLE, CC_WAVE_ROW, CC_WG_ROW (first guesses, not tuned).  gmsx_stats: kernel_ms (linking and flatten), setup_ms (the
+ * mask upload and the info reduction), launches, units = arcs the linking kernels examined (Jarvis–Patrick: edges scored = m), alg_elements =
+ * Σ(d_u + d_v) over the scored edges (Jarvis–Patrick only). */
+typedef struct {
+    int64_t components;     /* connected components, singletons included */
+    int64_t singletons;     /* components of one vertex */
+    int64_t largest;        /* vertices in the largest component */
+    int64_t kept_edges;     /* undirected edges the components were taken over */
+    int32_t largest_label;  /* its label; ties: the smallest label */
+    int32_t passes;         /* flatten rounds of the final pointer jumping (diagnostic; may differ between runs) */
+} gmsx_components_info;
+int gmsx_connected_components(const gmsx_graph *g, const uint8_t *arc_keep /* nnz, host, or NULL = every edge */,
+                              int32_t *label /* n, host, or NULL */, gmsx_components_info *info /* required */, gmsx_stats *stats);
+int gmsx_jarvis_patrick(const gmsx_graph *g, int metric /* GMSX_SIM_* */, double threshold,
+                        int32_t *label /* n, host, or NULL */, uint8_t *arc_keep /* nnz, host, or NULL: out */,
+                        gmsx_components_info *info /* required */, gmsx_stats *stats);
 
 /* ---- the one collective of the path: the OpenMP reduction(+:total) of parallel/total.h:12,
  * k_clique_count_set_based.h:25 and the BK_CLIQUE_COUNTER atomic (tomita.h:76-77) across GPUs = ONE all-reduce of a u64 over

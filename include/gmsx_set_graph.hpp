@@ -32,7 +32,10 @@
 //   gmsx::edge_support(g, out)           -> gmsx_edge_support      (per arc |N(u) ∩ N(v)|: one Set::intersect_count per edge; no reference driver; returns the triangles)
 //   gmsx::truss_numbers(g, out)          -> gmsx_truss_decomposition (the trussness per arc; returns the largest)
 //   gmsx::ktruss_edges(g, k)             -> gmsx_truss_decomposition (the u < v edges of the k-truss, a host-side filter)
-//   gmsx::link_prediction(g, metric, q)  -> gmsx_link_prediction   (set_based/link_prediction/link_prediction.h:42-101; the reference's padding reproduced)
+//   gmsx::connected_components(g, out)   -> gmsx_connected_components (representations/graphs/log_graph/cc.cc:40-72, ShiloachVishkin: out[v] = smallest id of v's component)
+//   gmsx::jarvis_patrick(g, metric, threshold, out) -> gmsx_jarvis_patrick (the components over the edges whose endpoints are similar enough; no reference driver)
+//   gmsx::ktruss_components(g, k, out)   -> gmsx_truss_decomposition + gmsx_connected_components (the communities of the k-truss: the mask truss >= k)
+//   gmsx::link_prediction(g, metric, q)  -> gmsx_link_prediction  (set_based/link_prediction/link_prediction.h:42-101; the reference's padding reproduced)
 //   gmsx::link_prediction_precision(g_test, edges) -> gmsx_link_prediction_precision (set_based/link_prediction/evaluation.h:99-124)
 //   gmsx::subgraph_isomorphisms(g, pattern, flags) -> gmsx_subgraph_match (every embedding of a small connected pattern, induced or not; no reference driver lists them)
 //   gmsx::subgraph_isomorphism(g, pattern) -> gmsx_subgraph_match, GMSX_SGM_FIRST (non_set_based/subgraphiso/vf2/sequential/vf2.hpp:39-81: the one mapping, target -> pattern)
@@ -621,6 +624,45 @@ inline std::vector<std::pair<int32_t, int32_t>> ktruss_edges(const HipGraphT<S> 
         for (int64_t j = g.offsets()[u]; j < g.offsets()[u + 1]; ++j)
             if (u < g.neighbors()[j] && truss[size_t(j)] >= k) res.emplace_back(int32_t(u), int32_t(g.neighbors()[j]));
     return res;
+}
+
+// ShiloachVishkin(g) (representations/graphs/log_graph/cc.cc:40-72), shaped like its pvector<NodeId> comp: comp[v] = the label of v's
+// component, which is the smallest vertex id in it (what the reference's hooking converges to); returns the number of components.  `info`
+// (optional) receives singletons, the largest component and its label.
+template <class S, class Output>
+inline int64_t connected_components(const HipGraphT<S> &g, Output &comp, gmsx_components_info *info = nullptr) {
+    comp.resize(size_t(g.num_nodes()));
+    static_assert(sizeof(*comp.data()) == sizeof(int32_t), "component labels are int32 vectors");
+    gmsx_components_info ci{};
+    detail::check(gmsx_connected_components(g.device(), nullptr, reinterpret_cast<int32_t *>(comp.data()), &ci, nullptr), "gmsx_connected_components");
+    if (info) *info = ci;
+    return ci.components;
+}
+// Jarvis–Patrick clustering (no reference counterpart): comp[v] = the label of v's cluster — the components over the edges whose endpoints
+// score >= threshold under `metric` (GMSX_SIM_*; the scores of gmsx_vertex_similarity_batch); returns the number of clusters.
+template <class S, class Output>
+inline int64_t jarvis_patrick(const HipGraphT<S> &g, int metric, double threshold, Output &comp, gmsx_components_info *info = nullptr) {
+    comp.resize(size_t(g.num_nodes()));
+    static_assert(sizeof(*comp.data()) == sizeof(int32_t), "cluster labels are int32 vectors");
+    gmsx_components_info ci{};
+    detail::check(gmsx_jarvis_patrick(g.device(), metric, threshold, reinterpret_cast<int32_t *>(comp.data()), nullptr, &ci, nullptr), "gmsx_jarvis_patrick");
+    if (info) *info = ci;
+    return ci.components;
+}
+// The communities of the k-truss: trussness per arc -> the mask truss >= k -> components over the kept edges (vertices outside the k-truss are
+// singletons); returns the number of components.  info->kept_edges is the number of edges of the k-truss.
+template <class S, class Output>
+inline int64_t ktruss_components(const HipGraphT<S> &g, int32_t k, Output &comp, gmsx_components_info *info = nullptr) {
+    std::vector<int32_t> truss;
+    truss_numbers(g, truss);
+    std::vector<uint8_t> keep(truss.size() + 1);
+    for (size_t j = 0; j < truss.size(); ++j) keep[j] = truss[j] >= k;
+    comp.resize(size_t(g.num_nodes()));
+    static_assert(sizeof(*comp.data()) == sizeof(int32_t), "component labels are int32 vectors");
+    gmsx_components_info ci{};
+    detail::check(gmsx_connected_components(g.device(), keep.data(), reinterpret_cast<int32_t *>(comp.data()), &ci, nullptr), "gmsx_connected_components");
+    if (info) *info = ci;
+    return ci.components;
 }
 
 // JonesV3::graph_coloring_jones(g, coloring, order) (coloring_jones_v3.h:38-68): the colouring (1..info->colors) under `order` — rank format
