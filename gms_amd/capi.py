@@ -45,6 +45,7 @@ SYMBOLS = [
     "gmsx_link_prediction", "gmsx_link_prediction_precision",
     "gmsx_subgraph_order", "gmsx_subgraph_match",
     "gmsx_connected_components", "gmsx_jarvis_patrick",
+    "gmsx_cycle4_count", "gmsx_cycle4_partial", "gmsx_motif_census4",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
 
@@ -133,6 +134,19 @@ class ComponentsInfo(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k in ("components", "singletons", "largest", "kept_edges", "largest_label", "passes")}
+
+
+MOTIFS = ("wedge", "triangle", "star3", "path4", "paw", "cycle4", "diamond", "clique4")  # GMSX_MOTIF_*: the index of a name is its value
+
+
+class MotifInfo(C.Structure):
+    _fields_ = [("subgraphs", C.c_uint64 * 8), ("induced", C.c_uint64 * 8), ("wedges_walked", C.c_uint64), ("max_codegree", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {"subgraphs": {k: int(self.subgraphs[i]) for i, k in enumerate(MOTIFS)},
+                "induced": {k: int(self.induced[i]) for i, k in enumerate(MOTIFS)},
+                "wedges_walked": int(self.wedges_walked), "max_codegree": int(self.max_codegree)}
 
 
 def clusters(label):
@@ -304,6 +318,9 @@ def lib():
                                       C.POINTER(SubgraphInfo), sp]
     L.gmsx_connected_components.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(ComponentsInfo), sp]
     L.gmsx_jarvis_patrick.argtypes = [vp, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(ComponentsInfo), sp]
+    L.gmsx_cycle4_count.argtypes = [vp, u64p, C.c_void_p, sp]
+    L.gmsx_cycle4_partial.argtypes = [vp, C.c_int, C.c_int, u64p, sp]
+    L.gmsx_motif_census4.argtypes = [vp, C.POINTER(MotifInfo), sp]
     L.gmsx_comm_unique_id.argtypes = [C.c_char_p]
     L.gmsx_comm_init.argtypes = [C.c_int, C.c_int, C.c_char_p, vpp]
     L.gmsx_comm_allreduce_u64.argtypes = [vp, u64p]
@@ -934,6 +951,31 @@ class DeviceGraph:
                                          mask.ctypes.data_as(C.c_void_p) if want_mask else None, C.byref(info), C.byref(st)), "gmsx_jarvis_patrick")
         r = (label[:n], info.as_dict()) + ((mask[:nnz],) if want_mask else ())
         return (r + (st.as_dict(),)) if stats else r
+
+    def cycle4_count(self, at_vertex=False, stats=False):
+        """gmsx_cycle4_count: the 4-cycles of the graph; with at_vertex=True (cycles, int64[n] — the 4-cycles through every vertex of the
+        uploaded CSR, which add up to 4 * cycles)."""
+        n = self.num_nodes
+        out, st = C.c_uint64(0), Stats()
+        at = np.zeros(max(n, 1), dtype=np.int64) if at_vertex else None
+        _check(lib().gmsx_cycle4_count(self._h, C.byref(out), at.ctypes.data_as(C.c_void_p) if at_vertex else None, C.byref(st)), "gmsx_cycle4_count")
+        r = (int(out.value), at[:n]) if at_vertex else int(out.value)
+        if stats:
+            return (r + (st.as_dict(),)) if at_vertex else (r, st.as_dict())
+        return r
+
+    def cycle4_partial(self, part, nparts, stats=False):
+        """gmsx_cycle4_partial: the 4-cycles whose source (their vertex of the smallest rank id) belongs to shard `part` of `nparts`."""
+        out, st = C.c_uint64(0), Stats()
+        _check(lib().gmsx_cycle4_partial(self._h, int(part), int(nparts), C.byref(out), C.byref(st)), "gmsx_cycle4_partial")
+        return (int(out.value), st.as_dict()) if stats else int(out.value)
+
+    def motif_census4(self, stats=False):
+        """gmsx_motif_census4: {subgraphs: {motif: non-induced copies}, induced: {motif: induced copies}, wedges_walked, max_codegree} over the
+        eight motifs of MOTIFS."""
+        info, st = MotifInfo(), Stats()
+        _check(lib().gmsx_motif_census4(self._h, C.byref(info), C.byref(st)), "gmsx_motif_census4")
+        return (info.as_dict(), st.as_dict()) if stats else info.as_dict()
 
     def free(self):
         if getattr(self, "_h", None):

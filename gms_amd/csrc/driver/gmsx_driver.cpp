@@ -45,7 +45,11 @@
 //                    and the number of components.  A component is global: not sharded (--gpus > 1 is refused).
 // Added:  jp --metric NAME --threshold X   Jarvis–Patrick clustering on the device (gmsx_jarvis_patrick; no reference driver; NAME as for lp): the same
 //                    loop and output plus "Kept Edges"; -v runs the BFS over the kept arcs the call returns and checks that they are symmetric.
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  motifs     the 3- / 4-vertex motif census on the device (gmsx_motif_census4; no reference driver) with the usual trial loop: per trial
+//                    "Trial Time", the eight motifs as "name: non-induced induced N", "Wedges Walked", "Max Codegree" and with -v "Verification" — the
+//                    counting rule of the 4-cycle kernels as this driver's own serial loop over the host CSR, the degree sums, the triangle count and
+//                    the induced / non-induced identities —, then the "@@@" line.  Not sharded (--gpus > 1 is refused).
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -144,7 +148,7 @@ Args parse(int argc, char **argv) {
     if (!a.error && a.file.empty() && a.gen.empty()) a.error = 101;  // cli/cli.h:131-133
     if (!a.error && !a.gen.empty() && a.gen != "kronecker" && a.gen != "uniform") a.error = 100;
     if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp" && a.kernel != "sgi") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
-    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss" || a.kernel == "sgi" || a.kernel == "cc" || a.kernel == "jp") && a.gpus > 1) a.error = 100;
+    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss" || a.kernel == "sgi" || a.kernel == "cc" || a.kernel == "jp" || a.kernel == "motifs") && a.gpus > 1) a.error = 100;
     if (!a.error && ((a.kernel == "jp") != !std::isnan(a.threshold))) a.error = 100;  // the threshold is required, and only there
     if (!a.error && ((a.kernel == "sgi") != !a.pattern_file.empty() || (a.mono && a.kernel != "sgi"))) a.error = 100;  // util/command_line.hpp:22: the pattern is required
     if (!a.error && (a.kernel == "lp" || a.kernel == "jp") && lp_metric(a.metric) < 0) a.error = 100;
@@ -492,6 +496,86 @@ bool verify_components(const HostGraph &hg, const std::vector<int32_t> &comp, co
     return true;
 }
 
+// The counting rule of gmsx_cycle4_count as a serial loop (no reference counterpart): ranks by decreasing (degree, id); for every source u with at
+// least two later neighbours, every wedge u - v - w with rank(v) > rank(u) < rank(w) adds to cnt[w]; the cycles of u are Σ_w C(cnt[w], 2); a
+// second walk returns the counters to zero.  Returns the cycles and the wedges walked.
+void host_cycle4(const HostGraph &hg, uint64_t *cycles, uint64_t *wedges) {
+    std::vector<int32_t> order(size_t(hg.n)), rank(size_t(hg.n));
+    for (int64_t v = 0; v < hg.n; ++v) order[size_t(v)] = int32_t(v);
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+        const int64_t da = hg.off[a + 1] - hg.off[a], db = hg.off[b + 1] - hg.off[b];
+        return da != db ? da > db : a > b;
+    });
+    for (int64_t i = 0; i < hg.n; ++i) rank[size_t(order[size_t(i)])] = int32_t(i);
+    std::vector<uint32_t> cnt(size_t(hg.n), 0);
+    uint64_t c = 0, w_all = 0;
+    for (int64_t u = 0; u < hg.n; ++u) {
+        const int32_t ru = rank[size_t(u)];
+        int64_t later = 0;
+        for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j) later += rank[size_t(hg.adj[j])] > ru;
+        if (later < 2) continue;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j) {
+                const int32_t v = hg.adj[j];
+                if (rank[size_t(v)] <= ru) continue;
+                for (int64_t k = hg.off[v]; k < hg.off[v + 1]; ++k) {
+                    const int32_t w = hg.adj[k];
+                    if (rank[size_t(w)] <= ru) continue;
+                    if (pass == 0) {
+                        ++cnt[size_t(w)];
+                        ++w_all;
+                    } else {
+                        const uint64_t x = cnt[size_t(w)];
+                        c += x * (x - 1) / 2;
+                        cnt[size_t(w)] = 0;
+                    }
+                }
+            }
+    }
+    *cycles = c;
+    *wedges = w_all;
+}
+
+// the motif census (gmsx::motif_census4) under the usual trial loop: the sixteen counts, one "@@@" line per trial
+int run_motifs(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
+    static const char *const names[GMSX_MOTIF_KINDS] = {"wedge", "triangle", "star3", "path4", "paw", "cycle4", "diamond", "clique4"};
+    double total_seconds = 0;
+    Timer t;
+    for (int64_t it = 0; it < args.trials; ++it) {
+        t.Start();
+        const gmsx_motif_info info = gmsx::motif_census4(g);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        for (int k = 0; k < GMSX_MOTIF_KINDS; ++k) PrintLabel(names[k], std::to_string(info.subgraphs[k]) + " induced " + std::to_string(info.induced[k]));
+        PrintLabel("Wedges Walked", std::to_string(info.wedges_walked));
+        PrintLabel("Max Codegree", std::to_string(info.max_codegree));
+        if (args.verify) {
+            uint64_t cycles = 0, wedges = 0;
+            host_cycle4(hg, &cycles, &wedges);
+            unsigned __int128 w2 = 0, w3 = 0;
+            for (int64_t v = 0; v < hg.n; ++v) {
+                const unsigned __int128 d = (unsigned __int128)(hg.off[v + 1] - hg.off[v]);
+                if (d >= 2) w2 += d * (d - 1) / 2;
+                if (d >= 3) w3 += d * (d - 1) * (d - 2) / 6;
+            }
+            const uint64_t *s = info.subgraphs, *i = info.induced;
+            bool ok = cycles == s[GMSX_MOTIF_CYCLE4] && wedges == info.wedges_walked && w2 == s[GMSX_MOTIF_WEDGE] && w3 == s[GMSX_MOTIF_STAR3];
+            ok = ok && s[GMSX_MOTIF_TRIANGLE] == uint64_t(gmsx::count_total(g)) && gmsx::cycle4_count(g) == cycles;
+            ok = ok && i[GMSX_MOTIF_CLIQUE4] == s[GMSX_MOTIF_CLIQUE4] && i[GMSX_MOTIF_DIAMOND] + 6 * s[GMSX_MOTIF_CLIQUE4] == s[GMSX_MOTIF_DIAMOND];
+            ok = ok && i[GMSX_MOTIF_CYCLE4] + i[GMSX_MOTIF_DIAMOND] + 3 * s[GMSX_MOTIF_CLIQUE4] == s[GMSX_MOTIF_CYCLE4];
+            ok = ok && i[GMSX_MOTIF_PAW] + 4 * i[GMSX_MOTIF_DIAMOND] + 12 * s[GMSX_MOTIF_CLIQUE4] == s[GMSX_MOTIF_PAW];
+            ok = ok && i[GMSX_MOTIF_STAR3] + i[GMSX_MOTIF_PAW] + 2 * i[GMSX_MOTIF_DIAMOND] + 4 * s[GMSX_MOTIF_CLIQUE4] == s[GMSX_MOTIF_STAR3];
+            ok = ok && i[GMSX_MOTIF_PATH4] + 2 * i[GMSX_MOTIF_PAW] + 4 * i[GMSX_MOTIF_CYCLE4] + 6 * i[GMSX_MOTIF_DIAMOND] + 12 * s[GMSX_MOTIF_CLIQUE4] == s[GMSX_MOTIF_PATH4];
+            ok = ok && i[GMSX_MOTIF_TRIANGLE] == s[GMSX_MOTIF_TRIANGLE] && i[GMSX_MOTIF_WEDGE] + 3 * s[GMSX_MOTIF_TRIANGLE] == s[GMSX_MOTIF_WEDGE];
+            PrintLabel("Verification", ok ? "PASS" : "FAIL");
+        }
+        std::cout << "@@@ motif census" << std::endl;
+    }
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
 // connected components (cc) and Jarvis–Patrick clustering (jp) under the usual trial loop, with PrintCompStats' facts (cc.cc:75-91) at the end
 int run_components(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
     const bool jp = args.kernel == "jp";
@@ -596,7 +680,7 @@ int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -670,8 +754,8 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp") {
-        const int rc_run = args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs") {
+        const int rc_run = args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
                                                                                                                                         : run_components(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);

@@ -30,6 +30,7 @@
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
 #include "frontier_rounds.hpp"
+#include "truss_edges.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -46,14 +47,7 @@ struct TrussCtrl : FrontierCtrl {  // (done = edges that have left in finished r
     int32_t min_sup;  // level sweep: smallest remaining support
 };
 
-// accumulators of the numbering and the support pass (one small block, zeroed per call)
-struct TrussAcc {
-    unsigned long long sum;  // Σ support over undirected edges
-    int32_t max_sup;
-    int32_t error;           // an arc without its twin, a self loop, or an append past its bound
-    int32_t nlong;           // edges parked by k_truss_support
-    int32_t pad;
-};
+// (TrussAcc, the accumulators of the numbering and the support pass, and TrussEdges: truss_edges.hpp)
 
 // position of x in the ascending row [lo, hi) of adj, or -1
 __device__ __forceinline__ int64_t find_in_row(const int32_t *__restrict__ adj, int64_t lo, int64_t hi, int32_t x) {
@@ -280,15 +274,10 @@ struct TrussPeel {
     __device__ __forceinline__ void finish() const {}
 };
 
-// what one call builds before anything is counted: the numbering, the costs and the support of every edge
-struct TrussEdges {
-    int64_t m = 0, long_cap = 0;
-    DevBuf eid, eu, ev, coff, sup, acc, longs;
-    TrussAcc h;
-    int launches = 0;
-};
+}  // namespace
 
-// Edge numbering and support.  rnd (m, device, or null) is set to -1.  Refuses m >= 2^31: edge ids are 32 bits.
+// Edge numbering and support (declared in truss_edges.hpp: motifs.hip calls it too).  rnd (m, device, or null) is set to -1.  Refuses
+// m >= 2^31: edge ids are 32 bits.
 int truss_edges(const gmsx_graph *g, TrussEdges &t, int32_t *rnd) {
     Ctx &c = ctx();
     hipStream_t s = c.stream;
@@ -341,6 +330,8 @@ int truss_edges(const gmsx_graph *g, TrussEdges &t, int32_t *rnd) {
     t.launches = 7;  // (two scans counted as one launch each)
     return GMSX_OK;
 }
+
+namespace {
 
 // per-edge values -> the caller's per-arc array (host), through a host staging vector: written only after everything else succeeded
 int gather_to_host(const TrussEdges &t, int64_t nnz, const int32_t *d_val, DevBuf &d_out, std::vector<int32_t> &h_out, hipStream_t s) {

@@ -788,6 +788,8 @@ Option g_options[] = {
     {"SGM_LAUNCH_TASKS", "", false},
     // connected components (components.hip)
     {"CC_SAMPLE", "", false}, {"CC_WAVE_ROW", "", false}, {"CC_WG_ROW", "", false},
+    // 4-cycles and the motif census (motifs.hip)
+    {"C4_LDS_SPAN", "", false}, {"C4_SLAB_MB", "", false}, {"C4_SPLIT_WEDGES", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

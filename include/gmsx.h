@@ -159,7 +159,12 @@ int gmsx_set_host_threads(int n);
  *   connected components   CC_SAMPLE (neighbours of every vertex linked in the first pass of gmsx_connected_components, before the giant component
  *                   is picked and skipped; default 2; 0 = no sampling pass: one pass covers every vertex and neighbour), CC_WAVE_ROW / CC_WG_ROW
  *                   (smallest row that gets a wave / a whole workgroup in the linking kernels, defaults 256 / 4096) — all three first guesses,
- *                   not tuned values; test hooks */
+ *                   not tuned values; test hooks
+ *   4-cycles and motifs    C4_LDS_SPAN (largest counter span of a source, in 32-bit counters, kept in a workgroup's LDS; default and maximum
+ *                   8192; 0 = no LDS path), C4_SLAB_MB (budget of the global counter spans, default 1024: a smaller budget = fewer workgroup
+ *                   spans and fewer split sources per launch), C4_SPLIT_WEDGES (wedge bound above which a source is walked by many workgroups
+ *                   into one span, default 2^18; 1 = every source with a wedge, a huge value = none) — all three first guesses, not tuned
+ *                   values; test hooks */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -691,6 +696,44 @@ int gmsx_connected_components(const gmsx_graph *g, const uint8_t *arc_keep /* nn
 int gmsx_jarvis_patrick(const gmsx_graph *g, int metric /* GMSX_SIM_* */, double threshold,
                         int32_t *label /* n, host, or NULL */, uint8_t *arc_keep /* nnz, host, or NULL: out */,
                         gmsx_components_info *info /* required */, gmsx_stats *stats);
+
+/* ---- 4-cycle counting and the 3- / 4-vertex motif census.  No reference counterpart (like the k-truss: a member of the family the suite
+ * describes and does not build).  All results are exact integers.
+ * gmsx_cycle4_count: *cycles = the 4-cycles of the graph (subgraphs, not necessarily induced; the butterflies of a bipartite graph).
+ * at_vertex[v] (n entries, indexed by the vertex ids of the uploaded CSR; may be NULL) = the 4-cycles through v = Σ_{w != v} C(|N(v) ∩ N(w)|, 2);
+ * their sum is 4 * *cycles.  THE RULE (motifs.hip): in the device's rank ids (decreasing (degree, id), rank 0 = the biggest hub) a cycle is
+ * counted once, at its vertex u of the smallest rank id, against the opposite vertex w — a WEDGE is a path u - v - w with rank(v) > rank(u) and
+ * rank(w) > rank(u), and the cycles of u are Σ_w C(wedges from u to w, 2).  A source with fewer than two later neighbours is not walked.
+ * gmsx_cycle4_partial: the cycles whose source belongs to shard `part` of `nparts` — a shard is a set of whole sources, assigned by the rule of
+ * gmsx_tc_partial applied to the source's rank id; the partials of one nparts add up to *cycles; (0, 1) is the whole graph, other out-of-range
+ * pairs → GMSX_ERR_INVALID.  No at_vertex in a partial.
+ * gmsx_motif_census4 (single GPU): subgraphs[] = non-induced copies (a copy = a vertex subset and an edge subset isomorphic to the motif, each
+ * once), induced[] = vertex subsets whose induced subgraph IS the motif.  With d the degree, sup(e) the support of gmsx_edge_support, T the
+ * triangles: wedge = Σ_v C(d_v, 2); star3 = Σ_v C(d_v, 3); triangle = Σ_e sup(e) / 3; path4 = Σ_{e = {u,v}} (d_u - 1)(d_v - 1) - 3 T;
+ * paw (tailed triangle) = ½ Σ_e sup(e)(d_u + d_v - 4); diamond = Σ_e C(sup(e), 2); clique4 = gmsx_kclique_count(k = 4); cycle4 = the kernel
+ * above.  Induced: I_K4 = K4; I_diamond = diamond - 6 K4; I_C4 = cycle4 - I_diamond - 3 K4; I_paw = paw - 4 I_diamond - 12 K4; I_star3 =
+ * star3 - I_paw - 2 I_diamond - 4 K4; I_path4 = path4 - 2 I_paw - 4 I_C4 - 6 I_diamond - 12 K4; I_triangle = T; I_wedge = wedge - 3 T.
+ * The sums are finished in 128 bits on the host: if any non-induced count does not fit 64 bits the call returns GMSX_ERR_OVERFLOW and writes
+ * nothing (Σ C(d, 3) alone passes 2^64 on a star of 4.9 M leaves).  The 4-cycle calls return GMSX_ERR_OVERFLOW, too, when wedges_walked *
+ * max_codegree / 2 — a bound of their 64-bit sum — does not fit 64 bits (more than 2^34 wedges at the least).
+ * n = 0 or no edge: GMSX_OK and zeros.  NULL g, info or cycles: GMSX_ERR_INVALID.  Outputs are written only after the device flag word was read
+ * as zero; a counter index outside its span, or a harvest that disagrees with the wedges counted (a counter that was not zero before or after
+ * its source), → GMSX_ERR_KERNEL; nothing is written out of bounds.  Every output except the gmsx_stats times is byte-identical in every
+ * process and run.  Test hooks: options C4_LDS_SPAN, C4_SLAB_MB, C4_SPLIT_WEDGES.  gmsx_stats: kernel_ms (the wedge kernels), setup_ms (source
+ * binning and the counter spans; census: also the support pass, the reductions and the 4-clique count), launches, units = sources walked,
+ * alg_elements = wedges_walked. */
+enum { GMSX_MOTIF_WEDGE = 0, GMSX_MOTIF_TRIANGLE = 1, GMSX_MOTIF_STAR3 = 2, GMSX_MOTIF_PATH4 = 3,
+       GMSX_MOTIF_PAW = 4, GMSX_MOTIF_CYCLE4 = 5, GMSX_MOTIF_DIAMOND = 6, GMSX_MOTIF_CLIQUE4 = 7, GMSX_MOTIF_KINDS = 8 };
+typedef struct {
+    uint64_t subgraphs[GMSX_MOTIF_KINDS];  /* non-induced copies: vertex subsets times edge subsets, each copy once */
+    uint64_t induced[GMSX_MOTIF_KINDS];    /* vertex subsets whose induced subgraph IS the motif */
+    uint64_t wedges_walked;                /* wedges the 4-cycle kernels examined (diagnostic, a fact about the graph) */
+    int32_t  max_codegree;                 /* largest counter value met: max over counted pairs (u, w) of |N(u) ∩ N(w)| restricted to later middles */
+    int32_t  reserved;
+} gmsx_motif_info;
+int gmsx_cycle4_count(const gmsx_graph *g, uint64_t *cycles, int64_t *at_vertex /* n, host, or NULL */, gmsx_stats *stats);
+int gmsx_cycle4_partial(const gmsx_graph *g, int part, int nparts, uint64_t *partial, gmsx_stats *stats);
+int gmsx_motif_census4(const gmsx_graph *g, gmsx_motif_info *info /* required */, gmsx_stats *stats);
 
 /* ---- the one collective of the path: the OpenMP reduction(+:total) of parallel/total.h:12,
  * k_clique_count_set_based.h:25 and the BK_CLIQUE_COUNTER atomic (tomita.h:76-77) across GPUs = ONE all-reduce of a u64 over

@@ -35,6 +35,8 @@
 //   gmsx::connected_components(g, out)   -> gmsx_connected_components (representations/graphs/log_graph/cc.cc:40-72, ShiloachVishkin: out[v] = smallest id of v's component)
 //   gmsx::jarvis_patrick(g, metric, threshold, out) -> gmsx_jarvis_patrick (the components over the edges whose endpoints are similar enough; no reference driver)
 //   gmsx::ktruss_components(g, k, out)   -> gmsx_truss_decomposition + gmsx_connected_components (the communities of the k-truss: the mask truss >= k)
+//   gmsx::cycle4_count(g) / cycle4_count(g, at_vertex) -> gmsx_cycle4_count (the 4-cycles, and those through every vertex; no reference driver)
+//   gmsx::motif_census4(g)               -> gmsx_motif_census4     (the eight 3- and 4-vertex motifs, non-induced and induced; no reference driver)
 //   gmsx::link_prediction(g, metric, q)  -> gmsx_link_prediction  (set_based/link_prediction/link_prediction.h:42-101; the reference's padding reproduced)
 //   gmsx::link_prediction_precision(g_test, edges) -> gmsx_link_prediction_precision (set_based/link_prediction/evaluation.h:99-124)
 //   gmsx::subgraph_isomorphisms(g, pattern, flags) -> gmsx_subgraph_match (every embedding of a small connected pattern, induced or not; no reference driver lists them)
@@ -663,6 +665,32 @@ inline int64_t ktruss_components(const HipGraphT<S> &g, int32_t k, Output &comp,
     detail::check(gmsx_connected_components(g.device(), keep.data(), reinterpret_cast<int32_t *>(comp.data()), &ci, nullptr), "gmsx_connected_components");
     if (info) *info = ci;
     return ci.components;
+}
+
+// The 4-cycles of the graph (no reference counterpart).  With `at_vertex` (a vector of 64-bit integers, resized to n): the 4-cycles through
+// every vertex as well, which add up to four times the return value.
+template <class S>
+inline uint64_t cycle4_count(const HipGraphT<S> &g) {
+    uint64_t cycles = 0;
+    detail::check(gmsx_cycle4_count(g.device(), &cycles, nullptr, nullptr), "gmsx_cycle4_count");
+    return cycles;
+}
+template <class S, class Output>
+inline uint64_t cycle4_count(const HipGraphT<S> &g, Output &at_vertex) {
+    at_vertex.resize(size_t(g.num_nodes()));
+    static_assert(sizeof(*at_vertex.data()) == sizeof(int64_t), "per-vertex cycle counts are 64-bit vectors");
+    uint64_t cycles = 0;
+    int64_t none = 0;  // (n = 0: data() may be null, and the library writes nothing)
+    detail::check(gmsx_cycle4_count(g.device(), &cycles, at_vertex.empty() ? &none : reinterpret_cast<int64_t *>(at_vertex.data()), nullptr), "gmsx_cycle4_count");
+    return cycles;
+}
+// The census of the eight 3- and 4-vertex motifs (GMSX_MOTIF_*): info.subgraphs[] non-induced, info.induced[] induced.  Throws on
+// GMSX_ERR_OVERFLOW (a count that does not fit 64 bits), like every other failed call.
+template <class S>
+inline gmsx_motif_info motif_census4(const HipGraphT<S> &g) {
+    gmsx_motif_info info{};
+    detail::check(gmsx_motif_census4(g.device(), &info, nullptr), "gmsx_motif_census4");
+    return info;
 }
 
 // JonesV3::graph_coloring_jones(g, coloring, order) (coloring_jones_v3.h:38-68): the colouring (1..info->colors) under `order` — rank format
