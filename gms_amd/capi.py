@@ -554,7 +554,7 @@ class DeviceGraph:
     BREAKDOWN = ["hub_rows_list", "hub_rows_bitset", "hub_rows_delta", "tail_rows_list", "tail_rows_delta", "entries", "pivot_containers",
                  "of_which_inline_rows", "light_streamed_hub_rows", "light_streamed_tail_rows", "light_pivot_lists_and_descriptors",
                  "count_entries", "count_inline_entries", "count_work_items", "count_light_streamed_members",
-                 "core_matrix", "core_k", "reserved17", "reserved18", "reserved19", "reserved20"]
+                 "core_matrix", "core_k", "gathered_rows", "row_line_bytes", "partial_line_entries", "gather_limit"]
     BREAKDOWN_BYTES = ("hub_rows_list", "hub_rows_bitset", "hub_rows_delta", "tail_rows_list", "tail_rows_delta", "entries", "pivot_containers",
                        "light_streamed_hub_rows", "light_streamed_tail_rows", "light_pivot_lists_and_descriptors", "core_matrix")  # these add up to stats.stream_bytes
 

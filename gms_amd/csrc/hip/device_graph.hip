@@ -21,6 +21,7 @@
 
 #include "../host/gmsx_internal.hpp"
 #include "../host/tc_core_plan.hpp"
+#include "../host/tc_gather_plan.hpp"
 #include "kc4_mfma.hpp"  // kc4m_stride: the row stride Kc4mBlock reads
 
 namespace gmsx {
@@ -596,12 +597,14 @@ __global__ __launch_bounds__(256) void k_inline_rows(int64_t first, int64_t end,
         }
     }
 }
-__global__ void k_inline_units(int64_t n, const unsigned long long *__restrict__ ids_h, const unsigned long long *__restrict__ ids_t,
+// (lines: every receiver's inline rows take whole 128-byte lines, so that each starts on a line boundary — with the gathered rows, see build_tc_sets)
+__global__ void k_inline_units(int64_t n, const unsigned long long *__restrict__ ids_h, const unsigned long long *__restrict__ ids_t, bool lines,
                                int64_t *__restrict__ units_h, int64_t *__restrict__ units_t) {
     const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (v > n) return;
-    units_h[v] = v < n ? int64_t((ids_h[v] + 7) / 8) : 0;
-    units_t[v] = v < n ? int64_t((ids_t[v] + 3) / 4) : 0;
+    const int64_t uh = v < n ? int64_t((ids_h[v] + 7) / 8) : 0, ut = v < n ? int64_t((ids_t[v] + 3) / 4) : 0;
+    units_h[v] = lines ? int64_t(gather_region_units(uint64_t(uh))) : uh;
+    units_t[v] = lines ? int64_t(gather_region_units(uint64_t(ut))) : ut;
 }
 static constexpr int kDefaultHotWindows = 0, kDefaultHotKB = 2048, kDefaultHotMin = 16;
 // ---- receivers -----------------------------------------------------------------------------------------------------------------------------
@@ -630,13 +633,15 @@ __global__ void k_recv_vertices(int64_t n_heavy, int64_t limit, const int32_t *_
 // MODE 0 counts them into the class counters, MODE 1 writes them (cursor = cur).
 template <bool FILL>
 __global__ void k_inline_entries(int64_t n, const int32_t *__restrict__ dplus, const int32_t *__restrict__ opos, const int64_t *__restrict__ lidx, int64_t n_heavy,
-                                 int32_t inline_limit, const int64_t *__restrict__ ihoff, const int64_t *__restrict__ itoff, int64_t base_h, int64_t base_t,
+                                 int32_t inline_limit, const int64_t *__restrict__ ihoff, const int64_t *__restrict__ itoff,
+                                 const unsigned long long *__restrict__ ids_h, const unsigned long long *__restrict__ ids_t, int64_t base_h, int64_t base_t,
                                  uint32_t *__restrict__ cnt, uint32_t *__restrict__ cur, const int64_t *__restrict__ hbeg, const int64_t *__restrict__ tbeg,
                                  TaskList htask, TaskList ttask, unsigned long long *__restrict__ totals, TcClasses cc) {
     const int kClasses = cc.count();
     const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (v >= n) return;
-    const int64_t uh = ihoff[v + 1] - ihoff[v], ut = itoff[v + 1] - itoff[v];
+    // the rows' lengths from their ids (the fill cursors of k_inline_rows, back at the counts): the offsets may be rounded to whole lines
+    const int64_t uh = int64_t((ids_h[v] + 7) / 8), ut = int64_t((ids_t[v] + 3) / 4);
     if (uh == 0 && ut == 0) return;
     if (dplus[v] < kHeavy && v >= inline_limit) return;  // cannot happen: only heavy vertices and rank ids < inline_limit receive
     const int64_t p = receiver_of(int32_t(v), dplus, opos, lidx, n_heavy);
@@ -843,6 +848,87 @@ __device__ __forceinline__ uint32_t claim_by_class(uint32_t *ctr, int cls, bool 
     }
     return mine;
 }
+// ---- gathered rows (device_graph.hpp; the rule: host/tc_gather_plan.hpp) --------------------------------------------------------------
+// Per receiver four gathered rows — hub list units, hub delta units, tail list units, tail delta units (slot = 2 * tail + gather_slot(form)) —
+// each a line-aligned region behind the pool it belongs to.  COUNT adds the units every trimmed descriptor moves to gunits[4 p + slot];
+// FILL claims that many units behind the cursor gcur[4 p + slot] and copies them.  reg = first unit of the regions of a pool, goff = the
+// line-rounded region offsets of all (receiver, form) of that pool (exclusive scan).
+struct GatherPlan {
+    int R = 0;                         // GMSX_TC_GATHER (0 = off: k_task_lists emits every descriptor as it is)
+    uint32_t *gunits = nullptr;        // [4 n_recv] units per gathered row
+    uint32_t *gcur = nullptr;          // [4 n_recv] FILL cursors
+    const int64_t *hoff = nullptr;     // [2 n_recv + 1] hub regions: offset of (receiver, form) in units
+    const int64_t *toff = nullptr;     // [2 n_recv + 1] tail regions
+    int64_t hreg = 0, treg = 0;        // first unit of the gathered regions in spool / tpool
+    uint4 *spool = nullptr, *tpool = nullptr;  // FILL: the (grown) pools, as units
+};
+// wave-aggregated claim of `mine` units (0 for the lanes that move nothing) in ONE counter: one atomic per wave; returns this lane's
+// offset behind the counter's old value
+__device__ __forceinline__ uint32_t claim_units(uint32_t *ctr, uint32_t mine, int lane) {
+    if (__ballot(mine != 0) == 0ull) return 0u;
+    uint32_t incl = mine;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t x = uint32_t(__shfl_up(int(incl), s));
+        if (lane >= s) incl += x;
+    }
+    const uint32_t total = uint32_t(__builtin_amdgcn_readlane(int(incl), 63));
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(ctr, total);
+    base = uint32_t(__builtin_amdgcn_readfirstlane(int(base)));
+    return base + incl - mine;
+}
+// the last `moved` units of the row d names go to units [at, at + moved) of gathered row `slot` of receiver p
+__device__ __forceinline__ void gather_copy(const GatherPlan &gp, bool tail, int64_t p, unsigned long long d, uint32_t moved, uint32_t at) {
+    uint4 *pool = tail ? gp.tpool : gp.spool;
+    const int slot = gather_slot((uint32_t(d) >> 22) & 3u);
+    const int64_t dst = (tail ? gp.treg + gp.toff[2 * p + slot] : gp.hreg + gp.hoff[2 * p + slot]) + int64_t(at);
+    const int64_t src = int64_t(d >> 24) + int64_t(uint32_t(d) & 0x3fffffu) - int64_t(moved);
+    for (uint32_t k = 0; k < moved; ++k) pool[dst + k] = pool[src + k];
+}
+// the line-rounded region sizes of the gathered rows (scanned into GatherPlan::hoff / toff)
+__global__ void k_gather_sizes(int64_t n_recv, const uint32_t *__restrict__ gunits, int64_t *__restrict__ hsize, int64_t *__restrict__ tsize,
+                               unsigned long long *__restrict__ moved) {
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;  // (receiver, form)
+    if (i > 2 * n_recv) return;
+    const int64_t p = i >> 1, fs = i & 1;
+    const uint32_t gh = i < 2 * n_recv ? gunits[4 * p + fs] : 0u, gt = i < 2 * n_recv ? gunits[4 * p + 2 + fs] : 0u;
+    hsize[i] = int64_t(gather_region_units(gh));
+    tsize[i] = int64_t(gather_region_units(gt));
+    if (gh + gt) atomicAdd(moved, (unsigned long long)gh + gt);
+}
+// the gathered rows of every receiver as entries — chunks of kGatherChunk units like the inline rows', the last one shorter, each in the class
+// its own descriptor maps to.  COUNT: into the class counters; FILL: into their class slots, and the filler units behind each row's end
+// (0xFFFF ids / -2 ids / a delta unit of count 0: never a hit in the region's form).
+template <bool FILL>
+__global__ void k_gather_entries(int64_t n_recv, const uint32_t *__restrict__ gunits, const int64_t *__restrict__ ghoff, const int64_t *__restrict__ gtoff,
+                                 int64_t hreg, int64_t treg, uint32_t *__restrict__ cnt, uint32_t *__restrict__ cur, const int64_t *__restrict__ hbeg,
+                                 const int64_t *__restrict__ tbeg, TaskList htask, TaskList ttask, uint4 *__restrict__ spool, uint4 *__restrict__ tpool,
+                                 TcClasses cc) {
+    const int kClasses = cc.count();
+    const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (p >= n_recv) return;
+    uint32_t *c = cnt + p * kClasses;
+    for (int slot = 0; slot < 4; ++slot) {
+        const bool tail = slot >= 2;
+        const int fs = slot & 1;
+        const uint64_t g = gunits[4 * p + slot];
+        if (g == 0) continue;
+        const unsigned long long form = fs ? kFormDelta : kFormList;
+        const int64_t reg = tail ? treg + gtoff[2 * p + fs] : hreg + ghoff[2 * p + fs];
+        for (uint64_t o = 0; o < g; o += kGatherChunk) {
+            const unsigned long long units = g - o < kGatherChunk ? g - o : kGatherChunk;
+            const unsigned long long d = ((unsigned long long)(reg + int64_t(o)) << 24) | (form << 22) | units;
+            const int cls = tail ? tail_class(cc, d) : hub_class(cc, d);
+            if (!FILL) atomicAdd(&c[cls], 1u);
+            else (tail ? ttask : htask).put((tail ? tbeg : hbeg)[p] + c[cls] + atomicAdd(&cur[p * kClasses + cls], 1u), d);
+        }
+        if (FILL) {
+            const uint4 filler = fs ? make_uint4(0u, 0u, 0u, 0u) : tail ? make_uint4(0xfffffffeu, 0xfffffffeu, 0xfffffffeu, 0xfffffffeu) : make_uint4(~0u, ~0u, ~0u, ~0u);
+            for (uint64_t o = g; o < gather_region_units(g); ++o) (tail ? tpool : spool)[reg + int64_t(o)] = filler;
+        }
+    }
+}
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_task_lists(int64_t n_heavy, const int32_t *__restrict__ order, const int64_t *__restrict__ hoff,
                                                     const uint16_t *__restrict__ hadj, const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj,
@@ -852,7 +938,8 @@ __global__ __launch_bounds__(256) void k_task_lists(int64_t n_heavy, const int32
                                                     uint32_t *__restrict__ cnt, uint32_t *__restrict__ cur, const int64_t *__restrict__ hbeg,
                                                     const int64_t *__restrict__ tbeg, TaskList htask, TaskList ttask,
                                                     int32_t *__restrict__ tunits, unsigned long long *__restrict__ reversed, const uint32_t *__restrict__ spool,
-                                                    const uint32_t *__restrict__ tpool, int32_t inline_limit, int inline_first, int32_t core, int nparts, int part, TcClasses cc) {
+                                                    const uint32_t *__restrict__ tpool, int32_t inline_limit, int inline_first, int32_t core, int nparts, int part, TcClasses cc,
+                                                    const GatherPlan gp) {
     const int kClasses = cc.count();
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
@@ -894,7 +981,24 @@ __global__ __launch_bounds__(256) void k_task_lists(int64_t n_heavy, const int32
             if (reverse && nparts > 1 && shard_of(opos[v], nparts) != part) v = -1;
             // forward: v's rows against u — the first member has no member below it (the edge closes no triangle); the tail ids of the first
             // tail member lie below every tail id of the pivot; a hub member has no tail part
-            const unsigned long long fh = (fwd && i > 0) ? srow[v] : 0ull, fh2 = (fwd && i > 0) ? srow2[v] : 0ull, ft = (fwd && i > hl) ? trow[v] : 0ull;
+            unsigned long long fh = (fwd && i > 0) ? srow[v] : 0ull, fh2 = (fwd && i > 0) ? srow2[v] : 0ull, ft = (fwd && i > hl) ? trow[v] : 0ull;
+            if (gp.R > 0) {  // gathered rows: the units behind a row's last line boundary move to this receiver's gathered row, the entry shrinks (or goes)
+                const uint32_t mh = gather_moved_of(fh, gp.R), mh2 = gather_moved_of(fh2, gp.R), mt = gather_moved_of(ft, gp.R);
+                const int sh_ = gather_slot((uint32_t(fh) >> 22) & 3u), sh2_ = gather_slot((uint32_t(fh2) >> 22) & 3u), st_ = gather_slot((uint32_t(ft) >> 22) & 3u);
+                uint32_t *gc = (FILL ? gp.gcur : gp.gunits) + 4 * pos;
+                for (int slot = 0; slot < kGatherForms; ++slot) {  // the forward entries of a wave all belong to receiver pos: one atomic per gathered row
+                    const uint32_t a = sh_ == slot ? mh : 0u, b = sh2_ == slot ? mh2 : 0u, c = st_ == slot ? mt : 0u;
+                    const uint32_t at = claim_units(gc + slot, a + b, lane), att = claim_units(gc + 2 + slot, c, lane);
+                    if (FILL) {
+                        if (a) gather_copy(gp, false, pos, fh, a, at);
+                        if (b) gather_copy(gp, false, pos, fh2, b, at + a);
+                        if (c) gather_copy(gp, true, pos, ft, c, att);
+                    }
+                }
+                fh = mh ? gather_shrink(fh, mh) : fh;
+                fh2 = mh2 ? gather_shrink(fh2, mh2) : fh2;
+                ft = mt ? gather_shrink(ft, mt) : ft;
+            }
             const bool fh_on = (fh & 0x3fffffull) != 0, fh2_on = (fh2 & 0x3fffffull) != 0, ft_on = (ft & 0x3fffffull) != 0;
             const uint32_t sh = claim_by_class(FILL ? ru : cu, hub_class(cc, fh), fh_on, lane);
             const uint32_t sh2 = claim_by_class(FILL ? ru : cu, hub_class(cc, fh2), fh2_on, lane);
@@ -907,8 +1011,19 @@ __global__ __launch_bounds__(256) void k_task_lists(int64_t n_heavy, const int32
             kept += __popcll(__ballot(fwd));
             if (v >= 0 && reverse) {  // u's rows, cut at v, against v
                 const int64_t pv = opos[v];
-                const unsigned long long rh = ch ? (du_s & ~0x3fffffull) | ch : 0ull, rh2 = ch2 ? (du_s2 & ~0x3fffffull) | ch2 : 0ull,
-                                         rt = ct ? (du_t & ~0x3fffffull) | ct : 0ull;
+                unsigned long long rd[3] = {ch ? (du_s & ~0x3fffffull) | ch : 0ull, ch2 ? (du_s2 & ~0x3fffffull) | ch2 : 0ull, ct ? (du_t & ~0x3fffffull) | ct : 0ull};
+                if (gp.R > 0) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {  // (a cut row is a prefix: it starts where the row starts)
+                        const uint32_t mv = gather_moved_of(rd[k], gp.R);
+                        if (mv == 0) continue;
+                        const int slot = (k == 2 ? 2 : 0) + gather_slot((uint32_t(rd[k]) >> 22) & 3u);
+                        if (!FILL) atomicAdd(&gp.gunits[4 * pv + slot], mv);
+                        else gather_copy(gp, k == 2, pv, rd[k], mv, atomicAdd(&gp.gcur[4 * pv + slot], mv));
+                        rd[k] = gather_shrink(rd[k], mv);
+                    }
+                }
+                const unsigned long long rh = rd[0], rh2 = rd[1], rt = rd[2];
                 uint32_t *cv = cnt + pv * kClasses;
                 if (!FILL) {
                     if (rh) atomicAdd(&cv[hub_class(cc, rh)], 1u);
@@ -1025,7 +1140,7 @@ static void free_tc(gmsx_graph *g) {
     g->htask_entries = g->ttask_entries = g->hitems = g->titems = g->inline_hentries = g->inline_tentries = 0;
     g->n_ledge = g->ledge_total = 0;
     for (int c = 0; c < 8; ++c) g->lpack_base[c] = g->lpack_n[c] = g->lpack_total[c] = 0;
-    g->task_reverse = g->inline_units = g->spool_units = g->tpool_units = 0;
+    g->task_reverse = g->inline_units = g->spool_units = g->tpool_units = g->gather_units = 0;
     g->stats_part = g->stats_nparts = -1;
 }
 
@@ -1521,12 +1636,21 @@ static int build_tc_sets(gmsx_graph *g) {
         DevGuard g_uh{uh};
         if (int rc = dmalloc(&ut, n + 1, nullptr)) return rc;
         DevGuard g_ut{ut};
-        hipLaunchKernelGGL(k_inline_units, dim3(unsigned(n / 256 + 1)), dim3(256), 0, s, n, inl_h, inl_t, uh, ut);
+        hipLaunchKernelGGL(k_inline_units, dim3(unsigned(n / 256 + 1)), dim3(256), 0, s, n, inl_h, inl_t, false, uh, ut);
         if (int rc = exclusive_scan_i64(uh, ihoff, n + 1, s)) return rc;
         if (int rc = exclusive_scan_i64(ut, itoff, n + 1, s)) return rc;
         GMSX_HIP(hipMemcpy(&inline_h_units, ihoff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
         GMSX_HIP(hipMemcpy(&inline_t_units, itoff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
         g->inline_units = inline_h_units + inline_t_units;
+        if (g->tc_gather > 0) {
+            // with gathered rows every row of the pools is whole lines from a line boundary on — the inline rows too: each receiver's starts on a
+            // boundary of the (line-aligned) inline region, at most 7 filler units behind its end (g->inline_units stays what the rows hold)
+            hipLaunchKernelGGL(k_inline_units, dim3(unsigned(n / 256 + 1)), dim3(256), 0, s, n, inl_h, inl_t, true, uh, ut);
+            if (int rc = exclusive_scan_i64(uh, ihoff, n + 1, s)) return rc;
+            if (int rc = exclusive_scan_i64(ut, itoff, n + 1, s)) return rc;
+            GMSX_HIP(hipMemcpy(&inline_h_units, ihoff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
+            GMSX_HIP(hipMemcpy(&inline_t_units, itoff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
+        }
     }
 
     pt.mark("inline row sizes");
@@ -1582,8 +1706,8 @@ static int build_tc_sets(gmsx_graph *g) {
         int64_t big_units = 0, small_units = 0;
         GMSX_HIP(hipMemcpy(&big_units, uoff + n2, sizeof(int64_t), hipMemcpyDeviceToHost));
         GMSX_HIP(hipMemcpy(&small_units, soff + n2, sizeof(int64_t), hipMemcpyDeviceToHost));
-        g->spool_units = big_units + small_units + inline_h_units;
-        inline_h_base = big_units + small_units;
+        inline_h_base = g->tc_gather > 0 ? int64_t(gather_region_units(uint64_t(big_units + small_units))) : big_units + small_units;
+        g->spool_units = inline_h_base + inline_h_units;
         if (g->spool_units >= (int64_t(1) << 40)) return GMSX_ERR_DEVICE_MEM;  // 40 offset bits in a srow entry (16 TB)
         if (int rc = dmalloc(&g->srow, n, g)) return rc;
         if (int rc = dmalloc(&g->srow2, n, g)) return rc;
@@ -1623,7 +1747,7 @@ static int build_tc_sets(gmsx_graph *g) {
         int64_t big_units = 0, small_units = 0;
         GMSX_HIP(hipMemcpy(&big_units, uoff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
         GMSX_HIP(hipMemcpy(&small_units, soff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
-        inline_t_base = big_units + small_units;
+        inline_t_base = g->tc_gather > 0 ? int64_t(gather_region_units(uint64_t(big_units + small_units))) : big_units + small_units;
         g->tpool_units = inline_t_base + inline_t_units;
         if (g->tpool_units >= (int64_t(1) << 40)) return GMSX_ERR_DEVICE_MEM;
         if (int rc = dmalloc(&g->trow, n, g)) return rc;
@@ -1754,10 +1878,32 @@ static int build_tc_sets(gmsx_graph *g) {
         GMSX_HIP(hipMemsetAsync(cur, 0, size_t(n_recv * kClasses + 1) * sizeof(uint32_t), s));
         if (int rc = dmalloc(&g->tunits, n_heavy + 1, g)) return rc;  // only heavy pivots keep or receive entries of edges: by position in `order`
         GMSX_HIP(hipMemsetAsync(g->tunits, 0, size_t(n_heavy + 1) * sizeof(int32_t), s));
-        unsigned long long *totals = nullptr;  // [0] hub inline entries [1] tail inline entries [2] reversed edges [3] rows too long for a task entry
-        if (int rc = dmalloc(&totals, 4, nullptr)) return rc;
+        unsigned long long *totals = nullptr;  // [0] hub inline entries [1] tail inline entries [2] reversed edges [3] rows too long for a task entry [4] units in gathered rows
+        if (int rc = dmalloc(&totals, 5, nullptr)) return rc;
         DevGuard g_tot{totals};
-        GMSX_HIP(hipMemsetAsync(totals, 0, 4 * sizeof(unsigned long long), s));
+        GMSX_HIP(hipMemsetAsync(totals, 0, 5 * sizeof(unsigned long long), s));
+        // gathered rows (device_graph.hpp): GMSX_TC_GATHER = R, the longest remainder behind a row's last line boundary that moves (0 = none)
+        GatherPlan gp{};
+        gp.R = g->tc_gather;  // (build_tc_once: the option, or the default and what it falls back to when the device is short of memory)
+        g->gather_units = 0;
+        int64_t *ghsize = nullptr, *gtsize = nullptr, *ghoff = nullptr, *gtoff = nullptr;
+        DevGuard g_gu{nullptr}, g_gc{nullptr}, g_ghs{nullptr}, g_gts{nullptr}, g_gho{nullptr}, g_gto{nullptr};
+        if (gp.R > 0) {
+            if (int rc = dmalloc(&gp.gunits, 4 * n_recv + 1, nullptr)) return rc;
+            g_gu.p = gp.gunits;
+            if (int rc = dmalloc(&gp.gcur, 4 * n_recv + 1, nullptr)) return rc;
+            g_gc.p = gp.gcur;
+            if (int rc = dmalloc(&ghsize, 2 * n_recv + 1, nullptr)) return rc;
+            g_ghs.p = ghsize;
+            if (int rc = dmalloc(&gtsize, 2 * n_recv + 1, nullptr)) return rc;
+            g_gts.p = gtsize;
+            if (int rc = dmalloc(&ghoff, 2 * n_recv + 1, nullptr)) return rc;
+            g_gho.p = ghoff;
+            if (int rc = dmalloc(&gtoff, 2 * n_recv + 1, nullptr)) return rc;
+            g_gto.p = gtoff;
+            GMSX_HIP(hipMemsetAsync(gp.gunits, 0, size_t(4 * n_recv + 1) * sizeof(uint32_t), s));
+            GMSX_HIP(hipMemsetAsync(gp.gcur, 0, size_t(4 * n_recv + 1) * sizeof(uint32_t), s));
+        }
         int64_t *hcnt = nullptr, *tcnt = nullptr, *hbeg = nullptr, *tbeg = nullptr;
         if (int rc = dmalloc(&hcnt, n_recv + 1, nullptr)) return rc;
         DevGuard g_hc{hcnt};
@@ -1777,12 +1923,52 @@ static int build_tc_sets(gmsx_graph *g) {
         }
         // COUNT
         if (n > 0)
-            hipLaunchKernelGGL(k_inline_entries<false>, dim3(vb), dim3(256), 0, s, n, g->dplus, opos, lidx, n_heavy, g->inline_limit, ihoff, itoff, inline_h_base,
+            hipLaunchKernelGGL(k_inline_entries<false>, dim3(vb), dim3(256), 0, s, n, g->dplus, opos, lidx, n_heavy, g->inline_limit, ihoff, itoff, inl_h, inl_t, inline_h_base,
                                inline_t_base, cnt, cur, hbeg, tbeg, TaskList{}, TaskList{}, totals, cc);
         if (n_heavy > 0)
             hipLaunchKernelGGL(k_task_lists<false>, dim3(grid), dim3(256), 0, s, n_heavy, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->srow, g->srow2, g->ksplit, g->trow,
                                two_sided, opos, cnt, cur, hbeg, tbeg, TaskList{}, TaskList{}, g->tunits,
-                               totals + 2, g->spool, g->tpool, g->inline_limit, g->inline_first, g->tc_core, g->shard_nparts, g->shard_part, cc);
+                               totals + 2, g->spool, g->tpool, g->inline_limit, g->inline_first, g->tc_core, g->shard_nparts, g->shard_part, cc, gp);
+        if (gp.R > 0) {
+            // the regions of the gathered rows: whole lines each, receiver by receiver behind the (line-rounded) end of the pool; the pools grow by them
+            hipLaunchKernelGGL(k_gather_sizes, dim3(unsigned(2 * n_recv / 256 + 1)), dim3(256), 0, s, n_recv, gp.gunits, ghsize, gtsize, totals + 4);
+            if (int rc = exclusive_scan_i64(ghsize, ghoff, 2 * n_recv + 1, s)) return rc;
+            if (int rc = exclusive_scan_i64(gtsize, gtoff, 2 * n_recv + 1, s)) return rc;
+            int64_t gh_units = 0, gt_units = 0;
+            GMSX_HIP(hipMemcpy(&gh_units, ghoff + 2 * n_recv, sizeof(int64_t), hipMemcpyDeviceToHost));
+            GMSX_HIP(hipMemcpy(&gt_units, gtoff + 2 * n_recv, sizeof(int64_t), hipMemcpyDeviceToHost));
+            gp.hoff = ghoff;
+            gp.toff = gtoff;
+            gp.hreg = int64_t(gather_region_units(uint64_t(g->spool_units)));
+            gp.treg = int64_t(gather_region_units(uint64_t(g->tpool_units)));
+            if (gp.hreg + gh_units + kPoolSlack >= (int64_t(1) << 32) || gp.treg + gt_units + kPoolSlack >= (int64_t(1) << 32)) return GMSX_ERR_DEVICE_MEM;  // the grown pools, as above
+            // grow: a new pool with the old one's bytes in front, the filler of the pool (0 / -2) behind them, then the old one goes
+            auto grow = [&](uint32_t *&pool, int64_t &pool_units, int64_t reg, int64_t extra, uint32_t filler) -> int {
+                if (extra == 0) return GMSX_OK;
+                uint32_t *bigger = nullptr;
+                const int64_t units = reg + extra;
+                if (int rc = dmalloc(&bigger, (units + kPoolSlack) * 4, g)) return rc;
+                DevGuard g_b{bigger};
+                GMSX_HIP(hipMemcpyAsync(bigger, pool, size_t(pool_units) * 16, hipMemcpyDeviceToDevice, s));
+                // (every unit of a region is written later — the moved units by FILL, the rest of its last line by k_gather_entries: only the gap in
+                //  front of the regions and the slack behind them are set here)
+                if (reg > pool_units) GMSX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(bigger + pool_units * 4), int(filler), size_t(reg - pool_units) * 4, s));
+                GMSX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(bigger + units * 4), int(filler), size_t(kPoolSlack) * 4, s));
+                GMSX_HIP(hipStreamSynchronize(s));
+                g_b.p = pool;  // the guard frees the old pool
+                g->device_bytes -= (pool_units + kPoolSlack) * 16;
+                pool = bigger;
+                pool_units = units;
+                return GMSX_OK;
+            };
+            if (int rc = grow(g->spool, g->spool_units, gp.hreg, gh_units, 0u)) return rc;
+            if (int rc = grow(g->tpool, g->tpool_units, gp.treg, gt_units, 0xFFFFFFFEu)) return rc;
+            gp.spool = reinterpret_cast<uint4 *>(g->spool);
+            gp.tpool = reinterpret_cast<uint4 *>(g->tpool);
+            if (n_recv > 0)
+                hipLaunchKernelGGL(k_gather_entries<false>, dim3(unsigned(n_recv / 256 + 1)), dim3(256), 0, s, n_recv, gp.gunits, ghoff, gtoff, gp.hreg, gp.treg, cnt, cur, hbeg,
+                                   tbeg, TaskList{}, TaskList{}, gp.spool, gp.tpool, cc);
+        }
         pt.mark("task lists count");
         // class offsets, list offsets
         hipLaunchKernelGGL(k_list_sizes, dim3(unsigned(n_recv / 256 + 1)), dim3(256), 0, s, n_recv, cnt, hcnt, tcnt, cc);
@@ -1796,6 +1982,7 @@ static int build_tc_sets(gmsx_graph *g) {
         g->inline_hentries = int64_t(tot[0]);
         g->inline_tentries = int64_t(tot[1]);
         g->task_reverse = int64_t(tot[2]);
+        if (gp.R > 0) GMSX_HIP(hipMemcpy(&g->gather_units, totals + 4, sizeof(int64_t), hipMemcpyDeviceToHost));
         if (g->htask_entries >= (int64_t(1) << 40) || g->ttask_entries >= (int64_t(1) << 40)) return GMSX_ERR_DEVICE_MEM;  // 40 position bits in a work item
         if (int rc = dmalloc(&g->htask.lo, g->htask_entries + 2, g)) return rc;
         if (int rc = dmalloc(&g->htask.hi, g->htask_entries + 2, g)) return rc;
@@ -1803,11 +1990,14 @@ static int build_tc_sets(gmsx_graph *g) {
         if (int rc = dmalloc(&g->ttask.hi, g->ttask_entries + 2, g)) return rc;
         // FILL
         if (n > 0)
-            hipLaunchKernelGGL(k_inline_entries<true>, dim3(vb), dim3(256), 0, s, n, g->dplus, opos, lidx, n_heavy, g->inline_limit, ihoff, itoff, inline_h_base,
+            hipLaunchKernelGGL(k_inline_entries<true>, dim3(vb), dim3(256), 0, s, n, g->dplus, opos, lidx, n_heavy, g->inline_limit, ihoff, itoff, inl_h, inl_t, inline_h_base,
                                inline_t_base, cnt, cur, hbeg, tbeg, g->htask, g->ttask, totals, cc);
         if (n_heavy > 0)
             hipLaunchKernelGGL(k_task_lists<true>, dim3(grid), dim3(256), 0, s, n_heavy, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->srow, g->srow2, g->ksplit, g->trow,
-                               two_sided, opos, cnt, cur, hbeg, tbeg, g->htask, g->ttask, g->tunits, totals + 2, g->spool, g->tpool, g->inline_limit, g->inline_first, g->tc_core, g->shard_nparts, g->shard_part, cc);
+                               two_sided, opos, cnt, cur, hbeg, tbeg, g->htask, g->ttask, g->tunits, totals + 2, g->spool, g->tpool, g->inline_limit, g->inline_first, g->tc_core, g->shard_nparts, g->shard_part, cc, gp);
+        if (gp.R > 0 && n_recv > 0)
+            hipLaunchKernelGGL(k_gather_entries<true>, dim3(unsigned(n_recv / 256 + 1)), dim3(256), 0, s, n_recv, gp.gunits, ghoff, gtoff, gp.hreg, gp.treg, cnt, cur, hbeg,
+                               tbeg, g->htask, g->ttask, gp.spool, gp.tpool, cc);
         pt.mark("task lists fill");
         // work items
         const int hub_phases = cc.hub_phases();
@@ -1859,17 +2049,29 @@ static int build_tc_sets(gmsx_graph *g) {
 }
 
 static int build_tc_once(gmsx_graph *g) {
-    g->tc_base_bytes = g->device_bytes;
-    g->tc_building = true;
-    const int rc = build_tc_sets(g);
-    g->tc_building = false;
-    g->tc_bytes = g->device_bytes - g->tc_base_bytes;
-    if (rc) {
+    // gathered rows cost device memory (at R = 7 about as much again as all other containers together, and both pools twice while they grow).
+    // GMSX_TC_GATHER set: that R or GMSX_ERR_DEVICE_MEM.  Unset: the default, then 3, then none — a build that fits without gathered rows
+    // is never pushed into passes (or refused) by them.
+    const bool fixed = opt("TC_GATHER") != nullptr;
+    const int tries[3] = {fixed ? std::max(0, std::min(kGatherMax, int(opt_int("TC_GATHER", kTcGatherDefault)))) : kTcGatherDefault, 3, 0};
+    int rc = GMSX_OK;
+    for (int k = 0; k < (fixed ? 1 : 3); ++k) {
+        if (k > 0 && tries[k] >= tries[k - 1]) continue;
+        g->tc_gather = tries[k];
+        g->tc_base_bytes = g->device_bytes;
+        g->tc_building = true;
+        rc = build_tc_sets(g);
+        g->tc_building = false;
+        g->tc_bytes = g->device_bytes - g->tc_base_bytes;
+        if (rc == GMSX_OK) {
+            g->tc_ready = true;
+            return GMSX_OK;
+        }
         free_tc(g);
-        return rc;
+        if (rc != GMSX_ERR_DEVICE_MEM) return rc;
+        (void)hipGetLastError();
     }
-    g->tc_ready = true;
-    return GMSX_OK;
+    return rc;
 }
 
 int ensure_tc(const gmsx_graph *cg) {

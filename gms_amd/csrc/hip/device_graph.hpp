@@ -169,6 +169,20 @@ struct gmsx_graph {
     int inline_first = 64;               // a HEAVY pivot hands the edges to its first inline_first members (<= 64) over inline rows as well
     int32_t inline_limit = 0;            // light pivots hand their edges to members of rank id < inline_limit (and to heavy ones) as INLINE ROWS
     int64_t inline_units = 0;            // 16-byte units of all inline rows (inside spool / tpool)
+    // GATHERED ROWS (GMSX_TC_GATHER = R > 0; the rule: host/tc_gather_plan.hpp).  A stream row that ends inside a 128-byte line costs the whole
+    // line, and the rows of >= 8 units start on line boundaries, so every one of them ends in such a line.  The units of every form but the
+    // bitset are self-contained (plain ids; base + count + gaps) and the count of an item is a sum over units, whichever row they sit in: the r
+    // units behind a row's last line boundary (0 < r <= R; a whole row of <= R units) are COPIED into a gathered row of the receiving pivot
+    // and the entry names the whole lines in front of them only (no entry when nothing is left).  A receiver has four gathered rows — hub list
+    // units, hub delta units, tail list units, tail delta units — each densely packed in a line-aligned region of its own behind the
+    // (line-rounded) end of spool / tpool, which grow by these regions after the task lists are counted; a region is rounded up to whole lines
+    // with fillers of its form (0xFFFF ids, -2 ids, a delta unit of count 0).  A gathered row is named by ordinary entries of its form, chunks
+    // of 64 units like an inline row's (the last one shorter), which take their class slots before the lists are cut into work items: the
+    // kernels see nothing new.  The 12-bit-gap rows (off by default) are left as they are.  With R > 0 the inline rows are laid out on line
+    // boundaries as well (the inline region and every receiver's rows in it start on one, fillers behind a row's end), so that every row an
+    // entry names is whole lines from a boundary on, or the one partial line at the end of an inline or a gathered row.
+    int tc_gather = 0;                   // R the containers were built with
+    int64_t gather_units = 0;            // 16-byte units moved into gathered rows (inside spool / tpool, behind the inline rows)
     unsigned long long *trow = nullptr;
     uint32_t *tpool = nullptr;
     int64_t tpool_units = 0;

@@ -15,6 +15,9 @@
 //   * u light: the members of u below v are COPIED into v's inline rows (v heavy or a popular target, rank id < inline_limit) —
 //     a 20-byte row behind a pointer would cost a 128-byte line per fetch, inline it is streamed; only far light members v stay
 //     with u and the light-pivot kernel.
+//   * GATHERED ROWS (GMSX_TC_GATHER, device_graph.hpp): a list or delta row that ends inside a 128-byte line leaves the units behind its last
+//     line boundary to a densely packed row of the receiving pivot — units are self-contained and an item's count is a sum over units — so
+//     the rows the entries name are whole lines: the L2 fetches none for a few units.  Nothing below knows: a gathered row is entries too.
 // Kernel shape, Roaring-style sets:
 //   1. every receiving vertex owns a HUB-entry list and a TAIL-entry list of 8-byte stream-row descriptors, laid out class by class
 //      (form x length step) at build time; a WORK ITEM is <= 1024 consecutive entries of one list, one workgroup each.  k_tc_block runs
@@ -1041,7 +1044,9 @@ __global__ __launch_bounds__(256) void k_tc_item_stats(const int64_t *__restrict
 //   out[11..14] counts: entries, inline entries, work items, light edges
 //   out[15]    the core (k_tc_core): per 64 x 64 block the fragment bytes of its 2 x 64 rows and its mask words, no reuse assumed (host)
 //   out[16]    K, the rank ids below which an edge belongs to the core (0 = none)
-//   out[17..20] reserved (0)
+//   out[17]    of out[0] + out[2] + out[3] + out[4]: gathered rows (units moved out of rows' partial last lines, GMSX_TC_GATHER; host, from the build's figure)
+//   out[18]    128 x the 128-byte lines the rows named by all entries touch (from first unit and units): what the item kernels' row traffic beyond the L2 should approach
+//   out[19]    non-bitset entries whose row ends inside a line          out[20]  R the containers were built with (GMSX_TC_GATHER, or what its default fell back to; host)
 __global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj, const int64_t *__restrict__ toff, const int32_t *__restrict__ tadj,
                                                       const int32_t *__restrict__ dplus, const int32_t *__restrict__ order,
                                                       const TaskList htask, const gmsx_tc_item *__restrict__ hitem, int64_t hitems,
@@ -1052,6 +1057,7 @@ __global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict_
     const int64_t wave0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
     unsigned long long c[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long lines = 0, partial = 0;
     for (int64_t q = wave0; q < hitems + titems; q += nwaves) {
         const bool tail = q >= hitems;
         const gmsx_tc_item &it = tail ? titem[q - hitems] : hitem[q];
@@ -1070,6 +1076,9 @@ __global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict_
             if (tail) c[fd == kFormDelta ? 4 : 3] += db;
             else c[fd == kFormList ? 0 : fd == kFormBitset ? 1 : 2] += db;
             c[5] += 6;
+            const unsigned long long first = d >> 24, end = first + (d & 0x3fffffull);
+            lines += ((end + 7) >> 3) - (first >> 3);
+            partial += ((tail || fd != kFormBitset) && (end & 7ull)) ? 1 : 0;
         }
     }
     for (int64_t pos = first_light + wave0; pos < end_light; pos += nwaves) {
@@ -1098,6 +1107,12 @@ __global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict_
         for (int s = 32; s > 0; s >>= 1) x += __shfl_down(x, s);
         if (lane == 0 && x) atomicAdd(&out[k], x);
     }
+    for (int s = 32; s > 0; s >>= 1) {
+        lines += __shfl_down(lines, s);
+        partial += __shfl_down(partial, s);
+    }
+    if (lane == 0 && lines) atomicAdd(&out[18], 128ull * lines);
+    if (lane == 0 && partial) atomicAdd(&out[19], partial);
 }
 
 // Diagnostics behind gmsx_tc_row_histogram: how the stream rows the work items read are distributed over row lengths (a group of W
@@ -1105,6 +1120,8 @@ __global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict_
 // bitset / byte-delta, tail rows as list / delta; bin: 1…16 units exactly, then 17-32, 33-64, … 1025+.  out[240…243]: entries, inline
 // entries, work items, pivots' own container bytes; out[248…251]: Σ over the oriented edges (u,v) of heavy then light pivots u of the
 // stream units of v's rows and of min(units of u's rows, units of v's rows) — what the smaller-endpoint rule is about.
+// (An entry is a row here: the chunks of inline rows and of gathered rows — GMSX_TC_GATHER — count as rows of up to 64 units, and a row that
+// left its remainder to a gathered row counts with the length it kept.  GMSX_TC_GATHER=0 shows the rows as the vertices own them.)
 __device__ __forceinline__ int hist_bin(unsigned long long units) {
     if (units <= 16) return int(units) - 1;
     int b = 16;
@@ -1500,6 +1517,8 @@ int gmsx_tc_stream_breakdown(const gmsx_graph *g, uint64_t *out21) {
         GMSX_HIP(hipGetLastError());
         out21[7] = uint64_t(g->inline_units) * 16ull;                         // the build's figures: the entries do not say what they name
         out21[12] = uint64_t(g->inline_hentries + g->inline_tentries);
+        out21[17] = uint64_t(g->gather_units) * 16ull;
+        out21[20] = uint64_t(g->tc_gather);
         out21[15] = core_bytes_of(g, 0, 1);
         out21[16] = uint64_t(g->tc_core);
         return GMSX_OK;

@@ -764,7 +764,7 @@ Option g_options[] = {
     {"INLINE_LIMIT", "", false}, {"TC_INLINE_FIRST", "", false}, {"TC_DELTA", "", false}, {"TC_DELTA_PCT", "", false}, {"TC_GAP12", "", false},
     {"TC_HYBRID", "", false}, {"TC_TAIL_DELTA", "", false}, {"TC_TWO_SIDED", "", false}, {"TC_HOT_WINDOWS", "", false}, {"TC_HOT_KB", "", false},
     {"TC_HOT_MIN", "", false}, {"TC_TEST_MAX_UNITS", "", false}, {"TC_KEEP_ROWS", "", false}, {"TC_MEM_LIMIT_MB", "", false}, {"TC_OVERLAP", "", false},
-    {"TC_PERSIST", "", false}, {"TC_ITEM_WGS", "", false}, {"TC_CORE", "", false}, {"TC_LIGHT_PACKED", "", false}, {"SORT_CHUNK", "", false}, {"UPLOAD_STAGED", "", false}, {"INIT_LAZY", "", false},
+    {"TC_PERSIST", "", false}, {"TC_ITEM_WGS", "", false}, {"TC_CORE", "", false}, {"TC_LIGHT_PACKED", "", false}, {"TC_GATHER", "", false}, {"SORT_CHUNK", "", false}, {"UPLOAD_STAGED", "", false}, {"INIT_LAZY", "", false},
     // k-clique (kclique.hip)
     {"KC_SLAB_MB", "", false}, {"KC_MAXD", "", false}, {"KC_STREAMS", "", false},
     {"KC_REVERSE", "", false}, {"KC_REV_MIN", "", false}, {"KC_REV_FACTOR", "", false}, {"KC_REV_TAIL", "", false}, {"KC_REV_TAIL_MIN", "", false}, {"KC_TRI", "", false}, {"KC_MFMA", "", false}, {"KC_POOL_MB", "", false},

@@ -132,7 +132,10 @@ int gmsx_set_host_threads(int n);
  *                   streamed; -1 = K chosen from the graph, a multiple of 1024 or 0 (the default), 0 = no core, N > 0 = K = N; always clamped
  *                   to min(hub ids, n, 32768)), TC_LIGHT_PACKED (read when the containers are built: 1, the default = the edges between two
  *                   light vertices as packed blocks of ids, streamed and compared by search; 0 = as 32-byte pointer records, gathered and
- *                   compared all-pairs)
+ *                   compared all-pairs), TC_GATHER (read when the containers are built: R = 0 … 7, default 7 (3, then 0, when the device is short of memory) — a stream row that ends inside
+ *                   a 128-byte line leaves the R or fewer 16-byte units behind its last line boundary, and a whole row of R or fewer units,
+ *                   to a densely packed gathered row of the receiving pivot, so that the row itself is whole lines; bitset rows never; 0 = no
+ *                   gathered rows: the task lists of the layout without them)
  *   k-clique        KC_MAXD (widest pivot of the bit-matrix kernels), KC_SLAB_MB (budget of the global slabs), KC_STREAMS (1 … 4 streams for the bins),
  *                   KC_REVERSE (0 = every member row streamed forward: no reverse rows; like KC_REV_* read when the lists of a graph are built, i.e. at its first k-clique call), KC_REV_MIN (edges a hub
  *                   receiver must get to take them, default 64), KC_REV_FACTOR (10 x how much cheaper in bytes the reverse side must be; default 0: every hub edge whose receiver qualifies),
@@ -272,7 +275,11 @@ int gmsx_tc_divisor(int algo); /* 1 for ORIENTED/AUTO, 3 for FULL */
  * out[0] + out[3] that is inline rows (ids handed over by light pivots); out[8..10]: the light-pivot kernel — hub rows, tail rows of
  * the far light members it streams, and its own lists + descriptors; out[11..14]: counts — entries, inline entries, work items,
  * members streamed by the light-pivot kernel; out[15]: the dense core (TC_CORE) — per 64 x 64 block the fragment bytes of its 2 x 64 rows
- * and its mask words, no reuse assumed; out[16]: K of the core (0 = none); out[17..20]: 0.  out[0..6] + out[8..10] + out[15] = stream_bytes.
+ * and its mask words, no reuse assumed; out[16]: K of the core (0 = none); out[17]: the part of
+ * out[0] + out[2] + out[3] + out[4] that is gathered rows (TC_GATHER); out[18]: 128 x the 128-byte lines that the rows named by all entries
+ * touch — what the row traffic of the item kernels beyond the L2 should approach; out[19]: non-bitset entries whose row ends inside a
+ * line; out[20]: the R the containers were built with — TC_GATHER, or what its default fell back to (7, 3, 0) when the gathered rows did not fit
+ * the device or the 32-bit first-unit field of a task entry.  out[0..6] + out[8..10] + out[15] = stream_bytes.
  * 21 values, host. */
 int gmsx_tc_stream_breakdown(const gmsx_graph *g, uint64_t *out21);
 /* Diagnostics: the stream rows named by the work items' entries as a histogram over row length in 16-byte units — out[(cls*24 +
