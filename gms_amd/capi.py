@@ -31,7 +31,7 @@ COMM_ID_BYTES = 128
 SYMBOLS = [
     "gmsx_strerror", "gmsx_version",
     "gmsx_csr_generate", "gmsx_csr_generate_rmat", "gmsx_csr_from_edges", "gmsx_csr_load", "gmsx_csr_save_sg", "gmsx_csr_save_sgx", "gmsx_csr_is_mapped", "gmsx_csr_from_arrays",
-    "gmsx_csr_worth_relabelling", "gmsx_csr_relabel_by_degree", "gmsx_csr_num_nodes", "gmsx_csr_num_edges",
+    "gmsx_csr_pick_sources", "gmsx_csr_worth_relabelling", "gmsx_csr_relabel_by_degree", "gmsx_csr_num_nodes", "gmsx_csr_num_edges",
     "gmsx_csr_num_edges_directed", "gmsx_csr_offsets", "gmsx_csr_neighbors", "gmsx_csr_merge_elements",
     "gmsx_csr_fingerprint", "gmsx_csr_free", "gmsx_set_host_threads", "gmsx_set_option", "gmsx_reset_options", "gmsx_option_name",
     "gmsx_init", "gmsx_set_stream", "gmsx_device_info", "gmsx_hbm_read_probe",
@@ -45,6 +45,7 @@ SYMBOLS = [
     "gmsx_link_prediction", "gmsx_link_prediction_precision",
     "gmsx_subgraph_order", "gmsx_subgraph_match",
     "gmsx_connected_components", "gmsx_jarvis_patrick",
+    "gmsx_bfs", "gmsx_betweenness",
     "gmsx_cycle4_count", "gmsx_cycle4_partial", "gmsx_motif_census4",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -137,6 +138,26 @@ class ComponentsInfo(C.Structure):
 
 
 MOTIFS = ("wedge", "triangle", "star3", "path4", "paw", "cycle4", "diamond", "clique4")  # GMSX_MOTIF_*: the index of a name is its value
+
+
+class BfsInfo(C.Structure):
+    _fields_ = [("reached", C.c_int64), ("reached_arcs", C.c_int64), ("depth_sum", C.c_int64), ("widest", C.c_int64),
+                ("levels", C.c_int32), ("widest_level", C.c_int32), ("bottom_up_levels", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("reached", "reached_arcs", "depth_sum", "widest", "levels", "widest_level", "bottom_up_levels")}
+
+
+BC_DEFAULT, BC_EXCLUDE_SOURCE, BC_NORMALIZE_MAX = 0, 1, 2
+
+
+class BcInfo(C.Structure):
+    _fields_ = [("sources", C.c_int64), ("reached_total", C.c_int64), ("max_levels", C.c_int32), ("reserved", C.c_int32),
+                ("max_score", C.c_double), ("max_sigma", C.c_double)]
+
+    def as_dict(self):
+        return {"sources": int(self.sources), "reached_total": int(self.reached_total), "max_levels": int(self.max_levels),
+                "max_score": float(self.max_score), "max_sigma": float(self.max_sigma)}
 
 
 class MotifInfo(C.Structure):
@@ -318,6 +339,9 @@ def lib():
                                       C.POINTER(SubgraphInfo), sp]
     L.gmsx_connected_components.argtypes = [vp, C.c_void_p, C.c_void_p, C.POINTER(ComponentsInfo), sp]
     L.gmsx_jarvis_patrick.argtypes = [vp, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(ComponentsInfo), sp]
+    L.gmsx_bfs.argtypes = [vp, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(BfsInfo), sp]
+    L.gmsx_betweenness.argtypes = [vp, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(BcInfo), sp]
+    L.gmsx_csr_pick_sources.argtypes = [vp, C.c_int64, C.c_int32, C.c_void_p]
     L.gmsx_cycle4_count.argtypes = [vp, u64p, C.c_void_p, sp]
     L.gmsx_cycle4_partial.argtypes = [vp, C.c_int, C.c_int, u64p, sp]
     L.gmsx_motif_census4.argtypes = [vp, C.POINTER(MotifInfo), sp]
@@ -431,6 +455,12 @@ class HostCSR:
 
     def merge_elements(self):
         return int(lib().gmsx_csr_merge_elements(self._h))
+
+    def pick_sources(self, count, given=-1):
+        """gmsx_csr_pick_sources: the first `count` picks of the reference's SourcePicker (int32[count]); given >= 0: `count` copies of it."""
+        out = np.zeros(max(int(count), 1), dtype=np.int32)
+        _check(lib().gmsx_csr_pick_sources(self._h, int(count), int(given), out.ctypes.data_as(C.c_void_p)), "gmsx_csr_pick_sources")
+        return out[:int(count)]
 
     def fingerprint(self):
         return int(lib().gmsx_csr_fingerprint(self._h, 0)), int(lib().gmsx_csr_fingerprint(self._h, 1))
@@ -950,6 +980,29 @@ class DeviceGraph:
         _check(lib().gmsx_jarvis_patrick(self._h, int(metric), float(threshold), label.ctypes.data_as(C.c_void_p),
                                          mask.ctypes.data_as(C.c_void_p) if want_mask else None, C.byref(info), C.byref(st)), "gmsx_jarvis_patrick")
         r = (label[:n], info.as_dict()) + ((mask[:nnz],) if want_mask else ())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def bfs(self, source, want_depth=True, want_parent=True, stats=False):
+        """gmsx_bfs from `source`: (depth int32[n] or None, parent int32[n] or None, {reached, reached_arcs, depth_sum, widest, levels,
+        widest_level, bottom_up_levels}).  parent[v] is the smallest-id neighbour of v one level up; -1 = unreachable."""
+        n = self.num_nodes
+        depth = np.zeros(max(n, 1), dtype=np.int32) if want_depth else None
+        parent = np.zeros(max(n, 1), dtype=np.int32) if want_parent else None
+        info, st = BfsInfo(), Stats()
+        _check(lib().gmsx_bfs(self._h, int(source), depth.ctypes.data_as(C.c_void_p) if want_depth else None,
+                              parent.ctypes.data_as(C.c_void_p) if want_parent else None, C.byref(info), C.byref(st)), "gmsx_bfs")
+        r = (depth[:n] if want_depth else None, parent[:n] if want_parent else None, info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def betweenness(self, sources, exclude_source=False, normalize=False, stats=False):
+        """gmsx_betweenness over the listed sources: (scores float64[n], {sources, reached_total, max_levels, max_score, max_sigma})."""
+        n = self.num_nodes
+        src = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        flags = (BC_EXCLUDE_SOURCE if exclude_source else 0) | (BC_NORMALIZE_MAX if normalize else 0)
+        scores, info, st = np.zeros(max(n, 1), dtype=np.float64), BcInfo(), Stats()
+        _check(lib().gmsx_betweenness(self._h, src.size, src.ctypes.data_as(C.c_void_p) if src.size else None, flags,
+                                      scores.ctypes.data_as(C.c_void_p), C.byref(info), C.byref(st)), "gmsx_betweenness")
+        r = (scores[:n], info.as_dict())
         return (r + (st.as_dict(),)) if stats else r
 
     def cycle4_count(self, at_vertex=False, stats=False):

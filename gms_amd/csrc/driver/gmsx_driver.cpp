@@ -49,7 +49,16 @@
 //                    "Trial Time", the eight motifs as "name: non-induced induced N", "Wedges Walked", "Max Codegree" and with -v "Verification" — the
 //                    counting rule of the 4-cycle kernels as this driver's own serial loop over the host CSR, the degree sums, the triangle count and
 //                    the induced / non-induced identities —, then the "@@@" line.  Not sharded (--gpus > 1 is refused).
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  bfs [-r SOURCE]   the reference's BFS driver (representations/graphs/log_graph/bfs.cc:261-275: DOBFS from SourcePicker's sources, PrintBFSStats,
+//                    BFSVerifier) on the device (gmsx_bfs): trial t starts from the t-th picked source (-r: always SOURCE); per trial "Trial Time", "Source",
+//                    "Levels", "Bottom-up Levels" and with -v "Verification" — BFSVerifier's checks (bfs.cc:212-258) as this driver's own serial BFS —,
+//                    then the "@@@" line; after the last trial PrintBFSStats' line (bfs.cc:193-204).  Not sharded (--gpus > 1 is refused).
+// Added:  bc [-r SOURCE] [-i ITERS]   the reference's betweenness driver (log_graph/bc.cc:235-253: Brandes from ITERS picked sources per trial — the
+//                    picker runs on across the trials —, PrintTopScores, BCVerifier) on the device (gmsx_betweenness, normalised): per trial "Trial
+//                    Time", "Max Score" and with -v "Verification" — BCVerifier's serial Brandes (bc.cc:172-232) in double, held to the derived bound
+//                    2 eps (L (d + 2) + S + 1) of include/gmsx.h's definition plus 2 eps for the normalisation —, then the "@@@" line; after the
+//                    last trial PrintTopScores' five id:score lines (bc.cc:156-164; ties: the smaller id).  Not sharded.
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -88,6 +97,9 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     std::string pattern_file;  // sgi -p pattern-file=FILE
     bool mono = false;         // sgi --mono
     double threshold = std::nan("");  // jp --threshold X
+    bool metric_given = false;
+    int64_t start = -1;  // bfs, bc -r SOURCE (gapbs/command_line.h: start_vertex)
+    int64_t iters = 1;   // bc -i ITERS
     int error = 0;
 };
 
@@ -121,7 +133,9 @@ Args parse(int argc, char **argv) {
         else if (f == "-g" || f == "--gen") { if (!need(2)) break; a.gen = argv[++i]; a.scale = std::atoi(argv[++i]); }
         else if (f == "--deg") { if (!need(1)) break; a.deg = std::atoi(argv[++i]); }
         else if (f == "--list") { if (!need(1)) break; a.list = argv[++i]; }
-        else if (f == "--metric") { if (!need(1)) break; a.metric = argv[++i]; }
+        else if (f == "--metric") { if (!need(1)) break; a.metric = argv[++i]; a.metric_given = true; }
+        else if (f == "-r") { if (!need(1)) break; a.start = std::atoll(argv[++i]); if (a.start < 0 || a.start > INT32_MAX) a.error = 100; }
+        else if (f == "-i") { if (!need(1)) break; a.iters = std::atoll(argv[++i]); if (a.iters < 1) a.error = 100; }
         else if (f == "-q") { if (!need(1)) break; a.q = std::atoll(argv[++i]); if (a.q < 1) a.error = 100; }
         else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; }
         else if (f == "--mono") a.mono = true;
@@ -150,6 +164,9 @@ Args parse(int argc, char **argv) {
     if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp" && a.kernel != "sgi") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
     if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss" || a.kernel == "sgi" || a.kernel == "cc" || a.kernel == "jp" || a.kernel == "motifs") && a.gpus > 1) a.error = 100;
     if (!a.error && ((a.kernel == "jp") != !std::isnan(a.threshold))) a.error = 100;  // the threshold is required, and only there
+    const bool traversal = a.kernel == "bfs" || a.kernel == "bc";
+    if (!a.error && traversal && (a.gpus > 1 || a.metric_given)) a.error = 100;  // a traversal is global; it has no metric
+    if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc"))) a.error = 100;
     if (!a.error && ((a.kernel == "sgi") != !a.pattern_file.empty() || (a.mono && a.kernel != "sgi"))) a.error = 100;  // util/command_line.hpp:22: the pattern is required
     if (!a.error && (a.kernel == "lp" || a.kernel == "jp") && lp_metric(a.metric) < 0) a.error = 100;
     if (!a.error && !a.order.empty() && a.kernel != "bk" && a.kernel != "color") a.error = 100;  // only Bron–Kerbosch and the colouring have a preprocessing step
@@ -162,10 +179,10 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
                 "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE] "
-                "[jp: --metric NAME --threshold X]\n", argv0);
+                "[jp: --metric NAME --threshold X] [bfs, bc: -r SOURCE] [bc: -i ITERS]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -619,6 +636,140 @@ int run_components(const Args &args, const gmsx::HipSetGraph &g, const HostGraph
     return 0;
 }
 
+// BFSVerifier (bfs.cc:212-258) as this driver's own loop: a serial BFS from the source; the source is its own parent, every other reached vertex
+// has a parent that is a neighbour one level up, and exactly the unreachable vertices have -1.  `depth` is held to the serial depths, too.
+bool verify_bfs(const HostGraph &hg, int32_t source, const std::vector<int32_t> &parent, const std::vector<int32_t> &depth_got) {
+    std::vector<int32_t> depth(size_t(hg.n), -1), to_visit;
+    to_visit.reserve(size_t(hg.n));
+    depth[size_t(source)] = 0;
+    to_visit.push_back(source);
+    for (size_t at = 0; at < to_visit.size(); ++at) {
+        const int32_t u = to_visit[at];
+        for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j)
+            if (depth[size_t(hg.adj[j])] == -1) {
+                depth[size_t(hg.adj[j])] = depth[size_t(u)] + 1;
+                to_visit.push_back(hg.adj[j]);
+            }
+    }
+    for (int64_t u = 0; u < hg.n; ++u) {
+        if (depth_got[size_t(u)] != depth[size_t(u)]) return false;
+        const int32_t p = parent[size_t(u)];
+        if (depth[size_t(u)] != -1 && p != -1) {
+            if (u == source) {
+                if (p != u) return false;
+                continue;
+            }
+            if (p < 0 || p >= hg.n || depth[size_t(p)] != depth[size_t(u)] - 1) return false;
+            if (!std::binary_search(hg.row(int32_t(u)), hg.row(int32_t(u)) + hg.deg(int32_t(u)), p)) return false;
+        } else if (depth[size_t(u)] != p) {
+            return false;
+        }
+    }
+    return true;
+}
+
+// BCVerifier (bc.cc:172-232) in double: serial Brandes from the same sources, normalised; returns whether `got` (normalised) lies within
+// 2 eps (L (d + 2) + S + 1) want + 2 eps want of it — the bound of include/gmsx.h's definition while every path count is exact (below 2^53);
+// beyond that 2 eps (L ((d + 2) + 2 L d) + S + 1) want + 2 eps want, and a line says so
+bool verify_bc(const HostGraph &hg, const std::vector<int32_t> &sources, const std::vector<double> &got) {
+    const size_t n = size_t(hg.n);
+    std::vector<double> scores(n, 0.0), sigma(n), delta(n);
+    std::vector<int32_t> depth(n), order;
+    order.reserve(n);
+    int64_t max_levels = 0, max_degree = 0;
+    double max_sigma = 0.0;
+    for (int64_t v = 0; v < hg.n; ++v) max_degree = std::max(max_degree, hg.deg(int32_t(v)));
+    for (const int32_t s : sources) {
+        std::fill(depth.begin(), depth.end(), -1);
+        std::fill(sigma.begin(), sigma.end(), 0.0);
+        std::fill(delta.begin(), delta.end(), 0.0);
+        order.clear();
+        depth[size_t(s)] = 0;
+        sigma[size_t(s)] = 1.0;
+        order.push_back(s);
+        for (size_t at = 0; at < order.size(); ++at) {
+            const int32_t u = order[at];
+            for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j) {
+                const int32_t v = hg.adj[j];
+                if (depth[size_t(v)] == -1) {
+                    depth[size_t(v)] = depth[size_t(u)] + 1;
+                    order.push_back(v);
+                }
+                if (depth[size_t(v)] == depth[size_t(u)] + 1) sigma[size_t(v)] += sigma[size_t(u)];
+            }
+        }
+        for (size_t at = order.size(); at-- > 0;) {
+            const int32_t u = order[at];
+            for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j) {
+                const int32_t v = hg.adj[j];
+                if (depth[size_t(v)] == depth[size_t(u)] + 1) delta[size_t(u)] += sigma[size_t(u)] / sigma[size_t(v)] * (1 + delta[size_t(v)]);
+            }
+            scores[size_t(u)] += delta[size_t(u)];
+            max_sigma = std::max(max_sigma, sigma[size_t(u)]);
+        }
+        max_levels = std::max<int64_t>(max_levels, depth[size_t(order.back())] + 1);
+    }
+    const double biggest = n ? *std::max_element(scores.begin(), scores.end()) : 0.0;
+    const double eps = 1.1102230246251565e-16, L = double(max_levels), d = double(max_degree), S = double(sources.size());
+    // beyond 2^53 the counts themselves carry up to L d eps and enter a term twice: the wider bound of the same derivation, per source
+    const bool exact = max_sigma < 9007199254740992.0;
+    if (!exact) std::printf("%-21s%s\n", "Path Counts:", "beyond 2^53: held to the bound of inexact counts");
+    const double factor = (exact ? 2.0 * eps * (L * (d + 2.0) + S + 1.0) : 2.0 * eps * (L * ((d + 2.0) + 2.0 * L * d) + S + 1.0)) + 2.0 * eps;
+    for (size_t v = 0; v < n; ++v) {
+        const double want = biggest > 0.0 ? scores[v] / biggest : 0.0;
+        if (!(std::fabs(got[v] - want) <= factor * want)) return false;
+    }
+    return true;
+}
+
+// breadth-first search (bfs) and betweenness centrality (bc) under the usual trial loop, with PrintBFSStats' / PrintTopScores' lines at the end
+int run_traversal(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg, const gmsx_csr *csr) {
+    const bool bc = args.kernel == "bc";
+    if (args.start >= hg.n) { std::printf("-r %lld: the graph has %lld vertices\n", (long long)args.start, (long long)hg.n); return 100; }
+    const int64_t per_trial = bc ? args.iters : 1;
+    std::vector<int32_t> picks(size_t(per_trial * std::max<int64_t>(args.trials, 0)) + 1);
+    if (int rc = gmsx_csr_pick_sources(csr, int64_t(picks.size()) - 1, int32_t(args.start), picks.data())) {
+        std::printf("no source to pick: %s\n", gmsx_strerror(rc));
+        return 2;
+    }
+    double total_seconds = 0;
+    Timer t;
+    std::vector<int32_t> parent, depth;
+    std::vector<double> scores;
+    gmsx_bfs_info info{};
+    gmsx_bc_info bi{};
+    for (int64_t it = 0; it < args.trials; ++it) {
+        const std::vector<int32_t> sources(picks.begin() + it * per_trial, picks.begin() + (it + 1) * per_trial);
+        t.Start();
+        if (bc) gmsx::betweenness(g, sources, scores, GMSX_BC_NORMALIZE_MAX, &bi);
+        else gmsx::bfs(g, sources[0], parent, &depth, &info);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        if (bc) {
+            std::printf("%-21s%g\n", "Max Score:", bi.max_score);
+            if (args.verify) PrintLabel("Verification", verify_bc(hg, sources, scores) ? "PASS" : "FAIL");
+            std::cout << "@@@ betweenness" << std::endl;
+        } else {
+            PrintLabel("Source", std::to_string(sources[0]));
+            PrintLabel("Levels", std::to_string(info.levels));
+            PrintLabel("Bottom-up Levels", std::to_string(info.bottom_up_levels));
+            if (args.verify) PrintLabel("Verification", verify_bfs(hg, sources[0], parent, depth) ? "PASS" : "FAIL");
+            std::cout << "@@@ bfs" << std::endl;
+        }
+    }
+    if (args.trials > 0 && !bc) std::cout << "BFS Tree has " << info.reached << " nodes and " << info.reached_arcs << " edges" << std::endl;
+    if (args.trials > 0 && bc) {
+        std::vector<std::pair<double, int32_t>> top;  // (-score, id): ascending = largest first, ties by the smaller id
+        for (int64_t v = 0; v < hg.n; ++v) top.emplace_back(-scores[size_t(v)], int32_t(v));
+        const size_t k = std::min<size_t>(5, top.size());
+        std::partial_sort(top.begin(), top.begin() + k, top.end());
+        for (size_t i = 0; i < k; ++i) std::cout << top[i].second << ":" << -top[i].first << std::endl;
+    }
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
 // subgraph matching: the reference's VF2 drivers (subgraphiso_vf2_sequential.cpp:33-51) over gmsx::subgraph_isomorphisms
 int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
     gmsx_csr *pc = nullptr;
@@ -680,7 +831,7 @@ int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -754,8 +905,8 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs") {
-        const int rc_run = args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc") {
+        const int rc_run = (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
                                                                                                                                         : run_components(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);

@@ -20,6 +20,8 @@
 //   long_walk(x, note, tid, threads, q)       the part of the parked row x that thread tid of `threads` walks
 //   settle(x, note, round, tid, error)        kNotes only: every thread of ONE workgroup of kTailThreads, behind the walks (may hold barriers)
 //   finish()                                  every thread, at the end of a kernel
+//   kStops, round_stop()                      optional: ONE thread at every round boundary, behind all appends of the round; true ends the step
+//                                             there (the tail returns, and the policy tells the host through its own control block)
 #pragma once
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
@@ -27,9 +29,16 @@
 #include <algorithm>
 #include <climits>
 #include <cstring>
+#include <type_traits>
 
 namespace gmsx {
 namespace {
+
+// does policy P decide at a round boundary whether the rounds go on (P::kStops, P::round_stop)?
+template <class P, class = void>
+struct policy_stops : std::false_type {};
+template <class P>
+struct policy_stops<P, std::void_t<decltype(P::kStops)>> : std::true_type {};
 
 // UNMEASURED: none of these bounds is tuned yet (tools/core_probe.py and tools/coloring_probe.py are the measurement).  They
 // follow the round table of the peel on R-MAT graphs (almost every round holds fewer than 256 vertices) and the row shapes named there.
@@ -161,6 +170,7 @@ __global__ __launch_bounds__(kTailThreads) void k_frontier_advance(P p, const in
         ctrl->nlong = 0;
         ctrl->round += 1;
         ctrl->cur ^= 1;
+        if constexpr (policy_stops<P>::value) p.round_stop();
     }
 }
 
@@ -250,6 +260,12 @@ __global__ __launch_bounds__(kTailThreads) void k_frontier_tail(P p, int32_t *__
             s_work = 0;
         }
         __syncthreads();
+        if constexpr (policy_stops<P>::value) {  // (s_stop is written again only behind the barriers of the next round)
+            __shared__ int32_t s_stop;
+            if (tid == 0) s_stop = p.round_stop() ? 1 : 0;
+            __syncthreads();
+            if (s_stop) break;
+        }
     }
     p.finish();
     if (tid == 0) {
@@ -265,14 +281,17 @@ __global__ __launch_bounds__(kTailThreads) void k_frontier_tail(P p, int32_t *__
 }
 
 // The host's round loop: steps until the frontier that the mirror h (Ctrl: derived from FrontierCtrl, read back whole after every step)
-// describes is empty.  A step is the tail or the three grid-wide launches.
-template <class P, class Ctrl>
-int run_frontier_rounds(const P &p, const FrontierBufs &b, Ctrl *ctrl, Ctrl &h, long long wg_frontier, int *launches) {
+// describes is empty, or until `stop` says so of the mirror (asked before every step).  A step is the tail or the three grid-wide launches.
+struct NeverStop {
+    template <class Ctrl> bool operator()(const Ctrl &) const { return false; }
+};
+template <class P, class Ctrl, class Stop = NeverStop>
+int run_frontier_rounds(const P &p, const FrontierBufs &b, Ctrl *ctrl, Ctrl &h, long long wg_frontier, int *launches, Stop stop = Stop{}) {
     Ctx &c = ctx();
     hipStream_t s = c.stream;
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
     const int64_t n = p.n;
-    while (h.count > 0) {
+    while (h.count > 0 && !stop(h)) {
         if (h.count <= wg_frontier && !h.bail) {
             hipLaunchKernelGGL(k_frontier_tail<P>, dim3(1), dim3(kTailThreads), 0, s, p, b.f[0], b.f[1], int32_t(wg_frontier), ctrl);
             *launches += 1;

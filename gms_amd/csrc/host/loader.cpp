@@ -790,6 +790,8 @@ Option g_options[] = {
     {"CC_SAMPLE", "", false}, {"CC_WAVE_ROW", "", false}, {"CC_WG_ROW", "", false},
     // 4-cycles and the motif census (motifs.hip)
     {"C4_LDS_SPAN", "", false}, {"C4_SLAB_MB", "", false}, {"C4_SPLIT_WEDGES", "", false},
+    // breadth-first search and betweenness centrality (traversal.hip)
+    {"BFS_DIRECTION", "", false}, {"BFS_ALPHA", "", false}, {"BFS_BETA", "", false}, {"BFS_BU_PROBE", "", false}, {"BFS_WG_FRONTIER", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;
@@ -947,6 +949,28 @@ int gmsx_csr_from_arrays(int64_t n, const int64_t *offsets, const int32_t *neigh
         std::memcpy(h->g.off.get(), offsets, size_t(n + 1) * 8);
         if (nnz) std::memcpy(h->g.neigh.get(), neigh, size_t(nnz) * 4);
         *out = h.release();
+        return GMSX_OK;
+    });
+}
+
+int gmsx_csr_pick_sources(const gmsx_csr *h, int64_t count, int32_t given, int32_t *out) {
+    return gmsx::guard([&]() -> int {
+        if (!h || count < 0 || (count > 0 && !out) || given < -1) return GMSX_ERR_INVALID;
+        const Csr &g = h->g;
+        if (given >= 0) {
+            if (int64_t(given) >= g.n) return GMSX_ERR_INVALID;
+            std::fill(out, out + count, given);
+            return GMSX_OK;
+        }
+        if (g.n <= 0 || g.nnz <= 0) return GMSX_ERR_INVALID;  // (no vertex of non-zero degree: SourcePicker would never return)
+        std::mt19937 rng(kSeed);
+        for (int64_t t = 0; t < count; ++t) {
+            int64_t src;
+            do {
+                src = int64_t(uniform_closed(rng, uint32_t(g.n - 1)));
+            } while (g.off[src + 1] == g.off[src]);
+            out[t] = int32_t(src);
+        }
         return GMSX_OK;
     });
 }

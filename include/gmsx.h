@@ -95,6 +95,10 @@ int gmsx_csr_is_mapped(const gmsx_csr *g);
 /* Wrap (copy) caller arrays; validates monotone offsets and id range. */
 int gmsx_csr_from_arrays(int64_t n, const int64_t *offsets, const int32_t *neigh, gmsx_csr **out);
 
+/* SourcePicker (gapbs/benchmark.h:51-75): out[0 .. count) = the first `count` picks — mt19937(kRandSeed), uniform over [0, n), redrawn while the
+ * degree is 0; given >= 0: `count` copies of it (given >= n → GMSX_ERR_INVALID).  A graph with no edge → GMSX_ERR_INVALID where the reference
+ * would draw for ever.  Host only. */
+int gmsx_csr_pick_sources(const gmsx_csr *g, int64_t count, int32_t given /* -1: random */, int32_t *out /* count, host */);
 int gmsx_csr_worth_relabelling(const gmsx_csr *g);                  /* gapbs/benchmark.h:158-176; 1/0 */
 int gmsx_csr_relabel_by_degree(const gmsx_csr *g, gmsx_csr **out);  /* builder.h:1699-1733 */
 
@@ -167,7 +171,13 @@ int gmsx_set_host_threads(int n);
  *                   8192; 0 = no LDS path), C4_SLAB_MB (budget of the global counter spans, default 1024: a smaller budget = fewer workgroup
  *                   spans and fewer split sources per launch), C4_SPLIT_WEDGES (wedge bound above which a source is walked by many workgroups
  *                   into one span, default 2^18; 1 = every source with a wedge, a huge value = none) — all three first guesses, not tuned
- *                   values; test hooks */
+ *                   values; test hooks
+ *   breadth-first search   BFS_DIRECTION (0, the default = the reference's direction-optimising rule; 1 = every level top-down; 2 = every level
+ *                   after the source's bottom-up), BFS_ALPHA (15) / BFS_BETA (18) (bfs.cc:120-121: bottom-up when scout_count > edges_to_check /
+ *                   alpha, and for as long as the awake count does not fall or exceeds n / beta), BFS_BU_PROBE (row entries a single lane probes
+ *                   in the bottom-up step before the row goes to a 16-lane group or a wave; default 16, at most 1024), BFS_WG_FRONTIER (as
+ *                   CORE_WG_FRONTIER for the top-down rounds, default 512; 0 = every round is a kernel boundary) — all first guesses and test
+ *                   hooks; none changes depth, parent, scores or any info field except bottom_up_levels; gmsx_betweenness reads them, too */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -703,6 +713,50 @@ int gmsx_connected_components(const gmsx_graph *g, const uint8_t *arc_keep /* nn
 int gmsx_jarvis_patrick(const gmsx_graph *g, int metric /* GMSX_SIM_* */, double threshold,
                         int32_t *label /* n, host, or NULL */, uint8_t *arc_keep /* nnz, host, or NULL: out */,
                         gmsx_components_info *info /* required */, gmsx_stats *stats);
+
+/* ---- breadth-first search and betweenness centrality (gms/representations/graphs/log_graph/bfs.cc: DOBFS, bc.cc: Brandes).
+ * gmsx_bfs: depth[v] = distance from source (-1: unreachable); parent[v] = the SMALLEST-id neighbour of v at depth[v] - 1, parent[source] =
+ * source, -1 for an unreachable vertex.  That is what the reference's bottom-up step writes (the first frontier entry of an ascending row), it
+ * passes BFSVerifier (bfs.cc:212-258), and unlike the reference's top-down parents it is a fact about (graph, source): depth, parent and every
+ * info field except bottom_up_levels are byte-identical in every run and process, under every BFS_* option, GMSX_UPLOAD_TRUSTED,
+ * GMSX_UPLOAD_HUB_LIMIT and a sharded upload.  bottom_up_levels is a fact about (graph, source, options).  The levels are taken top-down (the
+ * frontier-rounds engine) or bottom-up (every unvisited vertex scans its own row for a frontier bit) by the reference's rule, bfs.cc:142-188.
+ * source outside [0, n) (hence any source when n = 0), NULL g or info: GMSX_ERR_INVALID, nothing written.  An append past its bound, a level count
+ * above n, or `reached` disagreeing with the level sums: GMSX_ERR_KERNEL.  The caller's arrays are written only after the flag words were read as
+ * zero.  Single GPU, no shards.  gmsx_stats: kernel_ms, setup_ms, launches, units = reached_arcs, probes = levels.
+ * gmsx_betweenness: scores[u] = Σ_s delta_s(u) over the given sources, one after the other (a source listed twice counts twice, as bc.cc -r s -i 2),
+ * delta_s(u) = Σ_{v in N(u), depth(v) = depth(u) + 1} sigma(u) / sigma(v) * (1 + delta_s(v)) — bc.cc:131-132, its operand order — with sigma the
+ * number of shortest paths from s, in DOUBLE (the reference's 32-bit counts wrap; a 40 x 40 grid passes 2^64): exact while info->max_sigma < 2^53.
+ * The default adds delta_s(s) = reached(s) - 1 to the source's own score as Brandes and BCVerifier do (bc.cc:124-138, 207-216);
+ * GMSX_BC_EXCLUDE_SOURCE leaves it out (textbook Brandes; on an undirected graph with all n sources twice the unordered-pair value);
+ * GMSX_BC_NORMALIZE_MAX divides by the largest score (bc.cc:144-151; an all-zero result stays zeros).  No floating-point atomic is used: a row's
+ * sum is taken by fixed lanes over fixed strides and combined by a fixed tree, a score has one writer — scores is a fact about (graph, sources,
+ * flags), byte-identical in every run and under every BFS_* option.  An id outside [0, n), unknown flag bits, NULL g / info, NULL scores with
+ * n > 0 or NULL sources with n_sources > 0: GMSX_ERR_INVALID, nothing written.  n_sources = 0: zeros.  Single GPU.  gmsx_stats: kernel_ms,
+ * setup_ms, launches, units = Σ reached_arcs, probes = Σ levels. */
+typedef struct {
+    int64_t reached;          /* vertices with depth >= 0, the source included */
+    int64_t reached_arcs;     /* sum of their degrees */
+    int64_t depth_sum;        /* sum of depth over the reached vertices (closeness = (reached-1)/depth_sum) */
+    int64_t widest;           /* size of the largest level */
+    int32_t levels;           /* non-empty levels = eccentricity of the source + 1 */
+    int32_t widest_level;     /* its depth; ties: the smallest */
+    int32_t bottom_up_levels; /* levels discovered by the bottom-up step: a fact about (graph, source, options) */
+    int32_t reserved;
+} gmsx_bfs_info;
+int gmsx_bfs(const gmsx_graph *g, int32_t source, int32_t *depth /* n, host, or NULL */, int32_t *parent /* n, host, or NULL */,
+             gmsx_bfs_info *info /* required */, gmsx_stats *stats);
+enum { GMSX_BC_DEFAULT = 0, GMSX_BC_EXCLUDE_SOURCE = 1, GMSX_BC_NORMALIZE_MAX = 2 };
+typedef struct {
+    int64_t sources;       /* as passed */
+    int64_t reached_total; /* sum over the sources of gmsx_bfs's reached */
+    int32_t max_levels;    /* largest levels of any source */
+    int32_t reserved;
+    double  max_score;     /* before normalisation */
+    double  max_sigma;     /* largest shortest-path count met; below 2^53 every count was exact */
+} gmsx_bc_info;
+int gmsx_betweenness(const gmsx_graph *g, int64_t n_sources, const int32_t *sources /* host */, uint32_t flags,
+                     double *scores /* n, host */, gmsx_bc_info *info /* required */, gmsx_stats *stats);
 
 /* ---- 4-cycle counting and the 3- / 4-vertex motif census.  No reference counterpart (like the k-truss: a member of the family the suite
  * describes and does not build).  All results are exact integers.

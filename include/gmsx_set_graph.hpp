@@ -35,6 +35,9 @@
 //   gmsx::connected_components(g, out)   -> gmsx_connected_components (representations/graphs/log_graph/cc.cc:40-72, ShiloachVishkin: out[v] = smallest id of v's component)
 //   gmsx::jarvis_patrick(g, metric, threshold, out) -> gmsx_jarvis_patrick (the components over the edges whose endpoints are similar enough; no reference driver)
 //   gmsx::ktruss_components(g, k, out)   -> gmsx_truss_decomposition + gmsx_connected_components (the communities of the k-truss: the mask truss >= k)
+//   gmsx::bfs(g, source, parent)         -> gmsx_bfs                (representations/graphs/log_graph/bfs.cc:120-190, DOBFS: parent[v] = the smallest-id neighbour one level up)
+//   gmsx::betweenness(g, sources, scores) -> gmsx_betweenness       (log_graph/bc.cc:89-153, Brandes from the listed sources, in double)
+//   gmsx::pick_sources(csr, count)       -> gmsx_csr_pick_sources   (gapbs/benchmark.h:51-75, SourcePicker)
 //   gmsx::cycle4_count(g) / cycle4_count(g, at_vertex) -> gmsx_cycle4_count (the 4-cycles, and those through every vertex; no reference driver)
 //   gmsx::motif_census4(g)               -> gmsx_motif_census4     (the eight 3- and 4-vertex motifs, non-induced and induced; no reference driver)
 //   gmsx::link_prediction(g, metric, q)  -> gmsx_link_prediction  (set_based/link_prediction/link_prediction.h:42-101; the reference's padding reproduced)
@@ -665,6 +668,42 @@ inline int64_t ktruss_components(const HipGraphT<S> &g, int32_t k, Output &comp,
     detail::check(gmsx_connected_components(g.device(), keep.data(), reinterpret_cast<int32_t *>(comp.data()), &ci, nullptr), "gmsx_connected_components");
     if (info) *info = ci;
     return ci.components;
+}
+
+// DOBFS(g, source) (representations/graphs/log_graph/bfs.cc:120-190), shaped like its pvector<NodeId> parent: parent[v] = the smallest-id
+// neighbour of v one level nearer the source, parent[source] = source, -1 = unreachable (the reference leaves -degree there); BFSVerifier
+// (:212-258) accepts it.  `depth` (optional, a vector of int32) receives the distances, `info` (optional) the level statistics; returns the
+// number of reached vertices: the "nodes" of PrintBFSStats.
+template <class S, class Output>
+inline int64_t bfs(const HipGraphT<S> &g, int32_t source, Output &parent, std::vector<int32_t> *depth = nullptr, gmsx_bfs_info *info = nullptr) {
+    parent.resize(size_t(g.num_nodes()));
+    static_assert(sizeof(*parent.data()) == sizeof(int32_t), "parents are int32 vectors");
+    if (depth) depth->resize(size_t(g.num_nodes()));
+    gmsx_bfs_info bi{};
+    detail::check(gmsx_bfs(g.device(), source, depth ? depth->data() : nullptr, reinterpret_cast<int32_t *>(parent.data()), &bi, nullptr), "gmsx_bfs");
+    if (info) *info = bi;
+    return bi.reached;
+}
+// Brandes(g, sp, num_iters) (log_graph/bc.cc:89-153) from an explicit source list (pick_sources gives the reference's), in double where the
+// reference has float and 32-bit path counts; flags: GMSX_BC_*.  GMSX_BC_NORMALIZE_MAX gives the reference's normalised scores.  Returns the
+// largest score before normalisation.
+template <class S>
+inline double betweenness(const HipGraphT<S> &g, const std::vector<int32_t> &sources, std::vector<double> &scores, uint32_t flags = GMSX_BC_DEFAULT,
+                          gmsx_bc_info *info = nullptr) {
+    scores.resize(size_t(g.num_nodes()));
+    gmsx_bc_info bi{};
+    double none = 0.0;  // (n = 0: the library wants no array, the vector has none)
+    detail::check(gmsx_betweenness(g.device(), int64_t(sources.size()), sources.data(), flags, scores.empty() ? &none : scores.data(), &bi, nullptr),
+                  "gmsx_betweenness");
+    if (info) *info = bi;
+    return bi.max_score;
+}
+// SourcePicker (gapbs/benchmark.h:51-75): its first `count` picks, or `count` copies of `given`
+inline std::vector<int32_t> pick_sources(const gmsx_csr *csr, int64_t count, int32_t given = -1) {
+    std::vector<int32_t> out(size_t(count > 0 ? count : 0));
+    int32_t none = 0;
+    detail::check(gmsx_csr_pick_sources(csr, count, given, out.empty() ? &none : out.data()), "gmsx_csr_pick_sources");
+    return out;
 }
 
 // The 4-cycles of the graph (no reference counterpart).  With `at_vertex` (a vector of 64-bit integers, resized to n): the 4-cycles through
