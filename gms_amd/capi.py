@@ -45,7 +45,7 @@ SYMBOLS = [
     "gmsx_link_prediction", "gmsx_link_prediction_precision",
     "gmsx_subgraph_order", "gmsx_subgraph_match",
     "gmsx_connected_components", "gmsx_jarvis_patrick",
-    "gmsx_bfs", "gmsx_betweenness",
+    "gmsx_bfs", "gmsx_betweenness", "gmsx_bfs_multi",
     "gmsx_cycle4_count", "gmsx_cycle4_partial", "gmsx_motif_census4",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -158,6 +158,24 @@ class BcInfo(C.Structure):
     def as_dict(self):
         return {"sources": int(self.sources), "reached_total": int(self.reached_total), "max_levels": int(self.max_levels),
                 "max_score": float(self.max_score), "max_sigma": float(self.max_sigma)}
+
+
+class BfsSource(C.Structure):
+    _fields_ = [("reached", C.c_int64), ("reached_arcs", C.c_int64), ("depth_sum", C.c_int64), ("levels", C.c_int32), ("reserved", C.c_int32),
+                ("closeness", C.c_double), ("harmonic", C.c_double)]
+
+
+# gmsx_bfs_source as a numpy record (the same 48 bytes)
+BFS_SOURCE_DTYPE = np.dtype([("reached", "<i8"), ("reached_arcs", "<i8"), ("depth_sum", "<i8"), ("levels", "<i4"), ("reserved", "<i4"),
+                             ("closeness", "<f8"), ("harmonic", "<f8")])
+
+
+class BfsMultiInfo(C.Structure):
+    _fields_ = [("sources", C.c_int64), ("passes", C.c_int64), ("reached_total", C.c_int64), ("max_levels", C.c_int32), ("max_far", C.c_int32),
+                ("push_levels", C.c_int32), ("pull_levels", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class MotifInfo(C.Structure):
@@ -341,6 +359,7 @@ def lib():
     L.gmsx_jarvis_patrick.argtypes = [vp, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(ComponentsInfo), sp]
     L.gmsx_bfs.argtypes = [vp, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(BfsInfo), sp]
     L.gmsx_betweenness.argtypes = [vp, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(BcInfo), sp]
+    L.gmsx_bfs_multi.argtypes = [vp, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BfsMultiInfo), sp]
     L.gmsx_csr_pick_sources.argtypes = [vp, C.c_int64, C.c_int32, C.c_void_p]
     L.gmsx_cycle4_count.argtypes = [vp, u64p, C.c_void_p, sp]
     L.gmsx_cycle4_partial.argtypes = [vp, C.c_int, C.c_int, u64p, sp]
@@ -1003,6 +1022,25 @@ class DeviceGraph:
         _check(lib().gmsx_betweenness(self._h, src.size, src.ctypes.data_as(C.c_void_p) if src.size else None, flags,
                                       scores.ctypes.data_as(C.c_void_p), C.byref(info), C.byref(st)), "gmsx_betweenness")
         r = (scores[:n], info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def bfs_multi(self, sources, want_depth=False, want_vertex=True, stats=False):
+        """gmsx_bfs_multi over the listed sources: (per_source — a structured array of BFS_SOURCE_DTYPE, one record per list entry —,
+        depth int32[len(sources), n] or None, (dist_sum int64[n], reach int32[n], far int32[n]) or None, {sources, passes, reached_total,
+        max_levels, max_far, push_levels, pull_levels})."""
+        n = self.num_nodes
+        src = np.ascontiguousarray(sources, dtype=np.int32).reshape(-1)
+        per = np.zeros(max(src.size, 1), dtype=BFS_SOURCE_DTYPE)
+        depth = np.zeros(max(src.size * n, 1), dtype=np.int32) if want_depth else None
+        dist = np.zeros(max(n, 1), dtype=np.int64) if want_vertex else None
+        reach = np.zeros(max(n, 1), dtype=np.int32) if want_vertex else None
+        far = np.zeros(max(n, 1), dtype=np.int32) if want_vertex else None
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        info, st = BfsMultiInfo(), Stats()
+        _check(lib().gmsx_bfs_multi(self._h, src.size, p(src) if src.size else None, p(per), p(depth), p(dist), p(reach), p(far), C.byref(info),
+                                    C.byref(st)), "gmsx_bfs_multi")
+        r = (per[:src.size], depth[:src.size * n].reshape(src.size, n) if want_depth else None,
+             (dist[:n], reach[:n], far[:n]) if want_vertex else None, info.as_dict())
         return (r + (st.as_dict(),)) if stats else r
 
     def cycle4_count(self, at_vertex=False, stats=False):

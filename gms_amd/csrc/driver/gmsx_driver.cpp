@@ -58,7 +58,11 @@
 //                    Time", "Max Score" and with -v "Verification" — BCVerifier's serial Brandes (bc.cc:172-232) in double, held to the derived bound
 //                    2 eps (L (d + 2) + S + 1) of include/gmsx.h's definition plus 2 eps for the normalisation —, then the "@@@" line; after the
 //                    last trial PrintTopScores' five id:score lines (bc.cc:156-164; ties: the smaller id).  Not sharded.
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  closeness [-r SOURCE] [-i SOURCES]   closeness centrality of SOURCES picked sources per trial (the picker runs on across the trials, as for
+//                    bc) by batched multi-source BFS on the device (gmsx_bfs_multi; no reference driver): per trial "Trial Time", "Max Score" and with
+//                    -v "Verification" — this driver's own serial BFS per source must give the same reached, depth_sum and levels —, then the "@@@"
+//                    line; after the last trial the top five sources by closeness in PrintTopScores' shape (ties: the earlier source).  Not sharded.
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -164,9 +168,9 @@ Args parse(int argc, char **argv) {
     if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp" && a.kernel != "sgi") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
     if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss" || a.kernel == "sgi" || a.kernel == "cc" || a.kernel == "jp" || a.kernel == "motifs") && a.gpus > 1) a.error = 100;
     if (!a.error && ((a.kernel == "jp") != !std::isnan(a.threshold))) a.error = 100;  // the threshold is required, and only there
-    const bool traversal = a.kernel == "bfs" || a.kernel == "bc";
+    const bool traversal = a.kernel == "bfs" || a.kernel == "bc" || a.kernel == "closeness";
     if (!a.error && traversal && (a.gpus > 1 || a.metric_given)) a.error = 100;  // a traversal is global; it has no metric
-    if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc"))) a.error = 100;
+    if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc" && a.kernel != "closeness"))) a.error = 100;
     if (!a.error && ((a.kernel == "sgi") != !a.pattern_file.empty() || (a.mono && a.kernel != "sgi"))) a.error = 100;  // util/command_line.hpp:22: the pattern is required
     if (!a.error && (a.kernel == "lp" || a.kernel == "jp") && lp_metric(a.metric) < 0) a.error = 100;
     if (!a.error && !a.order.empty() && a.kernel != "bk" && a.kernel != "color") a.error = 100;  // only Bron–Kerbosch and the colouring have a preprocessing step
@@ -179,10 +183,10 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
                 "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE] "
-                "[jp: --metric NAME --threshold X] [bfs, bc: -r SOURCE] [bc: -i ITERS]\n", argv0);
+                "[jp: --metric NAME --threshold X] [bfs, bc, closeness: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -770,6 +774,67 @@ int run_traversal(const Args &args, const gmsx::HipSetGraph &g, const HostGraph 
     return 0;
 }
 
+// closeness centrality of the picked sources by batched multi-source BFS (gmsx_bfs_multi), under the usual trial loop; -v: a serial BFS per
+// source of this driver's own must give the same reached, depth_sum and levels
+int run_closeness(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg, const gmsx_csr *csr) {
+    if (args.start >= hg.n) { std::printf("-r %lld: the graph has %lld vertices\n", (long long)args.start, (long long)hg.n); return 100; }
+    if (args.iters < 1) { std::printf("-i %lld: at least one source per trial\n", (long long)args.iters); return 100; }
+    const int64_t per_trial = args.iters;
+    std::vector<int32_t> picks(size_t(per_trial * std::max<int64_t>(args.trials, 0)) + 1);
+    if (int rc = gmsx_csr_pick_sources(csr, int64_t(picks.size()) - 1, int32_t(args.start), picks.data())) {
+        std::printf("no source to pick: %s\n", gmsx_strerror(rc));
+        return 2;
+    }
+    double total_seconds = 0;
+    Timer t;
+    std::vector<int32_t> sources;
+    std::vector<gmsx_bfs_source> per;
+    for (int64_t it = 0; it < args.trials; ++it) {
+        sources.assign(picks.begin() + it * per_trial, picks.begin() + (it + 1) * per_trial);
+        t.Start();
+        gmsx::bfs_multi(g, sources, per);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        double top = 0.0;
+        for (const gmsx_bfs_source &x : per) top = std::max(top, x.closeness);
+        std::printf("%-21s%g\n", "Max Score:", top);
+        if (args.verify) {
+            bool ok = true;
+            std::vector<int32_t> depth(size_t(hg.n)), to_visit;
+            to_visit.reserve(size_t(hg.n));
+            for (size_t i = 0; i < sources.size(); ++i) {
+                std::fill(depth.begin(), depth.end(), -1);
+                to_visit.clear();
+                depth[size_t(sources[i])] = 0;
+                to_visit.push_back(sources[i]);
+                int64_t depth_sum = 0;
+                for (size_t at = 0; at < to_visit.size(); ++at) {
+                    const int32_t u = to_visit[at];
+                    depth_sum += depth[size_t(u)];
+                    for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j)
+                        if (depth[size_t(hg.adj[j])] == -1) {
+                            depth[size_t(hg.adj[j])] = depth[size_t(u)] + 1;
+                            to_visit.push_back(hg.adj[j]);
+                        }
+                }
+                if (per[i].reached != int64_t(to_visit.size()) || per[i].depth_sum != depth_sum || per[i].levels != depth[size_t(to_visit.back())] + 1) ok = false;
+            }
+            PrintLabel("Verification", ok ? "PASS" : "FAIL");
+        }
+        std::cout << "@@@ closeness" << std::endl;
+    }
+    if (args.trials > 0) {
+        std::vector<std::pair<double, size_t>> top;  // (-score, position in the list): ascending = largest first, ties by the earlier source
+        for (size_t i = 0; i < per.size(); ++i) top.emplace_back(-per[i].closeness, i);
+        const size_t k = std::min<size_t>(5, top.size());
+        std::partial_sort(top.begin(), top.begin() + k, top.end());
+        for (size_t i = 0; i < k; ++i) std::cout << sources[top[i].second] << ":" << -top[i].first << std::endl;
+    }
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
 // subgraph matching: the reference's VF2 drivers (subgraphiso_vf2_sequential.cpp:33-51) over gmsx::subgraph_isomorphisms
 int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
     gmsx_csr *pc = nullptr;
@@ -831,7 +896,7 @@ int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -905,8 +970,8 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc") {
-        const int rc_run = (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness") {
+        const int rc_run = args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
                                                                                                                                         : run_components(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);

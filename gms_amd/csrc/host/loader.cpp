@@ -792,6 +792,8 @@ Option g_options[] = {
     {"C4_LDS_SPAN", "", false}, {"C4_SLAB_MB", "", false}, {"C4_SPLIT_WEDGES", "", false},
     // breadth-first search and betweenness centrality (traversal.hip)
     {"BFS_DIRECTION", "", false}, {"BFS_ALPHA", "", false}, {"BFS_BETA", "", false}, {"BFS_BU_PROBE", "", false}, {"BFS_WG_FRONTIER", "", false},
+    // batched multi-source breadth-first search (msbfs.hip)
+    {"MSBFS_DIRECTION", "", false}, {"MSBFS_ALPHA", "", false}, {"MSBFS_WORDS", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

@@ -177,7 +177,13 @@ int gmsx_set_host_threads(int n);
  *                   alpha, and for as long as the awake count does not fall or exceeds n / beta), BFS_BU_PROBE (row entries a single lane probes
  *                   in the bottom-up step before the row goes to a 16-lane group or a wave; default 16, at most 1024), BFS_WG_FRONTIER (as
  *                   CORE_WG_FRONTIER for the top-down rounds, default 512; 0 = every round is a kernel boundary) — all first guesses and test
- *                   hooks; none changes depth, parent, scores or any info field except bottom_up_levels; gmsx_betweenness reads them, too */
+ *                   hooks; none changes depth, parent, scores or any info field except bottom_up_levels; gmsx_betweenness reads them, too
+ *   multi-source BFS       MSBFS_DIRECTION (0, the default = the rule: a level is pushed from the active list when the degree sum of that list is
+ *                   at most nnz / MSBFS_ALPHA, else pulled by every vertex that still lacks a source; 1 = every level pushed; 2 = every level
+ *                   pulled), MSBFS_ALPHA (default 15 — a first guess, not a tuned value), MSBFS_WORDS (W = 1 or 2: 64-bit words
+ *                   per vertex, so a pass advances 64 W sources; 0, the default = 1 for a list of at most 64 sources and 2 for a longer one, as
+ *                   measured: DESIGN.md §5.4j) — none changes any output of gmsx_bfs_multi but passes, push_levels and
+ *                   pull_levels; test hooks.  Under TIMING every level prints its direction and the two operands of the rule */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -757,6 +763,45 @@ typedef struct {
 } gmsx_bc_info;
 int gmsx_betweenness(const gmsx_graph *g, int64_t n_sources, const int32_t *sources /* host */, uint32_t flags,
                      double *scores /* n, host */, gmsx_bc_info *info /* required */, gmsx_stats *stats);
+
+/* ---- batched multi-source breadth-first search: closeness, harmonic centrality, eccentricity (no reference counterpart; msbfs.hip).
+ * gmsx_bfs_multi runs a BFS from every listed source, bit-parallel: a vertex holds W 64-bit words, one bit per source, and the sources are
+ * processed in passes of 64 W consecutive list entries (W: option MSBFS_WORDS), so one sweep of the CSR advances 64 W traversals.  A source listed
+ * twice is two rows of `depth` and counts twice in dist_sum and reach, as gmsx_betweenness counts it.  The integer outputs do not depend on the
+ * pass structure; closeness and harmonic are computed on the host from each source's per-level counts, ascending in the depth — every output is a
+ * function of (graph, sources) alone, byte-identical in every run and under every MSBFS_* option, GMSX_UPLOAD_TRUSTED, GMSX_UPLOAD_HUB_LIMIT and
+ * a sharded upload, except passes, push_levels and pull_levels, which are functions of (graph, sources, options).  On the undirected graphs this
+ * library holds, with all n vertices as sources: dist_sum[v] is v's farness, far[v] its eccentricity inside its component, and
+ * per_source[i].depth_sum == dist_sum[sources[i]].  A level is pushed (integer atomicOr only) or pulled (one owner per vertex) by the rule of
+ * MSBFS_DIRECTION / MSBFS_ALPHA; push_levels + pull_levels counts the levels that found a vertex: Σ over the passes of the largest levels - 1.
+ * NULL g or info, n_sources < 0, NULL sources with n_sources > 0, an id outside [0, n): GMSX_ERR_INVALID, nothing written.  n_sources = 0: GMSX_OK,
+ * dist_sum and reach zeros, far -1, info zeroed.  A level count above n, a bounded append past its bound, or per-source sums that disagree with
+ * the per-vertex sums (Σ_i reached_i == Σ_v reach[v], summed on the device): GMSX_ERR_KERNEL.  The caller's arrays are written only after the flag
+ * words were read as zero, through host staging.  depth is optional and meant for tests and small graphs: the device holds one pass's rows
+ * (256 W n bytes); if that does not fit: GMSX_ERR_DEVICE_MEM.  Single GPU, the source list is not sharded.  gmsx_stats: kernel_ms, setup_ms,
+ * launches, units = Σ reached_arcs, probes = Σ over the passes of the pass's level count (its largest levels). */
+typedef struct {
+    int64_t reached;       /* as gmsx_bfs_info, for this source */
+    int64_t reached_arcs;
+    int64_t depth_sum;
+    int32_t levels;
+    int32_t reserved;
+    double  closeness;     /* (reached - 1) / depth_sum, 0.0 when depth_sum == 0 */
+    double  harmonic;      /* sum over d = 1 .. levels-1, ascending, of double(count_d) / double(d); count_d = vertices at depth d */
+} gmsx_bfs_source;
+typedef struct {
+    int64_t sources, passes, reached_total;
+    int32_t max_levels;    /* largest levels of any source */
+    int32_t max_far;       /* largest depth met = max of far[] (a diameter lower bound; exact with every vertex as a source) */
+    int32_t push_levels, pull_levels;   /* summed over the passes: facts about (graph, sources, options) */
+} gmsx_bfs_multi_info;
+int gmsx_bfs_multi(const gmsx_graph *g, int64_t n_sources, const int32_t *sources /* host */,
+                   gmsx_bfs_source *per_source /* n_sources, host, or NULL */,
+                   int32_t *depth    /* n_sources * n, row i = depths from sources[i], -1 unreachable; host, or NULL */,
+                   int64_t *dist_sum /* n: sum over the listed sources that reach v of depth_i(v); host, or NULL */,
+                   int32_t *reach    /* n: how many listed sources reach v; host, or NULL */,
+                   int32_t *far      /* n: largest depth_i(v) over them, -1 if none; host, or NULL */,
+                   gmsx_bfs_multi_info *info /* required */, gmsx_stats *stats);
 
 /* ---- 4-cycle counting and the 3- / 4-vertex motif census.  No reference counterpart (like the k-truss: a member of the family the suite
  * describes and does not build).  All results are exact integers.

@@ -37,6 +37,8 @@
 //   gmsx::ktruss_components(g, k, out)   -> gmsx_truss_decomposition + gmsx_connected_components (the communities of the k-truss: the mask truss >= k)
 //   gmsx::bfs(g, source, parent)         -> gmsx_bfs                (representations/graphs/log_graph/bfs.cc:120-190, DOBFS: parent[v] = the smallest-id neighbour one level up)
 //   gmsx::betweenness(g, sources, scores) -> gmsx_betweenness       (log_graph/bc.cc:89-153, Brandes from the listed sources, in double)
+//   gmsx::bfs_multi(g, sources, per_source, …) -> gmsx_bfs_multi    (a BFS from every listed source, 64 per sweep: per-source sums, optional depths and per-vertex farness; no reference driver)
+//   gmsx::closeness(g, sources, out_scores, harmonic = false) -> gmsx_bfs_multi (closeness or harmonic centrality of the listed sources; returns the largest)
 //   gmsx::pick_sources(csr, count)       -> gmsx_csr_pick_sources   (gapbs/benchmark.h:51-75, SourcePicker)
 //   gmsx::cycle4_count(g) / cycle4_count(g, at_vertex) -> gmsx_cycle4_count (the 4-cycles, and those through every vertex; no reference driver)
 //   gmsx::motif_census4(g)               -> gmsx_motif_census4     (the eight 3- and 4-vertex motifs, non-induced and induced; no reference driver)
@@ -697,6 +699,42 @@ inline double betweenness(const HipGraphT<S> &g, const std::vector<int32_t> &sou
                   "gmsx_betweenness");
     if (info) *info = bi;
     return bi.max_score;
+}
+// A BFS from every listed source, 64 (or 128) of them per sweep of the graph (gmsx_bfs_multi; no reference counterpart): per_source[i] holds
+// reached, reached_arcs, depth_sum, levels, closeness and harmonic of sources[i].  Optional: depth (sources.size() rows of n, -1 = unreachable;
+// meant for small graphs) and the per-vertex dist_sum (64-bit), reach and far (int32).  Returns the number of reached vertices summed over the
+// sources.
+template <class S>
+inline int64_t bfs_multi(const HipGraphT<S> &g, const std::vector<int32_t> &sources, std::vector<gmsx_bfs_source> &per_source,
+                         std::vector<int32_t> *depth = nullptr, std::vector<int64_t> *dist_sum = nullptr, std::vector<int32_t> *reach = nullptr,
+                         std::vector<int32_t> *far = nullptr, gmsx_bfs_multi_info *info = nullptr) {
+    const size_t n = size_t(g.num_nodes());
+    per_source.resize(sources.size());
+    if (depth) depth->resize(sources.size() * n);
+    if (dist_sum) dist_sum->resize(n);
+    if (reach) reach->resize(n);
+    if (far) far->resize(n);
+    gmsx_bfs_multi_info mi{};
+    detail::check(gmsx_bfs_multi(g.device(), int64_t(sources.size()), sources.data(), per_source.data(), depth ? depth->data() : nullptr,
+                                 dist_sum ? dist_sum->data() : nullptr, reach ? reach->data() : nullptr, far ? far->data() : nullptr, &mi, nullptr),
+                  "gmsx_bfs_multi");
+    if (info) *info = mi;
+    return mi.reached_total;
+}
+// Closeness centrality of the listed sources inside their components: out_scores[i] = (reached - 1) / depth_sum of sources[i] (0 for an isolated
+// source), or with `harmonic` the harmonic centrality Σ_{v != s} 1 / depth(v).  Returns the largest score.
+template <class S>
+inline double closeness(const HipGraphT<S> &g, const std::vector<int32_t> &sources, std::vector<double> &out_scores, bool harmonic = false,
+                        gmsx_bfs_multi_info *info = nullptr) {
+    std::vector<gmsx_bfs_source> per;
+    bfs_multi(g, sources, per, nullptr, nullptr, nullptr, nullptr, info);
+    out_scores.resize(per.size());
+    double top = 0.0;
+    for (size_t i = 0; i < per.size(); ++i) {
+        out_scores[i] = harmonic ? per[i].harmonic : per[i].closeness;
+        if (out_scores[i] > top) top = out_scores[i];
+    }
+    return top;
 }
 // SourcePicker (gapbs/benchmark.h:51-75): its first `count` picks, or `count` copies of `given`
 inline std::vector<int32_t> pick_sources(const gmsx_csr *csr, int64_t count, int32_t given = -1) {
