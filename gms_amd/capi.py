@@ -46,6 +46,7 @@ SYMBOLS = [
     "gmsx_subgraph_order", "gmsx_subgraph_match",
     "gmsx_connected_components", "gmsx_jarvis_patrick",
     "gmsx_bfs", "gmsx_betweenness", "gmsx_bfs_multi",
+    "gmsx_pagerank", "gmsx_pagerank_residual",
     "gmsx_cycle4_count", "gmsx_cycle4_partial", "gmsx_motif_census4",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -176,6 +177,18 @@ class BfsMultiInfo(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+PR_DEFAULT, PR_DANGLING, PR_FLOAT32 = 0, 1, 2
+
+
+class PagerankInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("argmax", C.c_int32), ("reserved", C.c_int32), ("error", C.c_double),
+                ("sum", C.c_double), ("max_score", C.c_double), ("isolated", C.c_int64)]
+
+    def as_dict(self):
+        return {"iterations": int(self.iterations), "converged": int(self.converged), "argmax": int(self.argmax), "error": float(self.error),
+                "sum": float(self.sum), "max_score": float(self.max_score), "isolated": int(self.isolated)}
 
 
 class MotifInfo(C.Structure):
@@ -360,6 +373,8 @@ def lib():
     L.gmsx_bfs.argtypes = [vp, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(BfsInfo), sp]
     L.gmsx_betweenness.argtypes = [vp, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(BcInfo), sp]
     L.gmsx_bfs_multi.argtypes = [vp, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BfsMultiInfo), sp]
+    L.gmsx_pagerank.argtypes = [vp, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(PagerankInfo), sp]
+    L.gmsx_pagerank_residual.argtypes = [vp, C.c_void_p, C.c_double, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), sp]
     L.gmsx_csr_pick_sources.argtypes = [vp, C.c_int64, C.c_int32, C.c_void_p]
     L.gmsx_cycle4_count.argtypes = [vp, u64p, C.c_void_p, sp]
     L.gmsx_cycle4_partial.argtypes = [vp, C.c_int, C.c_int, u64p, sp]
@@ -1042,6 +1057,34 @@ class DeviceGraph:
         r = (per[:src.size], depth[:src.size * n].reshape(src.size, n) if want_depth else None,
              (dist[:n], reach[:n], far[:n]) if want_vertex else None, info.as_dict())
         return (r + (st.as_dict(),)) if stats else r
+
+    def pagerank(self, damping=0.85, max_iters=20, tolerance=1e-4, teleport=None, dangling=False, float32=False, stats=False):
+        """gmsx_pagerank: (scores float64[n], {iterations, converged, argmax, error, sum, max_score, isolated}).  teleport: n non-negative
+        weights (normalised by the library), None = uniform.  The defaults are the reference's (pr.cc: kDamp, -i 20, -t 1e-4)."""
+        n = self.num_nodes
+        tp = None if teleport is None else np.ascontiguousarray(teleport, dtype=np.float64).reshape(-1)
+        if tp is not None and tp.size != n:
+            raise ValueError("teleport must have one entry per vertex")
+        flags = (PR_DANGLING if dangling else 0) | (PR_FLOAT32 if float32 else 0)
+        scores, info, st = np.zeros(max(n, 1), dtype=np.float64), PagerankInfo(), Stats()
+        _check(lib().gmsx_pagerank(self._h, float(damping), int(max_iters), float(tolerance), tp.ctypes.data_as(C.c_void_p) if tp is not None and n else None,
+                                   flags, scores.ctypes.data_as(C.c_void_p), C.byref(info), C.byref(st)), "gmsx_pagerank")
+        r = (scores[:n], info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def pagerank_residual(self, scores, damping=0.85, teleport=None, dangling=False, float32=False, stats=False):
+        """gmsx_pagerank_residual: Σ_u |one sweep over `scores` - scores| (the reference's PRVerifier accepts scores iff this is below its tolerance)."""
+        n = self.num_nodes
+        sc = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+        tp = None if teleport is None else np.ascontiguousarray(teleport, dtype=np.float64).reshape(-1)
+        if sc.size != n or (tp is not None and tp.size != n):
+            raise ValueError("scores and teleport must have one entry per vertex")
+        flags = (PR_DANGLING if dangling else 0) | (PR_FLOAT32 if float32 else 0)
+        out, st = C.c_double(0.0), Stats()
+        _check(lib().gmsx_pagerank_residual(self._h, sc.ctypes.data_as(C.c_void_p) if n else None, float(damping),
+                                            tp.ctypes.data_as(C.c_void_p) if tp is not None and n else None, flags, C.byref(out), C.byref(st)),
+               "gmsx_pagerank_residual")
+        return (out.value, st.as_dict()) if stats else out.value
 
     def cycle4_count(self, at_vertex=False, stats=False):
         """gmsx_cycle4_count: the 4-cycles of the graph; with at_vertex=True (cycles, int64[n] — the 4-cycles through every vertex of the

@@ -62,7 +62,13 @@
 //                    bc) by batched multi-source BFS on the device (gmsx_bfs_multi; no reference driver): per trial "Trial Time", "Max Score" and with
 //                    -v "Verification" — this driver's own serial BFS per source must give the same reached, depth_sum and levels —, then the "@@@"
 //                    line; after the last trial the top five sources by closeness in PrintTopScores' shape (ties: the earlier source).  Not sharded.
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  pr [-i ITERS] [-t TOL]   the reference's PageRank driver (log_graph/pr.cc:100-114: PageRankPull with at most ITERS sweeps — default 20 — until the
+//                    L1 change of a sweep is below TOL — default 1e-4; for this subcommand -t is the tolerance, as in the reference's CLPageRank —,
+//                    PrintTopScores, PRVerifier) on the device (gmsx_pagerank, damping 0.85, in double): per trial "Trial Time", "Iterations", "Error"
+//                    and with -v "Verification" — PRVerifier's rule, residual < TOL, with the residual from gmsx_pagerank_residual and, beside it,
+//                    from this driver's own serial push sweep over the host CSR (pr.cc:79-97), which must agree —, then the "@@@" line; after the
+//                    last trial PrintTopScores' five id:score lines (pr.cc:64-74; ties: the smaller id).  Not sharded.
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -104,6 +110,8 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     bool metric_given = false;
     int64_t start = -1;  // bfs, bc -r SOURCE (gapbs/command_line.h: start_vertex)
     int64_t iters = 1;   // bc -i ITERS
+    bool iters_given = false;
+    double tol = 1e-4;   // pr -t TOL
     int error = 0;
 };
 
@@ -132,6 +140,7 @@ Args parse(int argc, char **argv) {
         auto need = [&](int k) { if (i + k >= argc) { a.error = 100; return false; } return true; };
         if (f == "-v" || f == "--verify") a.verify = true;
         else if (f == "-n" || f == "--num-trials") { if (!need(1)) break; a.trials = std::atoll(argv[++i]); }
+        else if (f == "-t" && a.kernel == "pr") { if (!need(1)) break; a.tol = std::atof(argv[++i]); if (!(a.tol >= 0.0)) a.error = 100; }
         else if (f == "-t" || f == "--threads") { if (!need(1)) break; a.threads = std::atoll(argv[++i]); }
         else if (f == "-f" || f == "--file") { if (!need(1)) break; a.file = argv[++i]; }
         else if (f == "-g" || f == "--gen") { if (!need(2)) break; a.gen = argv[++i]; a.scale = std::atoi(argv[++i]); }
@@ -139,7 +148,7 @@ Args parse(int argc, char **argv) {
         else if (f == "--list") { if (!need(1)) break; a.list = argv[++i]; }
         else if (f == "--metric") { if (!need(1)) break; a.metric = argv[++i]; a.metric_given = true; }
         else if (f == "-r") { if (!need(1)) break; a.start = std::atoll(argv[++i]); if (a.start < 0 || a.start > INT32_MAX) a.error = 100; }
-        else if (f == "-i") { if (!need(1)) break; a.iters = std::atoll(argv[++i]); if (a.iters < 1) a.error = 100; }
+        else if (f == "-i") { if (!need(1)) break; a.iters = std::atoll(argv[++i]); a.iters_given = true; if (a.iters < 1) a.error = 100; }
         else if (f == "-q") { if (!need(1)) break; a.q = std::atoll(argv[++i]); if (a.q < 1) a.error = 100; }
         else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; }
         else if (f == "--mono") a.mono = true;
@@ -166,11 +175,12 @@ Args parse(int argc, char **argv) {
     if (!a.error && a.file.empty() && a.gen.empty()) a.error = 101;  // cli/cli.h:131-133
     if (!a.error && !a.gen.empty() && a.gen != "kronecker" && a.gen != "uniform") a.error = 100;
     if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp" && a.kernel != "sgi") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
-    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss" || a.kernel == "sgi" || a.kernel == "cc" || a.kernel == "jp" || a.kernel == "motifs") && a.gpus > 1) a.error = 100;
+    if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss" || a.kernel == "sgi" || a.kernel == "cc" || a.kernel == "jp" || a.kernel == "motifs" || a.kernel == "pr") && a.gpus > 1) a.error = 100;
     if (!a.error && ((a.kernel == "jp") != !std::isnan(a.threshold))) a.error = 100;  // the threshold is required, and only there
     const bool traversal = a.kernel == "bfs" || a.kernel == "bc" || a.kernel == "closeness";
     if (!a.error && traversal && (a.gpus > 1 || a.metric_given)) a.error = 100;  // a traversal is global; it has no metric
-    if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc" && a.kernel != "closeness"))) a.error = 100;
+    if (!a.error && a.kernel == "pr" && a.metric_given) a.error = 100;              // … nor has PageRank
+    if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc" && a.kernel != "closeness" && a.kernel != "pr"))) a.error = 100;
     if (!a.error && ((a.kernel == "sgi") != !a.pattern_file.empty() || (a.mono && a.kernel != "sgi"))) a.error = 100;  // util/command_line.hpp:22: the pattern is required
     if (!a.error && (a.kernel == "lp" || a.kernel == "jp") && lp_metric(a.metric) < 0) a.error = 100;
     if (!a.error && !a.order.empty() && a.kernel != "bk" && a.kernel != "color") a.error = 100;  // only Bron–Kerbosch and the colouring have a preprocessing step
@@ -183,10 +193,10 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
                 "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE] "
-                "[jp: --metric NAME --threshold X] [bfs, bc, closeness: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES]\n", argv0);
+                "[jp: --metric NAME --threshold X] [bfs, bc, closeness: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES] [pr: -i ITERS -t TOL]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -835,6 +845,51 @@ int run_closeness(const Args &args, const gmsx::HipSetGraph &g, const HostGraph 
     return 0;
 }
 
+// PageRank (pr) under the usual trial loop: PageRankPull's sweeps on the device, PRVerifier's rule from gmsx_pagerank_residual and from this
+// driver's own serial push sweep (pr.cc:79-97, in double), PrintTopScores' lines at the end
+int run_pagerank(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
+    const double damping = 0.85;  // kDamp
+    const int32_t iters = args.iters_given ? int32_t(std::min<int64_t>(args.iters, INT32_MAX)) : 20;
+    double total_seconds = 0;
+    Timer t;
+    std::vector<double> scores;
+    gmsx_pagerank_info pi{};
+    for (int64_t it = 0; it < args.trials; ++it) {
+        t.Start();
+        gmsx::pagerank(g, scores, damping, iters, args.tol, nullptr, GMSX_PR_DEFAULT, &pi);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        PrintLabel("Iterations", std::to_string(pi.iterations));
+        std::printf("%-21s%g\n", "Error:", pi.error);
+        if (args.verify) {
+            const double residual = gmsx::pagerank_residual(g, scores, damping);
+            std::vector<double> incoming(size_t(hg.n), 0.0);
+            for (int64_t u = 0; u < hg.n; ++u) {
+                const int64_t deg = hg.off[u + 1] - hg.off[u];
+                if (deg == 0) continue;
+                const double contrib = scores[size_t(u)] / double(deg);
+                for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j) incoming[size_t(hg.adj[j])] += contrib;
+            }
+            double mine = 0.0, mass = 0.0;
+            const double base = (1.0 - damping) / double(hg.n > 0 ? hg.n : 1);
+            for (int64_t v = 0; v < hg.n; ++v) {
+                mine += std::fabs(base + damping * incoming[size_t(v)] - scores[size_t(v)]);
+                mass += scores[size_t(v)];
+            }
+            // the two residuals are the same sum taken in two orders: they differ by rounding only (2^-40 of the mass is far above it)
+            const bool ok = residual < args.tol && mine < args.tol && std::fabs(residual - mine) <= std::ldexp(mass > 1.0 ? mass : 1.0, -40);
+            std::printf("%-21s%g\n", "Residual:", residual);
+            PrintLabel("Verification", ok ? "PASS" : "FAIL");
+        }
+        std::cout << "@@@ pagerank" << std::endl;
+    }
+    if (args.trials > 0)
+        for (const auto &kv : gmsx::top_scores(scores, 5)) std::cout << kv.first << ":" << kv.second << std::endl;
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
 // subgraph matching: the reference's VF2 drivers (subgraphiso_vf2_sequential.cpp:33-51) over gmsx::subgraph_isomorphisms
 int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
     gmsx_csr *pc = nullptr;
@@ -896,7 +951,7 @@ int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -970,8 +1025,8 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness") {
-        const int rc_run = args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr") {
+        const int rc_run = args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
                                                                                                                                         : run_components(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);

@@ -1185,6 +1185,9 @@ static void free_graph(gmsx_graph *g) {
     (void)hipFree(g->kc_relt);
     (void)hipFree(g->kc_rect);
     (void)hipFree(g->kc_itemt);
+    (void)hipFree(g->pr_bins);
+    (void)hipFree(g->pr_first);
+    (void)hipFree(g->pr_slot_row);
     (void)hipFree(g->scratch);
     (void)hipFree(g->acc);
     delete g;

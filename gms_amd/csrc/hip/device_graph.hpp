@@ -216,6 +216,14 @@ struct gmsx_graph {
     mutable int64_t kc_recst = 0, kc_itemst = 0;
     mutable int64_t kc_recs = 0, kc_items = 0, kc_arena_words = 0, kc_rev_bytes = 0;
     mutable double kc_rev_build_ms = 0.0;    // what building the lists took (reported once, in gmsx_stats.setup_ms of the call that built them)
+    // PageRank ROW CLASSES (pagerank.hip, ensure_pr_bins — built at the first PageRank call): the n vertices class by class (degree 0; a lane,
+    // a 16-lane group, chunks of a wave per row), every class ascending in the vertex id; class c = pr_bins[pr_base[c], pr_base[c + 1])
+    mutable bool pr_ready = false;
+    mutable int32_t *pr_bins = nullptr;      // [n]
+    mutable int64_t pr_base[5] = {0, 0, 0, 0, 0};
+    mutable int64_t *pr_first = nullptr;     // [long rows + 1] first chunk slot of a long row (in class order); the last entry = pr_slots
+    mutable int32_t *pr_slot_row = nullptr;  // [pr_slots] which long row a slot belongs to
+    mutable int64_t pr_slots = 0;
     unsigned long long *scratch = nullptr;  // device: a few u64 accumulators
     unsigned long long *acc = nullptr;      // device: 64 spread u64 accumulators (128 B apart) + a few control words, reused by every call
     // host-side memo of read-only facts about the immutable graph (filled lazily; handles are single-threaded)

@@ -803,6 +803,41 @@ int gmsx_bfs_multi(const gmsx_graph *g, int64_t n_sources, const int32_t *source
                    int32_t *far      /* n: largest depth_i(v) over them, -1 if none; host, or NULL */,
                    gmsx_bfs_multi_info *info /* required */, gmsx_stats *stats);
 
+/* ---- PageRank (gms/representations/graphs/log_graph/pr.cc: PageRankPull, PRVerifier; pagerank.hip), the reference's constants as arguments
+ * (its own: damping 0.85, 20 sweeps, tolerance 1e-4).  t = teleport / Σ teleport (the host sums it ascending, in double), or 1 / n per entry when
+ * teleport is NULL.  scores = t at the start; every sweep computes contrib[v] = scores[v] / deg(v), new[u] = (1 - damping) t[u] + damping
+ * Σ_{v in N(u)} contrib[v] and error = Σ_u |new[u] - old[u]|; the loop stops behind the sweep whose error < tolerance, or after max_iters sweeps
+ * (tolerance = 0 never stops early, max_iters = 0 returns t).  A vertex of degree 0 keeps (1 - damping) t[u] and its own mass is dropped, as the
+ * reference drops it (so sum < 1 when such vertices exist); the device never divides by zero.  GMSX_PR_DANGLING hands that mass D = Σ_{deg(v) = 0}
+ * old[v] back through t: new[u] += damping D t[u], and sum stays 1 up to rounding.  GMSX_PR_FLOAT32 holds scores and contributions as float, the
+ * reference's ScoreT — every row sum and the error are still accumulated in double, and every value of `scores` is exactly a float; the default
+ * is double throughout.  gmsx_pagerank_residual is PRVerifier (pr.cc:79-97) as a number: Σ_u |(1 - damping) t[u] + damping Σ contrib[v] (+ the
+ * dangling term) - scores[u]| for one sweep over the caller's scores; nothing is stored; PRVerifier(g, s, tol) <=> residual < tol.
+ * No floating-point atomic is used: a row's sum is taken by a rule that is a function of the row's length alone (pagerank.hip states it), and the
+ * per-sweep error, sum and D are reduced over fixed blocks of vertices by a fixed tree — scores and every info field are byte-identical in every
+ * run and process, under GMSX_UPLOAD_TRUSTED, GMSX_UPLOAD_HUB_LIMIT and a sharded upload.  NULL g, info or residual, NULL scores in
+ * gmsx_pagerank_residual with n > 0, damping outside [0, 1] or NaN, max_iters < 0, a negative or NaN tolerance, a teleport with a negative, NaN
+ * or infinite entry or with sum 0, unknown flag bits: GMSX_ERR_INVALID, nothing written.  n = 0: GMSX_OK, info zeroed (argmax = -1).  A bin list
+ * that would overflow, a bin total that is not n, or a non-finite score: GMSX_ERR_KERNEL.  The caller's arrays are written only after the device
+ * flag word was read as zero.  Single GPU, no shards.  gmsx_stats: kernel_ms (the sweeps), setup_ms (binning, teleport upload, final reductions),
+ * launches, units = iterations * nnz, probes = iterations. */
+enum { GMSX_PR_DEFAULT = 0, GMSX_PR_DANGLING = 1, GMSX_PR_FLOAT32 = 2 };
+typedef struct {
+    int32_t iterations;   /* sweeps executed (<= max_iters) */
+    int32_t converged;    /* 1 iff the last sweep's error < tolerance */
+    int32_t argmax;       /* vertex of the largest score; ties: the smallest id; -1 for n = 0 */
+    int32_t reserved;
+    double  error;        /* Σ_u |new[u] - old[u]| of the last sweep; 0.0 when iterations == 0 */
+    double  sum;          /* Σ_u scores[u] */
+    double  max_score;
+    int64_t isolated;     /* vertices of degree 0 */
+} gmsx_pagerank_info;
+int gmsx_pagerank(const gmsx_graph *g, double damping, int32_t max_iters, double tolerance,
+                  const double *teleport /* n, host, or NULL = uniform */, uint32_t flags,
+                  double *scores /* n, host, or NULL */, gmsx_pagerank_info *info /* required */, gmsx_stats *stats);
+int gmsx_pagerank_residual(const gmsx_graph *g, const double *scores /* n, host */, double damping,
+                           const double *teleport, uint32_t flags, double *residual, gmsx_stats *stats);
+
 /* ---- 4-cycle counting and the 3- / 4-vertex motif census.  No reference counterpart (like the k-truss: a member of the family the suite
  * describes and does not build).  All results are exact integers.
  * gmsx_cycle4_count: *cycles = the 4-cycles of the graph (subgraphs, not necessarily induced; the butterflies of a bipartite graph).

@@ -39,6 +39,8 @@
 //   gmsx::betweenness(g, sources, scores) -> gmsx_betweenness       (log_graph/bc.cc:89-153, Brandes from the listed sources, in double)
 //   gmsx::bfs_multi(g, sources, per_source, …) -> gmsx_bfs_multi    (a BFS from every listed source, 64 per sweep: per-source sums, optional depths and per-vertex farness; no reference driver)
 //   gmsx::closeness(g, sources, out_scores, harmonic = false) -> gmsx_bfs_multi (closeness or harmonic centrality of the listed sources; returns the largest)
+//   gmsx::pagerank(g, scores, damping, max_iters, tolerance, …) -> gmsx_pagerank  (log_graph/pr.cc:34-61, PageRankPull; in double unless GMSX_PR_FLOAT32)
+//   gmsx::pagerank_residual(g, scores, …) -> gmsx_pagerank_residual  (pr.cc:79-97, PRVerifier as a number);  gmsx::top_scores(scores, k): PrintTopScores' top k on the host
 //   gmsx::pick_sources(csr, count)       -> gmsx_csr_pick_sources   (gapbs/benchmark.h:51-75, SourcePicker)
 //   gmsx::cycle4_count(g) / cycle4_count(g, at_vertex) -> gmsx_cycle4_count (the 4-cycles, and those through every vertex; no reference driver)
 //   gmsx::motif_census4(g)               -> gmsx_motif_census4     (the eight 3- and 4-vertex motifs, non-induced and induced; no reference driver)
@@ -735,6 +737,43 @@ inline double closeness(const HipGraphT<S> &g, const std::vector<int32_t> &sourc
         if (out_scores[i] > top) top = out_scores[i];
     }
     return top;
+}
+// PageRankPull(g, max_iters, epsilon) (log_graph/pr.cc:34-61) with its constants as arguments (the defaults are the reference's) and in double
+// unless GMSX_PR_FLOAT32 asks for its float; teleport: n non-negative weights or nullptr = uniform; flags: GMSX_PR_*.  Returns the number of
+// sweeps executed.
+template <class S>
+inline int32_t pagerank(const HipGraphT<S> &g, std::vector<double> &scores, double damping = 0.85, int32_t max_iters = 20, double tolerance = 1e-4,
+                        const std::vector<double> *teleport = nullptr, uint32_t flags = GMSX_PR_DEFAULT, gmsx_pagerank_info *info = nullptr) {
+    scores.resize(size_t(g.num_nodes()));
+    if (teleport && teleport->size() != scores.size()) detail::check(GMSX_ERR_INVALID, "gmsx_pagerank");
+    gmsx_pagerank_info pi{};
+    detail::check(gmsx_pagerank(g.device(), damping, max_iters, tolerance, teleport && !teleport->empty() ? teleport->data() : nullptr, flags,
+                                scores.empty() ? nullptr : scores.data(), &pi, nullptr),
+                  "gmsx_pagerank");
+    if (info) *info = pi;
+    return pi.iterations;
+}
+// PRVerifier(g, scores, target_error) (pr.cc:79-97) as a number: the L1 change of one sweep over `scores`; the reference accepts iff it is
+// below its tolerance
+template <class S>
+inline double pagerank_residual(const HipGraphT<S> &g, const std::vector<double> &scores, double damping = 0.85,
+                                const std::vector<double> *teleport = nullptr, uint32_t flags = GMSX_PR_DEFAULT) {
+    if (scores.size() != size_t(g.num_nodes()) || (teleport && teleport->size() != scores.size())) detail::check(GMSX_ERR_INVALID, "gmsx_pagerank_residual");
+    double r = 0.0;
+    detail::check(gmsx_pagerank_residual(g.device(), scores.empty() ? nullptr : scores.data(), damping,
+                                         teleport && !teleport->empty() ? teleport->data() : nullptr, flags, &r, nullptr),
+                  "gmsx_pagerank_residual");
+    return r;
+}
+// PrintTopScores' top k (pr.cc:64-74, gapbs/util.h TopK) on the host: the k largest scores as (id, score), largest first, ties by the smaller id
+inline std::vector<std::pair<int32_t, double>> top_scores(const std::vector<double> &scores, size_t k) {
+    std::vector<std::pair<double, int32_t>> key(scores.size());  // (-score, id): ascending = largest first, ties by the smaller id
+    for (size_t v = 0; v < scores.size(); ++v) key[v] = {-scores[v], int32_t(v)};
+    k = std::min(k, key.size());
+    std::partial_sort(key.begin(), key.begin() + std::ptrdiff_t(k), key.end());
+    std::vector<std::pair<int32_t, double>> out(k);
+    for (size_t i = 0; i < k; ++i) out[i] = {key[i].second, -key[i].first};
+    return out;
 }
 // SourcePicker (gapbs/benchmark.h:51-75): its first `count` picks, or `count` copies of `given`
 inline std::vector<int32_t> pick_sources(const gmsx_csr *csr, int64_t count, int32_t given = -1) {
