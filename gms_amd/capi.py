@@ -47,6 +47,8 @@ SYMBOLS = [
     "gmsx_connected_components", "gmsx_jarvis_patrick",
     "gmsx_bfs", "gmsx_betweenness", "gmsx_bfs_multi",
     "gmsx_pagerank", "gmsx_pagerank_residual",
+    "gmsx_csr_weights", "gmsx_csr_generate_weighted", "gmsx_csr_from_weighted_edges", "gmsx_csr_load_weighted", "gmsx_csr_save_wsg",
+    "gmsx_csr_from_arrays_weighted", "gmsx_graph_set_weights", "gmsx_graph_has_weights", "gmsx_sssp", "gmsx_sssp_verify",
     "gmsx_cycle4_count", "gmsx_cycle4_partial", "gmsx_motif_census4",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -189,6 +191,22 @@ class PagerankInfo(C.Structure):
     def as_dict(self):
         return {"iterations": int(self.iterations), "converged": int(self.converged), "argmax": int(self.argmax), "error": float(self.error),
                 "sum": float(self.sum), "max_score": float(self.max_score), "isolated": int(self.isolated)}
+
+
+class SsspInfo(C.Structure):
+    _fields_ = [("reached", C.c_int64), ("reached_arcs", C.c_int64), ("dist_sum", C.c_int64), ("max_dist", C.c_int64), ("delta", C.c_int64),
+                ("buckets", C.c_int64), ("rounds", C.c_int64), ("relaxations", C.c_int64), ("far_vertex", C.c_int32), ("wide", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class SsspCheck(C.Structure):
+    _fields_ = [("violated_arcs", C.c_int64), ("untight", C.c_int64), ("wrong_unreached", C.c_int64), ("source_ok", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
 class MotifInfo(C.Structure):
@@ -376,6 +394,17 @@ def lib():
     L.gmsx_pagerank.argtypes = [vp, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(PagerankInfo), sp]
     L.gmsx_pagerank_residual.argtypes = [vp, C.c_void_p, C.c_double, C.c_void_p, C.c_uint32, C.POINTER(C.c_double), sp]
     L.gmsx_csr_pick_sources.argtypes = [vp, C.c_int64, C.c_int32, C.c_void_p]
+    L.gmsx_csr_weights.restype = C.POINTER(C.c_int32)
+    L.gmsx_csr_weights.argtypes = [vp]
+    L.gmsx_csr_generate_weighted.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vpp]
+    L.gmsx_csr_from_weighted_edges.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, vpp]
+    L.gmsx_csr_load_weighted.argtypes = [C.c_char_p, C.c_int, C.c_int, vpp]
+    L.gmsx_csr_save_wsg.argtypes = [vp, C.c_char_p]
+    L.gmsx_csr_from_arrays_weighted.argtypes = [C.c_int64, _i64p, C.c_void_p, C.c_void_p, vpp]
+    L.gmsx_graph_set_weights.argtypes = [vp, C.c_void_p]
+    L.gmsx_graph_has_weights.argtypes = [vp]
+    L.gmsx_sssp.argtypes = [vp, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(SsspInfo), sp]
+    L.gmsx_sssp_verify.argtypes = [vp, C.c_int32, C.c_void_p, C.POINTER(SsspCheck), sp]
     L.gmsx_cycle4_count.argtypes = [vp, u64p, C.c_void_p, sp]
     L.gmsx_cycle4_partial.argtypes = [vp, C.c_int, C.c_int, u64p, sp]
     L.gmsx_motif_census4.argtypes = [vp, C.POINTER(MotifInfo), sp]
@@ -445,6 +474,60 @@ class HostCSR:
         _check(lib().gmsx_csr_from_arrays(off.size - 1, off, neigh if neigh.size else np.zeros(1, np.int32), C.byref(h)),
                "gmsx_csr_from_arrays")
         return cls(h)
+
+    @classmethod
+    def generate_weighted(cls, generator="kronecker", scale=10, degree=16, relabel=RELABEL_NEVER, threads=0):
+        """gmsx_csr_generate_weighted: the reference's WeightedBuilder on a generated graph (weights 1 … 255 by InsertWeights)."""
+        h = C.c_void_p()
+        gen = GEN_UNIFORM if generator in ("uniform", "u", GEN_UNIFORM) else GEN_KRONECKER
+        _check(lib().gmsx_csr_generate_weighted(gen, scale, degree, relabel, threads, C.byref(h)), "gmsx_csr_generate_weighted")
+        return cls(h)
+
+    @classmethod
+    def from_weighted_edges(cls, src, dst, w=None, num_nodes=-1, symmetrize=True, relabel=RELABEL_NEVER):
+        """gmsx_csr_from_weighted_edges; w = None: InsertWeights over the list."""
+        src = np.ascontiguousarray(src, dtype=np.int32)
+        dst = np.ascontiguousarray(dst, dtype=np.int32)
+        ww = None if w is None else np.ascontiguousarray(w, dtype=np.int32)
+        pad = np.zeros(1, np.int32)
+        h = C.c_void_p()
+        _check(lib().gmsx_csr_from_weighted_edges(num_nodes, src.size, (src if src.size else pad).ctypes.data_as(C.c_void_p),
+                                                  (dst if dst.size else pad).ctypes.data_as(C.c_void_p),
+                                                  None if ww is None else (ww if ww.size else pad).ctypes.data_as(C.c_void_p),
+                                                  int(symmetrize), relabel, C.byref(h)), "gmsx_csr_from_weighted_edges")
+        return cls(h)
+
+    @classmethod
+    def load_weighted(cls, path, symmetrize=True, relabel=RELABEL_NEVER):
+        h = C.c_void_p()
+        _check(lib().gmsx_csr_load_weighted(os.fsencode(path), int(symmetrize), relabel, C.byref(h)), "gmsx_csr_load_weighted")
+        return cls(h)
+
+    @classmethod
+    def from_arrays_weighted(cls, off, neigh, weights):
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        neigh = np.ascontiguousarray(neigh, dtype=np.int32)
+        weights = np.ascontiguousarray(weights, dtype=np.int32)
+        pad = np.zeros(1, np.int32)
+        h = C.c_void_p()
+        _check(lib().gmsx_csr_from_arrays_weighted(off.size - 1, off, (neigh if neigh.size else pad).ctypes.data_as(C.c_void_p),
+                                                   (weights if weights.size else pad).ctypes.data_as(C.c_void_p), C.byref(h)),
+               "gmsx_csr_from_arrays_weighted")
+        return cls(h)
+
+    def save_wsg(self, path):
+        _check(lib().gmsx_csr_save_wsg(self._h, os.fsencode(path)), "gmsx_csr_save_wsg")
+
+    def weights(self):
+        """int32[nnz] view of the weight array (valid while this object lives), or None for an unweighted CSR."""
+        p = lib().gmsx_csr_weights(self._h)
+        if not p:
+            return None
+        nnz = self.nnz
+        return np.ctypeslib.as_array(p, shape=(nnz,)) if nnz else np.zeros(0, dtype=np.int32)
+
+    def weights_fingerprint(self):
+        return int(lib().gmsx_csr_fingerprint(self._h, 2))
 
     def save_sg(self, path):
         _check(lib().gmsx_csr_save_sg(self._h, os.fsencode(path)), "gmsx_csr_save_sg")
@@ -1085,6 +1168,36 @@ class DeviceGraph:
                                             tp.ctypes.data_as(C.c_void_p) if tp is not None and n else None, flags, C.byref(out), C.byref(st)),
                "gmsx_pagerank_residual")
         return (out.value, st.as_dict()) if stats else out.value
+
+    def set_weights(self, w):
+        """gmsx_graph_set_weights: int32 w[nnz] parallel to the uploaded neighbour array; None detaches."""
+        if w is None:
+            _check(lib().gmsx_graph_set_weights(self._h, None), "gmsx_graph_set_weights")
+            return
+        w = np.ascontiguousarray(w, dtype=np.int32)
+        _check(lib().gmsx_graph_set_weights(self._h, (w if w.size else np.zeros(1, np.int32)).ctypes.data_as(C.c_void_p)), "gmsx_graph_set_weights")
+
+    has_weights = property(lambda self: bool(lib().gmsx_graph_has_weights(self._h)))
+
+    def sssp(self, source, delta=0, want_dist=True, want_parent=True, stats=False):
+        """gmsx_sssp from `source`: (dist int64[n] or None, parent int32[n] or None, {reached, reached_arcs, dist_sum, max_dist, delta, buckets,
+        rounds, relaxations, far_vertex, wide}).  -1 = unreachable; parent[v] is the smallest-id neighbour on a lightest path."""
+        n = self.num_nodes
+        dist = np.zeros(max(n, 1), dtype=np.int64) if want_dist else None
+        parent = np.zeros(max(n, 1), dtype=np.int32) if want_parent else None
+        info, st = SsspInfo(), Stats()
+        _check(lib().gmsx_sssp(self._h, int(source), int(delta), dist.ctypes.data_as(C.c_void_p) if want_dist else None,
+                               parent.ctypes.data_as(C.c_void_p) if want_parent else None, C.byref(info), C.byref(st)), "gmsx_sssp")
+        r = (dist[:n] if want_dist else None, parent[:n] if want_parent else None, info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def sssp_verify(self, source, dist, stats=False):
+        """gmsx_sssp_verify of a caller's distances: {violated_arcs, untight, wrong_unreached, source_ok}."""
+        d = np.ascontiguousarray(dist, dtype=np.int64)
+        out, st = SsspCheck(), Stats()
+        _check(lib().gmsx_sssp_verify(self._h, int(source), (d if d.size else np.zeros(1, np.int64)).ctypes.data_as(C.c_void_p), C.byref(out),
+                                      C.byref(st)), "gmsx_sssp_verify")
+        return (out.as_dict(), st.as_dict()) if stats else out.as_dict()
 
     def cycle4_count(self, at_vertex=False, stats=False):
         """gmsx_cycle4_count: the 4-cycles of the graph; with at_vertex=True (cycles, int64[n] — the 4-cycles through every vertex of the

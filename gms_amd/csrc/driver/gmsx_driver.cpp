@@ -68,7 +68,12 @@
 //                    and with -v "Verification" — PRVerifier's rule, residual < TOL, with the residual from gmsx_pagerank_residual and, beside it,
 //                    from this driver's own serial push sweep over the host CSR (pr.cc:79-97), which must agree —, then the "@@@" line; after the
 //                    last trial PrintTopScores' five id:score lines (pr.cc:64-74; ties: the smaller id).  Not sharded.
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  sssp [-r SOURCE] [-d DELTA]   the reference's shortest-path driver (log_graph/sssp.cc:178-199: DeltaStep from SourcePicker's sources,
+//                    PrintSSSPStats, SSSPVerifier) on the device (gmsx_sssp): a -g graph gets the generator's weights (InsertWeights), a -f file
+//                    .wel / .gr / .wsg keeps its own and an .el gets the generator's; the graph is not relabelled (sssp.cc does not).  Per trial
+//                    "Trial Time", "Source", "Delta", "Buckets" and with -v "Verification" (gmsx_sssp_verify's verdict), then the "@@@" line; after
+//                    the last trial PrintSSSPStats' line.  -d 0 (the default) = the library's choice.  Not sharded (--gpus > 1 is refused).
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -112,6 +117,7 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     int64_t iters = 1;   // bc -i ITERS
     bool iters_given = false;
     double tol = 1e-4;   // pr -t TOL
+    int64_t delta = 0;   // sssp -d DELTA (0: the library's choice)
     int error = 0;
 };
 
@@ -148,6 +154,7 @@ Args parse(int argc, char **argv) {
         else if (f == "--list") { if (!need(1)) break; a.list = argv[++i]; }
         else if (f == "--metric") { if (!need(1)) break; a.metric = argv[++i]; a.metric_given = true; }
         else if (f == "-r") { if (!need(1)) break; a.start = std::atoll(argv[++i]); if (a.start < 0 || a.start > INT32_MAX) a.error = 100; }
+        else if (f == "-d" && a.kernel == "sssp") { if (!need(1)) break; a.delta = std::atoll(argv[++i]); if (a.delta < 0) a.error = 100; }
         else if (f == "-i") { if (!need(1)) break; a.iters = std::atoll(argv[++i]); a.iters_given = true; if (a.iters < 1) a.error = 100; }
         else if (f == "-q") { if (!need(1)) break; a.q = std::atoll(argv[++i]); if (a.q < 1) a.error = 100; }
         else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; }
@@ -177,7 +184,7 @@ Args parse(int argc, char **argv) {
     if (!a.error && !a.list.empty() && ((a.kernel != "bk" && a.kernel != "kcstar" && a.kernel != "lp" && a.kernel != "sgi") || a.gpus > 1)) a.error = 100;  // one process writes the whole list
     if (!a.error && (a.kernel == "kcstar" || a.kernel == "lp" || a.kernel == "truss" || a.kernel == "sgi" || a.kernel == "cc" || a.kernel == "jp" || a.kernel == "motifs" || a.kernel == "pr") && a.gpus > 1) a.error = 100;
     if (!a.error && ((a.kernel == "jp") != !std::isnan(a.threshold))) a.error = 100;  // the threshold is required, and only there
-    const bool traversal = a.kernel == "bfs" || a.kernel == "bc" || a.kernel == "closeness";
+    const bool traversal = a.kernel == "bfs" || a.kernel == "bc" || a.kernel == "closeness" || a.kernel == "sssp";
     if (!a.error && traversal && (a.gpus > 1 || a.metric_given)) a.error = 100;  // a traversal is global; it has no metric
     if (!a.error && a.kernel == "pr" && a.metric_given) a.error = 100;              // … nor has PageRank
     if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc" && a.kernel != "closeness" && a.kernel != "pr"))) a.error = 100;
@@ -193,10 +200,10 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
                 "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE] "
-                "[jp: --metric NAME --threshold X] [bfs, bc, closeness: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES] [pr: -i ITERS -t TOL]\n", argv0);
+                "[jp: --metric NAME --threshold X] [bfs, bc, closeness, sssp: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES] [pr: -i ITERS -t TOL] [sssp: -d DELTA]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -890,6 +897,44 @@ int run_pagerank(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &
     return 0;
 }
 
+// shortest paths (sssp) under the usual trial loop: DeltaStep on the device from the t-th picked source, SSSPVerifier as gmsx_sssp_verify's four
+// numbers, PrintSSSPStats' line (sssp.cc:137-141) at the end
+int run_sssp(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg, const gmsx_csr *csr) {
+    if (args.start >= hg.n) { std::printf("-r %lld: the graph has %lld vertices\n", (long long)args.start, (long long)hg.n); return 100; }
+    std::vector<int32_t> picks(size_t(std::max<int64_t>(args.trials, 0)) + 1);
+    if (int rc = gmsx_csr_pick_sources(csr, int64_t(picks.size()) - 1, int32_t(args.start), picks.data())) {
+        std::printf("no source to pick: %s\n", gmsx_strerror(rc));
+        return 2;
+    }
+    gmsx::detail::check(gmsx_graph_set_weights(const_cast<gmsx_graph *>(g.device()), gmsx_csr_weights(csr)), "gmsx_graph_set_weights");
+    double total_seconds = 0;
+    Timer t;
+    std::vector<int64_t> dist;
+    gmsx_sssp_info info{};
+    for (int64_t it = 0; it < args.trials; ++it) {
+        const int32_t source = picks[size_t(it)];
+        t.Start();
+        gmsx::sssp(g, source, dist, args.delta, nullptr, &info);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        PrintLabel("Source", std::to_string(source));
+        PrintLabel("Delta", std::to_string(info.delta));
+        PrintLabel("Buckets", std::to_string(info.buckets));
+        if (args.verify) {
+            gmsx_sssp_check c{};
+            const bool ok = gmsx::sssp_verify(g, source, dist, &c);
+            std::printf("%-21s%lld violated, %lld untight, %lld wrongly unreached\n", "Check:", (long long)c.violated_arcs, (long long)c.untight,
+                        (long long)c.wrong_unreached);
+            PrintLabel("Verification", ok ? "PASS" : "FAIL");
+        }
+        std::cout << "@@@ sssp" << std::endl;
+    }
+    if (args.trials > 0) std::cout << "SSSP Tree reaches " << info.reached << " nodes" << std::endl;
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
 // subgraph matching: the reference's VF2 drivers (subgraphiso_vf2_sequential.cpp:33-51) over gmsx::subgraph_isomorphisms
 int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
     gmsx_csr *pc = nullptr;
@@ -951,7 +996,7 @@ int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr" && args.kernel != "sssp") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -971,7 +1016,11 @@ int main(int argc, char **argv) {
     t.Start();
     int rc;
     const int relabel = args.kernel == "sgi" ? GMSX_RELABEL_NEVER : GMSX_RELABEL_AUTO;  // the reference's subgraph drivers never relabel
-    if (!args.file.empty()) rc = gmsx_csr_load(args.file.c_str(), 1, relabel, &csr);
+    if (args.kernel == "sssp")  // WeightedBuilder: the weights of the file, or the generator's; never relabelled (sssp.cc:182-183)
+        rc = !args.file.empty() ? gmsx_csr_load_weighted(args.file.c_str(), 1, GMSX_RELABEL_NEVER, &csr)
+                                : gmsx_csr_generate_weighted(args.gen == "uniform" ? GMSX_GEN_UNIFORM : GMSX_GEN_KRONECKER, args.scale, args.deg,
+                                                             GMSX_RELABEL_NEVER, int(args.threads), &csr);
+    else if (!args.file.empty()) rc = gmsx_csr_load(args.file.c_str(), 1, relabel, &csr);
     else rc = gmsx_csr_generate(args.gen == "uniform" ? GMSX_GEN_UNIFORM : GMSX_GEN_KRONECKER, args.scale, args.deg, relabel,
                                 int(args.threads), &csr);
     t.Stop();
@@ -1025,8 +1074,8 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr") {
-        const int rc_run = args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr" || args.kernel == "sssp") {
+        const int rc_run = args.kernel == "sssp" ? run_sssp(args, g, hg, csr) : args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
                                                                                                                                         : run_components(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "device_buffer.hpp"
 #include "gmsx.h"
 #include "gmsx_internal.hpp"  // gmsx::guard: no exception crosses the C ABI
 
@@ -245,6 +246,14 @@ struct gmsx_graph {
     uint32_t upload_flags = 0;
     uint64_t alg_elements = 0;              // Σ_{u<v}(d_u+d_v), computed on the device at upload
     int64_t device_bytes = 0;
+    // EDGE WEIGHTS (gmsx_graph_set_weights, sssp.hip): int32[nnz] parallel to adj — two parallel arrays, not interleaved pairs, so that every
+    // unweighted kernel reads the bytes it always read.  Attached explicitly, validated on the device (every weight >= 1; symmetric unless the
+    // upload was TRUSTED), counted in device_bytes, released with the handle (DevBuf) or by a detach.
+    gmsx::DevBuf wgt;
+    int64_t wgt_bytes = 0;
+    int64_t wsum = 0;                       // Σ of the nnz weights
+    int32_t wmax = 0;
+    bool wide_dist = false;                 // (n − 1) · wmax does not fit below 2^31 − 1: distances are held in 64-bit words
 };
 
 namespace gmsx {

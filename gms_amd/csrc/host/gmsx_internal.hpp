@@ -50,6 +50,7 @@ struct Csr {
     int64_t nnz = 0;
     std::unique_ptr<int64_t[], ArrayFree> off;    // n + 1
     std::unique_ptr<int32_t[], ArrayFree> neigh;  // nnz
+    std::unique_ptr<int32_t[]> wgt;               // nnz, parallel to neigh, or empty: an unweighted CSR
     bool directed = false;
     bool mapped = false;  // off / neigh are private read-only mappings of a cache file: every process that loads it shares ONE copy in the page cache
 };

@@ -6,6 +6,8 @@
 //   builder    gms/third_party/gapbs/builder.h:108-117,145-156,206-298 (n = max id + 1, symmetrise, sort/unique/no-loop rows)
 //   relabel    gms/third_party/gapbs/builder.h:1699-1733, gapbs/benchmark.h:50-68,158-176 (WorthRelabelling)
 //   files      gms/third_party/gapbs/reader.h:49-56,252-305, writer.h:39-69
+//   weights    gms/third_party/gapbs/generator.h:131-146 (InsertWeights), builder.h:104 (GetSource), graph.h:39-46 (rows sorted by (id, weight),
+//              unique by id): an optional int32 array parallel to the neighbours — gmsx_csr_*_weighted, .wel / .gr / .wsg with their weights
 // The CSR it produces is bit-identical to the reference's (tests/test_loader.py: FNV fingerprints of
 // SURVEY Appendix B and array equality against the compiled reference).
 //
@@ -466,6 +468,27 @@ int relabel_by_degree(const Csr &g, Csr &out) {
     }
     if (int rc = alloc_csr(out, n, g.nnz)) return rc;
     prefix_sum(deg.get(), n, out.off.get());
+    if (g.wgt) {  // a weight travels with its arc: the row is re-sorted by id as (id, weight) pairs (ids are unique in a row)
+        out.wgt.reset(new (std::nothrow) int32_t[size_t(std::max<int64_t>(g.nnz, 1))]);
+        if (!out.wgt) return GMSX_ERR_NOMEM;
+#pragma omp parallel
+        {
+            std::vector<std::pair<int32_t, int32_t>> row;
+#pragma omp for schedule(dynamic, 256)
+            for (int64_t u = 0; u < n; ++u) {
+                row.clear();
+                for (int64_t e = g.off[u]; e < g.off[u + 1]; ++e) row.emplace_back(new_id[g.neigh[e]], g.wgt[e]);
+                std::sort(row.begin(), row.end());
+                const int64_t at = out.off[new_id[u]];
+                for (size_t k = 0; k < row.size(); ++k) {
+                    out.neigh[at + int64_t(k)] = row[k].first;
+                    out.wgt[at + int64_t(k)] = row[k].second;
+                }
+            }
+        }
+        out.directed = false;
+        return GMSX_OK;
+    }
 #pragma omp parallel for schedule(dynamic, 256)
     for (int64_t u = 0; u < n; ++u) {
         int32_t *dst = out.neigh.get() + out.off[new_id[u]];
@@ -723,6 +746,183 @@ static int read_sgx(const std::string &path, Csr &g) {
     return validate_csr_arrays(g.off.get(), g.neigh.get(), n, nnz);
 }
 
+// ---- weighted graphs: WeightedBuilder (builder.h with DestID_ = NodeWeight<NodeId, int32>) --------------------------------------------------
+
+struct WEdgeList {
+    EdgeList el;
+    std::unique_ptr<int32_t[]> w;
+    int alloc(int64_t edges) {
+        if (int rc = el.alloc(edges)) return rc;
+        w.reset(new (std::nothrow) int32_t[size_t(std::max<int64_t>(edges, 1))]);
+        return w ? GMSX_OK : GMSX_ERR_NOMEM;
+    }
+};
+
+// Generator::InsertWeights (generator.h:131-146): one mt19937 per block of 2^18 edges, seeded kRandSeed + block;
+// std::uniform_int_distribution<int>(1, 255) = 1 + an unbiased draw from [0, 254] (bounded_u32)
+static void insert_weights(int32_t *w, int64_t m) {
+#pragma omp parallel
+    {
+        std::mt19937 rng;
+#pragma omp for schedule(dynamic, 4)
+        for (int64_t block = 0; block < m; block += kGenBlock) {
+            rng.seed(uint32_t(kSeed + block / kGenBlock));
+            const int64_t end = std::min(block + kGenBlock, m);
+            for (int64_t e = block; e < end; ++e) w[e] = int32_t(1u + uniform_closed(rng, 254u));
+        }
+    }
+}
+
+// (id, weight) as one key that sorts like NodeWeight::operator< (graph.h:39-41): by id, then by the signed weight
+static inline uint64_t wkey(int32_t id, int32_t w) { return (uint64_t(uint32_t(id)) << 32) | uint64_t(uint32_t(w) ^ 0x80000000u); }
+static inline int32_t wkey_id(uint64_t k) { return int32_t(uint32_t(k >> 32)); }
+static inline int32_t wkey_weight(uint64_t k) { return int32_t(uint32_t(k) ^ 0x80000000u); }
+
+// MakeGraphFromEL + SquishGraph on a weighted list: both directions carry the edge's weight (GetSource, builder.h:104), a row is sorted by
+// (id, weight) and made unique by id alone (graph.h:43-46), so a repeated edge keeps its smallest weight; self loops are dropped.  The rows
+// are filled through atomic cursors; the per-row sort over whole keys makes the result independent of the thread count.
+static int build_from_wel(const WEdgeList &wl, int64_t num_nodes, bool symmetrize, Csr &out) {
+    const int64_t m = wl.el.m;
+    const int32_t *eu = wl.el.u.get(), *ev = wl.el.v.get(), *ew = wl.w.get();
+    if (num_nodes < 0) {
+        int32_t mx = 0;
+#pragma omp parallel for reduction(max : mx) schedule(static)
+        for (int64_t e = 0; e < m; ++e) mx = std::max(mx, std::max(eu[e], ev[e]));
+        num_nodes = int64_t(mx) + 1;
+    }
+    const int64_t n = num_nodes;
+    if (n > std::numeric_limits<int32_t>::max()) return GMSX_ERR_OVERFLOW;
+    int bad = 0;
+#pragma omp parallel for reduction(| : bad) schedule(static)
+    for (int64_t e = 0; e < m; ++e) bad |= int(eu[e] < 0 || ev[e] < 0 || eu[e] >= n || ev[e] >= n);
+    if (bad) return GMSX_ERR_INVALID;
+    std::unique_ptr<int64_t[]> cnt(new (std::nothrow) int64_t[size_t(n + 1)]);
+    std::unique_ptr<int64_t[]> raw_off(new (std::nothrow) int64_t[size_t(n + 1)]);
+    std::unique_ptr<int64_t[]> len(new (std::nothrow) int64_t[size_t(n + 1)]);
+    std::unique_ptr<int64_t[]> off(new (std::nothrow) int64_t[size_t(n + 1)]);
+    if (!cnt || !raw_off || !len || !off) return GMSX_ERR_NOMEM;
+    std::fill(cnt.get(), cnt.get() + n + 1, int64_t(0));
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < m; ++e) {
+        if (eu[e] == ev[e]) continue;
+#pragma omp atomic
+        ++cnt[eu[e]];
+        if (symmetrize) {
+#pragma omp atomic
+            ++cnt[ev[e]];
+        }
+    }
+    prefix_sum(cnt.get(), n, raw_off.get());
+    const int64_t raw_nnz = raw_off[n];
+    std::unique_ptr<uint64_t[]> raw(new (std::nothrow) uint64_t[size_t(std::max<int64_t>(raw_nnz, 1))]);
+    if (!raw) return GMSX_ERR_NOMEM;
+    std::copy(raw_off.get(), raw_off.get() + n + 1, cnt.get());  // the cursors
+#pragma omp parallel for schedule(static)
+    for (int64_t e = 0; e < m; ++e) {
+        const int32_t a = eu[e], c = ev[e];
+        if (a == c) continue;
+        int64_t p;
+#pragma omp atomic capture
+        p = cnt[a]++;
+        raw[p] = wkey(c, ew[e]);
+        if (symmetrize) {
+#pragma omp atomic capture
+            p = cnt[c]++;
+            raw[p] = wkey(a, ew[e]);
+        }
+    }
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int64_t u = 0; u < n; ++u) {
+        uint64_t *b = raw.get() + raw_off[u], *e = raw.get() + raw_off[u + 1];
+        std::sort(b, e);
+        len[u] = std::unique(b, e, [](uint64_t x, uint64_t y) { return (x >> 32) == (y >> 32); }) - b;
+    }
+    len[n] = 0;
+    prefix_sum(len.get(), n, off.get());
+    if (int rc = alloc_csr(out, n, off[n])) return rc;
+    out.wgt.reset(new (std::nothrow) int32_t[size_t(std::max<int64_t>(off[n], 1))]);
+    if (!out.wgt) return GMSX_ERR_NOMEM;
+    std::memcpy(out.off.get(), off.get(), size_t(n + 1) * sizeof(int64_t));
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int64_t u = 0; u < n; ++u)
+        for (int64_t k = 0; k < len[u]; ++k) {
+            const uint64_t key = raw[raw_off[u] + k];
+            out.neigh[off[u] + k] = wkey_id(key);
+            out.wgt[off[u] + k] = wkey_weight(key);
+        }
+    out.directed = !symmetrize;
+    return GMSX_OK;
+}
+
+static int push_wedge(std::vector<int32_t> &us, std::vector<int32_t> &vs, std::vector<int32_t> &ws, long long a, long long b, long long w) {
+    if (w < std::numeric_limits<int32_t>::min() || w > std::numeric_limits<int32_t>::max()) return GMSX_ERR_OVERFLOW;
+    if (int rc = push_edge(us, vs, a, b)) return rc;
+    ws.push_back(int32_t(w));
+    return GMSX_OK;
+}
+static int finish_wel(std::vector<int32_t> &us, std::vector<int32_t> &vs, std::vector<int32_t> &ws, WEdgeList &wl) {
+    if (int rc = wl.alloc(int64_t(us.size()))) return rc;
+    std::copy(us.begin(), us.end(), wl.el.u.get());
+    std::copy(vs.begin(), vs.end(), wl.el.v.get());
+    std::copy(ws.begin(), ws.end(), wl.w.get());
+    return GMSX_OK;
+}
+// .wel with its integer weights (reader.h:59-67: WeightT is int32): triples until the first parse failure, so a line without its third
+// column ends the list in front of it.  A weight that does not fit int32 fails the stream's extraction in the reference; here it is refused.
+static int read_wel_weighted(const std::string &path, WEdgeList &wl) {
+    std::ifstream in(path);
+    if (!in.is_open()) return GMSX_ERR_IO;
+    std::vector<int32_t> us, vs, ws;
+    long long a, b, w;
+    while (in >> a >> b >> w)
+        if (int rc = push_wedge(us, vs, ws, a, b, w)) return rc;
+    return finish_wel(us, vs, ws, wl);
+}
+static int read_gr_weighted(const std::string &path, WEdgeList &wl) {
+    std::ifstream in(path);
+    if (!in.is_open()) return GMSX_ERR_IO;
+    std::vector<int32_t> us, vs, ws;
+    std::string line;
+    while (std::getline(in, line)) {
+        if (line.empty() || line[0] != 'a') continue;
+        long long a, b, w;
+        char tag;
+        std::istringstream ls(line);
+        if (!(ls >> tag >> a >> b >> w)) return GMSX_ERR_FORMAT;
+        if (int rc = push_wedge(us, vs, ws, a - 1, b - 1, w)) return rc;
+    }
+    return finish_wel(us, vs, ws, wl);
+}
+
+// .wsg (reader.h:252-305, writer.h:39-69): bool directed; int64 nnz; int64 n; int64 offsets[n+1]; {int32 id, int32 weight} pairs[nnz]
+static int read_wsg(const std::string &path, Csr &g) {
+    std::FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) return GMSX_ERR_IO;
+    struct Closer { std::FILE *f; ~Closer() { std::fclose(f); } } closer{f};
+    struct stat st;
+    if (fstat(fileno(f), &st) != 0) return GMSX_ERR_IO;
+    unsigned char directed = 0;
+    int64_t nnz = 0, n = 0;
+    if (std::fread(&directed, 1, 1, f) != 1 || std::fread(&nnz, 8, 1, f) != 1 || std::fread(&n, 8, 1, f) != 1) return GMSX_ERR_FORMAT;
+    if (n < 0 || nnz < 0 || n > std::numeric_limits<int32_t>::max()) return GMSX_ERR_FORMAT;
+    // (a planted header must not size the allocations: the file has to hold what it announces)
+    if (nnz > (std::numeric_limits<int64_t>::max() - 17 - (n + 1) * 8) / 8 || int64_t(st.st_size) < 17 + (n + 1) * 8 + nnz * 8) return GMSX_ERR_FORMAT;
+    if (int rc = alloc_csr(g, n, nnz)) return rc;
+    g.wgt.reset(new (std::nothrow) int32_t[size_t(std::max<int64_t>(nnz, 1))]);
+    std::unique_ptr<int32_t[]> pairs(new (std::nothrow) int32_t[size_t(std::max<int64_t>(2 * nnz, 1))]);
+    if (!g.wgt || !pairs) return GMSX_ERR_NOMEM;
+    if (std::fread(g.off.get(), 8, size_t(n + 1), f) != size_t(n + 1)) return GMSX_ERR_FORMAT;
+    if (nnz && std::fread(pairs.get(), 8, size_t(nnz), f) != size_t(nnz)) return GMSX_ERR_FORMAT;
+#pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < nnz; ++j) {
+        g.neigh[j] = pairs[2 * j];
+        g.wgt[j] = pairs[2 * j + 1];
+    }
+    if (int rc = validate_csr_arrays(g.off.get(), g.neigh.get(), n, nnz)) return rc;
+    g.directed = directed != 0;
+    return GMSX_OK;
+}
+
 }  // namespace gmsx
 
 // ================================================================================================
@@ -794,6 +994,8 @@ Option g_options[] = {
     {"BFS_DIRECTION", "", false}, {"BFS_ALPHA", "", false}, {"BFS_BETA", "", false}, {"BFS_BU_PROBE", "", false}, {"BFS_WG_FRONTIER", "", false},
     // batched multi-source breadth-first search (msbfs.hip)
     {"MSBFS_DIRECTION", "", false}, {"MSBFS_ALPHA", "", false}, {"MSBFS_WORDS", "", false},
+    // delta-stepping shortest paths (sssp.hip)
+    {"SSSP_WG_FRONTIER", "", false}, {"SSSP_WIDE", "", false}, {"SSSP_DELTA_AUTO", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;
@@ -955,6 +1157,117 @@ int gmsx_csr_from_arrays(int64_t n, const int64_t *offsets, const int32_t *neigh
     });
 }
 
+// ---- weighted graphs ----------------------------------------------------------------------------------------------------------------------
+const int32_t *gmsx_csr_weights(const gmsx_csr *h) { return h ? h->g.wgt.get() : nullptr; }
+
+int gmsx_csr_generate_weighted(int generator, int scale, int degree, int relabel, int threads, gmsx_csr **out) {
+    return gmsx::guard([&]() -> int {
+        if (!out || scale < 1 || degree < 1 || relabel < 0 || relabel > 2) return GMSX_ERR_INVALID;
+        if (scale > 30) return GMSX_ERR_OVERFLOW;
+        if (generator != GMSX_GEN_KRONECKER && generator != GMSX_GEN_UNIFORM) return GMSX_ERR_INVALID;
+    #ifdef _OPENMP
+        struct Threads {
+            int saved, set;
+            ~Threads() { if (set > 0) omp_set_num_threads(saved); }
+        } threads_guard{omp_get_max_threads(), threads};
+        if (threads > 0) omp_set_num_threads(threads);
+    #else
+        (void)threads;
+    #endif
+        Csr g;
+        {
+            WEdgeList wl;
+            if (int rc = generator == GMSX_GEN_UNIFORM ? make_uniform(scale, degree, wl.el) : make_rmat(scale, degree, wl.el)) return rc;
+            wl.w.reset(new (std::nothrow) int32_t[size_t(std::max<int64_t>(wl.el.m, 1))]);
+            if (!wl.w) return GMSX_ERR_NOMEM;
+            insert_weights(wl.w.get(), wl.el.m);
+            if (int rc = build_from_wel(wl, -1, true, g)) return rc;
+        }
+        return finish(std::move(g), relabel, out);
+    });
+}
+
+int gmsx_csr_from_weighted_edges(int64_t num_nodes, int64_t num_edges, const int32_t *src, const int32_t *dst, const int32_t *w, int symmetrize,
+                                 int relabel, gmsx_csr **out) {
+    return gmsx::guard([&]() -> int {
+        if (!out || num_edges < 0 || (num_edges && (!src || !dst)) || relabel < 0 || relabel > 2) return GMSX_ERR_INVALID;
+        WEdgeList wl;
+        if (int rc = wl.alloc(num_edges)) return rc;
+        if (num_edges) {
+            std::memcpy(wl.el.u.get(), src, size_t(num_edges) * 4);
+            std::memcpy(wl.el.v.get(), dst, size_t(num_edges) * 4);
+            if (w) std::memcpy(wl.w.get(), w, size_t(num_edges) * 4);
+        }
+        if (!w) insert_weights(wl.w.get(), num_edges);
+        Csr g;
+        if (int rc = build_from_wel(wl, num_nodes, symmetrize != 0, g)) return rc;
+        return finish(std::move(g), relabel, out);
+    });
+}
+
+int gmsx_csr_load_weighted(const char *path, int symmetrize, int relabel, gmsx_csr **out) {
+    return gmsx::guard([&]() -> int {
+        if (!path || !out || relabel < 0 || relabel > 2) return GMSX_ERR_INVALID;
+        const std::string p(path), suf = suffix_of(p);
+        Csr g;
+        if (suf == ".wsg") {
+            if (int rc = read_wsg(p, g)) return rc;
+        } else if (suf == ".wel" || suf == ".gr") {
+            WEdgeList wl;
+            if (int rc = suf == ".wel" ? read_wel_weighted(p, wl) : read_gr_weighted(p, wl)) return rc;
+            if (int rc = build_from_wel(wl, -1, symmetrize != 0, g)) return rc;
+        } else if (suf == ".el") {
+            WEdgeList wl;
+            if (int rc = read_el(p, wl.el)) return rc;
+            wl.w.reset(new (std::nothrow) int32_t[size_t(std::max<int64_t>(wl.el.m, 1))]);
+            if (!wl.w) return GMSX_ERR_NOMEM;
+            insert_weights(wl.w.get(), wl.el.m);
+            if (int rc = build_from_wel(wl, -1, symmetrize != 0, g)) return rc;
+        } else if (suf == ".mtx" || suf == ".graph") {
+            return GMSX_ERR_UNSUPPORTED;
+        } else {
+            return GMSX_ERR_FORMAT;
+        }
+        return finish(std::move(g), relabel, out);
+    });
+}
+
+int gmsx_csr_save_wsg(const gmsx_csr *h, const char *path) {
+    return gmsx::guard([&]() -> int {
+        if (!h || !path || !h->g.wgt) return GMSX_ERR_INVALID;
+        const Csr &g = h->g;
+        std::unique_ptr<int32_t[]> pairs(new (std::nothrow) int32_t[size_t(std::max<int64_t>(2 * g.nnz, 1))]);
+        if (!pairs) return GMSX_ERR_NOMEM;
+        for (int64_t j = 0; j < g.nnz; ++j) {
+            pairs[2 * j] = g.neigh[j];
+            pairs[2 * j + 1] = g.wgt[j];
+        }
+        std::FILE *f = std::fopen(path, "wb");
+        if (!f) return GMSX_ERR_IO;
+        const unsigned char directed = g.directed ? 1 : 0;
+        bool ok = std::fwrite(&directed, 1, 1, f) == 1 && std::fwrite(&g.nnz, 8, 1, f) == 1 && std::fwrite(&g.n, 8, 1, f) == 1 &&
+                  std::fwrite(g.off.get(), 8, size_t(g.n + 1), f) == size_t(g.n + 1) &&
+                  (g.nnz == 0 || std::fwrite(pairs.get(), 8, size_t(g.nnz), f) == size_t(g.nnz));
+        ok = (std::fclose(f) == 0) && ok;
+        return ok ? GMSX_OK : GMSX_ERR_IO;
+    });
+}
+
+int gmsx_csr_from_arrays_weighted(int64_t n, const int64_t *offsets, const int32_t *neigh, const int32_t *weights, gmsx_csr **out) {
+    return gmsx::guard([&]() -> int {
+        if (!out || n < 0 || !offsets || (offsets[n] > 0 && !weights)) return GMSX_ERR_INVALID;
+        gmsx_csr *h = nullptr;
+        if (int rc = gmsx_csr_from_arrays(n, offsets, neigh, &h)) return rc;
+        std::unique_ptr<gmsx_csr> owner(h);
+        const int64_t nnz = h->g.nnz;
+        h->g.wgt.reset(new (std::nothrow) int32_t[size_t(std::max<int64_t>(nnz, 1))]);
+        if (!h->g.wgt) return GMSX_ERR_NOMEM;
+        if (nnz) std::memcpy(h->g.wgt.get(), weights, size_t(nnz) * 4);
+        *out = owner.release();
+        return GMSX_OK;
+    });
+}
+
 int gmsx_csr_pick_sources(const gmsx_csr *h, int64_t count, int32_t given, int32_t *out) {
     return gmsx::guard([&]() -> int {
         if (!h || count < 0 || (count > 0 && !out) || given < -1) return GMSX_ERR_INVALID;
@@ -1032,6 +1345,10 @@ uint64_t gmsx_csr_fingerprint(const gmsx_csr *h, int which) {
     if (which == 0) {
         p = reinterpret_cast<const unsigned char *>(h->g.off.get());
         len = size_t(h->g.n + 1) * 8;
+    } else if (which == 2) {
+        if (!h->g.wgt) return 0;
+        p = reinterpret_cast<const unsigned char *>(h->g.wgt.get());
+        len = size_t(h->g.nnz) * 4;
     } else {
         p = reinterpret_cast<const unsigned char *>(h->g.neigh.get());
         len = size_t(h->g.nnz) * 4;

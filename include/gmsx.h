@@ -109,9 +109,34 @@ const int64_t *gmsx_csr_offsets(const gmsx_csr *g);     /* n+1 entries; valid un
 const int32_t *gmsx_csr_neighbors(const gmsx_csr *g);   /* nnz entries */
 /* Σ_{(u,v)∈E,u<v}(d_u+d_v): element count behind the algorithmic-bytes figure. */
 uint64_t gmsx_csr_merge_elements(const gmsx_csr *g);
-/* FNV-1a-64 of the offsets / neighbour arrays (loader fingerprints). */
-uint64_t gmsx_csr_fingerprint(const gmsx_csr *g, int which /*0 offsets, 1 neighbours*/);
+/* FNV-1a-64 of the offsets / neighbour arrays (loader fingerprints); 2 = the weight array, 0 for an unweighted CSR. */
+uint64_t gmsx_csr_fingerprint(const gmsx_csr *g, int which /*0 offsets, 1 neighbours, 2 weights*/);
 void gmsx_csr_free(gmsx_csr *g);
+
+/* ---- EDGE WEIGHTS: a gmsx_csr may own int32 weights[nnz], parallel to its neighbour array (the reference's WGraph = CSRGraph<NodeId,
+ * NodeWeight<NodeId, int32>>, gapbs/benchmark.h).  Host only.  Every call above behaves on a weighted CSR exactly as on its structure
+ * (gmsx_csr_save_sg / _sgx write the structure only); gmsx_csr_relabel_by_degree carries a weight with its arc (rows re-sorted by id, each
+ * weight staying with its id) — where the reference's RelabelByDegree would reset every weight to 1.
+ * gmsx_csr_weights: the array (valid until gmsx_csr_free), or NULL for an unweighted CSR.
+ * gmsx_csr_generate_weighted: WeightedBuilder::MakeGraph for "-g/-u SCALE -k DEGREE -s" (builder.h:1642-1660): the edge list of
+ * gmsx_csr_generate, weights by Generator::InsertWeights (generator.h:131-146) over that list BEFORE symmetrisation — one mt19937 per block of
+ * 2^18 edges seeded kRandSeed + block, uniform_int_distribution<int>(1, 255) —, both directions of an edge carry its weight (builder.h:104), a
+ * row is sorted by (id, weight) and made unique by id (graph.h:39-46), so a repeated edge keeps its SMALLEST weight; self loops are dropped.  The
+ * result is symmetric in structure and in weights, bit-identical to the reference's and independent of the thread count.
+ * gmsx_csr_from_weighted_edges: the same builder on a caller's list; w == NULL = InsertWeights over that list (the reference on a weightless .el).
+ * gmsx_csr_load_weighted: ".wel", ".gr" and ".wsg" (reader.h:252-305: the neighbour array as {int32 id, int32 weight} pairs) keep their
+ * weights (a text weight outside int32 → GMSX_ERR_OVERFLOW; weights below 1 are loaded as they are: gmsx_graph_set_weights refuses them);
+ * ".el" gets InsertWeights in file order; ".sg" / ".sgx" → GMSX_ERR_FORMAT (the reference exits with -5); ".mtx" and ".graph" →
+ * GMSX_ERR_UNSUPPORTED from this entry point (their readers drop the weight column).
+ * gmsx_csr_save_wsg: Writer::WriteSerializedGraph of a weighted graph (writer.h:39-69); an unweighted CSR → GMSX_ERR_INVALID.
+ * gmsx_csr_from_arrays_weighted: gmsx_csr_from_arrays plus a copy of weights[nnz]. */
+const int32_t *gmsx_csr_weights(const gmsx_csr *g);
+int gmsx_csr_generate_weighted(int generator, int scale, int degree, int relabel, int threads, gmsx_csr **out);
+int gmsx_csr_from_weighted_edges(int64_t num_nodes, int64_t num_edges, const int32_t *src, const int32_t *dst, const int32_t *w /* or NULL */,
+                                 int symmetrize, int relabel, gmsx_csr **out);
+int gmsx_csr_load_weighted(const char *path, int symmetrize, int relabel, gmsx_csr **out);
+int gmsx_csr_save_wsg(const gmsx_csr *g, const char *path);
+int gmsx_csr_from_arrays_weighted(int64_t n, const int64_t *offsets, const int32_t *neigh, const int32_t *weights, gmsx_csr **out);
 
 /* Threads of the host substrate (generator, builder, relabelling: OpenMP, like the reference's loader).  n <= 0 restores
  * the runtime default.  Returns the previous maximum.  Launchers that export OMP_NUM_THREADS=1 to their workers
@@ -183,7 +208,12 @@ int gmsx_set_host_threads(int n);
  *                   pulled), MSBFS_ALPHA (default 15 — a first guess, not a tuned value), MSBFS_WORDS (W = 1 or 2: 64-bit words
  *                   per vertex, so a pass advances 64 W sources; 0, the default = 1 for a list of at most 64 sources and 2 for a longer one, as
  *                   measured: DESIGN.md §5.4j) — none changes any output of gmsx_bfs_multi but passes, push_levels and
- *                   pull_levels; test hooks.  Under TIMING every level prints its direction and the two operands of the rule */
+ *                   pull_levels; test hooks.  Under TIMING every level prints its direction and the two operands of the rule
+ *   shortest paths         SSSP_WG_FRONTIER (as CORE_WG_FRONTIER for the relaxation rounds of gmsx_sssp, default 512; 0 = every round is a kernel
+ *                   boundary), SSSP_WIDE (1 = 64-bit distance words whatever the weights), SSSP_DELTA_AUTO (the parameter c of the default
+ *                   bucket width, delta = max(1, c * mean weight / mean degree); default 16 — measured once, DESIGN.md §5.4l, and still a first guess) — test hooks;
+ *                   none changes dist, parent or any info field except delta (SSSP_DELTA_AUTO, with delta = 0), buckets (a fact about
+ *                   delta), rounds and relaxations */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -837,6 +867,48 @@ int gmsx_pagerank(const gmsx_graph *g, double damping, int32_t max_iters, double
                   double *scores /* n, host, or NULL */, gmsx_pagerank_info *info /* required */, gmsx_stats *stats);
 int gmsx_pagerank_residual(const gmsx_graph *g, const double *scores /* n, host */, double damping,
                            const double *teleport, uint32_t flags, double *residual, gmsx_stats *stats);
+
+/* ---- edge weights on the device and single-source shortest paths (gms/representations/graphs/log_graph/sssp.cc: DeltaStep, SSSPVerifier;
+ * sssp.hip).
+ * gmsx_graph_set_weights attaches weights[nnz] (host, parallel to the uploaded neighbour array) to a handle; NULL detaches.  Attachment is
+ * explicit: gmsx_graph_upload_csr of a weighted CSR uploads the structure only.  The array is validated on the device: a weight below 1 →
+ * GMSX_ERR_INVALID (never skipped; positive weights are what makes parent a tree and the verifier exact); weight(u→v) != weight(v→u) — the twin
+ * found by a bounded binary search in v's row — → GMSX_ERR_NOT_CANONICAL, a check a handle uploaded with GMSX_UPLOAD_TRUSTED skips.  A failed
+ * attach leaves the handle as it was; a second attach replaces the first.  The weights count in gmsx_graph_device_bytes and are released by
+ * gmsx_graph_free.  No other entry point reads them.  gmsx_graph_has_weights: 1 / 0.
+ * gmsx_sssp: dist[v] = the weight of a lightest path from source (dist[source] = 0; -1: unreachable); parent[v] = the SMALLEST-id neighbour u
+ * with dist[u] + w(u,v) == dist[v], parent[source] = source, -1 for an unreachable vertex.  Weights are at least 1, so dist strictly falls along
+ * parents: parent is a tree.  With all weights 1, dist and parent equal gmsx_bfs's depth and parent element for element.  The distances are
+ * found by delta-stepping (bucket i = tentative distances in [i delta, (i + 1) delta); delta > 0: as given, 0: max(1, SSSP_DELTA_AUTO * mean
+ * weight / mean degree)); parent by a PULL pass behind it — every reached vertex takes the first tight entry of its ascending row, one writer per
+ * vertex, no atomics — which also checks the relaxation: a reached vertex without a tight entry → GMSX_ERR_KERNEL.  dist, parent and every info
+ * field except rounds and relaxations are facts about (graph, weights, source) — buckets and delta about delta as well — byte-identical in
+ * every run and process, under every delta, every SSSP_* option, GMSX_UPLOAD_TRUSTED, GMSX_UPLOAD_HUB_LIMIT and a sharded upload.  Distances
+ * are held in 32-bit words when (n - 1) * wmax < 2^31 - 1, else in 64-bit words (info->wide).
+ * No weights attached, source outside [0, n), NULL g or info, delta < 0: GMSX_ERR_INVALID, nothing written.  An append past its bound, more
+ * than n + 1 rounds in one bucket (a bucket is done after at most n Bellman–Ford rounds) or more buckets than min(n, (n - 1) wmax / delta + 2):
+ * GMSX_ERR_KERNEL.  The caller's arrays are written only after the flag words were read as zero.  Single GPU, no shards.  gmsx_stats:
+ * kernel_ms, setup_ms, launches, units = reached_arcs, probes = buckets.
+ * gmsx_sssp_verify is the same pull pass over a caller's array (an entry below 0 = unreached): violated_arcs = arcs u→v, both ends reached,
+ * with dist[v] > dist[u] + w; untight = reached vertices other than the source without a tight arc; wrong_unreached = unreached vertices with
+ * a reached neighbour; source_ok = 1 iff dist[source] == 0.  SSSPVerifier(g, source, dist) (sssp.cc:145-175) <=> all three counts are 0 and
+ * source_ok is 1.  NULL g, dist (n > 0) or out, no weights, a bad source: GMSX_ERR_INVALID. */
+int gmsx_graph_set_weights(gmsx_graph *g, const int32_t *weights /* nnz, host, parallel to the uploaded neigh; NULL detaches */);
+int gmsx_graph_has_weights(const gmsx_graph *g);
+typedef struct {
+    int64_t reached, reached_arcs;   /* as gmsx_bfs_info */
+    int64_t dist_sum, max_dist;      /* over the reached vertices */
+    int64_t delta;                   /* the bucket width used */
+    int64_t buckets;                 /* non-empty buckets = distinct dist[v] / delta over the reached vertices: a fact about (graph, weights, source, delta) */
+    int64_t rounds, relaxations;     /* diagnostics: may differ between runs and under SSSP_* options */
+    int32_t far_vertex;              /* smallest id at max_dist; the source if nothing else is reached */
+    int32_t wide;                    /* 1 = 64-bit distance words were used */
+} gmsx_sssp_info;
+int gmsx_sssp(const gmsx_graph *g, int32_t source, int64_t delta /* > 0: as given; 0: the library's choice */,
+              int64_t *dist /* n, host, or NULL; -1 = unreachable */, int32_t *parent /* n, host, or NULL */,
+              gmsx_sssp_info *info /* required */, gmsx_stats *stats);
+typedef struct { int64_t violated_arcs, untight, wrong_unreached; int32_t source_ok, reserved; } gmsx_sssp_check;
+int gmsx_sssp_verify(const gmsx_graph *g, int32_t source, const int64_t *dist /* n, host */, gmsx_sssp_check *out, gmsx_stats *stats);
 
 /* ---- 4-cycle counting and the 3- / 4-vertex motif census.  No reference counterpart (like the k-truss: a member of the family the suite
  * describes and does not build).  All results are exact integers.

@@ -41,6 +41,9 @@
 //   gmsx::closeness(g, sources, out_scores, harmonic = false) -> gmsx_bfs_multi (closeness or harmonic centrality of the listed sources; returns the largest)
 //   gmsx::pagerank(g, scores, damping, max_iters, tolerance, …) -> gmsx_pagerank  (log_graph/pr.cc:34-61, PageRankPull; in double unless GMSX_PR_FLOAT32)
 //   gmsx::pagerank_residual(g, scores, …) -> gmsx_pagerank_residual  (pr.cc:79-97, PRVerifier as a number);  gmsx::top_scores(scores, k): PrintTopScores' top k on the host
+//   gmsx::set_weights(g, weights)        -> gmsx_graph_set_weights  (int32 weights parallel to g.neighbors(); what makes the graph a WGraph)
+//   gmsx::sssp(g, source, dist, delta, …) -> gmsx_sssp               (log_graph/sssp.cc:54-134, DeltaStep; dist in 64 bits, -1 = unreachable)
+//   gmsx::sssp_verify(g, source, dist)   -> gmsx_sssp_verify        (sssp.cc:145-175, SSSPVerifier)
 //   gmsx::pick_sources(csr, count)       -> gmsx_csr_pick_sources   (gapbs/benchmark.h:51-75, SourcePicker)
 //   gmsx::cycle4_count(g) / cycle4_count(g, at_vertex) -> gmsx_cycle4_count (the 4-cycles, and those through every vertex; no reference driver)
 //   gmsx::motif_census4(g)               -> gmsx_motif_census4     (the eight 3- and 4-vertex motifs, non-induced and induced; no reference driver)
@@ -764,6 +767,38 @@ inline double pagerank_residual(const HipGraphT<S> &g, const std::vector<double>
                                          teleport && !teleport->empty() ? teleport->data() : nullptr, flags, &r, nullptr),
                   "gmsx_pagerank_residual");
     return r;
+}
+// Edge weights for gmsx::sssp: weights[j] belongs to g.neighbors()[j] (every weight >= 1, w(u,v) == w(v,u)); an empty vector detaches.  The
+// weights live with the device copy of g: a graph that is uploaded again needs them attached again.
+template <class S>
+inline void set_weights(const HipGraphT<S> &g, const std::vector<int32_t> &weights) {
+    const int64_t nnz = g.num_nodes() > 0 ? g.offsets()[g.num_nodes()] : 0;
+    if (!weights.empty() && int64_t(weights.size()) != nnz) detail::check(GMSX_ERR_INVALID, "gmsx_graph_set_weights");
+    detail::check(gmsx_graph_set_weights(const_cast<gmsx_graph *>(g.device()), weights.empty() ? nullptr : weights.data()), "gmsx_graph_set_weights");
+}
+// DeltaStep(g, source, delta) (log_graph/sssp.cc:54-134), shaped like its pvector<WeightT> dist but in 64 bits and with -1 (not kDistInf) for an
+// unreachable vertex; delta = 0: the library's choice.  parent (optional): the smallest-id neighbour on a lightest path.  Returns the number of
+// reached vertices — what PrintSSSPStats prints.
+template <class S>
+inline int64_t sssp(const HipGraphT<S> &g, int32_t source, std::vector<int64_t> &dist, int64_t delta = 0, std::vector<int32_t> *parent = nullptr,
+                    gmsx_sssp_info *info = nullptr) {
+    dist.resize(size_t(g.num_nodes()));
+    if (parent) parent->resize(size_t(g.num_nodes()));
+    gmsx_sssp_info si{};
+    detail::check(gmsx_sssp(g.device(), source, delta, dist.empty() ? nullptr : dist.data(), parent && !parent->empty() ? parent->data() : nullptr, &si, nullptr),
+                  "gmsx_sssp");
+    if (info) *info = si;
+    return si.reached;
+}
+// SSSPVerifier(g, source, dist) (sssp.cc:145-175): true iff no arc is violated, every reached vertex but the source has a tight arc, no
+// unreached vertex has a reached neighbour and dist[source] == 0
+template <class S>
+inline bool sssp_verify(const HipGraphT<S> &g, int32_t source, const std::vector<int64_t> &dist, gmsx_sssp_check *out = nullptr) {
+    if (dist.size() != size_t(g.num_nodes())) detail::check(GMSX_ERR_INVALID, "gmsx_sssp_verify");
+    gmsx_sssp_check c{};
+    detail::check(gmsx_sssp_verify(g.device(), source, dist.empty() ? nullptr : dist.data(), &c, nullptr), "gmsx_sssp_verify");
+    if (out) *out = c;
+    return c.violated_arcs == 0 && c.untight == 0 && c.wrong_unreached == 0 && c.source_ok == 1;
 }
 // PrintTopScores' top k (pr.cc:64-74, gapbs/util.h TopK) on the host: the k largest scores as (id, score), largest first, ties by the smaller id
 inline std::vector<std::pair<int32_t, double>> top_scores(const std::vector<double> &scores, size_t k) {
