@@ -259,19 +259,17 @@ int gmsx_coloring_jp(const gmsx_graph *g, const int32_t *ordering, int rank_form
         }
         const int cus = c.compute_units > 0 ? c.compute_units : 256;
         const unsigned tb = unsigned((n + 255) / 256);
-        const int64_t long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
-        // every long row is parked once in the whole run and takes pred/32 + 1 <= degree/32 + 1 words
-        const unsigned long long slab_cap = (unsigned long long)(g->nnz / 32 + long_cap);
-        DevBuf d_in, d_rank, d_seen, d_cnt, d_pred, d_color, d_round, d_f0, d_f1, d_long, d_long_slab, d_slab, d_ctl, d_ctrl;
+        DevBuf d_in, d_rank, d_seen, d_cnt, d_pred, d_color, d_round, d_slab, d_ctl, d_ctrl;
+        FrontierStore store;  // (a parked row's note: where its bitmap starts in the slab)
         if (int rc = dalloc<int32_t>(d_in, n)) return rc;
         if (int rc = dalloc<int32_t>(d_cnt, n)) return rc;
         if (int rc = dalloc<int32_t>(d_pred, n)) return rc;
         if (int rc = dalloc<int32_t>(d_color, n)) return rc;
         if (int rc = dalloc<int32_t>(d_round, n)) return rc;
-        if (int rc = dalloc<int32_t>(d_f0, n)) return rc;
-        if (int rc = dalloc<int32_t>(d_f1, n)) return rc;
-        if (int rc = dalloc<int32_t>(d_long, long_cap)) return rc;
-        if (int rc = dalloc<unsigned long long>(d_long_slab, long_cap)) return rc;
+        if (int rc = store.alloc(n, g->nnz, true)) return rc;
+        const int64_t long_cap = store.long_cap;
+        // every long row is parked once in the whole run and takes pred/32 + 1 <= degree/32 + 1 words
+        const unsigned long long slab_cap = (unsigned long long)(g->nnz / 32 + long_cap);
         if (int rc = dalloc<uint32_t>(d_slab, int64_t(slab_cap))) return rc;
         if (int rc = dalloc<int32_t>(d_ctl, 4)) return rc;
         if (int rc = dalloc<ColorCtrl>(d_ctrl, 1)) return rc;
@@ -284,10 +282,9 @@ int gmsx_coloring_jp(const gmsx_graph *g, const int32_t *ordering, int rank_form
         int32_t *rank = own_rank ? d_rank.as<int32_t>() : d_in.as<int32_t>();
         int32_t *cnt = d_cnt.as<int32_t>(), *pred = d_pred.as<int32_t>(), *color = d_color.as<int32_t>(), *rnd = d_round.as<int32_t>();
         uint32_t *slab = d_slab.as<uint32_t>();
-        const FrontierBufs bufs{{d_f0.as<int32_t>(), d_f1.as<int32_t>()}, d_long.as<int32_t>(), d_long_slab.as<unsigned long long>(), long_cap};
+        const FrontierBufs bufs = store.bufs();
         const ColorJp jp{n, g->off, g->adj, pred, color, rnd, cnt, slab, slab_cap, &ctrl->slab_used, &ctrl->colors, 0};
-        long long wg_frontier = opt_int("COLOR_WG_FRONTIER", kWgFrontierDefault);  // test hook: 0 = every round a kernel boundary
-        wg_frontier = std::max<long long>(0, std::min<long long>(wg_frontier, INT_MAX));
+        const long long wg_frontier = frontier_wg_option("COLOR_WG_FRONTIER", kWgFrontierDefault);
 
         GMSX_HIP(hipMemsetAsync(d_ctl.p, 0, 4 * sizeof(int32_t), s));
         GMSX_HIP(hipMemsetAsync(ctrl, 0, sizeof(ColorCtrl), s));
@@ -311,9 +308,8 @@ int gmsx_coloring_jp(const gmsx_graph *g, const int32_t *ordering, int rank_form
         const unsigned lb = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
         const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
         const unsigned long_grid = unsigned(cus) * 4;
-        hipLaunchKernelGGL(k_oq_later, dim3(lb), dim3(256), 0, s, n, g->off, g->adj, rank, cnt, d_long.as<int32_t>(), long_cap, d_ctl.as<int32_t>());
-        hipLaunchKernelGGL(k_oq_later_long, dim3(long_grid), dim3(256), 0, s, g->off, g->adj, rank, cnt, d_long.as<int32_t>(), long_cap,
-                           d_ctl.as<int32_t>());
+        hipLaunchKernelGGL(k_oq_later, dim3(lb), dim3(256), 0, s, n, g->off, g->adj, rank, cnt, bufs.longs, long_cap, d_ctl.as<int32_t>());
+        hipLaunchKernelGGL(k_oq_later_long, dim3(long_grid), dim3(256), 0, s, g->off, g->adj, rank, cnt, bufs.longs, long_cap, d_ctl.as<int32_t>());
         hipLaunchKernelGGL(k_color_select, dim3(sweep), dim3(256), 0, s, n, cnt, pred, ctrl, bufs.f[0]);
         launches += 4;
         ColorCtrl h;
@@ -367,7 +363,7 @@ int gmsx_coloring_verify(const gmsx_graph *g, const int32_t *coloring, gmsx_colo
             return GMSX_OK;
         }
         const int cus = c.compute_units > 0 ? c.compute_units : 256;
-        const int64_t long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
+        const int64_t long_cap = frontier_long_cap(n, g->nnz);
         const int64_t words = n / 32 + 1;  // colours 0..n
         DevBuf d_color, d_present, d_long, d_ctl, d_acc;
         if (int rc = dalloc<int32_t>(d_color, n)) return rc;

@@ -151,21 +151,18 @@ int core_peel(const gmsx_graph *g, DevBuf &d_core, DevBuf &d_round, gmsx_core_in
     Ctx &c = ctx();
     hipStream_t s = c.stream;
     const int64_t n = g->n;
-    const int64_t long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
-    DevBuf d_deg, d_f0, d_f1, d_long, d_ctrl;
+    DevBuf d_deg, d_ctrl;
+    FrontierStore store;
     if (int rc = dalloc<int32_t>(d_deg, n)) return rc;
     if (int rc = dalloc<int32_t>(d_core, n)) return rc;
     if (int rc = dalloc<int32_t>(d_round, n)) return rc;
-    if (int rc = dalloc<int32_t>(d_f0, n)) return rc;
-    if (int rc = dalloc<int32_t>(d_f1, n)) return rc;
-    if (int rc = dalloc<int32_t>(d_long, long_cap)) return rc;
+    if (int rc = store.alloc(n, g->nnz, false)) return rc;
     if (int rc = dalloc<CoreCtrl>(d_ctrl, 1)) return rc;
     CoreCtrl *ctrl = d_ctrl.as<CoreCtrl>();
     int32_t *deg = d_deg.as<int32_t>();
-    const FrontierBufs bufs{{d_f0.as<int32_t>(), d_f1.as<int32_t>()}, d_long.as<int32_t>(), nullptr, long_cap};
+    const FrontierBufs bufs = store.bufs();
     CorePeel peel{n, g->off, g->adj, deg, d_round.as<int32_t>(), d_core.as<int32_t>(), 0};
-    long long wg_frontier = opt_int("CORE_WG_FRONTIER", kWgFrontierDefault);  // test hook: 0 = every round a kernel boundary, large = every round the tail may take
-    wg_frontier = std::max<long long>(0, std::min<long long>(wg_frontier, INT_MAX));
+    const long long wg_frontier = frontier_wg_option("CORE_WG_FRONTIER", kWgFrontierDefault);
 
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
     const unsigned tb = unsigned((n + 255) / 256);
@@ -337,7 +334,7 @@ int gmsx_order_quality(const gmsx_graph *g, const int32_t *ordering, int rank_fo
         }
         const int cus = c.compute_units > 0 ? c.compute_units : 256;
         const unsigned tb = unsigned((n + 255) / 256);
-        const int64_t long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
+        const int64_t long_cap = frontier_long_cap(n, g->nnz);
         DevBuf d_in, d_rank, d_seen, d_later, d_long, d_ctl, d_acc;
         if (int rc = dalloc<int32_t>(d_in, n)) return rc;
         if (int rc = dalloc<int32_t>(d_seen, n)) return rc;

@@ -1,7 +1,10 @@
-// The frontier-rounds engine: level-synchronous rounds over a frontier of vertices, written once for the k-core peel (core.hip) and
-// Jones–Plassmann colouring (coloring.hip).  A round walks the row of every frontier vertex; what a row entry means is the POLICY's business
-// (the peel pushes a decrement, colouring marks a bitmap, releases successors and picks a colour), and whatever the walk appends to the next
-// frontier is the next round's work.  The rule both share:
+// The frontier-rounds engine: level-synchronous rounds over a frontier of vertices, written once for the k-core peel (core.hip), Jones–Plassmann
+// colouring (coloring.hip), the truss peel (truss.hip: its items are edges), top-down BFS (traversal.hip) and delta-stepping shortest paths
+// (sssp.hip).  A round walks the row of every frontier vertex; what a row entry means is the POLICY's business (the peel pushes a decrement,
+// colouring marks a bitmap, releases successors and picks a colour, BFS claims, SSSP relaxes), and whatever the walk appends to the next
+// frontier is the next round's work.  The kernels, the host's round loop (run_frontier_rounds: nothing else launches a k_frontier_* kernel), the
+// owner of the buffers (FrontierStore) and the two device pieces the users share around the rounds (k_frontier_collect, RowGroup) are here and
+// nowhere else.  The rule all share:
 //   binning     a kGroup-lane group per frontier vertex up to kLongRow entries; longer rows are PARKED with a bounds-checked append and walked
 //               by all workgroups together (all threads of the workgroup in the tail) — no lane walks a long row alone
 //   boundary    a round boundary is a kernel boundary (k_frontier_round + k_frontier_round_long + k_frontier_advance, then the host reads the
@@ -19,9 +22,10 @@
 //   park(x, round, notes, pos, error)         lane 0, when x was parked at `pos`
 //   long_walk(x, note, tid, threads, q)       the part of the parked row x that thread tid of `threads` walks
 //   settle(x, note, round, tid, error)        kNotes only: every thread of ONE workgroup of kTailThreads, behind the walks (may hold barriers)
-//   finish()                                  every thread, at the end of a kernel
+//   finish()                                  every thread, converged, at the end of each of the four kernels (k_frontier_advance: kNotes only)
 //   kStops, round_stop()                      optional: ONE thread at every round boundary, behind all appends of the round; true ends the step
 //                                             there (the tail returns, and the policy tells the host through its own control block)
+//   kReenters                                 optional: a vertex may enter more than one frontier, so the host does not read ctrl->done
 #pragma once
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
@@ -39,6 +43,11 @@ template <class P, class = void>
 struct policy_stops : std::false_type {};
 template <class P>
 struct policy_stops<P, std::void_t<decltype(P::kStops)>> : std::true_type {};
+// may a vertex enter more than one frontier under policy P (P::kReenters)?
+template <class P, class = void>
+struct policy_reenters : std::false_type {};
+template <class P>
+struct policy_reenters<P, std::void_t<decltype(P::kReenters)>> : std::true_type {};
 
 // UNMEASURED: none of these bounds is tuned yet (tools/core_probe.py and tools/coloring_probe.py are the measurement).  They
 // follow the round table of the peel on R-MAT graphs (almost every round holds fewer than 256 vertices) and the row shapes named there.
@@ -55,7 +64,7 @@ struct FrontierCtrl {
     int32_t count;  // vertices in the current frontier
     int32_t next;   // appended to the next one so far
     int32_t round;  // index of the round the current frontier is worked in
-    int32_t done;   // vertices of finished rounds
+    int32_t done;   // vertices of finished rounds (kReenters: frontier entries, may pass n and wrap; the host does not read it)
     int32_t error;  // an append (or a policy) hit its bound
     int32_t nlong;  // long rows parked by k_frontier_round
     int32_t bail;   // the tail met a round too heavy for one workgroup: it belongs to the grid-wide kernels
@@ -69,6 +78,28 @@ struct FrontierBufs {
     unsigned long long *notes;
     int64_t long_cap;
 };
+
+// how many rows above kLongRow `items` rows of `entries` entries in all can hold (also for the passes that only bin rows and run no rounds)
+inline int64_t frontier_long_cap(int64_t items, int64_t entries) { return std::min<int64_t>(items, entries / kLongRow + 1); }
+
+// … and their owner
+struct FrontierStore {
+    DevBuf f0, f1, longs, notes;
+    int64_t long_cap = 0;
+    int alloc(int64_t items, int64_t entries, bool with_notes) {
+        long_cap = frontier_long_cap(items, entries);
+        if (int rc = dalloc<int32_t>(f0, items)) return rc;
+        if (int rc = dalloc<int32_t>(f1, items)) return rc;
+        if (int rc = dalloc<int32_t>(longs, long_cap)) return rc;
+        return with_notes ? dalloc<unsigned long long>(notes, long_cap) : GMSX_OK;
+    }
+    FrontierBufs bufs() const { return {{f0.as<int32_t>(), f1.as<int32_t>()}, longs.as<int32_t>(), notes.as<unsigned long long>(), long_cap}; }
+};
+
+// an algorithm's …_WG_FRONTIER option: 0 = every round a kernel boundary, large = every round the tail may take
+inline long long frontier_wg_option(const char *name, long long dflt) {
+    return std::max<long long>(0, std::min<long long>(opt_int(name, dflt), INT_MAX));
+}
 
 __device__ __forceinline__ int32_t load_now(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ uint32_t load_now(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -99,6 +130,33 @@ __device__ __forceinline__ void wave_append(bool take, int32_t v, int32_t *buf, 
         else *error = 1;
     }
 }
+
+// every v < n that `pred` (passed by value) holds of into a frontier list of n entries
+template <class Pred>
+__global__ __launch_bounds__(256) void k_frontier_collect(int64_t n, Pred pred, int32_t *__restrict__ list, int32_t *__restrict__ count,
+                                                          int32_t *__restrict__ error) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    const int64_t end = ((n + 63) / 64) * 64;  // whole waves stay converged for the ballot
+    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride)
+        wave_append(v < n && pred(v), int32_t(v), list, count, n, error);
+}
+template <class Pred>
+void frontier_collect(int64_t n, Pred pred, int32_t *list, int32_t *count, int32_t *error) {
+    const int cus = ctx().compute_units > 0 ? ctx().compute_units : 256;
+    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    hipLaunchKernelGGL(k_frontier_collect<Pred>, dim3(sweep), dim3(256), 0, ctx().stream, n, pred, list, count, error);
+}
+
+// a group of WIDTH lanes (a power of two) that scans a row chunk by chunk, a ballot per chunk
+template <int WIDTH>
+struct RowGroup {
+    static constexpr unsigned long long mask = WIDTH == 64 ? ~0ull : ((1ull << (WIDTH & 63)) - 1ull);
+    const int lane, shift;  // shift: where the group's lanes sit in the wave's ballot
+    __device__ __forceinline__ RowGroup() : lane(threadIdx.x & (WIDTH - 1)), shift((threadIdx.x & 63) & ~(WIDTH - 1)) {}
+    __device__ __forceinline__ unsigned long long ballot(bool b) const { return (__ballot(b) >> shift) & mask; }
+    // the lowest lane of `hits`: in an ascending row it holds the smallest id
+    __device__ static __forceinline__ int first(unsigned long long hits) { return __ffsll((long long)hits) - 1; }
+};
 
 // the next frontier as a policy sees it
 struct NextQueue {
@@ -148,6 +206,9 @@ __global__ __launch_bounds__(256) void k_frontier_round_long(P p, int32_t *__res
     const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, threads = int64_t(gridDim.x) * blockDim.x;
     const NextQueue q{next, &ctrl->next, p.n, &ctrl->error};
     for (int64_t i = 0; i < nlong; ++i) p.long_walk(longs[i], P::kNotes ? notes[i] : 0ull, tid, threads, q);
+    // SsspRelax flushes its walks' counts here.  ColorJp::finish() publishes `top`, which only give() raises and long_walk never calls: it stays
+    // the 0 the host passed, and the hook costs that policy one compare.
+    p.finish();
 }
 
 // … and the round boundary: the parked rows are settled (kNotes: ONE workgroup of kTailThreads — their walks are complete only behind the
@@ -291,6 +352,7 @@ int run_frontier_rounds(const P &p, const FrontierBufs &b, Ctrl *ctrl, Ctrl &h, 
     hipStream_t s = c.stream;
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
     const int64_t n = p.n;
+    constexpr bool once = !policy_reenters<P>::value;  // every vertex enters one frontier: `done` bounds the frontier and grows with every step
     while (h.count > 0 && !stop(h)) {
         if (h.count <= wg_frontier && !h.bail) {
             hipLaunchKernelGGL(k_frontier_tail<P>, dim3(1), dim3(kTailThreads), 0, s, p, b.f[0], b.f[1], int32_t(wg_frontier), ctrl);
@@ -309,8 +371,8 @@ int run_frontier_rounds(const P &p, const FrontierBufs &b, Ctrl *ctrl, Ctrl &h, 
         const int32_t done_was = h.done, round_was = h.round;
         GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
-        if (h.error || h.count < 0 || h.done > n || h.count > n - h.done) return GMSX_ERR_KERNEL;
-        if (!h.bail && (h.done <= done_was || h.round <= round_was)) return GMSX_ERR_KERNEL;  // a step that made no progress
+        if (h.error || h.count < 0 || (once ? h.done > n || h.count > n - h.done : h.count > n)) return GMSX_ERR_KERNEL;
+        if (!h.bail && ((once && h.done <= done_was) || h.round <= round_was)) return GMSX_ERR_KERNEL;  // a step that made no progress
     }
     return GMSX_OK;
 }

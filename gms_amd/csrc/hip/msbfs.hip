@@ -221,8 +221,8 @@ __global__ __launch_bounds__(256) void k_ms_pull(MsArgs<W> a, int32_t *__restric
 template <int W, int WIDTH>
 __global__ __launch_bounds__(256) void k_ms_pull_rows(MsArgs<W> a, const int32_t *__restrict__ rows) {
     constexpr int kPerWave = 64 / WIDTH;
-    const int wl = threadIdx.x & 63, lane = wl & (WIDTH - 1);
-    const int shift = wl & ~(WIDTH - 1);  // where the group's lanes sit in the wave's ballot
+    const RowGroup<WIDTH> grp;
+    const int wl = threadIdx.x & 63, lane = grp.lane;
     const int64_t wave0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6, waves = (int64_t(gridDim.x) * blockDim.x) >> 6;
     const int64_t count = min(int64_t(a.ctrl->rows), a.n);
     MsRegs<W> r;
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void k_ms_pull_rows(MsArgs<W> a, const int32_t
                         for (int o = WIDTH / 2; o > 0; o >>= 1) acc[k] |= __shfl_xor(acc[k], o, WIDTH);
                         rest |= need[k] & ~acc[k];
                     }
-                    if ((__ballot(rest == 0) >> shift) & 1ull) break;
+                    if (grp.ballot(rest == 0) & 1ull) break;
                 }
                 if (lane == 0) {
                     deg = j1 - j0;
@@ -572,7 +572,7 @@ int gmsx_bfs_multi(const gmsx_graph *g, int64_t n_sources, const int32_t *source
         const int64_t W = o.words;
         MsBufs b;
         GMSX_HIP(hipEventRecord(c.ev[0], s));
-        b.long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
+        b.long_cap = frontier_long_cap(n, g->nnz);
         b.tcap = n * W;
         if (int rc = dalloc<u64>(b.words, 3 * n * W)) return rc;
         if (int rc = dalloc<int64_t>(b.dist_sum, n)) return rc;

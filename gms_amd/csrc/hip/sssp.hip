@@ -12,8 +12,8 @@
 //
 // A ROUND of a bucket relaxes every arc of every frontier vertex and is a policy (SsspRelax) of the frontier-rounds engine's kernels
 // (frontier_rounds.hpp: a 16-lane group per short row, rows above kLongRow parked and walked by all workgroups, the one-workgroup tail under
-// SSSP_WG_FRONTIER with its hand-back).  The engine's HOST loop insists that a vertex enters a frontier once; shortest paths re-enter vertices, so
-// the host loop is this file's own (sssp_rounds) and the engine is not changed.  A walker of frontier vertex x reads dist[x] with load_now,
+// SSSP_WG_FRONTIER with its hand-back) and of its host loop.  Shortest paths re-enter vertices, so the policy declares kReenters: the loop then
+// leaves the once-per-vertex checks on `done` out and keeps the others.  A walker of frontier vertex x reads dist[x] with load_now,
 // reads dist[w] with a plain load and issues the integer atomicMin only when dist[x] + w(x,w) would improve it.  The walker whose atomicMin
 // improved w appends w to the next round's frontier iff the new distance lies in the current bucket and it is the first to set w's stamp to
 // this round's number (atomicExch): a vertex enters a round's frontier at most once, so a frontier never exceeds n.  The appends of a wave go
@@ -63,6 +63,7 @@ template <class D>
 struct SsspRelax {
     static constexpr int kGroupWords = 0;
     static constexpr bool kNotes = true;
+    static constexpr bool kReenters = true;
     int64_t n;
     const int64_t *off;
     const int32_t *adj, *wgt;
@@ -93,20 +94,12 @@ struct SsspRelax {
         for (int64_t j = off[x] + tid; j < j1; j += threads) relax(adj[j], dx + wgt[j], mark, q);
     }
     __device__ __forceinline__ void settle(int32_t, unsigned long long, int32_t, int, int32_t *) const {}
-    // every thread, converged (the end of a kernel, or behind a parked row's walk): one add per wave
+    // every thread, converged, at the end of a kernel: one add per wave
     __device__ __forceinline__ void finish() const {
         unsigned long long sum = improved;
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
         if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&ctrl->relax, sum);
         improved = 0;
-    }
-};
-// (k_frontier_round_long has no finish(): its walks flush through this kernel-end hook of their own)
-template <class D>
-struct SsspRelaxLong : SsspRelax<D> {
-    __device__ __forceinline__ void long_walk(int32_t x, unsigned long long note, int64_t tid, int64_t threads, const NextQueue &q) const {
-        SsspRelax<D>::long_walk(x, note, tid, threads, q);
-        SsspRelax<D>::finish();
     }
 };
 
@@ -133,21 +126,16 @@ __global__ __launch_bounds__(256) void k_sssp_next_min(int64_t n, const D *__res
     if ((threadIdx.x & 63) == 0 && best != ~0ull) atomicMin(&ctrl->next_min, best);
 }
 
-// the vertices of bucket [lo, hi) into the frontier list
+// k_frontier_collect's predicate: v lies in bucket [lo, hi)
 template <class D>
-__global__ __launch_bounds__(256) void k_sssp_collect(int64_t n, const D *__restrict__ dist, long long lo, long long hi, int32_t *__restrict__ list,
-                                                      SsspCtrl *__restrict__ ctrl) {
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    const int64_t end = ((n + 63) / 64) * 64;  // whole waves stay converged for the ballot
-    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride) {
-        bool take = false;
-        if (v < n) {
-            const D d = dist[v];
-            take = d != DistInf<D>::value && (long long)d >= lo && (long long)d < hi;
-        }
-        wave_append(take, int32_t(v), list, &ctrl->count, n, &ctrl->error);
+struct SsspInBucket {
+    const D *dist;
+    long long lo, hi;
+    __device__ __forceinline__ bool operator()(int64_t v) const {
+        const D d = dist[v];
+        return d != DistInf<D>::value && (long long)d >= lo && (long long)d < hi;
     }
-}
+};
 
 // the info pass's words (also the pull pass's)
 struct SsspAcc {
@@ -201,9 +189,8 @@ template <int WIDTH, bool kCount>
 __global__ __launch_bounds__(256) void k_sssp_pull(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
                                                    const int32_t *__restrict__ wgt, const long long *__restrict__ dist, int32_t source,
                                                    int32_t *__restrict__ parent, SsspAcc *__restrict__ acc) {
-    const int lane = threadIdx.x & (WIDTH - 1);
-    const int shift = (threadIdx.x & 63) & ~(WIDTH - 1);  // where the group's lanes sit in the wave's ballot
-    const unsigned long long mask = WIDTH == 64 ? ~0ull : ((1ull << (WIDTH & 63)) - 1ull);
+    const RowGroup<WIDTH> grp;
+    const int lane = grp.lane;
     const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
     const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
     const unsigned long long max_dist = kCount ? 0ull : acc->max_dist;
@@ -239,17 +226,17 @@ __global__ __launch_bounds__(256) void k_sssp_pull(int64_t n, const int64_t *__r
                     }
                 }
             }
-            const unsigned long long hits = (__ballot(tight) >> shift) & mask;
+            const unsigned long long hits = grp.ballot(tight);
             if (hits) {
                 found = true;
                 if (!kCount) {
-                    if (lane == __ffsll((long long)hits) - 1) parent[v] = u;  // the row ascends: the lowest hit lane holds the smallest id
+                    if (lane == grp.first(hits)) parent[v] = u;
                     break;
                 }
             }
         }
         if (kCount) {
-            const bool any_reached = ((__ballot(neighbour_reached) >> shift) & mask) != 0;
+            const bool any_reached = grp.ballot(neighbour_reached) != 0;
             if (lane == 0) {
                 if (dv >= 0 && !is_source && !found) ++untight;
                 if (dv < 0 && any_reached) ++wrong;
@@ -327,45 +314,9 @@ __global__ __launch_bounds__(256) void k_weights_check(int64_t n, int64_t nnz, c
 // ---- the host ------------------------------------------------------------------------------------------------------------------------------
 
 struct SsspBufs {
-    DevBuf dist, stamp, f0, f1, longs, notes, out, parent, ctrl, acc;
-    int64_t long_cap = 0;
+    DevBuf dist, stamp, out, parent, ctrl, acc;
+    FrontierStore store;
 };
-
-// The engine's step (frontier_rounds.hpp, run_frontier_rounds) without its once-per-vertex checks: a vertex re-enters the frontier here, so
-// `done` — the frontier entries worked so far — may pass n; what stays checked is the frontier size and that every step advanced the round.
-template <class D>
-int sssp_rounds(const SsspRelax<D> &p, const FrontierBufs &b, SsspCtrl *ctrl, SsspCtrl &h, long long wg_frontier, int64_t round_cap, int *launches) {
-    Ctx &c = ctx();
-    hipStream_t s = c.stream;
-    const int cus = c.compute_units > 0 ? c.compute_units : 256;
-    const int64_t n = p.n;
-    SsspRelaxLong<D> pl;
-    static_cast<SsspRelax<D> &>(pl) = p;
-    while (h.count > 0) {
-        if (int64_t(h.round) > round_cap) return GMSX_ERR_KERNEL;
-        if (h.count <= wg_frontier && !h.bail) {
-            hipLaunchKernelGGL(k_frontier_tail<SsspRelax<D>>, dim3(1), dim3(kTailThreads), 0, s, p, b.f[0], b.f[1], int32_t(wg_frontier), ctrl);
-            *launches += 1;
-        } else {
-            const unsigned rb = unsigned(std::min<int64_t>((int64_t(h.count) * kGroup + 255) / 256, int64_t(cus) * 32));
-            hipLaunchKernelGGL(k_frontier_round<SsspRelax<D>>, dim3(rb), dim3(256), 0, s, p, b.f[h.cur], b.f[h.cur ^ 1], b.longs, b.notes, b.long_cap, ctrl);
-            hipLaunchKernelGGL(k_frontier_round_long<SsspRelaxLong<D>>, dim3(unsigned(cus) * 4), dim3(256), 0, s, pl, b.f[h.cur ^ 1], b.longs, b.notes, b.long_cap,
-                               ctrl);
-            hipLaunchKernelGGL(k_frontier_advance<SsspRelax<D>>, dim3(1), dim3(kTailThreads), 0, s, p, b.longs, b.notes, b.long_cap, ctrl);
-            *launches += 3;
-            if (h.bail) {
-                h.bail = 0;
-                GMSX_HIP(hipMemsetAsync(&ctrl->bail, 0, sizeof(int32_t), s));
-            }
-        }
-        const int32_t round_was = h.round;
-        GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipStreamSynchronize(s));
-        if (h.error || h.count < 0 || int64_t(h.count) > n) return GMSX_ERR_KERNEL;
-        if (!h.bail && h.round <= round_was) return GMSX_ERR_KERNEL;  // a step that made no progress
-    }
-    return GMSX_OK;
-}
 
 struct SsspRun {
     int64_t buckets = 0, rounds = 0, relaxations = 0;
@@ -382,7 +333,7 @@ int sssp_run(const gmsx_graph *g, int32_t source, long long delta, long long wg_
     const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
     D *dist = b.dist.as<D>();
     SsspCtrl *ctrl = b.ctrl.as<SsspCtrl>();
-    const FrontierBufs bufs{{b.f0.as<int32_t>(), b.f1.as<int32_t>()}, b.longs.as<int32_t>(), b.notes.as<unsigned long long>(), b.long_cap};
+    const FrontierBufs bufs = b.store.bufs();
     SsspRelax<D> p{n, g->off, g->adj, g->wgt.as<const int32_t>(), dist, b.stamp.as<int32_t>(), ctrl, 0};
 
     hipLaunchKernelGGL(k_sssp_init<D>, dim3(per_vertex), dim3(256), 0, s, n, source, dist, b.stamp.as<int32_t>(), bufs.f[0]);
@@ -400,8 +351,9 @@ int sssp_run(const gmsx_graph *g, int32_t source, long long delta, long long wg_
         if (++run->buckets > bucket_cap) return GMSX_ERR_KERNEL;
         p.hi = hi;
         GMSX_HIP(hipMemcpyAsync(ctrl, &h, sizeof h, hipMemcpyHostToDevice, s));
-        const int64_t round0 = h.round;
-        if (int rc = sssp_rounds<D>(p, bufs, ctrl, h, wg_frontier, round0 + n + 1, launches)) return rc;
+        const int64_t round_cap = int64_t(h.round) + n + 1;  // a bucket is done after at most n rounds (BOUNDS)
+        if (int rc = run_frontier_rounds(p, bufs, ctrl, h, wg_frontier, launches, [=](const SsspCtrl &m) { return int64_t(m.round) > round_cap; })) return rc;
+        if (h.count > 0) return GMSX_ERR_KERNEL;
         // ---- the next bucket: the one of the smallest tentative distance at or above hi
         if (hi == LLONG_MAX) break;
         hipLaunchKernelGGL(k_sssp_next_min<D>, dim3(sweep), dim3(256), 0, s, n, dist, hi, ctrl);
@@ -416,7 +368,7 @@ int sssp_run(const gmsx_graph *g, int32_t source, long long delta, long long wg_
         h.next = h.nlong = h.bail = h.cur = h.done = 0;
         h.next_min = ~0ull;
         GMSX_HIP(hipMemcpyAsync(ctrl, &h, sizeof h, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_sssp_collect<D>, dim3(sweep), dim3(256), 0, s, n, dist, lo, hi2, bufs.f[0], ctrl);
+        frontier_collect(n, SsspInBucket<D>{dist, lo, hi2}, bufs.f[0], &ctrl->count, &ctrl->error);
         ++*launches;
         GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
@@ -429,13 +381,9 @@ int sssp_run(const gmsx_graph *g, int32_t source, long long delta, long long wg_
 
 int sssp_alloc(const gmsx_graph *g, bool wide, SsspBufs &b) {
     const int64_t n = g->n;
-    b.long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
+    if (int rc = b.store.alloc(n, g->nnz, true)) return rc;
     if (int rc = wide ? dalloc<long long>(b.dist, n) : dalloc<int32_t>(b.dist, n)) return rc;
     if (int rc = dalloc<int32_t>(b.stamp, n)) return rc;
-    if (int rc = dalloc<int32_t>(b.f0, n)) return rc;
-    if (int rc = dalloc<int32_t>(b.f1, n)) return rc;
-    if (int rc = dalloc<int32_t>(b.longs, b.long_cap)) return rc;
-    if (int rc = dalloc<unsigned long long>(b.notes, b.long_cap)) return rc;
     if (int rc = dalloc<long long>(b.out, n)) return rc;
     if (int rc = dalloc<int32_t>(b.parent, n)) return rc;
     if (int rc = dalloc<SsspCtrl>(b.ctrl, 1)) return rc;
@@ -522,7 +470,7 @@ int gmsx_sssp(const gmsx_graph *g, int32_t source, int64_t delta, int64_t *dist,
         hipStream_t s = c.stream;
         const int cus = c.compute_units > 0 ? c.compute_units : 256;
         const bool wide = g->wide_dist || opt_int("SSSP_WIDE", 0) != 0;
-        const long long wg_frontier = std::max<long long>(0, std::min<long long>(opt_int("SSSP_WG_FRONTIER", kWgFrontierDefault), INT_MAX));
+        const long long wg_frontier = frontier_wg_option("SSSP_WG_FRONTIER", kWgFrontierDefault);
         long long d = delta;
         if (d == 0) {  // the default rule: a function of the handle's mean weight and mean degree
             const long long cpar = std::max<long long>(1, std::min<long long>(opt_int("SSSP_DELTA_AUTO", kSsspDeltaAutoDefault), 1 << 20));

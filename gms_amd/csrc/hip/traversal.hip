@@ -188,9 +188,8 @@ __global__ __launch_bounds__(256) void k_bfs_bottom_up_rows(int64_t n, const int
                                                             int32_t probe, const uint32_t *__restrict__ front, uint32_t *__restrict__ next,
                                                             int32_t *__restrict__ depth, int32_t *__restrict__ parent,
                                                             const int32_t *__restrict__ list, BfsCtrl *__restrict__ ctrl) {
-    const int lane = threadIdx.x & (WIDTH - 1);
-    const int shift = (threadIdx.x & 63) & ~(WIDTH - 1);  // where the group's lanes sit in the wave's ballot
-    const unsigned long long mask = WIDTH == 64 ? ~0ull : ((1ull << (WIDTH & 63)) - 1ull);
+    const RowGroup<WIDTH> grp;
+    const int lane = grp.lane;
     const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
     const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
     const int64_t rows = min(int64_t(ctrl->bu_list), n);
@@ -204,10 +203,9 @@ __global__ __launch_bounds__(256) void k_bfs_bottom_up_rows(int64_t n, const int
             const int64_t j = c + lane;
             const int32_t w = j < j1 ? adj[j] : -1;
             const bool hit = w >= 0 && bit_set(front, w);
-            const unsigned long long hits = (__ballot(hit) >> shift) & mask;
+            const unsigned long long hits = grp.ballot(hit);
             if (hits) {
-                const int first = __ffsll((long long)hits) - 1;  // the row ascends: the lowest hit lane holds the smallest id
-                if (lane == first) {
+                if (lane == grp.first(hits)) {
                     bu_take(v, w, level, depth, parent, next);
                     ++awake;
                     deg += (unsigned long long)(j1 - j0);
@@ -226,14 +224,12 @@ __global__ __launch_bounds__(256) void k_bfs_bottom_up_rows(int64_t n, const int
     }
 }
 
-// BitmapToQueue (bfs.cc:98-110), from the depths: the vertices of level d into a frontier list
-__global__ __launch_bounds__(256) void k_bfs_collect(int64_t n, const int32_t *__restrict__ depth, int32_t d, int32_t *__restrict__ list,
-                                                     BfsCtrl *__restrict__ ctrl) {
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    const int64_t end = ((n + 63) / 64) * 64;
-    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride)
-        wave_append(v < n && depth[v] == d, int32_t(v), list, &ctrl->count, n, &ctrl->error);
-}
+// BitmapToQueue (bfs.cc:98-110), from the depths: k_frontier_collect's predicate for the vertices of level d
+struct BfsAtDepth {
+    const int32_t *depth;
+    int32_t d;
+    __device__ __forceinline__ bool operator()(int64_t v) const { return depth[v] == d; }
+};
 
 // the final pass: parent of the unreached = -1, hist[depth] (one add per distinct depth of a wave), the sums
 __global__ __launch_bounds__(256) void k_bfs_info(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ depth,
@@ -495,26 +491,24 @@ BfsOptions bfs_options() {
     o.alpha = std::max<long long>(1, std::min<long long>(opt_int("BFS_ALPHA", kBfsAlphaDefault), INT_MAX));
     o.beta = std::max<long long>(1, std::min<long long>(opt_int("BFS_BETA", kBfsBetaDefault), INT_MAX));
     o.probe = std::max<long long>(0, std::min<long long>(opt_int("BFS_BU_PROBE", kBfsProbeDefault), kLongRow));
-    o.wg_frontier = std::max<long long>(0, std::min<long long>(opt_int("BFS_WG_FRONTIER", kWgFrontierDefault), INT_MAX));
+    o.wg_frontier = frontier_wg_option("BFS_WG_FRONTIER", kWgFrontierDefault);
     return o;
 }
 
 // the device arrays of one BFS; a betweenness call keeps them over its sources
 struct BfsBufs {
-    DevBuf depth, parent, hist, f0, f1, longs, front, next, bu_list, ctrl, acc;
-    int64_t long_cap = 0, words = 0;
+    DevBuf depth, parent, hist, front, next, bu_list, ctrl, acc;
+    FrontierStore store;  // (betweenness parks its own long rows in store.longs between the searches)
+    int64_t words = 0;
 };
 
 int bfs_alloc(const gmsx_graph *g, BfsBufs &b) {
     const int64_t n = g->n;
-    b.long_cap = std::min<int64_t>(n, g->nnz / kLongRow + 1);
     b.words = (n + 31) / 32;
+    if (int rc = b.store.alloc(n, g->nnz, false)) return rc;
     if (int rc = dalloc<int32_t>(b.depth, n)) return rc;
     if (int rc = dalloc<int32_t>(b.parent, n)) return rc;
     if (int rc = dalloc<int32_t>(b.hist, n)) return rc;
-    if (int rc = dalloc<int32_t>(b.f0, n)) return rc;
-    if (int rc = dalloc<int32_t>(b.f1, n)) return rc;
-    if (int rc = dalloc<int32_t>(b.longs, b.long_cap)) return rc;
     if (int rc = dalloc<uint32_t>(b.front, b.words)) return rc;
     if (int rc = dalloc<uint32_t>(b.next, b.words)) return rc;
     if (int rc = dalloc<int32_t>(b.bu_list, n)) return rc;
@@ -535,7 +529,7 @@ int bfs_run(const gmsx_graph *g, int32_t source, const BfsOptions &o, const BfsB
     int32_t *depth = b.depth.as<int32_t>(), *parent = b.parent.as<int32_t>(), *hist = b.hist.as<int32_t>();
     BfsCtrl *ctrl = b.ctrl.as<BfsCtrl>();
     BfsAcc *acc = b.acc.as<BfsAcc>();
-    const FrontierBufs bufs{{b.f0.as<int32_t>(), b.f1.as<int32_t>()}, b.longs.as<int32_t>(), nullptr, b.long_cap};
+    const FrontierBufs bufs = b.store.bufs();
     const BfsTopDown td{n, g->off, g->adj, depth, parent, ctrl, o.direction == 0 ? o.alpha : 0};
     uint32_t *front = b.front.as<uint32_t>(), *next = b.next.as<uint32_t>();
 
@@ -595,7 +589,7 @@ int bfs_run(const gmsx_graph *g, int32_t source, const BfsOptions &o, const BfsB
             h.error = h.nlong = h.bail = h.cur = h.stop = h.bu_list = 0;
             h.scout_acc = 0;
             GMSX_HIP(hipMemcpyAsync(ctrl, &h, sizeof h, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_bfs_collect, dim3(sweep), dim3(256), 0, s, n, depth, int32_t(level), bufs.f[0], ctrl);
+            frontier_collect(n, BfsAtDepth{depth, int32_t(level)}, bufs.f[0], &ctrl->count, &ctrl->error);
             ++*launches;
             GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
             GMSX_HIP(hipStreamSynchronize(s));
@@ -706,7 +700,7 @@ int gmsx_betweenness(const gmsx_graph *g, int64_t n_sources, const int32_t *sour
         hipStream_t s = c.stream;
         const int cus = c.compute_units > 0 ? c.compute_units : 256;
         const BfsOptions o = bfs_options();
-        const int64_t slot_cap = g->nnz / kBcChunk + std::min<int64_t>(n, g->nnz / kLongRow + 1);
+        const int64_t slot_cap = g->nnz / kBcChunk + frontier_long_cap(n, g->nnz);
         BfsBufs b;
         DevBuf d_sigma, d_delta, d_scores, d_order, d_loff, d_cursor, d_notes, d_slot_row, d_slots, d_bc;
         GMSX_HIP(hipEventRecord(c.ev[0], s));
@@ -717,7 +711,7 @@ int gmsx_betweenness(const gmsx_graph *g, int64_t n_sources, const int32_t *sour
         if (int rc = dalloc<int32_t>(d_order, n)) return rc;
         if (int rc = dalloc<int32_t>(d_loff, n + 1)) return rc;
         if (int rc = dalloc<int32_t>(d_cursor, n + 1)) return rc;
-        if (int rc = dalloc<unsigned long long>(d_notes, b.long_cap)) return rc;
+        if (int rc = dalloc<unsigned long long>(d_notes, b.store.long_cap)) return rc;
         if (int rc = dalloc<int32_t>(d_slot_row, slot_cap)) return rc;
         if (int rc = dalloc<double>(d_slots, slot_cap)) return rc;
         if (int rc = dalloc<BcCtrl>(d_bc, 1)) return rc;
@@ -726,10 +720,10 @@ int gmsx_betweenness(const gmsx_graph *g, int64_t n_sources, const int32_t *sour
         GMSX_HIP(hipMemsetAsync(bc, 0, sizeof(BcCtrl), s));
         GMSX_HIP(hipEventRecord(c.ev[1], s));
         BcArgs a{g->off, g->adj, b.depth.as<const int32_t>(), d_order.as<const int32_t>(), d_sigma.as<double>(), d_delta.as<double>(),
-                 d_scores.as<double>(), b.longs.as<int32_t>(), d_notes.as<unsigned long long>(), d_slot_row.as<int32_t>(), d_slots.as<double>(), b.long_cap, slot_cap, bc, -1};
+                 d_scores.as<double>(), b.store.longs.as<int32_t>(), d_notes.as<unsigned long long>(), d_slot_row.as<int32_t>(), d_slots.as<double>(), b.store.long_cap, slot_cap, bc, -1};
         const unsigned per_vertex = unsigned((n + 255) / 256);
         const unsigned long_grid = unsigned(cus) * 8;
-        const unsigned sum_grid = unsigned((b.long_cap + 255) / 256);
+        const unsigned sum_grid = unsigned((b.store.long_cap + 255) / 256);
         int launches = 0;
         uint64_t arcs = 0, levels_sum = 0;
         std::vector<int32_t> loff;

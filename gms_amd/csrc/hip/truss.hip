@@ -309,12 +309,11 @@ int truss_edges(const gmsx_graph *g, TrussEdges &t, int32_t *rnd) {
     hipLaunchKernelGGL(k_truss_number, dim3(unsigned((nnz + 255) / 256)), dim3(256), 0, s, n, nnz, m, g->off, g->adj, d_up0.as<int64_t>(), d_ebase.as<int64_t>(),
                        t.eid.as<int32_t>(), t.eu.as<int32_t>(), t.ev.as<int32_t>(), d_cost.as<int64_t>(), t.acc.as<TrussAcc>());
     if (int rc = exclusive_scan_i64(d_cost.as<const int64_t>(), t.coff.as<int64_t>(), m + 1, s)) return rc;
-    int64_t total_cost = 0;
-    GMSX_HIP(hipMemcpyAsync(&total_cost, t.coff.as<int64_t>() + m, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    GMSX_HIP(hipMemcpyAsync(&t.total_cost, t.coff.as<int64_t>() + m, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     GMSX_HIP(hipMemcpyAsync(&t.h, t.acc.p, sizeof(TrussAcc), hipMemcpyDeviceToHost, s));
     GMSX_HIP(hipStreamSynchronize(s));
     if (t.h.error) return GMSX_ERR_KERNEL;
-    t.long_cap = std::min<int64_t>(m, total_cost / kLongRow + 1);
+    t.long_cap = frontier_long_cap(m, t.total_cost);
     if (int rc = dalloc<int32_t>(t.longs, t.long_cap)) return rc;
     const unsigned sb = unsigned(std::min<int64_t>((m * kGroup + 255) / 256, int64_t(cus) * 32));
     const unsigned sweep = unsigned(std::min<int64_t>((m + 255) / 256, int64_t(cus) * 16));
@@ -396,7 +395,8 @@ int gmsx_truss_decomposition(const gmsx_graph *g, int32_t *truss, int32_t *round
         const int64_t nnz = g->nnz;
         const int cus = c.compute_units > 0 ? c.compute_units : 256;
         TrussEdges t;
-        DevBuf d_rnd, d_truss, d_f0, d_f1, d_ctrl, d_out;
+        DevBuf d_rnd, d_truss, d_ctrl, d_out;
+        FrontierStore store;  // (the items are edges, their rows the cost ranges of coff; its longs list stands beside t.longs of the support pass)
         // ---- setup: numbering and support
         GMSX_HIP(hipEventRecord(c.ev[0], s));
         if (int rc = dalloc<int32_t>(d_rnd, nnz / 2)) return rc;  // (the support pass's last kernel fills it; the numbering refuses m != nnz / 2)
@@ -404,17 +404,15 @@ int gmsx_truss_decomposition(const gmsx_graph *g, int32_t *truss, int32_t *round
         GMSX_HIP(hipEventRecord(c.ev[1], s));
         const int64_t m = t.m;
         if (int rc = dalloc<int32_t>(d_truss, m)) return rc;
-        if (int rc = dalloc<int32_t>(d_f0, m)) return rc;
-        if (int rc = dalloc<int32_t>(d_f1, m)) return rc;
+        if (int rc = store.alloc(m, t.total_cost, false)) return rc;
         if (int rc = dalloc<TrussCtrl>(d_ctrl, 1)) return rc;
         TrussCtrl *ctrl = d_ctrl.as<TrussCtrl>();
         int32_t *sup = t.sup.as<int32_t>(), *rnd = d_rnd.as<int32_t>();
-        const FrontierBufs bufs{{d_f0.as<int32_t>(), d_f1.as<int32_t>()}, t.longs.as<int32_t>(), nullptr, t.long_cap};
+        const FrontierBufs bufs = store.bufs();
         TrussPeel peel{m, t.coff.as<int64_t>(), g->off, g->adj, t.eid.as<int32_t>(), t.eu.as<int32_t>(), t.ev.as<int32_t>(), sup, rnd, d_truss.as<int32_t>(), 0};
         // test hook: 0 = every round a kernel boundary, large = every round the tail may take.  The default is 0: a round here is an intersection per
         // frontier edge, and the one-workgroup tail measured slower than kernel boundaries at every size.
-        long long wg_frontier = opt_int("TRUSS_WG_FRONTIER", 0);
-        wg_frontier = std::max<long long>(0, std::min<long long>(wg_frontier, INT_MAX));
+        const long long wg_frontier = frontier_wg_option("TRUSS_WG_FRONTIER", 0);
         res.max_support = t.h.max_sup;
         res.triangles = int64_t(t.h.sum / 3);
         // ---- the peel

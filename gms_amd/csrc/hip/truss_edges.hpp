@@ -19,7 +19,7 @@ struct TrussAcc {
 
 // what one call builds before anything is counted: the numbering, the costs and the support of every edge
 struct TrussEdges {
-    int64_t m = 0, long_cap = 0;
+    int64_t m = 0, total_cost = 0, long_cap = 0;  // total_cost: Σ cost over the edges, what coff ends in
     DevBuf eid, eu, ev, coff, sup, acc, longs;
     TrussAcc h;
     int launches = 0;

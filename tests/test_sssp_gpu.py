@@ -4,7 +4,8 @@ restatement of tests/test_sssp_golden_cpu.py (dijkstra_np, parent_np, verify_np,
   goldens      every record at delta 1, 16, 0 (the library's choice) and 2^31 - 1
   re-entry     a path 0 - 1 - … - 2047 of weight 1 plus arcs (0, i) of weight 3 i: every vertex is improved again and again; with one bucket that
                is 2000+ rounds inside the one-workgroup kernel (SSSP_WG_FRONTIER 512) or as many kernel boundaries (0)
-  row classes  a star with 1 500 leaves (above kLongRow), one with 40 000 (above kWgRowMax: the tail hands the round back), kronecker 14
+  row classes  a star with 1 500 leaves (above kLongRow), one with 40 000 (above kWgRowMax: the tail hands the round back), kronecker 14;
+               on the stars info.relaxations is exactly the number of leaves at both ends of SSSP_WG_FRONTIER
   wide         an 8-vertex path of weights 2^31 - 1: distances above 2^32 in 64-bit words; SSSP_WIDE = 1 gives the bytes of the narrow run
   unreachable  two components, isolated vertices, n = 1, an edgeless graph with a weight array of length 0
   unit weights dist and parent are gmsx_bfs's depth and parent
@@ -113,6 +114,25 @@ def test_star(gpu, leaves):
             dist, parent, info = check(g, off, adj, w, source, delta)
             assert g.sssp_verify(source, dist) == CLEAN
     assert dist[0] == wt[6] and parent[0] == 7 and np.all(np.delete(parent, [0, 7]) == 0)
+    g.free()
+
+
+@pytest.mark.parametrize("leaves", [1500, 40000])
+def test_star_counts_every_relaxation_once(gpu, leaves):
+    """info.relaxations is exact here, wherever the walkers flush their counts: every leaf has one arc in and is improved once, from infinity, and
+    no arc back to the hub improves distance 0.  1 500 leaves: the hub's row is walked by k_frontier_round_long (frontier bound 0) or by the
+    tail's own long walk (512); 40 000: the tail hands the round back."""
+    wt = np.random.RandomState(leaves).randint(1, 256, size=leaves)
+    csr = gpu.HostCSR.from_weighted_edges(np.zeros(leaves, dtype=np.int64), np.arange(1, leaves + 1), wt, num_nodes=leaves + 1)
+    g = weighted_graph(gpu, csr)
+    runs = []
+    for wg_frontier in (512, 0, 512, 0):
+        with gpu.options(SSSP_WG_FRONTIER=wg_frontier):
+            dist, parent, info = g.sssp(0, 2 ** 31 - 1)
+        assert info["relaxations"] == leaves and info["buckets"] == 1, (wg_frontier, info)
+        runs.append((dist.tobytes(), parent.tobytes()))
+    assert all(r == runs[0] for r in runs)
+    assert np.array_equal(dist[1:], wt) and dist[0] == 0
     g.free()
 
 
