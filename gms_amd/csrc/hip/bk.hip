@@ -218,9 +218,12 @@ __device__ __forceinline__ void bk_scan_row_group8(const int64_t *__restrict__ h
     }
 }
 
-__device__ __forceinline__ int wave_sum(int x) {
-    for (int s = 32; s > 0; s >>= 1) x += __shfl_xor(x, s);
-    return x;
+// the pivot rule between two lanes: the larger score; ties -> the smaller index, so every lane of the butterfly agrees
+__device__ __forceinline__ void bk_better(int &score, int &u, int os, int ou) {
+    if (os > score || (os == score && ou < u)) {
+        score = os;
+        u = ou;
+    }
 }
 
 // ---- load balancing ------------------------------------------------------------------------------------------
@@ -312,7 +315,7 @@ __device__ __forceinline__ void bk_search(const uint32_t *Cadj, const uint32_t *
                 int pc_ = 0;
 #pragma unroll
                 for (int h = 0; h < WPL; ++h) pc_ += __popc(P[h]);
-                pc_ = wave_sum(pc_);
+                pc_ = wave_sum_all(pc_);
                 BK_STAT(c <= 32 ? 0 : c <= 64 ? 1 : c <= 128 ? 2 : c <= 256 ? 3 : c <= 512 ? 4 : c <= 1024 ? 5 : c <= 2048 ? 6 : 7, 1);
                 BK_STAT(8 + (pc_ == 0 ? 0 : pc_ == 1 ? 1 : pc_ <= 6 ? 2 : pc_ <= 16 ? 3 : pc_ <= 32 ? 4 : pc_ <= 64 ? 5 : pc_ <= 256 ? 6 : 7), 1);
                 if (xf_ne) BK_STAT(16, 1);
@@ -383,7 +386,7 @@ __device__ __forceinline__ void bk_search(const uint32_t *Cadj, const uint32_t *
                 int pc = 0;
 #pragma unroll
                 for (int h = 0; h < WPL; ++h) pc += __popc(P[h]);
-                pc = wave_sum(pc);
+                pc = wave_sum_all(pc);
                 if (pc <= sh.small_p) {  // wave-uniform
                     int hsel = 0;
 #pragma unroll
@@ -420,11 +423,7 @@ __device__ __forceinline__ void bk_search(const uint32_t *Cadj, const uint32_t *
                 mine += __popc(U[h]);
                 if (lane + 64 * h < cw) piv_P[lane + 64 * h] = P[h];
             }
-            int pre = mine;
-            for (int sft = 1; sft < 64; sft <<= 1) {
-                const int o = __shfl_up(pre, sft);
-                if (lane >= sft) pre += o;
-            }
+            const int pre = wave_incl_scan(mine, lane);
             const int ncand = __builtin_amdgcn_readlane(pre, 63);
             BK_STAT(21, 1);
             BK_STAT(22, ncand);
@@ -451,13 +450,7 @@ __device__ __forceinline__ void bk_search(const uint32_t *Cadj, const uint32_t *
                     best = u;
                 }
             }
-            for (int sft = 32; sft > 0; sft >>= 1) {  // wave argmax (ties -> smallest index, so every lane agrees)
-                const int os = __shfl_xor(best_score, sft), ob = __shfl_xor(best, sft);
-                if (os > best_score || (os == best_score && ob < best)) {
-                    best_score = os;
-                    best = ob;
-                }
-            }
+            wave_fold2_all(best_score, best, bk_better);  // wave argmax
             __builtin_amdgcn_wave_barrier();
             best = uni32(best);  // every lane holds the same winner
 #pragma unroll
@@ -523,7 +516,7 @@ __device__ __forceinline__ void bk_search(const uint32_t *Cadj, const uint32_t *
                 auto level_bits = [&](int l) {
                     int b = 0;
                     for (int w = lane; w < cw; w += 64) b += __popc(stack[size_t(l) * lvl + 2 * cw + w]);
-                    for (int sft = 32; sft > 0; sft >>= 1) b += __shfl_xor(b, sft);
+                    b = wave_sum_all(b);
                     return b;
                 };
                 for (int l = 0; l <= depth; ++l) nrec += min(level_bits(l), kBkSplit);
@@ -573,11 +566,7 @@ __device__ __forceinline__ void bk_search(const uint32_t *Cadj, const uint32_t *
                                 const int w = w0 + lane;
                                 const uint32_t e = w < cw ? lv[2 * cw + w] : 0u;
                                 const int mine = __popc(e);
-                                int pre = mine;
-                                for (int sft = 1; sft < 64; sft <<= 1) {
-                                    const int o = __shfl_up(pre, sft);
-                                    if (lane >= sft) pre += o;
-                                }
+                                const int pre = wave_incl_scan(mine, lane);
                                 const int rank0 = base + pre - mine;  // rank of this word's first pending branch
                                 base += __builtin_amdgcn_readlane(pre, 63);
                                 if (w < cw) {
@@ -721,7 +710,7 @@ __device__ __forceinline__ void bk_search(const uint32_t *Cadj, const uint32_t *
             child_ne = __ballot(any != 0) != 0 ? 1 : 0;
             BK_T1(28);
 #ifdef GMSX_BK_STATS
-            nzw_ = wave_sum(nzw_);
+            nzw_ = wave_sum_all(nzw_);
             BK_STAT(31, nzw_);
 #endif
         }
@@ -793,11 +782,7 @@ __device__ __forceinline__ void bk_search_mem(const uint32_t *Cadj, const uint32
                 const int w = w0 + lane;
                 uint32_t bits = w < cw ? (P[w] | Xc[w]) : 0u;
                 const int mine = __popc(bits);
-                int pre = mine;
-                for (int sft = 1; sft < 64; sft <<= 1) {
-                    const int o = __shfl_up(pre, sft);
-                    if (lane >= sft) pre += o;
-                }
+                const int pre = wave_incl_scan(mine, lane);
                 int at = ncand + pre - mine;
                 while (bits) {
                     piv_list[at++] = uint32_t((w << 5) + __ffs(bits) - 1);
@@ -818,13 +803,7 @@ __device__ __forceinline__ void bk_search_mem(const uint32_t *Cadj, const uint32
                     best = u;
                 }
             }
-            for (int sft = 32; sft > 0; sft >>= 1) {
-                const int os = __shfl_xor(best_score, sft), ob = __shfl_xor(best, sft);
-                if (os > best_score || (os == best_score && ob < best)) {
-                    best_score = os;
-                    best = ob;
-                }
-            }
+            wave_fold2_all(best_score, best, bk_better);
             best = uni32(best);
             const uint32_t *prow = Cadj + size_t(best) * cw;
             for (int w = lane; w < cw; w += 64) ext[w] = P[w] & ~prow[w];
@@ -1612,13 +1591,6 @@ template <int G> __device__ __forceinline__ int bkg_min(int x) {
 }
 template <int G> __device__ __forceinline__ int bkg_first(uint32_t w, int sub) { return bkg_min<G>(w != 0u ? (sub << 5) + __ffs(w) - 1 : 0xffff); }  // lowest set bit of the group's set
 template <int G> __device__ __forceinline__ uint32_t bkg_ballot(bool p, int gsh) { return uint32_t(__ballot(p) >> gsh) & ((1u << G) - 1u); }  // the group's bits of the wave ballot
-template <int G> __device__ __forceinline__ int bkg_scan(int x, int sub) {  // inclusive prefix sum over the lanes of the group (rare paths only)
-    for (int d = 1; d < G; d <<= 1) {
-        const int t = __shfl_up(x, d, G);
-        if (sub >= d) x += t;
-    }
-    return x;
-}
 
 // Xf of a level held in memory — dense words (n < 0: the xw words at src) or a list of n (word index, word) pairs — against row(s) of XT.
 // MODE 0: the child list Xf ∩ N(q) -> dst, returns its length; 1: is Xf ∩ N(q) non-empty; 2: is Xf ∩ N(q) ∩ N(q2) non-empty.
@@ -1884,7 +1856,7 @@ __device__ __forceinline__ void bk_group_searches(const uint32_t *__restrict__ p
                 BKG_ST(3, 1);
                 const uint32_t U = P | Xc;
                 const int mine = __popc(U);
-                const int incl = bkg_scan<G>(mine, sub);
+                const int incl = wave_incl_scan<G>(mine, sub);
                 const int ncand = __shfl(incl, gsh + G - 1);
                 my_P[sub] = P;
                 {
@@ -1984,7 +1956,7 @@ __device__ __forceinline__ void bk_group_searches(const uint32_t *__restrict__ p
                             const int ln = int(ls[3]);
                             const uint32_t lidx = ls[4], lval = ls[5];
                             const int mine = __popc(e);
-                            const int incl = bkg_scan<G>(mine, sub);
+                            const int incl = wave_incl_scan<G>(mine, sub);
                             const int nb = __shfl(incl, gsh + G - 1);
                             if (nb == 0) continue;
                             const int rank0 = incl - mine;  // rank of this word's first pending branch
@@ -2114,7 +2086,7 @@ __global__ __launch_bounds__(256) void k_stat_bk_bytes(int64_t n_tasks, int npar
             b += 2ull * (unsigned long long)(hoff[w + 1] - hoff[w]) + 4ull * (unsigned long long)(toff[w + 1] - toff[w]);
         }
     }
-    for (int sft = 32; sft > 0; sft >>= 1) b += __shfl_xor(b, sft);
+    b = wave_sum_all(b);
     if (lane == 0 && b) atomicAdd(out, b);
 }
 

@@ -40,16 +40,6 @@ __host__ __device__ inline unsigned long long bkl_need(long long c, long long x)
 
 __device__ __forceinline__ void bkl_flag(unsigned long long *acc, unsigned long long f) { atomicOr(&acc[kListFlags], f); }
 
-__device__ __forceinline__ unsigned long long bkl_max64(unsigned long long k) {
-    for (int m = 32; m >= 1; m >>= 1) {
-        const unsigned lo = unsigned(__shfl_xor(int(unsigned(k)), m));
-        const unsigned hi = unsigned(__shfl_xor(int(unsigned(k >> 32)), m));
-        const unsigned long long o = (static_cast<unsigned long long>(hi) << 32) | lo;
-        k = o > k ? o : k;
-    }
-    return k;
-}
-
 // local index of rank id t in the ascending candidate list, or -1
 __device__ __forceinline__ int bkl_find(const uint32_t *cand, int c, uint32_t t) {
     int lo = 0, hi = c;
@@ -95,7 +85,7 @@ __device__ __forceinline__ void bkl_pivot(const uint32_t *P, const uint32_t *Xc,
         const unsigned long long k = (static_cast<unsigned long long>(s + 1) << 32) | (0xFFFFFFFFu - uint32_t(u));
         key = k > key ? k : key;
     }
-    key = bkl_max64(key);
+    key = wave_max_all_halves(key);
     const long long piv = (long long)(0xFFFFFFFFu - uint32_t(key));
     const uint32_t *prow = Cadj + piv * cw;
     for (long long i = lane; i < cw; i += 64) E[i] = P[i] & ~prow[i];

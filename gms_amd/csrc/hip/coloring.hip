@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void k_color_select(int64_t n, const int32_t *
         }
         wave_append(take, int32_t(v), frontier, &ctrl->count, n, &ctrl->error);
     }
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_down(mx, o));
+    mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0 && mx) atomicMax(&ctrl->max_pred, mx);
 }
 
@@ -133,7 +133,7 @@ struct ColorJp {
             const uint32_t free = ~bits[w];
             if (free) best = min(best, w * 32 + __ffs(free) - 1);
         }
-        for (int o = kGroup / 2; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o, kGroup));
+        best = wave_min_all<kGroup>(best);
         group_phase();  // (the next vertex of this group zeroes the same words)
         if (lane == 0) give(x, best <= p ? best + 1 : 0, round, q.error);
     }
@@ -200,12 +200,10 @@ __global__ __launch_bounds__(256) void k_cv_rows(int64_t n, const int64_t *__res
         }
         for (int64_t j = j0 + lane; j < j1; j += kGroup) arcs += color[adj[j]] == c ? 1 : 0;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        arcs += __shfl_down(arcs, o);
-        invalid += __shfl_down(invalid, o);
-        mx = max(mx, (unsigned long long)__shfl_down((long long)mx, o));
-        deg = max(deg, (unsigned long long)__shfl_down((long long)deg, o));
-    }
+    arcs = wave_sum(arcs);
+    invalid = wave_sum(invalid);
+    mx = wave_max(mx);
+    deg = wave_max(deg);
     if ((threadIdx.x & 63) == 0) {
         if (arcs) atomicAdd(&acc[kAccArcs], arcs);
         if (invalid) atomicAdd(&acc[kAccInvalid], invalid);
@@ -225,13 +223,13 @@ __global__ __launch_bounds__(256) void k_cv_long(const int64_t *__restrict__ off
         const int64_t j1 = off[v + 1];
         for (int64_t j = off[v] + tid; j < j1; j += threads) arcs += color[adj[j]] == c ? 1 : 0;
     }
-    for (int o = 32; o > 0; o >>= 1) arcs += __shfl_down(arcs, o);
+    arcs = wave_sum(arcs);
     if ((threadIdx.x & 63) == 0 && arcs) atomicAdd(&acc[kAccArcs], arcs);
 }
 __global__ __launch_bounds__(256) void k_cv_distinct(int64_t words, const uint32_t *__restrict__ present, unsigned long long *__restrict__ acc) {
     unsigned long long c = 0;
     for (int64_t w = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; w < words; w += int64_t(gridDim.x) * blockDim.x) c += __popc(present[w]);
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(&acc[kAccDistinct], c);
 }
 

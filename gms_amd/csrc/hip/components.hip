@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void k_cc_link(Src src, int64_t n, const int64
             if (src.keep(j)) cc_link(parent, v, adj[j], cap, &acc->error);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) examined += __shfl_down(examined, o);
+    examined = wave_sum(examined);
     if ((threadIdx.x & 63) == 0 && examined) atomicAdd(&acc->examined, examined);
 }
 
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void k_cc_mask_edges(int64_t n, const int64_t 
                 else if (!mask[twin]) ++kept;
             }
         }
-    for (int o = 32; o > 0; o >>= 1) kept += __shfl_down(kept, o);
+    kept = wave_sum(kept);
     if ((threadIdx.x & 63) == 0 && kept) atomicAdd(&acc->kept, kept);
 }
 
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(kCcSamples) void k_cc_vote(int64_t n, const int32_t
     uint32_t c = 0;
     for (int i = 0; i < kCcSamples; ++i) c += s_label[i] == mine;
     unsigned long long key = ((unsigned long long)c << 32) | (0xffffffffu - uint32_t(mine));
-    for (int o = 32; o > 0; o >>= 1) key = max(key, __shfl_down(key, o));
+    key = wave_max(key);
     if ((t & 63) == 0) s_best[t >> 6] = key;
     __syncthreads();
     if (t == 0) {
@@ -332,11 +332,9 @@ __global__ __launch_bounds__(256) void k_cc_info(int64_t n, const int32_t *__res
         singles += s == 1;
         best = max(best, ((unsigned long long)s << 32) | (0xffffffffu - uint32_t(v)));
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        comps += __shfl_down(comps, o);
-        singles += __shfl_down(singles, o);
-        best = max(best, __shfl_down(best, o));
-    }
+    comps = wave_sum(comps);
+    singles = wave_sum(singles);
+    best = wave_max(best);
     if ((threadIdx.x & 63) == 0 && comps) {
         atomicAdd(&acc->comps, comps);
         if (singles) atomicAdd(&acc->singles, singles);

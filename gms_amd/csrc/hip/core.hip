@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_core_min(int64_t n, const int32_t *__re
         const int32_t d = deg[v];
         if (d > k_done) m = min(m, d);
     }
-    for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_down(m, o));
+    m = wave_min(m);
     if ((threadIdx.x & 63) == 0 && m != INT_MAX) atomicMin(&ctrl->min_deg, m);
 }
 
@@ -217,11 +217,9 @@ __global__ __launch_bounds__(256) void k_oq_reduce(int64_t n, const int32_t *__r
             excess += (unsigned long long)(l - core_number);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        mx = max(mx, (unsigned long long)__shfl_down((long long)mx, o));
-        faulty += __shfl_down(faulty, o);
-        excess += __shfl_down(excess, o);
-    }
+    mx = wave_max(mx);
+    faulty = wave_sum(faulty);
+    excess = wave_sum(excess);
     if ((threadIdx.x & 63) == 0) {
         if (mx) atomicMax(&acc[0], mx);
         if (faulty) atomicAdd(&acc[1], faulty);

@@ -80,16 +80,13 @@ __global__ __launch_bounds__(256) void k_validate(int64_t n, const int64_t *__re
             }
         }
     }
-    for (int s = 32; s > 0; s >>= 1) {
-        elems += __shfl_down(elems, s);
-        flags |= __shfl_down(flags, s);
-        const unsigned long long o = __shfl_down(maxdeg, s);
-        maxdeg = o > maxdeg ? o : maxdeg;
-        f0 += __shfl_down(f0, s);
-        r0 += __shfl_down(r0, s);
-        f1 += __shfl_down(f1, s);
-        r1 += __shfl_down(r1, s);
-    }
+    elems = wave_sum(elems);
+    flags = wave_or(flags);
+    maxdeg = wave_max(maxdeg);
+    f0 = wave_sum(f0);
+    r0 = wave_sum(r0);
+    f1 = wave_sum(f1);
+    r1 = wave_sum(r1);
     if (lane == 0) {
         if (flags) atomicOr(&acc[0], (unsigned long long)flags);
         if (elems) atomicAdd(&acc[1], elems);
@@ -135,10 +132,8 @@ __global__ __launch_bounds__(256) void k_count_parts(int64_t n, const int64_t *_
                 if (nv < hub_limit) ch++; else ct++;
             }
         }
-        for (int s = 32; s > 0; s >>= 1) {
-            ch += __shfl_down(ch, s);
-            ct += __shfl_down(ct, s);
-        }
+        ch = wave_sum(ch);
+        ct = wave_sum(ct);
         if (lane == 0) {
             hcnt[nu] = (ch + 1) & ~1;
             tcnt[nu] = ct;
@@ -481,7 +476,7 @@ __global__ __launch_bounds__(256) void k_core_units(int32_t cap, const int64_t *
             const uint32_t ids = uint32_t(min(i, dplus[v]));
             units += min((ids + 7u) / 8u, (v + 127u) / 128u);
         }
-        for (int s = 32; s > 0; s >>= 1) units += __shfl_down(units, s);
+        units = wave_sum(units);
         if (lane == 0 && units) atomicAdd(&bucket[u / kTcCoreBucket], units);
     }
 }
@@ -495,7 +490,7 @@ __global__ __launch_bounds__(256) void k_tail_split(int64_t n, const int64_t *__
     for (int64_t u = wave0; u < n; u += nwaves) {
         int c = 0;
         for (int64_t j = toff[u] + lane; j < toff[u + 1]; j += 64) c += tadj[j] < limit;
-        for (int s = 32; s > 0; s >>= 1) c += __shfl_down(c, s);
+        c = wave_sum(c);
         if (lane == 0) tsplit[u] = c;
     }
 }
@@ -866,12 +861,7 @@ struct GatherPlan {
 // offset behind the counter's old value
 __device__ __forceinline__ uint32_t claim_units(uint32_t *ctr, uint32_t mine, int lane) {
     if (__ballot(mine != 0) == 0ull) return 0u;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t x = uint32_t(__shfl_up(int(incl), s));
-        if (lane >= s) incl += x;
-    }
+    const uint32_t incl = wave_incl_scan(mine, lane);
     const uint32_t total = uint32_t(__builtin_amdgcn_readlane(int(incl), 63));
     uint32_t base = 0;
     if (lane == 0) base = atomicAdd(ctr, total);
@@ -1042,7 +1032,7 @@ __global__ __launch_bounds__(256) void k_task_lists(int64_t n_heavy, const int32
         if (!FILL && lane == 0 && kept) atomicAdd(&tunits[pos], kept);
     }
     if (!FILL) {
-        for (int s = 32; s > 0; s >>= 1) rev += __shfl_down(rev, s);
+        rev = wave_sum(rev);
         if (lane == 0 && rev) atomicAdd(reversed, rev);
     }
 }

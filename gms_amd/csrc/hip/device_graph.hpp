@@ -7,6 +7,7 @@
 #include "device_buffer.hpp"
 #include "gmsx.h"
 #include "gmsx_internal.hpp"  // gmsx::guard: no exception crosses the C ABI
+#include "wave_ops.hpp"       // every kernel source folds and scans through it
 
 // The A/B switches of the kernel sources ("wrong counts" builds that compile a part of a kernel out to time the rest, GMSX_TC_ONLY)
 // exist in DEVELOPMENT builds only: `make` never defines GMSX_DEV_HOOKS, tools/ab_lib.sh does.  A shipped libgmsx.so cannot be

@@ -25,6 +25,8 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "wave_ops.hpp"
+
 namespace gmsx {
 
 typedef int kc4m_v8i __attribute__((ext_vector_type(8)));
@@ -299,7 +301,7 @@ __global__ __launch_bounds__(NT) void k_kc4_mfma(const uint32_t *__restrict__ po
         }
         __syncthreads();  // every wave is done with s_blk
     }
-    for (int s = 32; s > 0; s >>= 1) total += __shfl_down(total, s);
+    total = wave_sum(total);
     if (lane == 0) red[wave] = total;
     __syncthreads();
     if (tid == 0) {

@@ -861,7 +861,7 @@ __global__ __launch_bounds__(256) void k_kc_small(const int64_t *__restrict__ ho
             for (int i = 0; i < d; ++i) cs += (rows[i] >> lane) & 1u;  // rows[i] is a broadcast read; lanes >= d see zeros
             if (lane < d && rp + cs) atomicAdd(&vcounts[oldid[my]], 2ull * (rp + cs));
             uint32_t ps = rp;
-            for (int sft = 32; sft > 0; sft >>= 1) ps += __shfl_xor(ps, sft);
+            ps = wave_sum_all(ps);
             if (lane == 0 && ps) atomicAdd(&vcounts[oldid[u]], 2ull * ps);
             cnt += rp;
         } else {
@@ -869,7 +869,7 @@ __global__ __launch_bounds__(256) void k_kc_small(const int64_t *__restrict__ ho
         }
         __builtin_amdgcn_wave_barrier();
     }
-    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_down(cnt, s);
+    cnt = wave_sum(cnt);
     if (lane == 0) red[wave] = cnt;
     __syncthreads();
     if (tid == 0) {
@@ -1290,7 +1290,7 @@ __global__ __launch_bounds__(1024) void k_kc_block(const int64_t *__restrict__ h
             }
         }
     }
-    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_down(cnt, s);
+    cnt = wave_sum(cnt);
     if (lane == 0) red[wave] = cnt;
     __syncthreads();
     if (tid == 0) {
@@ -1424,7 +1424,7 @@ __global__ __launch_bounds__(256) void k_kc_generic(const int64_t *__restrict__ 
             }
         }
     }
-    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_down(cnt, s);
+    cnt = wave_sum(cnt);
     if (lane == 0) red[wave] = cnt;
     __syncthreads();
     if (tid == 0) {
@@ -1557,12 +1557,7 @@ __global__ __launch_bounds__(256) void k_kcr_edges(int64_t n_piv, const int32_t 
                 }
             }
             if (MODE >= 1) {
-                int wi = take ? rev_row_words(i) : 0, pre = wi;  // inclusive prefix over the 16 lanes of the group
-#pragma unroll
-                for (int sft = 1; sft < 16; sft <<= 1) {
-                    const int t = __shfl_up(pre, sft, 16);
-                    if (sub >= sft) pre += t;
-                }
+                const int wi = take ? rev_row_words(i) : 0, pre = wave_incl_scan<16>(wi, sub);  // inclusive prefix over the 16 lanes of the group
                 const int tot = __shfl(pre, 15, 16);
                 if (MODE == 2 && i < hc) {
                     const int64_t r = run + pre - wi;
@@ -1598,12 +1593,7 @@ __global__ __launch_bounds__(256) void k_kcr_edges(int64_t n_piv, const int32_t 
                     }
                 }
                 if (MODE >= 1) {
-                    int wi = take ? rev_row_words(i) : 0, pre = wi;
-#pragma unroll
-                    for (int sft = 1; sft < 16; sft <<= 1) {
-                        const int t = __shfl_up(pre, sft, 16);
-                        if (sub >= sft) pre += t;
-                    }
+                    const int wi = take ? rev_row_words(i) : 0, pre = wave_incl_scan<16>(wi, sub);
                     const int tot = __shfl(pre, 15, 16);
                     if (MODE == 2 && k < tc) {
                         const int64_t r = run + pre - wi;
@@ -2374,7 +2364,7 @@ __global__ __launch_bounds__(256) void k_stat_kc_bytes(int64_t n_min, int nparts
             }
         }
     }
-    for (int sft = 32; sft > 0; sft >>= 1) b += __shfl_xor(b, sft);
+    b = wave_sum_all(b);
     if (lane == 0 && b) atomicAdd(out, b);
 }
 

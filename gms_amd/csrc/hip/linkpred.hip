@@ -61,11 +61,7 @@ __device__ __forceinline__ uint32_t load_word(const uint32_t *p) { return __hip_
 // exclusive scan of c over the workgroup (kThreads = 4 waves); *total = the sum.  Every thread calls it.
 __device__ __forceinline__ int block_excl_scan(int c, int *s_w, int *total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = c;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
+    const int x = wave_incl_scan(c, lane);
     if (lane == 63) s_w[wave] = x;
     __syncthreads();
     int base = 0, sum = 0;

@@ -121,7 +121,7 @@ __device__ __forceinline__ void c4_walk(const C4Graph &G, int32_t u, int32_t ru,
             }
         }
         if (PHASE == 2) {
-            for (int o = width >> 1; o > 0; o >>= 1) s += __shfl_down(s, o, width);
+            s = wave_sum(s, width);
             if (lane == 0 && s) atomicAdd(&at[v], s);
         }
     }
@@ -129,12 +129,10 @@ __device__ __forceinline__ void c4_walk(const C4Graph &G, int32_t u, int32_t ru,
 
 // the thread sums of a kernel into the call's block: one 64-bit atomic per wave and value
 __device__ __forceinline__ void c4_flush(C4Thread t, C4Acc *__restrict__ acc) {
-    for (int o = 32; o > 0; o >>= 1) {
-        t.cycles += __shfl_down(t.cycles, o);
-        t.wedges += __shfl_down(t.wedges, o);
-        t.harvested += __shfl_down(t.harvested, o);
-        t.mx = max(t.mx, __shfl_down(t.mx, o));
-    }
+    t.cycles = wave_sum(t.cycles);
+    t.wedges = wave_sum(t.wedges);
+    t.harvested = wave_sum(t.harvested);
+    t.mx = wave_max(t.mx);
     if ((threadIdx.x & 63) == 0) {
         if (t.cycles) atomicAdd(&acc->cycles, t.cycles);
         if (t.wedges) atomicAdd(&acc->wedges, t.wedges);
@@ -145,7 +143,7 @@ __device__ __forceinline__ void c4_flush(C4Thread t, C4Acc *__restrict__ acc) {
 
 // at[u] += the pairs this source harvested (cycles before / after its clean walk): one atomic per wave
 __device__ __forceinline__ void c4_source_share(unsigned long long pairs, int32_t u, unsigned long long *__restrict__ at) {
-    for (int o = 32; o > 0; o >>= 1) pairs += __shfl_down(pairs, o);
+    pairs = wave_sum(pairs);
     if ((threadIdx.x & 63) == 0 && pairs) atomicAdd(&at[u], pairs);
 }
 
@@ -167,10 +165,8 @@ __global__ __launch_bounds__(256) void k_c4_classify(C4Graph G, int32_t *__restr
                 b += G.off[v + 1] - G.off[v];
             }
         }
-        for (int o = kGroup / 2; o > 0; o >>= 1) {
-            l += __shfl_down(l, o, kGroup);
-            b += __shfl_down(b, o, kGroup);
-        }
+        l = wave_sum<kGroup>(l);
+        b = wave_sum<kGroup>(b);
         if (lane == 0) {
             later[u] = l;
             bound[u] = b;
@@ -195,10 +191,8 @@ __global__ __launch_bounds__(256) void k_c4_classify_long(C4Graph G, int32_t *__
                 b += G.off[v + 1] - G.off[v];
             }
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            l += __shfl_down(l, o);
-            b += __shfl_down(b, o);
-        }
+        l = wave_sum(l);
+        b = wave_sum(b);
         if ((threadIdx.x & 63) == 0) {
             s_l[threadIdx.x >> 6] = l;
             s_b[threadIdx.x >> 6] = b;
@@ -456,7 +450,7 @@ struct U128 {
     }
 };
 __device__ __forceinline__ void wave_store(U128 v, unsigned long long *__restrict__ out) {
-    for (int o = 32; o > 0; o >>= 1) v.add(__shfl_down(v.lo, o), __shfl_down(v.hi, o));
+    wave_fold2(v.lo, v.hi, [&v](unsigned long long &, unsigned long long &, unsigned long long lo, unsigned long long hi) { v.add(lo, hi); });
     if ((threadIdx.x & 63) == 0) {
         out[0] = v.lo;
         out[1] = v.hi;

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void k_ms_pull_rows(MsArgs<W> a, const int32_t
                     }
                     u64 rest = 0;
                     for (int k = 0; k < W; ++k) {
-                        for (int o = WIDTH / 2; o > 0; o >>= 1) acc[k] |= __shfl_xor(acc[k], o, WIDTH);
+                        acc[k] = wave_or_all<WIDTH>(acc[k]);
                         rest |= need[k] & ~acc[k];
                     }
                     if (grp.ballot(rest == 0) & 1ull) break;
@@ -375,10 +375,8 @@ __global__ __launch_bounds__(256) void k_ms_sums(int64_t n, const int32_t *__res
         sum += u64(max(rv, 0));
         mx = max(mx, fv);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_down(sum, o);
-        mx = max(mx, __shfl_down(mx, o));
-    }
+    sum = wave_sum(sum);
+    mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0 && sum) {
         atomicAdd(&out->reach_sum, sum);
         atomicMax(&out->max_far, mx);

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void k_oq_later(int64_t n, const int64_t *__re
         }
         const bool parked = cnt < 0;
         if (parked) cnt = 0;
-        for (int o = kGroup / 2; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, kGroup);
+        cnt = wave_sum<kGroup>(cnt);
         if (v < n && lane == 0 && !parked) later[v] = cnt;
     }
 }
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void k_oq_later_long(const int64_t *__restrict
         const int64_t j0 = off[v], j1 = off[v + 1];
         int32_t cnt = 0;
         for (int64_t j = j0 + tid; j < j1; j += threads) cnt += rank[adj[j]] > rv ? 1 : 0;
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+        cnt = wave_sum(cnt);
         if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&later[v], cnt);
     }
 }

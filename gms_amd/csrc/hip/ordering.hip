@@ -44,10 +44,8 @@ __global__ __launch_bounds__(256) void k_adg_sum(int64_t n, const int32_t *__res
             s += (unsigned long long)deg[v];
             ++c;
         }
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_down(s, o);
-        c += __shfl_down(c, o);
-    }
+    s = wave_sum(s);
+    c = wave_sum(c);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
         red[wave * 2] = s;

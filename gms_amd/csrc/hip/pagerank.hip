@@ -54,21 +54,6 @@ struct PrCtrl {
 
 __host__ __device__ inline int pr_class(int64_t len) { return len <= 0 ? 0 : len <= kPrLaneRow ? 1 : len <= kPrGroupRow ? 2 : 3; }
 
-// the fixed tree of a workgroup of 64 kWaves threads; EVERY thread calls it; the total is returned to thread 0 (0.0 elsewhere)
-template <int kWaves>
-__device__ __forceinline__ double block_sum(double x, double *s_w) {
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = x;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) {
-        r = s_w[0];
-        for (int w = 1; w < kWaves; ++w) r += s_w[w];
-    }
-    __syncthreads();
-    return r;
-}
-
 // ---- the classes ---------------------------------------------------------------------------------------------------------------------------
 
 // cnt[c * nb + b] = vertices of class c among the 256 of block b
@@ -247,7 +232,7 @@ __global__ __launch_bounds__(256) void k_pr_group(PrArgs<S> a, int64_t lo, int64
         const int64_t j0 = a.off[u], j1 = a.off[u + 1];
         double sum = 0.0;
         for (int64_t j = j0 + lane; j < j1; j += kPrGroup) sum += double(a.contrib[a.adj[j]]);
-        for (int o = kPrGroup / 2; o > 0; o >>= 1) sum += __shfl_down(sum, o, kPrGroup);
+        sum = wave_sum<kPrGroup>(sum);
         if (lane == 0) e += pr_finish<S, kDangling, kStore>(a, u, sum, j1 - j0, dd, &nw);
     }
     e = block_sum<4>(e, s_w);
@@ -279,7 +264,7 @@ __global__ __launch_bounds__(256) void k_pr_long(PrArgs<S> a, int64_t lo, int64_
         }
         double sum = 0.0;
         for (int64_t j = c0 + lane; j < c1; j += 64) sum += double(a.contrib[a.adj[j]]);
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
+        sum = wave_sum(sum);
         if (lane == 0) a.slots[s] = sum;
     }
 }
@@ -362,11 +347,7 @@ __global__ __launch_bounds__(256) void k_pr_final(int64_t n, const S *__restrict
         m = x;
         at = int32_t(v);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double m2 = __shfl_down(m, o);
-        const int32_t a2 = __shfl_down(at, o);
-        pr_best(m, at, m2, a2);
-    }
+    wave_fold2(m, at, pr_best);
     if ((threadIdx.x & 63) == 0) {
         s_m[threadIdx.x >> 6] = m;
         s_a[threadIdx.x >> 6] = at;
@@ -391,11 +372,7 @@ __global__ __launch_bounds__(1024) void k_pr_final_reduce(int64_t cells, const d
         x += fsum[i];
         pr_best(m, at, fmax[i], farg[i]);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const double m2 = __shfl_down(m, o);
-        const int32_t a2 = __shfl_down(at, o);
-        pr_best(m, at, m2, a2);
-    }
+    wave_fold2(m, at, pr_best);
     if ((threadIdx.x & 63) == 0) {
         s_m[threadIdx.x >> 6] = m;
         s_a[threadIdx.x >> 6] = at;

@@ -62,7 +62,7 @@ __device__ __forceinline__ double wave_pair_similarity(const int64_t *__restrict
                 }
             }
         }
-        for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s);
+        sum = wave_sum_all(sum);
         r = sum;
     } else {
         const double cnt = double(wave_intersect_count(a, la, b, lb, lane));

@@ -97,7 +97,7 @@ struct SsspRelax {
     // every thread, converged, at the end of a kernel: one add per wave
     __device__ __forceinline__ void finish() const {
         unsigned long long sum = improved;
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
+        sum = wave_sum(sum);
         if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&ctrl->relax, sum);
         improved = 0;
     }
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_sssp_next_min(int64_t n, const D *__res
         const D d = dist[v];
         if (d != DistInf<D>::value && (long long)d >= from) best = min(best, (unsigned long long)d);
     }
-    for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_down(best, o));
+    best = wave_min(best);
     if ((threadIdx.x & 63) == 0 && best != ~0ull) atomicMin(&ctrl->next_min, best);
 }
 
@@ -167,12 +167,10 @@ __global__ __launch_bounds__(256) void k_sssp_info(int64_t n, const int64_t *__r
             mx = max(mx, (unsigned long long)d);
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        reached += __shfl_down(reached, o);
-        arcs += __shfl_down(arcs, o);
-        dsum += __shfl_down(dsum, o);
-        mx = max(mx, __shfl_down(mx, o));
-    }
+    reached = wave_sum(reached);
+    arcs = wave_sum(arcs);
+    dsum = wave_sum(dsum);
+    mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0 && reached) {
         atomicAdd(&acc->reached, reached);
         atomicAdd(&acc->arcs, arcs);
@@ -245,11 +243,9 @@ __global__ __launch_bounds__(256) void k_sssp_pull(int64_t n, const int64_t *__r
             ++untight;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        violated += __shfl_down(violated, o);
-        untight += __shfl_down(untight, o);
-        wrong += __shfl_down(wrong, o);
-    }
+    violated = wave_sum(violated);
+    untight = wave_sum(untight);
+    wrong = wave_sum(wrong);
     if ((threadIdx.x & 63) == 0) {
         if (violated) atomicAdd(&acc->violated, violated);
         if (untight) atomicAdd(&acc->untight, untight);
@@ -301,10 +297,8 @@ __global__ __launch_bounds__(256) void k_weights_check(int64_t n, int64_t nnz, c
         }
         if (a >= off[v + 1] || int64_t(adj[a]) != u || wgt[a] != w) acc->bad_twin = 1;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_down(sum, o);
-        wmax = max(wmax, __shfl_down(wmax, o));
-    }
+    sum = wave_sum(sum);
+    wmax = wave_max(wmax);
     if ((threadIdx.x & 63) == 0 && sum) {
         atomicAdd(&acc->sum, sum);
         atomicMax(&acc->wmax, wmax);

@@ -363,7 +363,7 @@ __device__ __forceinline__ void stage_item(const TaskList ent, int ne, int tid, 
     __syncthreads();
 }
 __device__ __forceinline__ void block_add(unsigned long long cnt, unsigned long long *red, int lane, int wave, int tid, unsigned long long *__restrict__ acc) {
-    for (int s = 32; s > 0; s >>= 1) cnt += __shfl_down(cnt, s);
+    cnt = wave_sum(cnt);
     if (lane == 0) red[wave] = cnt;
     __syncthreads();
     if (tid == 0) {
@@ -923,7 +923,7 @@ __global__ __launch_bounds__(1024) void k_tc_core(const uint32_t *__restrict__ b
     }
     const int lane = lane_id();
     unsigned long long total = cnt;
-    for (int sft = 32; sft > 0; sft >>= 1) total += __shfl_down(total, sft);
+    total = wave_sum(total);
     if (lane == 0) red[wave] = total;
     __syncthreads();
     if (wave == 0 && lane == 0) {
@@ -988,11 +988,9 @@ __global__ __launch_bounds__(256) void k_tc_stats(const int64_t *__restrict__ ho
             probes += hv + tv;  // v's ids, each compared with u's
         }
     }
-    for (int s = 32; s > 0; s >>= 1) {
-        units += __shfl_down(units, s);
-        probes += __shfl_down(probes, s);
-        bytes += __shfl_down(bytes, s);
-    }
+    units = wave_sum(units);
+    probes = wave_sum(probes);
+    bytes = wave_sum(bytes);
     if (lane == 0) {
         if (units) atomicAdd(&out[0], units);
         if (probes) atomicAdd(&out[1], probes);
@@ -1023,10 +1021,8 @@ __global__ __launch_bounds__(256) void k_tc_item_stats(const int64_t *__restrict
             probes += slots(d);
         }
     }
-    for (int s = 32; s > 0; s >>= 1) {
-        probes += __shfl_down(probes, s);
-        bytes += __shfl_down(bytes, s);
-    }
+    probes = wave_sum(probes);
+    bytes = wave_sum(bytes);
     if (lane == 0) {
         if (probes) atomicAdd(&out[1], probes);
         if (bytes) atomicAdd(&out[2], bytes);
@@ -1104,13 +1100,11 @@ __global__ __launch_bounds__(256) void k_tc_breakdown(const int64_t *__restrict_
     }
     for (int k = 0; k < 15; ++k) {
         unsigned long long x = c[k];
-        for (int s = 32; s > 0; s >>= 1) x += __shfl_down(x, s);
+        x = wave_sum(x);
         if (lane == 0 && x) atomicAdd(&out[k], x);
     }
-    for (int s = 32; s > 0; s >>= 1) {
-        lines += __shfl_down(lines, s);
-        partial += __shfl_down(partial, s);
-    }
+    lines = wave_sum(lines);
+    partial = wave_sum(partial);
     if (lane == 0 && lines) atomicAdd(&out[18], 128ull * lines);
     if (lane == 0 && partial) atomicAdd(&out[19], partial);
 }
@@ -1146,10 +1140,8 @@ __global__ __launch_bounds__(256) void k_tc_comember_keys(const TaskList htask, 
             units += d & 0x3fffffull;
         }
     }
-    for (int sft = 32; sft > 0; sft >>= 1) {
-        ents += __shfl_xor(ents, sft);
-        units += __shfl_xor(units, sft);
-    }
+    ents = wave_sum_all(ents);
+    units = wave_sum_all(units);
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(&sums[0], ents);
         atomicAdd(&sums[1], units);
@@ -1158,7 +1150,7 @@ __global__ __launch_bounds__(256) void k_tc_comember_keys(const TaskList htask, 
 __global__ __launch_bounds__(256) void k_tc_sum_u32(const uint32_t *__restrict__ v, unsigned long long n, unsigned long long *__restrict__ out) {
     unsigned long long t = 0;
     for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) t += v[i];
-    for (int sft = 32; sft > 0; sft >>= 1) t += __shfl_xor(t, sft);
+    t = wave_sum_all(t);
     if ((threadIdx.x & 63) == 0) atomicAdd(out, t);
 }
 __global__ __launch_bounds__(256) void k_tc_row_hist(const int64_t *__restrict__ hoff, const uint16_t *__restrict__ hadj,

@@ -171,10 +171,8 @@ __global__ __launch_bounds__(256) void k_bfs_bottom_up(int64_t n, const int64_t 
         }
         wave_append(more, int32_t(v), list, &ctrl->bu_list, n, &ctrl->error);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        awake += __shfl_down(awake, o);
-        deg += __shfl_down(deg, o);
-    }
+    awake = wave_sum(awake);
+    deg = wave_sum(deg);
     if ((threadIdx.x & 63) == 0 && awake) {
         atomicAdd(&ctrl->awake, awake);
         atomicAdd(&ctrl->awake_deg, deg);
@@ -214,10 +212,8 @@ __global__ __launch_bounds__(256) void k_bfs_bottom_up_rows(int64_t n, const int
             }
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        awake += __shfl_down(awake, o);
-        deg += __shfl_down(deg, o);
-    }
+    awake = wave_sum(awake);
+    deg = wave_sum(deg);
     if ((threadIdx.x & 63) == 0 && awake) {
         atomicAdd(&ctrl->awake, awake);
         atomicAdd(&ctrl->awake_deg, deg);
@@ -267,12 +263,10 @@ __global__ __launch_bounds__(256) void k_bfs_info(int64_t n, const int64_t *__re
             todo &= ~same;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        reached += __shfl_down(reached, o);
-        arcs += __shfl_down(arcs, o);
-        dsum += __shfl_down(dsum, o);
-        mx = max(mx, __shfl_down(mx, o));
-    }
+    reached = wave_sum(reached);
+    arcs = wave_sum(arcs);
+    dsum = wave_sum(dsum);
+    mx = wave_max(mx);
     if (lane == 0 && reached) {
         atomicAdd(&acc->reached, reached);
         atomicAdd(&acc->arcs, arcs);
@@ -292,11 +286,9 @@ __global__ __launch_bounds__(256) void k_bfs_levels(int64_t n, const int32_t *__
         sum += s;
         best = max(best, ((unsigned long long)s << 32) | (0xffffffffu - uint32_t(d)));
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        nonempty += __shfl_down(nonempty, o);
-        sum += __shfl_down(sum, o);
-        best = max(best, __shfl_down(best, o));
-    }
+    nonempty = wave_sum(nonempty);
+    sum = wave_sum(sum);
+    best = wave_max(best);
     if ((threadIdx.x & 63) == 0 && nonempty) {
         atomicAdd(&acc->nonempty, nonempty);
         atomicAdd(&acc->hist_sum, sum);
@@ -426,7 +418,7 @@ __global__ __launch_bounds__(256) void k_bc_rows(BcArgs a, int32_t lo, int32_t h
         const double sx = kDelta ? a.sigma[x] : 0.0;
         double part = 0.0;
         for (int64_t j = j0 + lane; j < j1; j += kGroup) part += bc_term<kDelta>(a, a.adj[j], d, sx);
-        for (int o = kGroup / 2; o > 0; o >>= 1) part += __shfl_down(part, o, kGroup);
+        part = wave_sum<kGroup>(part);
         if (lane == 0) bc_store<kDelta>(a, x, part);
     }
 }
@@ -456,7 +448,7 @@ __global__ __launch_bounds__(256) void k_bc_long(BcArgs a, int32_t d) {
         const double sx = kDelta ? a.sigma[x] : 0.0;
         double part = 0.0;
         for (int64_t j = c0 + lane; j < c1; j += 64) part += bc_term<kDelta>(a, a.adj[j], d, sx);
-        for (int o = 32; o > 0; o >>= 1) part += __shfl_down(part, o);
+        part = wave_sum(part);
         if (lane == 0) a.slots[s] = part;
     }
 }

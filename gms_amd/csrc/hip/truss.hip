@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void k_truss_support(int64_t m, const int64_t 
             continue;
         }
         uint32_t c = intersect_share(off, adj, eu[e], ev[e], lane, kGroup);
-        for (int o = kGroup / 2; o > 0; o >>= 1) c += __shfl_down(c, o, kGroup);
+        c = wave_sum<kGroup>(c);
         if (lane == 0) sup[e] = int32_t(c);
     }
 }
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void k_truss_support_long(const int64_t *__res
     for (int64_t i = blockIdx.x; i < nlong; i += gridDim.x) {
         const int32_t e = longs[i];
         uint32_t c = intersect_share(off, adj, eu[e], ev[e], threadIdx.x, blockDim.x);
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+        c = wave_sum(c);
         if ((threadIdx.x & 63) == 0 && c) atomicAdd(&sup[e], int32_t(c));
     }
 }
@@ -174,10 +174,8 @@ __global__ __launch_bounds__(256) void k_truss_reduce(int64_t m, const int32_t *
         mx = max(mx, s);
         if (rnd) rnd[e] = -1;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_down(sum, o);
-        mx = max(mx, __shfl_down(mx, o));
-    }
+    sum = wave_sum(sum);
+    mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0) {
         if (sum) atomicAdd(&acc->sum, sum);
         if (mx) atomicMax(&acc->max_sup, mx);
@@ -195,7 +193,7 @@ __global__ __launch_bounds__(256) void k_truss_min(int64_t m, const int32_t *__r
     int32_t mn = INT_MAX;
     for (int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < m; e += int64_t(gridDim.x) * blockDim.x)
         if (rnd[e] < 0) mn = min(mn, sup[e]);
-    for (int o = 32; o > 0; o >>= 1) mn = min(mn, __shfl_down(mn, o));
+    mn = wave_min(mn);
     if ((threadIdx.x & 63) == 0 && mn != INT_MAX) atomicMin(&ctrl->min_sup, mn);
 }
 
