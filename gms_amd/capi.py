@@ -49,6 +49,7 @@ SYMBOLS = [
     "gmsx_pagerank", "gmsx_pagerank_residual",
     "gmsx_csr_weights", "gmsx_csr_generate_weighted", "gmsx_csr_from_weighted_edges", "gmsx_csr_load_weighted", "gmsx_csr_save_wsg",
     "gmsx_csr_from_arrays_weighted", "gmsx_graph_set_weights", "gmsx_graph_has_weights", "gmsx_sssp", "gmsx_sssp_verify",
+    "gmsx_min_spanning_forest",
     "gmsx_cycle4_count", "gmsx_cycle4_partial", "gmsx_motif_census4",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -204,6 +205,17 @@ class SsspInfo(C.Structure):
 class SsspCheck(C.Structure):
     _fields_ = [("violated_arcs", C.c_int64), ("untight", C.c_int64), ("wrong_unreached", C.c_int64), ("source_ok", C.c_int32),
                 ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+MSF_MAXIMUM = 1
+
+
+class MsfInfo(C.Structure):
+    _fields_ = [("edges", C.c_int64), ("total_weight", C.c_int64), ("trees", C.c_int64), ("isolated", C.c_int64), ("largest_tree", C.c_int64),
+                ("min_weight", C.c_int32), ("max_weight", C.c_int32), ("rounds", C.c_int32), ("reserved", C.c_int32)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
@@ -405,6 +417,7 @@ def lib():
     L.gmsx_graph_has_weights.argtypes = [vp]
     L.gmsx_sssp.argtypes = [vp, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(SsspInfo), sp]
     L.gmsx_sssp_verify.argtypes = [vp, C.c_int32, C.c_void_p, C.POINTER(SsspCheck), sp]
+    L.gmsx_min_spanning_forest.argtypes = [vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MsfInfo), sp]
     L.gmsx_cycle4_count.argtypes = [vp, u64p, C.c_void_p, sp]
     L.gmsx_cycle4_partial.argtypes = [vp, C.c_int, C.c_int, u64p, sp]
     L.gmsx_motif_census4.argtypes = [vp, C.POINTER(MotifInfo), sp]
@@ -1198,6 +1211,24 @@ class DeviceGraph:
         _check(lib().gmsx_sssp_verify(self._h, int(source), (d if d.size else np.zeros(1, np.int64)).ctypes.data_as(C.c_void_p), C.byref(out),
                                       C.byref(st)), "gmsx_sssp_verify")
         return (out.as_dict(), st.as_dict()) if stats else out.as_dict()
+
+    def min_spanning_forest(self, maximum=False, want_edges=True, want_mask=False, want_labels=False, stats=False):
+        """gmsx_min_spanning_forest over the attached weights: (u, v, w, mask, label, info[, stats]).  u, v, w: int32[edges], the forest's edges
+        with u < v, ascending by (u, v), or None each; mask: uint8[nnz], 1 on both arcs of every forest edge, or None; label: int32[n], the
+        smallest vertex id of every vertex's tree, or None; info: {edges, total_weight, trees, isolated, largest_tree, min_weight, max_weight,
+        rounds}.  maximum=True: the maximum spanning forest (GMSX_MSF_MAXIMUM)."""
+        n, nnz = self.num_nodes, 2 * self.num_edges
+        eu, ev, ew = (np.zeros(max(n - 1, 1), dtype=np.int32) for _ in range(3)) if want_edges else (None, None, None)
+        mask = np.zeros(max(nnz, 1), dtype=np.uint8) if want_mask else None
+        label = np.zeros(max(n, 1), dtype=np.int32) if want_labels else None
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        info, st = MsfInfo(), Stats()
+        _check(lib().gmsx_min_spanning_forest(self._h, MSF_MAXIMUM if maximum else 0, p(eu), p(ev), p(ew), p(mask), p(label), C.byref(info),
+                                              C.byref(st)), "gmsx_min_spanning_forest")
+        ne = int(info.edges)
+        r = (eu[:ne] if want_edges else None, ev[:ne] if want_edges else None, ew[:ne] if want_edges else None,
+             mask[:nnz] if want_mask else None, label[:n] if want_labels else None, info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
 
     def cycle4_count(self, at_vertex=False, stats=False):
         """gmsx_cycle4_count: the 4-cycles of the graph; with at_vertex=True (cycles, int64[n] — the 4-cycles through every vertex of the

@@ -73,7 +73,11 @@
 //                    .wel / .gr / .wsg keeps its own and an .el gets the generator's; the graph is not relabelled (sssp.cc does not).  Per trial
 //                    "Trial Time", "Source", "Delta", "Buckets" and with -v "Verification" (gmsx_sssp_verify's verdict), then the "@@@" line; after
 //                    the last trial PrintSSSPStats' line.  -d 0 (the default) = the library's choice.  Not sharded (--gpus > 1 is refused).
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  msf [--max]   the minimum (--max: maximum) spanning forest over the weights on the device (gmsx_min_spanning_forest; no reference driver):
+//                    the graph is generated or loaded with its weights as for sssp.  Per trial "Trial Time", "Trees", "Edges", "Total Weight",
+//                    "Rounds" and with -v "Verification" — this driver's own serial Kruskal under the order of gmsx.h (weight, then the smaller
+//                    (min id, max id)) must give the same edge list and total weight —, then the "@@@" line.  Not sharded (--gpus > 1 is refused).
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -118,6 +122,7 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     bool iters_given = false;
     double tol = 1e-4;   // pr -t TOL
     int64_t delta = 0;   // sssp -d DELTA (0: the library's choice)
+    bool maximum = false;  // msf --max
     int error = 0;
 };
 
@@ -159,6 +164,7 @@ Args parse(int argc, char **argv) {
         else if (f == "-q") { if (!need(1)) break; a.q = std::atoll(argv[++i]); if (a.q < 1) a.error = 100; }
         else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; }
         else if (f == "--mono") a.mono = true;
+        else if (f == "--max") a.maximum = true;
         else if (f == "--threshold") { if (!need(1)) break; a.threshold = std::atof(argv[++i]); }
         else if (f == "--eps") { if (!need(1)) break; a.eps = std::atof(argv[++i]); }
         else if (f == "--gpus") { if (!need(1)) break; a.gpus = std::atoi(argv[++i]); if (a.gpus < 1 || a.gpus > 64) a.error = 100; }
@@ -187,6 +193,7 @@ Args parse(int argc, char **argv) {
     const bool traversal = a.kernel == "bfs" || a.kernel == "bc" || a.kernel == "closeness" || a.kernel == "sssp";
     if (!a.error && traversal && (a.gpus > 1 || a.metric_given)) a.error = 100;  // a traversal is global; it has no metric
     if (!a.error && a.kernel == "pr" && a.metric_given) a.error = 100;              // … nor has PageRank
+    if (!a.error && ((a.kernel == "msf" && (a.gpus > 1 || a.metric_given)) || (a.maximum && a.kernel != "msf"))) a.error = 100;  // a forest is global
     if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc" && a.kernel != "closeness" && a.kernel != "pr"))) a.error = 100;
     if (!a.error && ((a.kernel == "sgi") != !a.pattern_file.empty() || (a.mono && a.kernel != "sgi"))) a.error = 100;  // util/command_line.hpp:22: the pattern is required
     if (!a.error && (a.kernel == "lp" || a.kernel == "jp") && lp_metric(a.metric) < 0) a.error = 100;
@@ -200,10 +207,10 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
                 "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE] "
-                "[jp: --metric NAME --threshold X] [bfs, bc, closeness, sssp: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES] [pr: -i ITERS -t TOL] [sssp: -d DELTA]\n", argv0);
+                "[jp: --metric NAME --threshold X] [bfs, bc, closeness, sssp: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES] [pr: -i ITERS -t TOL] [sssp: -d DELTA] [msf: --max]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -935,6 +942,70 @@ int run_sssp(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg, 
     return 0;
 }
 
+// serial Kruskal over the host CSR under the order of gmsx.h: the u < v arcs by (weight — heavier first for the maximum —, u, v), a union-find
+// with path halving; the forest's edges ascending by (u, v)
+std::vector<gmsx::WeightedEdge> host_kruskal(const HostGraph &hg, const int32_t *wgt, bool maximum) {
+    std::vector<gmsx::WeightedEdge> all;
+    for (int64_t u = 0; u < hg.n; ++u)
+        for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j)
+            if (int64_t(hg.adj[j]) > u) all.push_back({int32_t(u), hg.adj[j], wgt[j]});
+    const auto by_uv = [](const gmsx::WeightedEdge &a, const gmsx::WeightedEdge &b) { return a.u != b.u ? a.u < b.u : a.v < b.v; };
+    std::sort(all.begin(), all.end(), [&](const gmsx::WeightedEdge &a, const gmsx::WeightedEdge &b) {
+        return a.w != b.w ? (maximum ? a.w > b.w : a.w < b.w) : by_uv(a, b);
+    });
+    std::vector<int32_t> parent(size_t(hg.n));
+    for (int64_t v = 0; v < hg.n; ++v) parent[size_t(v)] = int32_t(v);
+    const auto find = [&](int32_t x) {
+        while (parent[size_t(x)] != x) x = parent[size_t(x)] = parent[size_t(parent[size_t(x)])];
+        return x;
+    };
+    std::vector<gmsx::WeightedEdge> forest;
+    for (const gmsx::WeightedEdge &e : all) {
+        const int32_t a = find(e.u), b = find(e.v);
+        if (a == b) continue;
+        parent[size_t(std::max(a, b))] = std::min(a, b);
+        forest.push_back(e);
+    }
+    std::sort(forest.begin(), forest.end(), by_uv);
+    return forest;
+}
+
+// the spanning forest (msf) under the usual trial loop; -v: the edge list and the total weight against host_kruskal
+int run_msf(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg, const gmsx_csr *csr) {
+    gmsx::detail::check(gmsx_graph_set_weights(const_cast<gmsx_graph *>(g.device()), gmsx_csr_weights(csr)), "gmsx_graph_set_weights");
+    const uint32_t flags = args.maximum ? uint32_t(GMSX_MSF_MAXIMUM) : 0u;
+    double total_seconds = 0, host_seconds = 0;
+    Timer t;
+    std::vector<gmsx::WeightedEdge> edges, want;
+    gmsx_msf_info info{};
+    for (int64_t it = 0; it < args.trials; ++it) {
+        t.Start();
+        gmsx::min_spanning_forest(g, edges, flags, &info);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        PrintLabel("Trees", std::to_string(info.trees));
+        PrintLabel("Edges", std::to_string(info.edges));
+        PrintLabel("Total Weight", std::to_string(info.total_weight));
+        PrintLabel("Rounds", std::to_string(info.rounds));
+        if (args.verify) {
+            if (want.empty() && hg.n > 0) {
+                t.Start();
+                want = host_kruskal(hg, gmsx_csr_weights(csr), args.maximum);
+                t.Stop();
+                host_seconds = t.Seconds();
+            }
+            int64_t want_weight = 0;
+            for (const gmsx::WeightedEdge &e : want) want_weight += e.w;
+            PrintTime("Host Kruskal", host_seconds);
+            PrintLabel("Verification", edges == want && want_weight == info.total_weight && int64_t(want.size()) == info.edges ? "PASS" : "FAIL");
+        }
+        std::cout << "@@@ msf " << (args.maximum ? "maximum" : "minimum") << std::endl;
+    }
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
 // subgraph matching: the reference's VF2 drivers (subgraphiso_vf2_sequential.cpp:33-51) over gmsx::subgraph_isomorphisms
 int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
     gmsx_csr *pc = nullptr;
@@ -996,7 +1067,7 @@ int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr" && args.kernel != "sssp") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr" && args.kernel != "sssp" && args.kernel != "msf") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -1016,7 +1087,7 @@ int main(int argc, char **argv) {
     t.Start();
     int rc;
     const int relabel = args.kernel == "sgi" ? GMSX_RELABEL_NEVER : GMSX_RELABEL_AUTO;  // the reference's subgraph drivers never relabel
-    if (args.kernel == "sssp")  // WeightedBuilder: the weights of the file, or the generator's; never relabelled (sssp.cc:182-183)
+    if (args.kernel == "sssp" || args.kernel == "msf")  // WeightedBuilder: the weights of the file, or the generator's; never relabelled (sssp.cc:182-183)
         rc = !args.file.empty() ? gmsx_csr_load_weighted(args.file.c_str(), 1, GMSX_RELABEL_NEVER, &csr)
                                 : gmsx_csr_generate_weighted(args.gen == "uniform" ? GMSX_GEN_UNIFORM : GMSX_GEN_KRONECKER, args.scale, args.deg,
                                                              GMSX_RELABEL_NEVER, int(args.threads), &csr);
@@ -1074,8 +1145,8 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr" || args.kernel == "sssp") {
-        const int rc_run = args.kernel == "sssp" ? run_sssp(args, g, hg, csr) : args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr" || args.kernel == "sssp" || args.kernel == "msf") {
+        const int rc_run = args.kernel == "msf" ? run_msf(args, g, hg, csr) : args.kernel == "sssp" ? run_sssp(args, g, hg, csr) : args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
                                                                                                                                         : run_components(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);

@@ -4,20 +4,8 @@
 //   gmsx_jarvis_patrick         the same over the edges {u, v} with metric(N(u), N(v)) >= threshold; no reference counterpart
 // The definitions are those of include/gmsx.h.
 //
-// THE UNION-FIND.  parent[n] (int32, a DevBuf of the call; the handle is not touched), parent[v] = v at the start.  THE ONE RULE: a root is
-// only ever hooked under a SMALLER vertex id — link(u, v) walks to both roots and, where they differ, does atomicCAS(&parent[larger], larger,
-// smaller) at device scope; when the CAS fails (the larger root was hooked meanwhile) it walks again from the two roots it held.  So
-//   - parents only decrease, and every value parent[x] ever holds is an ancestor-or-self of x in every later state (a stale read is still an
-//     ancestor: correctness never depends on freshness);
-//   - the root of a finished tree is the smallest id of its component;
-//   - after a full flatten label[v] is the smallest vertex id of v's component: a fact about the edge set, independent of the arrival order of
-//     the atomics.
-// MEMORY MODEL.  The L2s of the eight XCDs are not coherent for plain loads inside one kernel, and a plain load may be served from a CU's L1 for
-// good.  Every read of parent inside a walk or a retry loop is a relaxed agent-scope atomic load (load_now), every compression write an
-// atomicMin (linking kernels, where other threads hook and compress the same word) or a relaxed agent-scope store (flatten kernels, where a
-// word has one writer).  No loop spins on a cached value, and NO LOOP IS UNBOUNDED: a walk strictly descends, so it takes fewer than n steps; a
-// retry follows a failed CAS, i.e. a root that stopped being one, which happens fewer than n times to the roots one link holds.  Both loops
-// carry the cap n + 64, and exceeding it (memory that is not a parent array any more) raises the call's flag word: GMSX_ERR_KERNEL.
+// THE UNION-FIND (cc_find, cc_link, the flatten and size kernels, their memory model and their caps) is union_find.hpp's: a root is only ever
+// hooked under a SMALLER vertex id, so after a full flatten label[v] is the smallest vertex id of v's component.
 //
 // WORK DISTRIBUTION over CSR rows (k_cc_link, one template over the edge source and the lanes per row): one lane per row below kCcShortRow
 // entries, a 16-lane group per row below CC_WAVE_ROW, a wave per row below CC_WG_ROW, a whole workgroup per row from there on (a hub of 10^5 to
@@ -38,14 +26,13 @@
 // writes 1 to both arcs' bytes — the twin by a binary search of u in row v.  No score array and no edge list exist.  Every edge gets one wave:
 // the workgroup-per-long-edge variant of truss.hip's support pass is not built here.
 //
-// FLATTEN (k_cc_flatten): every vertex walks up to kCcJump steps and stores where it got; a round in which every walk reached a root changes
-// nothing afterwards.  The host reads the flag between launches (a path of 2^20 vertices hooked into one chain needs four rounds).
-// INFO (k_cc_sizes, k_cc_info): size[label[v]] by atomicAdd, one add per distinct label of a wave (in the giant component that is one add per
-// wave); then per root: components, singletons, and the largest component as the maximum of size << 32 | ~label, i.e. ties go to the smaller label.
+// INFO (k_cc_sizes of union_find.hpp, k_cc_info): the sizes per label; then per root: components, singletons, and the largest component as the
+// maximum of size << 32 | ~label, i.e. ties go to the smaller label.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
 #include "frontier_rounds.hpp"  // load_now, store_now, wave_append, kGroup
 #include "pair_similarity.hpp"
+#include "union_find.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -58,15 +45,13 @@ namespace gmsx {
 namespace {
 
 constexpr int kCcShortRow = 16;    // rows below this: one lane
-constexpr int kCcJump = 64;        // steps of one flatten walk
 constexpr int kCcSamples = 1024;   // vertex ids the giant-component vote reads
-constexpr int kCcFlattenMax = 64;  // flatten rounds before the call gives up (every round divides the depth by kCcJump)
 constexpr long long kCcSampleDefault = 2, kCcWaveRowDefault = 256, kCcWgRowDefault = 4096;  // first guesses (gmsx.h, OPTIONS)
 
 // the call's small device block, zeroed per call and read once
 struct CcAcc {
     int32_t error;   // the flag word: a cap was exceeded, an append hit its bound, an arc has no twin
-    int32_t again;   // flatten: a walk ended below its root
+    int32_t again;   // flatten: a walk ended below its root (behind error: union_find.hpp's flatten reads the two words together)
     int32_t giant;   // the label pass B skips, -1 = none
     int32_t nlist[3];  // vertices in the group / wave / workgroup list
     int32_t pad[2];
@@ -75,37 +60,6 @@ struct CcAcc {
     unsigned long long comps, singles;
     unsigned long long best;      // size << 32 | ~label of the largest component
 };
-
-// root of x; compresses by halving on the way (atomicMin: other threads hook and compress the same words, and parents only decrease)
-__device__ __forceinline__ int32_t cc_find(int32_t *__restrict__ parent, int32_t x, uint32_t cap, int32_t *error) {
-    int32_t p = load_now(&parent[x]);
-    for (uint32_t it = 0; p != x; ++it) {
-        if (it > cap) {
-            *error = 1;
-            return x;
-        }
-        const int32_t gp = load_now(&parent[p]);
-        if (gp != p) atomicMin(&parent[x], gp);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
-// the one rule: the larger root goes under the smaller one, or the walk starts again from the two roots just read
-__device__ __forceinline__ void cc_link(int32_t *__restrict__ parent, int32_t u, int32_t v, uint32_t cap, int32_t *error) {
-    int32_t ru = cc_find(parent, u, cap, error), rv = cc_find(parent, v, cap, error);
-    for (uint32_t it = 0; ru != rv; ++it) {
-        if (it > cap) {
-            *error = 1;
-            return;
-        }
-        const int32_t hi = max(ru, rv), lo = min(ru, rv);
-        if (atomicCAS(&parent[hi], hi, lo) == hi) return;
-        ru = cc_find(parent, hi, cap, error);
-        rv = cc_find(parent, lo, cap, error);
-    }
-}
 
 // edge sources of the row kernels
 struct SrcAll {
@@ -164,17 +118,6 @@ __global__ __launch_bounds__(256) void k_cc_link(Src src, int64_t n, const int64
     }
     examined = wave_sum(examined);
     if ((threadIdx.x & 63) == 0 && examined) atomicAdd(&acc->examined, examined);
-}
-
-// position of x in the ascending row [lo, hi) of adj, or -1
-__device__ __forceinline__ int64_t cc_find_in_row(const int32_t *__restrict__ adj, int64_t lo, int64_t hi, int32_t x) {
-    const int64_t end = hi;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (adj[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return (lo < end && adj[lo] == x) ? lo : -1;
 }
 
 // Jarvis–Patrick: wave w takes the arcs w, w + W, …, 64 at a time (a lane resolves the source of each); one score per `u < v` arc, the kept
@@ -258,24 +201,6 @@ __global__ __launch_bounds__(256) void k_cc_mask_edges(int64_t n, const int64_t 
     if ((threadIdx.x & 63) == 0 && kept) atomicAdd(&acc->kept, kept);
 }
 
-// one flatten round: parent[v] = where a walk of at most kCcJump steps got; acc->again when one ended below its root.  Nothing hooks while
-// this runs and parent[v] has one writer, so the roots are fixed and a relaxed agent-scope store is enough.
-__global__ __launch_bounds__(256) void k_cc_flatten(int64_t n, int32_t *__restrict__ parent, CcAcc *__restrict__ acc) {
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    bool again = false;
-    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < n; v += stride) {
-        const int32_t p0 = load_now(&parent[v]);
-        int32_t x = p0, p = load_now(&parent[x]);
-        for (int it = 0; p != x && it < kCcJump; ++it) {
-            x = p;
-            p = load_now(&parent[x]);
-        }
-        if (p != x) again = true;
-        if (x != p0) store_now(&parent[v], x);
-    }
-    if (__ballot(again) && (threadIdx.x & 63) == 0) store_now(&acc->again, 1);
-}
-
 // the giant-component vote: the labels of kCcSamples seeded vertex ids, the most frequent one (ties: the smaller label) into acc->giant.
 // One workgroup of kCcSamples threads; 4 KB + 128 B of LDS.
 __global__ __launch_bounds__(kCcSamples) void k_cc_vote(int64_t n, const int32_t *__restrict__ parent, CcAcc *__restrict__ acc) {
@@ -298,24 +223,6 @@ __global__ __launch_bounds__(kCcSamples) void k_cc_vote(int64_t n, const int32_t
     if (t == 0) {
         for (int i = 1; i < kCcSamples / 64; ++i) key = max(key, s_best[i]);
         acc->giant = int32_t(0xffffffffu - uint32_t(key));
-    }
-}
-
-// size[label[v]] += 1, one add per distinct label of a wave
-__global__ __launch_bounds__(256) void k_cc_sizes(int64_t n, const int32_t *__restrict__ label, int32_t *__restrict__ size) {
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    const int64_t end = ((n + 63) / 64) * 64;
-    const int lane = threadIdx.x & 63;
-    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride) {
-        const int32_t l = v < n ? label[v] : -1;
-        unsigned long long todo = __ballot(l >= 0);
-        while (todo) {  // at most 64 turns: every turn retires the lanes of one label
-            const int first = __ffsll((long long)todo) - 1;
-            const int32_t l0 = __shfl(l, first);
-            const unsigned long long same = __ballot(l == l0) & todo;
-            if (lane == first) atomicAdd(&size[l0], int32_t(__popcll(same)));
-            todo &= ~same;
-        }
     }
 }
 
@@ -366,25 +273,6 @@ void link_rows(const Src &src, const gmsx_graph *g, const CcLists &l, int64_t lo
     hipLaunchKernelGGL((k_cc_link<Src, 256>), dim3(grid), dim3(256), 0, s, src, n, g->off, g->adj, l.b.as<const int32_t>(), 2, l.cap_b, int64_t(INT64_MAX),
                        lo, hi, use_giant, parent, acc);
     *launches += 4;
-}
-
-// pointer jumping until a round changes nothing; the flag is read between launches
-int flatten(int64_t n, int32_t *parent, CcAcc *acc, int cus, hipStream_t s, int *launches, int32_t *rounds) {
-    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
-    for (int r = 1; r <= kCcFlattenMax; ++r) {
-        GMSX_HIP(hipMemsetAsync(&acc->again, 0, sizeof(int32_t), s));
-        hipLaunchKernelGGL(k_cc_flatten, dim3(sweep), dim3(256), 0, s, n, parent, acc);
-        ++*launches;
-        int32_t flags[2] = {0, 0};  // error, again
-        GMSX_HIP(hipMemcpyAsync(flags, acc, sizeof flags, hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipStreamSynchronize(s));
-        if (flags[0]) return GMSX_ERR_KERNEL;
-        if (!flags[1]) {
-            if (rounds) *rounds = r;
-            return GMSX_OK;
-        }
-    }
-    return GMSX_ERR_KERNEL;
 }
 
 // Both entry points.  mask_in (host, nnz) for kSrcMask; mask_out (host, nnz, or null) for kSrcJp.
@@ -459,7 +347,7 @@ int components(const gmsx_graph *g, int source, const uint8_t *mask_in, int metr
                                    int64_t(INT64_MAX), int64_t(0), sample, 0, parent, acc);
             ++launches;
             if (source == kSrcAll) {  // the skip is valid only where every kept edge is visible from both sides
-                if (int rc = flatten(n, parent, acc, cus, s, &launches, nullptr)) return rc;
+                if (int rc = flatten(n, parent, &acc->error, cus, s, &launches, nullptr)) return rc;
                 hipLaunchKernelGGL(k_cc_vote, dim3(1), dim3(kCcSamples), 0, s, n, parent, acc);
                 ++launches;
                 use_giant = 1;
@@ -469,7 +357,7 @@ int components(const gmsx_graph *g, int source, const uint8_t *mask_in, int metr
         else link_rows(masked, g, l, sample, int64_t(INT64_MAX), 0, parent, acc, cus, s, &launches);
     }
     int32_t passes = 0;
-    if (int rc = flatten(n, parent, acc, cus, s, &launches, &passes)) return rc;
+    if (int rc = flatten(n, parent, &acc->error, cus, s, &launches, &passes)) return rc;
     // ---- the info reduction
     GMSX_HIP(hipEventRecord(c.ev[2], s));
     hipLaunchKernelGGL(k_cc_sizes, dim3(sweep), dim3(256), 0, s, n, parent, d_size.as<int32_t>());

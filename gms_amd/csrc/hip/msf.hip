@@ -1,0 +1,553 @@
+// Minimum (or maximum) spanning forest on gfx950 over the uploaded CSR and its attached weights: Borůvka's rounds on the device union-find.
+//   gmsx_min_spanning_forest   the forest's edges ascending by (u, v), its arc mask, label[v] = smallest vertex id of v's tree, and the info
+//                              block; no reference counterpart.  The definitions are those of include/gmsx.h.
+//
+// THE ORDER.  key(e) = (w, lo, hi) for e = {lo, hi}, lo < hi, compared lexicographically; GMSX_MSF_MAXIMUM puts the heavier edge first and
+// still breaks ties by the smaller (lo, hi).  On the device the weight travels as k0 = w (minimum) or ~w (maximum), an unsigned word of which
+// the smaller one always comes first; ~0 is no edge (weights lie in [1, 2^31 - 1]).  The CSR has no parallel edges and no self loops, so the
+// order is strict and the forest is unique: Kruskal's output under the order, and the output of the rounds below.
+// INSIDE ONE ROW the order needs two words only: for the arcs v - x of a fixed v, (min(v, x), max(v, x)) ascends with x — (x, v) for x < v, then
+// (v, x) for x > v —, so the first crossing arc of v's row in the order is the minimum of k0 << 32 | x, one wave_min (wave_ops.hpp) per group.
+//
+// A ROUND is four steps with kernel boundaries between them; nothing spins and no workgroup waits for another.  comp = the parent array of
+// union_find.hpp, flattened: comp[v] is the root of v's component, read with plain loads (an earlier kernel wrote it).
+//   (a) search   k_msf_search<WIDTH>, THE HOT PASS: every live vertex v finds the first arc j of its row in the order with comp[adj[j]] !=
+//                comp[v] (the weight is loaded for crossing arcs only).  Rows are binned by their length as k_cc_link's: a lane per row below
+//                kMsfShortRow entries, a 16-lane group below MSF_WAVE_ROW, a wave below MSF_WG_ROW, a whole workgroup from there on — no lane
+//                walks a long row alone.  The result goes to best[v] and root[v], one writer each, and the writer folds k0 into the
+//                component's word with an integer atomicMin (cw[root]; for the maximum that is the atomicMax of w).  A vertex that finds no
+//                crossing arc is dead for good — components only merge.  Under MSF_PRUNE = 1 it is not appended to the next round's live list, so
+//                that later rounds touch the shrinking border only; under MSF_PRUNE = 0, THE DEFAULT, the lists stay as classified and every
+//                vertex is searched every round — on the four graphs measured the appends cost more than the arcs they save.
+//   (b) minimum  k_msf_pair: the live vertices whose k0 equals their component's fold lo << 32 | hi into cpair[root], a 64-bit atomicMin.
+//   (c) apply    k_msf_apply: the one vertex of a component whose (k0, lo, hi) is the component's is its WINNER (the chosen edge has one end
+//                in the component).  It marks both arc bytes of the edge in the nnz-byte mask — its own arc and the twin found by
+//                cc_find_in_row; two components that picked the same edge write the same bytes — calls cc_link(lo, hi) and counts the pick.
+//                It compares against root[v], cw and cpair, which no thread of this kernel writes; parent is only walked, never compared.
+//   (d) flatten  union_find.hpp's pointer jumping to the roots, so that comp is flat again.
+// cw and cpair are one buffer set to ones before every round.  The host loop ends at a round without picks (under the option TIMING every
+// round prints its live vertices, the arcs it examined and its winners).  Every component that has a
+// crossing edge picks its first one, so the components after round r are a fact about (graph, weights, flags), and so is the number of
+// rounds; every round at least doubles the smallest component that still grows: at most 64 rounds, else GMSX_ERR_KERNEL.
+// WHY THE PICKS ARE A FOREST.  Under a strict order the first crossing edge of a component belongs to the unique forest (the cut property),
+// and a cycle among one round's picks would need an edge that is not the first of the component that picked it.  Only (lo, hi) keeps unit
+// weights acyclic.  The union-find does not depend on it: a link inside one component changes nothing.
+//
+// AFTER THE ROUNDS.  k_msf_count: per row the marked `u < v` arcs (and, in the same pass, Σ w, min w, max w over them and the marked `u > v`
+// arcs, which must be as many); a scan of the counts; k_msf_fill: every row compacts its marked arcs chunk by chunk with a ballot, in CSR
+// order — the edge list ascends by (u, v) without a sort.  k_cc_sizes and k_msf_info give trees, isolated and largest_tree.  The host checks
+// edges == n - trees before anything is written.
+// STATE: parent, root, sizes, the live lists (2 x their capacities, at most 4 n + 6 entries) as 32-bit words, best, cpair, the row counts and
+// their scan as 64-bit words, cw, the nnz-byte mask, and up to 3 (n - 1) words of edges — O(n) words and a byte per arc, DevBufs of the call.
+#include "device_buffer.hpp"
+#include "device_graph.hpp"
+#include "frontier_rounds.hpp"  // load_now, wave_append, append_checked, RowGroup, kGroup, kLongRow
+#include "union_find.hpp"
+
+#include <algorithm>
+#include <climits>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+namespace gmsx {
+
+namespace {
+
+constexpr int kMsfShortRow = 16;  // rows below this: one lane
+constexpr int kMsfMaxRounds = 64;
+constexpr long long kMsfWaveRowDefault = 256, kMsfWgRowDefault = 4096;  // first guesses (gmsx.h, OPTIONS)
+constexpr long long kMsfPruneDefault = 0;  // measured: the live lists cost more than they save on every graph tried
+constexpr unsigned long long kNoArc = ~0ull;
+
+__device__ __forceinline__ unsigned long long load_now(const unsigned long long *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the call's small device block, mirrored to the host after every round
+struct MsfCtrl {
+    int32_t error;       // the flag word: a cap was exceeded, an append hit its bound, an arc has no twin
+    int32_t again;       // flatten: a walk ended below its root (behind error: union_find.hpp's flatten reads the two words together)
+    int32_t picks;       // winners of the round (an edge two components picked counts twice)
+    int32_t pad;
+    int32_t count[2][4];  // vertices in the lane / group / wave / workgroup list of either buffer
+    unsigned long long examined;  // arcs the search pass looked at
+};
+
+// the four live lists: list b of buffer i is lists[i] + base[b], at most cap[b] entries
+struct MsfLists {
+    int32_t *buf[2];
+    int64_t base[4], cap[4];
+};
+
+// the info pass's words
+struct MsfAcc {
+    int32_t error, pad;
+    unsigned long long upper, lower;  // marked arcs u -> v with u < v / with u > v
+    unsigned long long weight;        // Σ w over the upper ones
+    uint32_t wmin, wmax;
+    unsigned long long trees, isolated, largest;
+};
+
+__global__ void k_msf_init(int64_t n, int32_t *__restrict__ parent, int32_t *__restrict__ size) {
+    const int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (v < n) {
+        parent[v] = int32_t(v);
+        size[v] = 0;
+    }
+}
+
+// every vertex with an arc into the list of its row class (whole waves stay converged for the ballots)
+__global__ __launch_bounds__(256) void k_msf_classify(int64_t n, const int64_t *__restrict__ off, int64_t short_row, int64_t wave_row, int64_t wg_row,
+                                                      MsfLists l, MsfCtrl *__restrict__ ctrl) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    const int64_t end = ((n + 63) / 64) * 64;
+    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride) {
+        const int64_t d = v < n ? off[v + 1] - off[v] : 0;
+        wave_append(d >= 1 && d < short_row, int32_t(v), l.buf[0] + l.base[0], &ctrl->count[0][0], l.cap[0], &ctrl->error);
+        wave_append(d >= short_row && d < wave_row, int32_t(v), l.buf[0] + l.base[1], &ctrl->count[0][1], l.cap[1], &ctrl->error);
+        wave_append(d >= wave_row && d < wg_row, int32_t(v), l.buf[0] + l.base[2], &ctrl->count[0][2], l.cap[2], &ctrl->error);
+        wave_append(d >= wg_row && d >= 1, int32_t(v), l.buf[0] + l.base[3], &ctrl->count[0][3], l.cap[3], &ctrl->error);
+    }
+}
+
+// (a) THE HOT PASS: WIDTH lanes (1, kGroup, 64, or the 256 threads of the workgroup) per live row of list `which` of buffer `cur`.
+// flip = 0 (minimum) or ~0 (maximum): k0 = w ^ flip.  next != nullptr: a vertex that found a crossing arc is appended to the next live list.
+template <int WIDTH>
+__global__ __launch_bounds__(256) void k_msf_search(const int64_t *__restrict__ off, const int32_t *__restrict__ adj, const int32_t *__restrict__ wgt,
+                                                    const int32_t *__restrict__ comp, const int32_t *__restrict__ list, int32_t *__restrict__ next,
+                                                    int cur, int which, int64_t list_cap, uint32_t flip, unsigned long long *__restrict__ best,
+                                                    int32_t *__restrict__ root, uint32_t *__restrict__ cw, MsfCtrl *__restrict__ ctrl) {
+    constexpr int kLanes = WIDTH > 64 ? 64 : WIDTH;  // lanes of one wave that share a row
+    constexpr int kUnit = WIDTH > 64 ? WIDTH : 64;   // threads that go through the row loop together: the wave, or the workgroup
+    __shared__ unsigned long long s_min[4];
+    const int lane = threadIdx.x & (WIDTH - 1);
+    const int64_t first = ((int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / kUnit) * (kUnit / WIDTH);
+    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
+    const int64_t rows = min(int64_t(ctrl->count[cur][which]), list_cap);
+    unsigned long long examined = 0;
+    // a wave takes 64 / WIDTH consecutive rows at a time and stays together (its appends are one atomic, and the next list keeps runs of
+    // the order of this one); WIDTH = 256: a row per workgroup, whose barriers the loop passes
+    for (int64_t base = first; base < rows; base += rows_step) {
+        const int64_t i = base + (threadIdx.x & (kUnit - 1)) / WIDTH;
+        const bool active = i < rows;
+        const int32_t v = active ? list[i] : 0;
+        const int32_t cv = active ? comp[v] : 0;
+        const int64_t j1 = active ? off[v + 1] : 0;
+        unsigned long long mine = kNoArc;
+        for (int64_t j = active ? off[v] + lane : 0; j < j1; j += WIDTH) {
+            ++examined;
+            const int32_t x = adj[j];
+            if (comp[x] != cv) mine = min(mine, ((unsigned long long)(uint32_t(wgt[j]) ^ flip) << 32) | uint32_t(x));
+        }
+        mine = wave_min<kLanes>(mine);
+        if (WIDTH > 64) {
+            if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = mine;
+            __syncthreads();
+            if (threadIdx.x == 0) mine = min(min(s_min[0], s_min[1]), min(s_min[2], s_min[3]));
+            __syncthreads();
+        }
+        const bool writer = active && lane == 0;  // the row's one writer
+        const bool found = writer && mine != kNoArc;
+        if (writer) {
+            best[v] = mine;
+            root[v] = cv;
+        }
+        if (found) {
+            const uint32_t k0 = uint32_t(mine >> 32);
+            if (k0 < load_now(&cw[cv])) atomicMin(&cw[cv], k0);  // (the word only falls: a stale read costs an atomic, never misses one)
+        }
+        if (next) {
+            if (WIDTH > 64) {
+                if (found) append_checked(next, &ctrl->count[cur ^ 1][which], list_cap, v, &ctrl->error);
+            } else {
+                wave_append(found, v, next, &ctrl->count[cur ^ 1][which], list_cap, &ctrl->error);
+            }
+        }
+    }
+    examined = wave_sum(examined);
+    if ((threadIdx.x & 63) == 0 && examined) atomicAdd(&ctrl->examined, examined);
+}
+
+// lo << 32 | hi of the arc v - x
+__device__ __forceinline__ unsigned long long msf_pair(int32_t v, int32_t x) {
+    return ((unsigned long long)uint32_t(min(v, x)) << 32) | uint32_t(max(v, x));
+}
+
+// (b) the live vertices whose weight word is their component's fold (lo, hi) into the component's pair
+__global__ __launch_bounds__(256) void k_msf_pair(MsfLists l, int cur, const unsigned long long *__restrict__ best, const int32_t *__restrict__ root,
+                                                  const uint32_t *__restrict__ cw, unsigned long long *__restrict__ cpair,
+                                                  const MsfCtrl *__restrict__ ctrl) {
+    const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, stride = int64_t(gridDim.x) * blockDim.x;
+    for (int b = 0; b < 4; ++b) {
+        const int32_t *list = l.buf[cur] + l.base[b];
+        const int64_t rows = min(int64_t(ctrl->count[cur][b]), l.cap[b]);
+        for (int64_t i = tid; i < rows; i += stride) {
+            const int32_t v = list[i];
+            const unsigned long long mine = best[v];
+            if (mine == kNoArc) continue;
+            const int32_t r = root[v];
+            if (uint32_t(mine >> 32) != cw[r]) continue;
+            const unsigned long long pair = msf_pair(v, int32_t(uint32_t(mine)));
+            if (pair < load_now(&cpair[r])) atomicMin(&cpair[r], pair);
+        }
+    }
+}
+
+// (c) the winner of every component marks both arcs of its edge, links its ends and counts the pick
+__global__ __launch_bounds__(256) void k_msf_apply(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj, MsfLists l, int cur,
+                                                   const unsigned long long *__restrict__ best, const int32_t *__restrict__ root,
+                                                   const uint32_t *__restrict__ cw, const unsigned long long *__restrict__ cpair,
+                                                   int32_t *__restrict__ parent, uint8_t *__restrict__ mask, MsfCtrl *__restrict__ ctrl) {
+    const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, stride = int64_t(gridDim.x) * blockDim.x;
+    const uint32_t cap = uint32_t(min(n + 64, int64_t(INT_MAX)));
+    int32_t picks = 0;
+    for (int b = 0; b < 4; ++b) {
+        const int32_t *list = l.buf[cur] + l.base[b];
+        const int64_t rows = min(int64_t(ctrl->count[cur][b]), l.cap[b]);
+        for (int64_t i = tid; i < rows; i += stride) {
+            const int32_t v = list[i];
+            const unsigned long long mine = best[v];
+            if (mine == kNoArc) continue;
+            const int32_t r = root[v], x = int32_t(uint32_t(mine));
+            if (uint32_t(mine >> 32) != cw[r] || msf_pair(v, x) != cpair[r]) continue;
+            const int64_t own = cc_find_in_row(adj, off[v], off[v + 1], x), twin = cc_find_in_row(adj, off[x], off[x + 1], v);
+            if (own < 0 || twin < 0) {
+                ctrl->error = 1;
+                continue;
+            }
+            mask[own] = 1;
+            mask[twin] = 1;
+            cc_link(parent, min(v, x), max(v, x), cap, &ctrl->error);
+            ++picks;
+        }
+    }
+    picks = wave_sum(picks);  // (at most n in all)
+    if ((threadIdx.x & 63) == 0 && picks) atomicAdd(&ctrl->picks, picks);
+}
+
+// per row the marked `u < v` arcs into cnt[u] (one writer); Σ w, min w, max w over them and the marked `u > v` arcs into acc.  WIDTH lanes
+// per row: kGroup up to kLongRow entries, 64 beyond
+template <int WIDTH>
+__global__ __launch_bounds__(256) void k_msf_count(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                   const int32_t *__restrict__ wgt, const uint8_t *__restrict__ mask, int64_t *__restrict__ cnt,
+                                                   MsfAcc *__restrict__ acc) {
+    const int lane = threadIdx.x & (WIDTH - 1);
+    const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
+    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
+    unsigned long long upper = 0, lower = 0, weight = 0;
+    uint32_t wmin = ~0u, wmax = 0;
+    for (int64_t u = row0; u < n; u += rows_step) {
+        const int64_t j0 = off[u], j1 = off[u + 1];
+        if ((j1 - j0 > kLongRow) != (WIDTH == 64)) continue;
+        int64_t here = 0;
+        for (int64_t j = j0 + lane; j < j1; j += WIDTH) {
+            if (!mask[j]) continue;
+            if (int64_t(adj[j]) > u) {
+                const uint32_t w = uint32_t(wgt[j]);
+                ++here;
+                weight += w;
+                wmin = min(wmin, w);
+                wmax = max(wmax, w);
+            } else {
+                ++lower;
+            }
+        }
+        upper += (unsigned long long)here;
+        here = wave_sum<WIDTH>(here);
+        if (lane == 0) cnt[u] = here;
+    }
+    upper = wave_sum(upper);
+    lower = wave_sum(lower);
+    weight = wave_sum(weight);
+    wmin = wave_min(wmin);
+    wmax = wave_max(wmax);
+    if ((threadIdx.x & 63) == 0 && (upper || lower)) {
+        atomicAdd(&acc->upper, upper);
+        atomicAdd(&acc->lower, lower);
+        atomicAdd(&acc->weight, weight);
+        atomicMin(&acc->wmin, wmin);
+        atomicMax(&acc->wmax, wmax);
+    }
+}
+
+// the marked `u < v` arcs of row u to the positions pos[u], pos[u] + 1, … in CSR order: a ballot per chunk of the row
+template <int WIDTH>
+__global__ __launch_bounds__(256) void k_msf_fill(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
+                                                  const int32_t *__restrict__ wgt, const uint8_t *__restrict__ mask, const int64_t *__restrict__ pos,
+                                                  int64_t cap, int32_t *__restrict__ eu, int32_t *__restrict__ ev, int32_t *__restrict__ ew,
+                                                  MsfAcc *__restrict__ acc) {
+    const RowGroup<WIDTH> grp;
+    const int lane = grp.lane;
+    const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
+    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
+    for (int64_t u = row0; u < n; u += rows_step) {  // (uniform in the group: its lanes leave together)
+        const int64_t j0 = off[u], j1 = off[u + 1];
+        if ((j1 - j0 > kLongRow) != (WIDTH == 64)) continue;
+        int64_t at = pos[u];
+        const int64_t stop = pos[u + 1];
+        if (at == stop) continue;
+        for (int64_t c = j0; c < j1; c += WIDTH) {
+            const int64_t j = c + lane;
+            const bool take = j < j1 && mask[j] && int64_t(adj[j]) > u;
+            const unsigned long long hits = grp.ballot(take);
+            if (take) {
+                const int64_t p = at + __popcll(hits & ((1ull << lane) - 1ull));
+                if (p < stop && p < cap) {
+                    eu[p] = int32_t(u);
+                    ev[p] = adj[j];
+                    ew[p] = wgt[j];
+                } else {
+                    acc->error = 1;
+                }
+            }
+            at += __popcll(hits);
+        }
+        if (at != stop && lane == 0) acc->error = 1;
+    }
+}
+
+// per root: trees, isolated vertices (trees of one vertex), the largest tree.  A label that is no root raises the flag.
+__global__ __launch_bounds__(256) void k_msf_info(int64_t n, const int32_t *__restrict__ label, const int32_t *__restrict__ size, MsfAcc *__restrict__ acc) {
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
+    unsigned long long trees = 0, isolated = 0, largest = 0;
+    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < n; v += stride) {
+        const int32_t l = label[v];
+        if (l < 0 || l > v || label[l] != l) acc->error = 1;
+        if (l != v) continue;
+        const uint32_t s = uint32_t(size[v]);
+        ++trees;
+        isolated += s == 1;
+        largest = max(largest, (unsigned long long)s);
+    }
+    trees = wave_sum(trees);
+    isolated = wave_sum(isolated);
+    largest = wave_max(largest);
+    if ((threadIdx.x & 63) == 0 && trees) {
+        atomicAdd(&acc->trees, trees);
+        if (isolated) atomicAdd(&acc->isolated, isolated);
+        atomicMax(&acc->largest, largest);
+    }
+}
+
+// (a) over list b of buffer cur, `rows` entries: WIDTH lanes per row, at most per_cu workgroups per compute unit; nxt == cur: no pruning.
+// comp is the parent array, flat between the rounds.
+template <int WIDTH>
+void search_rows(const gmsx_graph *g, const MsfLists &l, int cur, int nxt, int b, int64_t rows, int per_cu, uint32_t flip, const int32_t *comp,
+                 unsigned long long *best, int32_t *root, uint32_t *cw, MsfCtrl *ctrl, int *launches) {
+    if (rows <= 0) return;
+    Ctx &c = ctx();
+    const int cus = c.compute_units > 0 ? c.compute_units : 256;
+    const unsigned grid = unsigned(std::min<int64_t>((rows * WIDTH + 255) / 256, int64_t(cus) * per_cu));
+    hipLaunchKernelGGL((k_msf_search<WIDTH>), dim3(grid), dim3(256), 0, c.stream, g->off, g->adj, g->wgt.as<const int32_t>(), comp, l.buf[cur] + l.base[b],
+                       nxt != cur ? l.buf[nxt] + l.base[b] : (int32_t *)nullptr, cur, b, l.cap[b], flip, best, root, cw, ctrl);
+    ++*launches;
+}
+
+int msf(const gmsx_graph *g, uint32_t flags, int32_t *edge_u, int32_t *edge_v, int32_t *edge_w, uint8_t *arc_keep, int32_t *label, gmsx_msf_info *info,
+        gmsx_stats *stats) {
+    gmsx_msf_info res;
+    std::memset(&res, 0, sizeof res);
+    const int64_t n = g->n, nnz = g->nnz;
+    if (n == 0 || nnz == 0) {  // every vertex is a tree of its own
+        res.trees = res.isolated = n;
+        res.largest_tree = n > 0 ? 1 : 0;
+        for (int64_t v = 0; label && v < n; ++v) label[v] = int32_t(v);
+        *info = res;
+        if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0, 0};
+        return GMSX_OK;
+    }
+    Ctx &c = ctx();
+    hipStream_t s = c.stream;
+    const int cus = c.compute_units > 0 ? c.compute_units : 256;
+    // test hooks, first guesses
+    const int64_t wave_row = std::max<long long>(1, std::min<long long>(opt_int("MSF_WAVE_ROW", kMsfWaveRowDefault), INT_MAX));
+    const int64_t wg_row = std::max<long long>(wave_row, std::min<long long>(opt_int("MSF_WG_ROW", kMsfWgRowDefault), INT_MAX));
+    const bool prune = opt_int("MSF_PRUNE", kMsfPruneDefault) != 0;
+    const bool timing = opt_on("TIMING");  // one line per round on stderr: its live vertices, the arcs it examined, its winners
+    const int64_t short_row = std::min<int64_t>(kMsfShortRow, wave_row);
+    const uint32_t flip = (flags & GMSX_MSF_MAXIMUM) ? ~0u : 0u;
+    const bool want_edges = edge_u != nullptr;
+    MsfLists l;
+    const int64_t bound[4] = {1, short_row, wave_row, wg_row};  // the shortest row of every list
+    int64_t total = 0;
+    for (int b = 0; b < 4; ++b) {
+        l.base[b] = total;
+        l.cap[b] = std::min<int64_t>(n, nnz / bound[b] + 1);
+        total += l.cap[b];
+    }
+    // ---- setup: the buffers
+    DevBuf d_parent, d_root, d_size, d_list0, d_list1, d_best, d_comp, d_mask, d_ctrl, d_acc, d_cnt, d_pos, d_eu, d_ev, d_ew;
+    GMSX_HIP(hipEventRecord(c.ev[0], s));
+    if (int rc = dalloc<int32_t>(d_parent, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_root, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_size, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_list0, total)) return rc;
+    if (prune)
+        if (int rc = dalloc<int32_t>(d_list1, total)) return rc;
+    if (int rc = dalloc<unsigned long long>(d_best, n)) return rc;
+    if (int rc = dalloc<uint32_t>(d_comp, 3 * n)) return rc;  // cpair: n 64-bit words, then cw: n 32-bit words
+    if (int rc = dalloc<uint8_t>(d_mask, nnz)) return rc;
+    if (int rc = dalloc<MsfCtrl>(d_ctrl, 1)) return rc;
+    if (int rc = dalloc<MsfAcc>(d_acc, 1)) return rc;
+    if (int rc = dalloc<int64_t>(d_cnt, n + 1)) return rc;
+    if (want_edges) {
+        if (int rc = dalloc<int64_t>(d_pos, n + 1)) return rc;
+        if (int rc = dalloc<int32_t>(d_eu, n - 1)) return rc;
+        if (int rc = dalloc<int32_t>(d_ev, n - 1)) return rc;
+        if (int rc = dalloc<int32_t>(d_ew, n - 1)) return rc;
+    }
+    l.buf[0] = d_list0.as<int32_t>();
+    l.buf[1] = prune ? d_list1.as<int32_t>() : d_list0.as<int32_t>();
+    MsfCtrl *ctrl = d_ctrl.as<MsfCtrl>();
+    MsfAcc *acc = d_acc.as<MsfAcc>();
+    int32_t *parent = d_parent.as<int32_t>();
+    unsigned long long *cpair = d_comp.as<unsigned long long>();
+    uint32_t *cw = d_comp.as<uint32_t>() + 2 * n;
+    unsigned long long *best = d_best.as<unsigned long long>();
+    int32_t *root = d_root.as<int32_t>();
+    const int32_t *wgt = g->wgt.as<const int32_t>();
+    GMSX_HIP(hipMemsetAsync(ctrl, 0, sizeof(MsfCtrl), s));
+    GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(MsfAcc), s));
+    GMSX_HIP(hipMemsetAsync(&acc->wmin, 0xff, sizeof(uint32_t), s));
+    GMSX_HIP(hipMemsetAsync(d_mask.p, 0, size_t(nnz), s));
+    GMSX_HIP(hipMemsetAsync(d_cnt.p, 0, size_t(n + 1) * sizeof(int64_t), s));
+    // ---- the rounds
+    GMSX_HIP(hipEventRecord(c.ev[1], s));
+    int launches = 0;
+    const unsigned per_vertex = unsigned((n + 255) / 256);
+    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    hipLaunchKernelGGL(k_msf_init, dim3(per_vertex), dim3(256), 0, s, n, parent, d_size.as<int32_t>());
+    hipLaunchKernelGGL(k_msf_classify, dim3(sweep), dim3(256), 0, s, n, g->off, short_row, wave_row, wg_row, l, ctrl);
+    launches += 2;
+    MsfCtrl h;
+    GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
+    GMSX_HIP(hipStreamSynchronize(s));
+    if (h.error) return GMSX_ERR_KERNEL;
+    int cur = 0;
+    int32_t rounds = 0;
+    for (;;) {
+        int64_t live = 0;
+        for (int b = 0; b < 4; ++b) {
+            if (h.count[cur][b] < 0 || int64_t(h.count[cur][b]) > l.cap[b]) return GMSX_ERR_KERNEL;
+            live += h.count[cur][b];
+        }
+        if (live == 0) break;  // no vertex has a crossing arc left
+        if (rounds >= kMsfMaxRounds) return GMSX_ERR_KERNEL;
+        const int nxt = prune ? cur ^ 1 : cur;
+        GMSX_HIP(hipMemsetAsync(d_comp.p, 0xff, size_t(n) * 12, s));
+        GMSX_HIP(hipMemsetAsync(&ctrl->picks, 0, sizeof(int32_t), s));
+        if (prune) GMSX_HIP(hipMemsetAsync(&ctrl->count[nxt][0], 0, 4 * sizeof(int32_t), s));
+        search_rows<1>(g, l, cur, nxt, 0, h.count[cur][0], 16, flip, parent, best, root, cw, ctrl, &launches);
+        search_rows<kGroup>(g, l, cur, nxt, 1, h.count[cur][1], 32, flip, parent, best, root, cw, ctrl, &launches);
+        search_rows<64>(g, l, cur, nxt, 2, h.count[cur][2], 32, flip, parent, best, root, cw, ctrl, &launches);
+        search_rows<256>(g, l, cur, nxt, 3, h.count[cur][3], 8, flip, parent, best, root, cw, ctrl, &launches);
+        const unsigned over_live = unsigned(std::max<int64_t>(1, std::min<int64_t>((live + 255) / 256, int64_t(cus) * 16)));
+        hipLaunchKernelGGL(k_msf_pair, dim3(over_live), dim3(256), 0, s, l, cur, best, root, cw, cpair, ctrl);
+        hipLaunchKernelGGL(k_msf_apply, dim3(over_live), dim3(256), 0, s, n, g->off, g->adj, l, cur, best, root, cw, cpair, parent,
+                           d_mask.as<uint8_t>(), ctrl);
+        launches += 2;
+        const unsigned long long examined_was = h.examined;
+        GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        if (h.error || h.picks < 0) return GMSX_ERR_KERNEL;
+        if (timing)
+            std::fprintf(stderr, "[gmsx msf] round %d: %lld live vertices, %llu arcs examined, %d winners\n", int(rounds) + 1, (long long)live,
+                         h.examined - examined_was, int(h.picks));
+        if (h.picks == 0) break;
+        ++rounds;
+        if (int rc = flatten(n, parent, &ctrl->error, cus, s, &launches, nullptr)) return rc;
+        cur = nxt;
+    }
+    // ---- the edge list and the info reduction
+    GMSX_HIP(hipEventRecord(c.ev[2], s));
+    const unsigned grid16 = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
+    const unsigned grid64 = unsigned(std::min<int64_t>((n * 64 + 255) / 256, int64_t(cus) * 8));
+    const bool long_rows = g->max_deg > kLongRow;
+    hipLaunchKernelGGL((k_msf_count<kGroup>), dim3(grid16), dim3(256), 0, s, n, g->off, g->adj, wgt, d_mask.as<const uint8_t>(), d_cnt.as<int64_t>(), acc);
+    if (long_rows)
+        hipLaunchKernelGGL((k_msf_count<64>), dim3(grid64), dim3(256), 0, s, n, g->off, g->adj, wgt, d_mask.as<const uint8_t>(), d_cnt.as<int64_t>(), acc);
+    hipLaunchKernelGGL(k_cc_sizes, dim3(sweep), dim3(256), 0, s, n, parent, d_size.as<int32_t>());
+    hipLaunchKernelGGL(k_msf_info, dim3(sweep), dim3(256), 0, s, n, parent, d_size.as<const int32_t>(), acc);
+    launches += long_rows ? 4 : 3;
+    if (want_edges) {
+        if (int rc = exclusive_scan_i64(d_cnt.as<const int64_t>(), d_pos.as<int64_t>(), n + 1, s)) return rc;
+        hipLaunchKernelGGL((k_msf_fill<kGroup>), dim3(grid16), dim3(256), 0, s, n, g->off, g->adj, wgt, d_mask.as<const uint8_t>(), d_pos.as<const int64_t>(),
+                           n - 1, d_eu.as<int32_t>(), d_ev.as<int32_t>(), d_ew.as<int32_t>(), acc);
+        if (long_rows)
+            hipLaunchKernelGGL((k_msf_fill<64>), dim3(grid64), dim3(256), 0, s, n, g->off, g->adj, wgt, d_mask.as<const uint8_t>(),
+                               d_pos.as<const int64_t>(), n - 1, d_eu.as<int32_t>(), d_ev.as<int32_t>(), d_ew.as<int32_t>(), acc);
+        launches += long_rows ? 3 : 2;
+    }
+    MsfAcc a;
+    GMSX_HIP(hipMemcpyAsync(&a, acc, sizeof a, hipMemcpyDeviceToHost, s));
+    GMSX_HIP(hipEventRecord(c.ev[3], s));
+    GMSX_HIP(hipStreamSynchronize(s));
+    GMSX_HIP(hipGetLastError());
+    if (a.error || a.trees < 1 || a.trees > (unsigned long long)n || a.upper != a.lower || a.upper != (unsigned long long)n - a.trees ||
+        a.largest < 1 || (a.upper > 0) != (rounds > 0))
+        return GMSX_ERR_KERNEL;
+    res.edges = int64_t(a.upper);
+    res.total_weight = int64_t(a.weight);
+    res.trees = int64_t(a.trees);
+    res.isolated = int64_t(a.isolated);
+    res.largest_tree = int64_t(a.largest);
+    res.min_weight = a.upper ? int32_t(a.wmin) : 0;
+    res.max_weight = a.upper ? int32_t(a.wmax) : 0;
+    res.rounds = rounds;
+    // the flag words were read as zero: the caller's arrays are written now, through host staging
+    const size_t ne = size_t(res.edges);
+    std::vector<int32_t> h_label, h_eu, h_ev, h_ew;
+    std::vector<uint8_t> h_mask;
+    if (label) {
+        h_label.resize(size_t(n));
+        GMSX_HIP(hipMemcpyAsync(h_label.data(), parent, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    if (arc_keep) {
+        h_mask.resize(size_t(nnz));
+        GMSX_HIP(hipMemcpyAsync(h_mask.data(), d_mask.p, size_t(nnz), hipMemcpyDeviceToHost, s));
+    }
+    if (want_edges && ne > 0) {
+        h_eu.resize(ne);
+        h_ev.resize(ne);
+        h_ew.resize(ne);
+        GMSX_HIP(hipMemcpyAsync(h_eu.data(), d_eu.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipMemcpyAsync(h_ev.data(), d_ev.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipMemcpyAsync(h_ew.data(), d_ew.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    GMSX_HIP(hipStreamSynchronize(s));
+    float up_ms = 0.f, ms = 0.f, info_ms = 0.f;
+    GMSX_HIP(hipEventElapsedTime(&up_ms, c.ev[0], c.ev[1]));
+    GMSX_HIP(hipEventElapsedTime(&ms, c.ev[1], c.ev[2]));
+    GMSX_HIP(hipEventElapsedTime(&info_ms, c.ev[2], c.ev[3]));
+    if (label) std::memcpy(label, h_label.data(), size_t(n) * sizeof(int32_t));
+    if (arc_keep) std::memcpy(arc_keep, h_mask.data(), size_t(nnz));
+    if (!h_eu.empty()) {
+        std::memcpy(edge_u, h_eu.data(), ne * sizeof(int32_t));
+        std::memcpy(edge_v, h_ev.data(), ne * sizeof(int32_t));
+        std::memcpy(edge_w, h_ew.data(), ne * sizeof(int32_t));
+    }
+    *info = res;
+    if (stats) *stats = gmsx_stats{double(ms), double(up_ms) + double(info_ms), uint64_t(res.edges), uint64_t(h.examined), uint64_t(rounds), launches, 0, 0};
+    return GMSX_OK;
+}
+
+}  // namespace
+}  // namespace gmsx
+
+using namespace gmsx;
+
+extern "C" {
+
+int gmsx_min_spanning_forest(const gmsx_graph *g, uint32_t flags, int32_t *edge_u, int32_t *edge_v, int32_t *edge_w, uint8_t *arc_keep, int32_t *label,
+                             gmsx_msf_info *info, gmsx_stats *stats) {
+    return gmsx::guard([&]() -> int {
+        const int given = (edge_u ? 1 : 0) + (edge_v ? 1 : 0) + (edge_w ? 1 : 0);
+        if (!g || !info || (flags & ~uint32_t(GMSX_MSF_MAXIMUM)) || (given != 0 && given != 3)) return GMSX_ERR_INVALID;
+        if (int rc = ensure_init()) return rc;  // (before the handle is read: without a device there is no valid one)
+        if (!g->wgt.p) return GMSX_ERR_INVALID;
+        return msf(g, flags, edge_u, edge_v, edge_w, arc_keep, label, info, stats);
+    });
+}
+
+}  // extern "C"

@@ -996,6 +996,8 @@ Option g_options[] = {
     {"MSBFS_DIRECTION", "", false}, {"MSBFS_ALPHA", "", false}, {"MSBFS_WORDS", "", false},
     // delta-stepping shortest paths (sssp.hip)
     {"SSSP_WG_FRONTIER", "", false}, {"SSSP_WIDE", "", false}, {"SSSP_DELTA_AUTO", "", false},
+    // minimum spanning forest (msf.hip)
+    {"MSF_WAVE_ROW", "", false}, {"MSF_WG_ROW", "", false}, {"MSF_PRUNE", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

@@ -213,7 +213,12 @@ int gmsx_set_host_threads(int n);
  *                   boundary), SSSP_WIDE (1 = 64-bit distance words whatever the weights), SSSP_DELTA_AUTO (the parameter c of the default
  *                   bucket width, delta = max(1, c * mean weight / mean degree); default 16 — measured once, DESIGN.md §5.4l, and still a first guess) — test hooks;
  *                   none changes dist, parent or any info field except delta (SSSP_DELTA_AUTO, with delta = 0), buckets (a fact about
- *                   delta), rounds and relaxations */
+ *                   delta), rounds and relaxations
+ *   spanning forest        MSF_WAVE_ROW / MSF_WG_ROW (smallest row that gets a wave / a whole workgroup in the search pass of
+ *                   gmsx_min_spanning_forest, defaults 256 / 4096, as CC_WAVE_ROW / CC_WG_ROW), MSF_PRUNE (0, the default = every vertex is searched in every
+ *                   round; 1 = a vertex without a crossing arc leaves the live list for good, so that later rounds walk the shrinking border
+ *                   only — measured slower on four graphs) — the bin edges are first guesses, not tuned values; test hooks;
+ *                   none changes any output of gmsx_min_spanning_forest except gmsx_stats */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -909,6 +914,42 @@ int gmsx_sssp(const gmsx_graph *g, int32_t source, int64_t delta /* > 0: as give
               gmsx_sssp_info *info /* required */, gmsx_stats *stats);
 typedef struct { int64_t violated_arcs, untight, wrong_unreached; int32_t source_ok, reserved; } gmsx_sssp_check;
 int gmsx_sssp_verify(const gmsx_graph *g, int32_t source, const int64_t *dist /* n, host */, gmsx_sssp_check *out, gmsx_stats *stats);
+
+/* ---- minimum (or maximum) spanning forest over the attached weights (msf.hip; no reference counterpart, like the k-truss).
+ * THE ORDER.  An edge is e = {u, v} with lo = min(u, v), hi = max(u, v) and weight w.  Minimum: key(e) = (w, lo, hi), compared
+ * lexicographically.  Maximum (GMSX_MSF_MAXIMUM in flags): the heavier edge comes first, ties are still broken by the smaller (lo, hi).  The CSR
+ * has no parallel edges and no self loops, so the order is strict, and the spanning forest under it is unique: "the forest" is Kruskal's output
+ * under that order, which is also the output of Borůvka's rounds under it — what the device runs: in every round every current component that
+ * has one picks its first crossing edge in the order, and all picks are applied (union_find.hpp's links: a root goes under a smaller id).
+ * edge_u / edge_v / edge_w (all three or none): the forest's edges with edge_u[i] < edge_v[i], ascending by (u, v) — the CSR order of the u < v
+ * arcs; the first info->edges entries are written.  arc_keep: a symmetric 0 / 1 byte per arc of the uploaded CSR, the shape gmsx_jarvis_patrick
+ * produces and gmsx_connected_components consumes; exactly 2 * edges bytes are 1.  label[v] = the smallest vertex id of v's tree, which is
+ * gmsx_connected_components(g, NULL)'s label byte for byte.  info->rounds counts the rounds that added an edge: the components after round r are
+ * a fact about (graph, weights, flags), so rounds is, and rounds <= floor(log2(max(largest_tree, 1))).
+ * Every output except the gmsx_stats times is byte-identical in every run and process, under every MSF_* option, GMSX_UPLOAD_TRUSTED,
+ * GMSX_UPLOAD_HUB_LIMIT, a sharded upload and re-attached weights.
+ * No weights attached, NULL g or info, unknown flag bits, only one or two of the three edge arrays: GMSX_ERR_INVALID, nothing written.  A walk
+ * or retry past its cap (n + 64), an append past its bound, more than 64 rounds, a picked arc whose twin is not found (possible only under
+ * GMSX_UPLOAD_TRUSTED), or an edge count that is not n - trees: GMSX_ERR_KERNEL.  The caller's arrays are written only after the flag word was
+ * read as zero, through host staging.  Single GPU, no shards.  n = 0 or no edge: GMSX_OK with trees = isolated = n.  The handle is not modified;
+ * the call's device state is O(n) words and one byte per arc.  Test hooks: options MSF_WAVE_ROW, MSF_WG_ROW (first guesses, not
+ * tuned) and MSF_PRUNE.  gmsx_stats: kernel_ms (the rounds), setup_ms (buffers, the edge list and the info reduction), launches, units = edges, probes =
+ * rounds, alg_elements = arcs the search pass examined. */
+enum { GMSX_MSF_MAXIMUM = 1u };
+typedef struct {
+    int64_t edges;          /* forest edges = n - trees */
+    int64_t total_weight;   /* sum of their weights */
+    int64_t trees;          /* components of the graph, isolated vertices included */
+    int64_t isolated;
+    int64_t largest_tree;   /* vertices of the largest tree; 0 for n = 0 */
+    int32_t min_weight, max_weight;  /* lightest / heaviest forest edge (the bottleneck); 0 when edges == 0 */
+    int32_t rounds;         /* Boruvka rounds that added at least one edge: a fact about (graph, weights, flags) */
+    int32_t reserved;
+} gmsx_msf_info;
+int gmsx_min_spanning_forest(const gmsx_graph *g, uint32_t flags,
+                             int32_t *edge_u, int32_t *edge_v, int32_t *edge_w /* each: room for n - 1 entries, host, or NULL (all three or none) */,
+                             uint8_t *arc_keep /* nnz, host, or NULL */, int32_t *label /* n, host, or NULL */,
+                             gmsx_msf_info *info /* required */, gmsx_stats *stats);
 
 /* ---- 4-cycle counting and the 3- / 4-vertex motif census.  No reference counterpart (like the k-truss: a member of the family the suite
  * describes and does not build).  All results are exact integers.

@@ -44,6 +44,8 @@
 //   gmsx::set_weights(g, weights)        -> gmsx_graph_set_weights  (int32 weights parallel to g.neighbors(); what makes the graph a WGraph)
 //   gmsx::sssp(g, source, dist, delta, …) -> gmsx_sssp               (log_graph/sssp.cc:54-134, DeltaStep; dist in 64 bits, -1 = unreachable)
 //   gmsx::sssp_verify(g, source, dist)   -> gmsx_sssp_verify        (sssp.cc:145-175, SSSPVerifier)
+//   gmsx::min_spanning_forest(g, edges, flags, info) -> gmsx_min_spanning_forest (the forest's (u, v, w), u < v, ascending; GMSX_MSF_MAXIMUM: the maximum one; no reference driver)
+//   gmsx::msf_arc_mask(g, flags)         -> gmsx_min_spanning_forest (a byte per arc of g.neighbors(): 1 on both arcs of every forest edge — what gmsx_connected_components takes)
 //   gmsx::pick_sources(csr, count)       -> gmsx_csr_pick_sources   (gapbs/benchmark.h:51-75, SourcePicker)
 //   gmsx::cycle4_count(g) / cycle4_count(g, at_vertex) -> gmsx_cycle4_count (the 4-cycles, and those through every vertex; no reference driver)
 //   gmsx::motif_census4(g)               -> gmsx_motif_census4     (the eight 3- and 4-vertex motifs, non-induced and induced; no reference driver)
@@ -799,6 +801,38 @@ inline bool sssp_verify(const HipGraphT<S> &g, int32_t source, const std::vector
     detail::check(gmsx_sssp_verify(g.device(), source, dist.empty() ? nullptr : dist.data(), &c, nullptr), "gmsx_sssp_verify");
     if (out) *out = c;
     return c.violated_arcs == 0 && c.untight == 0 && c.wrong_unreached == 0 && c.source_ok == 1;
+}
+// One edge of a spanning forest: u < v and the weight attached to the arc u -> v.
+struct WeightedEdge {
+    int32_t u, v, w;
+    friend bool operator==(const WeightedEdge &a, const WeightedEdge &b) { return a.u == b.u && a.v == b.v && a.w == b.w; }
+    friend bool operator!=(const WeightedEdge &a, const WeightedEdge &b) { return !(a == b); }
+};
+// The minimum spanning forest of g under the weights attached with gmsx::set_weights — the maximum one with flags = GMSX_MSF_MAXIMUM — under
+// the strict order of gmsx.h (weight, then the smaller (min id, max id)), so the forest is unique: `edges` receives its n - trees edges
+// ascending by (u, v).  No reference counterpart.  Returns the total weight; `info` (optional) receives trees, rounds, the bottleneck weights …
+template <class S>
+inline int64_t min_spanning_forest(const HipGraphT<S> &g, std::vector<WeightedEdge> &edges, uint32_t flags = 0, gmsx_msf_info *info = nullptr) {
+    const size_t room = size_t(std::max<int64_t>(g.num_nodes() - 1, 1));
+    std::vector<int32_t> u(room), v(room), w(room);
+    gmsx_msf_info mi{};
+    detail::check(gmsx_min_spanning_forest(g.device(), flags, u.data(), v.data(), w.data(), nullptr, nullptr, &mi, nullptr), "gmsx_min_spanning_forest");
+    edges.resize(size_t(mi.edges));
+    for (size_t i = 0; i < edges.size(); ++i) edges[i] = WeightedEdge{u[i], v[i], w[i]};
+    if (info) *info = mi;
+    return mi.total_weight;
+}
+// The same forest as a byte per arc, parallel to g.neighbors(): 1 on both arcs of every forest edge.  gmsx_connected_components over this mask
+// gives the labels of the whole graph.
+template <class S>
+inline std::vector<uint8_t> msf_arc_mask(const HipGraphT<S> &g, uint32_t flags = 0, gmsx_msf_info *info = nullptr) {
+    const int64_t nnz = g.num_nodes() > 0 ? g.offsets()[g.num_nodes()] : 0;
+    std::vector<uint8_t> keep(size_t(nnz) + 1);
+    gmsx_msf_info mi{};
+    detail::check(gmsx_min_spanning_forest(g.device(), flags, nullptr, nullptr, nullptr, keep.data(), nullptr, &mi, nullptr), "gmsx_min_spanning_forest");
+    keep.resize(size_t(nnz));
+    if (info) *info = mi;
+    return keep;
 }
 // PrintTopScores' top k (pr.cc:64-74, gapbs/util.h TopK) on the host: the k largest scores as (id, score), largest first, ties by the smaller id
 inline std::vector<std::pair<int32_t, double>> top_scores(const std::vector<double> &scores, size_t k) {
