@@ -403,7 +403,7 @@ int bk_list(const gmsx_graph *g, int part, int nparts, int64_t *offsets, int32_t
     const bool sizing = offsets == nullptr && members == nullptr;
     double ms1 = 0.0, ms2 = 0.0;
     int launches = 0;
-    if (int rc = ensure_pass1(p1, ListKey(g, part, nparts), sizing, [&] { return bk_list_pass1(g, part, nparts, p1, &ms1, &launches); })) return rc;
+    if (int rc = ensure_pass1(p1, ListKey(g->serial, g, g->off, g->adj, g->n, g->nnz, part, nparts), sizing, [&] { return bk_list_pass1(g, part, nparts, p1, &ms1, &launches); })) return rc;
     *info = p1.info;
     if (!sizing) {
         const int64_t nc = p1.info.cliques, nm = p1.info.members;

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <mutex>
 #include <array>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -2250,6 +2251,8 @@ int gmsx_graph_upload_shard(int64_t n, const int64_t *offsets, const int32_t *ne
         std::unique_ptr<gmsx_graph, Free> owner(new (std::nothrow) gmsx_graph);  // freed on every way out, an exception in a build step included
         gmsx_graph *g = owner.get();
         if (!g) return GMSX_ERR_NOMEM;
+        static std::atomic<uint64_t> uploads{0};  // every upload ends here: one counter for the process
+        g->serial = ++uploads;
         g->n = n;
         g->nnz = offsets[n];
         g->shard_part = part;

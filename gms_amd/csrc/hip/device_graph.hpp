@@ -81,6 +81,7 @@ struct TaskList {
     }
 };
 struct gmsx_graph {
+    uint64_t serial = 0;  // which upload of this process this is (from 1 on; gmsx_graph_upload_shard): what a cache keyed on a handle compares, addresses repeat
     int64_t n = 0, nnz = 0, m = 0;
     int64_t *off = nullptr;
     int32_t *adj = nullptr;

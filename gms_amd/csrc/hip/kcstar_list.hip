@@ -377,7 +377,7 @@ int kcstar_list(const gmsx_graph *g, int k, uint32_t flags, int part, int nparts
     const bool sizing = cliques == nullptr && star_offsets == nullptr && star_members == nullptr;
     double ms1 = 0.0, ms2 = 0.0, setup = 0.0;
     int launches = 0;
-    if (int rc = ensure_pass1(p1, ListKey(g, part, nparts, k, flags), sizing,
+    if (int rc = ensure_pass1(p1, ListKey(g->serial, g, g->off, g->adj, g->n, g->nnz, part, nparts, k, flags), sizing,
                               [&] { return kcstar_pass1(g, k, flags, part, nparts, p1, &ms1, &setup, &launches); }))
         return rc;
     *info = p1.info;

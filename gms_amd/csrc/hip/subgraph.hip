@@ -412,7 +412,7 @@ int sgm_list(const gmsx_graph *g, const HostPattern &hp, const int64_t *p_off, c
         p1.clear();  // pass 1 of another pattern
     double ms1 = 0.0, ms2 = 0.0, setup = 0.0;
     int launches = 0;
-    if (int rc = ensure_pass1(p1, ListKey(g, part, nparts, k, flags), sizing,
+    if (int rc = ensure_pass1(p1, ListKey(g->serial, g, g->off, g->adj, g->n, g->nnz, part, nparts, k, flags), sizing,
                               [&] { return sgm_pass1(g, hp, pat, part, nparts, p1, &ms1, &setup, &launches); }))
         return rc;
     p1.p_off.assign(p_off, p_off + k + 1);

@@ -10,8 +10,8 @@
 // or other than pass 1 counted raises a flag word instead (GMSX_ERR_KERNEL), it never writes past its span, and the caller's buffers are
 // written only after the fill's flag word was read as zero.
 // Pass 1 of the last call is kept: a sizing call always searches (it is what a caller times), a fill call whose key matches re-uses it
-// instead of searching a third time.  The key is the handle, its device arrays and the call's parameters; a stale entry can only make pass 2
-// disagree with it, which is reported (GMSX_ERR_KERNEL), never written.
+// instead of searching a third time.  The key (host/list_key.hpp) is the upload's serial, the handle, its device arrays and the call's
+// parameters: a cached pass 1 belongs to one upload, and a handle that re-uses the addresses of a freed one searches again.
 //
 // A new listing call brings its kernel, its slab-size formula, the host loop that fills ListPass1::soff and its task arrays, the copy into
 // the caller's arrays and the extern "C" entry; it calls, in this order: ensure_pass1 { upload_tasks, alloc_zeroed x3, run_list_pass,
@@ -20,6 +20,7 @@
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
 #include "launch_plan.hpp"
+#include "list_key.hpp"
 
 #include <vector>
 
@@ -30,22 +31,6 @@ __device__ __forceinline__ void wave_slab_sync() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
 }
-
-struct ListKey {
-    const gmsx_graph *g = nullptr;
-    const int64_t *off = nullptr;
-    const int32_t *adj = nullptr;
-    int64_t n = -1, nnz = -1;
-    int part = -1, nparts = -1;
-    int64_t extra[2] = {0, 0};  // the call's own parameters (kcstar: k, flags)
-    ListKey() = default;
-    ListKey(const gmsx_graph *g_, int part_, int nparts_, int64_t e0 = 0, int64_t e1 = 0)
-        : g(g_), off(g_->off), adj(g_->adj), n(g_->n), nnz(g_->nnz), part(part_), nparts(nparts_), extra{e0, e1} {}
-    bool operator==(const ListKey &o) const {
-        return g == o.g && off == o.off && adj == o.adj && n == o.n && nnz == o.nnz && part == o.part && nparts == o.nparts && extra[0] == o.extra[0] &&
-               extra[1] == o.extra[1];
-    }
-};
 
 // pass 1 of the last call; an algorithm derives from it to add its info struct
 struct ListPass1 {
