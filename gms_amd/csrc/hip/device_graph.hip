@@ -1092,105 +1092,33 @@ static int grid_for_waves(int64_t rows) {
     return int(want < 1 ? 1 : (want > cap ? cap : want));
 }
 
+// an array that stays with the graph: the MEM_TRACE line, the TC_MEM_LIMIT_MB hook and device_bytes on top of dalloc (a temporary takes dalloc itself)
 template <class T>
-static int dmalloc(T **p, int64_t count, gmsx_graph *g, int line = __builtin_LINE()) {
+static int dmalloc(DevArr<T> &d, int64_t count, gmsx_graph *g, int line = __builtin_LINE()) {
     const size_t bytes = size_t(count > 0 ? count : 1) * sizeof(T);
     const bool trace = opt("MEM_TRACE") != nullptr;  // where the device bytes go: one line per allocation that stays with the graph
-    if (trace && g && bytes >= (1u << 20)) std::fprintf(stderr, "gmsx mem: device_graph.hip:%d %.3f GB (elements of %zu B)\n", line, double(bytes) * 1e-9, sizeof(T));
-    if (g && g->tc_building && g->tc_limit_bytes > 0 && g->device_bytes + int64_t(bytes) - g->tc_base_bytes > g->tc_limit_bytes) {
-        *p = nullptr;  // test hook: pretend the device is this small
-        return GMSX_ERR_DEVICE_MEM;
-    }
-    if (hipMalloc(reinterpret_cast<void **>(p), bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        return GMSX_ERR_DEVICE_MEM;
-    }
-    if (g) g->device_bytes += int64_t(bytes);
+    if (trace && bytes >= (1u << 20)) std::fprintf(stderr, "gmsx mem: device_graph.hip:%d %.3f GB (elements of %zu B)\n", line, double(bytes) * 1e-9, sizeof(T));
+    if (g->tc_building && g->tc_limit_bytes > 0 && g->device_bytes + int64_t(bytes) - g->tc_base_bytes > g->tc_limit_bytes)
+        return GMSX_ERR_DEVICE_MEM;  // test hook: pretend the device is this small
+    if (int rc = dalloc(d, count)) return rc;
+    g->device_bytes += int64_t(bytes);
     return GMSX_OK;
 }
 
-struct DevGuard {
-    void *p;
-    ~DevGuard() { (void)hipFree(p); }
-};
-
 // the triangle-count containers only (a failed or abandoned build_tc_sets leaves the base layout usable)
 static void free_tc(gmsx_graph *g) {
-    auto drop = [](auto *&p) {
-        (void)hipFree(p);
-        p = nullptr;
-    };
-    drop(g->tsplit); drop(g->srow); drop(g->srow2); drop(g->ksplit); drop(g->spool); drop(g->trow); drop(g->htask.lo); drop(g->htask.hi); drop(g->ttask.lo); drop(g->ttask.hi); drop(g->hitem); drop(g->titem); drop(g->tunits);
-    drop(g->ledge); drop(g->lpack); drop(g->tpool); drop(g->shard_hitem); drop(g->shard_titem); drop(g->core_bits);
-    g->tc_core = 0;
-    g->shard_idx_part = g->shard_idx_nparts = -1;
+    g->tc = TcContainers{};
     g->device_bytes -= g->tc_bytes;
     g->tc_bytes = 0;
     g->tc_ready = false;
-    g->htask_entries = g->ttask_entries = g->hitems = g->titems = g->inline_hentries = g->inline_tentries = 0;
-    g->n_ledge = g->ledge_total = 0;
-    for (int c = 0; c < 8; ++c) g->lpack_base[c] = g->lpack_n[c] = g->lpack_total[c] = 0;
-    g->task_reverse = g->inline_units = g->spool_units = g->tpool_units = g->gather_units = 0;
-    g->stats_part = g->stats_nparts = -1;
-}
-
-static void free_graph(gmsx_graph *g) {
-    if (!g) return;
-    (void)hipFree(g->off);
-    (void)hipFree(g->adj);
-    (void)hipFree(g->newid);
-    (void)hipFree(g->oldid);
-    (void)hipFree(g->hoff);
-    (void)hipFree(g->hadj);
-    (void)hipFree(g->toff);
-    (void)hipFree(g->tadj);
-    (void)hipFree(g->bmoff);
-    (void)hipFree(g->bmpool);
-    (void)hipFree(g->tsplit);
-    (void)hipFree(g->srow);
-    (void)hipFree(g->srow2);
-    (void)hipFree(g->ksplit);
-    (void)hipFree(g->spool);
-    (void)hipFree(g->trow);
-    (void)hipFree(g->htask.lo);
-    (void)hipFree(g->htask.hi);
-    (void)hipFree(g->ttask.lo);
-    (void)hipFree(g->ttask.hi);
-    (void)hipFree(g->hitem);
-    (void)hipFree(g->titem);
-    (void)hipFree(g->tunits);
-    (void)hipFree(g->shard_hitem);
-    (void)hipFree(g->shard_titem);
-    (void)hipFree(g->ledge);
-    (void)hipFree(g->lpack);
-    (void)hipFree(g->core_bits);
-    (void)hipFree(g->tpool);
-    (void)hipFree(g->dplus);
-    (void)hipFree(g->order);
-    (void)hipFree(g->kc_rel);
-    (void)hipFree(g->kc_aoff);
-    (void)hipFree(g->kc_arena);
-    (void)hipFree(g->kc_rec);
-    (void)hipFree(g->kc_item);
-    (void)hipFree(g->kc_relt);
-    (void)hipFree(g->kc_rect);
-    (void)hipFree(g->kc_itemt);
-    (void)hipFree(g->pr_bins);
-    (void)hipFree(g->pr_first);
-    (void)hipFree(g->pr_slot_row);
-    (void)hipFree(g->scratch);
-    (void)hipFree(g->acc);
-    delete g;
 }
 
 int exclusive_scan_i64(const int64_t *in, int64_t *out, int64_t count, hipStream_t s) {
     size_t tmp_bytes = 0;
     GMSX_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, in, out, int64_t(0), size_t(count), rocprim::plus<int64_t>(), s));
-    void *tmp = nullptr;
-    GMSX_HIP(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 8));
-    DevGuard g_tmp{tmp};
-    GMSX_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, in, out, int64_t(0), size_t(count), rocprim::plus<int64_t>(), s));
+    DevBuf tmp;
+    GMSX_HIP(hipMalloc(&tmp.p, tmp_bytes ? tmp_bytes : 8));
+    GMSX_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, in, out, int64_t(0), size_t(count), rocprim::plus<int64_t>(), s));
     GMSX_HIP(hipStreamSynchronize(s));
     return GMSX_OK;
 }
@@ -1208,21 +1136,20 @@ __global__ void k_lower_bound_i64(int64_t count, const int64_t *__restrict__ a, 
     }
     out[0] = lo;
 }
-template <class K>
-static int sort_rows(K *keys, int64_t entries, int64_t n, const int64_t *d_off, int end_bit, hipStream_t s) {
+// the walk: rows [v0, v1) = entries [base, base + cnt) at a time — as many whole rows as fit `chunk` entries, at least one — to sort_range
+template <class F>
+static int for_row_ranges(int64_t entries, int64_t n, const int64_t *d_off, hipStream_t s, F &&sort_range) {
     if (n <= 0 || entries <= 0) return GMSX_OK;
     int64_t chunk = int64_t(1) << 31;
     if (const char *e = opt("SORT_CHUNK")) {  // test hook: force several ranges on a small graph
         const long long v = std::atoll(e);
         if (v > 0) chunk = v;
     }
-    int64_t *d_v = nullptr;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&d_v), sizeof(int64_t)));
-    DevGuard g_v{d_v};
+    DevArr<int64_t> d_v;
+    GMSX_HIP(hipMalloc(&d_v.p, sizeof(int64_t)));
     GMSX_HIP(hipStreamSynchronize(s));  // the offsets are read with blocking copies below: whatever produced them must be done
     int64_t v0 = 0, base = 0;
     while (v0 < n) {
-        // the range [v0, v1): as many whole rows as fit below base + chunk, at least one
         int64_t v1 = n;
         if (entries - base > chunk) {
             hipLaunchKernelGGL(k_lower_bound_i64, dim3(1), dim3(1), 0, s, n + 1, d_off, base + chunk + 1, d_v);
@@ -1234,77 +1161,52 @@ static int sort_rows(K *keys, int64_t entries, int64_t n, const int64_t *d_off, 
         GMSX_HIP(hipMemcpy(&end, d_off + v1, sizeof(int64_t), hipMemcpyDeviceToHost));
         const int64_t cnt = end - base;
         if (cnt >= (int64_t(1) << 32)) return GMSX_ERR_UNSUPPORTED;  // one row of 2^32 entries: not a graph this library can hold
-        if (cnt > 0) {
-            K *sorted = nullptr;
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&sorted), size_t(cnt) * sizeof(K)));
-            DevGuard g_sorted{sorted};
-            auto begin = rocprim::make_transform_iterator(d_off + v0, OffsetMinus{base});
-            auto endit = rocprim::make_transform_iterator(d_off + v0 + 1, OffsetMinus{base});
-            size_t tmp_bytes = 0;
-            GMSX_HIP(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, keys + base, sorted, unsigned(cnt), unsigned(v1 - v0), begin, endit, 0, end_bit, s));
-            void *tmp = nullptr;
-            GMSX_HIP(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 8));
-            DevGuard g_tmp{tmp};
-            GMSX_HIP(rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, keys + base, sorted, unsigned(cnt), unsigned(v1 - v0), begin, endit, 0, end_bit, s));
-            GMSX_HIP(hipMemcpyAsync(keys + base, sorted, size_t(cnt) * sizeof(K), hipMemcpyDeviceToDevice, s));
-            GMSX_HIP(hipStreamSynchronize(s));
-        }
+        if (cnt > 0)
+            if (int rc = sort_range(v0, v1, base, cnt)) return rc;  // (synchronises before its buffers go)
         v0 = v1;
         base = end;
     }
     return GMSX_OK;
 }
+template <class K>
+static int sort_rows(K *keys, int64_t entries, int64_t n, const int64_t *d_off, int end_bit, hipStream_t s) {
+    return for_row_ranges(entries, n, d_off, s, [&](int64_t v0, int64_t v1, int64_t base, int64_t cnt) -> int {
+        DevArr<K> sorted;
+        GMSX_HIP(hipMalloc(&sorted.p, size_t(cnt) * sizeof(K)));
+        auto begin = rocprim::make_transform_iterator(d_off + v0, OffsetMinus{base});
+        auto endit = rocprim::make_transform_iterator(d_off + v0 + 1, OffsetMinus{base});
+        size_t tmp_bytes = 0;
+        GMSX_HIP(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, keys + base, sorted.get(), unsigned(cnt), unsigned(v1 - v0), begin, endit, 0, end_bit, s));
+        DevBuf tmp;
+        GMSX_HIP(hipMalloc(&tmp.p, tmp_bytes ? tmp_bytes : 8));
+        GMSX_HIP(rocprim::segmented_radix_sort_keys(tmp.p, tmp_bytes, keys + base, sorted.get(), unsigned(cnt), unsigned(v1 - v0), begin, endit, 0, end_bit, s));
+        GMSX_HIP(hipMemcpyAsync(keys + base, sorted, size_t(cnt) * sizeof(K), hipMemcpyDeviceToDevice, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        return GMSX_OK;
+    });
+}
 
 // the same for (key, value) pairs: values reordered in place by their keys, segment by segment
 template <class K, class V>
 static int sort_segment_pairs(K *keys, V *vals, int64_t entries, int64_t n, const int64_t *d_off, int end_bit, hipStream_t s) {
-    if (n <= 0 || entries <= 0) return GMSX_OK;
-    int64_t chunk = int64_t(1) << 31;
-    if (const char *e = opt("SORT_CHUNK")) {
-        const long long v = std::atoll(e);
-        if (v > 0) chunk = v;
-    }
-    int64_t *d_v = nullptr;
-    GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&d_v), sizeof(int64_t)));
-    DevGuard g_v{d_v};
-    GMSX_HIP(hipStreamSynchronize(s));  // the offsets are read with blocking copies below: whatever produced them must be done
-    int64_t v0 = 0, base = 0;
-    while (v0 < n) {
-        int64_t v1 = n;
-        if (entries - base > chunk) {
-            hipLaunchKernelGGL(k_lower_bound_i64, dim3(1), dim3(1), 0, s, n + 1, d_off, base + chunk + 1, d_v);
-            GMSX_HIP(hipStreamSynchronize(s));
-            GMSX_HIP(hipMemcpy(&v1, d_v, sizeof(int64_t), hipMemcpyDeviceToHost));
-            v1 = std::max(v0 + 1, std::min(n, v1 - 1));
-        }
-        int64_t end = 0;
-        GMSX_HIP(hipMemcpy(&end, d_off + v1, sizeof(int64_t), hipMemcpyDeviceToHost));
-        const int64_t cnt = end - base;
-        if (cnt >= (int64_t(1) << 32)) return GMSX_ERR_UNSUPPORTED;
-        if (cnt > 0) {
-            K *k_out = nullptr;
-            V *v_out = nullptr;
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&k_out), size_t(cnt) * sizeof(K)));
-            DevGuard g_ko{k_out};
-            GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&v_out), size_t(cnt) * sizeof(V)));
-            DevGuard g_vo{v_out};
-            auto begin = rocprim::make_transform_iterator(d_off + v0, OffsetMinus{base});
-            auto endit = rocprim::make_transform_iterator(d_off + v0 + 1, OffsetMinus{base});
-            size_t tmp_bytes = 0;
-            GMSX_HIP(rocprim::segmented_radix_sort_pairs(nullptr, tmp_bytes, keys + base, k_out, vals + base, v_out, unsigned(cnt), unsigned(v1 - v0), begin, endit, 0,
-                                                         end_bit, s));
-            void *tmp = nullptr;
-            GMSX_HIP(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 8));
-            DevGuard g_tmp{tmp};
-            GMSX_HIP(rocprim::segmented_radix_sort_pairs(tmp, tmp_bytes, keys + base, k_out, vals + base, v_out, unsigned(cnt), unsigned(v1 - v0), begin, endit, 0,
-                                                         end_bit, s));
-            GMSX_HIP(hipMemcpyAsync(vals + base, v_out, size_t(cnt) * sizeof(V), hipMemcpyDeviceToDevice, s));
-            GMSX_HIP(hipStreamSynchronize(s));
-        }
-        v0 = v1;
-        base = end;
-    }
-    return GMSX_OK;
+    return for_row_ranges(entries, n, d_off, s, [&](int64_t v0, int64_t v1, int64_t base, int64_t cnt) -> int {
+        DevArr<K> k_out;
+        DevArr<V> v_out;
+        GMSX_HIP(hipMalloc(&k_out.p, size_t(cnt) * sizeof(K)));
+        GMSX_HIP(hipMalloc(&v_out.p, size_t(cnt) * sizeof(V)));
+        auto begin = rocprim::make_transform_iterator(d_off + v0, OffsetMinus{base});
+        auto endit = rocprim::make_transform_iterator(d_off + v0 + 1, OffsetMinus{base});
+        size_t tmp_bytes = 0;
+        GMSX_HIP(rocprim::segmented_radix_sort_pairs(nullptr, tmp_bytes, keys + base, k_out.get(), vals + base, v_out.get(), unsigned(cnt), unsigned(v1 - v0), begin, endit, 0,
+                                                     end_bit, s));
+        DevBuf tmp;
+        GMSX_HIP(hipMalloc(&tmp.p, tmp_bytes ? tmp_bytes : 8));
+        GMSX_HIP(rocprim::segmented_radix_sort_pairs(tmp.p, tmp_bytes, keys + base, k_out.get(), vals + base, v_out.get(), unsigned(cnt), unsigned(v1 - v0), begin, endit, 0,
+                                                     end_bit, s));
+        GMSX_HIP(hipMemcpyAsync(vals + base, v_out, size_t(cnt) * sizeof(V), hipMemcpyDeviceToDevice, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        return GMSX_OK;
+    });
 }
 
 // GMSX_TIMING=1: phase times of the device-side builds on stderr (each mark synchronises the stream)
@@ -1382,8 +1284,8 @@ static int build_device_sets(gmsx_graph *g, uint32_t flags) {
     hipStream_t s = ctx().stream;
     PhaseTimer pt(s, "base build");
     const int64_t n = g->n;
-    if (int rc = dmalloc(&g->scratch, 16, g)) return rc;
-    if (int rc = dmalloc(&g->acc, kAccWords, g)) return rc;
+    if (int rc = dmalloc(g->scratch, 16, g)) return rc;
+    if (int rc = dmalloc(g->acc, kAccWords, g)) return rc;
     GMSX_HIP(hipMemsetAsync(g->scratch, 0, 16 * sizeof(unsigned long long), s));
 
     // 1. invariant check + Σ(d_u+d_v) + max degree
@@ -1414,21 +1316,18 @@ static int build_device_sets(gmsx_graph *g, uint32_t flags) {
     pt.mark("validate");
     const unsigned tb = unsigned((n + 255) / 256);
     // 2. rank ids: sort (degree, id) descending
-    if (int rc = dmalloc(&g->newid, n, g)) return rc;
-    if (int rc = dmalloc(&g->oldid, n, g)) return rc;
+    if (int rc = dmalloc(g->newid, n, g)) return rc;
+    if (int rc = dmalloc(g->oldid, n, g)) return rc;
     if (n > 0) {
-        unsigned long long *k_in = nullptr, *k_out = nullptr;
-        if (int rc = dmalloc(&k_in, n, nullptr)) return rc;
-        DevGuard g1{k_in};
-        if (int rc = dmalloc(&k_out, n, nullptr)) return rc;
-        DevGuard g2{k_out};
+        DevArr<unsigned long long> k_in, k_out;
+        if (int rc = dalloc(k_in, n)) return rc;
+        if (int rc = dalloc(k_out, n)) return rc;
         hipLaunchKernelGGL(k_rank_keys, dim3(tb), dim3(256), 0, s, n, g->off, k_in);
         size_t tmp_bytes = 0;
-        GMSX_HIP(rocprim::radix_sort_keys_desc(nullptr, tmp_bytes, k_in, k_out, size_t(n), 0, 64, s));
-        void *tmp = nullptr;
-        GMSX_HIP(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 8));
-        DevGuard g3{tmp};
-        GMSX_HIP(rocprim::radix_sort_keys_desc(tmp, tmp_bytes, k_in, k_out, size_t(n), 0, 64, s));
+        GMSX_HIP(rocprim::radix_sort_keys_desc(nullptr, tmp_bytes, k_in.get(), k_out.get(), size_t(n), 0, 64, s));
+        DevBuf tmp;
+        GMSX_HIP(hipMalloc(&tmp.p, tmp_bytes ? tmp_bytes : 8));
+        GMSX_HIP(rocprim::radix_sort_keys_desc(tmp.p, tmp_bytes, k_in.get(), k_out.get(), size_t(n), 0, 64, s));
         hipLaunchKernelGGL(k_assign_ids, dim3(tb), dim3(256), 0, s, n, k_out, g->oldid, g->newid);
         GMSX_HIP(hipStreamSynchronize(s));
     }
@@ -1438,26 +1337,24 @@ static int build_device_sets(gmsx_graph *g, uint32_t flags) {
     //    exercise the tail containers (0 = the production value kHub).
     int hub_limit = int((flags >> 8) & 0xffffu);
     if (hub_limit == 0 || hub_limit > kHub) hub_limit = kHub;
-    int64_t *hcnt = nullptr, *tcnt = nullptr;
-    if (int rc = dmalloc(&hcnt, n + 1, nullptr)) return rc;
-    DevGuard g_h{hcnt};
-    if (int rc = dmalloc(&tcnt, n + 1, nullptr)) return rc;
-    DevGuard g_t{tcnt};
+    DevArr<int64_t> hcnt, tcnt;
+    if (int rc = dalloc(hcnt, n + 1)) return rc;
+    if (int rc = dalloc(tcnt, n + 1)) return rc;
     GMSX_HIP(hipMemsetAsync(hcnt, 0, size_t(n + 1) * sizeof(int64_t), s));
     GMSX_HIP(hipMemsetAsync(tcnt, 0, size_t(n + 1) * sizeof(int64_t), s));
-    if (int rc = dmalloc(&g->dplus, n, g)) return rc;
+    if (int rc = dmalloc(g->dplus, n, g)) return rc;
     if (n > 0)
         hipLaunchKernelGGL(k_count_parts, dim3(grid_for_waves(n)), dim3(256), 0, s, n, g->off, g->adj, g->newid, hub_limit, hcnt, tcnt, g->dplus);
-    if (int rc = dmalloc(&g->hoff, n + 1, g)) return rc;
-    if (int rc = dmalloc(&g->toff, n + 1, g)) return rc;
+    if (int rc = dmalloc(g->hoff, n + 1, g)) return rc;
+    if (int rc = dmalloc(g->toff, n + 1, g)) return rc;
     if (int rc = exclusive_scan_i64(hcnt, g->hoff, n + 1, s)) return rc;
     if (int rc = exclusive_scan_i64(tcnt, g->toff, n + 1, s)) return rc;
     GMSX_HIP(hipMemcpy(&g->hub_entries, g->hoff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
     GMSX_HIP(hipMemcpy(&g->tail_entries, g->toff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
 
     // 4. containers (+16 bytes of slack each: the 16-byte row loads of the count kernels may overrun the last row)
-    if (int rc = dmalloc(&g->hadj, g->hub_entries + 8, g)) return rc;
-    if (int rc = dmalloc(&g->tadj, g->tail_entries + 4, g)) return rc;
+    if (int rc = dmalloc(g->hadj, g->hub_entries + 8, g)) return rc;
+    if (int rc = dmalloc(g->tadj, g->tail_entries + 4, g)) return rc;
     GMSX_HIP(hipMemsetAsync(g->hadj + g->hub_entries, 0xff, 8 * sizeof(uint16_t), s));
     GMSX_HIP(hipMemsetAsync(g->tadj + g->tail_entries, 0xff, 4 * sizeof(int32_t), s));
     if (n > 0)
@@ -1468,8 +1365,8 @@ static int build_device_sets(gmsx_graph *g, uint32_t flags) {
     // 4a. both containers of every row ascending by rank id (the 0xFFFF pad sorts last): "the members below v" are then the entries in
     //     front of v — what the inline rows, the cut of handed-over rows, the delta forms and the k-clique binary searches rely on.
     //     rocPRIM's segmented sort counts items in 32 bits, so the rows are sorted in vertex ranges of < 2^31 entries each.
-    if (int rc = sort_rows(g->hadj, g->hub_entries, n, g->hoff, 16, s)) return rc;
-    if (int rc = sort_rows(g->tadj, g->tail_entries, n, g->toff, 32, s)) return rc;
+    if (int rc = sort_rows(g->hadj.get(), g->hub_entries, n, g->hoff, 16, s)) return rc;
+    if (int rc = sort_rows(g->tadj.get(), g->tail_entries, n, g->toff, 32, s)) return rc;
     g->rows_sorted = true;
 
     pt.mark("row sorts");
@@ -1479,36 +1376,31 @@ static int build_device_sets(gmsx_graph *g, uint32_t flags) {
     g->bitset_limit = g->dense_limit;
     {
         const int32_t K = g->bitset_limit;
-        int64_t *sizes = nullptr;
-        if (int rc = dmalloc(&sizes, int64_t(K) + 1, nullptr)) return rc;
-        DevGuard g_sz{sizes};
-        if (int rc = dmalloc(&g->bmoff, int64_t(K) + 1, g)) return rc;
+        DevArr<int64_t> sizes;
+        if (int rc = dalloc(sizes, int64_t(K) + 1)) return rc;
+        if (int rc = dmalloc(g->bmoff, int64_t(K) + 1, g)) return rc;
         hipLaunchKernelGGL(k_dense_sizes, dim3(unsigned(K / 256 + 1)), dim3(256), 0, s, K, g->dplus, sizes);
         if (int rc = exclusive_scan_i64(sizes, g->bmoff, int64_t(K) + 1, s)) return rc;
         GMSX_HIP(hipMemcpy(&g->bmpool_words, g->bmoff + K, sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (int rc = dmalloc(&g->bmpool, g->bmpool_words + 4, g)) return rc;
+        if (int rc = dmalloc(g->bmpool, g->bmpool_words + 4, g)) return rc;
         GMSX_HIP(hipMemsetAsync(g->bmpool, 0, size_t(g->bmpool_words + 4) * sizeof(uint32_t), s));
         if (K > 0 && g->bmpool_words > 0)
             hipLaunchKernelGGL(k_dense_fill, dim3(grid_for_waves(K)), dim3(256), 0, s, K, g->hoff, g->hadj, g->toff, g->tadj, g->bmoff, g->bmpool);
     }
     pt.mark("bitsets");
     // 5. work-sorted launch order: rank ids by decreasing d+
-    if (int rc = dmalloc(&g->order, n, g)) return rc;
+    if (int rc = dmalloc(g->order, n, g)) return rc;
     if (n > 0) {
-        int32_t *keys_in = nullptr, *vals_in = nullptr, *keys_out = nullptr;  // (the sorted keys are dplus[order[i]]: not kept)
-        if (int rc = dmalloc(&keys_out, n, nullptr)) return rc;
-        DevGuard g_ko{keys_out};
-        if (int rc = dmalloc(&keys_in, n, nullptr)) return rc;
-        DevGuard g_ki{keys_in};
-        if (int rc = dmalloc(&vals_in, n, nullptr)) return rc;
-        DevGuard g_vi{vals_in};
+        DevArr<int32_t> keys_in, vals_in, keys_out;  // (the sorted keys are dplus[order[i]]: not kept)
+        if (int rc = dalloc(keys_out, n)) return rc;
+        if (int rc = dalloc(keys_in, n)) return rc;
+        if (int rc = dalloc(vals_in, n)) return rc;
         hipLaunchKernelGGL(k_order_keys, dim3(tb), dim3(256), 0, s, n, g->dplus, keys_in, vals_in);
         size_t tmp_bytes = 0;
-        GMSX_HIP(rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, keys_in, keys_out, vals_in, g->order, size_t(n), 0, 32, s));
-        void *tmp = nullptr;
-        GMSX_HIP(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 8));
-        DevGuard g_tmp{tmp};
-        GMSX_HIP(rocprim::radix_sort_pairs_desc(tmp, tmp_bytes, keys_in, keys_out, vals_in, g->order, size_t(n), 0, 32, s));
+        GMSX_HIP(rocprim::radix_sort_pairs_desc(nullptr, tmp_bytes, keys_in.get(), keys_out.get(), vals_in.get(), g->order.get(), size_t(n), 0, 32, s));
+        DevBuf tmp;
+        GMSX_HIP(hipMalloc(&tmp.p, tmp_bytes ? tmp_bytes : 8));
+        GMSX_HIP(rocprim::radix_sort_pairs_desc(tmp.p, tmp_bytes, keys_in.get(), keys_out.get(), vals_in.get(), g->order.get(), size_t(n), 0, 32, s));
         int32_t top = 0;
         GMSX_HIP(hipMemcpyAsync(&top, keys_out, sizeof(int32_t), hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
@@ -1534,9 +1426,8 @@ static int build_tc_sets(gmsx_graph *g) {
     const uint32_t flags = g->upload_flags;
     const int hub_limit = g->hub_limit;
     const unsigned tb = unsigned((n + 255) / 256);
-    int32_t *opos = nullptr;  // position of every vertex in `order`: the receiver index of a heavy pivot, and what shard_of() is evaluated on
-    if (int rc = dmalloc(&opos, n + 1, nullptr)) return rc;
-    DevGuard g_opos{opos};
+    DevArr<int32_t> opos;  // position of every vertex in `order`: the receiver index of a heavy pivot, and what shard_of() is evaluated on
+    if (int rc = dalloc(opos, n + 1)) return rc;
     if (n > 0) hipLaunchKernelGGL(k_opos, dim3(tb), dim3(256), 0, s, n, g->order, opos);
     // 4b'. THE CORE (device_graph.hpp).  GMSX_TC_CORE: 0 = none, N > 0 = the rank ids below N, -1 = choose_tc_core on the estimate of
     //      k_core_units; always clamped to the hub ids, n and kTcCoreCap; unset = kTcCoreDefault (host/tc_core_plan.hpp, with the measurements
@@ -1544,31 +1435,30 @@ static int build_tc_sets(gmsx_graph *g) {
     {
         long long want = kTcCoreDefault;
         if (const char *e = opt("TC_CORE")) want = std::atoll(e);
-        g->tc_core = 0;
-        if (want > 0) g->tc_core = tc_core_clamp(want, hub_limit, n);
+        g->tc.tc_core = 0;
+        if (want > 0) g->tc.tc_core = tc_core_clamp(want, hub_limit, n);
         else if (want < 0) {
             const int cap = tc_core_clamp(kTcCoreCap, hub_limit, n) / kTcCoreBucket * kTcCoreBucket;
             if (cap > 0) {
                 const int nbk = cap / kTcCoreBucket;
-                unsigned long long *bucket = nullptr;
-                if (int rc = dmalloc(&bucket, nbk, nullptr)) return rc;
-                DevGuard g_b{bucket};
+                DevArr<unsigned long long> bucket;
+                if (int rc = dalloc(bucket, nbk)) return rc;
                 GMSX_HIP(hipMemsetAsync(bucket, 0, size_t(nbk) * sizeof(unsigned long long), s));
                 hipLaunchKernelGGL(k_core_units, dim3(grid_for_waves(cap)), dim3(256), 0, s, cap, g->hoff, g->hadj, g->dplus, bucket);
                 std::vector<uint64_t> h(size_t(nbk), 0);
                 static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "bucket words");
                 GMSX_HIP(hipMemcpyAsync(h.data(), bucket, size_t(nbk) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
                 GMSX_HIP(hipStreamSynchronize(s));
-                g->tc_core = choose_tc_core(h, cap);
+                g->tc.tc_core = choose_tc_core(h, cap);
             }
         }
-        if (g->tc_core > 0) {
-            const int32_t K = g->tc_core;
+        if (g->tc.tc_core > 0) {
+            const int32_t K = g->tc.tc_core;
             const int WS = kc4m_stride(K);
             const int64_t words = int64_t(K) * WS + 8;
-            if (int rc = dmalloc(&g->core_bits, words, g)) return rc;
-            GMSX_HIP(hipMemsetAsync(g->core_bits, 0, size_t(words) * sizeof(uint32_t), s));
-            hipLaunchKernelGGL(k_core_fill, dim3(grid_for_waves(K)), dim3(256), 0, s, K, WS, g->hoff, g->hadj, g->core_bits);
+            if (int rc = dmalloc(g->tc.core_bits, words, g)) return rc;
+            GMSX_HIP(hipMemsetAsync(g->tc.core_bits, 0, size_t(words) * sizeof(uint32_t), s));
+            hipLaunchKernelGGL(k_core_fill, dim3(grid_for_waves(K)), dim3(256), 0, s, K, WS, g->hoff, g->hadj, g->tc.core_bits);
         }
     }
     pt.mark("core matrix");
@@ -1588,29 +1478,24 @@ static int build_tc_sets(gmsx_graph *g) {
         g->inline_limit = int32_t(std::min<int64_t>(n, std::max<int64_t>(want, g->dense_limit)));
         g->inline_first = kDefaultInlineFirst;
         if (const char *e = opt("TC_INLINE_FIRST")) g->inline_first = std::max(1, std::min(kInlineFirstMax, std::atoi(e)));  // A/B knob
-        if (int rc = dmalloc(&g->tsplit, n, g)) return rc;
-        if (n > 0) hipLaunchKernelGGL(k_tail_split, dim3(grid_for_waves(n)), dim3(256), 0, s, n, g->toff, g->tadj, g->inline_limit, g->tsplit);
+        if (int rc = dmalloc(g->tc.tsplit, n, g)) return rc;
+        if (n > 0) hipLaunchKernelGGL(k_tail_split, dim3(grid_for_waves(n)), dim3(256), 0, s, n, g->toff, g->tadj, g->inline_limit, g->tc.tsplit);
     }
 
     pt.mark("tail split");
     // 5b. sizes of the inline rows (4c): ids handed over per receiving vertex
     int64_t n_heavy = 0, n_work = 0;
-    unsigned long long *inl_h = nullptr, *inl_t = nullptr;  // [n + 1] ids per receiver, later the fill cursors
-    int64_t *ihoff = nullptr, *itoff = nullptr;             // [n + 1] first 16-byte unit of the receiver's inline rows (relative to the inline region)
-    if (int rc = dmalloc(&inl_h, n + 1, nullptr)) return rc;
-    DevGuard g_inl_h{inl_h};
-    if (int rc = dmalloc(&inl_t, n + 1, nullptr)) return rc;
-    DevGuard g_inl_t{inl_t};
-    if (int rc = dmalloc(&ihoff, n + 1, nullptr)) return rc;
-    DevGuard g_ihoff{ihoff};
-    if (int rc = dmalloc(&itoff, n + 1, nullptr)) return rc;
-    DevGuard g_itoff{itoff};
+    DevArr<unsigned long long> inl_h, inl_t;  // [n + 1] ids per receiver, later the fill cursors
+    DevArr<int64_t> ihoff, itoff;             // [n + 1] first 16-byte unit of the receiver's inline rows (relative to the inline region)
+    if (int rc = dalloc(inl_h, n + 1)) return rc;
+    if (int rc = dalloc(inl_t, n + 1)) return rc;
+    if (int rc = dalloc(ihoff, n + 1)) return rc;
+    if (int rc = dalloc(itoff, n + 1)) return rc;
     int64_t inline_h_units = 0, inline_t_units = 0;
     {
         if (n > 0) {
-            int64_t *d_cnt = nullptr;
-            if (int rc = dmalloc(&d_cnt, 2, nullptr)) return rc;
-            DevGuard g_c{d_cnt};
+            DevArr<int64_t> d_cnt;
+            if (int rc = dalloc(d_cnt, 2)) return rc;
             hipLaunchKernelGGL(k_count_ge, dim3(1), dim3(1), 0, s, n, g->order, g->dplus, int32_t(kHeavy), d_cnt);
             hipLaunchKernelGGL(k_count_ge, dim3(1), dim3(1), 0, s, n, g->order, g->dplus, int32_t(2), d_cnt + 1);
             GMSX_HIP(hipStreamSynchronize(s));
@@ -1623,22 +1508,20 @@ static int build_tc_sets(gmsx_graph *g) {
         GMSX_HIP(hipMemsetAsync(inl_t, 0, size_t(n + 1) * sizeof(unsigned long long), s));
         if (n_work > 0)
             hipLaunchKernelGGL(k_inline_rows<false>, dim3(grid_for_waves(n_work)), dim3(256), 0, s, int64_t(0), n_work, g->order, g->hoff, g->hadj,
-                               g->toff, g->tadj, g->dplus, g->inline_limit, g->inline_first, g->tc_core, opos, g->shard_nparts, g->shard_part, inl_h, inl_t, ihoff, itoff, int64_t(0), static_cast<uint16_t *>(nullptr),
+                               g->toff, g->tadj, g->dplus, g->inline_limit, g->inline_first, g->tc.tc_core, opos, g->shard_nparts, g->shard_part, inl_h, inl_t, ihoff, itoff, int64_t(0), static_cast<uint16_t *>(nullptr),
                                int64_t(0), static_cast<int32_t *>(nullptr));
-        int64_t *uh = nullptr, *ut = nullptr;
-        if (int rc = dmalloc(&uh, n + 1, nullptr)) return rc;
-        DevGuard g_uh{uh};
-        if (int rc = dmalloc(&ut, n + 1, nullptr)) return rc;
-        DevGuard g_ut{ut};
+        DevArr<int64_t> uh, ut;
+        if (int rc = dalloc(uh, n + 1)) return rc;
+        if (int rc = dalloc(ut, n + 1)) return rc;
         hipLaunchKernelGGL(k_inline_units, dim3(unsigned(n / 256 + 1)), dim3(256), 0, s, n, inl_h, inl_t, false, uh, ut);
         if (int rc = exclusive_scan_i64(uh, ihoff, n + 1, s)) return rc;
         if (int rc = exclusive_scan_i64(ut, itoff, n + 1, s)) return rc;
         GMSX_HIP(hipMemcpy(&inline_h_units, ihoff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
         GMSX_HIP(hipMemcpy(&inline_t_units, itoff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
-        g->inline_units = inline_h_units + inline_t_units;
+        g->tc.inline_units = inline_h_units + inline_t_units;
         if (g->tc_gather > 0) {
             // with gathered rows every row of the pools is whole lines from a line boundary on — the inline rows too: each receiver's starts on a
-            // boundary of the (line-aligned) inline region, at most 7 filler units behind its end (g->inline_units stays what the rows hold)
+            // boundary of the (line-aligned) inline region, at most 7 filler units behind its end (g->tc.inline_units stays what the rows hold)
             hipLaunchKernelGGL(k_inline_units, dim3(unsigned(n / 256 + 1)), dim3(256), 0, s, n, inl_h, inl_t, true, uh, ut);
             if (int rc = exclusive_scan_i64(uh, ihoff, n + 1, s)) return rc;
             if (int rc = exclusive_scan_i64(ut, itoff, n + 1, s)) return rc;
@@ -1676,41 +1559,35 @@ static int build_tc_sets(gmsx_graph *g) {
             const int v = std::atoi(e);
             if (v >= 0 && v <= 2 && g->rows_sorted) hybrid_mode = v;
         }
-        int64_t *units = nullptr, *uoff = nullptr, *small = nullptr, *soff = nullptr;
-        uint32_t *real = nullptr;
-        unsigned char *form = nullptr;
+        DevArr<int64_t> units, uoff, small, soff;
+        DevArr<uint32_t> real;
+        DevArr<unsigned char> form;
         const int64_t n2 = 2 * n;  // two slots per row
-        if (int rc = dmalloc(&units, n2 + 1, nullptr)) return rc;
-        DevGuard g_u{units};
-        if (int rc = dmalloc(&uoff, n2 + 1, nullptr)) return rc;
-        DevGuard g_o{uoff};
-        if (int rc = dmalloc(&small, n2 + 1, nullptr)) return rc;
-        DevGuard g_s{small};
-        if (int rc = dmalloc(&soff, n2 + 1, nullptr)) return rc;
-        DevGuard g_so{soff};
-        if (int rc = dmalloc(&real, n2 + 1, nullptr)) return rc;
-        DevGuard g_r{real};
-        if (int rc = dmalloc(&form, n2 + 1, nullptr)) return rc;
-        DevGuard g_f{form};
-        if (int rc = dmalloc(&g->ksplit, n + 1, g)) return rc;
+        if (int rc = dalloc(units, n2 + 1)) return rc;
+        if (int rc = dalloc(uoff, n2 + 1)) return rc;
+        if (int rc = dalloc(small, n2 + 1)) return rc;
+        if (int rc = dalloc(soff, n2 + 1)) return rc;
+        if (int rc = dalloc(real, n2 + 1)) return rc;
+        if (int rc = dalloc(form, n2 + 1)) return rc;
+        if (int rc = dmalloc(g->tc.ksplit, n + 1, g)) return rc;
         hipLaunchKernelGGL(k_srow_sizes, dim3(unsigned(n / 256 + 1)), dim3(256), 0, s, n, g->hoff, g->hadj, g->dplus, g->dense_limit, delta_mode, delta_pct, gap12_mode,
-                           hybrid_mode, units, small, real, form, g->ksplit);
+                           hybrid_mode, units, small, real, form, g->tc.ksplit);
         if (int rc = exclusive_scan_i64(units, uoff, n2 + 1, s)) return rc;
         if (int rc = exclusive_scan_i64(small, soff, n2 + 1, s)) return rc;
         int64_t big_units = 0, small_units = 0;
         GMSX_HIP(hipMemcpy(&big_units, uoff + n2, sizeof(int64_t), hipMemcpyDeviceToHost));
         GMSX_HIP(hipMemcpy(&small_units, soff + n2, sizeof(int64_t), hipMemcpyDeviceToHost));
         inline_h_base = g->tc_gather > 0 ? int64_t(gather_region_units(uint64_t(big_units + small_units))) : big_units + small_units;
-        g->spool_units = inline_h_base + inline_h_units;
-        if (g->spool_units >= (int64_t(1) << 40)) return GMSX_ERR_DEVICE_MEM;  // 40 offset bits in a srow entry (16 TB)
-        if (int rc = dmalloc(&g->srow, n, g)) return rc;
-        if (int rc = dmalloc(&g->srow2, n, g)) return rc;
-        if (int rc = dmalloc(&g->spool, (g->spool_units + kPoolSlack) * 4, g)) return rc;  // + slack: the scans load whole lane groups past a row's end
-        GMSX_HIP(hipMemsetAsync(g->spool, 0, size_t((g->spool_units + kPoolSlack) * 4) * sizeof(uint32_t), s));  // the alignment gaps are never read, but keep them defined
-        if (inline_h_units > 0) GMSX_HIP(hipMemsetAsync(g->spool + inline_h_base * 4, 0xff, size_t(inline_h_units) * 16, s));  // list filler 0xFFFF
+        g->tc.spool_units = inline_h_base + inline_h_units;
+        if (g->tc.spool_units >= (int64_t(1) << 40)) return GMSX_ERR_DEVICE_MEM;  // 40 offset bits in a srow entry (16 TB)
+        if (int rc = dmalloc(g->tc.srow, n, g)) return rc;
+        if (int rc = dmalloc(g->tc.srow2, n, g)) return rc;
+        if (int rc = dmalloc(g->tc.spool, (g->tc.spool_units + kPoolSlack) * 4, g)) return rc;  // + slack: the scans load whole lane groups past a row's end
+        GMSX_HIP(hipMemsetAsync(g->tc.spool, 0, size_t((g->tc.spool_units + kPoolSlack) * 4) * sizeof(uint32_t), s));  // the alignment gaps are never read, but keep them defined
+        if (inline_h_units > 0) GMSX_HIP(hipMemsetAsync(g->tc.spool + inline_h_base * 4, 0xff, size_t(inline_h_units) * 16, s));  // list filler 0xFFFF
         if (n > 0)
             hipLaunchKernelGGL(k_srow_fill, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, n, g->hoff, g->hadj, g->bmoff, g->bmpool, uoff, soff, real, form,
-                               g->ksplit, g->srow, g->srow2, g->spool);
+                               g->tc.ksplit, g->tc.srow, g->tc.srow2, g->tc.spool);
         GMSX_HIP(hipStreamSynchronize(s));
     }
     // 4e. … and of the tail parts
@@ -1720,21 +1597,15 @@ static int build_tc_sets(gmsx_graph *g) {
             const int v = std::atoi(e);
             if (v >= 0 && v <= 2 && g->rows_sorted) delta_mode = v;
         }
-        int64_t *units = nullptr, *uoff = nullptr, *small = nullptr, *soff = nullptr;
-        uint32_t *real = nullptr;
-        unsigned char *form = nullptr;
-        if (int rc = dmalloc(&units, n + 1, nullptr)) return rc;
-        DevGuard g_u{units};
-        if (int rc = dmalloc(&uoff, n + 1, nullptr)) return rc;
-        DevGuard g_o{uoff};
-        if (int rc = dmalloc(&small, n + 1, nullptr)) return rc;
-        DevGuard g_s{small};
-        if (int rc = dmalloc(&soff, n + 1, nullptr)) return rc;
-        DevGuard g_so{soff};
-        if (int rc = dmalloc(&real, n + 1, nullptr)) return rc;
-        DevGuard g_r{real};
-        if (int rc = dmalloc(&form, n + 1, nullptr)) return rc;
-        DevGuard g_f{form};
+        DevArr<int64_t> units, uoff, small, soff;
+        DevArr<uint32_t> real;
+        DevArr<unsigned char> form;
+        if (int rc = dalloc(units, n + 1)) return rc;
+        if (int rc = dalloc(uoff, n + 1)) return rc;
+        if (int rc = dalloc(small, n + 1)) return rc;
+        if (int rc = dalloc(soff, n + 1)) return rc;
+        if (int rc = dalloc(real, n + 1)) return rc;
+        if (int rc = dalloc(form, n + 1)) return rc;
         hipLaunchKernelGGL(k_trow_sizes, dim3(unsigned(n / 256 + 1)), dim3(256), 0, s, n, g->toff, g->tadj, delta_mode, units, small, real, form);
         if (int rc = exclusive_scan_i64(units, uoff, n + 1, s)) return rc;
         if (int rc = exclusive_scan_i64(small, soff, n + 1, s)) return rc;
@@ -1742,13 +1613,13 @@ static int build_tc_sets(gmsx_graph *g) {
         GMSX_HIP(hipMemcpy(&big_units, uoff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
         GMSX_HIP(hipMemcpy(&small_units, soff + n, sizeof(int64_t), hipMemcpyDeviceToHost));
         inline_t_base = g->tc_gather > 0 ? int64_t(gather_region_units(uint64_t(big_units + small_units))) : big_units + small_units;
-        g->tpool_units = inline_t_base + inline_t_units;
-        if (g->tpool_units >= (int64_t(1) << 40)) return GMSX_ERR_DEVICE_MEM;
-        if (int rc = dmalloc(&g->trow, n, g)) return rc;
-        if (int rc = dmalloc(&g->tpool, (g->tpool_units + kPoolSlack) * 4, g)) return rc;
-        GMSX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g->tpool), int(0xFFFFFFFEu), size_t(g->tpool_units + kPoolSlack) * 4, s));  // filler -2 (alignment gaps, inline rows, the slack the scans may load)
+        g->tc.tpool_units = inline_t_base + inline_t_units;
+        if (g->tc.tpool_units >= (int64_t(1) << 40)) return GMSX_ERR_DEVICE_MEM;
+        if (int rc = dmalloc(g->tc.trow, n, g)) return rc;
+        if (int rc = dmalloc(g->tc.tpool, (g->tc.tpool_units + kPoolSlack) * 4, g)) return rc;
+        GMSX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g->tc.tpool.get()), int(0xFFFFFFFEu), size_t(g->tc.tpool_units + kPoolSlack) * 4, s));  // filler -2 (alignment gaps, inline rows, the slack the scans may load)
         if (n > 0)
-            hipLaunchKernelGGL(k_trow_fill, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, n, g->toff, g->tadj, uoff, soff, real, form, g->trow, g->tpool);
+            hipLaunchKernelGGL(k_trow_fill, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, n, g->toff, g->tadj, uoff, soff, real, form, g->tc.trow, g->tc.tpool);
         GMSX_HIP(hipStreamSynchronize(s));
     }
 
@@ -1758,8 +1629,8 @@ static int build_tc_sets(gmsx_graph *g) {
         GMSX_HIP(hipMemsetAsync(inl_h, 0, size_t(n + 1) * sizeof(unsigned long long), s));  // now the fill cursors
         GMSX_HIP(hipMemsetAsync(inl_t, 0, size_t(n + 1) * sizeof(unsigned long long), s));
         hipLaunchKernelGGL(k_inline_rows<true>, dim3(grid_for_waves(n_work)), dim3(256), 0, s, int64_t(0), n_work, g->order, g->hoff, g->hadj, g->toff,
-                           g->tadj, g->dplus, g->inline_limit, g->inline_first, g->tc_core, opos, g->shard_nparts, g->shard_part, inl_h, inl_t, ihoff, itoff, inline_h_base, reinterpret_cast<uint16_t *>(g->spool),
-                           inline_t_base, reinterpret_cast<int32_t *>(g->tpool));
+                           g->tadj, g->dplus, g->inline_limit, g->inline_first, g->tc.tc_core, opos, g->shard_nparts, g->shard_part, inl_h, inl_t, ihoff, itoff, inline_h_base, reinterpret_cast<uint16_t *>(g->tc.spool.get()),
+                           inline_t_base, reinterpret_cast<int32_t *>(g->tc.tpool.get()));
     }
     pt.mark("inline rows fill");
     // (the ids arrive in the inline rows through atomic cursors, in any order — and stay so: a receiver's inline rows are scanned whole by
@@ -1768,19 +1639,17 @@ static int build_tc_sets(gmsx_graph *g) {
     // 5e. light edges (k_tc_light): count per light pivot -> scan -> fill (the same list on every rank: built with a scan)
     {
         const int64_t nl = n_work - n_heavy;
-        g->n_ledge = g->ledge_total = 0;
+        g->tc.n_ledge = g->tc.ledge_total = 0;
         g->light_packed = opt_int("TC_LIGHT_PACKED", 1) != 0;  // 0 (A/B): the 32-byte pointer records and k_tc_light
-        for (int c = 0; c < 8; ++c) g->lpack_base[c] = g->lpack_n[c] = g->lpack_total[c] = 0;
+        for (int c = 0; c < 8; ++c) g->tc.lpack_base[c] = g->tc.lpack_n[c] = g->tc.lpack_total[c] = 0;
         if (nl > 0 && g->light_packed) {
-            int64_t *ecnt = nullptr, *ebeg = nullptr;
+            DevArr<int64_t> ecnt, ebeg;
             const int64_t cells = int64_t(kLightClasses) * nl;
-            if (int rc = dmalloc(&ecnt, cells + 1, nullptr)) return rc;
-            DevGuard g_ec{ecnt};
-            if (int rc = dmalloc(&ebeg, cells + 1, nullptr)) return rc;
-            DevGuard g_eb{ebeg};
+            if (int rc = dalloc(ecnt, cells + 1)) return rc;
+            if (int rc = dalloc(ebeg, cells + 1)) return rc;
             GMSX_HIP(hipMemsetAsync(ecnt + cells, 0, sizeof(int64_t), s));
-            hipLaunchKernelGGL(k_lpack_count, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->tsplit, g->dplus,
-                               g->tc_core, ecnt);
+            hipLaunchKernelGGL(k_lpack_count, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->tc.tsplit, g->dplus,
+                               g->tc.tc_core, ecnt);
             if (int rc = exclusive_scan_i64(ecnt, ebeg, cells + 1, s)) return rc;
             const int np = g->shard_nparts > 1 ? g->shard_nparts : 1, pp = g->shard_nparts > 1 ? g->shard_part : 0;
             LpackPlan plan{};
@@ -1792,40 +1661,38 @@ static int build_tc_sets(gmsx_graph *g) {
                 const int64_t total = b[1] - b[0], full = total / np, rem = total % np;  // whole stripes of np blocks + this shard's share of the partial one
                 plan.class_beg[c] = b[0];
                 plan.unit_base[c] = units;
-                g->lpack_total[c] = total;
-                g->lpack_n[c] = np <= 1 ? total : full + (((full & 1) ? np - 1 - pp : pp) < rem ? 1 : 0);
-                g->lpack_base[c] = units;
-                units += g->lpack_n[c] * light_shape(c).stride();
-                g->ledge_total += total;
-                g->n_ledge += g->lpack_n[c];
+                g->tc.lpack_total[c] = total;
+                g->tc.lpack_n[c] = np <= 1 ? total : full + (((full & 1) ? np - 1 - pp : pp) < rem ? 1 : 0);
+                g->tc.lpack_base[c] = units;
+                units += g->tc.lpack_n[c] * light_shape(c).stride();
+                g->tc.ledge_total += total;
+                g->tc.n_ledge += g->tc.lpack_n[c];
             }
             if (opt("MEM_TRACE"))
                 for (int c = 0; c < kLightClasses; ++c) {
                     const LightShape k = light_shape(c);
                     std::fprintf(stderr, "gmsx light class %d (ids <= %d / %d / %d / %d, %d units): %lld blocks\n", c, 8 * k.ah, 4 * k.at, 8 * k.bh, 4 * k.bt, k.stride(),
-                                 (long long)g->lpack_total[c]);
+                                 (long long)g->tc.lpack_total[c]);
                 }
-            if (int rc = dmalloc(&g->lpack, units + 1, g)) return rc;
-            hipLaunchKernelGGL(k_lpack_fill, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->tsplit, g->dplus,
-                               g->tc_core, ebeg, plan, np, pp, g->lpack);
+            if (int rc = dmalloc(g->tc.lpack, units + 1, g)) return rc;
+            hipLaunchKernelGGL(k_lpack_fill, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->tc.tsplit, g->dplus,
+                               g->tc.tc_core, ebeg, plan, np, pp, g->tc.lpack);
             GMSX_HIP(hipStreamSynchronize(s));
         } else if (nl > 0) {
-            int64_t *ecnt = nullptr, *ebeg = nullptr;
-            if (int rc = dmalloc(&ecnt, nl + 1, nullptr)) return rc;
-            DevGuard g_ec{ecnt};
-            if (int rc = dmalloc(&ebeg, nl + 1, nullptr)) return rc;
-            DevGuard g_eb{ebeg};
-            hipLaunchKernelGGL(k_ledge_count, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->toff, g->tadj, g->tsplit, g->dplus, g->tc_core, ecnt);
+            DevArr<int64_t> ecnt, ebeg;
+            if (int rc = dalloc(ecnt, nl + 1)) return rc;
+            if (int rc = dalloc(ebeg, nl + 1)) return rc;
+            hipLaunchKernelGGL(k_ledge_count, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->toff, g->tadj, g->tc.tsplit, g->dplus, g->tc.tc_core, ecnt);
             if (int rc = exclusive_scan_i64(ecnt, ebeg, nl + 1, s)) return rc;
-            GMSX_HIP(hipMemcpy(&g->ledge_total, ebeg + nl, sizeof(int64_t), hipMemcpyDeviceToHost));
+            GMSX_HIP(hipMemcpy(&g->tc.ledge_total, ebeg + nl, sizeof(int64_t), hipMemcpyDeviceToHost));
             const int np = g->shard_nparts > 1 ? g->shard_nparts : 1, pp = g->shard_nparts > 1 ? g->shard_part : 0;
             {
-                const int64_t full = g->ledge_total / np, rem = g->ledge_total % np;  // whole stripes of np edges + this shard's share of the partial one
-                g->n_ledge = np <= 1 ? g->ledge_total : full + (((full & 1) ? np - 1 - pp : pp) < rem ? 1 : 0);
+                const int64_t full = g->tc.ledge_total / np, rem = g->tc.ledge_total % np;  // whole stripes of np edges + this shard's share of the partial one
+                g->tc.n_ledge = np <= 1 ? g->tc.ledge_total : full + (((full & 1) ? np - 1 - pp : pp) < rem ? 1 : 0);
             }
-            if (int rc = dmalloc(&g->ledge, 2 * g->n_ledge + 2, g)) return rc;
-            hipLaunchKernelGGL(k_ledge_fill, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->hoff, g->toff, g->tadj, g->tsplit, g->dplus, g->tc_core, ebeg,
-                               np, pp, g->ledge);
+            if (int rc = dmalloc(g->tc.ledge, 2 * g->tc.n_ledge + 2, g)) return rc;
+            hipLaunchKernelGGL(k_ledge_fill, dim3(unsigned(nl / 256 + 1)), dim3(256), 0, s, n_heavy, n_work, g->order, g->hoff, g->toff, g->tadj, g->tc.tsplit, g->dplus, g->tc.tc_core, ebeg,
+                               np, pp, g->tc.ledge);
             GMSX_HIP(hipStreamSynchronize(s));
         }
     }
@@ -1839,19 +1706,16 @@ static int build_tc_sets(gmsx_graph *g) {
         const unsigned vb = unsigned(n / 256 + 1);
         // light receivers: rank ids below inline_limit that are not heavy
         const int64_t L = g->inline_limit;
-        int64_t *lflag = nullptr, *lidx = nullptr;
-        if (int rc = dmalloc(&lflag, L + 1, nullptr)) return rc;
-        DevGuard g_lf{lflag};
-        if (int rc = dmalloc(&lidx, L + 1, nullptr)) return rc;
-        DevGuard g_li{lidx};
+        DevArr<int64_t> lflag, lidx;
+        if (int rc = dalloc(lflag, L + 1)) return rc;
+        if (int rc = dalloc(lidx, L + 1)) return rc;
         hipLaunchKernelGGL(k_light_flags, dim3(unsigned(L / 256 + 1)), dim3(256), 0, s, L, g->dplus, lflag);
         if (int rc = exclusive_scan_i64(lflag, lidx, L + 1, s)) return rc;
         int64_t n_light_recv = 0;
         GMSX_HIP(hipMemcpy(&n_light_recv, lidx + L, sizeof(int64_t), hipMemcpyDeviceToHost));
         const int64_t n_recv = n_heavy + n_light_recv;
-        int32_t *recv_v = nullptr;
-        if (int rc = dmalloc(&recv_v, n_recv + 1, nullptr)) return rc;
-        DevGuard g_rv{recv_v};
+        DevArr<int32_t> recv_v;
+        if (int rc = dalloc(recv_v, n_recv + 1)) return rc;
         if (std::max<int64_t>(n_heavy, L) > 0)
             hipLaunchKernelGGL(k_recv_vertices, dim3(unsigned(std::max<int64_t>(n_heavy, L) / 256 + 1)), dim3(256), 0, s, n_heavy, L, g->order, g->dplus, lidx, recv_v);
         // hot windows of the hub lists (device_graph.hpp): GMSX_TC_HOT_WINDOWS x GMSX_TC_HOT_KB of the pool's front, GMSX_TC_HOT_MIN entries
@@ -1863,66 +1727,55 @@ static int build_tc_sets(gmsx_graph *g) {
         }
         const TcClasses cc{g->tc_hot_windows, g->tc_window_units, g->tc_hot_min};
         const int kClasses = cc.count();
-        uint32_t *cnt = nullptr, *cur = nullptr;
-        if (int rc = dmalloc(&cnt, n_recv * kClasses + 1, nullptr)) return rc;
-        DevGuard g_cnt{cnt};
-        if (int rc = dmalloc(&cur, n_recv * kClasses + 1, nullptr)) return rc;
-        DevGuard g_cur{cur};
+        DevArr<uint32_t> cnt, cur;
+        if (int rc = dalloc(cnt, n_recv * kClasses + 1)) return rc;
+        if (int rc = dalloc(cur, n_recv * kClasses + 1)) return rc;
         GMSX_HIP(hipMemsetAsync(cnt, 0, size_t(n_recv * kClasses + 1) * sizeof(uint32_t), s));
         GMSX_HIP(hipMemsetAsync(cur, 0, size_t(n_recv * kClasses + 1) * sizeof(uint32_t), s));
-        if (int rc = dmalloc(&g->tunits, n_heavy + 1, g)) return rc;  // only heavy pivots keep or receive entries of edges: by position in `order`
-        GMSX_HIP(hipMemsetAsync(g->tunits, 0, size_t(n_heavy + 1) * sizeof(int32_t), s));
-        unsigned long long *totals = nullptr;  // [0] hub inline entries [1] tail inline entries [2] reversed edges [3] rows too long for a task entry [4] units in gathered rows
-        if (int rc = dmalloc(&totals, 5, nullptr)) return rc;
-        DevGuard g_tot{totals};
+        if (int rc = dmalloc(g->tc.tunits, n_heavy + 1, g)) return rc;  // only heavy pivots keep or receive entries of edges: by position in `order`
+        GMSX_HIP(hipMemsetAsync(g->tc.tunits, 0, size_t(n_heavy + 1) * sizeof(int32_t), s));
+        DevArr<unsigned long long> totals;  // [0] hub inline entries [1] tail inline entries [2] reversed edges [3] rows too long for a task entry [4] units in gathered rows
+        if (int rc = dalloc(totals, 5)) return rc;
         GMSX_HIP(hipMemsetAsync(totals, 0, 5 * sizeof(unsigned long long), s));
         // gathered rows (device_graph.hpp): GMSX_TC_GATHER = R, the longest remainder behind a row's last line boundary that moves (0 = none)
         GatherPlan gp{};
         gp.R = g->tc_gather;  // (build_tc_once: the option, or the default and what it falls back to when the device is short of memory)
-        g->gather_units = 0;
-        int64_t *ghsize = nullptr, *gtsize = nullptr, *ghoff = nullptr, *gtoff = nullptr;
-        DevGuard g_gu{nullptr}, g_gc{nullptr}, g_ghs{nullptr}, g_gts{nullptr}, g_gho{nullptr}, g_gto{nullptr};
+        g->tc.gather_units = 0;
+        DevArr<uint32_t> gunits, gcur;
+        DevArr<int64_t> ghsize, gtsize, ghoff, gtoff;
         if (gp.R > 0) {
-            if (int rc = dmalloc(&gp.gunits, 4 * n_recv + 1, nullptr)) return rc;
-            g_gu.p = gp.gunits;
-            if (int rc = dmalloc(&gp.gcur, 4 * n_recv + 1, nullptr)) return rc;
-            g_gc.p = gp.gcur;
-            if (int rc = dmalloc(&ghsize, 2 * n_recv + 1, nullptr)) return rc;
-            g_ghs.p = ghsize;
-            if (int rc = dmalloc(&gtsize, 2 * n_recv + 1, nullptr)) return rc;
-            g_gts.p = gtsize;
-            if (int rc = dmalloc(&ghoff, 2 * n_recv + 1, nullptr)) return rc;
-            g_gho.p = ghoff;
-            if (int rc = dmalloc(&gtoff, 2 * n_recv + 1, nullptr)) return rc;
-            g_gto.p = gtoff;
+            if (int rc = dalloc(gunits, 4 * n_recv + 1)) return rc;
+            if (int rc = dalloc(gcur, 4 * n_recv + 1)) return rc;
+            if (int rc = dalloc(ghsize, 2 * n_recv + 1)) return rc;
+            if (int rc = dalloc(gtsize, 2 * n_recv + 1)) return rc;
+            if (int rc = dalloc(ghoff, 2 * n_recv + 1)) return rc;
+            if (int rc = dalloc(gtoff, 2 * n_recv + 1)) return rc;
+            gp.gunits = gunits;
+            gp.gcur = gcur;
             GMSX_HIP(hipMemsetAsync(gp.gunits, 0, size_t(4 * n_recv + 1) * sizeof(uint32_t), s));
             GMSX_HIP(hipMemsetAsync(gp.gcur, 0, size_t(4 * n_recv + 1) * sizeof(uint32_t), s));
         }
-        int64_t *hcnt = nullptr, *tcnt = nullptr, *hbeg = nullptr, *tbeg = nullptr;
-        if (int rc = dmalloc(&hcnt, n_recv + 1, nullptr)) return rc;
-        DevGuard g_hc{hcnt};
-        if (int rc = dmalloc(&tcnt, n_recv + 1, nullptr)) return rc;
-        DevGuard g_tc{tcnt};
-        if (int rc = dmalloc(&hbeg, n_recv + 1, nullptr)) return rc;
-        DevGuard g_hb{hbeg};
-        if (int rc = dmalloc(&tbeg, n_recv + 1, nullptr)) return rc;
-        DevGuard g_tb{tbeg};
+        DevArr<int64_t> hcnt, tcnt, hbeg, tbeg;
+        if (int rc = dalloc(hcnt, n_recv + 1)) return rc;
+        if (int rc = dalloc(tcnt, n_recv + 1)) return rc;
+        if (int rc = dalloc(hbeg, n_recv + 1)) return rc;
+        if (int rc = dalloc(tbeg, n_recv + 1)) return rc;
         const int grid = grid_for_waves(n_heavy);
         // a task entry has 32 bits for the first unit of its row and 14 / 15 for the row's units (TaskList)
-        if (g->spool_units + kPoolSlack >= (int64_t(1) << 32) || g->tpool_units + kPoolSlack >= (int64_t(1) << 32)) return GMSX_ERR_DEVICE_MEM;
+        if (g->tc.spool_units + kPoolSlack >= (int64_t(1) << 32) || g->tc.tpool_units + kPoolSlack >= (int64_t(1) << 32)) return GMSX_ERR_DEVICE_MEM;
         {
             uint32_t hub_max = kTaskHubUnitsMax, tail_max = kTaskTailUnitsMax;
             if (const char *e = opt("TC_TEST_MAX_UNITS")) hub_max = tail_max = uint32_t(std::max(1, std::atoi(e)));  // test hook: pretend the fields are this narrow
-            if (n > 0) hipLaunchKernelGGL(k_task_limits, dim3(vb), dim3(256), 0, s, n, g->srow, g->srow2, g->trow, hub_max, tail_max, totals + 3);
+            if (n > 0) hipLaunchKernelGGL(k_task_limits, dim3(vb), dim3(256), 0, s, n, g->tc.srow, g->tc.srow2, g->tc.trow, hub_max, tail_max, totals + 3);
         }
         // COUNT
         if (n > 0)
             hipLaunchKernelGGL(k_inline_entries<false>, dim3(vb), dim3(256), 0, s, n, g->dplus, opos, lidx, n_heavy, g->inline_limit, ihoff, itoff, inl_h, inl_t, inline_h_base,
                                inline_t_base, cnt, cur, hbeg, tbeg, TaskList{}, TaskList{}, totals, cc);
         if (n_heavy > 0)
-            hipLaunchKernelGGL(k_task_lists<false>, dim3(grid), dim3(256), 0, s, n_heavy, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->srow, g->srow2, g->ksplit, g->trow,
-                               two_sided, opos, cnt, cur, hbeg, tbeg, TaskList{}, TaskList{}, g->tunits,
-                               totals + 2, g->spool, g->tpool, g->inline_limit, g->inline_first, g->tc_core, g->shard_nparts, g->shard_part, cc, gp);
+            hipLaunchKernelGGL(k_task_lists<false>, dim3(grid), dim3(256), 0, s, n_heavy, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->tc.srow, g->tc.srow2, g->tc.ksplit, g->tc.trow,
+                               two_sided, opos, cnt, cur, hbeg, tbeg, TaskList{}, TaskList{}, g->tc.tunits,
+                               totals + 2, g->tc.spool, g->tc.tpool, g->inline_limit, g->inline_first, g->tc.tc_core, g->shard_nparts, g->shard_part, cc, gp);
         if (gp.R > 0) {
             // the regions of the gathered rows: whole lines each, receiver by receiver behind the (line-rounded) end of the pool; the pools grow by them
             hipLaunchKernelGGL(k_gather_sizes, dim3(unsigned(2 * n_recv / 256 + 1)), dim3(256), 0, s, n_recv, gp.gunits, ghsize, gtsize, totals + 4);
@@ -1933,32 +1786,30 @@ static int build_tc_sets(gmsx_graph *g) {
             GMSX_HIP(hipMemcpy(&gt_units, gtoff + 2 * n_recv, sizeof(int64_t), hipMemcpyDeviceToHost));
             gp.hoff = ghoff;
             gp.toff = gtoff;
-            gp.hreg = int64_t(gather_region_units(uint64_t(g->spool_units)));
-            gp.treg = int64_t(gather_region_units(uint64_t(g->tpool_units)));
+            gp.hreg = int64_t(gather_region_units(uint64_t(g->tc.spool_units)));
+            gp.treg = int64_t(gather_region_units(uint64_t(g->tc.tpool_units)));
             if (gp.hreg + gh_units + kPoolSlack >= (int64_t(1) << 32) || gp.treg + gt_units + kPoolSlack >= (int64_t(1) << 32)) return GMSX_ERR_DEVICE_MEM;  // the grown pools, as above
             // grow: a new pool with the old one's bytes in front, the filler of the pool (0 / -2) behind them, then the old one goes
-            auto grow = [&](uint32_t *&pool, int64_t &pool_units, int64_t reg, int64_t extra, uint32_t filler) -> int {
+            auto grow = [&](DevArr<uint32_t> &pool, int64_t &pool_units, int64_t reg, int64_t extra, uint32_t filler) -> int {
                 if (extra == 0) return GMSX_OK;
-                uint32_t *bigger = nullptr;
+                DevArr<uint32_t> bigger;
                 const int64_t units = reg + extra;
-                if (int rc = dmalloc(&bigger, (units + kPoolSlack) * 4, g)) return rc;
-                DevGuard g_b{bigger};
+                if (int rc = dmalloc(bigger, (units + kPoolSlack) * 4, g)) return rc;
                 GMSX_HIP(hipMemcpyAsync(bigger, pool, size_t(pool_units) * 16, hipMemcpyDeviceToDevice, s));
                 // (every unit of a region is written later — the moved units by FILL, the rest of its last line by k_gather_entries: only the gap in
                 //  front of the regions and the slack behind them are set here)
                 if (reg > pool_units) GMSX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(bigger + pool_units * 4), int(filler), size_t(reg - pool_units) * 4, s));
                 GMSX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(bigger + units * 4), int(filler), size_t(kPoolSlack) * 4, s));
                 GMSX_HIP(hipStreamSynchronize(s));
-                g_b.p = pool;  // the guard frees the old pool
+                std::swap(pool, bigger);  // the old pool goes with `bigger`
                 g->device_bytes -= (pool_units + kPoolSlack) * 16;
-                pool = bigger;
                 pool_units = units;
                 return GMSX_OK;
             };
-            if (int rc = grow(g->spool, g->spool_units, gp.hreg, gh_units, 0u)) return rc;
-            if (int rc = grow(g->tpool, g->tpool_units, gp.treg, gt_units, 0xFFFFFFFEu)) return rc;
-            gp.spool = reinterpret_cast<uint4 *>(g->spool);
-            gp.tpool = reinterpret_cast<uint4 *>(g->tpool);
+            if (int rc = grow(g->tc.spool, g->tc.spool_units, gp.hreg, gh_units, 0u)) return rc;
+            if (int rc = grow(g->tc.tpool, g->tc.tpool_units, gp.treg, gt_units, 0xFFFFFFFEu)) return rc;
+            gp.spool = reinterpret_cast<uint4 *>(g->tc.spool.get());
+            gp.tpool = reinterpret_cast<uint4 *>(g->tc.tpool.get());
             if (n_recv > 0)
                 hipLaunchKernelGGL(k_gather_entries<false>, dim3(unsigned(n_recv / 256 + 1)), dim3(256), 0, s, n_recv, gp.gunits, ghoff, gtoff, gp.hreg, gp.treg, cnt, cur, hbeg,
                                    tbeg, TaskList{}, TaskList{}, gp.spool, gp.tpool, cc);
@@ -1969,50 +1820,50 @@ static int build_tc_sets(gmsx_graph *g) {
         if (int rc = exclusive_scan_i64(hcnt, hbeg, n_recv + 1, s)) return rc;
         if (int rc = exclusive_scan_i64(tcnt, tbeg, n_recv + 1, s)) return rc;
         unsigned long long tot[4] = {0, 0, 0, 0};
-        GMSX_HIP(hipMemcpy(&g->htask_entries, hbeg + n_recv, sizeof(int64_t), hipMemcpyDeviceToHost));
-        GMSX_HIP(hipMemcpy(&g->ttask_entries, tbeg + n_recv, sizeof(int64_t), hipMemcpyDeviceToHost));
+        GMSX_HIP(hipMemcpy(&g->tc.htask_entries, hbeg + n_recv, sizeof(int64_t), hipMemcpyDeviceToHost));
+        GMSX_HIP(hipMemcpy(&g->tc.ttask_entries, tbeg + n_recv, sizeof(int64_t), hipMemcpyDeviceToHost));
         GMSX_HIP(hipMemcpy(tot, totals, sizeof(tot), hipMemcpyDeviceToHost));
         if (tot[3]) return GMSX_ERR_UNSUPPORTED;  // a row of > 16 383 hub / 32 767 tail units (no graph that fits the device has one): not a matter of memory — building a share of the pivots at a time would not help
-        g->inline_hentries = int64_t(tot[0]);
-        g->inline_tentries = int64_t(tot[1]);
-        g->task_reverse = int64_t(tot[2]);
-        if (gp.R > 0) GMSX_HIP(hipMemcpy(&g->gather_units, totals + 4, sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (g->htask_entries >= (int64_t(1) << 40) || g->ttask_entries >= (int64_t(1) << 40)) return GMSX_ERR_DEVICE_MEM;  // 40 position bits in a work item
-        if (int rc = dmalloc(&g->htask.lo, g->htask_entries + 2, g)) return rc;
-        if (int rc = dmalloc(&g->htask.hi, g->htask_entries + 2, g)) return rc;
-        if (int rc = dmalloc(&g->ttask.lo, g->ttask_entries + 2, g)) return rc;
-        if (int rc = dmalloc(&g->ttask.hi, g->ttask_entries + 2, g)) return rc;
+        g->tc.inline_hentries = int64_t(tot[0]);
+        g->tc.inline_tentries = int64_t(tot[1]);
+        g->tc.task_reverse = int64_t(tot[2]);
+        if (gp.R > 0) GMSX_HIP(hipMemcpy(&g->tc.gather_units, totals + 4, sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (g->tc.htask_entries >= (int64_t(1) << 40) || g->tc.ttask_entries >= (int64_t(1) << 40)) return GMSX_ERR_DEVICE_MEM;  // 40 position bits in a work item
+        if (int rc = dmalloc(g->tc.htask_lo, g->tc.htask_entries + 2, g)) return rc;
+        if (int rc = dmalloc(g->tc.htask_hi, g->tc.htask_entries + 2, g)) return rc;
+        if (int rc = dmalloc(g->tc.ttask_lo, g->tc.ttask_entries + 2, g)) return rc;
+        if (int rc = dmalloc(g->tc.ttask_hi, g->tc.ttask_entries + 2, g)) return rc;
+        g->tc.htask = TaskList{g->tc.htask_lo, g->tc.htask_hi, false};
+        g->tc.ttask = TaskList{g->tc.ttask_lo, g->tc.ttask_hi, true};
         // FILL
         if (n > 0)
             hipLaunchKernelGGL(k_inline_entries<true>, dim3(vb), dim3(256), 0, s, n, g->dplus, opos, lidx, n_heavy, g->inline_limit, ihoff, itoff, inl_h, inl_t, inline_h_base,
-                               inline_t_base, cnt, cur, hbeg, tbeg, g->htask, g->ttask, totals, cc);
+                               inline_t_base, cnt, cur, hbeg, tbeg, g->tc.htask, g->tc.ttask, totals, cc);
         if (n_heavy > 0)
-            hipLaunchKernelGGL(k_task_lists<true>, dim3(grid), dim3(256), 0, s, n_heavy, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->srow, g->srow2, g->ksplit, g->trow,
-                               two_sided, opos, cnt, cur, hbeg, tbeg, g->htask, g->ttask, g->tunits, totals + 2, g->spool, g->tpool, g->inline_limit, g->inline_first, g->tc_core, g->shard_nparts, g->shard_part, cc, gp);
+            hipLaunchKernelGGL(k_task_lists<true>, dim3(grid), dim3(256), 0, s, n_heavy, g->order, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->tc.srow, g->tc.srow2, g->tc.ksplit, g->tc.trow,
+                               two_sided, opos, cnt, cur, hbeg, tbeg, g->tc.htask, g->tc.ttask, g->tc.tunits, totals + 2, g->tc.spool, g->tc.tpool, g->inline_limit, g->inline_first, g->tc.tc_core, g->shard_nparts, g->shard_part, cc, gp);
         if (gp.R > 0 && n_recv > 0)
             hipLaunchKernelGGL(k_gather_entries<true>, dim3(unsigned(n_recv / 256 + 1)), dim3(256), 0, s, n_recv, gp.gunits, ghoff, gtoff, gp.hreg, gp.treg, cnt, cur, hbeg,
-                               tbeg, g->htask, g->ttask, gp.spool, gp.tpool, cc);
+                               tbeg, g->tc.htask, g->tc.ttask, gp.spool, gp.tpool, cc);
         pt.mark("task lists fill");
         // work items
         const int hub_phases = cc.hub_phases();
         const int64_t slots = int64_t(hub_phases) * n_recv;
-        int64_t *icnt = nullptr, *ioff = nullptr;
-        if (int rc = dmalloc(&icnt, slots + 1, nullptr)) return rc;
-        DevGuard g_ic{icnt};
-        if (int rc = dmalloc(&ioff, slots + 1, nullptr)) return rc;
-        DevGuard g_io{ioff};
+        DevArr<int64_t> icnt, ioff;
+        if (int rc = dalloc(icnt, slots + 1)) return rc;
+        if (int rc = dalloc(ioff, slots + 1)) return rc;
         const unsigned rb = unsigned(n_recv / 256 + 1);
         hipLaunchKernelGGL(k_item_counts, dim3(rb), dim3(256), 0, s, n_recv, hbeg, cnt, cc, hub_phases, icnt);
         if (int rc = exclusive_scan_i64(icnt, ioff, slots + 1, s)) return rc;
-        GMSX_HIP(hipMemcpy(&g->hitems, ioff + slots, sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (int rc = dmalloc(&g->hitem, g->hitems + 1, g)) return rc;
-        if (n_recv > 0) hipLaunchKernelGGL(k_item_fill, dim3(rb), dim3(256), 0, s, n_recv, recv_v, opos, hbeg, ioff, g->htask, g->hoff, 0, cnt, cc, hub_phases, g->hitem);
+        GMSX_HIP(hipMemcpy(&g->tc.hitems, ioff + slots, sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (int rc = dmalloc(g->tc.hitem, g->tc.hitems + 1, g)) return rc;
+        if (n_recv > 0) hipLaunchKernelGGL(k_item_fill, dim3(rb), dim3(256), 0, s, n_recv, recv_v, opos, hbeg, ioff, g->tc.htask, g->hoff, 0, cnt, cc, hub_phases, g->tc.hitem);
         hipLaunchKernelGGL(k_item_counts, dim3(rb), dim3(256), 0, s, n_recv, tbeg, cnt, cc, 1, icnt);
         if (int rc = exclusive_scan_i64(icnt, ioff, n_recv + 1, s)) return rc;
-        GMSX_HIP(hipMemcpy(&g->titems, ioff + n_recv, sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (int rc = dmalloc(&g->titem, g->titems + 1, g)) return rc;
-        if (n_recv > 0) hipLaunchKernelGGL(k_item_fill, dim3(rb), dim3(256), 0, s, n_recv, recv_v, opos, tbeg, ioff, g->ttask, g->toff, 1, cnt, cc, 1, g->titem);
-        if (g->hitems >= (int64_t(1) << 31) || g->titems >= (int64_t(1) << 31)) return GMSX_ERR_DEVICE_MEM;  // 32-bit queue tickets
+        GMSX_HIP(hipMemcpy(&g->tc.titems, ioff + n_recv, sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (int rc = dmalloc(g->tc.titem, g->tc.titems + 1, g)) return rc;
+        if (n_recv > 0) hipLaunchKernelGGL(k_item_fill, dim3(rb), dim3(256), 0, s, n_recv, recv_v, opos, tbeg, ioff, g->tc.ttask, g->toff, 1, cnt, cc, 1, g->tc.titem);
+        if (g->tc.hitems >= (int64_t(1) << 31) || g->tc.titems >= (int64_t(1) << 31)) return GMSX_ERR_DEVICE_MEM;  // 32-bit queue tickets
         GMSX_HIP(hipStreamSynchronize(s));
     }
     pt.mark("work items");
@@ -2021,23 +1872,22 @@ static int build_tc_sets(gmsx_graph *g) {
     // what only the BUILD read — the tail split, the second descriptors and the split points of hybrid rows — does not stay on the device
     // (16 bytes per vertex: 1.07 GB at scale 26); build_tc_once takes tc_bytes from device_bytes afterwards, so the bookkeeping follows
     {
-        auto drop = [&](auto *&p, size_t bytes) {
-            if (!p) return;
-            (void)hipFree(p);
-            p = nullptr;
+        auto drop = [&](DevBuf &d, size_t bytes) {
+            if (!d.p) return;
+            d.reset();
             g->device_bytes -= int64_t(bytes);
         };
         const size_t nn = size_t(n > 0 ? n : 1);
-        drop(g->tsplit, nn * sizeof(int32_t));
-        drop(g->srow2, nn * sizeof(unsigned long long));
+        drop(g->tc.tsplit, nn * sizeof(int32_t));
+        drop(g->tc.srow2, nn * sizeof(unsigned long long));
         // the first descriptors too: every task entry carries its own copy, and only gmsx_tc_row_histogram's what-if estimates read them
         // afterwards (GMSX_TC_KEEP_ROWS=1 keeps them for tools/tc_row_hist.py)
         const char *keep = opt("TC_KEEP_ROWS");
         if (!(keep && std::atoi(keep) != 0)) {
-            drop(g->srow, nn * sizeof(unsigned long long));
-            drop(g->trow, nn * sizeof(unsigned long long));
+            drop(g->tc.srow, nn * sizeof(unsigned long long));
+            drop(g->tc.trow, nn * sizeof(unsigned long long));
         }
-        drop(g->ksplit, size_t(n + 1) * sizeof(int32_t));
+        drop(g->tc.ksplit, size_t(n + 1) * sizeof(int32_t));
     }
     return GMSX_OK;
 }
@@ -2104,32 +1954,27 @@ __global__ void k_shard_scatter(int64_t n_items, const int64_t *__restrict__ fla
     if (i < n_items && flags[i]) out[slot[i]] = items[i];
 }
 int tc_shard_items(const gmsx_graph *g, int part, int nparts) {
-    if (g->shard_idx_part == part && g->shard_idx_nparts == nparts) return GMSX_OK;
+    if (g->tc.shard.part == part && g->tc.shard.nparts == nparts) return GMSX_OK;
     hipStream_t s = ctx().stream;
-    (void)hipFree(g->shard_hitem);
-    (void)hipFree(g->shard_titem);
-    g->shard_hitem = g->shard_titem = nullptr;
-    g->shard_idx_part = g->shard_idx_nparts = -1;
-    auto one = [&](const gmsx_tc_item *items, int64_t n_items, gmsx_tc_item **idx, int64_t *count) -> int {
+    g->tc.shard = TcContainers::ShardItems{};
+    auto one = [&](const gmsx_tc_item *items, int64_t n_items, DevArr<gmsx_tc_item> &idx, int64_t *count) -> int {
         *count = 0;
         if (n_items == 0) return GMSX_OK;
-        int64_t *flags = nullptr, *slot = nullptr;
-        if (int rc = dmalloc(&flags, n_items + 1, nullptr)) return rc;
-        DevGuard g_f{flags};
-        if (int rc = dmalloc(&slot, n_items + 1, nullptr)) return rc;
-        DevGuard g_s{slot};
+        DevArr<int64_t> flags, slot;
+        if (int rc = dalloc(flags, n_items + 1)) return rc;
+        if (int rc = dalloc(slot, n_items + 1)) return rc;
         hipLaunchKernelGGL(k_shard_flags, dim3(unsigned(n_items / 256 + 1)), dim3(256), 0, s, n_items, items, nparts, part, flags);
         if (int rc = exclusive_scan_i64(flags, slot, n_items + 1, s)) return rc;
         GMSX_HIP(hipMemcpy(count, slot + n_items, sizeof(int64_t), hipMemcpyDeviceToHost));
-        if (int rc = dmalloc(idx, *count + 1, nullptr)) return rc;
-        hipLaunchKernelGGL(k_shard_scatter, dim3(unsigned(n_items / 256 + 1)), dim3(256), 0, s, n_items, flags, slot, items, *idx);
+        if (int rc = dalloc(idx, *count + 1)) return rc;
+        hipLaunchKernelGGL(k_shard_scatter, dim3(unsigned(n_items / 256 + 1)), dim3(256), 0, s, n_items, flags, slot, items, idx);
         GMSX_HIP(hipStreamSynchronize(s));
         return GMSX_OK;
     };
-    if (int rc = one(g->hitem, g->hitems, &g->shard_hitem, &g->shard_hitems)) return rc;
-    if (int rc = one(g->titem, g->titems, &g->shard_titem, &g->shard_titems)) return rc;
-    g->shard_idx_part = part;
-    g->shard_idx_nparts = nparts;
+    if (int rc = one(g->tc.hitem, g->tc.hitems, g->tc.shard.hitem, &g->tc.shard.hitems)) return rc;
+    if (int rc = one(g->tc.titem, g->tc.titems, g->tc.shard.titem, &g->tc.shard.titems)) return rc;
+    g->tc.shard.part = part;
+    g->tc.shard.nparts = nparts;
     return GMSX_OK;
 }
 
@@ -2247,8 +2092,7 @@ int gmsx_graph_upload_shard(int64_t n, const int64_t *offsets, const int32_t *ne
         if (!out || n < 0 || !offsets || n > 0x7fffffffll || nparts < 1 || part < 0 || part >= nparts) return GMSX_ERR_INVALID;
         if (offsets[0] != 0 || offsets[n] < 0 || (offsets[n] > 0 && !neigh)) return GMSX_ERR_INVALID;
         if (int rc = ensure_init()) return rc;
-        struct Free { void operator()(gmsx_graph *p) const { free_graph(p); } };
-        std::unique_ptr<gmsx_graph, Free> owner(new (std::nothrow) gmsx_graph);  // freed on every way out, an exception in a build step included
+        std::unique_ptr<gmsx_graph> owner(new (std::nothrow) gmsx_graph);  // freed on every way out, an exception in a build step included
         gmsx_graph *g = owner.get();
         if (!g) return GMSX_ERR_NOMEM;
         static std::atomic<uint64_t> uploads{0};  // every upload ends here: one counter for the process
@@ -2257,8 +2101,8 @@ int gmsx_graph_upload_shard(int64_t n, const int64_t *offsets, const int32_t *ne
         g->nnz = offsets[n];
         g->shard_part = part;
         g->shard_nparts = nparts;
-        int rc = dmalloc(&g->off, n + 1, g);
-        if (!rc) rc = dmalloc(&g->adj, g->nnz, g);
+        int rc = dmalloc(g->off, n + 1, g);
+        if (!rc) rc = dmalloc(g->adj, g->nnz, g);
         if (!rc) {
             hipStream_t s = ctx().stream;
             PhaseTimer pt(s, "h2d");
@@ -2305,7 +2149,7 @@ int gmsx_graph_tc_passes(const gmsx_graph *g) { return !g ? GMSX_ERR_INVALID : (
 
 int gmsx_graph_free(gmsx_graph *g) {
     return gmsx::guard([&]() -> int {
-        free_graph(g);
+        delete g;  // every array goes with its owner
         return GMSX_OK;
     });
 }

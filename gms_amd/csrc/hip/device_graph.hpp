@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "device_buffer.hpp"
 #include "gmsx.h"
@@ -14,7 +15,7 @@
 // steered into a miscount — neither by a macro that slipped into EXTRA nor by the environment (tests/test_capi_symbols.py checks the strings).
 #if !defined(GMSX_DEV_HOOKS) &&                                                                                                               \
     (defined(GMSX_KC_NO_PROBE) || defined(GMSX_KC_NO_HITS) || defined(GMSX_KC_NO_TAIL) || defined(GMSX_KC_NO_INNER) || defined(GMSX_KC_CELLS_ONLY) ||   \
-     defined(GMSX_KC_NO_ROWS) || defined(GMSX_KC_BUILD_ONLY) || defined(GMSX_KC_NO_SLAB_CALL) || defined(GMSX_KC_NO_PAIRS) || defined(GMSX_KC_SLAB_ROW_SCAN) || \
+     defined(GMSX_KC_NO_ROWS) || defined(GMSX_KC_BUILD_ONLY) || defined(GMSX_KC_NO_SLAB_CALL) || \
      defined(GMSX_BK_AB) || defined(GMSX_BK_NO_HIT_ATOMICS) || defined(GMSX_BK_STATS) || defined(GMSX_TC_NO_PROBE) || defined(GMSX_TC_STAGING_ONLY))
 #error "A/B switches need -DGMSX_DEV_HOOKS (tools/ab_lib.sh sets it); the default build of libgmsx.so carries none of them"
 #endif
@@ -80,21 +81,9 @@ struct TaskList {
         hi[i] = uint16_t(first >> 16);
     }
 };
-struct gmsx_graph {
-    uint64_t serial = 0;  // which upload of this process this is (from 1 on; gmsx_graph_upload_shard): what a cache keyed on a handle compares, addresses repeat
-    int64_t n = 0, nnz = 0, m = 0;
-    int64_t *off = nullptr;
-    int32_t *adj = nullptr;
-    int32_t *newid = nullptr;
-    int32_t *oldid = nullptr;
-    int64_t *hoff = nullptr;
-    uint16_t *hadj = nullptr;
-    int64_t *toff = nullptr;
-    int32_t *tadj = nullptr;
-    int64_t *bmoff = nullptr;   // [dense_limit + 1] word offsets into bmpool (multiples of 4); equal neighbours = not dense
-    uint32_t *bmpool = nullptr; // bitset containers of the dense hub rows
-    int32_t dense_limit = 0;    // = min(n, hub limit): hub rank ids; their rows have a bitset AND only hub entries
-    int32_t bitset_limit = 0;   // = dense_limit: every rank id below it has a bitset container over [0, v) in bmpool
+// THE TRIANGLE-COUNT CONTAINERS of a graph (stream rows, inline rows, task lists, work items, light edges, core …; built on demand by
+// ensure_tc(), device_graph.hip) and what is cached about them.  One lifetime: a failed, abandoned or replaced build is `tc = TcContainers{}`.
+struct TcContainers {
     // STREAM ROWS (triangle kernels): the hub part of every row once more, in the form that is cheapest to stream,
     // every row a whole number of 16-byte units (padded with neutral fillers, so the scanners need no tail handling) at a 16-byte
     // aligned offset of ONE pool; srow[v] packs (offset / 16) << 24 | form << 22 | units into 8 bytes = one load per row fetch.
@@ -104,13 +93,17 @@ struct gmsx_graph {
     //                            14 ids per unit when gaps < 256: 1.14 B/id against 2 B/id
     //   form 3  12-bit gaps      unit = 16-bit base id + 4-bit count + nine 12-bit gaps; a gap above 4095 ends the unit early.
     //                            10 ids per unit = 1.6 B/id: the sparse rows (gaps of 256 … 4095) that would otherwise stay lists
-    unsigned long long *srow = nullptr;  // [n]
-    unsigned long long *srow2 = nullptr; // [n] second descriptor of a HYBRID row (0 otherwise): srow = prefix bitmap over [0, B), srow2 = the ids from B on
-    int32_t *ksplit = nullptr;           // [n] ids of the row below B (0 = not hybrid)
-    uint32_t *spool = nullptr;           // 16-byte units
+    gmsx::DevArr<unsigned long long> srow;  // [n]
+    gmsx::DevArr<unsigned long long> srow2; // [n] second descriptor of a HYBRID row (0 otherwise): srow = prefix bitmap over [0, B), srow2 = the ids from B on
+    gmsx::DevArr<int32_t> ksplit;           // [n] ids of the row below B (0 = not hybrid)
+    gmsx::DevArr<uint32_t> spool;           // 16-byte units
     int64_t spool_units = 0;
     // … and the TAIL part of every row the same way (trow / tpool): form 0 = 32-bit ids, 4 per unit, filler -2 (never a key of a
     // pivot's tail set); form 2 = 16-bit delta: 32-bit base, count, five 16-bit gaps — 6 ids per unit, 2.67 B/id against 4 B/id
+    gmsx::DevArr<unsigned long long> trow;
+    gmsx::DevArr<uint32_t> tpool;
+    int64_t tpool_units = 0;
+    gmsx::DevArr<int32_t> tsplit;  // int32[n]: position in the tail row of the first target >= inline_limit (= tail length if none)
     // TASK LISTS (tc.hip).  |N+(u) ∩ N+(v)| of an oriented edge (u,v) can be counted with either endpoint as the pivot (its row as bitmap +
     // tail set in LDS) and the other one streamed; the pass streams the SMALLER row (fewer 16-byte units).  So every receiving vertex w
     // owns two lists of stream-row descriptors (6 bytes each: TaskList) — HUB entries (rows probed against w's bitmap) and TAIL entries (rows probed against
@@ -122,23 +115,28 @@ struct gmsx_graph {
     // arrival order of atomic cursors — it differs from process to process, which is why a multi-GPU shard is a set of whole PIVOTS.
     TaskList htask{nullptr, nullptr, false};  // hub entries of all receivers, receiver by receiver (in `order`), class by class
     TaskList ttask{nullptr, nullptr, true};   // tail entries likewise
+    gmsx::DevArr<uint32_t> htask_lo, ttask_lo;  // the arrays the two views above point into (a TaskList goes to the kernels by value)
+    gmsx::DevArr<uint16_t> htask_hi, ttask_hi;
     int64_t htask_entries = 0, ttask_entries = 0;
-    struct gmsx_tc_item *hitem = nullptr, *titem = nullptr;  // work items over htask / ttask
+    gmsx::DevArr<gmsx_tc_item> hitem, titem;  // work items over htask / ttask
     int64_t hitems = 0, titems = 0;
     int64_t inline_hentries = 0, inline_tentries = 0;  // of which: chunks of inline rows
     // gmsx_tc_partial(part, nparts) on a FULL upload: the work items of that shard, compacted on demand (cached for the last
     // (part, nparts)), so that a shard walks its own items only
-    mutable struct gmsx_tc_item *shard_hitem = nullptr, *shard_titem = nullptr;
-    mutable int64_t shard_hitems = 0, shard_titems = 0;
-    mutable int shard_idx_part = -1, shard_idx_nparts = -1;
-    int32_t *tunits = nullptr;           // [heavy pivots, by position in `order`] oriented edges whose entries live at this pivot (forward + reverse): the bookkeeping of gmsx_stats.units
+    struct ShardItems {
+        gmsx::DevArr<gmsx_tc_item> hitem, titem;
+        int64_t hitems = 0, titems = 0;
+        int part = -1, nparts = -1;
+    };
+    mutable ShardItems shard;
+    gmsx::DevArr<int32_t> tunits;        // [heavy pivots, by position in `order`] oriented edges whose entries live at this pivot (forward + reverse): the bookkeeping of gmsx_stats.units
     int64_t task_reverse = 0;            // edges handed over to the other endpoint
     // LIGHT EDGES (round 4, k_tc_light): the oriented edges (u, v) no work item covers — u light (2 <= d+ < kHeavy), v a FAR LIGHT member of it
     // (rank id >= inline_limit, d+ < kHeavy) — as self-contained 32-byte records: where the hub part and the tail part of u's row and of
     // v's row lie in hadj / tadj (first id, 40 bits | ids << 40; of u's tail part only the ids in front of v: nothing else can be in N+(v)).
     // Both rows are short (< 64 ids), so the edge is ONE all-pairs comparison in registers: no LDS, no per-pivot state, every edge
     // independent.  Edge e of the (deterministic) list belongs to shard shard_of(e, nparts) — the pivots' rule; a sharded upload keeps its own at slot e / nparts.
-    uint4 *ledge = nullptr;
+    gmsx::DevArr<uint4> ledge;
     int64_t n_ledge = 0, ledge_total = 0;
     // PACKED LIGHT EDGES (GMSX_TC_LIGHT_PACKED=1, the default; k_tc_lpack): the same edges in the same order, but every edge as one BLOCK of
     // whole 16-byte units that holds the ids themselves — u's hub ids, u's tail ids in front of v, v's hub ids, v's tail ids (16-bit / 32-bit
@@ -149,17 +147,72 @@ struct gmsx_graph {
     // tail part, 0xFFFFFFFE in v's (rank ids are < 2^31).  A block carries no header: the fillers make the lengths redundant.  Within a class
     // the blocks follow the enumeration order of `ledge` (count per pivot and class -> scan -> fill: no atomics); block k of a class belongs
     // to shard shard_of(k, nparts), a sharded upload keeps its own at slot k / nparts.  With the option on `ledge` is not built.
-    uint4 *lpack = nullptr;
+    gmsx::DevArr<uint4> lpack;
     int64_t lpack_base[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // first unit of class c
     int64_t lpack_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // blocks of class c held here
     int64_t lpack_total[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // … in the whole list (= lpack_n unless this is a sharded upload)
-    bool light_packed = false;
     // CORE (k_tc_core, tc.hip): the oriented edges (u, v) with rank id u < tc_core.  v and all of N+(v) lie below u, so the sum of their
     // intersect_counts is Σ_ij L_ij (L Lᵀ)_ij on the strictly lower-triangular tc_core x tc_core bit matrix L of those rows — a masked bit-GEMM
     // on the matrix cores (kc4_mfma.hpp) instead of streamed rows.  Such an edge has no task entry, no inline copy and no light-edge record.
     // core_bits: tc_core rows of kc4m_stride(tc_core) words, row i = the ids of N+(i), zero beyond its last bit; whole on every shard.
-    uint32_t *core_bits = nullptr;
+    gmsx::DevArr<uint32_t> core_bits;
     int32_t tc_core = 0;                 // 0 = no core (GMSX_TC_CORE)
+    int64_t inline_units = 0;            // 16-byte units of all inline rows (inside spool / tpool)
+    int64_t gather_units = 0;            // 16-byte units moved into gathered rows (inside spool / tpool, behind the inline rows)
+    mutable int stats_part = -1, stats_nparts = -1;  // shard whose TC bookkeeping (units, probes) is cached below
+    mutable uint64_t stats_units = 0, stats_probes = 0, stats_bytes = 0;
+};
+// k-clique REVERSE ROWS (round 6; kclique.hip, ensure_kc_reverse — built at the first k-clique call, like the triangle-count task lists).  The BUILD
+// needs rows[i] = N+(v_i) ∩ N+(u) for every member v_i of every pivot u.  Forward it streams N+(v_i) against u's bitmap; but nothing of N+(v_i)
+// above v_i's predecessors can hit, and for a HUB member w = v_i the same bits come from the other side: the i members below w — a prefix of u's
+// own hub list, 2 i bytes — probed against w's bitset container.  An edge is handed to its receiver w when that is at least twice cheaper; the
+// receivers then run first (k_kc_reverse: w's bitset staged in LDS, the prefixes of all its in-neighbours streamed through it, hit bits written
+// as finished matrix rows into an arena) and the pivots copy those rows instead of streaming the member.
+struct KcReverse {
+    bool rev_tried = false;           // built (or found not worth building) already
+    gmsx::DevArr<uint32_t> rel;       // [hoff[n]] per hub-entry position: word offset of that member's row inside its pivot's arena span; ~0u = streamed forward
+    gmsx::DevArr<int64_t> aoff;       // [n + 1] word offset of a pivot's span in the arena (by rank id)
+    gmsx::DevArr<uint32_t> arena;     // the reverse rows of one call
+    gmsx::DevArr<ulonglong2> rec;     // [recs] one record per reverse edge, receiver by receiver: x = first id of the pivot's hub list in hadj (40 bits) | i << 40,
+                                      //         y = arena word of the row (36 bits) | position of the pivot in `order` << 36 (what a shard is decided on)
+    gmsx::DevArr<uint4> item;         // [items] work items: x = receiver, y = entries, z | w << 32 = first record
+    // TAIL receivers (round 6b): a tail member w (rank id >= 65 535: no bitset container) takes its edges too — k_kc_reverse_tail builds w's bitmap and tail set
+    // in LDS from its two lists and streams the pivot's whole hub list and its tail members below w through them.  (With the matrix-core count the forward
+    // rows of the tail members were 206 of the 470 ms of a k = 4 call at scale 26.)
+    gmsx::DevArr<uint32_t> relt;      // [toff[n]] per tail-entry position, as rel
+    gmsx::DevArr<ulonglong2> rect;    // [2 recst] two 16-byte halves per record: {hadj offset | i << 40, arena word | position << 36}, {tadj offset | hc << 40, 0}
+    gmsx::DevArr<uint4> itemt;        // [itemst] work items of tail receivers
+    int64_t recst = 0, itemst = 0;
+    int64_t recs = 0, items = 0, arena_words = 0, rev_bytes = 0;
+    double rev_build_ms = 0.0;        // what building the lists took (reported once, in gmsx_stats.setup_ms of the call that built them)
+};
+// PageRank ROW CLASSES (pagerank.hip, ensure_pr_bins — built at the first PageRank call): the n vertices class by class (degree 0; a lane,
+// a 16-lane group, chunks of a wave per row), every class ascending in the vertex id; class c = bins[base[c], base[c + 1])
+struct PrBins {
+    bool ready = false;
+    gmsx::DevArr<int32_t> bins;      // [n]
+    int64_t base[5] = {0, 0, 0, 0, 0};
+    gmsx::DevArr<int64_t> first;     // [long rows + 1] first chunk slot of a long row (in class order); the last entry = slots
+    gmsx::DevArr<int32_t> slot_row;  // [slots] which long row a slot belongs to
+    int64_t slots = 0;
+};
+struct gmsx_graph {
+    uint64_t serial = 0;  // which upload of this process this is (from 1 on; gmsx_graph_upload_shard): what a cache keyed on a handle compares, addresses repeat
+    int64_t n = 0, nnz = 0, m = 0;
+    gmsx::DevArr<int64_t> off;
+    gmsx::DevArr<int32_t> adj;
+    gmsx::DevArr<int32_t> newid;
+    gmsx::DevArr<int32_t> oldid;
+    gmsx::DevArr<int64_t> hoff;
+    gmsx::DevArr<uint16_t> hadj;
+    gmsx::DevArr<int64_t> toff;
+    gmsx::DevArr<int32_t> tadj;
+    gmsx::DevArr<int64_t> bmoff;   // [dense_limit + 1] word offsets into bmpool (multiples of 4); equal neighbours = not dense
+    gmsx::DevArr<uint32_t> bmpool; // bitset containers of the dense hub rows
+    int32_t dense_limit = 0;    // = min(n, hub limit): hub rank ids; their rows have a bitset AND only hub entries
+    int32_t bitset_limit = 0;   // = dense_limit: every rank id below it has a bitset container over [0, v) in bmpool
+    TcContainers tc;  // the triangle-count containers
+    bool light_packed = false;
     mutable int core_bytes_k = -1, core_bytes_part = -1, core_bytes_nparts = -1;  // memo of tc_core_bytes() for the last (K, part, nparts)
     mutable uint64_t core_bytes = 0;
     // HOT WINDOWS (round 4): the hub-entry list of a receiver is laid out phase by phase — first the entries whose stream row starts in
@@ -171,7 +224,6 @@ struct gmsx_graph {
     int tc_hot_min = 0;                  // a receiver with fewer entries than this in a window streams them with its next phase
     int inline_first = 64;               // a HEAVY pivot hands the edges to its first inline_first members (<= 64) over inline rows as well
     int32_t inline_limit = 0;            // light pivots hand their edges to members of rank id < inline_limit (and to heavy ones) as INLINE ROWS
-    int64_t inline_units = 0;            // 16-byte units of all inline rows (inside spool / tpool)
     // GATHERED ROWS (GMSX_TC_GATHER = R > 0; the rule: host/tc_gather_plan.hpp).  A stream row that ends inside a 128-byte line costs the whole
     // line, and the rows of >= 8 units start on line boundaries, so every one of them ends in such a line.  The units of every form but the
     // bitset are self-contained (plain ids; base + count + gaps) and the count of an item is a sum over units, whichever row they sit in: the r
@@ -185,56 +237,21 @@ struct gmsx_graph {
     // boundaries as well (the inline region and every receiver's rows in it start on one, fillers behind a row's end), so that every row an
     // entry names is whole lines from a boundary on, or the one partial line at the end of an inline or a gathered row.
     int tc_gather = 0;                   // R the containers were built with
-    int64_t gather_units = 0;            // 16-byte units moved into gathered rows (inside spool / tpool, behind the inline rows)
-    unsigned long long *trow = nullptr;
-    uint32_t *tpool = nullptr;
-    int64_t tpool_units = 0;
-    int32_t *tsplit = nullptr;  // int32[n]: position in the tail row of the first target >= inline_limit (= tail length if none)
     int64_t dense_rows = 0, bmpool_words = 0;
     bool rows_sorted = false;   // both containers of every row ascending (always: sorted in vertex ranges at upload)
-    int32_t *dplus = nullptr;
-    int32_t *order = nullptr;
+    gmsx::DevArr<int32_t> dplus;
+    gmsx::DevArr<int32_t> order;
     int64_t hub_entries = 0, tail_entries = 0;
     int32_t max_dplus = 0;
     int32_t max_deg = 0;
-    // k-clique REVERSE ROWS (round 6; kclique.hip, ensure_kc_reverse — built at the first k-clique call, like the triangle-count task lists).  The BUILD
-    // needs rows[i] = N+(v_i) ∩ N+(u) for every member v_i of every pivot u.  Forward it streams N+(v_i) against u's bitmap; but nothing of N+(v_i)
-    // above v_i's predecessors can hit, and for a HUB member w = v_i the same bits come from the other side: the i members below w — a prefix of u's
-    // own hub list, 2 i bytes — probed against w's bitset container.  An edge is handed to its receiver w when that is at least twice cheaper; the
-    // receivers then run first (k_kc_reverse: w's bitset staged in LDS, the prefixes of all its in-neighbours streamed through it, hit bits written
-    // as finished matrix rows into an arena) and the pivots copy those rows instead of streaming the member.
-    mutable bool kc_rev_tried = false;       // built (or found not worth building) already
-    mutable uint32_t *kc_rel = nullptr;      // [hoff[n]] per hub-entry position: word offset of that member's row inside its pivot's arena span; ~0u = streamed forward
-    mutable int64_t *kc_aoff = nullptr;      // [n + 1] word offset of a pivot's span in the arena (by rank id)
-    mutable uint32_t *kc_arena = nullptr;    // the reverse rows of one call
-    mutable ulonglong2 *kc_rec = nullptr;    // [kc_recs] one record per reverse edge, receiver by receiver: x = first id of the pivot's hub list in hadj (40 bits) | i << 40,
-                                             //           y = arena word of the row (36 bits) | position of the pivot in `order` << 36 (what a shard is decided on)
-    mutable uint4 *kc_item = nullptr;        // [kc_items] work items: x = receiver, y = entries, z | w << 32 = first record
-    // TAIL receivers (round 6b): a tail member w (rank id >= 65 535: no bitset container) takes its edges too — k_kc_reverse_tail builds w's bitmap and tail set
-    // in LDS from its two lists and streams the pivot's whole hub list and its tail members below w through them.  (With the matrix-core count the forward
-    // rows of the tail members were 206 of the 470 ms of a k = 4 call at scale 26.)
-    mutable uint32_t *kc_relt = nullptr;     // [toff[n]] per tail-entry position, as kc_rel
-    mutable ulonglong2 *kc_rect = nullptr;   // [2 kc_recst] two 16-byte halves per record: {hadj offset | i << 40, arena word | position << 36}, {tadj offset | hc << 40, 0}
-    mutable uint4 *kc_itemt = nullptr;       // [kc_itemst] work items of tail receivers
-    mutable int64_t kc_recst = 0, kc_itemst = 0;
-    mutable int64_t kc_recs = 0, kc_items = 0, kc_arena_words = 0, kc_rev_bytes = 0;
-    mutable double kc_rev_build_ms = 0.0;    // what building the lists took (reported once, in gmsx_stats.setup_ms of the call that built them)
-    // PageRank ROW CLASSES (pagerank.hip, ensure_pr_bins — built at the first PageRank call): the n vertices class by class (degree 0; a lane,
-    // a 16-lane group, chunks of a wave per row), every class ascending in the vertex id; class c = pr_bins[pr_base[c], pr_base[c + 1])
-    mutable bool pr_ready = false;
-    mutable int32_t *pr_bins = nullptr;      // [n]
-    mutable int64_t pr_base[5] = {0, 0, 0, 0, 0};
-    mutable int64_t *pr_first = nullptr;     // [long rows + 1] first chunk slot of a long row (in class order); the last entry = pr_slots
-    mutable int32_t *pr_slot_row = nullptr;  // [pr_slots] which long row a slot belongs to
-    mutable int64_t pr_slots = 0;
-    unsigned long long *scratch = nullptr;  // device: a few u64 accumulators
-    unsigned long long *acc = nullptr;      // device: 64 spread u64 accumulators (128 B apart) + a few control words, reused by every call
+    mutable KcReverse kc;  // kclique.hip, ensure_kc_reverse
+    mutable PrBins pr;     // pagerank.hip, ensure_pr_bins
+    gmsx::DevArr<unsigned long long> scratch;  // device: a few u64 accumulators
+    gmsx::DevArr<unsigned long long> acc;      // device: 64 spread u64 accumulators (128 B apart) + a few control words, reused by every call
     // host-side memo of read-only facts about the immutable graph (filled lazily; handles are single-threaded)
     mutable int32_t ge_thr[40] = {0};
     mutable int64_t ge_cnt[40] = {0};
     mutable int ge_used = 0;
-    mutable int stats_part = -1, stats_nparts = -1;  // shard whose TC bookkeeping (units, probes) is cached below
-    mutable uint64_t stats_units = 0, stats_probes = 0, stats_bytes = 0;
     // the triangle-count containers (stream rows, inline rows, task lists …) are built on demand: ensure_tc()
     int shard_part = 0, shard_nparts = 1;   // gmsx_graph_upload_shard: the triangle-count containers hold this rank's pivots only
     // FALLBACK when the triangle-count containers of the whole graph do not fit the device: they are built for 1/tc_passes of the pivots at
@@ -250,19 +267,20 @@ struct gmsx_graph {
     int64_t device_bytes = 0;
     // EDGE WEIGHTS (gmsx_graph_set_weights, sssp.hip): int32[nnz] parallel to adj — two parallel arrays, not interleaved pairs, so that every
     // unweighted kernel reads the bytes it always read.  Attached explicitly, validated on the device (every weight >= 1; symmetric unless the
-    // upload was TRUSTED), counted in device_bytes, released with the handle (DevBuf) or by a detach.
+    // upload was TRUSTED), counted in device_bytes, released with the handle or by a detach.
     gmsx::DevBuf wgt;
     int64_t wgt_bytes = 0;
     int64_t wsum = 0;                       // Σ of the nnz weights
     int32_t wmax = 0;
     bool wide_dist = false;                 // (n − 1) · wmax does not fit below 2^31 − 1: distances are held in 64-bit words
 };
+static_assert(!std::is_copy_constructible<gmsx_graph>::value, "a handle is the one owner of its device arrays");
 
 namespace gmsx {
 
 static constexpr int kHub = 65535;         // rank ids below this live in the 16-bit hub containers
 static constexpr int kBitmapWords = 2048;  // 65536-bit LDS bitmap over the hub id range
-static constexpr int kAccWords = 64 * 16 + 16;
+static constexpr int kAccWords = 64 * 16 + 16;  // size of gmsx_graph::acc in u64
 static constexpr int kFormList = 0, kFormBitset = 1, kFormDelta = 2, kFormGap12 = 3;
 static constexpr int kPoolSlack = 64;    // 16-byte units of padding behind spool / tpool: a lane group loads up to 15 units past the end of a row (tc.hip, scan_run)
 static constexpr int kTaskChunk = 512;   // entries per work item (4 KB of descriptors: two such buffers per workgroup, the next item's arriving while this one is scanned)
@@ -318,7 +336,7 @@ __host__ __device__ inline int shard_of(int64_t pos, int nparts) {
     return ((pos / nparts) & 1) ? nparts - 1 - j : j;
 }
 static constexpr int kHeavy = 64;        // d+ from which a pivot runs on the workgroup kernel
-static constexpr int kDeltaIds = 14;  // ids per full 16-byte delta unit  // size of gmsx_graph::acc in u64
+static constexpr int kDeltaIds = 14;  // ids per full 16-byte delta unit
 
 // SIZE CLASSES of the packed light edges (gmsx_graph::lpack).  A shape gives the capacity of the four parts of a block in 16-byte units
 // (8 hub ids or 4 tail ids each): u's hub ids, u's tail ids in front of v, v's hub ids, v's tail ids.  The class of an edge is the first
@@ -374,7 +392,7 @@ int exclusive_scan_i64(const int64_t *in, int64_t *out, int64_t count, hipStream
 int ensure_tc(const gmsx_graph *g);
 // … for one shard / pass (frees and rebuilds when another one is resident)
 int ensure_tc_shard(const gmsx_graph *g, int part, int nparts);
-// fills g->shard_hitem / shard_titem for (part, nparts) (device_graph.hip)
+// fills g->tc.shard for (part, nparts) (device_graph.hip)
 int tc_shard_items(const gmsx_graph *g, int part, int nparts);
 // counts[u] = Σ_{v∈N(u)} |N(u)∩N(v)| into a zeroed device array (pairs.hip); shared by the per-vertex count and the TC ordering
 int tc_vertex_counts_device(const gmsx_graph *g, unsigned long long *d_counts, gmsx_stats *st);

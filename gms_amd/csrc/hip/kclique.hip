@@ -1847,10 +1847,10 @@ __global__ __launch_bounds__(256) void k_kc_reverse_tail(const uint4 *__restrict
     }
 }
 
-// builds the lists above for the graph (once); leaves kc_rel == nullptr when no receiver qualifies or the option KC_REVERSE = 0 says no
+// builds the lists above for the graph (once); leaves g->kc.rel empty when no receiver qualifies or the option KC_REVERSE = 0 says no
 static int ensure_kc_reverse(const gmsx_graph *g) {
-    if (g->kc_rev_tried) return GMSX_OK;
-    g->kc_rev_tried = true;
+    if (g->kc.rev_tried) return GMSX_OK;
+    g->kc.rev_tried = true;
     if (const char *e = opt("KC_REVERSE"); e && std::atoi(e) == 0) return GMSX_OK;
     if (!g->rows_sorted || g->dense_limit <= 0 || g->n >= (int64_t(1) << 28)) return GMSX_OK;  // (28 bits of a record hold the pivot's position)
     Ctx &c = ctx();
@@ -1864,10 +1864,17 @@ static int ensure_kc_reverse(const gmsx_graph *g) {
     GMSX_HIP(hipStreamSynchronize(s));
     if (hub_total <= 0) return GMSX_OK;
     const int32_t H = g->dense_limit;
-    // what leaves this function early is freed; what the graph keeps is handed over at the end (release).  A failed allocation is no error
+    // what leaves this function early is freed; what the graph keeps is moved into g->kc at the end.  A failed allocation is no error
     // here: no room for the lists, the forward BUILD needs none
-    DevBuf d_rel, d_rcnt, d_words, d_aoff, d_roff, d_ioff, d_rec, d_item, d_arena;
-    DevBuf d_relt, d_rcntt, d_sizes, d_rect, d_itemt;  // tail receivers (option KC_REV_TAIL = 0: none)
+    DevBuf d_rcnt, d_words, d_roff, d_ioff;
+    DevArr<uint32_t> d_rel, d_arena;
+    DevArr<int64_t> d_aoff;
+    DevArr<ulonglong2> d_rec;
+    DevArr<uint4> d_item;
+    DevBuf d_rcntt, d_sizes;  // tail receivers (option KC_REV_TAIL = 0: none)
+    DevArr<uint32_t> d_relt;
+    DevArr<ulonglong2> d_rect;
+    DevArr<uint4> d_itemt;
     if (dalloc<uint32_t>(d_rel, hub_total) || dalloc<uint32_t>(d_rcnt, int64_t(H + 1) * 2) || dalloc<int64_t>(d_words, g->n + 1) || dalloc<int64_t>(d_aoff, g->n + 1))
         return GMSX_OK;
     uint32_t *rel = d_rel.as<uint32_t>(), *rcnt = d_rcnt.as<uint32_t>(), *rcur = rcnt + (H + 1);
@@ -1955,46 +1962,46 @@ static int ensure_kc_reverse(const gmsx_graph *g) {
     GMSX_HIP(hipGetLastError());
     GMSX_HIP(hipStreamSynchronize(s));
     if (tl.rcnt && recs_t > 0) {
-        g->kc_relt = d_relt.release<uint32_t>();
-        g->kc_rect = d_rect.release<ulonglong2>();
-        g->kc_itemt = d_itemt.release<uint4>();
-        g->kc_recst = recs_t;
-        g->kc_itemst = items_t;
+        g->kc.relt = std::move(d_relt);
+        g->kc.rect = std::move(d_rect);
+        g->kc.itemt = std::move(d_itemt);
+        g->kc.recst = recs_t;
+        g->kc.itemst = items_t;
     }
-    g->kc_rel = d_rel.release<uint32_t>();
-    g->kc_aoff = d_aoff.release<int64_t>();
-    g->kc_arena = d_arena.release<uint32_t>();
-    g->kc_rec = d_rec.release<ulonglong2>();
-    g->kc_item = d_item.release<uint4>();
-    g->kc_recs = recs;
-    g->kc_items = items;
-    g->kc_arena_words = arena_words;
-    g->kc_rev_bytes = hub_total * 4 + (g->n + 1) * 8 + arena_words * 4 + 64 + recs * int64_t(sizeof(ulonglong2)) + items * int64_t(sizeof(uint4));
-    if (g->kc_relt) g->kc_rev_bytes += tail_total * 4 + recs_t * 2 * int64_t(sizeof(ulonglong2)) + items_t * int64_t(sizeof(uint4));
-    const_cast<gmsx_graph *>(g)->device_bytes += g->kc_rev_bytes;
-    g->kc_rev_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    g->kc.rel = std::move(d_rel);
+    g->kc.aoff = std::move(d_aoff);
+    g->kc.arena = std::move(d_arena);
+    g->kc.rec = std::move(d_rec);
+    g->kc.item = std::move(d_item);
+    g->kc.recs = recs;
+    g->kc.items = items;
+    g->kc.arena_words = arena_words;
+    g->kc.rev_bytes = hub_total * 4 + (g->n + 1) * 8 + arena_words * 4 + 64 + recs * int64_t(sizeof(ulonglong2)) + items * int64_t(sizeof(uint4));
+    if (g->kc.relt) g->kc.rev_bytes += tail_total * 4 + recs_t * 2 * int64_t(sizeof(ulonglong2)) + items_t * int64_t(sizeof(uint4));
+    const_cast<gmsx_graph *>(g)->device_bytes += g->kc.rev_bytes;
+    g->kc.rev_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     if (opt_on("TIMING"))
         std::fprintf(stderr, "[gmsx kclique] reverse rows: %lld of the hub edges of %lld pivots handed to %lld work items of hub receivers, %lld tail edges to %lld work items of tail receivers, arena %.3f GB, lists %.3f GB, built in %.1f ms\n",
-                     (long long)recs, (long long)n_piv, (long long)items, (long long)recs_t, (long long)items_t, double(arena_words) * 4e-9, double(g->kc_rev_bytes - arena_words * 4) * 1e-9, g->kc_rev_build_ms);
+                     (long long)recs, (long long)n_piv, (long long)items, (long long)recs_t, (long long)items_t, double(arena_words) * 4e-9, double(g->kc.rev_bytes - arena_words * 4) * 1e-9, g->kc.rev_build_ms);
     return GMSX_OK;
 }
 // the receivers' pass of one call (inside the timed region, ahead of the pivots' kernels)
 static int launch_kc_reverse(const gmsx_graph *g, int part, int nparts, const KcBins &bins, unsigned long long *acc, int *launches, hipStream_t s) {
-    if (!g->kc_rel || (g->kc_items <= 0 && g->kc_itemst <= 0)) return GMSX_OK;
+    if (!g->kc.rel || (g->kc.items <= 0 && g->kc.itemst <= 0)) return GMSX_OK;
     Ctx &c = ctx();
     unsigned int *queue = reinterpret_cast<unsigned int *>(acc + (kAccSlots - 1) * kAccStride + 8);  // a spare word of the accumulator array (zeroed by the caller)
     const int cu = c.compute_units > 0 ? c.compute_units : 256;
-    const unsigned blocks = unsigned(std::min<int64_t>(g->kc_items, int64_t(cu) * 8));
-    if (g->kc_items > 0) {
-        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, g->kc_item, g->kc_items, g->kc_rec, g->bmoff, g->bmpool, g->hadj, g->kc_arena, nparts, part, bins, queue); };
+    const unsigned blocks = unsigned(std::min<int64_t>(g->kc.items, int64_t(cu) * 8));
+    if (g->kc.items > 0) {
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, g->kc.item, g->kc.items, g->kc.rec, g->bmoff, g->bmpool, g->hadj, g->kc.arena, nparts, part, bins, queue); };
         if (nparts > 1) go(k_kc_reverse<16, true>);
         else go(k_kc_reverse<16, false>);
         ++*launches;
     }
-    if (g->kc_relt && g->kc_itemst > 0) {
-        const unsigned blocks_t = unsigned(std::min<int64_t>(g->kc_itemst, int64_t(cu) * 8));
+    if (g->kc.relt && g->kc.itemst > 0) {
+        const unsigned blocks_t = unsigned(std::min<int64_t>(g->kc.itemst, int64_t(cu) * 8));
         auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(blocks_t), dim3(256), 0, s, g->kc_itemt, g->kc_itemst, g->kc_rect, g->hoff, g->hadj, g->toff, g->tadj, g->kc_arena, nparts, part, bins, queue + 1);
+            hipLaunchKernelGGL(kern, dim3(blocks_t), dim3(256), 0, s, g->kc.itemt, g->kc.itemst, g->kc.rect, g->hoff, g->hadj, g->toff, g->tadj, g->kc.arena, nparts, part, bins, queue + 1);
         };
         if (nparts > 1) go(k_kc_reverse_tail<16, true>);
         else go(k_kc_reverse_tail<16, false>);
@@ -2216,12 +2223,12 @@ static int launch_all(const gmsx_graph *g, int k, bool vtx, KcLaunchFn launch, i
     hipStream_t rev_stream = n_streams > 1 ? sides[kSides - 2] : s, small_stream = n_streams > 1 ? sides[kSides - 1] : s;
     // (Measured and dropped: the tail receivers' pass on a stream of its own beside the hub receivers' — 425 … 442 against 421 ms at scale 26.)
     if (int rc = launch_kc_reverse(g, part, nparts, starts, acc, launches, rev_stream)) return rc;
-    const KcRev rv{g->kc_rel, g->kc_aoff, g->kc_arena, g->kc_relt};
-    if (g->kc_rel && (g->kc_items > 0 || g->kc_itemst > 0) && n_streams > 1) {
+    const KcRev rv{g->kc.rel, g->kc.aoff, g->kc.arena, g->kc.relt};
+    if (g->kc.rel && (g->kc.items > 0 || g->kc.itemst > 0) && n_streams > 1) {
         GMSX_HIP(hipEventRecord(sd.ev_rev, rev_stream));
         GMSX_HIP(hipStreamWaitEvent(s, sd.ev_rev, 0));
         for (int i = 0; i + 2 < kSides; ++i) GMSX_HIP(hipStreamWaitEvent(sides[i], sd.ev_rev, 0));
-        if (g->kc_relt) GMSX_HIP(hipStreamWaitEvent(small_stream, sd.ev_rev, 0));  // (the wave kernel reads its tail members' rows from the arena too)
+        if (g->kc.relt) GMSX_HIP(hipStreamWaitEvent(small_stream, sd.ev_rev, 0));  // (the wave kernel reads its tail members' rows from the arena too)
     }
     int next_stream = 0;
     auto pick = [&]() -> hipStream_t {  // round robin over the launch stream and the side streams in use
@@ -2407,10 +2414,10 @@ static int kclique_partial(const gmsx_graph *g, int k, int part, int nparts, uin
     }
     // the reverse-row lists of the graph: built by the first k-clique call on it, outside the timed region and reported in setup_ms (an immutable
     // container like the triangle-count task lists; the reference's harness likewise times its SetGraph build apart, k_clique_count_set_based.h:22)
-    const bool rev_was_there = g->kc_rev_tried;
+    const bool rev_was_there = g->kc.rev_tried;
     if (k <= kMaxK && g->rows_sorted)
         if (int rc0 = ensure_kc_reverse(g)) return rc0;
-    const double setup_ms = rev_was_there ? 0.0 : g->kc_rev_build_ms;
+    const double setup_ms = rev_was_there ? 0.0 : g->kc.rev_build_ms;
     KcCall call;
     if (int rc = call.begin(c)) return rc;
     int slab_from = kKcLdsTop;
@@ -2433,7 +2440,7 @@ static int kclique_partial(const gmsx_graph *g, int k, int part, int nparts, uin
             GMSX_HIP(hipMemsetAsync(call.acc, 0, 8, s));
             const int cu = c.compute_units > 0 ? c.compute_units : 256;
             hipLaunchKernelGGL(k_stat_kc_bytes, dim3(unsigned(cu * 8)), dim3(256), 0, s, n_min, nparts, part, g->order, g->dplus, g->hoff, g->hadj, g->toff, g->tadj,
-                               g->dense_limit, g->kc_rel, g->kc_relt, slab_from, call.acc);
+                               g->dense_limit, g->kc.rel, g->kc.relt, slab_from, call.acc);
             GMSX_HIP(hipMemcpyAsync(&alg, call.acc, 8, hipMemcpyDeviceToHost, s));
             GMSX_HIP(hipStreamSynchronize(s));
         }

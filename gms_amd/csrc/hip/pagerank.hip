@@ -392,10 +392,12 @@ inline unsigned blocks_of(int64_t count, int per = kPrBlock) { return unsigned((
 
 // the classes of g, built at its first call and kept on the handle
 int ensure_pr_bins(const gmsx_graph *g, int *launches) {
-    if (g->pr_ready) return GMSX_OK;
+    if (g->pr.ready) return GMSX_OK;
     hipStream_t s = ctx().stream;
     const int64_t n = g->n, nb = (n + kPrBlock - 1) / kPrBlock;
-    DevBuf d_cnt, d_pos, d_bins, d_ctrl, d_chunks, d_first, d_slot_row;
+    DevBuf d_cnt, d_pos, d_ctrl, d_chunks;
+    DevArr<int32_t> d_bins, d_slot_row;  // what the graph keeps
+    DevArr<int64_t> d_first;
     if (int rc = dalloc<int64_t>(d_cnt, 4 * nb + 1)) return rc;
     if (int rc = dalloc<int64_t>(d_pos, 4 * nb + 1)) return rc;
     if (int rc = dalloc<int32_t>(d_bins, n)) return rc;
@@ -437,12 +439,12 @@ int ensure_pr_bins(const gmsx_graph *g, int *launches) {
     GMSX_HIP(hipStreamSynchronize(s));
     GMSX_HIP(hipGetLastError());
     if (h.flag) return GMSX_ERR_KERNEL;  // (a bin list that would overflow)
-    g->pr_bins = d_bins.release<int32_t>();
-    g->pr_first = n3 > 0 ? d_first.release<int64_t>() : nullptr;
-    g->pr_slot_row = n3 > 0 ? d_slot_row.release<int32_t>() : nullptr;
-    for (int c = 0; c <= 4; ++c) g->pr_base[c] = base[c];
-    g->pr_slots = nslots;
-    g->pr_ready = true;
+    g->pr.bins = std::move(d_bins);
+    g->pr.first = std::move(d_first);  // (both empty when there is no long row)
+    g->pr.slot_row = std::move(d_slot_row);
+    for (int c = 0; c <= 4; ++c) g->pr.base[c] = base[c];
+    g->pr.slots = nslots;
+    g->pr.ready = true;
     return GMSX_OK;
 }
 
@@ -455,7 +457,7 @@ struct PrOut {
 // one sweep on stream s; the cells of `part`: class by class, a cell per 256 positions
 template <class S, bool kDangling, bool kStore>
 void pr_sweep(const gmsx_graph *g, const PrArgs<S> &a, hipStream_t s, unsigned long_grid, int *launches) {
-    const int64_t *b = g->pr_base;
+    const int64_t *b = g->pr.base;
     int64_t pbase = 0;
     const int64_t c0 = b[1] - b[0], c1 = b[2] - b[1], c2 = b[3] - b[2], c3 = b[4] - b[3];
     if (c0 > 0) {
@@ -490,7 +492,7 @@ int pr_run(const gmsx_graph *g, const std::vector<double> &t, const double *star
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
     GMSX_HIP(hipEventRecord(c.ev[0], s));
     if (int rc = ensure_pr_bins(g, &out->launches)) return rc;
-    const int64_t *b = g->pr_base;
+    const int64_t *b = g->pr.base;
     const int64_t cells = int64_t(blocks_of(b[1] - b[0])) + blocks_of(b[2] - b[1]) + blocks_of(b[3] - b[2]) + blocks_of(b[4] - b[3]);
     const int64_t dcells = blocks_of(b[1] - b[0]), vcells = blocks_of(n);
     DevBuf d_t, d_in, d_s0, d_s1, d_c0, d_c1, d_part, d_dpart, d_slots, d_fmax, d_farg, d_ctrl;
@@ -503,7 +505,7 @@ int pr_run(const gmsx_graph *g, const std::vector<double> &t, const double *star
     if (int rc = dalloc<S>(d_c1, n)) return rc;
     if (int rc = dalloc<double>(d_part, std::max(cells, vcells))) return rc;
     if (int rc = dalloc<double>(d_dpart, dcells)) return rc;
-    if (int rc = dalloc<double>(d_slots, g->pr_slots)) return rc;
+    if (int rc = dalloc<double>(d_slots, g->pr.slots)) return rc;
     if (int rc = dalloc<double>(d_fmax, vcells)) return rc;
     if (int rc = dalloc<int32_t>(d_farg, vcells)) return rc;
     if (int rc = dalloc<PrCtrl>(d_ctrl, 1)) return rc;
@@ -515,8 +517,8 @@ int pr_run(const gmsx_graph *g, const std::vector<double> &t, const double *star
     hipLaunchKernelGGL((k_pr_init<S>), dim3(blocks_of(n)), dim3(256), 0, s, n, g->off, start ? d_in.as<const double>() : d_t.as<const double>(), score[0],
                        contrib[0]);
     ++out->launches;
-    PrArgs<S> a{n, g->off, g->adj, g->pr_bins, d_t.as<const double>(), score[0], score[1], contrib[0], contrib[1], d_part.as<double>(),
-                d_dpart.as<double>(), g->pr_slot_row, g->pr_first, d_slots.as<double>(), g->pr_slots, ctrl, 1.0 - damping, damping};
+    PrArgs<S> a{n, g->off, g->adj, g->pr.bins, d_t.as<const double>(), score[0], score[1], contrib[0], contrib[1], d_part.as<double>(),
+                d_dpart.as<double>(), g->pr.slot_row, g->pr.first, d_slots.as<double>(), g->pr.slots, ctrl, 1.0 - damping, damping};
     if (dangling) {  // D of the first sweep
         if (dcells > 0) {
             hipLaunchKernelGGL((k_pr_zero_sum<S>), dim3(unsigned(dcells)), dim3(256), 0, s, a, b[0], b[1] - b[0]);
@@ -526,7 +528,7 @@ int pr_run(const gmsx_graph *g, const std::vector<double> &t, const double *star
         ++out->launches;
     }
     GMSX_HIP(hipEventRecord(c.ev[1], s));
-    const unsigned long_grid = unsigned(std::max<int64_t>(1, std::min<int64_t>((g->pr_slots + 3) / 4, int64_t(cus) * 8)));
+    const unsigned long_grid = unsigned(std::max<int64_t>(1, std::min<int64_t>((g->pr.slots + 3) / 4, int64_t(cus) * 8)));
     int cur = 0;
     int32_t iterations = 0;
     double error = 0.0;

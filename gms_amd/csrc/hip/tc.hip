@@ -1223,10 +1223,10 @@ __global__ __launch_bounds__(256) void k_tc_row_hist(const int64_t *__restrict__
 // (cpart, cnparts): the share of the core's blocks this call counts — cnparts = 0: none (a later pass of a call that walks several)
 static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnparts, uint64_t *partial, gmsx_stats *st);
 static uint64_t core_bytes_of(const gmsx_graph *g, int part, int nparts) {
-    if (g->tc_core <= 0 || nparts < 1) return 0;
-    if (!(g->core_bytes_k == g->tc_core && g->core_bytes_part == part && g->core_bytes_nparts == nparts)) {
-        g->core_bytes = tc_core_bytes(g->tc_core, part, nparts);
-        g->core_bytes_k = g->tc_core;
+    if (g->tc.tc_core <= 0 || nparts < 1) return 0;
+    if (!(g->core_bytes_k == g->tc.tc_core && g->core_bytes_part == part && g->core_bytes_nparts == nparts)) {
+        g->core_bytes = tc_core_bytes(g->tc.tc_core, part, nparts);
+        g->core_bytes_k = g->tc.tc_core;
         g->core_bytes_part = part;
         g->core_bytes_nparts = nparts;
     }
@@ -1307,8 +1307,8 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
     const bool use_idx = nparts > 1 && g->shard_nparts == 1;
     if (use_idx)
         if (int rc = tc_shard_items(g, part, nparts)) return rc;
-    const gmsx_tc_item *hitem = use_idx ? g->shard_hitem : g->hitem, *titem = use_idx ? g->shard_titem : g->titem;
-    int64_t n_hitems = use_idx ? g->shard_hitems : g->hitems, n_titems = use_idx ? g->shard_titems : g->titems;
+    const gmsx_tc_item *hitem = use_idx ? g->tc.shard.hitem.get() : g->tc.hitem.get(), *titem = use_idx ? g->tc.shard.titem.get() : g->tc.titem.get();
+    int64_t n_hitems = use_idx ? g->tc.shard.hitems : g->tc.hitems, n_titems = use_idx ? g->tc.shard.titems : g->tc.titems;
 #ifdef GMSX_DEV_HOOKS  // profiling build only (WRONG counts): the hub items / the tail items / the light pivots alone
     const char *only = std::getenv("GMSX_TC_ONLY");
     if (only) {
@@ -1341,8 +1341,8 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
         return full + (((full & 1) ? nparts - 1 - part : part) < rem ? 1 : 0);
     };
     int64_t cnt_class[kLightClasses], cnt_light = 0;  // packed light edges (gmsx_graph::lpack): every class is a list of its own
-    for (int k = 0; k < kLightClasses; ++k) cnt_light += cnt_class[k] = g->light_packed ? light_share(g->lpack_n[k]) : 0;
-    if (!g->light_packed) cnt_light = light_share(g->n_ledge);
+    for (int k = 0; k < kLightClasses; ++k) cnt_light += cnt_class[k] = g->light_packed ? light_share(g->tc.lpack_n[k]) : 0;
+    if (!g->light_packed) cnt_light = light_share(g->tc.n_ledge);
     // LAUNCH PLAN (round 4).  k_tc_items — one persistent launch over the hub and the tail items — then k_tc_light, both on the launch stream.
     // GMSX_TC_OVERLAP=1 puts k_tc_light on a side stream behind the item kernel (its workgroups need no LDS and start wherever a persistent
     // workgroup has left): measured 72.0-72.4 ms against 71.3-71.6 one after the other at scale 26 — the items kernel is bound by memory and
@@ -1371,13 +1371,13 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
         GMSX_HIP(hipStreamWaitEvent(c.side[1], c.ev_fork, 0));
         join.armed[1] = true;
     }
-    const bool run_core = g->tc_core > 0 && cnparts > 0 && !only;
+    const bool run_core = g->tc.tc_core > 0 && cnparts > 0 && !only;
     if (run_core) {
-        const int K = g->tc_core, nb = (K + 63) / 64, nblk = int(tc_core_blocks(K));
+        const int K = g->tc.tc_core, nb = (K + 63) / 64, nblk = int(tc_core_blocks(K));
         const int64_t ns = (int64_t(nblk) - cpart + cnparts - 1) / cnparts;
         if (ns > 0) {  // one workgroup of 16 waves per CU at the most, a multiple of 8 workgroups
             const int64_t wgs = std::max<int64_t>(8, std::min<int64_t>(cus / 8 * 8, ((ns + 15) / 16 + 7) / 8 * 8));
-            hipLaunchKernelGGL(k_tc_core, dim3(unsigned(wgs)), dim3(1024), 0, s, g->core_bits, kc4m_stride(K), K, nb, nblk, cpart, cnparts, acc);
+            hipLaunchKernelGGL(k_tc_core, dim3(unsigned(wgs)), dim3(1024), 0, s, g->tc.core_bits, kc4m_stride(K), K, nb, nblk, cpart, cnparts, acc);
             ++launches;
         }
     }
@@ -1387,21 +1387,21 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
             return unsigned(std::max<int64_t>(1, std::min<int64_t>((n + kGrab - 1) / kGrab, int64_t(cus) * (wgs_env > 0 ? wgs_env : wgs))));
         };
         if (n_hitems > 0) {
-            hipLaunchKernelGGL(k_tc_items<false>, dim3(grid(n_hitems, GMSX_TC_HUB_MIN_WAVES)), dim3(256), 0, s, g->hadj, g->tadj, g->spool, g->htask, hitem, int(n_hitems), qhead, acc);
+            hipLaunchKernelGGL(k_tc_items<false>, dim3(grid(n_hitems, GMSX_TC_HUB_MIN_WAVES)), dim3(256), 0, s, g->hadj, g->tadj, g->tc.spool, g->tc.htask, hitem, int(n_hitems), qhead, acc);
             ++launches;
         }
         if (n_titems > 0) {
-            hipLaunchKernelGGL(k_tc_items<true>, dim3(grid(n_titems, GMSX_TC_TAIL_MIN_WAVES)), dim3(256), 0, s, g->hadj, g->tadj, g->tpool, g->ttask, titem, int(n_titems),
+            hipLaunchKernelGGL(k_tc_items<true>, dim3(grid(n_titems, GMSX_TC_TAIL_MIN_WAVES)), dim3(256), 0, s, g->hadj, g->tadj, g->tc.tpool, g->tc.ttask, titem, int(n_titems),
                                qhead + kQueueStride, acc);
             ++launches;
         }
     } else {
         if (n_hitems > 0) {
-            hipLaunchKernelGGL(k_tc_block, dim3(unsigned(n_hitems)), dim3(256), 0, s, g->hoff, g->hadj, g->spool, g->htask, hitem, acc);
+            hipLaunchKernelGGL(k_tc_block, dim3(unsigned(n_hitems)), dim3(256), 0, s, g->hoff, g->hadj, g->tc.spool, g->tc.htask, hitem, acc);
             ++launches;
         }
         if (n_titems > 0) {
-            hipLaunchKernelGGL(k_tc_tail, dim3(unsigned(n_titems)), dim3(256), 0, side_tail ? c.side[0] : s, g->toff, g->tadj, g->tpool, g->ttask, titem, acc);
+            hipLaunchKernelGGL(k_tc_tail, dim3(unsigned(n_titems)), dim3(256), 0, side_tail ? c.side[0] : s, g->toff, g->tadj, g->tc.tpool, g->tc.ttask, titem, acc);
             ++launches;
         }
     }
@@ -1409,7 +1409,7 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
         auto launch = [&](auto kernel, int k) {
             if (cnt_class[k] <= 0) return;
             const int64_t blocks = std::min<int64_t>((cnt_class[k] + 15) / 16, int64_t(cus) * 8);
-            hipLaunchKernelGGL(kernel, dim3(unsigned(blocks)), dim3(256), 0, side_light ? c.side[1] : s, g->lpack + g->lpack_base[k], strided ? nparts : 1, strided ? part : 0,
+            hipLaunchKernelGGL(kernel, dim3(unsigned(blocks)), dim3(256), 0, side_light ? c.side[1] : s, g->tc.lpack + g->tc.lpack_base[k], strided ? nparts : 1, strided ? part : 0,
                                cnt_class[k], acc);
             ++launches;
         };
@@ -1422,7 +1422,7 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
         launch(k_tc_lpack<5>, 5);
     } else if (cnt_light > 0) {
         const int64_t blocks = std::min<int64_t>((cnt_light + 15) / 16, int64_t(cus) * 8);
-        hipLaunchKernelGGL(k_tc_light, dim3(unsigned(blocks)), dim3(256), 0, side_light ? c.side[1] : s, g->hadj, g->tadj, g->ledge, strided ? nparts : 1,
+        hipLaunchKernelGGL(k_tc_light, dim3(unsigned(blocks)), dim3(256), 0, side_light ? c.side[1] : s, g->hadj, g->tadj, g->tc.ledge, strided ? nparts : 1,
                            strided ? part : 0, cnt_light, acc);
         ++launches;
     }
@@ -1435,19 +1435,19 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
     GMSX_HIP(hipEventRecord(c.ev[2], s));
     GMSX_HIP(hipGetLastError());
 
-    const bool need_stats = st && !(g->stats_part == part && g->stats_nparts == nparts);
+    const bool need_stats = st && !(g->tc.stats_part == part && g->tc.stats_nparts == nparts);
     if (need_stats) {  // untimed bookkeeping, once per shard (the graph is immutable)
         if (g->n > 0) {
             const int64_t blocks = std::min<int64_t>((g->n + 3) / 4, cap_blocks);
             hipLaunchKernelGGL(k_tc_stats, dim3(unsigned(blocks)), dim3(256), 0, s, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->order,
-                               g->tunits, g->inline_limit, g->inline_first, g->tc_core, g->light_packed ? 1 : 0, g->n, nparts, part, acc + kAccSlots * kAccStride);
+                               g->tc.tunits, g->inline_limit, g->inline_first, g->tc.tc_core, g->light_packed ? 1 : 0, g->n, nparts, part, acc + kAccSlots * kAccStride);
         }
-        if (g->hitems > 0)
-            hipLaunchKernelGGL(k_tc_item_stats, dim3(unsigned(std::min<int64_t>((g->hitems + 3) / 4, cap_blocks))), dim3(256), 0, s, g->hoff, 2, 0, g->htask, g->hitem,
-                               g->hitems, nparts, part, acc + kAccSlots * kAccStride);
-        if (g->titems > 0)
-            hipLaunchKernelGGL(k_tc_item_stats, dim3(unsigned(std::min<int64_t>((g->titems + 3) / 4, cap_blocks))), dim3(256), 0, s, g->toff, 4, 1, g->ttask, g->titem,
-                               g->titems, nparts, part, acc + kAccSlots * kAccStride);
+        if (g->tc.hitems > 0)
+            hipLaunchKernelGGL(k_tc_item_stats, dim3(unsigned(std::min<int64_t>((g->tc.hitems + 3) / 4, cap_blocks))), dim3(256), 0, s, g->hoff, 2, 0, g->tc.htask, g->tc.hitem,
+                               g->tc.hitems, nparts, part, acc + kAccSlots * kAccStride);
+        if (g->tc.titems > 0)
+            hipLaunchKernelGGL(k_tc_item_stats, dim3(unsigned(std::min<int64_t>((g->tc.titems + 3) / 4, cap_blocks))), dim3(256), 0, s, g->toff, 4, 1, g->tc.ttask, g->tc.titem,
+                               g->tc.titems, nparts, part, acc + kAccSlots * kAccStride);
     }
     unsigned long long host[kAccSlots * kAccStride + 3];
     GMSX_HIP(hipMemcpyAsync(host, acc, sizeof(host), hipMemcpyDeviceToHost, s));
@@ -1462,18 +1462,18 @@ static int tc_one(const gmsx_graph *g, int part, int nparts, int cpart, int cnpa
         st->kernel_ms = ms_kernel;
         st->setup_ms = ms_setup;
         if (need_stats) {
-            g->stats_part = part;
-            g->stats_nparts = nparts;
-            g->stats_units = host[kAccSlots * kAccStride];
-            g->stats_probes = host[kAccSlots * kAccStride + 1];
-            g->stats_bytes = host[kAccSlots * kAccStride + 2];
+            g->tc.stats_part = part;
+            g->tc.stats_nparts = nparts;
+            g->tc.stats_units = host[kAccSlots * kAccStride];
+            g->tc.stats_probes = host[kAccSlots * kAccStride + 1];
+            g->tc.stats_bytes = host[kAccSlots * kAccStride + 2];
         }
-        st->units = g->stats_units;
-        st->probes = g->stats_probes;
+        st->units = g->tc.stats_units;
+        st->probes = g->tc.stats_probes;
         st->alg_elements = nparts == 1 ? g->alg_elements : 0;
         st->launches = launches;
         st->reserved = 0;
-        st->stream_bytes = g->stats_bytes + (run_core ? core_bytes_of(g, cpart, cnparts) : 0);
+        st->stream_bytes = g->tc.stats_bytes + (run_core ? core_bytes_of(g, cpart, cnparts) : 0);
     }
     return GMSX_OK;
 }
@@ -1497,22 +1497,21 @@ int gmsx_tc_stream_breakdown(const gmsx_graph *g, uint64_t *out21) {
         int64_t n_block = 0, n_work = 0;
         if (int rc = count_dplus_ge(g, kHeavy, &n_block)) return rc;
         if (int rc = count_dplus_ge(g, 2, &n_work)) return rc;
-        unsigned long long *acc = nullptr;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&acc), 21 * 8));
-        struct Guard { void *p; ~Guard() { (void)hipFree(p); } } g1{acc};
+        DevArr<unsigned long long> acc;
+        GMSX_HIP(hipMalloc(&acc.p, 21 * 8));
         GMSX_HIP(hipMemsetAsync(acc, 0, 21 * 8, s));
         const int cus = ctx().compute_units > 0 ? ctx().compute_units : 256;
-        hipLaunchKernelGGL(k_tc_breakdown, dim3(unsigned(cus * 16)), dim3(256), 0, s, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->order, g->htask,
-                           g->hitem, g->hitems, g->ttask, g->titem, g->titems, g->inline_limit, g->tc_core, g->light_packed ? 1 : 0, n_block, n_work, acc);
+        hipLaunchKernelGGL(k_tc_breakdown, dim3(unsigned(cus * 16)), dim3(256), 0, s, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->order, g->tc.htask,
+                           g->tc.hitem, g->tc.hitems, g->tc.ttask, g->tc.titem, g->tc.titems, g->inline_limit, g->tc.tc_core, g->light_packed ? 1 : 0, n_block, n_work, acc);
         GMSX_HIP(hipMemcpyAsync(out21, acc, 21 * 8, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
         GMSX_HIP(hipGetLastError());
-        out21[7] = uint64_t(g->inline_units) * 16ull;                         // the build's figures: the entries do not say what they name
-        out21[12] = uint64_t(g->inline_hentries + g->inline_tentries);
-        out21[17] = uint64_t(g->gather_units) * 16ull;
+        out21[7] = uint64_t(g->tc.inline_units) * 16ull;                         // the build's figures: the entries do not say what they name
+        out21[12] = uint64_t(g->tc.inline_hentries + g->tc.inline_tentries);
+        out21[17] = uint64_t(g->tc.gather_units) * 16ull;
         out21[20] = uint64_t(g->tc_gather);
         out21[15] = core_bytes_of(g, 0, 1);
-        out21[16] = uint64_t(g->tc_core);
+        out21[16] = uint64_t(g->tc.tc_core);
         return GMSX_OK;
     });
 }
@@ -1526,18 +1525,17 @@ int gmsx_tc_row_histogram(const gmsx_graph *g, uint64_t *out256) {
         hipStream_t s = ctx().stream;
         std::memset(out248, 0, 256 * sizeof(uint64_t));
         if (g->n == 0) return GMSX_OK;
-        unsigned long long *acc = nullptr;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&acc), 256 * 8));
-        struct Guard { void *p; ~Guard() { (void)hipFree(p); } } g1{acc};
+        DevArr<unsigned long long> acc;
+        GMSX_HIP(hipMalloc(&acc.p, 256 * 8));
         GMSX_HIP(hipMemsetAsync(acc, 0, 256 * 8, s));
         const int cus = ctx().compute_units > 0 ? ctx().compute_units : 256;
-        hipLaunchKernelGGL(k_tc_row_hist, dim3(unsigned(cus * 8)), dim3(256), 0, s, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->order, g->srow, g->trow,
-                           g->htask, g->hitem, g->hitems, g->ttask, g->titem, g->titems, g->n, acc);
+        hipLaunchKernelGGL(k_tc_row_hist, dim3(unsigned(cus * 8)), dim3(256), 0, s, g->hoff, g->hadj, g->toff, g->tadj, g->dplus, g->order, g->tc.srow, g->tc.trow,
+                           g->tc.htask, g->tc.hitem, g->tc.hitems, g->tc.ttask, g->tc.titem, g->tc.titems, g->n, acc);
         GMSX_HIP(hipGetLastError());
         GMSX_HIP(hipMemcpyAsync(out248, acc, 256 * 8, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
         GMSX_HIP(hipGetLastError());
-        out248[241] = uint64_t(g->inline_hentries + g->inline_tentries);
+        out248[241] = uint64_t(g->tc.inline_hentries + g->tc.inline_tentries);
         return GMSX_OK;
     });
 }
@@ -1549,35 +1547,35 @@ int gmsx_tc_comembership(const gmsx_graph *g, int batch, uint64_t *out8) {
         if (int rc = ensure_tc(g)) return rc;
         hipStream_t s = ctx().stream;
         std::memset(out8, 0, 8 * sizeof(uint64_t));
-        const int64_t ne = g->htask_entries;
-        if (g->n == 0 || ne == 0 || g->hitems == 0) return GMSX_OK;
-        struct Guard { void *p = nullptr; ~Guard() { (void)hipFree(p); } } gk0, gk1, gv0, gv1, gu, ga, gc, gt, gsum;
-        unsigned long long *k0 = nullptr, *k1 = nullptr, *uk = nullptr, *cnt = nullptr, *sum = nullptr;
-        uint32_t *v0 = nullptr, *v1 = nullptr, *agg = nullptr;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&k0), size_t(ne) * 8)); gk0.p = k0;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&k1), size_t(ne) * 8)); gk1.p = k1;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&v0), size_t(ne) * 4)); gv0.p = v0;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&v1), size_t(ne) * 4)); gv1.p = v1;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&sum), 4 * 8)); gsum.p = sum;
+        const int64_t ne = g->tc.htask_entries;
+        if (g->n == 0 || ne == 0 || g->tc.hitems == 0) return GMSX_OK;
+        DevArr<unsigned long long> d_k0, d_k1, d_cnt, d_sum;
+        DevArr<uint32_t> d_v0, d_v1;
+        DevBuf tmp, tmp2;
+        GMSX_HIP(hipMalloc(&d_k0.p, size_t(ne) * 8));
+        GMSX_HIP(hipMalloc(&d_k1.p, size_t(ne) * 8));
+        GMSX_HIP(hipMalloc(&d_v0.p, size_t(ne) * 4));
+        GMSX_HIP(hipMalloc(&d_v1.p, size_t(ne) * 4));
+        GMSX_HIP(hipMalloc(&d_sum.p, 4 * 8));
+        unsigned long long *k0 = d_k0, *k1 = d_k1, *sum = d_sum;  // (plain pointers: rocPRIM deduces its iterator types from them)
+        uint32_t *v0 = d_v0, *v1 = d_v1;
         GMSX_HIP(hipMemsetAsync(k0, 0xff, size_t(ne) * 8, s));  // entries no item covers (none expected) sort to the end as one key of 0 units
         GMSX_HIP(hipMemsetAsync(v0, 0, size_t(ne) * 4, s));
         GMSX_HIP(hipMemsetAsync(sum, 0, 4 * 8, s));
-        hipLaunchKernelGGL(k_tc_comember_keys, dim3(unsigned(std::min<int64_t>(g->hitems, 1 << 20))), dim3(256), 0, s, g->htask, g->hitem, g->hitems, batch, k0, v0, sum);
+        hipLaunchKernelGGL(k_tc_comember_keys, dim3(unsigned(std::min<int64_t>(g->tc.hitems, 1 << 20))), dim3(256), 0, s, g->tc.htask, g->tc.hitem, g->tc.hitems, batch, k0, v0, sum);
         size_t tb = 0;
         GMSX_HIP(rocprim::radix_sort_pairs(nullptr, tb, k0, k1, v0, v1, size_t(ne), 0, 64, s));
-        void *tmp = nullptr;
-        GMSX_HIP(hipMalloc(&tmp, tb ? tb : 8)); gt.p = tmp;
-        GMSX_HIP(rocprim::radix_sort_pairs(tmp, tb, k0, k1, v0, v1, size_t(ne), 0, 64, s));
+        GMSX_HIP(hipMalloc(&tmp.p, tb ? tb : 8));
+        GMSX_HIP(rocprim::radix_sort_pairs(tmp.p, tb, k0, k1, v0, v1, size_t(ne), 0, 64, s));
         // per distinct (batch, row): the longest cut of the row any pivot of the batch streams (k0 / v0 are free again: outputs)
-        uk = k0;
-        agg = v0;
-        GMSX_HIP(hipMalloc(reinterpret_cast<void **>(&cnt), 8)); gc.p = cnt;
+        unsigned long long *uk = k0, *cnt = nullptr;
+        uint32_t *agg = v0;
+        GMSX_HIP(hipMalloc(&d_cnt.p, 8));
+        cnt = d_cnt;
         size_t rb = 0;
         GMSX_HIP(rocprim::reduce_by_key(nullptr, rb, k1, v1, size_t(ne), uk, agg, cnt, rocprim::maximum<uint32_t>(), rocprim::equal_to<unsigned long long>(), s));
-        void *tmp2 = nullptr;
-        Guard g2;
-        GMSX_HIP(hipMalloc(&tmp2, rb ? rb : 8)); g2.p = tmp2;
-        GMSX_HIP(rocprim::reduce_by_key(tmp2, rb, k1, v1, size_t(ne), uk, agg, cnt, rocprim::maximum<uint32_t>(), rocprim::equal_to<unsigned long long>(), s));
+        GMSX_HIP(hipMalloc(&tmp2.p, rb ? rb : 8));
+        GMSX_HIP(rocprim::reduce_by_key(tmp2.p, rb, k1, v1, size_t(ne), uk, agg, cnt, rocprim::maximum<uint32_t>(), rocprim::equal_to<unsigned long long>(), s));
         unsigned long long nuniq = 0;
         GMSX_HIP(hipMemcpyAsync(&nuniq, cnt, 8, hipMemcpyDeviceToHost, s));
         GMSX_HIP(hipStreamSynchronize(s));
@@ -1590,7 +1588,7 @@ int gmsx_tc_comembership(const gmsx_graph *g, int batch, uint64_t *out8) {
         out8[1] = uint64_t(h[1]);   // their 16-byte units: what the hub items stream per pass
         out8[2] = uint64_t(nuniq);  // distinct (batch, row) pairs
         out8[3] = uint64_t(h[2]);   // units if every row were streamed once per batch (at its longest cut)
-        out8[4] = uint64_t(g->hitems);
+        out8[4] = uint64_t(g->tc.hitems);
         return GMSX_OK;
     });
 }

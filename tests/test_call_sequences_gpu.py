@@ -15,6 +15,7 @@ test_random_gpu.py.  pair_ab() asserts those properties on the host before any d
   e  the lazy triangle-count containers in six orders under four kinds of upload
   f  weights attached, replaced, detached, attached again
   g  80 seeded random operations over at most two live handles per graph
+  h  a handle gives back what it took: free device memory over eight cycles of upload, build, count, free, and over eight refused builds
 """
 import ctypes as C
 
@@ -22,6 +23,7 @@ import numpy as np
 import pytest
 
 import test_bk_list_gpu as bkl
+from conftest import host_graph
 import test_kcstar_list_gpu as kcs
 import test_subgraph_gpu as sgm
 from test_coloring_golden_cpu import jp_np
@@ -760,3 +762,73 @@ def test_one_random_sequence(gpu, tabs):
         for hs in live.values():
             for g in hs:
                 g.free()
+
+
+# ---- h. a handle gives back what it took ----------------------------------------------------------------------------------------------
+LEAK_MARGIN = 0   # bytes: the largest drop of free memory over cycles 2 … 8 measured with the parent commit's library (see the docstring)
+
+
+@gpu_test
+def test_a_handle_gives_back_what_it_took(gpu, oracle):
+    """Free device memory (torch.cuda.mem_get_info: the whole process, the library's hipMalloc calls included) after every cycle of
+    upload, prepare, tc_total, kclique_count(4), pagerank (3 iterations), two sharded calls that fill and replace the shard index cache, free
+    — and after every round of refused and fallback builds: an upload refused after the CSR is on the device (an id out of range), a
+    container budget too small for one pass (GMSX_ERR_DEVICE_MEM, the base layout stays usable), and a budget of half the containers (the
+    passes fallback: every call frees and rebuilds the containers shard by shard).  Free memory after cycle 8 is not below free memory after
+    cycle 2 (the first cycles pay for the k-clique pool, which only grows, and for code objects).
+
+    Graph: kronecker scale 15, degree 16 — adj is about 4 MB, every nnz-sized array and both pools are above the allocator's granule.
+    Margin: the same test against the parent commit's library (hand-kept free lists) dropped by 0 bytes over cycles 2 … 8 of both loops, so
+    LEAK_MARGIN = 0.  What the test cannot see: an array smaller than the granule of the device allocator, which may be carved
+    out of a block that stays mapped — the scratch words, the per-class tables, an empty graph's arrays."""
+    import torch
+    csr = host_graph(gpu, "kronecker", 15)
+    off, adj = csr.offsets().copy(), csr.neighbors().copy()
+    T = oracle.tc_total(off, adj)
+    free = lambda: int(torch.cuda.mem_get_info()[0])
+    free()
+    seen, after = {}, []
+    for cycle in range(1, 9):
+        g = gpu.DeviceGraph.from_csr(csr)
+        try:
+            g.prepare()
+            got = {"T": g.tc_total(), "k4": g.kclique_count(4)[0], "pr": g.pagerank(max_iters=3, tolerance=0.0)[1]["iterations"],
+                   "parts": sum(g.tc_partial(p, 3) for p in range(3)) + g.tc_partial(0, 2) + g.tc_partial(1, 2), "bytes": g.device_bytes}
+        finally:
+            g.free()
+        assert got["T"] == T and got["parts"] == 2 * T and got["pr"] == 3 and seen.setdefault("cycle", got) == got, (cycle, got, seen)
+        after.append(free())
+        print(f"cycle {cycle}: free {after[-1]} ({after[-1] - after[0]:+d} against cycle 1), device_bytes {got['bytes']}")
+    assert after[7] >= after[1] - LEAK_MARGIN, after
+
+    bad = adj.copy()
+    bad[bad.size // 2] = off.size - 1   # an id = n: found by the validation kernel, after off, adj, scratch and acc were allocated
+    g = gpu.DeviceGraph.from_csr(csr)
+    base = g.device_bytes
+    g.prepare()
+    half_mb = max(1, (g.device_bytes - base) // 2 >> 20)
+    g.free()
+    after = []
+    try:
+        for turn in range(1, 9):
+            assert status_of(gpu, lambda: gpu.DeviceGraph.upload(off, bad)) == gpu.ERR_NOT_CANONICAL
+            gpu.set_option("TC_MEM_LIMIT_MB", 1)
+            g = gpu.DeviceGraph.from_csr(csr)
+            try:
+                assert status_of(gpu, g.tc_total) == gpu.ERR_DEVICE_MEM and g.tc_passes == 0 and g.device_bytes == base
+                assert g.tc_total(gpu.TC_FULL) == T
+            finally:
+                g.free()
+            gpu.set_option("TC_MEM_LIMIT_MB", half_mb)
+            g = gpu.DeviceGraph.from_csr(csr)
+            try:
+                assert g.tc_total() == T and g.tc_passes >= 2 and sum(g.tc_partial(p, 3) for p in range(3)) == T
+                passes = g.tc_passes
+            finally:
+                g.free()
+            gpu.set_option("TC_MEM_LIMIT_MB", None)
+            after.append(free())
+            print(f"refused round {turn}: free {after[-1]} ({after[-1] - after[0]:+d} against round 1), budget {half_mb} MB -> {passes} passes")
+    finally:
+        gpu.reset_options()
+    assert after[7] >= after[1] - LEAK_MARGIN, after
