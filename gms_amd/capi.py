@@ -50,6 +50,7 @@ SYMBOLS = [
     "gmsx_csr_weights", "gmsx_csr_generate_weighted", "gmsx_csr_from_weighted_edges", "gmsx_csr_load_weighted", "gmsx_csr_save_wsg",
     "gmsx_csr_from_arrays_weighted", "gmsx_graph_set_weights", "gmsx_graph_has_weights", "gmsx_sssp", "gmsx_sssp_verify",
     "gmsx_min_spanning_forest",
+    "gmsx_label_propagation", "gmsx_modularity",
     "gmsx_cycle4_count", "gmsx_cycle4_partial", "gmsx_motif_census4",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -219,6 +220,29 @@ class MsfInfo(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+LP_WEIGHTED = 1
+
+
+class LpInfo(C.Structure):
+    _fields_ = [("communities", C.c_int64), ("largest", C.c_int64), ("singletons", C.c_int64), ("changes", C.c_int64),
+                ("first_sweep_changes", C.c_int64), ("sweeps", C.c_int32), ("colors", C.c_int32), ("converged", C.c_int32),
+                ("largest_label", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class ModularityInfo(C.Structure):
+    _fields_ = [("total_weight", C.c_int64), ("intra_weight", C.c_int64), ("sumsq_hi", C.c_uint64), ("sumsq_lo", C.c_uint64),
+                ("communities", C.c_int64), ("largest", C.c_int64), ("unstable", C.c_int64), ("modularity", C.c_double)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "modularity"}
+        d["sumsq"] = (d["sumsq_hi"] << 64) | d["sumsq_lo"]
+        d["modularity"] = float(self.modularity)
+        return d
 
 
 class MotifInfo(C.Structure):
@@ -418,6 +442,8 @@ def lib():
     L.gmsx_sssp.argtypes = [vp, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(SsspInfo), sp]
     L.gmsx_sssp_verify.argtypes = [vp, C.c_int32, C.c_void_p, C.POINTER(SsspCheck), sp]
     L.gmsx_min_spanning_forest.argtypes = [vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MsfInfo), sp]
+    L.gmsx_label_propagation.argtypes = [vp, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(LpInfo), sp]
+    L.gmsx_modularity.argtypes = [vp, C.c_uint32, C.c_void_p, C.POINTER(ModularityInfo), sp]
     L.gmsx_cycle4_count.argtypes = [vp, u64p, C.c_void_p, sp]
     L.gmsx_cycle4_partial.argtypes = [vp, C.c_int, C.c_int, u64p, sp]
     L.gmsx_motif_census4.argtypes = [vp, C.POINTER(MotifInfo), sp]
@@ -1229,6 +1255,35 @@ class DeviceGraph:
         r = (eu[:ne] if want_edges else None, ev[:ne] if want_edges else None, ew[:ne] if want_edges else None,
              mask[:nnz] if want_mask else None, label[:n] if want_labels else None, info.as_dict())
         return (r + (st.as_dict(),)) if stats else r
+
+    def label_propagation(self, weighted=False, coloring=None, max_sweeps=0, want_labels=True, stats=False):
+        """gmsx_label_propagation: (label, info[, stats]).  label: int32[n], the community of every vertex as the id of one of its members (None
+        with want_labels=False); info: {communities, largest, singletons, changes, first_sweep_changes, sweeps, colors, converged,
+        largest_label}.  coloring: a proper colouring int32[n] with colours >= 1 that fixes the order of the asynchronous sweeps; None = the
+        colouring coloring_jp() returns.  weighted=True sums the attached weights (GMSX_LP_WEIGHTED) instead of counting arcs."""
+        n = self.num_nodes
+        col = None if coloring is None else np.ascontiguousarray(coloring, dtype=np.int32)
+        if col is not None and col.size != n:
+            raise ValueError("coloring must have one entry per vertex")
+        label = np.zeros(max(n, 1), dtype=np.int32) if want_labels else None
+        info, st = LpInfo(), Stats()
+        _check(lib().gmsx_label_propagation(self._h, LP_WEIGHTED if weighted else 0,
+                                            (col if col.size else np.zeros(1, np.int32)).ctypes.data_as(C.c_void_p) if col is not None else None,
+                                            int(max_sweeps), label.ctypes.data_as(C.c_void_p) if want_labels else None, C.byref(info), C.byref(st)),
+               "gmsx_label_propagation")
+        r = (label[:n] if want_labels else None, info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def modularity(self, label, weighted=False, stats=False):
+        """gmsx_modularity of a labelling int32[n] with labels in [0, n): {total_weight, intra_weight, sumsq_hi, sumsq_lo, sumsq, communities,
+        largest, unstable, modularity}.  The integers are exact; modularity = I / W - S / W^2 is computed from them once."""
+        lab = np.ascontiguousarray(label, dtype=np.int32)
+        if lab.size != self.num_nodes:
+            raise ValueError("label must have one entry per vertex")
+        info, st = ModularityInfo(), Stats()
+        _check(lib().gmsx_modularity(self._h, LP_WEIGHTED if weighted else 0, (lab if lab.size else np.zeros(1, np.int32)).ctypes.data_as(C.c_void_p),
+                                     C.byref(info), C.byref(st)), "gmsx_modularity")
+        return (info.as_dict(), st.as_dict()) if stats else info.as_dict()
 
     def cycle4_count(self, at_vertex=False, stats=False):
         """gmsx_cycle4_count: the 4-cycles of the graph; with at_vertex=True (cycles, int64[n] — the 4-cycles through every vertex of the

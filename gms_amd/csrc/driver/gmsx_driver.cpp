@@ -77,7 +77,12 @@
 //                    the graph is generated or loaded with its weights as for sssp.  Per trial "Trial Time", "Trees", "Edges", "Total Weight",
 //                    "Rounds" and with -v "Verification" — this driver's own serial Kruskal under the order of gmsx.h (weight, then the smaller
 //                    (min id, max id)) must give the same edge list and total weight —, then the "@@@" line.  Not sharded (--gpus > 1 is refused).
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  communities [-i MAX_SWEEPS] [--weighted]   communities by label propagation on the device (gmsx_label_propagation under the default colouring,
+//                    then gmsx_modularity of the result; no reference driver — `lp` is the link-prediction driver): --weighted generates or loads
+//                    the graph with its weights as for sssp and sums them.  Per trial "Trial Time", "Communities", "Sweeps", "Modularity" and with
+//                    -v "Verification" — this driver's own sequential propagation over the host CSR, the vertices ascending by (colour, id), must
+//                    give the same label for every vertex —, then the "@@@" line.  Not sharded (--gpus > 1 is refused).
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf|communities> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -123,6 +128,7 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     double tol = 1e-4;   // pr -t TOL
     int64_t delta = 0;   // sssp -d DELTA (0: the library's choice)
     bool maximum = false;  // msf --max
+    bool weighted = false; // communities --weighted
     int error = 0;
 };
 
@@ -165,6 +171,7 @@ Args parse(int argc, char **argv) {
         else if (f == "--order") { if (!need(1)) break; a.order = argv[++i]; }
         else if (f == "--mono") a.mono = true;
         else if (f == "--max") a.maximum = true;
+        else if (f == "--weighted") a.weighted = true;
         else if (f == "--threshold") { if (!need(1)) break; a.threshold = std::atof(argv[++i]); }
         else if (f == "--eps") { if (!need(1)) break; a.eps = std::atof(argv[++i]); }
         else if (f == "--gpus") { if (!need(1)) break; a.gpus = std::atoi(argv[++i]); if (a.gpus < 1 || a.gpus > 64) a.error = 100; }
@@ -194,7 +201,9 @@ Args parse(int argc, char **argv) {
     if (!a.error && traversal && (a.gpus > 1 || a.metric_given)) a.error = 100;  // a traversal is global; it has no metric
     if (!a.error && a.kernel == "pr" && a.metric_given) a.error = 100;              // … nor has PageRank
     if (!a.error && ((a.kernel == "msf" && (a.gpus > 1 || a.metric_given)) || (a.maximum && a.kernel != "msf"))) a.error = 100;  // a forest is global
-    if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc" && a.kernel != "closeness" && a.kernel != "pr"))) a.error = 100;
+    if (!a.error && ((a.kernel == "communities" && (a.gpus > 1 || a.metric_given)) || (a.weighted && a.kernel != "communities"))) a.error = 100;  // communities are global
+    if (!a.error && a.kernel == "communities" && a.iters > INT32_MAX) a.error = 100;
+    if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc" && a.kernel != "closeness" && a.kernel != "pr" && a.kernel != "communities"))) a.error = 100;
     if (!a.error && ((a.kernel == "sgi") != !a.pattern_file.empty() || (a.mono && a.kernel != "sgi"))) a.error = 100;  // util/command_line.hpp:22: the pattern is required
     if (!a.error && (a.kernel == "lp" || a.kernel == "jp") && lp_metric(a.metric) < 0) a.error = 100;
     if (!a.error && !a.order.empty() && a.kernel != "bk" && a.kernel != "color") a.error = 100;  // only Bron–Kerbosch and the colouring have a preprocessing step
@@ -207,10 +216,10 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf|communities> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
                 "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE] "
-                "[jp: --metric NAME --threshold X] [bfs, bc, closeness, sssp: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES] [pr: -i ITERS -t TOL] [sssp: -d DELTA] [msf: --max]\n", argv0);
+                "[jp: --metric NAME --threshold X] [bfs, bc, closeness, sssp: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES] [pr: -i ITERS -t TOL] [sssp: -d DELTA] [msf: --max] [communities: -i MAX_SWEEPS --weighted]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -1006,6 +1015,74 @@ int run_msf(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg, c
     return 0;
 }
 
+// the sequential propagation of gmsx.h over the host CSR: the vertices ascending by (colour, id); a vertex keeps its label if that is a heaviest
+// one among its neighbours, else takes the smallest heaviest label; wgt == nullptr: every arc weighs 1
+std::vector<int32_t> host_label_propagation(const HostGraph &hg, const int32_t *wgt, const std::vector<int32_t> &color, int64_t max_sweeps) {
+    std::vector<int32_t> order(size_t(hg.n)), label(size_t(hg.n));
+    for (int64_t v = 0; v < hg.n; ++v) order[size_t(v)] = label[size_t(v)] = int32_t(v);
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return color[size_t(a)] != color[size_t(b)] ? color[size_t(a)] < color[size_t(b)] : a < b; });
+    std::vector<std::pair<int32_t, int64_t>> seen;  // (label, weight) of the row at hand, ascending by the label
+    for (int64_t sweep = 0; sweep < (max_sweeps > 0 ? max_sweeps : 1000); ++sweep) {
+        int64_t changes = 0;
+        for (const int32_t v : order) {
+            seen.clear();
+            for (int64_t j = hg.off[v]; j < hg.off[v + 1]; ++j) seen.push_back({label[size_t(hg.adj[j])], wgt ? int64_t(wgt[j]) : 1});
+            if (seen.empty()) continue;
+            std::sort(seen.begin(), seen.end());
+            int64_t best_weight = 0, own = 0;
+            int32_t best = -1;
+            for (size_t i = 0; i < seen.size();) {
+                int64_t sum = 0;
+                const int32_t l = seen[i].first;
+                for (; i < seen.size() && seen[i].first == l; ++i) sum += seen[i].second;
+                if (sum > best_weight) best_weight = sum, best = l;  // (ascending labels: the first at the maximum is the smallest)
+                if (l == label[size_t(v)]) own = sum;
+            }
+            if (own == best_weight) continue;
+            label[size_t(v)] = best;
+            ++changes;
+        }
+        if (changes == 0) break;
+    }
+    return label;
+}
+
+// communities by label propagation under the usual trial loop; -v: every label against host_label_propagation
+int run_communities(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg, const gmsx_csr *csr) {
+    if (args.weighted) gmsx::detail::check(gmsx_graph_set_weights(const_cast<gmsx_graph *>(g.device()), gmsx_csr_weights(csr)), "gmsx_graph_set_weights");
+    const uint32_t flags = args.weighted ? uint32_t(GMSX_LP_WEIGHTED) : 0u;
+    const int32_t max_sweeps = args.iters_given ? int32_t(args.iters) : 0;
+    double total_seconds = 0, host_seconds = 0;
+    Timer t;
+    std::vector<int32_t> label, want;
+    gmsx_lp_info info{};
+    for (int64_t it = 0; it < args.trials; ++it) {
+        t.Start();
+        gmsx::label_propagation(g, label, flags, nullptr, max_sweeps, &info);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        const gmsx_modularity_info mod = gmsx::modularity(g, label, flags);
+        PrintLabel("Communities", std::to_string(info.communities));
+        PrintLabel("Sweeps", std::to_string(info.sweeps));
+        std::printf("%-21s%.6f\n", "Modularity:", mod.modularity);
+        if (args.verify) {
+            if (want.empty() && hg.n > 0) {
+                const std::vector<int32_t> color = gmsx::coloring(g, "id");
+                t.Start();
+                want = host_label_propagation(hg, args.weighted ? gmsx_csr_weights(csr) : nullptr, color, max_sweeps);
+                t.Stop();
+                host_seconds = t.Seconds();
+            }
+            PrintTime("Host Propagation", host_seconds);
+            PrintLabel("Verification", label == want && mod.communities == info.communities && (!info.converged || mod.unstable == 0) ? "PASS" : "FAIL");
+        }
+        std::cout << "@@@ communities " << (args.weighted ? "weighted" : "unweighted") << std::endl;
+    }
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
 // subgraph matching: the reference's VF2 drivers (subgraphiso_vf2_sequential.cpp:33-51) over gmsx::subgraph_isomorphisms
 int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
     gmsx_csr *pc = nullptr;
@@ -1067,7 +1144,7 @@ int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr" && args.kernel != "sssp" && args.kernel != "msf") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr" && args.kernel != "sssp" && args.kernel != "msf" && args.kernel != "communities") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -1087,7 +1164,7 @@ int main(int argc, char **argv) {
     t.Start();
     int rc;
     const int relabel = args.kernel == "sgi" ? GMSX_RELABEL_NEVER : GMSX_RELABEL_AUTO;  // the reference's subgraph drivers never relabel
-    if (args.kernel == "sssp" || args.kernel == "msf")  // WeightedBuilder: the weights of the file, or the generator's; never relabelled (sssp.cc:182-183)
+    if (args.kernel == "sssp" || args.kernel == "msf" || (args.kernel == "communities" && args.weighted))  // WeightedBuilder: the weights of the file, or the generator's; never relabelled (sssp.cc:182-183)
         rc = !args.file.empty() ? gmsx_csr_load_weighted(args.file.c_str(), 1, GMSX_RELABEL_NEVER, &csr)
                                 : gmsx_csr_generate_weighted(args.gen == "uniform" ? GMSX_GEN_UNIFORM : GMSX_GEN_KRONECKER, args.scale, args.deg,
                                                              GMSX_RELABEL_NEVER, int(args.threads), &csr);
@@ -1145,8 +1222,8 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr" || args.kernel == "sssp" || args.kernel == "msf") {
-        const int rc_run = args.kernel == "msf" ? run_msf(args, g, hg, csr) : args.kernel == "sssp" ? run_sssp(args, g, hg, csr) : args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr" || args.kernel == "sssp" || args.kernel == "msf" || args.kernel == "communities") {
+        const int rc_run = args.kernel == "communities" ? run_communities(args, g, hg, csr) : args.kernel == "msf" ? run_msf(args, g, hg, csr) : args.kernel == "sssp" ? run_sssp(args, g, hg, csr) : args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
                                                                                                                                         : run_components(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);

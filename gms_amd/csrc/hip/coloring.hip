@@ -18,6 +18,7 @@
 // supplies the per-vertex work (ColorJp), the setup and the final checks.  A short row keeps its bitmap in the group's LDS words; a long row is
 // parked with a piece of a zeroed global slab (its note) and takes its colour at the round boundary, so no graph is refused for a wide
 // neighbourhood.
+#include "coloring_device.hpp"
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
 #include "frontier_rounds.hpp"
@@ -234,6 +235,122 @@ __global__ __launch_bounds__(256) void k_cv_distinct(int64_t words, const uint32
 }
 
 }  // namespace
+
+// The colouring on the device: color and round_of stay in the two buffers (n words each), res and *launches_out are filled, and the rounds lie
+// between the events ev[0] and ev[1] of the context.  gmsx_coloring_jp copies the arrays out; label propagation (communities.hip) keeps them
+// where they are.  n > 0.
+int coloring_jp_device(const gmsx_graph *g, const int32_t *ordering, int rank_format, DevBuf &d_color, DevBuf &d_round, gmsx_coloring_info &res,
+                       int *launches_out) {
+    Ctx &c = ctx();
+    hipStream_t s = c.stream;
+    const int64_t n = g->n;
+    const int cus = c.compute_units > 0 ? c.compute_units : 256;
+    const unsigned tb = unsigned((n + 255) / 256);
+    DevBuf d_in, d_rank, d_seen, d_cnt, d_pred, d_slab, d_ctl, d_ctrl;
+    FrontierStore store;  // (a parked row's note: where its bitmap starts in the slab)
+    if (int rc = dalloc<int32_t>(d_in, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_cnt, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_pred, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_color, n)) return rc;
+    if (int rc = dalloc<int32_t>(d_round, n)) return rc;
+    if (int rc = store.alloc(n, g->nnz, true)) return rc;
+    const int64_t long_cap = store.long_cap;
+    // every long row is parked once in the whole run and takes pred/32 + 1 <= degree/32 + 1 words
+    const unsigned long long slab_cap = (unsigned long long)(g->nnz / 32 + long_cap);
+    if (int rc = dalloc<uint32_t>(d_slab, int64_t(slab_cap))) return rc;
+    if (int rc = dalloc<int32_t>(d_ctl, 4)) return rc;
+    if (int rc = dalloc<ColorCtrl>(d_ctrl, 1)) return rc;
+    const bool own_rank = ordering && !rank_format;
+    if (ordering)
+        if (int rc = dalloc<int32_t>(d_seen, n)) return rc;
+    if (own_rank)
+        if (int rc = dalloc<int32_t>(d_rank, n)) return rc;
+    ColorCtrl *ctrl = d_ctrl.as<ColorCtrl>();
+    int32_t *rank = own_rank ? d_rank.as<int32_t>() : d_in.as<int32_t>();
+    int32_t *cnt = d_cnt.as<int32_t>(), *pred = d_pred.as<int32_t>(), *color = d_color.as<int32_t>(), *rnd = d_round.as<int32_t>();
+    uint32_t *slab = d_slab.as<uint32_t>();
+    const FrontierBufs bufs = store.bufs();
+    const ColorJp jp{n, g->off, g->adj, pred, color, rnd, cnt, slab, slab_cap, &ctrl->slab_used, &ctrl->colors, 0};
+    const long long wg_frontier = frontier_wg_option("COLOR_WG_FRONTIER", kWgFrontierDefault);
+
+    GMSX_HIP(hipMemsetAsync(d_ctl.p, 0, 4 * sizeof(int32_t), s));
+    GMSX_HIP(hipMemsetAsync(ctrl, 0, sizeof(ColorCtrl), s));
+    GMSX_HIP(hipMemsetAsync(color, 0, size_t(n) * sizeof(int32_t), s));
+    GMSX_HIP(hipMemsetAsync(slab, 0, size_t(std::max<unsigned long long>(slab_cap, 1)) * sizeof(uint32_t), s));
+    int &launches = *launches_out;
+    launches = 0;
+    GMSX_HIP(hipEventRecord(c.ev[0], s));
+    if (ordering) {
+        GMSX_HIP(hipMemcpyAsync(d_in.p, ordering, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        GMSX_HIP(hipMemsetAsync(d_seen.p, 0, size_t(n) * sizeof(int32_t), s));
+        // a permutation of 0..n-1, checked before anything reads rank[] as an index; the reference mis-colours on ties
+        hipLaunchKernelGGL(k_oq_rank, dim3(tb), dim3(256), 0, s, n, d_in.as<int32_t>(), rank_format ? 1 : 0, rank, d_seen.as<int32_t>(),
+                           d_ctl.as<int32_t>() + 2);
+        int32_t ctl[4] = {0, 0, 0, 0};
+        GMSX_HIP(hipMemcpyAsync(ctl, d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+        GMSX_HIP(hipStreamSynchronize(s));
+        if (ctl[2]) return GMSX_ERR_INVALID;
+    } else {
+        hipLaunchKernelGGL(k_iota, dim3(tb), dim3(256), 0, s, n, rank);  // getSimpleIdOrdering: what coloring.cc:25-30 hands to JonesV3
+    }
+    const unsigned lb = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
+    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    const unsigned long_grid = unsigned(cus) * 4;
+    hipLaunchKernelGGL(k_oq_later, dim3(lb), dim3(256), 0, s, n, g->off, g->adj, rank, cnt, bufs.longs, long_cap, d_ctl.as<int32_t>());
+    hipLaunchKernelGGL(k_oq_later_long, dim3(long_grid), dim3(256), 0, s, g->off, g->adj, rank, cnt, bufs.longs, long_cap, d_ctl.as<int32_t>());
+    hipLaunchKernelGGL(k_color_select, dim3(sweep), dim3(256), 0, s, n, cnt, pred, ctrl, bufs.f[0]);
+    launches += 4;
+    ColorCtrl h;
+    std::memset(&h, 0, sizeof h);
+    int32_t ctl[4] = {0, 0, 0, 0};
+    GMSX_HIP(hipMemcpyAsync(ctl, d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
+    GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
+    GMSX_HIP(hipStreamSynchronize(s));
+    if (ctl[1] || h.error || h.count <= 0 || h.count > n) return GMSX_ERR_KERNEL;  // (a permutation has a maximum: the first frontier is not empty)
+    res.first_round = h.count;
+    res.max_pred = h.max_pred;
+    if (int rc = run_frontier_rounds(jp, bufs, ctrl, h, wg_frontier, &launches)) return rc;
+    GMSX_HIP(hipEventRecord(c.ev[1], s));
+    GMSX_HIP(hipStreamSynchronize(s));
+    GMSX_HIP(hipGetLastError());
+    if (h.done != n || h.colors < 1 || h.colors > h.max_pred + 1 || h.slab_used > slab_cap) return GMSX_ERR_KERNEL;
+    res.colors = h.colors;
+    res.rounds = h.round;
+    return GMSX_OK;
+}
+
+int coloring_verify_device(const gmsx_graph *g, const int32_t *d_color, unsigned long long acc[8], int32_t ctl[4], float *ms) {
+    Ctx &c = ctx();
+    hipStream_t s = c.stream;
+    const int64_t n = g->n;
+    const int cus = c.compute_units > 0 ? c.compute_units : 256;
+    const int64_t long_cap = frontier_long_cap(n, g->nnz);
+    const int64_t words = n / 32 + 1;  // colours 0..n
+    DevBuf d_present, d_long, d_ctl, d_acc;
+    if (int rc = dalloc<uint32_t>(d_present, words)) return rc;
+    if (int rc = dalloc<int32_t>(d_long, long_cap)) return rc;
+    if (int rc = dalloc<int32_t>(d_ctl, 4)) return rc;
+    if (int rc = dalloc<unsigned long long>(d_acc, 8)) return rc;
+    GMSX_HIP(hipMemsetAsync(d_present.p, 0, size_t(words) * sizeof(uint32_t), s));
+    GMSX_HIP(hipMemsetAsync(d_ctl.p, 0, 4 * sizeof(int32_t), s));
+    GMSX_HIP(hipMemsetAsync(d_acc.p, 0, 8 * sizeof(unsigned long long), s));
+    GMSX_HIP(hipEventRecord(c.ev[0], s));
+    const unsigned lb = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
+    const unsigned sweep = unsigned(std::min<int64_t>((words + 255) / 256, int64_t(cus) * 16));
+    hipLaunchKernelGGL(k_cv_rows, dim3(lb), dim3(256), 0, s, n, g->off, g->adj, d_color, d_present.as<uint32_t>(), d_long.as<int32_t>(), long_cap,
+                       d_ctl.as<int32_t>(), d_acc.as<unsigned long long>());
+    hipLaunchKernelGGL(k_cv_long, dim3(unsigned(cus) * 4), dim3(256), 0, s, g->off, g->adj, d_color, d_long.as<int32_t>(), long_cap, d_ctl.as<int32_t>(),
+                       d_acc.as<unsigned long long>());
+    hipLaunchKernelGGL(k_cv_distinct, dim3(sweep), dim3(256), 0, s, words, d_present.as<uint32_t>(), d_acc.as<unsigned long long>());
+    GMSX_HIP(hipEventRecord(c.ev[1], s));
+    GMSX_HIP(hipMemcpyAsync(acc, d_acc.p, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    GMSX_HIP(hipMemcpyAsync(ctl, d_ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GMSX_HIP(hipStreamSynchronize(s));
+    GMSX_HIP(hipGetLastError());
+    GMSX_HIP(hipEventElapsedTime(ms, c.ev[0], c.ev[1]));
+    return GMSX_OK;
+}
+
 }  // namespace gmsx
 
 using namespace gmsx;
@@ -246,7 +363,6 @@ int gmsx_coloring_jp(const gmsx_graph *g, const int32_t *ordering, int rank_form
         if (!g || !info) return GMSX_ERR_INVALID;
         if (int rc = ensure_init()) return rc;
         Ctx &c = ctx();
-        hipStream_t s = c.stream;
         const int64_t n = g->n;
         gmsx_coloring_info res;
         std::memset(&res, 0, sizeof res);
@@ -255,77 +371,10 @@ int gmsx_coloring_jp(const gmsx_graph *g, const int32_t *ordering, int rank_form
             if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0, 0};
             return GMSX_OK;
         }
-        const int cus = c.compute_units > 0 ? c.compute_units : 256;
-        const unsigned tb = unsigned((n + 255) / 256);
-        DevBuf d_in, d_rank, d_seen, d_cnt, d_pred, d_color, d_round, d_slab, d_ctl, d_ctrl;
-        FrontierStore store;  // (a parked row's note: where its bitmap starts in the slab)
-        if (int rc = dalloc<int32_t>(d_in, n)) return rc;
-        if (int rc = dalloc<int32_t>(d_cnt, n)) return rc;
-        if (int rc = dalloc<int32_t>(d_pred, n)) return rc;
-        if (int rc = dalloc<int32_t>(d_color, n)) return rc;
-        if (int rc = dalloc<int32_t>(d_round, n)) return rc;
-        if (int rc = store.alloc(n, g->nnz, true)) return rc;
-        const int64_t long_cap = store.long_cap;
-        // every long row is parked once in the whole run and takes pred/32 + 1 <= degree/32 + 1 words
-        const unsigned long long slab_cap = (unsigned long long)(g->nnz / 32 + long_cap);
-        if (int rc = dalloc<uint32_t>(d_slab, int64_t(slab_cap))) return rc;
-        if (int rc = dalloc<int32_t>(d_ctl, 4)) return rc;
-        if (int rc = dalloc<ColorCtrl>(d_ctrl, 1)) return rc;
-        const bool own_rank = ordering && !rank_format;
-        if (ordering)
-            if (int rc = dalloc<int32_t>(d_seen, n)) return rc;
-        if (own_rank)
-            if (int rc = dalloc<int32_t>(d_rank, n)) return rc;
-        ColorCtrl *ctrl = d_ctrl.as<ColorCtrl>();
-        int32_t *rank = own_rank ? d_rank.as<int32_t>() : d_in.as<int32_t>();
-        int32_t *cnt = d_cnt.as<int32_t>(), *pred = d_pred.as<int32_t>(), *color = d_color.as<int32_t>(), *rnd = d_round.as<int32_t>();
-        uint32_t *slab = d_slab.as<uint32_t>();
-        const FrontierBufs bufs = store.bufs();
-        const ColorJp jp{n, g->off, g->adj, pred, color, rnd, cnt, slab, slab_cap, &ctrl->slab_used, &ctrl->colors, 0};
-        const long long wg_frontier = frontier_wg_option("COLOR_WG_FRONTIER", kWgFrontierDefault);
-
-        GMSX_HIP(hipMemsetAsync(d_ctl.p, 0, 4 * sizeof(int32_t), s));
-        GMSX_HIP(hipMemsetAsync(ctrl, 0, sizeof(ColorCtrl), s));
-        GMSX_HIP(hipMemsetAsync(color, 0, size_t(n) * sizeof(int32_t), s));
-        GMSX_HIP(hipMemsetAsync(slab, 0, size_t(std::max<unsigned long long>(slab_cap, 1)) * sizeof(uint32_t), s));
+        DevBuf d_color, d_round;
         int launches = 0;
-        GMSX_HIP(hipEventRecord(c.ev[0], s));
-        if (ordering) {
-            GMSX_HIP(hipMemcpyAsync(d_in.p, ordering, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            GMSX_HIP(hipMemsetAsync(d_seen.p, 0, size_t(n) * sizeof(int32_t), s));
-            // a permutation of 0..n-1, checked before anything reads rank[] as an index; the reference mis-colours on ties
-            hipLaunchKernelGGL(k_oq_rank, dim3(tb), dim3(256), 0, s, n, d_in.as<int32_t>(), rank_format ? 1 : 0, rank, d_seen.as<int32_t>(),
-                               d_ctl.as<int32_t>() + 2);
-            int32_t ctl[4] = {0, 0, 0, 0};
-            GMSX_HIP(hipMemcpyAsync(ctl, d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
-            GMSX_HIP(hipStreamSynchronize(s));
-            if (ctl[2]) return GMSX_ERR_INVALID;
-        } else {
-            hipLaunchKernelGGL(k_iota, dim3(tb), dim3(256), 0, s, n, rank);  // getSimpleIdOrdering: what coloring.cc:25-30 hands to JonesV3
-        }
-        const unsigned lb = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
-        const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
-        const unsigned long_grid = unsigned(cus) * 4;
-        hipLaunchKernelGGL(k_oq_later, dim3(lb), dim3(256), 0, s, n, g->off, g->adj, rank, cnt, bufs.longs, long_cap, d_ctl.as<int32_t>());
-        hipLaunchKernelGGL(k_oq_later_long, dim3(long_grid), dim3(256), 0, s, g->off, g->adj, rank, cnt, bufs.longs, long_cap, d_ctl.as<int32_t>());
-        hipLaunchKernelGGL(k_color_select, dim3(sweep), dim3(256), 0, s, n, cnt, pred, ctrl, bufs.f[0]);
-        launches += 4;
-        ColorCtrl h;
-        std::memset(&h, 0, sizeof h);
-        int32_t ctl[4] = {0, 0, 0, 0};
-        GMSX_HIP(hipMemcpyAsync(ctl, d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipStreamSynchronize(s));
-        if (ctl[1] || h.error || h.count <= 0 || h.count > n) return GMSX_ERR_KERNEL;  // (a permutation has a maximum: the first frontier is not empty)
-        res.first_round = h.count;
-        res.max_pred = h.max_pred;
-        if (int rc = run_frontier_rounds(jp, bufs, ctrl, h, wg_frontier, &launches)) return rc;
-        GMSX_HIP(hipEventRecord(c.ev[1], s));
-        GMSX_HIP(hipStreamSynchronize(s));
-        GMSX_HIP(hipGetLastError());
-        if (h.done != n || h.colors < 1 || h.colors > h.max_pred + 1 || h.slab_used > slab_cap) return GMSX_ERR_KERNEL;
-        res.colors = h.colors;
-        res.rounds = h.round;
+        if (int rc = coloring_jp_device(g, ordering, rank_format, d_color, d_round, res, &launches)) return rc;
+        const int32_t *color = d_color.as<const int32_t>(), *rnd = d_round.as<const int32_t>();
         // the outputs are written only now, when nothing can fail but the copies themselves
         std::vector<int32_t> h_color, h_round;
         if (coloring) {
@@ -360,34 +409,13 @@ int gmsx_coloring_verify(const gmsx_graph *g, const int32_t *coloring, gmsx_colo
             if (stats) *stats = gmsx_stats{0.0, 0.0, 0, 0, 0, 0, 0, 0};
             return GMSX_OK;
         }
-        const int cus = c.compute_units > 0 ? c.compute_units : 256;
-        const int64_t long_cap = frontier_long_cap(n, g->nnz);
-        const int64_t words = n / 32 + 1;  // colours 0..n
-        DevBuf d_color, d_present, d_long, d_ctl, d_acc;
+        DevBuf d_color;
         if (int rc = dalloc<int32_t>(d_color, n)) return rc;
-        if (int rc = dalloc<uint32_t>(d_present, words)) return rc;
-        if (int rc = dalloc<int32_t>(d_long, long_cap)) return rc;
-        if (int rc = dalloc<int32_t>(d_ctl, 4)) return rc;
-        if (int rc = dalloc<unsigned long long>(d_acc, 8)) return rc;
         GMSX_HIP(hipMemcpyAsync(d_color.p, coloring, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        GMSX_HIP(hipMemsetAsync(d_present.p, 0, size_t(words) * sizeof(uint32_t), s));
-        GMSX_HIP(hipMemsetAsync(d_ctl.p, 0, 4 * sizeof(int32_t), s));
-        GMSX_HIP(hipMemsetAsync(d_acc.p, 0, 8 * sizeof(unsigned long long), s));
-        GMSX_HIP(hipEventRecord(c.ev[0], s));
-        const unsigned lb = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
-        const unsigned sweep = unsigned(std::min<int64_t>((words + 255) / 256, int64_t(cus) * 16));
-        hipLaunchKernelGGL(k_cv_rows, dim3(lb), dim3(256), 0, s, n, g->off, g->adj, d_color.as<int32_t>(), d_present.as<uint32_t>(), d_long.as<int32_t>(),
-                           long_cap, d_ctl.as<int32_t>(), d_acc.as<unsigned long long>());
-        hipLaunchKernelGGL(k_cv_long, dim3(unsigned(cus) * 4), dim3(256), 0, s, g->off, g->adj, d_color.as<int32_t>(), d_long.as<int32_t>(), long_cap,
-                           d_ctl.as<int32_t>(), d_acc.as<unsigned long long>());
-        hipLaunchKernelGGL(k_cv_distinct, dim3(sweep), dim3(256), 0, s, words, d_present.as<uint32_t>(), d_acc.as<unsigned long long>());
-        GMSX_HIP(hipEventRecord(c.ev[1], s));
         unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int32_t ctl[4] = {0, 0, 0, 0};
-        GMSX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipMemcpyAsync(ctl, d_ctl.p, sizeof ctl, hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipStreamSynchronize(s));
-        GMSX_HIP(hipGetLastError());
+        float ms = 0.f;
+        if (int rc = coloring_verify_device(g, d_color.as<const int32_t>(), acc, ctl, &ms)) return rc;
         if (ctl[1] || (acc[kAccArcs] & 1ull)) return GMSX_ERR_KERNEL;  // (the CSR is symmetric: every equal pair is met from both ends)
         // the colours the bitmap does not cover — negative, or above n — are counted here; a colouring of any algorithm has none
         std::vector<int32_t> outliers;
@@ -395,8 +423,6 @@ int gmsx_coloring_verify(const gmsx_graph *g, const int32_t *coloring, gmsx_colo
             if (coloring[v] < 0 || int64_t(coloring[v]) > n) outliers.push_back(coloring[v]);
         std::sort(outliers.begin(), outliers.end());
         const int64_t extra = int64_t(std::unique(outliers.begin(), outliers.end()) - outliers.begin());
-        float ms = 0.f;
-        GMSX_HIP(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
         res.conflicts = int64_t(acc[kAccArcs] / 2);
         res.invalid = int64_t(acc[kAccInvalid]);
         res.max_color = int32_t(int64_t(acc[kAccMax]) - (1ll << 31));

@@ -4,10 +4,12 @@
 // Every function is called by ALL lanes of the wave (of the WIDTH-lane group: WIDTH a power of two <= 64, groups aligned to WIDTH lanes).
 //   wave_sum / wave_max / wave_min / wave_or           the DOWN tree: offsets WIDTH/2, …, 1 with __shfl_down(x, o, WIDTH).  The result is valid in
 //                                                      LANE 0 OF EACH GROUP ONLY; the other lanes hold partial values.
-//   wave_sum_all / wave_min_all / wave_or_all
+//   wave_sum_all / wave_max_all / wave_min_all / wave_or_all
 //                                                      the same offsets as a BUTTERFLY (__shfl_xor): the result is valid in EVERY lane.
 //   wave_incl_scan<WIDTH>(x, lane_in_group)            inclusive prefix sum over the group (__shfl_up, offsets 1, 2, …, WIDTH/2).
 //   wave_fold2 / wave_fold2_all(a, b, f)               the down tree / the butterfly over a PAIR: f(a, b, a_of_other_lane, b_of_other_lane) updates a, b.
+//   wave_pair_max / wave_pair_max_all<WIDTH>(w, l)     the down tree / the butterfly over a (weight, label) pair: the larger weight wins, of equal weights
+//                                                      the SMALLER label (label propagation's pick: integers, so the order of the lanes cannot matter).
 //   block_sum<kWaves>(x, s_w)                          the down tree per wave, then s_w[0] + s_w[1] + … on thread 0; two barriers.
 // THE ORDER OF THE ADDITIONS IS PART OF THE CONTRACT: lane l adds x[l + o] to x[l] for o = WIDTH/2, …, 1 in this order.  Floating-point callers
 // (PageRank's scores, betweenness' dependencies, the pair similarities) are bit-identical to their goldens only because of it, so a change of
@@ -41,6 +43,7 @@ template <int WIDTH = 64, class T> __device__ __forceinline__ T wave_max(T x) { 
 template <int WIDTH = 64, class T> __device__ __forceinline__ T wave_min(T x) { return wave_fold<WIDTH>(x, FoldMin()); }
 template <int WIDTH = 64, class T> __device__ __forceinline__ T wave_or(T x) { return wave_fold<WIDTH>(x, FoldOr()); }
 template <int WIDTH = 64, class T> __device__ __forceinline__ T wave_sum_all(T x) { return wave_fold_all<WIDTH>(x, FoldSum()); }
+template <int WIDTH = 64, class T> __device__ __forceinline__ T wave_max_all(T x) { return wave_fold_all<WIDTH>(x, FoldMax()); }
 template <int WIDTH = 64, class T> __device__ __forceinline__ T wave_min_all(T x) { return wave_fold_all<WIDTH>(x, FoldMin()); }
 template <int WIDTH = 64, class T> __device__ __forceinline__ T wave_or_all(T x) { return wave_fold_all<WIDTH>(x, FoldOr()); }
 
@@ -75,6 +78,24 @@ __device__ __forceinline__ void wave_fold2_all(A &a, B &b, F f) {
         const A a2 = __shfl_xor(a, o);
         const B b2 = __shfl_xor(b, o);
         f(a, b, a2, b2);
+    }
+}
+
+// the maximum of a (weight, label) pair over WIDTH-lane groups: (w, l) beats (w2, l2) iff w > w2, or w == w2 and l < l2
+template <int WIDTH = 64, class W, class L>
+__device__ __forceinline__ void wave_pair_max(W &w, L &l) {
+    for (int o = WIDTH / 2; o > 0; o >>= 1) {
+        const W w2 = __shfl_down(w, o, shfl_width<WIDTH>());
+        const L l2 = __shfl_down(l, o, shfl_width<WIDTH>());
+        if (w2 > w || (w2 == w && l2 < l)) w = w2, l = l2;
+    }
+}
+template <int WIDTH = 64, class W, class L>
+__device__ __forceinline__ void wave_pair_max_all(W &w, L &l) {
+    for (int o = WIDTH / 2; o > 0; o >>= 1) {
+        const W w2 = __shfl_xor(w, o, shfl_width<WIDTH>());
+        const L l2 = __shfl_xor(l, o, shfl_width<WIDTH>());
+        if (w2 > w || (w2 == w && l2 < l)) w = w2, l = l2;
     }
 }
 

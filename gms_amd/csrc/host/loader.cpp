@@ -998,6 +998,8 @@ Option g_options[] = {
     {"SSSP_WG_FRONTIER", "", false}, {"SSSP_WIDE", "", false}, {"SSSP_DELTA_AUTO", "", false},
     // minimum spanning forest (msf.hip)
     {"MSF_WAVE_ROW", "", false}, {"MSF_WG_ROW", "", false}, {"MSF_PRUNE", "", false},
+    // label propagation and modularity (communities.hip)
+    {"LP_WAVE_ROW", "", false}, {"LP_LDS_ROW", "", false}, {"LP_LDS_SLOTS", "", false}, {"LP_WG_WORK", "", false}, {"LP_ACTIVE", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

@@ -218,7 +218,15 @@ int gmsx_set_host_threads(int n);
  *                   gmsx_min_spanning_forest, defaults 256 / 4096, as CC_WAVE_ROW / CC_WG_ROW), MSF_PRUNE (0, the default = every vertex is searched in every
  *                   round; 1 = a vertex without a crossing arc leaves the live list for good, so that later rounds walk the shrinking border
  *                   only — measured slower on four graphs) — the bin edges are first guesses, not tuned values; test hooks;
- *                   none changes any output of gmsx_min_spanning_forest except gmsx_stats */
+ *                   none changes any output of gmsx_min_spanning_forest except gmsx_stats
+ *   communities            LP_WAVE_ROW (longest row a lane group evaluates with one entry per lane, default and maximum 64; 0 = no such rows),
+ *                   LP_LDS_ROW (longest row whose label table lives in a workgroup's LDS, default 2048, at most LP_LDS_SLOTS; 0 = none),
+ *                   LP_LDS_SLOTS (slots of that table, a power of two in 16 … 4096, default 4096 = 48 KB of the 160 KB of a compute unit),
+ *                   LP_WG_WORK (consecutive colour classes whose rows hold at most this many entries in all are run by one workgroup in one
+ *                   launch, default 4096; 0 = every class in launches of its own), LP_ACTIVE (1, the default = from the second sweep on only
+ *                   the vertices a neighbour of which changed are evaluated; 0 = every vertex in every sweep) — the three row bounds are first
+ *                   guesses, not tuned values; LP_WG_WORK and LP_ACTIVE were set from a measurement; test hooks; none changes any output of gmsx_label_propagation or gmsx_modularity except
+ *                   gmsx_stats */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -950,6 +958,56 @@ int gmsx_min_spanning_forest(const gmsx_graph *g, uint32_t flags,
                              int32_t *edge_u, int32_t *edge_v, int32_t *edge_w /* each: room for n - 1 entries, host, or NULL (all three or none) */,
                              uint8_t *arc_keep /* nnz, host, or NULL */, int32_t *label /* n, host, or NULL */,
                              gmsx_msf_info *info /* required */, gmsx_stats *stats);
+
+/* ---- label-propagation communities and the exact modularity of a labelling (communities.hip; no reference counterpart).  Everything is an
+ * integer; nothing on the device is floating point.
+ * INPUTS.  The uploaded CSR and, with GMSX_LP_WEIGHTED in flags, the attached weights (>= 1, symmetric unless the handle was uploaded with
+ * GMSX_UPLOAD_TRUSTED); without the flag every arc weighs 1.
+ * COLOURING.  A proper colouring c[v] in 1 … C fixes the order of the work.  A caller's array is checked on the device: a colour below 1 or
+ * above n, or an edge with equal colours at its ends → GMSX_ERR_INVALID, nothing written.  NULL = exactly the array gmsx_coloring_jp(g, NULL, …)
+ * returns, computed by the same code and left on the device.
+ * A SWEEP.  label[v] = v at the start.  The colours are taken in the order 1, 2, …, C, all vertices of a colour at once.  W_v(l) = the total
+ * weight (an int64 sum) of v's arcs to neighbours that hold label l now, M = max_l W_v(l).  If W_v(label[v]) == M, v keeps its label (an
+ * isolated vertex always does); otherwise it takes the SMALLEST l with W_v(l) == M.  A colour class is an independent set, so this is the
+ * sequential asynchronous propagation that visits the vertices ascending by (colour, id) — the whole CPU restatement.
+ * STOP.  After the first sweep that changes no label (converged = 1), or after max_sweeps sweeps (converged = 0 unless that last sweep changed
+ * nothing); max_sweeps == 0: the library's cap of 1000; max_sweeps < 0: GMSX_ERR_INVALID.  Every change makes the vertex's label strictly
+ * heavier among its neighbours and no neighbour moves at the same time, so under symmetric weights the total weight of the arcs whose ends share
+ * a label rises strictly with every change and the propagation ends; asymmetric weights (TRUSTED) have only the cap.
+ * gmsx_modularity scores any labelling with labels in [0, n): W = the total arc weight (2 m unweighted), I = the total weight of the arcs whose
+ * ends share a label (both directions), D_c = the weighted degrees of the vertices labelled c, S = Σ_c D_c² exactly, in 128 bits (hi, lo).
+ * modularity = I / W - S / W², computed once on the host by the fixed expression (long double)I / W - ((long double)hi * 2^64 + lo) / (W * W)
+ * in long double and rounded to double; 0 when W = 0.  The integers are the contract, modularity is a convenience.  unstable = the non-isolated
+ * vertices with W_v(label[v]) < M: a labelling is a fixed point of the propagation under every colouring iff unstable == 0.
+ * label and every field of both info blocks are byte-identical in every run and process, under every LP_* option, GMSX_UPLOAD_TRUSTED,
+ * GMSX_UPLOAD_HUB_LIMIT, a sharded upload, a second handle and re-attached weights; "smallest label" is the smallest in the caller's ids.
+ * NULL g or info, unknown flag bits, GMSX_LP_WEIGHTED without attached weights, a NULL label (n > 0) or one outside [0, n) in gmsx_modularity:
+ * GMSX_ERR_INVALID, nothing written.  n = 0: GMSX_OK, info zeroed.  No edge: n singletons, sweeps = 1, converged = 1, modularity = 0.  A table
+ * insert or a placement past its bound, or a probe loop past its cap: GMSX_ERR_KERNEL; nothing is written out of bounds.  The caller's arrays
+ * are written only after the device flag word was read as zero.  Single GPU, no shards; the handle is not modified.  Test hooks: options
+ * LP_WAVE_ROW, LP_LDS_ROW, LP_LDS_SLOTS, LP_WG_WORK, LP_ACTIVE.  gmsx_stats: kernel_ms (the sweeps / the scoring pass), setup_ms, launches,
+ * units = rows evaluated, alg_elements = arcs gathered, probes = sweeps — these may differ under the options. */
+enum { GMSX_LP_WEIGHTED = 1u };
+typedef struct {
+    int64_t communities;   /* distinct labels at the end */
+    int64_t largest;       /* vertices of the largest community */
+    int64_t singletons;    /* communities of one vertex, isolated vertices included */
+    int64_t changes;       /* label changes over all sweeps: a fact about (graph, weights, colouring, max_sweeps) */
+    int64_t first_sweep_changes;
+    int32_t sweeps;        /* sweeps run, the changeless last one included */
+    int32_t colors;        /* C */
+    int32_t converged, largest_label;   /* ties: the smallest label */
+} gmsx_lp_info;
+int gmsx_label_propagation(const gmsx_graph *g, uint32_t flags, const int32_t *coloring /* n, host, or NULL */, int32_t max_sweeps,
+                           int32_t *label /* n, host, or NULL */, gmsx_lp_info *info /* required */, gmsx_stats *stats);
+typedef struct {
+    int64_t total_weight, intra_weight;   /* W, I */
+    uint64_t sumsq_hi, sumsq_lo;          /* S */
+    int64_t communities, largest, unstable;
+    double modularity;
+} gmsx_modularity_info;
+int gmsx_modularity(const gmsx_graph *g, uint32_t flags, const int32_t *label /* n, host */, gmsx_modularity_info *info /* required */,
+                    gmsx_stats *stats);
 
 /* ---- 4-cycle counting and the 3- / 4-vertex motif census.  No reference counterpart (like the k-truss: a member of the family the suite
  * describes and does not build).  All results are exact integers.

@@ -46,6 +46,8 @@
 //   gmsx::sssp_verify(g, source, dist)   -> gmsx_sssp_verify        (sssp.cc:145-175, SSSPVerifier)
 //   gmsx::min_spanning_forest(g, edges, flags, info) -> gmsx_min_spanning_forest (the forest's (u, v, w), u < v, ascending; GMSX_MSF_MAXIMUM: the maximum one; no reference driver)
 //   gmsx::msf_arc_mask(g, flags)         -> gmsx_min_spanning_forest (a byte per arc of g.neighbors(): 1 on both arcs of every forest edge — what gmsx_connected_components takes)
+//   gmsx::label_propagation(g, label, flags, coloring, max_sweeps, info) -> gmsx_label_propagation (communities by asynchronous label propagation, colour class by colour class; no reference driver)
+//   gmsx::modularity(g, label, flags)    -> gmsx_modularity         (W, I, Σ D_c² in 128 bits, unstable and Q = I / W - S / W² of any labelling)
 //   gmsx::pick_sources(csr, count)       -> gmsx_csr_pick_sources   (gapbs/benchmark.h:51-75, SourcePicker)
 //   gmsx::cycle4_count(g) / cycle4_count(g, at_vertex) -> gmsx_cycle4_count (the 4-cycles, and those through every vertex; no reference driver)
 //   gmsx::motif_census4(g)               -> gmsx_motif_census4     (the eight 3- and 4-vertex motifs, non-induced and induced; no reference driver)
@@ -833,6 +835,31 @@ inline std::vector<uint8_t> msf_arc_mask(const HipGraphT<S> &g, uint32_t flags =
     keep.resize(size_t(nnz));
     if (info) *info = mi;
     return keep;
+}
+// Communities by label propagation (gmsx.h): label[v] = the id of a member of v's community.  flags = GMSX_LP_WEIGHTED sums the weights attached
+// with gmsx::set_weights instead of counting arcs; coloring (optional, one colour >= 1 per vertex, proper) fixes the order of the asynchronous
+// sweeps — nullptr: the colouring gmsx::coloring(g) returns; max_sweeps = 0: the library's cap.  No reference counterpart.  Returns the number
+// of communities; `info` (optional) receives sweeps, changes, converged …
+template <class S>
+inline int64_t label_propagation(const HipGraphT<S> &g, std::vector<int32_t> &label, uint32_t flags = 0, const std::vector<int32_t> *coloring = nullptr,
+                                 int32_t max_sweeps = 0, gmsx_lp_info *info = nullptr) {
+    if (coloring && coloring->size() != size_t(g.num_nodes())) detail::check(GMSX_ERR_INVALID, "gmsx_label_propagation");
+    label.resize(size_t(g.num_nodes()));
+    gmsx_lp_info li{};
+    detail::check(gmsx_label_propagation(g.device(), flags, coloring && !coloring->empty() ? coloring->data() : nullptr, max_sweeps,
+                                         label.empty() ? nullptr : label.data(), &li, nullptr),
+                  "gmsx_label_propagation");
+    if (info) *info = li;
+    return li.communities;
+}
+// The exact modularity integers of any labelling with labels in [0, n) (gmsx.h): W, I, S = Σ D_c² as (hi, lo), communities, largest, unstable,
+// and modularity = I / W - S / W² computed from them once.
+template <class S>
+inline gmsx_modularity_info modularity(const HipGraphT<S> &g, const std::vector<int32_t> &label, uint32_t flags = 0) {
+    if (label.size() != size_t(g.num_nodes())) detail::check(GMSX_ERR_INVALID, "gmsx_modularity");
+    gmsx_modularity_info mi{};
+    detail::check(gmsx_modularity(g.device(), flags, label.empty() ? nullptr : label.data(), &mi, nullptr), "gmsx_modularity");
+    return mi;
 }
 // PrintTopScores' top k (pr.cc:64-74, gapbs/util.h TopK) on the host: the k largest scores as (id, score), largest first, ties by the smaller id
 inline std::vector<std::pair<int32_t, double>> top_scores(const std::vector<double> &scores, size_t k) {
