@@ -51,6 +51,7 @@ SYMBOLS = [
     "gmsx_csr_from_arrays_weighted", "gmsx_graph_set_weights", "gmsx_graph_has_weights", "gmsx_sssp", "gmsx_sssp_verify",
     "gmsx_min_spanning_forest",
     "gmsx_label_propagation", "gmsx_modularity",
+    "gmsx_greedy_matching", "gmsx_matching_verify",
     "gmsx_cycle4_count", "gmsx_cycle4_partial", "gmsx_motif_census4",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -243,6 +244,25 @@ class ModularityInfo(C.Structure):
         d["sumsq"] = (d["sumsq_hi"] << 64) | d["sumsq_lo"]
         d["modularity"] = float(self.modularity)
         return d
+
+
+MATCH_WEIGHTED = 1
+
+
+class MatchingInfo(C.Structure):
+    _fields_ = [("pairs", C.c_int64), ("total_weight", C.c_int64), ("free_vertices", C.c_int64), ("exposed", C.c_int64),
+                ("min_weight", C.c_int32), ("max_weight", C.c_int32), ("rounds", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class MatchingCheck(C.Structure):
+    _fields_ = [("invalid", C.c_int64), ("pairs", C.c_int64), ("total_weight", C.c_int64), ("free_vertices", C.c_int64),
+                ("augmentable", C.c_int64), ("undominated", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class MotifInfo(C.Structure):
@@ -444,6 +464,8 @@ def lib():
     L.gmsx_min_spanning_forest.argtypes = [vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MsfInfo), sp]
     L.gmsx_label_propagation.argtypes = [vp, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(LpInfo), sp]
     L.gmsx_modularity.argtypes = [vp, C.c_uint32, C.c_void_p, C.POINTER(ModularityInfo), sp]
+    L.gmsx_greedy_matching.argtypes = [vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MatchingInfo), sp]
+    L.gmsx_matching_verify.argtypes = [vp, C.c_uint32, C.c_void_p, C.POINTER(MatchingCheck), sp]
     L.gmsx_cycle4_count.argtypes = [vp, u64p, C.c_void_p, sp]
     L.gmsx_cycle4_partial.argtypes = [vp, C.c_int, C.c_int, u64p, sp]
     L.gmsx_motif_census4.argtypes = [vp, C.POINTER(MotifInfo), sp]
@@ -1284,6 +1306,34 @@ class DeviceGraph:
         _check(lib().gmsx_modularity(self._h, LP_WEIGHTED if weighted else 0, (lab if lab.size else np.zeros(1, np.int32)).ctypes.data_as(C.c_void_p),
                                      C.byref(info), C.byref(st)), "gmsx_modularity")
         return (info.as_dict(), st.as_dict()) if stats else info.as_dict()
+
+    def greedy_matching(self, weighted=False, want_mate=True, want_edges=False, stats=False):
+        """gmsx_greedy_matching: (mate, u, v, w, info[, stats]).  mate: int32[n], every vertex's partner or -1 (None with want_mate=False);
+        u, v, w: int32[pairs], the pairs with u < v ascending by u and their weights, or None each; info: {pairs, total_weight, free_vertices,
+        exposed, min_weight, max_weight, rounds}.  weighted=True orders the edges by the attached weights, heavier first (GMSX_MATCH_WEIGHTED);
+        else every edge weighs 1.  The matching is the sequential greedy one under the strict order of gmsx.h: the same bytes in every run."""
+        n = self.num_nodes
+        mate = np.zeros(max(n, 1), dtype=np.int32) if want_mate else None
+        eu, ev, ew = (np.zeros(max(n // 2, 1), dtype=np.int32) for _ in range(3)) if want_edges else (None, None, None)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        info, st = MatchingInfo(), Stats()
+        _check(lib().gmsx_greedy_matching(self._h, MATCH_WEIGHTED if weighted else 0, p(mate), p(eu), p(ev), p(ew), C.byref(info), C.byref(st)),
+               "gmsx_greedy_matching")
+        ne = int(info.pairs)
+        r = (mate[:n] if want_mate else None, eu[:ne] if want_edges else None, ev[:ne] if want_edges else None, ew[:ne] if want_edges else None,
+             info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
+
+    def matching_verify(self, mate, weighted=False, stats=False):
+        """gmsx_matching_verify of a mate array int32[n] (-1 = free): {invalid, pairs, total_weight, free_vertices, augmentable, undominated}.
+        invalid == 0 and undominated == 0 iff mate is the greedy matching under the order of gmsx.h; augmentable == 0 iff it is maximal."""
+        m = np.ascontiguousarray(mate, dtype=np.int32)
+        if m.size != self.num_nodes:
+            raise ValueError("mate must have one entry per vertex")
+        out, st = MatchingCheck(), Stats()
+        _check(lib().gmsx_matching_verify(self._h, MATCH_WEIGHTED if weighted else 0, (m if m.size else np.zeros(1, np.int32)).ctypes.data_as(C.c_void_p),
+                                          C.byref(out), C.byref(st)), "gmsx_matching_verify")
+        return (out.as_dict(), st.as_dict()) if stats else out.as_dict()
 
     def cycle4_count(self, at_vertex=False, stats=False):
         """gmsx_cycle4_count: the 4-cycles of the graph; with at_vertex=True (cycles, int64[n] — the 4-cycles through every vertex of the

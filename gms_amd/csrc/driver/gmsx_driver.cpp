@@ -82,7 +82,12 @@
 //                    the graph with its weights as for sssp and sums them.  Per trial "Trial Time", "Communities", "Sweeps", "Modularity" and with
 //                    -v "Verification" — this driver's own sequential propagation over the host CSR, the vertices ascending by (colour, id), must
 //                    give the same label for every vertex —, then the "@@@" line.  Not sharded (--gpus > 1 is refused).
-// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf|communities> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
+// Added:  matching [--weighted]   the greedy matching on the device (gmsx_greedy_matching; no reference driver): unit weights, or with --weighted the
+//                    weights, heavier first; the graph is generated or loaded with its weights as for sssp either way (never relabelled).  Per trial "Trial Time", "Pairs", "Total Weight",
+//                    "Free", "Rounds" and with -v "Verification" — this driver's own sequential greedy over the edges sorted by the order of gmsx.h
+//                    must give the same mate for every vertex, and gmsx_matching_verify must certify it —, then the "@@@" line.  Not sharded
+//                    (--gpus > 1 is refused).
+// Usage:  gmsx_driver <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf|communities|matching> [reference flags] [--gpus N]     e.g.  gmsx_driver tc -g kronecker 20 --deg 16 -n 3 -v
 #include <sys/prctl.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -128,7 +133,7 @@ struct Args {  // gms/common/cli/args.h:17-107 defaults
     double tol = 1e-4;   // pr -t TOL
     int64_t delta = 0;   // sssp -d DELTA (0: the library's choice)
     bool maximum = false;  // msf --max
-    bool weighted = false; // communities --weighted
+    bool weighted = false; // communities --weighted, matching --weighted
     int error = 0;
 };
 
@@ -201,7 +206,8 @@ Args parse(int argc, char **argv) {
     if (!a.error && traversal && (a.gpus > 1 || a.metric_given)) a.error = 100;  // a traversal is global; it has no metric
     if (!a.error && a.kernel == "pr" && a.metric_given) a.error = 100;              // … nor has PageRank
     if (!a.error && ((a.kernel == "msf" && (a.gpus > 1 || a.metric_given)) || (a.maximum && a.kernel != "msf"))) a.error = 100;  // a forest is global
-    if (!a.error && ((a.kernel == "communities" && (a.gpus > 1 || a.metric_given)) || (a.weighted && a.kernel != "communities"))) a.error = 100;  // communities are global
+    if (!a.error && ((a.kernel == "communities" && (a.gpus > 1 || a.metric_given)) || (a.weighted && a.kernel != "communities" && a.kernel != "matching"))) a.error = 100;  // communities are global
+    if (!a.error && a.kernel == "matching" && (a.gpus > 1 || a.metric_given)) a.error = 100;  // … and so is a matching
     if (!a.error && a.kernel == "communities" && a.iters > INT32_MAX) a.error = 100;
     if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc" && a.kernel != "closeness" && a.kernel != "pr" && a.kernel != "communities"))) a.error = 100;
     if (!a.error && ((a.kernel == "sgi") != !a.pattern_file.empty() || (a.mono && a.kernel != "sgi"))) a.error = 100;  // util/command_line.hpp:22: the pattern is required
@@ -216,10 +222,10 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf|communities> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf|communities|matching> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
                 "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE] "
-                "[jp: --metric NAME --threshold X] [bfs, bc, closeness, sssp: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES] [pr: -i ITERS -t TOL] [sssp: -d DELTA] [msf: --max] [communities: -i MAX_SWEEPS --weighted]\n", argv0);
+                "[jp: --metric NAME --threshold X] [bfs, bc, closeness, sssp: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES] [pr: -i ITERS -t TOL] [sssp: -d DELTA] [msf: --max] [communities: -i MAX_SWEEPS --weighted] [matching: --weighted]\n", argv0);
 }
 
 // ---- host-side verifiers: this driver's own plain loops over the host CSR (independent of the device kernels) ----------
@@ -1083,6 +1089,67 @@ int run_communities(const Args &args, const gmsx::HipSetGraph &g, const HostGrap
     return 0;
 }
 
+// the sequential greedy matching over the host CSR under the order of gmsx.h: the u < v arcs by (heavier weight first, h(u, v), u, v); an edge
+// is kept iff both ends are still free
+std::vector<int32_t> host_greedy_matching(const HostGraph &hg, const int32_t *wgt) {
+    struct Edge { uint32_t k0, h; int32_t u, v; };
+    const auto mix = [](uint32_t lo, uint32_t hi) {
+        uint32_t h = lo * 0x9E3779B1u + hi;
+        h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+        return h;
+    };
+    std::vector<Edge> all;
+    for (int64_t u = 0; u < hg.n; ++u)
+        for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j)
+            if (int64_t(hg.adj[j]) > u) all.push_back({wgt ? ~uint32_t(wgt[j]) : 0u, mix(uint32_t(u), uint32_t(hg.adj[j])), int32_t(u), hg.adj[j]});
+    std::sort(all.begin(), all.end(), [](const Edge &a, const Edge &b) {
+        return a.k0 != b.k0 ? a.k0 < b.k0 : a.h != b.h ? a.h < b.h : a.u != b.u ? a.u < b.u : a.v < b.v;
+    });
+    std::vector<int32_t> mate(size_t(hg.n), -1);
+    for (const Edge &e : all)
+        if (mate[size_t(e.u)] < 0 && mate[size_t(e.v)] < 0) {
+            mate[size_t(e.u)] = e.v;
+            mate[size_t(e.v)] = e.u;
+        }
+    return mate;
+}
+
+// the greedy matching under the usual trial loop; -v: every mate against host_greedy_matching, and the device's own certificate
+int run_matching(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg, const gmsx_csr *csr) {
+    if (args.weighted) gmsx::detail::check(gmsx_graph_set_weights(const_cast<gmsx_graph *>(g.device()), gmsx_csr_weights(csr)), "gmsx_graph_set_weights");
+    const uint32_t flags = args.weighted ? uint32_t(GMSX_MATCH_WEIGHTED) : 0u;
+    double total_seconds = 0, host_seconds = 0;
+    Timer t;
+    std::vector<int32_t> mate, want;
+    gmsx_matching_info info{};
+    for (int64_t it = 0; it < args.trials; ++it) {
+        t.Start();
+        gmsx::greedy_matching(g, mate, flags, nullptr, &info);
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        PrintLabel("Pairs", std::to_string(info.pairs));
+        PrintLabel("Total Weight", std::to_string(info.total_weight));
+        PrintLabel("Free", std::to_string(info.free_vertices));
+        PrintLabel("Rounds", std::to_string(info.rounds));
+        if (args.verify) {
+            if (want.empty() && hg.n > 0) {
+                t.Start();
+                want = host_greedy_matching(hg, args.weighted ? gmsx_csr_weights(csr) : nullptr);
+                t.Stop();
+                host_seconds = t.Seconds();
+            }
+            gmsx_matching_check check{};
+            const bool certified = gmsx::matching_verify(g, mate, flags, &check);
+            PrintTime("Host Greedy", host_seconds);
+            PrintLabel("Verification", mate == want && certified && check.pairs == info.pairs && check.total_weight == info.total_weight ? "PASS" : "FAIL");
+        }
+        std::cout << "@@@ matching " << (args.weighted ? "weighted" : "unweighted") << std::endl;
+    }
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
 // subgraph matching: the reference's VF2 drivers (subgraphiso_vf2_sequential.cpp:33-51) over gmsx::subgraph_isomorphisms
 int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
     gmsx_csr *pc = nullptr;
@@ -1144,7 +1211,7 @@ int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr" && args.kernel != "sssp" && args.kernel != "msf" && args.kernel != "communities") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr" && args.kernel != "sssp" && args.kernel != "msf" && args.kernel != "communities" && args.kernel != "matching") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -1164,7 +1231,7 @@ int main(int argc, char **argv) {
     t.Start();
     int rc;
     const int relabel = args.kernel == "sgi" ? GMSX_RELABEL_NEVER : GMSX_RELABEL_AUTO;  // the reference's subgraph drivers never relabel
-    if (args.kernel == "sssp" || args.kernel == "msf" || (args.kernel == "communities" && args.weighted))  // WeightedBuilder: the weights of the file, or the generator's; never relabelled (sssp.cc:182-183)
+    if (args.kernel == "sssp" || args.kernel == "msf" || args.kernel == "matching" || (args.kernel == "communities" && args.weighted))  // WeightedBuilder: the weights of the file, or the generator's; never relabelled (sssp.cc:182-183)
         rc = !args.file.empty() ? gmsx_csr_load_weighted(args.file.c_str(), 1, GMSX_RELABEL_NEVER, &csr)
                                 : gmsx_csr_generate_weighted(args.gen == "uniform" ? GMSX_GEN_UNIFORM : GMSX_GEN_KRONECKER, args.scale, args.deg,
                                                              GMSX_RELABEL_NEVER, int(args.threads), &csr);
@@ -1222,8 +1289,8 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr" || args.kernel == "sssp" || args.kernel == "msf" || args.kernel == "communities") {
-        const int rc_run = args.kernel == "communities" ? run_communities(args, g, hg, csr) : args.kernel == "msf" ? run_msf(args, g, hg, csr) : args.kernel == "sssp" ? run_sssp(args, g, hg, csr) : args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr" || args.kernel == "sssp" || args.kernel == "msf" || args.kernel == "communities" || args.kernel == "matching") {
+        const int rc_run = args.kernel == "matching" ? run_matching(args, g, hg, csr) : args.kernel == "communities" ? run_communities(args, g, hg, csr) : args.kernel == "msf" ? run_msf(args, g, hg, csr) : args.kernel == "sssp" ? run_sssp(args, g, hg, csr) : args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
                                                                                                                                         : run_components(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);

@@ -1000,6 +1000,8 @@ Option g_options[] = {
     {"MSF_WAVE_ROW", "", false}, {"MSF_WG_ROW", "", false}, {"MSF_PRUNE", "", false},
     // label propagation and modularity (communities.hip)
     {"LP_WAVE_ROW", "", false}, {"LP_LDS_ROW", "", false}, {"LP_LDS_SLOTS", "", false}, {"LP_WG_WORK", "", false}, {"LP_ACTIVE", "", false},
+    // greedy matching (matching.hip)
+    {"MATCH_WAVE_ROW", "", false}, {"MATCH_WG_ROW", "", false}, {"MATCH_KEEP", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

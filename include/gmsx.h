@@ -226,7 +226,12 @@ int gmsx_set_host_threads(int n);
  *                   launch, default 4096; 0 = every class in launches of its own), LP_ACTIVE (1, the default = from the second sweep on only
  *                   the vertices a neighbour of which changed are evaluated; 0 = every vertex in every sweep) — the three row bounds are first
  *                   guesses, not tuned values; LP_WG_WORK and LP_ACTIVE were set from a measurement; test hooks; none changes any output of gmsx_label_propagation or gmsx_modularity except
- *                   gmsx_stats */
+ *                   gmsx_stats
+ *   matching               MATCH_WAVE_ROW / MATCH_WG_ROW (smallest row that gets a wave / a whole workgroup in the search pass of
+ *                   gmsx_greedy_matching, defaults 256 / 4096, as MSF_WAVE_ROW / MSF_WG_ROW), MATCH_KEEP (1, the default = a live vertex whose
+ *                   candidate of the last round is still free keeps it without walking its row; 0 = every live vertex searches its row in
+ *                   every round) — the bin edges are first guesses, not tuned values; test hooks; none changes any output
+ *                   of gmsx_greedy_matching except gmsx_stats (alg_elements, the arcs examined, is smaller or equal under MATCH_KEEP = 1) */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -1008,6 +1013,58 @@ typedef struct {
 } gmsx_modularity_info;
 int gmsx_modularity(const gmsx_graph *g, uint32_t flags, const int32_t *label /* n, host */, gmsx_modularity_info *info /* required */,
                     gmsx_stats *stats);
+
+/* ---- greedy (weighted) matching and its verifier (matching.hip; no reference counterpart, like the k-truss and the spanning forest).
+ * THE ORDER.  An edge is e = {lo, hi}, lo < hi, with weight w: the attached weight (in [1, 2^31 - 1]) with GMSX_MATCH_WEIGHTED in flags, else
+ * w = 1 for every edge, and no weights need be attached.  key(e) = (heavier w first, h(lo, hi) ascending, lo ascending, hi ascending), h a
+ * fixed 32-bit mixer in uint32 arithmetic:
+ *     h = lo * 0x9E3779B1 + hi;  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16;
+ * (h(0,1) = 0x514e28b7, h(0,2) = 0x30f4c306, h(1,2) = 0x7e32275d, h(5,7) = 0xc71f3556).  The CSR has no parallel edges and no self loops,
+ * so the trailing (lo, hi) makes the order strict.  The hash is in the order because plain (lo, hi) ties serialise the rounds below (a path
+ * of unit weights takes n / 2 rounds without it, 3 with it); two arcs of one row can share h — h(0, 50549) =
+ * h(50549, 62096) = 0xe935fad8 —, so the tail does decide.
+ * "THE MATCHING" is the output of the sequential greedy algorithm: take the edges in the order and keep an edge iff both ends are still free.
+ * It is a maximal matching; with weights its total weight is at least half the maximum's.  The device runs the locally dominant rounds
+ * (Preis; Manne, Bisseling), which give the same matching: vertex v is LIVE while it is free and has a free neighbour; in a round every live
+ * v finds cand[v], the other end of the first arc of its row in the order whose other end is free (none: v is dead for good, matched
+ * vertices stay matched), then mate[v] = cand[v] wherever cand[cand[v]] == v; until no vertex is live.  The first live edge in the order is
+ * always mutual, so every round matches at least one edge and rounds <= pairs <= n / 2; the set matched in round r is the set of locally
+ * dominant edges among the live ones, so info->rounds (the rounds that matched an edge) is a fact about (graph, weights, flags) like
+ * everything else.  A path with strictly increasing weights takes one round per pair: that is inherent in the order.
+ * mate[v] = v's partner or -1 (free).  edge_u / edge_v / edge_w (all three or none, room for n / 2 entries each): the pairs with
+ * edge_u[i] < edge_v[i], ascending by u, and their weights (1 when unweighted); the first info->pairs entries are written.
+ * Every output except gmsx_stats is byte-identical in every run and process, under every MATCH_* option, GMSX_UPLOAD_TRUSTED,
+ * GMSX_UPLOAD_HUB_LIMIT, a sharded upload (the call is single-GPU and reads the whole CSR) and re-attached weights.
+ * NULL g or info, unknown flag bits, GMSX_MATCH_WEIGHTED without attached weights, one or two of the three edge arrays: GMSX_ERR_INVALID,
+ * nothing written.  n = 0 or no edge: GMSX_OK, pairs = 0, rounds = 0, every vertex free.  An append past its bound, more than n / 2 + 1
+ * rounds, or a failed check of the result (2 * pairs != matched vertices, a mate whose mate is someone else, a live vertex left):
+ * GMSX_ERR_KERNEL.  The caller's arrays are written only after the flag word was read as zero, through host staging.  The handle is not
+ * modified; the call's device state is O(n) words.  Test hooks: options MATCH_WAVE_ROW, MATCH_WG_ROW (first guesses, not tuned) and
+ * MATCH_KEEP.  gmsx_stats: kernel_ms (the rounds), setup_ms (buffers, the edge list and the info reduction), launches, units = pairs,
+ * probes = rounds, alg_elements = arcs the search pass examined (may differ under the options).
+ * gmsx_matching_verify: the six integers of gmsx_matching_check for any mate array under the same flags.  A vertex is INVALID if its
+ * mate is outside [-1, n), is itself or no neighbour, or if its mate's mate is not the vertex; the other fields treat invalid vertices as
+ * free (pairs, total_weight over the valid pairs; free_vertices = n - 2 * pairs).  THE CERTIFICATE: invalid == 0 && undominated == 0 holds
+ * iff mate is THE greedy matching under the order (induction over the order: an edge greedy keeps has no earlier adjacent matching edge, so
+ * it must be in the matching; an edge greedy rejects has one, so it cannot be) — an O(m) check that needs no second run.  Every augmentable
+ * edge is also undominated.  NULL g or out, NULL mate with n > 0, unknown flag bits, GMSX_MATCH_WEIGHTED without weights: GMSX_ERR_INVALID. */
+enum { GMSX_MATCH_WEIGHTED = 1u };
+typedef struct {
+    int64_t pairs, total_weight;      /* total_weight = pairs when unweighted */
+    int64_t free_vertices, exposed;   /* unmatched; unmatched with degree >= 1 (all their neighbours are matched) */
+    int32_t min_weight, max_weight;   /* over the matched edges; 0 when pairs == 0 */
+    int32_t rounds, reserved;
+} gmsx_matching_info;
+int gmsx_greedy_matching(const gmsx_graph *g, uint32_t flags, int32_t *mate /* n, host, or NULL; -1 = free */,
+                         int32_t *edge_u, int32_t *edge_v, int32_t *edge_w /* room for n / 2 each, all three or none; u < v, ascending by u */,
+                         gmsx_matching_info *info /* required */, gmsx_stats *stats);
+typedef struct {
+    int64_t invalid;       /* vertices whose mate is outside [-1, n), is not a neighbour, or whose mate's mate is not them */
+    int64_t pairs, total_weight, free_vertices;   /* over the valid pairs */
+    int64_t augmentable;   /* edges with both ends free: the matching is maximal iff 0 */
+    int64_t undominated;   /* non-matching edges with no adjacent matching edge EARLIER in the order */
+} gmsx_matching_check;
+int gmsx_matching_verify(const gmsx_graph *g, uint32_t flags, const int32_t *mate /* n, host */, gmsx_matching_check *out, gmsx_stats *stats);
 
 /* ---- 4-cycle counting and the 3- / 4-vertex motif census.  No reference counterpart (like the k-truss: a member of the family the suite
  * describes and does not build).  All results are exact integers.

@@ -48,6 +48,8 @@
 //   gmsx::msf_arc_mask(g, flags)         -> gmsx_min_spanning_forest (a byte per arc of g.neighbors(): 1 on both arcs of every forest edge — what gmsx_connected_components takes)
 //   gmsx::label_propagation(g, label, flags, coloring, max_sweeps, info) -> gmsx_label_propagation (communities by asynchronous label propagation, colour class by colour class; no reference driver)
 //   gmsx::modularity(g, label, flags)    -> gmsx_modularity         (W, I, Σ D_c² in 128 bits, unstable and Q = I / W - S / W² of any labelling)
+//   gmsx::greedy_matching(g, mate, flags, edges, info) -> gmsx_greedy_matching (the greedy matching under a strict edge order; GMSX_MATCH_WEIGHTED: heavier first; no reference driver)
+//   gmsx::matching_verify(g, mate, flags, out) -> gmsx_matching_verify (true iff mate is that matching: an O(m) certificate)
 //   gmsx::pick_sources(csr, count)       -> gmsx_csr_pick_sources   (gapbs/benchmark.h:51-75, SourcePicker)
 //   gmsx::cycle4_count(g) / cycle4_count(g, at_vertex) -> gmsx_cycle4_count (the 4-cycles, and those through every vertex; no reference driver)
 //   gmsx::motif_census4(g)               -> gmsx_motif_census4     (the eight 3- and 4-vertex motifs, non-induced and induced; no reference driver)
@@ -860,6 +862,37 @@ inline gmsx_modularity_info modularity(const HipGraphT<S> &g, const std::vector<
     gmsx_modularity_info mi{};
     detail::check(gmsx_modularity(g.device(), flags, label.empty() ? nullptr : label.data(), &mi, nullptr), "gmsx_modularity");
     return mi;
+}
+// The greedy matching of g under the strict order of gmsx.h (heavier weight first with flags = GMSX_MATCH_WEIGHTED and the weights attached
+// with gmsx::set_weights, else unit weights; ties by the hash of the ends, then by the ids), so the matching is unique: mate[v] = v's partner
+// or -1; `edges` (optional) receives the pairs (u, v, w), u < v, ascending by u.  No reference counterpart.  Returns the number of pairs;
+// `info` (optional) receives total_weight, free_vertices, exposed, rounds …
+template <class S>
+inline int64_t greedy_matching(const HipGraphT<S> &g, std::vector<int32_t> &mate, uint32_t flags = 0, std::vector<WeightedEdge> *edges = nullptr,
+                               gmsx_matching_info *info = nullptr) {
+    mate.resize(size_t(g.num_nodes()));
+    const size_t room = edges ? size_t(std::max<int64_t>(g.num_nodes() / 2, 1)) : 0;
+    std::vector<int32_t> u(room), v(room), w(room);
+    gmsx_matching_info mi{};
+    detail::check(gmsx_greedy_matching(g.device(), flags, mate.empty() ? nullptr : mate.data(), edges ? u.data() : nullptr, edges ? v.data() : nullptr,
+                                       edges ? w.data() : nullptr, &mi, nullptr),
+                  "gmsx_greedy_matching");
+    if (edges) {
+        edges->resize(size_t(mi.pairs));
+        for (size_t i = 0; i < edges->size(); ++i) (*edges)[i] = WeightedEdge{u[i], v[i], w[i]};
+    }
+    if (info) *info = mi;
+    return mi.pairs;
+}
+// gmsx_matching_verify of any mate array (-1 = free) under the same flags: true iff it is THE greedy matching (invalid == 0 and
+// undominated == 0, gmsx.h); `out` (optional) receives the six integers — augmentable == 0 iff the matching is maximal.
+template <class S>
+inline bool matching_verify(const HipGraphT<S> &g, const std::vector<int32_t> &mate, uint32_t flags = 0, gmsx_matching_check *out = nullptr) {
+    if (mate.size() != size_t(g.num_nodes())) detail::check(GMSX_ERR_INVALID, "gmsx_matching_verify");
+    gmsx_matching_check mc{};
+    detail::check(gmsx_matching_verify(g.device(), flags, mate.empty() ? nullptr : mate.data(), &mc, nullptr), "gmsx_matching_verify");
+    if (out) *out = mc;
+    return mc.invalid == 0 && mc.undominated == 0;
 }
 // PrintTopScores' top k (pr.cc:64-74, gapbs/util.h TopK) on the host: the k largest scores as (id, score), largest first, ties by the smaller id
 inline std::vector<std::pair<int32_t, double>> top_scores(const std::vector<double> &scores, size_t k) {
