@@ -52,6 +52,7 @@ SYMBOLS = [
     "gmsx_min_spanning_forest",
     "gmsx_label_propagation", "gmsx_modularity",
     "gmsx_greedy_matching", "gmsx_matching_verify",
+    "gmsx_biconnected_components",
     "gmsx_cycle4_count", "gmsx_cycle4_partial", "gmsx_motif_census4",
     "gmsx_comm_unique_id", "gmsx_comm_init", "gmsx_comm_allreduce_u64", "gmsx_comm_rank", "gmsx_comm_size", "gmsx_comm_finalize",
 ]
@@ -265,6 +266,15 @@ class MatchingCheck(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class BiccInfo(C.Structure):
+    _fields_ = [("blocks", C.c_int64), ("bridges", C.c_int64), ("articulation_points", C.c_int64), ("largest_block_edges", C.c_int64),
+                ("largest_block_vertices", C.c_int64), ("components", C.c_int64), ("isolated", C.c_int64), ("largest_block", C.c_int32),
+                ("max_blocks_at", C.c_int32), ("levels", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
 class MotifInfo(C.Structure):
     _fields_ = [("subgraphs", C.c_uint64 * 8), ("induced", C.c_uint64 * 8), ("wedges_walked", C.c_uint64), ("max_codegree", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -466,6 +476,7 @@ def lib():
     L.gmsx_modularity.argtypes = [vp, C.c_uint32, C.c_void_p, C.POINTER(ModularityInfo), sp]
     L.gmsx_greedy_matching.argtypes = [vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MatchingInfo), sp]
     L.gmsx_matching_verify.argtypes = [vp, C.c_uint32, C.c_void_p, C.POINTER(MatchingCheck), sp]
+    L.gmsx_biconnected_components.argtypes = [vp, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BiccInfo), sp]
     L.gmsx_cycle4_count.argtypes = [vp, u64p, C.c_void_p, sp]
     L.gmsx_cycle4_partial.argtypes = [vp, C.c_int, C.c_int, u64p, sp]
     L.gmsx_motif_census4.argtypes = [vp, C.POINTER(MotifInfo), sp]
@@ -1334,6 +1345,22 @@ class DeviceGraph:
         _check(lib().gmsx_matching_verify(self._h, MATCH_WEIGHTED if weighted else 0, (m if m.size else np.zeros(1, np.int32)).ctypes.data_as(C.c_void_p),
                                           C.byref(out), C.byref(st)), "gmsx_matching_verify")
         return (out.as_dict(), st.as_dict()) if stats else out.as_dict()
+
+    def biconnected_components(self, want_block=True, want_blocks_at=True, want_mask=False, stats=False):
+        """gmsx_biconnected_components: (block, blocks_at, arc_keep, info[, stats]).  block: int32[nnz], the id of the block of every arc of the
+        uploaded CSR (ids ascend with each block's smallest `u < v` arc); blocks_at: int32[n], the blocks that contain a vertex (>= 2: an
+        articulation point); arc_keep: uint8[nnz], 0 on both arcs of a bridge, else 1 (want_mask=True); an output that was not asked for is
+        None.  info: {blocks, bridges, articulation_points, largest_block_edges, largest_block_vertices, components, isolated,
+        largest_block, max_blocks_at, levels}.  Facts about the graph: the same bytes in every run."""
+        n, nnz = self.num_nodes, 2 * self.num_edges
+        block = np.zeros(max(nnz, 1), dtype=np.int32) if want_block else None
+        at = np.zeros(max(n, 1), dtype=np.int32) if want_blocks_at else None
+        mask = np.zeros(max(nnz, 1), dtype=np.uint8) if want_mask else None
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
+        info, st = BiccInfo(), Stats()
+        _check(lib().gmsx_biconnected_components(self._h, 0, p(block), p(at), p(mask), C.byref(info), C.byref(st)), "gmsx_biconnected_components")
+        r = (block[:nnz] if want_block else None, at[:n] if want_blocks_at else None, mask[:nnz] if want_mask else None, info.as_dict())
+        return (r + (st.as_dict(),)) if stats else r
 
     def cycle4_count(self, at_vertex=False, stats=False):
         """gmsx_cycle4_count: the 4-cycles of the graph; with at_vertex=True (cycles, int64[n] — the 4-cycles through every vertex of the

@@ -208,6 +208,7 @@ Args parse(int argc, char **argv) {
     if (!a.error && ((a.kernel == "msf" && (a.gpus > 1 || a.metric_given)) || (a.maximum && a.kernel != "msf"))) a.error = 100;  // a forest is global
     if (!a.error && ((a.kernel == "communities" && (a.gpus > 1 || a.metric_given)) || (a.weighted && a.kernel != "communities" && a.kernel != "matching"))) a.error = 100;  // communities are global
     if (!a.error && a.kernel == "matching" && (a.gpus > 1 || a.metric_given)) a.error = 100;  // … and so is a matching
+    if (!a.error && a.kernel == "bicc" && (a.gpus > 1 || a.metric_given)) a.error = 100;  // … and so are the blocks
     if (!a.error && a.kernel == "communities" && a.iters > INT32_MAX) a.error = 100;
     if (!a.error && ((a.start >= 0 && !traversal) || (a.iters != 1 && a.kernel != "bc" && a.kernel != "closeness" && a.kernel != "pr" && a.kernel != "communities"))) a.error = 100;
     if (!a.error && ((a.kernel == "sgi") != !a.pattern_file.empty() || (a.mono && a.kernel != "sgi"))) a.error = 100;  // util/command_line.hpp:22: the pattern is required
@@ -222,7 +223,7 @@ Args parse(int argc, char **argv) {
 }
 
 void usage(const char *argv0) {
-    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf|communities|matching> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
+    std::printf("usage: %s <tc|vertex|kclique|kcstar|bk|lp|color|truss|sgi|cc|jp|motifs|bfs|bc|closeness|pr|sssp|msf|communities|matching|bicc> (-g kronecker|uniform <scale> [--deg d] | -f file.{el,sg}) [-v] [-n trials] [-t threads] "
                 "[-p clique-size=k] [--gpus N] [--opt NAME=VALUE ...] [bk, kcstar: --list FILE] [bk: --order adg|deg|dgr] "
                 "[lp: --metric jaccard|overlap|adamic_adar|resource|common|total|prefatt -q N --list FILE] [color: --order id|ff|lf|sl|adg --eps e] [sgi: -p pattern-file=FILE --mono --list FILE] "
                 "[jp: --metric NAME --threshold X] [bfs, bc, closeness, sssp: -r SOURCE] [bc: -i ITERS] [closeness: -i SOURCES] [pr: -i ITERS -t TOL] [sssp: -d DELTA] [msf: --max] [communities: -i MAX_SWEEPS --weighted] [matching: --weighted]\n", argv0);
@@ -674,6 +675,124 @@ int run_components(const Args &args, const gmsx::HipSetGraph &g, const HostGraph
         std::cout << std::endl << k << " biggest clusters" << std::endl;
         for (size_t i = 0; i < k; ++i) std::cout << top[i].second << ":" << -top[i].first << std::endl;
         std::cout << "There are " << top.size() << " components" << std::endl;
+    }
+    PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
+    return 0;
+}
+
+// Hopcroft–Tarjan on the host, iterative (a depth-first search with an edge stack), its blocks renumbered by their smallest `u < v` arc in CSR
+// order: block per arc, blocks_at per vertex, arc_keep per arc as include/gmsx.h defines them.  The driver's own loop, independent of the device.
+void host_bicc(const HostGraph &hg, std::vector<int32_t> &block, std::vector<int32_t> &blocks_at, std::vector<uint8_t> &keep) {
+    const int64_t n = hg.n, nnz = hg.off[n];
+    auto arc_of = [&](int32_t u, int32_t v) { return int64_t(std::lower_bound(hg.row(u), hg.row(u) + hg.deg(u), v) - hg.adj); };
+    std::vector<int32_t> disc(size_t(n), -1), low(size_t(n), 0), parent(size_t(n), -1);
+    std::vector<int64_t> next(size_t(n), 0), raw(size_t(nnz), -1), edges;  // the edge stack holds arc indices
+    std::vector<int32_t> stack;
+    int32_t clock = 0;
+    int64_t nraw = 0;
+    for (int32_t root = 0; root < n; ++root) {
+        if (disc[size_t(root)] >= 0) continue;
+        disc[size_t(root)] = low[size_t(root)] = clock++;
+        next[size_t(root)] = hg.off[root];
+        stack.assign(1, root);
+        while (!stack.empty()) {
+            const int32_t v = stack.back();
+            if (next[size_t(v)] < hg.off[v + 1]) {
+                const int64_t j = next[size_t(v)]++;
+                const int32_t w = hg.adj[j];
+                if (w == parent[size_t(v)]) continue;
+                if (disc[size_t(w)] < 0) {
+                    edges.push_back(j);
+                    parent[size_t(w)] = v;
+                    disc[size_t(w)] = low[size_t(w)] = clock++;
+                    next[size_t(w)] = hg.off[w];
+                    stack.push_back(w);
+                } else if (disc[size_t(w)] < disc[size_t(v)]) {  // a back edge to an ancestor, met from its lower end only
+                    edges.push_back(j);
+                    low[size_t(v)] = std::min(low[size_t(v)], disc[size_t(w)]);
+                }
+            } else {
+                stack.pop_back();
+                const int32_t p = parent[size_t(v)];
+                if (p < 0) continue;
+                low[size_t(p)] = std::min(low[size_t(p)], low[size_t(v)]);
+                if (low[size_t(v)] >= disc[size_t(p)]) {  // p separates v's subtree: the arcs above p -> v on the stack are one block
+                    const int64_t tree = arc_of(p, v);
+                    for (;;) {
+                        const int64_t j = edges.back();
+                        edges.pop_back();
+                        raw[size_t(j)] = nraw;
+                        if (j == tree) break;
+                    }
+                    ++nraw;
+                }
+            }
+        }
+    }
+    // the twin of a stacked arc gets its number; then ids by the first `u < v` arc
+    std::vector<int32_t> id(size_t(nraw), -1);
+    std::vector<int64_t> edges_of(size_t(nraw), 0);
+    block.assign(size_t(nnz), -1);
+    blocks_at.assign(size_t(n), 0);
+    keep.assign(size_t(nnz), 0);
+    int32_t ids = 0;
+    for (int32_t u = 0; u < n; ++u)
+        for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j) {
+            if (raw[size_t(j)] < 0) raw[size_t(j)] = raw[size_t(arc_of(hg.adj[j], u))];
+            if (hg.adj[j] > u) {
+                if (id[size_t(raw[size_t(j)])] < 0) id[size_t(raw[size_t(j)])] = ids++;
+                ++edges_of[size_t(raw[size_t(j)])];
+            }
+        }
+    std::vector<int32_t> mine;
+    for (int32_t u = 0; u < n; ++u) {
+        mine.clear();
+        for (int64_t j = hg.off[u]; j < hg.off[u + 1]; ++j) {
+            block[size_t(j)] = id[size_t(raw[size_t(j)])];
+            keep[size_t(j)] = edges_of[size_t(raw[size_t(j)])] > 1 ? 1 : 0;
+            mine.push_back(block[size_t(j)]);
+        }
+        std::sort(mine.begin(), mine.end());
+        blocks_at[size_t(u)] = int32_t(std::unique(mine.begin(), mine.end()) - mine.begin());
+    }
+}
+
+// biconnected components (bicc) under the usual trial loop; -v holds every array to host_bicc
+int run_bicc(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
+    const int64_t nnz = hg.n > 0 ? hg.off[hg.n] : 0;
+    double total_seconds = 0;
+    Timer t;
+    std::vector<int32_t> block(size_t(nnz) + 1), blocks_at(size_t(hg.n) + 1);
+    std::vector<uint8_t> keep(size_t(nnz) + 1);
+    gmsx_bicc_info info{};
+    for (int64_t it = 0; it < args.trials; ++it) {
+        t.Start();
+        gmsx::detail::check(gmsx_biconnected_components(g.device(), 0, block.data(), blocks_at.data(), keep.data(), &info, nullptr), "gmsx_biconnected_components");
+        t.Stop();
+        PrintTime("Trial Time", t.Seconds());
+        total_seconds += t.Seconds();
+        PrintLabel("Blocks", std::to_string(info.blocks));
+        PrintLabel("Bridges", std::to_string(info.bridges));
+        PrintLabel("Articulation Points", std::to_string(info.articulation_points));
+        PrintLabel("Largest Block", std::to_string(info.largest_block_edges) + " edges " + std::to_string(info.largest_block_vertices) + " vertices");
+        PrintLabel("Components", std::to_string(info.components));
+        PrintLabel("Levels", std::to_string(info.levels));
+        if (args.verify) {
+            std::vector<int32_t> hb, ha;
+            std::vector<uint8_t> hk;
+            host_bicc(hg, hb, ha, hk);
+            int64_t cut = 0, bridges2 = 0, most = -1;
+            for (int64_t v = 0; v < hg.n; ++v) cut += ha[size_t(v)] >= 2;
+            for (int64_t j = 0; j < nnz; ++j) {
+                bridges2 += hk[size_t(j)] == 0;
+                most = std::max<int64_t>(most, hb[size_t(j)]);
+            }
+            const bool ok = std::equal(hb.begin(), hb.end(), block.begin()) && std::equal(ha.begin(), ha.end(), blocks_at.begin()) &&
+                            std::equal(hk.begin(), hk.end(), keep.begin()) && cut == info.articulation_points && bridges2 == 2 * info.bridges &&
+                            most + 1 == info.blocks;
+            PrintLabel("Verification", ok ? "PASS" : "FAIL");
+        }
+        std::cout << "@@@ biconnected components" << std::endl;
     }
     PrintTime("Average Time", total_seconds / double(args.trials > 0 ? args.trials : 1));
     return 0;
@@ -1211,7 +1330,7 @@ int run_sgi(const Args &args, const gmsx::HipSetGraph &g, const HostGraph &hg) {
 int main(int argc, char **argv) {
     Args args = parse(argc, argv);
     if (args.error) { usage(argv[0]); return args.error; }  // the reference exits with 100 / 101 (cli/cli.h:122-133,159-160)
-    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr" && args.kernel != "sssp" && args.kernel != "msf" && args.kernel != "communities" && args.kernel != "matching") { usage(argv[0]); return 100; }
+    if (args.kernel != "tc" && args.kernel != "vertex" && args.kernel != "kclique" && args.kernel != "kcstar" && args.kernel != "bk" && args.kernel != "lp" && args.kernel != "color" && args.kernel != "truss" && args.kernel != "sgi" && args.kernel != "cc" && args.kernel != "jp" && args.kernel != "motifs" && args.kernel != "bfs" && args.kernel != "bc" && args.kernel != "closeness" && args.kernel != "pr" && args.kernel != "sssp" && args.kernel != "msf" && args.kernel != "communities" && args.kernel != "matching" && args.kernel != "bicc") { usage(argv[0]); return 100; }
     if (args.gpus >= 1 && !std::getenv("GMSX_DRIVER_RANK")) {
         const int rc_launch = launch_ranks(args.gpus);
         if (rc_launch >= 0) return rc_launch;  // the supervisor; a child (-1) falls through as its rank
@@ -1230,7 +1349,7 @@ int main(int argc, char **argv) {
     gmsx_csr *csr = nullptr;
     t.Start();
     int rc;
-    const int relabel = args.kernel == "sgi" ? GMSX_RELABEL_NEVER : GMSX_RELABEL_AUTO;  // the reference's subgraph drivers never relabel
+    const int relabel = (args.kernel == "sgi" || args.kernel == "bicc") ? GMSX_RELABEL_NEVER : GMSX_RELABEL_AUTO;  // the reference's subgraph drivers never relabel; block ids are those of the graph as loaded
     if (args.kernel == "sssp" || args.kernel == "msf" || args.kernel == "matching" || (args.kernel == "communities" && args.weighted))  // WeightedBuilder: the weights of the file, or the generator's; never relabelled (sssp.cc:182-183)
         rc = !args.file.empty() ? gmsx_csr_load_weighted(args.file.c_str(), 1, GMSX_RELABEL_NEVER, &csr)
                                 : gmsx_csr_generate_weighted(args.gen == "uniform" ? GMSX_GEN_UNIFORM : GMSX_GEN_KRONECKER, args.scale, args.deg,
@@ -1289,8 +1408,8 @@ int main(int argc, char **argv) {
     t.Stop();
     PrintTime("GraphExec buildTime", t.Seconds());
     const HostGraph hg{n, gmsx_csr_offsets(csr), gmsx_csr_neighbors(csr)};
-    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr" || args.kernel == "sssp" || args.kernel == "msf" || args.kernel == "communities" || args.kernel == "matching") {
-        const int rc_run = args.kernel == "matching" ? run_matching(args, g, hg, csr) : args.kernel == "communities" ? run_communities(args, g, hg, csr) : args.kernel == "msf" ? run_msf(args, g, hg, csr) : args.kernel == "sssp" ? run_sssp(args, g, hg, csr) : args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
+    if (args.kernel == "color" || args.kernel == "truss" || args.kernel == "sgi" || args.kernel == "cc" || args.kernel == "jp" || args.kernel == "motifs" || args.kernel == "bfs" || args.kernel == "bc" || args.kernel == "closeness" || args.kernel == "pr" || args.kernel == "sssp" || args.kernel == "msf" || args.kernel == "communities" || args.kernel == "matching" || args.kernel == "bicc") {
+        const int rc_run = args.kernel == "bicc" ? run_bicc(args, g, hg) : args.kernel == "matching" ? run_matching(args, g, hg, csr) : args.kernel == "communities" ? run_communities(args, g, hg, csr) : args.kernel == "msf" ? run_msf(args, g, hg, csr) : args.kernel == "sssp" ? run_sssp(args, g, hg, csr) : args.kernel == "pr" ? run_pagerank(args, g, hg) : args.kernel == "closeness" ? run_closeness(args, g, hg, csr) : (args.kernel == "bfs" || args.kernel == "bc") ? run_traversal(args, g, hg, csr) : args.kernel == "motifs" ? run_motifs(args, g, hg) : args.kernel == "color" ? run_color(args, g) : args.kernel == "truss" ? run_truss(args, g) : args.kernel == "sgi" ? run_sgi(args, g, hg)
                                                                                                                                         : run_components(args, g, hg);
         if (comm) gmsx_comm_finalize(comm);
         gmsx_csr_free(csr);

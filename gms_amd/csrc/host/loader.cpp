@@ -1002,6 +1002,8 @@ Option g_options[] = {
     {"LP_WAVE_ROW", "", false}, {"LP_LDS_ROW", "", false}, {"LP_LDS_SLOTS", "", false}, {"LP_WG_WORK", "", false}, {"LP_ACTIVE", "", false},
     // greedy matching (matching.hip)
     {"MATCH_WAVE_ROW", "", false}, {"MATCH_WG_ROW", "", false}, {"MATCH_KEEP", "", false},
+    // biconnected components (bicc.hip)
+    {"BCC_WAVE_ROW", "", false}, {"BCC_WG_ROW", "", false}, {"BCC_WG_FRONTIER", "", false}, {"BCC_WG_LEVEL", "", false},
 };
 Option *find_option(const char *name) {
     if (!name) return nullptr;

@@ -231,7 +231,13 @@ int gmsx_set_host_threads(int n);
  *                   gmsx_greedy_matching, defaults 256 / 4096, as MSF_WAVE_ROW / MSF_WG_ROW), MATCH_KEEP (1, the default = a live vertex whose
  *                   candidate of the last round is still free keeps it without walking its row; 0 = every live vertex searches its row in
  *                   every round) — the bin edges are first guesses, not tuned values; test hooks; none changes any output
- *                   of gmsx_greedy_matching except gmsx_stats (alg_elements, the arcs examined, is smaller or equal under MATCH_KEEP = 1) */
+ *                   of gmsx_greedy_matching except gmsx_stats (alg_elements, the arcs examined, is smaller or equal under MATCH_KEEP = 1)
+ *   biconnectivity         BCC_WAVE_ROW / BCC_WG_ROW (smallest row that gets a wave / a whole workgroup in the row passes of
+ *                   gmsx_biconnected_components, defaults 256 / 4096, as CC_WAVE_ROW / CC_WG_ROW), BCC_WG_FRONTIER (largest frontier of the
+ *                   BFS forest that one workgroup takes round after round, default 512, as BFS_WG_FRONTIER; 0 = every round a kernel
+ *                   boundary), BCC_WG_LEVEL (consecutive levels of the forest that each hold at most this many vertices are swept by one
+ *                   workgroup in one launch, default 1024; 0 = every level a launch of its own) — all four are first guesses, not tuned
+ *                   values; test hooks; none changes any output of gmsx_biconnected_components except gmsx_stats */
 int gmsx_set_option(const char *name, const char *value);
 void gmsx_reset_options(void);                          /* every option back to its default */
 int gmsx_option_name(int index, const char **name);     /* enumerates the names: GMSX_ERR_INVALID past the last */
@@ -1065,6 +1071,49 @@ typedef struct {
     int64_t undominated;   /* non-matching edges with no adjacent matching edge EARLIER in the order */
 } gmsx_matching_check;
 int gmsx_matching_verify(const gmsx_graph *g, uint32_t flags, const int32_t *mate /* n, host */, gmsx_matching_check *out, gmsx_stats *stats);
+
+/* ---- biconnected components, articulation points and bridges (bicc.hip; no reference counterpart, like the k-truss and the spanning
+ * forest).
+ * BLOCKS.  A block (biconnected component) is a maximal set of edges in which any two edges lie on a common simple cycle; a BRIDGE is a
+ * block of one edge.  Every edge lies in exactly one block.  BLOCK IDS are dense, 0 … blocks - 1, and ascend with each block's smallest edge
+ * under the order (min end, max end) — the CSR order of the `u < v` arcs; they fit 32 bits because blocks <= n - components.
+ * block[j] = the id of the block of edge {u, neigh[j]}, parallel to the uploaded neigh: both arcs of an edge carry the same id.
+ * blocks_at[v] = the number of blocks that contain v, 0 for an isolated vertex; v is an ARTICULATION POINT (cut vertex) iff blocks_at[v] >= 2.
+ * arc_keep[j] = 0 for a bridge, else 1: symmetric, the shape gmsx_jarvis_patrick and gmsx_min_spanning_forest produce; fed to
+ * gmsx_connected_components it gives the 2-edge-connected components.
+ * levels = the non-empty levels of the BFS forest rooted at every component's smallest id: the roots are fixed and BFS depth is unique, so
+ * it is a fact about the graph.
+ * ALWAYS: Σ blocks_at = n - components + blocks; the components over arc_keep = components + bridges; Σ over the blocks of their edges =
+ * nnz / 2.
+ * The device runs Tarjan–Vishkin on a BFS forest (integers only): component roots by the union-find, a forest by claims, subtree sizes,
+ * preorder numbers, low and high by three sweeps over the levels, a second union-find over the tree edges, then ids by the rank of each
+ * set's first arc.  The forest depends on the arrival of the claims; the partition of the edges it yields does not.
+ * Every output except the times of gmsx_stats is byte-identical in every run and process, under every BCC_* option, GMSX_UPLOAD_TRUSTED,
+ * GMSX_UPLOAD_HUB_LIMIT, a sharded upload (the call is single-GPU and reads the whole CSR) and a second handle.
+ * NULL g or info, unknown flag bits (flags must be 0): GMSX_ERR_INVALID, nothing written.  n = 0 or no edge: GMSX_OK, zeros, components =
+ * isolated = n.  A capped walk exceeded (n + 64, union_find.hpp), an append past its bound, arcs without their twins (as many `u > v` as
+ * `u < v` arcs are required; possible only under GMSX_UPLOAD_TRUSTED), or a failed self-check (order short of n vertices, Σ subtree sizes of
+ * the roots != n, Σ edges of the sets != nnz / 2, the first identity on the device's own numbers): GMSX_ERR_KERNEL.  The caller's arrays
+ * are written only after the flag word was read as zero, through host staging.  The handle is not modified; the call's device state is O(n)
+ * words, plus 4 bytes per arc for block and 1 byte per arc for arc_keep only when the caller asks for them.  Test hooks: options
+ * BCC_WAVE_ROW, BCC_WG_ROW, BCC_WG_FRONTIER, BCC_WG_LEVEL (first guesses, not tuned).  gmsx_stats: kernel_ms (the kernels), setup_ms (buffers
+ * and the copies back), launches, units = blocks, probes = levels, alg_elements = arcs the arc passes examined. */
+typedef struct {
+    int64_t blocks;                 /* biconnected components (bridges are blocks of one edge); 0 without edges */
+    int64_t bridges;                /* blocks of exactly one edge */
+    int64_t articulation_points;    /* vertices with blocks_at >= 2 */
+    int64_t largest_block_edges;    /* edges of the largest block (by edges) */
+    int64_t largest_block_vertices; /* its vertices */
+    int64_t components;             /* connected components, isolated vertices included */
+    int64_t isolated;
+    int32_t largest_block;          /* its id; ties: the smallest id */
+    int32_t max_blocks_at;          /* largest blocks_at[v] */
+    int32_t levels;                 /* non-empty levels of the BFS forest rooted at every component's smallest id */
+    int32_t reserved;
+} gmsx_bicc_info;
+int gmsx_biconnected_components(const gmsx_graph *g, uint32_t flags /* 0 */, int32_t *block /* nnz, host, or NULL */,
+                                int32_t *blocks_at /* n, host, or NULL */, uint8_t *arc_keep /* nnz, host, or NULL */,
+                                gmsx_bicc_info *info /* required */, gmsx_stats *stats);
 
 /* ---- 4-cycle counting and the 3- / 4-vertex motif census.  No reference counterpart (like the k-truss: a member of the family the suite
  * describes and does not build).  All results are exact integers.

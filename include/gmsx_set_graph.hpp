@@ -50,6 +50,9 @@
 //   gmsx::modularity(g, label, flags)    -> gmsx_modularity         (W, I, Σ D_c² in 128 bits, unstable and Q = I / W - S / W² of any labelling)
 //   gmsx::greedy_matching(g, mate, flags, edges, info) -> gmsx_greedy_matching (the greedy matching under a strict edge order; GMSX_MATCH_WEIGHTED: heavier first; no reference driver)
 //   gmsx::matching_verify(g, mate, flags, out) -> gmsx_matching_verify (true iff mate is that matching: an O(m) certificate)
+//   gmsx::biconnected_components(g, block, blocks_at, info) -> gmsx_biconnected_components (the block id of every arc of g.neighbors(), the blocks at every vertex; no reference driver)
+//   gmsx::articulation_points(g)         -> gmsx_biconnected_components (the cut vertices, ascending)
+//   gmsx::bridges(g)                     -> gmsx_biconnected_components (the bridges as (u, v), u < v, ascending)
 //   gmsx::pick_sources(csr, count)       -> gmsx_csr_pick_sources   (gapbs/benchmark.h:51-75, SourcePicker)
 //   gmsx::cycle4_count(g) / cycle4_count(g, at_vertex) -> gmsx_cycle4_count (the 4-cycles, and those through every vertex; no reference driver)
 //   gmsx::motif_census4(g)               -> gmsx_motif_census4     (the eight 3- and 4-vertex motifs, non-induced and induced; no reference driver)
@@ -893,6 +896,48 @@ inline bool matching_verify(const HipGraphT<S> &g, const std::vector<int32_t> &m
     detail::check(gmsx_matching_verify(g.device(), flags, mate.empty() ? nullptr : mate.data(), &mc, nullptr), "gmsx_matching_verify");
     if (out) *out = mc;
     return mc.invalid == 0 && mc.undominated == 0;
+}
+// The biconnected components (blocks) of g (gmsx.h): block[j] = the id of the block of the arc j of g.neighbors() — ids ascend with each block's
+// smallest `u < v` arc, both arcs of an edge carry the same id —, blocks_at[v] = the blocks that contain v.  No reference counterpart.  Returns
+// the number of blocks; `info` (optional) receives bridges, articulation_points, the largest block, components, levels …
+template <class S>
+inline int64_t biconnected_components(const HipGraphT<S> &g, std::vector<int32_t> &block, std::vector<int32_t> &blocks_at, gmsx_bicc_info *info = nullptr) {
+    const int64_t nnz = g.num_nodes() > 0 ? g.offsets()[g.num_nodes()] : 0;
+    block.resize(size_t(nnz));
+    blocks_at.resize(size_t(g.num_nodes()));
+    gmsx_bicc_info bi{};
+    detail::check(gmsx_biconnected_components(g.device(), 0, block.empty() ? nullptr : block.data(), blocks_at.empty() ? nullptr : blocks_at.data(), nullptr,
+                                              &bi, nullptr),
+                  "gmsx_biconnected_components");
+    if (info) *info = bi;
+    return bi.blocks;
+}
+// The articulation points (cut vertices) of g, ascending: the vertices that lie in two blocks or more.
+template <class S>
+inline std::vector<int32_t> articulation_points(const HipGraphT<S> &g, gmsx_bicc_info *info = nullptr) {
+    std::vector<int32_t> at(size_t(g.num_nodes())), cut;
+    gmsx_bicc_info bi{};
+    detail::check(gmsx_biconnected_components(g.device(), 0, nullptr, at.empty() ? nullptr : at.data(), nullptr, &bi, nullptr), "gmsx_biconnected_components");
+    cut.reserve(size_t(bi.articulation_points));
+    for (size_t v = 0; v < at.size(); ++v)
+        if (at[v] >= 2) cut.push_back(int32_t(v));
+    if (info) *info = bi;
+    return cut;
+}
+// The bridges of g as (u, v) with u < v, ascending: the edges whose removal disconnects their component (the arcs with arc_keep == 0).
+template <class S>
+inline std::vector<std::pair<int32_t, int32_t>> bridges(const HipGraphT<S> &g, gmsx_bicc_info *info = nullptr) {
+    const int64_t n = g.num_nodes(), nnz = n > 0 ? g.offsets()[n] : 0;
+    std::vector<uint8_t> keep(size_t(nnz) + 1);
+    gmsx_bicc_info bi{};
+    detail::check(gmsx_biconnected_components(g.device(), 0, nullptr, nullptr, keep.data(), &bi, nullptr), "gmsx_biconnected_components");
+    std::vector<std::pair<int32_t, int32_t>> out;
+    out.reserve(size_t(bi.bridges));
+    for (int64_t u = 0; u < n; ++u)
+        for (int64_t j = g.offsets()[u]; j < g.offsets()[u + 1]; ++j)
+            if (!keep[size_t(j)] && int64_t(g.neighbors()[j]) > u) out.emplace_back(int32_t(u), g.neighbors()[j]);
+    if (info) *info = bi;
+    return out;
 }
 // PrintTopScores' top k (pr.cc:64-74, gapbs/util.h TopK) on the host: the k largest scores as (id, score), largest first, ties by the smaller id
 inline std::vector<std::pair<int32_t, double>> top_scores(const std::vector<double> &scores, size_t k) {
