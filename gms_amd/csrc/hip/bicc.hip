@@ -34,8 +34,8 @@
 //               the smallest such child; blocks_at[v] = [v has a parent] + the sets whose top's parent is v.
 //   9 info      one reduction over the vertices, then the largest block's id and vertices among the sets with the most edges.
 //  10 outputs   only when asked for: OpOut writes block[j] and arc_keep[j] for every arc (4 + 1 bytes per arc, device memory of the call).
-// THE ROW PASSES (k_bicc_rows<Op, WIDTH>) bin rows as k_cc_link does: one lane per row below kBiccShortRow entries, a 16-lane group below
-// BCC_WAVE_ROW, a wave below BCC_WG_ROW, a whole workgroup from there on; the three upper bins are vertex lists a classify kernel fills once.
+// THE ROW PASSES are row_classes.hpp's (a lane, a 16-lane group, a wave or a workgroup per row by its length; the bounds are BCC_WAVE_ROW and
+// BCC_WG_ROW); the five Ops below say what an arc means in each.
 // THE SWEEPS BY LEVEL (steps 3, 4, 5; k_bicc_sweep<Op>) do not cost a launch per level on a deep forest: consecutive levels that each hold at
 // most BCC_WG_LEVEL vertices are swept by ONE workgroup in one launch with a __syncthreads() between levels; what one level writes and the next
 // reads goes through atomics, store_now and load_now (frontier_rounds.hpp; the note at the top of union_find.hpp).  A larger level is a grid-wide
@@ -46,7 +46,8 @@
 // frontiers: DevBufs of the call; the handle is not touched.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
-#include "frontier_rounds.hpp"  // the engine, load_now, store_now, wave_append, RowGroup, kGroup, kLongRow
+#include "frontier_rounds.hpp"  // the engine, load_now, store_now, RowGroup, kGroup, kLongRow
+#include "row_classes.hpp"
 #include "union_find.hpp"
 #include "wave_ops.hpp"
 
@@ -61,13 +62,8 @@ namespace gmsx {
 
 namespace {
 
-constexpr int kBiccShortRow = 16;     // rows below this: one lane
 constexpr int kBiccSweepThreads = 1024;
-constexpr long long kBiccWaveRowDefault = 256, kBiccWgRowDefault = 4096, kBiccWgLevelDefault = 1024;  // first guesses (gmsx.h, OPTIONS)
-
-__device__ __forceinline__ unsigned long long load_now(const unsigned long long *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+constexpr long long kBiccWgLevelDefault = 1024;  // a first guess (gmsx.h, OPTIONS)
 
 // control block of the forest's rounds: the engine's, plus the level order's words
 struct BiccCtrl : FrontierCtrl {
@@ -79,20 +75,15 @@ struct BiccCtrl : FrontierCtrl {
 struct BiccAcc {
     int32_t error;     // the flag word: a cap was exceeded, an append hit its bound, a self-check of a kernel failed
     int32_t again;     // flatten: a walk ended below its root (behind error: union_find.hpp's flatten reads the two words together)
-    int32_t nlist[3];  // vertices in the group / wave / workgroup list
+    int32_t count[4];  // vertices in the group / wave / workgroup list: words 1 .. 3 (row_classes.hpp)
     int32_t max_at;    // largest blocks_at
+    int32_t pad;
     unsigned long long examined;      // arcs the arc passes looked at
     unsigned long long upper, lower;  // arcs u -> v with u < v / with u > v
     unsigned long long comps, isolated, nd_roots;
     unsigned long long blocks, bridges, artic, sum_at, sum_edges;
     unsigned long long best_edges;  // edges of the largest block
     unsigned long long best;        // id << 32 | vertices of the block of the smallest id among those
-};
-
-struct BiccLists {
-    const int32_t *list[3];
-    int64_t cap[3];
-    int64_t short_row;
 };
 
 // every per-vertex word of the call
@@ -119,43 +110,6 @@ __global__ __launch_bounds__(256) void k_bicc_init(int64_t n, BiccArrays a) {
     a.top[v] = INT_MAX;
 }
 
-// the three lists of the rows that get more than a lane (whole waves stay converged for the ballots)
-__global__ __launch_bounds__(256) void k_bicc_classify(int64_t n, const int64_t *__restrict__ off, int64_t short_row, int64_t wave_row, int64_t wg_row,
-                                                       int32_t *__restrict__ lg, int32_t *__restrict__ lw, int32_t *__restrict__ lb, int64_t cap_g,
-                                                       int64_t cap_w, int64_t cap_b, BiccAcc *__restrict__ acc) {
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    const int64_t end = ((n + 63) / 64) * 64;
-    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride) {
-        const int64_t d = v < n ? off[v + 1] - off[v] : -1;
-        wave_append(d >= short_row && d < wave_row, int32_t(v), lg, &acc->nlist[0], cap_g, &acc->error);
-        wave_append(d >= wave_row && d < wg_row, int32_t(v), lw, &acc->nlist[1], cap_w, &acc->error);
-        wave_append(d >= wg_row, int32_t(v), lb, &acc->nlist[2], cap_b, &acc->error);
-    }
-}
-
-// A ROW PASS: WIDTH lanes (1, kGroup, 64, or the 256 threads of the workgroup) per row; what an arc means is the Op's business.  list ==
-// nullptr: the rows are the vertices 0 .. n - 1 with fewer than dmax entries; else list[0 .. nlist[which]).  Op::row<kLanes> is called by all
-// WIDTH lanes of a row (kLanes of them share a wave) and returns the arcs this lane looked at; Op::finish by every thread, converged.
-template <class Op, int WIDTH>
-__global__ __launch_bounds__(256) void k_bicc_rows(Op op, int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ list, int which,
-                                                   int64_t list_cap, int64_t dmax, BiccAcc *__restrict__ acc) {
-    constexpr int kLanes = WIDTH > 64 ? 64 : WIDTH;
-    const int lane = threadIdx.x & (WIDTH - 1);
-    const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
-    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
-    const int64_t rows = list ? min(int64_t(acc->nlist[which]), list_cap) : n;
-    unsigned long long examined = 0;
-    for (int64_t i = row0; i < rows; i += rows_step) {
-        const int32_t v = list ? list[i] : int32_t(i);
-        const int64_t j0 = off[v], j1 = off[v + 1];
-        if (j1 - j0 >= dmax || j1 == j0) continue;
-        examined += op.template row<kLanes>(v, j0, j1, lane, WIDTH);
-    }
-    op.finish(acc);
-    examined = wave_sum(examined);
-    if ((threadIdx.x & 63) == 0 && examined) atomicAdd(&acc->examined, examined);
-}
-
 // step 1: every edge is linked from its end of the larger id
 struct OpLink {
     const int32_t *adj;
@@ -171,7 +125,8 @@ struct OpLink {
         }
         return seen;
     }
-    __device__ __forceinline__ void finish(BiccAcc *) {}
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void finish() {}
 };
 
 // step 5: pre[w] over the non-tree neighbours of v into low[v] and high[v] (which start at pre[v]); the first lane of every wave's share of
@@ -199,7 +154,8 @@ struct OpLowHigh {
         }
         return seen;
     }
-    __device__ __forceinline__ void finish(BiccAcc *) {}
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void finish() {}
 };
 
 // step 6: the two rules of the auxiliary graph
@@ -222,7 +178,8 @@ struct OpAux {
         }
         return seen;
     }
-    __device__ __forceinline__ void finish(BiccAcc *) {}
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void finish() {}
 };
 
 // the set of arc {v, w}: that of its end with the larger pre
@@ -234,6 +191,7 @@ __device__ __forceinline__ int32_t bicc_set(const int32_t *__restrict__ aux, con
 struct OpFirst {
     const int32_t *adj, *pre, *aux;
     unsigned long long *first, *edges;
+    BiccAcc *acc;
     int32_t run_set;
     unsigned long long run, upper, lower;
     __device__ __forceinline__ void flush() {
@@ -261,7 +219,8 @@ struct OpFirst {
         }
         return seen;
     }
-    __device__ __forceinline__ void finish(BiccAcc *acc) {
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void finish() {
         flush();
         upper = wave_sum(upper);
         lower = wave_sum(lower);
@@ -288,7 +247,8 @@ struct OpOut {
         }
         return seen;
     }
-    __device__ __forceinline__ void finish(BiccAcc *) {}
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void finish() {}
 };
 
 // step 2: one level of the forest as a policy of the engine
@@ -562,19 +522,6 @@ __global__ __launch_bounds__(256) void k_bicc_largest(int64_t n, BiccArrays a, B
     if ((threadIdx.x & 63) == 0 && best != ~0ull) atomicMin(&acc->best, best);
 }
 
-// one row pass: the lane bin over all vertices, the three lists above it
-template <class Op>
-void bicc_rows(const Op &op, const gmsx_graph *g, const BiccLists &l, BiccAcc *acc, int cus, hipStream_t s, int *launches) {
-    const int64_t n = g->n;
-    const unsigned lanes = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
-    const unsigned grid = unsigned(cus) * 8;
-    hipLaunchKernelGGL((k_bicc_rows<Op, 1>), dim3(lanes), dim3(256), 0, s, op, n, g->off, (const int32_t *)nullptr, 0, int64_t(0), l.short_row, acc);
-    hipLaunchKernelGGL((k_bicc_rows<Op, kGroup>), dim3(grid), dim3(256), 0, s, op, n, g->off, l.list[0], 0, l.cap[0], int64_t(INT64_MAX), acc);
-    hipLaunchKernelGGL((k_bicc_rows<Op, 64>), dim3(grid), dim3(256), 0, s, op, n, g->off, l.list[1], 1, l.cap[1], int64_t(INT64_MAX), acc);
-    hipLaunchKernelGGL((k_bicc_rows<Op, 256>), dim3(grid), dim3(256), 0, s, op, n, g->off, l.list[2], 2, l.cap[2], int64_t(INT64_MAX), acc);
-    *launches += 4;
-}
-
 // one sweep over the levels from .. to (either direction) of the host's copy of loff: runs of levels of at most wg_level vertices each go to
 // one workgroup in one launch, every other level to a grid of its own
 template <class Op>
@@ -611,14 +558,13 @@ int bicc(const gmsx_graph *g, int32_t *block, int32_t *blocks_at, uint8_t *arc_k
     hipStream_t s = c.stream;
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
     // test hooks, first guesses
-    const int64_t wave_row = std::max<long long>(1, std::min<long long>(opt_int("BCC_WAVE_ROW", kBiccWaveRowDefault), INT_MAX));
-    const int64_t wg_row = std::max<long long>(wave_row, std::min<long long>(opt_int("BCC_WG_ROW", kBiccWgRowDefault), INT_MAX));
+    const RowBounds bounds = row_bounds("BCC_WAVE_ROW", "BCC_WG_ROW");
     const int64_t wg_level = std::max<long long>(0, std::min<long long>(opt_int("BCC_WG_LEVEL", kBiccWgLevelDefault), INT_MAX));
     const long long wg_frontier = frontier_wg_option("BCC_WG_FRONTIER", kWgFrontierDefault);
     const bool timing = opt_on("TIMING");  // one line per call on stderr: the wall time of every phase (each ends in a synchronize then)
     // ---- setup: the buffers
     GMSX_HIP(hipEventRecord(c.ev[0], s));
-    DevBuf d32[17], d64[4], d_lists[3], d_ctrl, d_acc, d_block, d_keep;
+    DevBuf d32[17], d64[4], d_ctrl, d_acc, d_block, d_keep;
     FrontierStore store;
     BiccArrays a;
     int32_t **w32[17] = {&a.label, &a.depth, &a.parent, &a.rank, &a.order, &a.loff, &a.nd,  &a.slot, &a.rel,
@@ -637,14 +583,8 @@ int bicc(const gmsx_graph *g, int32_t *block, int32_t *blocks_at, uint8_t *arc_k
     a.pos = d64[1].as<int64_t>();
     a.first = d64[2].as<unsigned long long>();
     a.edges = d64[3].as<unsigned long long>();
-    BiccLists l;
-    l.short_row = std::min<int64_t>(kBiccShortRow, wave_row);
-    const int64_t bound[3] = {l.short_row, wave_row, wg_row};
-    for (int b = 0; b < 3; ++b) {
-        l.cap[b] = std::min<int64_t>(n, nnz / bound[b] + 1);
-        if (int rc = dalloc<int32_t>(d_lists[b], l.cap[b])) return rc;
-        l.list[b] = d_lists[b].as<const int32_t>();
-    }
+    RowListStore lists;
+    if (int rc = lists.alloc(n, nnz, bounds, false, false)) return rc;
     if (int rc = store.alloc(n, nnz, false)) return rc;
     if (int rc = dalloc<BiccCtrl>(d_ctrl, 1)) return rc;
     if (int rc = dalloc<BiccAcc>(d_acc, 1)) return rc;
@@ -661,7 +601,7 @@ int bicc(const gmsx_graph *g, int32_t *block, int32_t *blocks_at, uint8_t *arc_k
     int launches = 0;
     const unsigned per_vertex = unsigned((n + 256) / 256);  // n + 1 threads
     const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
-    const uint32_t cap = uint32_t(std::min<int64_t>(n + 64, int64_t(INT_MAX)));
+    const uint32_t cap = cc_walk_cap(n);
     double phase_ms[7] = {0, 0, 0, 0, 0, 0, 0};  // roots, forest, nd, preorder, low / high, arc passes, ids
     auto t0 = std::chrono::steady_clock::now();
     auto phase_end = [&](int which) -> int {  // (TIMING only: the phases of an ordinary call run back to back)
@@ -674,10 +614,10 @@ int bicc(const gmsx_graph *g, int32_t *block, int32_t *blocks_at, uint8_t *arc_k
     };
     // ---- 1: the roots
     hipLaunchKernelGGL(k_bicc_init, dim3(per_vertex), dim3(256), 0, s, n, a);
-    hipLaunchKernelGGL(k_bicc_classify, dim3(sweep), dim3(256), 0, s, n, g->off, l.short_row, wave_row, wg_row, d_lists[0].as<int32_t>(),
-                       d_lists[1].as<int32_t>(), d_lists[2].as<int32_t>(), l.cap[0], l.cap[1], l.cap[2], acc);
-    launches += 2;
-    bicc_rows(OpLink{g->adj, a.label, cap, &acc->error}, g, l, acc, cus, s, &launches);
+    ++launches;
+    classify_rows<false>(g, bounds, lists.l, acc->count, &acc->error, cus, s, &launches);
+    auto rows = [&](const auto &op) { launch_rows(op, g, bounds, lists.l, acc->count, &acc->examined, cus, s, &launches); };
+    rows(OpLink{g->adj, a.label, cap, &acc->error});
     if (int rc = flatten(n, a.label, &acc->error, cus, s, &launches, nullptr)) return rc;
     hipLaunchKernelGGL(k_bicc_forest_init, dim3(per_vertex), dim3(256), 0, s, n, a.label, a.depth, a.parent);
     frontier_collect(n, BiccIsRoot{a.label}, a.order, &ctrl->placed, &ctrl->error);
@@ -720,17 +660,17 @@ int bicc(const gmsx_graph *g, int32_t *block, int32_t *blocks_at, uint8_t *arc_k
     bicc_sweep(SweepPre{a.parent, a.rel, a.pre, a.low, a.high}, n, h_loff, 0, levels - 1, wg_level, a.order, a.loff, s, &launches);
     if (int rc = phase_end(3)) return rc;
     // ---- 5: low and high
-    bicc_rows(OpLowHigh{g->adj, a.parent, a.pre, a.low, a.high}, g, l, acc, cus, s, &launches);
+    rows(OpLowHigh{g->adj, a.parent, a.pre, a.low, a.high});
     if (int rc = phase_end(5)) return rc;
     if (levels > 1) bicc_sweep(SweepLowHigh{a.parent, a.low, a.high}, n, h_loff, levels - 1, 1, wg_level, a.order, a.loff, s, &launches);
     if (int rc = phase_end(4)) return rc;
     // ---- 6: the auxiliary unions
-    bicc_rows(OpAux{g->adj, a.parent, a.pre, a.nd, a.low, a.high, a.aux, cap, &acc->error}, g, l, acc, cus, s, &launches);
+    rows(OpAux{g->adj, a.parent, a.pre, a.nd, a.low, a.high, a.aux, cap, &acc->error});
     if (int rc = flatten(n, a.aux, &acc->error, cus, s, &launches, nullptr)) return rc;
     // ---- 7: first arcs, edges, ids
     hipLaunchKernelGGL(k_bicc_ids_init, dim3(per_vertex), dim3(256), 0, s, n, a);
     ++launches;
-    bicc_rows(OpFirst{g->adj, a.pre, a.aux, a.first, a.edges, -1, 0, 0, 0}, g, l, acc, cus, s, &launches);
+    rows(OpFirst{g->adj, a.pre, a.aux, a.first, a.edges, acc, -1, 0, 0, 0});
     if (int rc = phase_end(5)) return rc;
     const unsigned grid16 = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
     const unsigned grid64 = unsigned(std::min<int64_t>((n * 64 + 255) / 256, int64_t(cus) * 8));
@@ -752,7 +692,7 @@ int bicc(const gmsx_graph *g, int32_t *block, int32_t *blocks_at, uint8_t *arc_k
     if (int rc = phase_end(6)) return rc;
     // ---- 10: the per-arc outputs
     if (block || arc_keep) {
-        bicc_rows(OpOut{g->adj, a.pre, a.aux, a.id, a.size, d_block.as<int32_t>(), d_keep.as<uint8_t>()}, g, l, acc, cus, s, &launches);
+        rows(OpOut{g->adj, a.pre, a.aux, a.id, a.size, d_block.as<int32_t>(), d_keep.as<uint8_t>()});
         if (int rc = phase_end(5)) return rc;
     }
     GMSX_HIP(hipEventRecord(c.ev[2], s));
@@ -776,29 +716,17 @@ int bicc(const gmsx_graph *g, int32_t *block, int32_t *blocks_at, uint8_t *arc_k
     res.max_blocks_at = r.max_at;
     res.levels = levels;
     // the flag word was read as zero: the caller's arrays are written now, through host staging
-    std::vector<int32_t> h_block, h_at;
-    std::vector<uint8_t> h_keep;
-    if (block) {
-        h_block.resize(size_t(nnz));
-        GMSX_HIP(hipMemcpyAsync(h_block.data(), d_block.p, size_t(nnz) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    if (blocks_at) {
-        h_at.resize(size_t(n));
-        GMSX_HIP(hipMemcpyAsync(h_at.data(), a.at, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    if (arc_keep) {
-        h_keep.resize(size_t(nnz));
-        GMSX_HIP(hipMemcpyAsync(h_keep.data(), d_keep.p, size_t(nnz), hipMemcpyDeviceToHost, s));
-    }
+    HostStage out;
+    if (int rc = out.fetch(block, d_block.p, size_t(nnz) * sizeof(int32_t), s)) return rc;
+    if (int rc = out.fetch(blocks_at, a.at, size_t(n) * sizeof(int32_t), s)) return rc;
+    if (int rc = out.fetch(arc_keep, d_keep.p, size_t(nnz), s)) return rc;
     GMSX_HIP(hipEventRecord(c.ev[3], s));
     GMSX_HIP(hipStreamSynchronize(s));
     float up_ms = 0.f, ms = 0.f, out_ms = 0.f;
     GMSX_HIP(hipEventElapsedTime(&up_ms, c.ev[0], c.ev[1]));
     GMSX_HIP(hipEventElapsedTime(&ms, c.ev[1], c.ev[2]));
     GMSX_HIP(hipEventElapsedTime(&out_ms, c.ev[2], c.ev[3]));
-    if (block) std::memcpy(block, h_block.data(), size_t(nnz) * sizeof(int32_t));
-    if (blocks_at) std::memcpy(blocks_at, h_at.data(), size_t(n) * sizeof(int32_t));
-    if (arc_keep) std::memcpy(arc_keep, h_keep.data(), size_t(nnz));
+    out.deliver();
     *info = res;
     if (timing)
         std::fprintf(stderr,

@@ -66,10 +66,6 @@ constexpr int64_t kLpSlabBytes = int64_t(1) << 30;  // the long rows' regions to
 // and 22: 0, 1024 and 4096 measured the same, 32768 up to 30 % slower at scale 20; LP_ACTIVE = 1 is 7 – 17 % faster.
 constexpr long long kLpWaveRowDefault = 64, kLpLdsRowDefault = 2048, kLpLdsSlotsDefault = kLpSlotsMax, kLpWgWorkDefault = 4096, kLpActiveDefault = 1;
 
-__device__ __forceinline__ unsigned long long load_now(const unsigned long long *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // the call's small device block, mirrored to the host after every sweep
 struct LpCtrl {
     int32_t error;    // the flag word: a probe loop passed its cap, a table would not fit its region, a placement hit its bound

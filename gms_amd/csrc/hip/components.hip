@@ -7,10 +7,8 @@
 // THE UNION-FIND (cc_find, cc_link, the flatten and size kernels, their memory model and their caps) is union_find.hpp's: a root is only ever
 // hooked under a SMALLER vertex id, so after a full flatten label[v] is the smallest vertex id of v's component.
 //
-// WORK DISTRIBUTION over CSR rows (k_cc_link, one template over the edge source and the lanes per row): one lane per row below kCcShortRow
-// entries, a 16-lane group per row below CC_WAVE_ROW, a wave per row below CC_WG_ROW, a whole workgroup per row from there on (a hub of 10^5 to
-// 10^6 entries is not one wave's job).  The three upper bins are vertex lists a classify kernel fills once per call (their order is the arrival
-// order of atomics and reaches no output).  The bin edges are options and first guesses, not tuned values.
+// WORK DISTRIBUTION over CSR rows is row_classes.hpp's (a lane, a 16-lane group, a wave or a workgroup per row by its length; the bounds are
+// CC_WAVE_ROW and CC_WG_ROW); CcLink, one template over the edge source, is the Op of its row pass.
 //
 // THE GIANT COMPONENT (Afforest's sampling; whole-graph call only).  Pass A links the first CC_SAMPLE neighbours of every vertex, a flatten
 // follows, one workgroup reads the labels of 1024 seeded vertex ids and picks the most frequent label L (ties: the smaller), and pass B links the
@@ -32,29 +30,28 @@
 #include "device_graph.hpp"
 #include "frontier_rounds.hpp"  // load_now, store_now, wave_append, kGroup
 #include "pair_similarity.hpp"
+#include "row_classes.hpp"
 #include "union_find.hpp"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <vector>
 
 namespace gmsx {
 
 namespace {
 
-constexpr int kCcShortRow = 16;    // rows below this: one lane
 constexpr int kCcSamples = 1024;   // vertex ids the giant-component vote reads
-constexpr long long kCcSampleDefault = 2, kCcWaveRowDefault = 256, kCcWgRowDefault = 4096;  // first guesses (gmsx.h, OPTIONS)
+constexpr long long kCcSampleDefault = 2;  // a first guess (gmsx.h, OPTIONS)
 
 // the call's small device block, zeroed per call and read once
 struct CcAcc {
     int32_t error;   // the flag word: a cap was exceeded, an append hit its bound, an arc has no twin
     int32_t again;   // flatten: a walk ended below its root (behind error: union_find.hpp's flatten reads the two words together)
     int32_t giant;   // the label pass B skips, -1 = none
-    int32_t nlist[3];  // vertices in the group / wave / workgroup list
-    int32_t pad[2];
+    int32_t pad;
+    int32_t count[4];  // vertices in the group / wave / workgroup list: words 1 .. 3 (row_classes.hpp)
     unsigned long long examined;  // arcs the linking kernels looked at (Jarvis–Patrick: edges scored)
     unsigned long long kept;      // undirected edges the components are taken over
     unsigned long long comps, singles;
@@ -78,47 +75,32 @@ __global__ void k_cc_init(int64_t n, int32_t *__restrict__ parent, int32_t *__re
     }
 }
 
-// the three lists of the rows that get more than a lane (whole waves stay converged for the ballots)
-__global__ __launch_bounds__(256) void k_cc_classify(int64_t n, const int64_t *__restrict__ off, int64_t short_row, int64_t wave_row, int64_t wg_row,
-                                                     int32_t *__restrict__ lg, int32_t *__restrict__ lw, int32_t *__restrict__ lb, int64_t cap_g,
-                                                     int64_t cap_w, int64_t cap_b, CcAcc *__restrict__ acc) {
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    const int64_t end = ((n + 63) / 64) * 64;
-    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride) {
-        const int64_t d = v < n ? off[v + 1] - off[v] : -1;
-        wave_append(d >= short_row && d < wave_row, int32_t(v), lg, &acc->nlist[0], cap_g, &acc->error);
-        wave_append(d >= wave_row && d < wg_row, int32_t(v), lw, &acc->nlist[1], cap_w, &acc->error);
-        wave_append(d >= wg_row, int32_t(v), lb, &acc->nlist[2], cap_b, &acc->error);
+// The Op of the linking passes: links the arcs at positions [lo, min(degree, hi)) of a row that the source keeps.  A row whose label is *giant
+// (giant != nullptr) is skipped.
+template <class Src>
+struct CcLink {
+    Src src;
+    int64_t lo, hi;
+    const int32_t *giant;
+    int32_t *parent;
+    const int32_t *adj;
+    uint32_t cap;
+    int32_t *error;
+    int32_t skip = -1;
+    __device__ __forceinline__ void begin() { skip = giant ? *giant : -1; }
+    template <int>
+    __device__ __forceinline__ unsigned long long row(int32_t v, int64_t j0, int64_t j1, int lane, int width) {
+        const int64_t d = j1 - j0;
+        if (d <= lo) return 0;
+        if (skip >= 0 && load_now(&parent[v]) == skip) return 0;
+        unsigned long long seen = 0;
+        j1 = j0 + min(d, hi);
+        for (int64_t j = j0 + lo + lane; j < j1; j += width, ++seen)
+            if (src.keep(j)) cc_link(parent, v, adj[j], cap, error);
+        return seen;
     }
-}
-
-// Links the arcs at positions [lo, min(degree, hi)) of its rows that the source keeps: WIDTH lanes per row.  list == nullptr: the rows are the
-// vertices 0 .. n - 1 whose degree is below dmax; else list[0 .. *count).  A row whose label is `giant` (acc->giant when use_giant) is skipped.
-template <class Src, int WIDTH>
-__global__ __launch_bounds__(256) void k_cc_link(Src src, int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                 const int32_t *__restrict__ list, int which, int64_t list_cap, int64_t dmax, int64_t lo, int64_t hi,
-                                                 int use_giant, int32_t *__restrict__ parent, CcAcc *__restrict__ acc) {
-    const int lane = threadIdx.x & (WIDTH - 1);
-    const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
-    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
-    const int64_t rows = list ? min(int64_t(acc->nlist[which]), list_cap) : n;
-    const int32_t giant = use_giant ? acc->giant : -1;
-    const uint32_t cap = uint32_t(min(n + 64, int64_t(INT_MAX)));
-    unsigned long long examined = 0;
-    for (int64_t i = row0; i < rows; i += rows_step) {
-        const int32_t v = list ? list[i] : int32_t(i);
-        const int64_t j0 = off[v], d = off[v + 1] - j0;
-        if (d >= dmax || d <= lo) continue;
-        if (giant >= 0 && load_now(&parent[v]) == giant) continue;
-        const int64_t j1 = j0 + min(d, hi);
-        for (int64_t j = j0 + lo + lane; j < j1; j += WIDTH) {
-            ++examined;
-            if (src.keep(j)) cc_link(parent, v, adj[j], cap, &acc->error);
-        }
-    }
-    examined = wave_sum(examined);
-    if ((threadIdx.x & 63) == 0 && examined) atomicAdd(&acc->examined, examined);
-}
+    __device__ __forceinline__ void finish() {}
+};
 
 // Jarvis–Patrick: wave w takes the arcs w, w + W, …, 64 at a time (a lane resolves the source of each); one score per `u < v` arc, the kept
 // ones linked (and marked on both arcs when mask != nullptr).  amdgpu_waves_per_eu(8, 8): the score loop is latency-bound and lives on resident
@@ -130,7 +112,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = uni64((int64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 6);
     const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
-    const uint32_t cap = uint32_t(min(n + 64, int64_t(INT_MAX)));
+    const uint32_t cap = cc_walk_cap(n);
     unsigned long long scored = 0, kept = 0;  // (lane 0's are the wave's)
     for (int64_t k0 = 0; wave0 + k0 * nwaves < nnz; k0 += 64) {
         // lane t resolves arc wave0 + (k0 + t) nwaves: its source is the last u with off[u] <= j (off[n] = nnz > j, so u <= n - 1)
@@ -251,30 +233,6 @@ __global__ __launch_bounds__(256) void k_cc_info(int64_t n, const int32_t *__res
 
 enum { kSrcAll = 0, kSrcMask = 1, kSrcJp = 2 };
 
-struct CcLists {
-    DevBuf g, w, b;
-    int64_t cap_g = 0, cap_w = 0, cap_b = 0;
-    int64_t short_row = 0;
-};
-
-// one pass of the row kernels over the positions [lo, hi) of every row: the lane bin over all vertices, the three lists above it
-template <class Src>
-void link_rows(const Src &src, const gmsx_graph *g, const CcLists &l, int64_t lo, int64_t hi, int use_giant, int32_t *parent, CcAcc *acc, int cus,
-               hipStream_t s, int *launches) {
-    const int64_t n = g->n;
-    const unsigned lanes = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
-    hipLaunchKernelGGL((k_cc_link<Src, 1>), dim3(lanes), dim3(256), 0, s, src, n, g->off, g->adj, (const int32_t *)nullptr, 0, int64_t(0), l.short_row, lo,
-                       hi, use_giant, parent, acc);
-    const unsigned grid = unsigned(cus) * 8;
-    hipLaunchKernelGGL((k_cc_link<Src, kGroup>), dim3(grid), dim3(256), 0, s, src, n, g->off, g->adj, l.g.as<const int32_t>(), 0, l.cap_g,
-                       int64_t(INT64_MAX), lo, hi, use_giant, parent, acc);
-    hipLaunchKernelGGL((k_cc_link<Src, 64>), dim3(grid), dim3(256), 0, s, src, n, g->off, g->adj, l.w.as<const int32_t>(), 1, l.cap_w, int64_t(INT64_MAX),
-                       lo, hi, use_giant, parent, acc);
-    hipLaunchKernelGGL((k_cc_link<Src, 256>), dim3(grid), dim3(256), 0, s, src, n, g->off, g->adj, l.b.as<const int32_t>(), 2, l.cap_b, int64_t(INT64_MAX),
-                       lo, hi, use_giant, parent, acc);
-    *launches += 4;
-}
-
 // Both entry points.  mask_in (host, nnz) for kSrcMask; mask_out (host, nnz, or null) for kSrcJp.
 int components(const gmsx_graph *g, int source, const uint8_t *mask_in, int metric, double threshold, int32_t *label, uint8_t *mask_out,
                gmsx_components_info *info, gmsx_stats *stats) {
@@ -291,13 +249,8 @@ int components(const gmsx_graph *g, int source, const uint8_t *mask_in, int metr
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
     // test hooks, first guesses
     const int64_t sample = std::max<long long>(0, std::min<long long>(opt_int("CC_SAMPLE", kCcSampleDefault), INT_MAX));
-    const int64_t wave_row = std::max<long long>(1, std::min<long long>(opt_int("CC_WAVE_ROW", kCcWaveRowDefault), INT_MAX));
-    const int64_t wg_row = std::max<long long>(wave_row, std::min<long long>(opt_int("CC_WG_ROW", kCcWgRowDefault), INT_MAX));
-    CcLists l;
-    l.short_row = std::min<int64_t>(kCcShortRow, wave_row);
-    l.cap_g = std::min<int64_t>(n, nnz / l.short_row + 1);
-    l.cap_w = std::min<int64_t>(n, nnz / wave_row + 1);
-    l.cap_b = std::min<int64_t>(n, nnz / wg_row + 1);
+    const RowBounds bounds = row_bounds("CC_WAVE_ROW", "CC_WG_ROW");
+    RowListStore lists;
     DevBuf d_parent, d_size, d_acc, d_mask;
     const bool dev_mask = source == kSrcMask || (source == kSrcJp && mask_out);
     // ---- setup: the buffers and the caller's mask
@@ -305,11 +258,8 @@ int components(const gmsx_graph *g, int source, const uint8_t *mask_in, int metr
     if (int rc = dalloc<int32_t>(d_parent, n)) return rc;
     if (int rc = dalloc<int32_t>(d_size, n)) return rc;
     if (int rc = dalloc<CcAcc>(d_acc, 1)) return rc;
-    if (source != kSrcJp) {
-        if (int rc = dalloc<int32_t>(l.g, l.cap_g)) return rc;
-        if (int rc = dalloc<int32_t>(l.w, l.cap_w)) return rc;
-        if (int rc = dalloc<int32_t>(l.b, l.cap_b)) return rc;
-    }
+    if (source != kSrcJp)
+        if (int rc = lists.alloc(n, nnz, bounds, false, false)) return rc;
     if (dev_mask)
         if (int rc = dalloc<uint8_t>(d_mask, nnz)) return rc;
     CcAcc *acc = d_acc.as<CcAcc>();
@@ -333,28 +283,28 @@ int components(const gmsx_graph *g, int source, const uint8_t *mask_in, int metr
             ++launches;
         }
     } else if (nnz > 0) {
-        hipLaunchKernelGGL(k_cc_classify, dim3(sweep), dim3(256), 0, s, n, g->off, l.short_row, wave_row, wg_row, l.g.as<int32_t>(), l.w.as<int32_t>(),
-                           l.b.as<int32_t>(), l.cap_g, l.cap_w, l.cap_b, acc);
-        ++launches;
-        const SrcMask masked{d_mask.as<const uint8_t>()};
-        int use_giant = 0;
-        if (sample > 0) {  // pass A: the first `sample` entries of every row, a lane per row
-            if (source == kSrcAll)
-                hipLaunchKernelGGL((k_cc_link<SrcAll, 1>), dim3(sweep), dim3(256), 0, s, SrcAll{}, n, g->off, g->adj, (const int32_t *)nullptr, 0, int64_t(0),
-                                   int64_t(INT64_MAX), int64_t(0), sample, 0, parent, acc);
-            else
-                hipLaunchKernelGGL((k_cc_link<SrcMask, 1>), dim3(sweep), dim3(256), 0, s, masked, n, g->off, g->adj, (const int32_t *)nullptr, 0, int64_t(0),
-                                   int64_t(INT64_MAX), int64_t(0), sample, 0, parent, acc);
-            ++launches;
-            if (source == kSrcAll) {  // the skip is valid only where every kept edge is visible from both sides
-                if (int rc = flatten(n, parent, &acc->error, cus, s, &launches, nullptr)) return rc;
-                hipLaunchKernelGGL(k_cc_vote, dim3(1), dim3(kCcSamples), 0, s, n, parent, acc);
+        classify_rows<false>(g, bounds, lists.l, acc->count, &acc->error, cus, s, &launches);
+        // pass A (the first `sample` entries of every row, a lane per row over all vertices), the vote where it is valid, pass B (the rest)
+        auto link = [&](auto src) -> int {
+            using Op = CcLink<decltype(src)>;
+            const int64_t all = INT64_MAX;
+            const int32_t *giant = nullptr;
+            if (sample > 0) {
+                hipLaunchKernelGGL((k_rows<Op, 1>), dim3(sweep), dim3(256), 0, s, Op{src, 0, sample, nullptr, parent, g->adj, cc_walk_cap(n), &acc->error}, n,
+                                   g->off, (const int32_t *)nullptr, acc->count, int64_t(0), all, &acc->examined);
                 ++launches;
-                use_giant = 1;
+                if (source == kSrcAll) {  // the skip is valid only where every kept edge is visible from both sides
+                    if (int rc = flatten(n, parent, &acc->error, cus, s, &launches, nullptr)) return rc;
+                    hipLaunchKernelGGL(k_cc_vote, dim3(1), dim3(kCcSamples), 0, s, n, parent, acc);
+                    ++launches;
+                    giant = &acc->giant;
+                }
             }
-        }
-        if (source == kSrcAll) link_rows(SrcAll{}, g, l, sample, int64_t(INT64_MAX), use_giant, parent, acc, cus, s, &launches);
-        else link_rows(masked, g, l, sample, int64_t(INT64_MAX), 0, parent, acc, cus, s, &launches);
+            launch_rows(Op{src, sample, all, giant, parent, g->adj, cc_walk_cap(n), &acc->error}, g, bounds, lists.l, acc->count, &acc->examined, cus, s,
+                        &launches);
+            return GMSX_OK;
+        };
+        if (int rc = source == kSrcAll ? link(SrcAll{}) : link(SrcMask{d_mask.as<const uint8_t>()})) return rc;
     }
     int32_t passes = 0;
     if (int rc = flatten(n, parent, &acc->error, cus, s, &launches, &passes)) return rc;
@@ -379,23 +329,16 @@ int components(const gmsx_graph *g, int source, const uint8_t *mask_in, int metr
     res.kept_edges = source == kSrcAll ? nnz / 2 : int64_t(h.kept);
     res.passes = passes;
     // the flag word was read as zero: the caller's arrays are written now, through host staging
-    std::vector<int32_t> h_label;
-    std::vector<uint8_t> h_mask;
-    if (label) {
-        h_label.resize(size_t(n));
-        GMSX_HIP(hipMemcpyAsync(h_label.data(), parent, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    if (source == kSrcJp && mask_out && nnz > 0) {
-        h_mask.resize(size_t(nnz));
-        GMSX_HIP(hipMemcpyAsync(h_mask.data(), d_mask.p, size_t(nnz), hipMemcpyDeviceToHost, s));
-    }
+    HostStage out;
+    if (int rc = out.fetch(label, parent, size_t(n) * sizeof(int32_t), s)) return rc;
+    if (source == kSrcJp)
+        if (int rc = out.fetch(mask_out, d_mask.p, size_t(nnz), s)) return rc;
     GMSX_HIP(hipStreamSynchronize(s));
     float up_ms = 0.f, ms = 0.f, info_ms = 0.f;
     GMSX_HIP(hipEventElapsedTime(&up_ms, c.ev[0], c.ev[1]));
     GMSX_HIP(hipEventElapsedTime(&ms, c.ev[1], c.ev[2]));
     GMSX_HIP(hipEventElapsedTime(&info_ms, c.ev[2], c.ev[3]));
-    if (label) std::memcpy(label, h_label.data(), size_t(n) * sizeof(int32_t));
-    if (!h_mask.empty()) std::memcpy(mask_out, h_mask.data(), size_t(nnz));
+    out.deliver();
     *info = res;
     if (stats)
         *stats = gmsx_stats{double(ms), double(up_ms) + double(info_ms), uint64_t(h.examined), source == kSrcJp ? g->alg_elements : 0, 0, launches, 0, 0};

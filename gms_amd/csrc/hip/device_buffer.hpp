@@ -1,10 +1,13 @@
-// The one owner of a device allocation in the host code of the kernel translation units: freed when it leaves scope.
+// The one owner of a device allocation in the host code of the kernel translation units: freed when it leaves scope.  Beside it HostStage, the
+// one way results leave device memory for a caller's arrays.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <type_traits>
+#include <vector>
 
 #include "gmsx.h"
 
@@ -58,5 +61,36 @@ template <class T>
 int dalloc(DevArr<T> &d, int64_t count) {
     return dalloc<T>(static_cast<DevBuf &>(d), count);
 }
+
+// Results on their way from device memory to a caller's arrays.  THE ORDER: the call reads its flag words as zero, fetch() starts a copy into
+// host memory of the stage's own, the call synchronizes, and only then deliver() writes the caller's memory — a call that fails on the way
+// has not touched it.  A null dst or an empty array is skipped.
+class HostStage {
+    struct Item {
+        void *dst;
+        std::vector<unsigned char> tmp;
+    };
+    std::vector<Item> items;
+
+  public:
+    int fetch(void *dst, const void *src, size_t bytes, hipStream_t s) {
+        if (!dst || bytes == 0) return GMSX_OK;
+        items.push_back(Item{dst, std::vector<unsigned char>(bytes)});
+        if (hipMemcpyAsync(items.back().tmp.data(), src, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) {
+            (void)hipGetLastError();
+            return GMSX_ERR_KERNEL;
+        }
+        return GMSX_OK;
+    }
+    // the three arrays of an edge list of ne entries (all given, or none)
+    int fetch_edges(int32_t *eu, int32_t *ev, int32_t *ew, const DevBuf &du, const DevBuf &dv, const DevBuf &dw, size_t ne, hipStream_t s) {
+        if (int rc = fetch(eu, du.p, ne * sizeof(int32_t), s)) return rc;
+        if (int rc = fetch(ev, dv.p, ne * sizeof(int32_t), s)) return rc;
+        return fetch(ew, dw.p, ne * sizeof(int32_t), s);
+    }
+    void deliver() const {
+        for (const Item &it : items) std::memcpy(it.dst, it.tmp.data(), it.tmp.size());
+    }
+};
 
 }  // namespace gmsx

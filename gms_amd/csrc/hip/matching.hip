@@ -13,11 +13,11 @@
 //
 // A ROUND is two steps with a kernel boundary between them; nothing spins and no workgroup waits for another.  The live lists hold every free
 // vertex that may still have a free neighbour.
-//   (a) search   k_match_search<WIDTH>, THE HOT PASS: every listed v finds cand[v] = the other end of the first arc of its row in the order
-//                whose other end is free (mate[x] < 0, plain loads: the pair pass of the round before wrote it; the weight is loaded for
-//                free ends only), or -1.  Rows are binned by their length as msf.hip's: a lane per row below kMatchShortRow entries, a
-//                16-lane group below MATCH_WAVE_ROW, a wave below MATCH_WG_ROW, a whole workgroup from there on — no lane walks a long row
-//                alone.  cand[v] and candw[v] (the arc's weight) have one writer.  Under MATCH_KEEP = 1 a vertex whose candidate of the last
+//   (a) search   MatchSearch, THE HOT PASS: every listed v finds cand[v] = the other end of the first arc of its row in the order whose other
+//                end is free (mate[x] < 0, plain loads: the pair pass of the round before wrote it; the weight is loaded for free ends
+//                only), or -1.  It is the Op of row_classes.hpp's live-list row pass: a lane, a 16-lane group, a wave or a workgroup per
+//                row by its length (the bounds are MATCH_WAVE_ROW and MATCH_WG_ROW) — no lane walks a long row alone.  cand[v] and
+//                candw[v] (the arc's weight) have one writer.  Under MATCH_KEEP = 1 a vertex whose candidate of the last
 //                round is still free keeps it without walking its row: mates only appear, so its first free arc cannot have changed.
 //   (b) pair     k_match_pair: mate[v] = cand[v] where cand[cand[v]] == v — every vertex writes its own word only, and the kernel reads
 //                cand, which it does not write.  A vertex without a candidate is dead for good (matched vertices stay matched) and a paired
@@ -35,20 +35,18 @@
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
 #include "frontier_rounds.hpp"  // wave_append, kGroup, kLongRow
+#include "row_classes.hpp"
 #include "union_find.hpp"       // cc_find_in_row
 
 #include <algorithm>
 #include <climits>
 #include <cstdio>
 #include <cstring>
-#include <vector>
 
 namespace gmsx {
 
 namespace {
 
-constexpr int kMatchShortRow = 16;  // rows below this: one lane
-constexpr long long kMatchWaveRowDefault = 256, kMatchWgRowDefault = 4096;  // first guesses, msf.hip's (gmsx.h, OPTIONS)
 constexpr long long kMatchKeepDefault = 1;
 constexpr unsigned long long kNoKey = ~0ull;
 
@@ -56,14 +54,8 @@ constexpr unsigned long long kNoKey = ~0ull;
 struct MatchCtrl {
     int32_t error;        // the flag word: an append hit its bound
     int32_t took;         // vertices that took a mate this round: two per pair
-    int32_t count[2][4];  // vertices in the lane / group / wave / workgroup list of either buffer
+    int32_t count[2][4];  // vertices in the lane / group / wave / workgroup list of either buffer (row_classes.hpp)
     unsigned long long examined;  // arcs the search pass looked at
-};
-
-// the four live lists: list b of buffer i is buf[i] + base[b], at most cap[b] entries
-struct MatchLists {
-    int32_t *buf[2];
-    int64_t base[4], cap[4];
 };
 
 // the info pass's words
@@ -104,41 +96,19 @@ __global__ void k_match_init(int64_t n, int32_t *__restrict__ mate, int32_t *__r
     }
 }
 
-// every vertex with an arc into the list of its row class (whole waves stay converged for the ballots)
-__global__ __launch_bounds__(256) void k_match_classify(int64_t n, const int64_t *__restrict__ off, int64_t short_row, int64_t wave_row, int64_t wg_row,
-                                                        MatchLists l, MatchCtrl *__restrict__ ctrl) {
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    const int64_t end = ((n + 63) / 64) * 64;
-    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride) {
-        const int64_t d = v < n ? off[v + 1] - off[v] : 0;
-        wave_append(d >= 1 && d < short_row, int32_t(v), l.buf[0] + l.base[0], &ctrl->count[0][0], l.cap[0], &ctrl->error);
-        wave_append(d >= short_row && d < wave_row, int32_t(v), l.buf[0] + l.base[1], &ctrl->count[0][1], l.cap[1], &ctrl->error);
-        wave_append(d >= wave_row && d < wg_row, int32_t(v), l.buf[0] + l.base[2], &ctrl->count[0][2], l.cap[2], &ctrl->error);
-        wave_append(d >= wg_row && d >= 1, int32_t(v), l.buf[0] + l.base[3], &ctrl->count[0][3], l.cap[3], &ctrl->error);
-    }
-}
-
-// (a) THE HOT PASS: WIDTH lanes (1, kGroup, 64, or the 256 threads of the workgroup) per row of list `which` of buffer `cur`.
+// (a) THE HOT PASS, the Op of a live-list row pass: WIDTH lanes (1, kGroup, 64, or the 256 threads of the workgroup) per listed row.
 // wgt == nullptr: unit weights (k0 = 0).  keep: a candidate that is still free stands.
-template <int WIDTH>
-__global__ __launch_bounds__(256) void k_match_search(const int64_t *__restrict__ off, const int32_t *__restrict__ adj, const int32_t *__restrict__ wgt,
-                                                      const int32_t *__restrict__ mate, const int32_t *__restrict__ list, int cur, int which,
-                                                      int64_t list_cap, int keep, int32_t *__restrict__ cand, int32_t *__restrict__ candw,
-                                                      MatchCtrl *__restrict__ ctrl) {
-    constexpr int kLanes = WIDTH > 64 ? 64 : WIDTH;  // lanes of one wave that share a row
-    constexpr int kUnit = WIDTH > 64 ? WIDTH : 64;   // threads that go through the row loop together: the wave, or the workgroup
-    __shared__ unsigned long long s_key[4];
-    __shared__ uint32_t s_x[4];
-    const int lane = threadIdx.x & (WIDTH - 1);
-    const int64_t first = ((int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / kUnit) * (kUnit / WIDTH);
-    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
-    const int64_t rows = min(int64_t(ctrl->count[cur][which]), list_cap);
-    unsigned long long examined = 0;
-    // a wave takes 64 / WIDTH consecutive rows at a time and stays together; WIDTH = 256: a row per workgroup, whose barriers the loop passes
-    for (int64_t base = first; base < rows; base += rows_step) {
-        const int64_t i = base + (threadIdx.x & (kUnit - 1)) / WIDTH;
-        const bool active = i < rows;
-        const int32_t v = active ? list[i] : 0;
+struct MatchSearch {
+    const int64_t *off;
+    const int32_t *adj, *wgt, *mate;
+    int keep;
+    int32_t *cand, *candw;
+    template <int WIDTH>
+    __device__ __forceinline__ unsigned long long row(int32_t v, bool active, int lane) const {
+        constexpr int kLanes = WIDTH > 64 ? 64 : WIDTH;  // lanes of one wave that share a row
+        __shared__ unsigned long long s_key[4];
+        __shared__ uint32_t s_x[4];
+        unsigned long long examined = 0;
         bool walk = active;
         if (active && keep) {  // (the lanes of a row read the same two words)
             const int32_t c = cand[v];
@@ -177,19 +147,18 @@ __global__ __launch_bounds__(256) void k_match_search(const int64_t *__restrict_
             cand[v] = best != kNoKey ? int32_t(best_x) : -1;
             candw[v] = wgt ? int32_t(~uint32_t(best >> 32)) : 1;
         }
+        return examined;
     }
-    examined = wave_sum(examined);
-    if ((threadIdx.x & 63) == 0 && examined) atomicAdd(&ctrl->examined, examined);
-}
+};
 
 // (b) mutual candidates become mates; whoever still has a candidate goes to the next list of its class
-__global__ __launch_bounds__(256) void k_match_pair(MatchLists l, int cur, const int32_t *__restrict__ cand, int32_t *__restrict__ mate,
+__global__ __launch_bounds__(256) void k_match_pair(RowLists l, int cur, const int32_t *__restrict__ cand, int32_t *__restrict__ mate,
                                                     MatchCtrl *__restrict__ ctrl) {
     const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, stride = int64_t(gridDim.x) * blockDim.x;
     int32_t took = 0;
     for (int b = 0; b < 4; ++b) {
-        const int32_t *list = l.buf[cur] + l.base[b];
-        const int64_t rows = min(int64_t(ctrl->count[cur][b]), l.cap[b]);
+        const int32_t *list = l.list(cur, b);
+        const int64_t rows = l.rows(ctrl->count[cur], b);
         const int64_t end = ((rows + 63) / 64) * 64;  // whole waves stay converged for the ballot
         for (int64_t i = tid; i < end; i += stride) {
             bool stay = false;
@@ -206,7 +175,7 @@ __global__ __launch_bounds__(256) void k_match_pair(MatchLists l, int cur, const
                     }
                 }
             }
-            wave_append(stay, v, l.buf[cur ^ 1] + l.base[b], &ctrl->count[cur ^ 1][b], l.cap[b], &ctrl->error);
+            wave_append(stay, v, l.list(cur ^ 1, b), &ctrl->count[cur ^ 1][b], l.cap[b], &ctrl->error);
         }
     }
     took = wave_sum(took);  // (at most n in all)
@@ -361,19 +330,6 @@ __global__ __launch_bounds__(256) void k_match_check(int64_t n, const int64_t *_
     }
 }
 
-// (a) over list b of buffer cur, `rows` entries: WIDTH lanes per row, at most per_cu workgroups per compute unit
-template <int WIDTH>
-void search_rows(const gmsx_graph *g, const int32_t *wgt, const MatchLists &l, int cur, int b, int64_t rows, int per_cu, int keep, const int32_t *mate,
-                 int32_t *cand, int32_t *candw, MatchCtrl *ctrl, int *launches) {
-    if (rows <= 0) return;
-    Ctx &c = ctx();
-    const int cus = c.compute_units > 0 ? c.compute_units : 256;
-    const unsigned grid = unsigned(std::min<int64_t>((rows * WIDTH + 255) / 256, int64_t(cus) * per_cu));
-    hipLaunchKernelGGL((k_match_search<WIDTH>), dim3(grid), dim3(256), 0, c.stream, g->off, g->adj, wgt, mate, l.buf[cur] + l.base[b], cur, b, l.cap[b], keep,
-                       cand, candw, ctrl);
-    ++*launches;
-}
-
 int matching(const gmsx_graph *g, uint32_t flags, int32_t *mate_out, int32_t *edge_u, int32_t *edge_v, int32_t *edge_w, gmsx_matching_info *info,
              gmsx_stats *stats) {
     gmsx_matching_info res;
@@ -390,29 +346,19 @@ int matching(const gmsx_graph *g, uint32_t flags, int32_t *mate_out, int32_t *ed
     hipStream_t s = c.stream;
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
     // test hooks, first guesses
-    const int64_t wave_row = std::max<long long>(1, std::min<long long>(opt_int("MATCH_WAVE_ROW", kMatchWaveRowDefault), INT_MAX));
-    const int64_t wg_row = std::max<long long>(wave_row, std::min<long long>(opt_int("MATCH_WG_ROW", kMatchWgRowDefault), INT_MAX));
+    const RowBounds bounds = row_bounds("MATCH_WAVE_ROW", "MATCH_WG_ROW");
     const int keep = opt_int("MATCH_KEEP", kMatchKeepDefault) != 0 ? 1 : 0;
     const bool timing = opt_on("TIMING");  // one line per round on stderr: its listed vertices, the arcs it examined, its pairs
-    const int64_t short_row = std::min<int64_t>(kMatchShortRow, wave_row);
     const bool want_edges = edge_u != nullptr;
     const int64_t room = std::max<int64_t>(n / 2, 1);
-    MatchLists l;
-    const int64_t bound[4] = {1, short_row, wave_row, wg_row};  // the shortest row of every list
-    int64_t total = 0;
-    for (int b = 0; b < 4; ++b) {
-        l.base[b] = total;
-        l.cap[b] = std::min<int64_t>(n, nnz / bound[b] + 1);
-        total += l.cap[b];
-    }
+    RowListStore lists;
     // ---- setup: the buffers
-    DevBuf d_mate, d_cand, d_candw, d_list0, d_list1, d_ctrl, d_acc, d_cnt, d_pos, d_eu, d_ev, d_ew;
+    DevBuf d_mate, d_cand, d_candw, d_ctrl, d_acc, d_cnt, d_pos, d_eu, d_ev, d_ew;
     GMSX_HIP(hipEventRecord(c.ev[0], s));
     if (int rc = dalloc<int32_t>(d_mate, n)) return rc;
     if (int rc = dalloc<int32_t>(d_cand, n)) return rc;
     if (int rc = dalloc<int32_t>(d_candw, n)) return rc;
-    if (int rc = dalloc<int32_t>(d_list0, total)) return rc;
-    if (int rc = dalloc<int32_t>(d_list1, total)) return rc;
+    if (int rc = lists.alloc(n, nnz, bounds, true, true)) return rc;
     if (int rc = dalloc<MatchCtrl>(d_ctrl, 1)) return rc;
     if (int rc = dalloc<MatchAcc>(d_acc, 1)) return rc;
     if (int rc = dalloc<int64_t>(d_cnt, n + 1)) return rc;
@@ -422,8 +368,7 @@ int matching(const gmsx_graph *g, uint32_t flags, int32_t *mate_out, int32_t *ed
         if (int rc = dalloc<int32_t>(d_ev, room)) return rc;
         if (int rc = dalloc<int32_t>(d_ew, room)) return rc;
     }
-    l.buf[0] = d_list0.as<int32_t>();
-    l.buf[1] = d_list1.as<int32_t>();
+    const RowLists &l = lists.l;
     MatchCtrl *ctrl = d_ctrl.as<MatchCtrl>();
     MatchAcc *acc = d_acc.as<MatchAcc>();
     int32_t *mate = d_mate.as<int32_t>(), *cand = d_cand.as<int32_t>(), *candw = d_candw.as<int32_t>();
@@ -439,8 +384,8 @@ int matching(const gmsx_graph *g, uint32_t flags, int32_t *mate_out, int32_t *ed
     const unsigned per_vertex = unsigned((n + 255) / 256);
     const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
     hipLaunchKernelGGL(k_match_init, dim3(per_vertex), dim3(256), 0, s, n, mate, cand);
-    hipLaunchKernelGGL(k_match_classify, dim3(sweep), dim3(256), 0, s, n, g->off, short_row, wave_row, wg_row, l, ctrl);
-    launches += 2;
+    ++launches;
+    classify_rows<true>(g, bounds, l, ctrl->count[0], &ctrl->error, cus, s, &launches);
     MatchCtrl h;
     GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
     GMSX_HIP(hipStreamSynchronize(s));
@@ -448,19 +393,14 @@ int matching(const gmsx_graph *g, uint32_t flags, int32_t *mate_out, int32_t *ed
     int cur = 0;
     int64_t rounds = 0;
     for (;;) {
-        int64_t live = 0;
-        for (int b = 0; b < 4; ++b) {
-            if (h.count[cur][b] < 0 || int64_t(h.count[cur][b]) > l.cap[b]) return GMSX_ERR_KERNEL;
-            live += h.count[cur][b];
-        }
+        const int64_t live = live_count(h.count[cur], l);
+        if (live < 0) return GMSX_ERR_KERNEL;
         if (live == 0) break;  // no vertex has a candidate left
         if (rounds > n / 2 + 1) return GMSX_ERR_KERNEL;
         GMSX_HIP(hipMemsetAsync(&ctrl->took, 0, sizeof(int32_t), s));
         GMSX_HIP(hipMemsetAsync(&ctrl->count[cur ^ 1][0], 0, 4 * sizeof(int32_t), s));
-        search_rows<1>(g, wgt, l, cur, 0, h.count[cur][0], 16, keep, mate, cand, candw, ctrl, &launches);
-        search_rows<kGroup>(g, wgt, l, cur, 1, h.count[cur][1], 32, keep, mate, cand, candw, ctrl, &launches);
-        search_rows<64>(g, wgt, l, cur, 2, h.count[cur][2], 32, keep, mate, cand, candw, ctrl, &launches);
-        search_rows<256>(g, wgt, l, cur, 3, h.count[cur][3], 8, keep, mate, cand, candw, ctrl, &launches);
+        auto search = [&](int) { return MatchSearch{g->off, g->adj, wgt, mate, keep, cand, candw}; };
+        launch_live_rows(search, l, cur, ctrl->count[cur], h.count[cur], &ctrl->examined, cus, s, &launches);
         const unsigned over_live = unsigned(std::max<int64_t>(1, std::min<int64_t>((live + 255) / 256, int64_t(cus) * 16)));
         hipLaunchKernelGGL(k_match_pair, dim3(over_live), dim3(256), 0, s, l, cur, cand, mate, ctrl);
         ++launches;
@@ -505,30 +445,15 @@ int matching(const gmsx_graph *g, uint32_t flags, int32_t *mate_out, int32_t *ed
     res.rounds = int32_t(rounds);
     // the flag words were read as zero: the caller's arrays are written now, through host staging
     const size_t ne = size_t(res.pairs);
-    std::vector<int32_t> h_mate, h_eu, h_ev, h_ew;
-    if (mate_out) {
-        h_mate.resize(size_t(n));
-        GMSX_HIP(hipMemcpyAsync(h_mate.data(), mate, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    if (want_edges && ne > 0) {
-        h_eu.resize(ne);
-        h_ev.resize(ne);
-        h_ew.resize(ne);
-        GMSX_HIP(hipMemcpyAsync(h_eu.data(), d_eu.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipMemcpyAsync(h_ev.data(), d_ev.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipMemcpyAsync(h_ew.data(), d_ew.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
+    HostStage out;
+    if (int rc = out.fetch(mate_out, mate, size_t(n) * sizeof(int32_t), s)) return rc;
+    if (int rc = out.fetch_edges(edge_u, edge_v, edge_w, d_eu, d_ev, d_ew, ne, s)) return rc;
     GMSX_HIP(hipStreamSynchronize(s));
     float up_ms = 0.f, ms = 0.f, info_ms = 0.f;
     GMSX_HIP(hipEventElapsedTime(&up_ms, c.ev[0], c.ev[1]));
     GMSX_HIP(hipEventElapsedTime(&ms, c.ev[1], c.ev[2]));
     GMSX_HIP(hipEventElapsedTime(&info_ms, c.ev[2], c.ev[3]));
-    if (mate_out) std::memcpy(mate_out, h_mate.data(), size_t(n) * sizeof(int32_t));
-    if (!h_eu.empty()) {
-        std::memcpy(edge_u, h_eu.data(), ne * sizeof(int32_t));
-        std::memcpy(edge_v, h_ev.data(), ne * sizeof(int32_t));
-        std::memcpy(edge_w, h_ew.data(), ne * sizeof(int32_t));
-    }
+    out.deliver();
     *info = res;
     if (stats) *stats = gmsx_stats{double(ms), double(up_ms) + double(info_ms), uint64_t(res.pairs), uint64_t(h.examined), uint64_t(rounds), launches, 0, 0};
     return GMSX_OK;

@@ -11,10 +11,10 @@
 //
 // A ROUND is four steps with kernel boundaries between them; nothing spins and no workgroup waits for another.  comp = the parent array of
 // union_find.hpp, flattened: comp[v] is the root of v's component, read with plain loads (an earlier kernel wrote it).
-//   (a) search   k_msf_search<WIDTH>, THE HOT PASS: every live vertex v finds the first arc j of its row in the order with comp[adj[j]] !=
-//                comp[v] (the weight is loaded for crossing arcs only).  Rows are binned by their length as k_cc_link's: a lane per row below
-//                kMsfShortRow entries, a 16-lane group below MSF_WAVE_ROW, a wave below MSF_WG_ROW, a whole workgroup from there on — no lane
-//                walks a long row alone.  The result goes to best[v] and root[v], one writer each, and the writer folds k0 into the
+//   (a) search   MsfSearch, THE HOT PASS: every live vertex v finds the first arc j of its row in the order with comp[adj[j]] != comp[v]
+//                (the weight is loaded for crossing arcs only).  It is the Op of row_classes.hpp's live-list row pass: a lane, a 16-lane
+//                group, a wave or a workgroup per row by its length (the bounds are MSF_WAVE_ROW and MSF_WG_ROW) — no lane walks a long
+//                row alone.  The result goes to best[v] and root[v], one writer each, and the writer folds k0 into the
 //                component's word with an integer atomicMin (cw[root]; for the maximum that is the atomicMax of w).  A vertex that finds no
 //                crossing arc is dead for good — components only merge.  Under MSF_PRUNE = 1 it is not appended to the next round's live list, so
 //                that later rounds touch the shrinking border only; under MSF_PRUNE = 0, THE DEFAULT, the lists stay as classified and every
@@ -42,27 +42,21 @@
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
 #include "frontier_rounds.hpp"  // load_now, wave_append, append_checked, RowGroup, kGroup, kLongRow
+#include "row_classes.hpp"
 #include "union_find.hpp"
 
 #include <algorithm>
 #include <climits>
 #include <cstdio>
 #include <cstring>
-#include <vector>
 
 namespace gmsx {
 
 namespace {
 
-constexpr int kMsfShortRow = 16;  // rows below this: one lane
 constexpr int kMsfMaxRounds = 64;
-constexpr long long kMsfWaveRowDefault = 256, kMsfWgRowDefault = 4096;  // first guesses (gmsx.h, OPTIONS)
 constexpr long long kMsfPruneDefault = 0;  // measured: the live lists cost more than they save on every graph tried
 constexpr unsigned long long kNoArc = ~0ull;
-
-__device__ __forceinline__ unsigned long long load_now(const unsigned long long *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // the call's small device block, mirrored to the host after every round
 struct MsfCtrl {
@@ -70,14 +64,8 @@ struct MsfCtrl {
     int32_t again;       // flatten: a walk ended below its root (behind error: union_find.hpp's flatten reads the two words together)
     int32_t picks;       // winners of the round (an edge two components picked counts twice)
     int32_t pad;
-    int32_t count[2][4];  // vertices in the lane / group / wave / workgroup list of either buffer
+    int32_t count[2][4];  // vertices in the lane / group / wave / workgroup list of either buffer (row_classes.hpp)
     unsigned long long examined;  // arcs the search pass looked at
-};
-
-// the four live lists: list b of buffer i is lists[i] + base[b], at most cap[b] entries
-struct MsfLists {
-    int32_t *buf[2];
-    int64_t base[4], cap[4];
 };
 
 // the info pass's words
@@ -97,41 +85,24 @@ __global__ void k_msf_init(int64_t n, int32_t *__restrict__ parent, int32_t *__r
     }
 }
 
-// every vertex with an arc into the list of its row class (whole waves stay converged for the ballots)
-__global__ __launch_bounds__(256) void k_msf_classify(int64_t n, const int64_t *__restrict__ off, int64_t short_row, int64_t wave_row, int64_t wg_row,
-                                                      MsfLists l, MsfCtrl *__restrict__ ctrl) {
-    const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-    const int64_t end = ((n + 63) / 64) * 64;
-    for (int64_t v = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; v < end; v += stride) {
-        const int64_t d = v < n ? off[v + 1] - off[v] : 0;
-        wave_append(d >= 1 && d < short_row, int32_t(v), l.buf[0] + l.base[0], &ctrl->count[0][0], l.cap[0], &ctrl->error);
-        wave_append(d >= short_row && d < wave_row, int32_t(v), l.buf[0] + l.base[1], &ctrl->count[0][1], l.cap[1], &ctrl->error);
-        wave_append(d >= wave_row && d < wg_row, int32_t(v), l.buf[0] + l.base[2], &ctrl->count[0][2], l.cap[2], &ctrl->error);
-        wave_append(d >= wg_row && d >= 1, int32_t(v), l.buf[0] + l.base[3], &ctrl->count[0][3], l.cap[3], &ctrl->error);
-    }
-}
-
-// (a) THE HOT PASS: WIDTH lanes (1, kGroup, 64, or the 256 threads of the workgroup) per live row of list `which` of buffer `cur`.
-// flip = 0 (minimum) or ~0 (maximum): k0 = w ^ flip.  next != nullptr: a vertex that found a crossing arc is appended to the next live list.
-template <int WIDTH>
-__global__ __launch_bounds__(256) void k_msf_search(const int64_t *__restrict__ off, const int32_t *__restrict__ adj, const int32_t *__restrict__ wgt,
-                                                    const int32_t *__restrict__ comp, const int32_t *__restrict__ list, int32_t *__restrict__ next,
-                                                    int cur, int which, int64_t list_cap, uint32_t flip, unsigned long long *__restrict__ best,
-                                                    int32_t *__restrict__ root, uint32_t *__restrict__ cw, MsfCtrl *__restrict__ ctrl) {
-    constexpr int kLanes = WIDTH > 64 ? 64 : WIDTH;  // lanes of one wave that share a row
-    constexpr int kUnit = WIDTH > 64 ? WIDTH : 64;   // threads that go through the row loop together: the wave, or the workgroup
-    __shared__ unsigned long long s_min[4];
-    const int lane = threadIdx.x & (WIDTH - 1);
-    const int64_t first = ((int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / kUnit) * (kUnit / WIDTH);
-    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
-    const int64_t rows = min(int64_t(ctrl->count[cur][which]), list_cap);
-    unsigned long long examined = 0;
-    // a wave takes 64 / WIDTH consecutive rows at a time and stays together (its appends are one atomic, and the next list keeps runs of
-    // the order of this one); WIDTH = 256: a row per workgroup, whose barriers the loop passes
-    for (int64_t base = first; base < rows; base += rows_step) {
-        const int64_t i = base + (threadIdx.x & (kUnit - 1)) / WIDTH;
-        const bool active = i < rows;
-        const int32_t v = active ? list[i] : 0;
+// (a) THE HOT PASS, the Op of a live-list row pass: WIDTH lanes (1, kGroup, 64, or the 256 threads of the workgroup) per live row.
+// flip = 0 (minimum) or ~0 (maximum): k0 = w ^ flip.  next != nullptr: a vertex that found a crossing arc is appended to the next live list
+// of its class (next_count, at most next_cap entries).
+struct MsfSearch {
+    const int64_t *off;
+    const int32_t *adj, *wgt, *comp;
+    int32_t *next, *next_count;
+    int64_t next_cap;
+    uint32_t flip;
+    unsigned long long *best;
+    int32_t *root;
+    uint32_t *cw;
+    int32_t *error;
+    template <int WIDTH>
+    __device__ __forceinline__ unsigned long long row(int32_t v, bool active, int lane) const {
+        constexpr int kLanes = WIDTH > 64 ? 64 : WIDTH;  // lanes of one wave that share a row
+        __shared__ unsigned long long s_min[4];
+        unsigned long long examined = 0;
         const int32_t cv = active ? comp[v] : 0;
         const int64_t j1 = active ? off[v + 1] : 0;
         unsigned long long mine = kNoArc;
@@ -159,15 +130,14 @@ __global__ __launch_bounds__(256) void k_msf_search(const int64_t *__restrict__ 
         }
         if (next) {
             if (WIDTH > 64) {
-                if (found) append_checked(next, &ctrl->count[cur ^ 1][which], list_cap, v, &ctrl->error);
+                if (found) append_checked(next, next_count, next_cap, v, error);
             } else {
-                wave_append(found, v, next, &ctrl->count[cur ^ 1][which], list_cap, &ctrl->error);
+                wave_append(found, v, next, next_count, next_cap, error);
             }
         }
+        return examined;
     }
-    examined = wave_sum(examined);
-    if ((threadIdx.x & 63) == 0 && examined) atomicAdd(&ctrl->examined, examined);
-}
+};
 
 // lo << 32 | hi of the arc v - x
 __device__ __forceinline__ unsigned long long msf_pair(int32_t v, int32_t x) {
@@ -175,13 +145,13 @@ __device__ __forceinline__ unsigned long long msf_pair(int32_t v, int32_t x) {
 }
 
 // (b) the live vertices whose weight word is their component's fold (lo, hi) into the component's pair
-__global__ __launch_bounds__(256) void k_msf_pair(MsfLists l, int cur, const unsigned long long *__restrict__ best, const int32_t *__restrict__ root,
+__global__ __launch_bounds__(256) void k_msf_pair(RowLists l, int cur, const unsigned long long *__restrict__ best, const int32_t *__restrict__ root,
                                                   const uint32_t *__restrict__ cw, unsigned long long *__restrict__ cpair,
                                                   const MsfCtrl *__restrict__ ctrl) {
     const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, stride = int64_t(gridDim.x) * blockDim.x;
     for (int b = 0; b < 4; ++b) {
-        const int32_t *list = l.buf[cur] + l.base[b];
-        const int64_t rows = min(int64_t(ctrl->count[cur][b]), l.cap[b]);
+        const int32_t *list = l.list(cur, b);
+        const int64_t rows = l.rows(ctrl->count[cur], b);
         for (int64_t i = tid; i < rows; i += stride) {
             const int32_t v = list[i];
             const unsigned long long mine = best[v];
@@ -195,16 +165,16 @@ __global__ __launch_bounds__(256) void k_msf_pair(MsfLists l, int cur, const uns
 }
 
 // (c) the winner of every component marks both arcs of its edge, links its ends and counts the pick
-__global__ __launch_bounds__(256) void k_msf_apply(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj, MsfLists l, int cur,
+__global__ __launch_bounds__(256) void k_msf_apply(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj, RowLists l, int cur,
                                                    const unsigned long long *__restrict__ best, const int32_t *__restrict__ root,
                                                    const uint32_t *__restrict__ cw, const unsigned long long *__restrict__ cpair,
                                                    int32_t *__restrict__ parent, uint8_t *__restrict__ mask, MsfCtrl *__restrict__ ctrl) {
     const int64_t tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, stride = int64_t(gridDim.x) * blockDim.x;
-    const uint32_t cap = uint32_t(min(n + 64, int64_t(INT_MAX)));
+    const uint32_t cap = cc_walk_cap(n);
     int32_t picks = 0;
     for (int b = 0; b < 4; ++b) {
-        const int32_t *list = l.buf[cur] + l.base[b];
-        const int64_t rows = min(int64_t(ctrl->count[cur][b]), l.cap[b]);
+        const int32_t *list = l.list(cur, b);
+        const int64_t rows = l.rows(ctrl->count[cur], b);
         for (int64_t i = tid; i < rows; i += stride) {
             const int32_t v = list[i];
             const unsigned long long mine = best[v];
@@ -330,20 +300,6 @@ __global__ __launch_bounds__(256) void k_msf_info(int64_t n, const int32_t *__re
     }
 }
 
-// (a) over list b of buffer cur, `rows` entries: WIDTH lanes per row, at most per_cu workgroups per compute unit; nxt == cur: no pruning.
-// comp is the parent array, flat between the rounds.
-template <int WIDTH>
-void search_rows(const gmsx_graph *g, const MsfLists &l, int cur, int nxt, int b, int64_t rows, int per_cu, uint32_t flip, const int32_t *comp,
-                 unsigned long long *best, int32_t *root, uint32_t *cw, MsfCtrl *ctrl, int *launches) {
-    if (rows <= 0) return;
-    Ctx &c = ctx();
-    const int cus = c.compute_units > 0 ? c.compute_units : 256;
-    const unsigned grid = unsigned(std::min<int64_t>((rows * WIDTH + 255) / 256, int64_t(cus) * per_cu));
-    hipLaunchKernelGGL((k_msf_search<WIDTH>), dim3(grid), dim3(256), 0, c.stream, g->off, g->adj, g->wgt.as<const int32_t>(), comp, l.buf[cur] + l.base[b],
-                       nxt != cur ? l.buf[nxt] + l.base[b] : (int32_t *)nullptr, cur, b, l.cap[b], flip, best, root, cw, ctrl);
-    ++*launches;
-}
-
 int msf(const gmsx_graph *g, uint32_t flags, int32_t *edge_u, int32_t *edge_v, int32_t *edge_w, uint8_t *arc_keep, int32_t *label, gmsx_msf_info *info,
         gmsx_stats *stats) {
     gmsx_msf_info res;
@@ -361,30 +317,19 @@ int msf(const gmsx_graph *g, uint32_t flags, int32_t *edge_u, int32_t *edge_v, i
     hipStream_t s = c.stream;
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
     // test hooks, first guesses
-    const int64_t wave_row = std::max<long long>(1, std::min<long long>(opt_int("MSF_WAVE_ROW", kMsfWaveRowDefault), INT_MAX));
-    const int64_t wg_row = std::max<long long>(wave_row, std::min<long long>(opt_int("MSF_WG_ROW", kMsfWgRowDefault), INT_MAX));
+    const RowBounds bounds = row_bounds("MSF_WAVE_ROW", "MSF_WG_ROW");
     const bool prune = opt_int("MSF_PRUNE", kMsfPruneDefault) != 0;
     const bool timing = opt_on("TIMING");  // one line per round on stderr: its live vertices, the arcs it examined, its winners
-    const int64_t short_row = std::min<int64_t>(kMsfShortRow, wave_row);
     const uint32_t flip = (flags & GMSX_MSF_MAXIMUM) ? ~0u : 0u;
     const bool want_edges = edge_u != nullptr;
-    MsfLists l;
-    const int64_t bound[4] = {1, short_row, wave_row, wg_row};  // the shortest row of every list
-    int64_t total = 0;
-    for (int b = 0; b < 4; ++b) {
-        l.base[b] = total;
-        l.cap[b] = std::min<int64_t>(n, nnz / bound[b] + 1);
-        total += l.cap[b];
-    }
+    RowListStore lists;
     // ---- setup: the buffers
-    DevBuf d_parent, d_root, d_size, d_list0, d_list1, d_best, d_comp, d_mask, d_ctrl, d_acc, d_cnt, d_pos, d_eu, d_ev, d_ew;
+    DevBuf d_parent, d_root, d_size, d_best, d_comp, d_mask, d_ctrl, d_acc, d_cnt, d_pos, d_eu, d_ev, d_ew;
     GMSX_HIP(hipEventRecord(c.ev[0], s));
     if (int rc = dalloc<int32_t>(d_parent, n)) return rc;
     if (int rc = dalloc<int32_t>(d_root, n)) return rc;
     if (int rc = dalloc<int32_t>(d_size, n)) return rc;
-    if (int rc = dalloc<int32_t>(d_list0, total)) return rc;
-    if (prune)
-        if (int rc = dalloc<int32_t>(d_list1, total)) return rc;
+    if (int rc = lists.alloc(n, nnz, bounds, true, prune)) return rc;
     if (int rc = dalloc<unsigned long long>(d_best, n)) return rc;
     if (int rc = dalloc<uint32_t>(d_comp, 3 * n)) return rc;  // cpair: n 64-bit words, then cw: n 32-bit words
     if (int rc = dalloc<uint8_t>(d_mask, nnz)) return rc;
@@ -397,8 +342,7 @@ int msf(const gmsx_graph *g, uint32_t flags, int32_t *edge_u, int32_t *edge_v, i
         if (int rc = dalloc<int32_t>(d_ev, n - 1)) return rc;
         if (int rc = dalloc<int32_t>(d_ew, n - 1)) return rc;
     }
-    l.buf[0] = d_list0.as<int32_t>();
-    l.buf[1] = prune ? d_list1.as<int32_t>() : d_list0.as<int32_t>();
+    const RowLists &l = lists.l;
     MsfCtrl *ctrl = d_ctrl.as<MsfCtrl>();
     MsfAcc *acc = d_acc.as<MsfAcc>();
     int32_t *parent = d_parent.as<int32_t>();
@@ -418,8 +362,8 @@ int msf(const gmsx_graph *g, uint32_t flags, int32_t *edge_u, int32_t *edge_v, i
     const unsigned per_vertex = unsigned((n + 255) / 256);
     const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
     hipLaunchKernelGGL(k_msf_init, dim3(per_vertex), dim3(256), 0, s, n, parent, d_size.as<int32_t>());
-    hipLaunchKernelGGL(k_msf_classify, dim3(sweep), dim3(256), 0, s, n, g->off, short_row, wave_row, wg_row, l, ctrl);
-    launches += 2;
+    ++launches;
+    classify_rows<true>(g, bounds, l, ctrl->count[0], &ctrl->error, cus, s, &launches);
     MsfCtrl h;
     GMSX_HIP(hipMemcpyAsync(&h, ctrl, sizeof h, hipMemcpyDeviceToHost, s));
     GMSX_HIP(hipStreamSynchronize(s));
@@ -427,21 +371,20 @@ int msf(const gmsx_graph *g, uint32_t flags, int32_t *edge_u, int32_t *edge_v, i
     int cur = 0;
     int32_t rounds = 0;
     for (;;) {
-        int64_t live = 0;
-        for (int b = 0; b < 4; ++b) {
-            if (h.count[cur][b] < 0 || int64_t(h.count[cur][b]) > l.cap[b]) return GMSX_ERR_KERNEL;
-            live += h.count[cur][b];
-        }
+        const int64_t live = live_count(h.count[cur], l);
+        if (live < 0) return GMSX_ERR_KERNEL;
         if (live == 0) break;  // no vertex has a crossing arc left
         if (rounds >= kMsfMaxRounds) return GMSX_ERR_KERNEL;
         const int nxt = prune ? cur ^ 1 : cur;
         GMSX_HIP(hipMemsetAsync(d_comp.p, 0xff, size_t(n) * 12, s));
         GMSX_HIP(hipMemsetAsync(&ctrl->picks, 0, sizeof(int32_t), s));
         if (prune) GMSX_HIP(hipMemsetAsync(&ctrl->count[nxt][0], 0, 4 * sizeof(int32_t), s));
-        search_rows<1>(g, l, cur, nxt, 0, h.count[cur][0], 16, flip, parent, best, root, cw, ctrl, &launches);
-        search_rows<kGroup>(g, l, cur, nxt, 1, h.count[cur][1], 32, flip, parent, best, root, cw, ctrl, &launches);
-        search_rows<64>(g, l, cur, nxt, 2, h.count[cur][2], 32, flip, parent, best, root, cw, ctrl, &launches);
-        search_rows<256>(g, l, cur, nxt, 3, h.count[cur][3], 8, flip, parent, best, root, cw, ctrl, &launches);
+        // comp is the parent array, flat between the rounds; nxt == cur: no pruning
+        auto search = [&](int b) {
+            return MsfSearch{g->off, g->adj, wgt, parent, prune ? l.buf[nxt] + l.base[b] : nullptr, &ctrl->count[nxt][b], l.cap[b], flip,
+                             best, root, cw, &ctrl->error};
+        };
+        launch_live_rows(search, l, cur, ctrl->count[cur], h.count[cur], &ctrl->examined, cus, s, &launches);
         const unsigned over_live = unsigned(std::max<int64_t>(1, std::min<int64_t>((live + 255) / 256, int64_t(cus) * 16)));
         hipLaunchKernelGGL(k_msf_pair, dim3(over_live), dim3(256), 0, s, l, cur, best, root, cw, cpair, ctrl);
         hipLaunchKernelGGL(k_msf_apply, dim3(over_live), dim3(256), 0, s, n, g->off, g->adj, l, cur, best, root, cw, cpair, parent,
@@ -497,36 +440,16 @@ int msf(const gmsx_graph *g, uint32_t flags, int32_t *edge_u, int32_t *edge_v, i
     res.rounds = rounds;
     // the flag words were read as zero: the caller's arrays are written now, through host staging
     const size_t ne = size_t(res.edges);
-    std::vector<int32_t> h_label, h_eu, h_ev, h_ew;
-    std::vector<uint8_t> h_mask;
-    if (label) {
-        h_label.resize(size_t(n));
-        GMSX_HIP(hipMemcpyAsync(h_label.data(), parent, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    if (arc_keep) {
-        h_mask.resize(size_t(nnz));
-        GMSX_HIP(hipMemcpyAsync(h_mask.data(), d_mask.p, size_t(nnz), hipMemcpyDeviceToHost, s));
-    }
-    if (want_edges && ne > 0) {
-        h_eu.resize(ne);
-        h_ev.resize(ne);
-        h_ew.resize(ne);
-        GMSX_HIP(hipMemcpyAsync(h_eu.data(), d_eu.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipMemcpyAsync(h_ev.data(), d_ev.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        GMSX_HIP(hipMemcpyAsync(h_ew.data(), d_ew.p, ne * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
+    HostStage out;
+    if (int rc = out.fetch(label, parent, size_t(n) * sizeof(int32_t), s)) return rc;
+    if (int rc = out.fetch(arc_keep, d_mask.p, size_t(nnz), s)) return rc;
+    if (int rc = out.fetch_edges(edge_u, edge_v, edge_w, d_eu, d_ev, d_ew, ne, s)) return rc;
     GMSX_HIP(hipStreamSynchronize(s));
     float up_ms = 0.f, ms = 0.f, info_ms = 0.f;
     GMSX_HIP(hipEventElapsedTime(&up_ms, c.ev[0], c.ev[1]));
     GMSX_HIP(hipEventElapsedTime(&ms, c.ev[1], c.ev[2]));
     GMSX_HIP(hipEventElapsedTime(&info_ms, c.ev[2], c.ev[3]));
-    if (label) std::memcpy(label, h_label.data(), size_t(n) * sizeof(int32_t));
-    if (arc_keep) std::memcpy(arc_keep, h_mask.data(), size_t(nnz));
-    if (!h_eu.empty()) {
-        std::memcpy(edge_u, h_eu.data(), ne * sizeof(int32_t));
-        std::memcpy(edge_v, h_ev.data(), ne * sizeof(int32_t));
-        std::memcpy(edge_w, h_ew.data(), ne * sizeof(int32_t));
-    }
+    out.deliver();
     *info = res;
     if (stats) *stats = gmsx_stats{double(ms), double(up_ms) + double(info_ms), uint64_t(res.edges), uint64_t(h.examined), uint64_t(rounds), launches, 0, 0};
     return GMSX_OK;

@@ -25,12 +25,16 @@
 #include "frontier_rounds.hpp"  // load_now, store_now
 
 #include <algorithm>
+#include <climits>
 
 namespace gmsx {
 namespace {
 
 constexpr int kCcJump = 64;        // steps of one flatten walk
 constexpr int kCcFlattenMax = 64;  // flatten rounds before the call gives up (every round divides the depth by kCcJump)
+
+// the cap of both loops for a parent array of n words: what cc_find and cc_link are given
+__host__ __device__ __forceinline__ uint32_t cc_walk_cap(int64_t n) { return uint32_t(n + 64 < int64_t(INT_MAX) ? n + 64 : int64_t(INT_MAX)); }
 
 // root of x; compresses by halving on the way (atomicMin: other threads hook and compress the same words, and parents only decrease)
 __device__ __forceinline__ int32_t cc_find(int32_t *__restrict__ parent, int32_t x, uint32_t cap, int32_t *error) {
