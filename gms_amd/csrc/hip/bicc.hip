@@ -27,7 +27,7 @@
 //               a root v).  Flatten.  The block of arc {v, w} is the set of its end with the larger pre.
 //   7 ids       OpFirst: first[set] = the smallest `u < v` arc index of the set (64-bit atomicMin behind a read of the word, which only
 //               falls) and edges[set] (a lane adds a run of arcs of one set with one atomic: a giant block costs a few adds per lane).  Per
-//               row the arcs that are their set's first are counted (k_bicc_rank<false>), the counts scanned, and k_bicc_rank<true> gives
+//               row the arcs that are their set's first are counted (BiccRank<false>), the counts scanned, and BiccRank<true> gives
 //               every set the rank of its first arc: ids ascend with each block's smallest edge in CSR order.  k_cc_sizes counts the tree
 //               edges of a set; its vertices are that + 1 (the tree edges of a block are a subtree), and a set of one tree edge is a bridge.
 //   8 blocks_at a child c is AT THE TOP of its block iff its parent is a root or the parent's own tree edge lies in another set; top[set] =
@@ -35,7 +35,7 @@
 //   9 info      one reduction over the vertices, then the largest block's id and vertices among the sets with the most edges.
 //  10 outputs   only when asked for: OpOut writes block[j] and arc_keep[j] for every arc (4 + 1 bytes per arc, device memory of the call).
 // THE ROW PASSES are row_classes.hpp's (a lane, a 16-lane group, a wave or a workgroup per row by its length; the bounds are BCC_WAVE_ROW and
-// BCC_WG_ROW); the five Ops below say what an arc means in each.
+// BCC_WG_ROW); the five Ops below say what an arc means in each.  BiccRank needs a row's CSR order and is an Op of its two-width pass.
 // THE SWEEPS BY LEVEL (steps 3, 4, 5; k_bicc_sweep<Op>) do not cost a launch per level on a deep forest: consecutive levels that each hold at
 // most BCC_WG_LEVEL vertices are swept by ONE workgroup in one launch with a __syncthreads() between levels; what one level writes and the next
 // reads goes through atomics, store_now and load_now (frontier_rounds.hpp; the note at the top of union_find.hpp).  A larger level is a grid-wide
@@ -46,7 +46,7 @@
 // frontiers: DevBufs of the call; the handle is not touched.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
-#include "frontier_rounds.hpp"  // the engine, load_now, store_now, RowGroup, kGroup, kLongRow
+#include "frontier_rounds.hpp"  // the engine, load_now, store_now, RowGroup, kGroup
 #include "row_classes.hpp"
 #include "union_find.hpp"
 #include "wave_ops.hpp"
@@ -395,31 +395,32 @@ __global__ __launch_bounds__(256) void k_bicc_ids_init(int64_t n, BiccArrays a) 
     a.cnt[v] = 0;
 }
 
-// step 7: the `u < v` arcs of row u that are their set's first: counted into cnt[u] (one writer), or ranked from pos[u] on.  WIDTH lanes per
-// row: kGroup up to kLongRow entries, 64 beyond; a ballot per chunk keeps the CSR order.
-template <bool kAssign, int WIDTH>
-__global__ __launch_bounds__(256) void k_bicc_rank(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj, BiccArrays a,
-                                                   BiccAcc *__restrict__ acc) {
-    const RowGroup<WIDTH> grp;
-    const int lane = grp.lane;
-    const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
-    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
-    unsigned long long examined = 0;
-    for (int64_t u = row0; u < n; u += rows_step) {  // (uniform in the group: its lanes leave together)
-        const int64_t j0 = off[u], j1 = off[u + 1];
-        if (j1 == j0 || (j1 - j0 > kLongRow) != (WIDTH == 64)) continue;
+// step 7: the `u < v` arcs of row u that are their set's first: counted into cnt[u] (one writer), or ranked from pos[u] on.  An Op of
+// row_classes.hpp's two-width pass; a ballot per chunk keeps the CSR order (the row's lanes leave together).
+template <bool kAssign>
+struct BiccRank {
+    const int32_t *adj;
+    BiccArrays a;
+    int64_t n;
+    BiccAcc *acc;
+    __device__ __forceinline__ void begin() {}
+    template <int kLanes>
+    __device__ __forceinline__ unsigned long long row(int32_t u, int64_t j0, int64_t j1, int lane, int width) {
+        const RowGroup<kLanes> grp;
+        if (j1 == j0) return 0;
         int64_t at = kAssign ? a.pos[u] : 0;
-        if (kAssign && at == a.pos[u + 1]) continue;
+        if (kAssign && at == a.pos[u + 1]) return 0;
+        unsigned long long examined = 0;
         const int32_t pu = a.pre[u];
-        for (int64_t c = j0; c < j1; c += WIDTH) {
+        for (int64_t c = j0; c < j1; c += width) {
             const int64_t j = c + lane;
             bool take = false;
             int32_t s = 0;
             if (j < j1) {
                 ++examined;
                 const int32_t w = adj[j];
-                if (int64_t(w) > u) {
-                    s = bicc_set(a.aux, a.pre, int32_t(u), pu, w);
+                if (w > u) {
+                    s = bicc_set(a.aux, a.pre, u, pu, w);
                     take = a.first[s] == (unsigned long long)j;
                 }
             }
@@ -432,10 +433,10 @@ __global__ __launch_bounds__(256) void k_bicc_rank(int64_t n, const int64_t *__r
             at += __popcll(hits);
         }
         if (!kAssign && lane == 0) a.cnt[u] = at;
+        return examined;
     }
-    examined = wave_sum(examined);
-    if ((threadIdx.x & 63) == 0 && examined) atomicAdd(&acc->examined, examined);
-}
+    __device__ __forceinline__ void finish() {}
+};
 
 // step 8: top[set] = the smallest child at the top of its block …
 __global__ __launch_bounds__(256) void k_bicc_top(int64_t n, BiccArrays a) {
@@ -600,7 +601,7 @@ int bicc(const gmsx_graph *g, int32_t *block, int32_t *blocks_at, uint8_t *arc_k
     GMSX_HIP(hipEventRecord(c.ev[1], s));
     int launches = 0;
     const unsigned per_vertex = unsigned((n + 256) / 256);  // n + 1 threads
-    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    const unsigned sweep = row_grid(n, 1, cus, 16);
     const uint32_t cap = cc_walk_cap(n);
     double phase_ms[7] = {0, 0, 0, 0, 0, 0, 0};  // roots, forest, nd, preorder, low / high, arc passes, ids
     auto t0 = std::chrono::steady_clock::now();
@@ -672,16 +673,11 @@ int bicc(const gmsx_graph *g, int32_t *block, int32_t *blocks_at, uint8_t *arc_k
     ++launches;
     rows(OpFirst{g->adj, a.pre, a.aux, a.first, a.edges, acc, -1, 0, 0, 0});
     if (int rc = phase_end(5)) return rc;
-    const unsigned grid16 = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
-    const unsigned grid64 = unsigned(std::min<int64_t>((n * 64 + 255) / 256, int64_t(cus) * 8));
-    const bool long_rows = g->max_deg > kLongRow;
-    hipLaunchKernelGGL((k_bicc_rank<false, kGroup>), dim3(grid16), dim3(256), 0, s, n, g->off, g->adj, a, acc);
-    if (long_rows) hipLaunchKernelGGL((k_bicc_rank<false, 64>), dim3(grid64), dim3(256), 0, s, n, g->off, g->adj, a, acc);
+    launch_rows_two_width(BiccRank<false>{g->adj, a, n, acc}, g, &acc->examined, cus, s, &launches);
     // (pos is cbase's buffer: the scan reads cnt = kids' buffer)
     if (int rc = exclusive_scan_i64(a.cnt, a.pos, n + 1, s)) return rc;
-    hipLaunchKernelGGL((k_bicc_rank<true, kGroup>), dim3(grid16), dim3(256), 0, s, n, g->off, g->adj, a, acc);
-    if (long_rows) hipLaunchKernelGGL((k_bicc_rank<true, 64>), dim3(grid64), dim3(256), 0, s, n, g->off, g->adj, a, acc);
-    launches += long_rows ? 5 : 3;
+    ++launches;
+    launch_rows_two_width(BiccRank<true>{g->adj, a, n, acc}, g, &acc->examined, cus, s, &launches);
     // ---- 8, 9: sizes, blocks_at, the info reduction
     hipLaunchKernelGGL(k_cc_sizes, dim3(sweep), dim3(256), 0, s, n, a.aux, a.size);
     hipLaunchKernelGGL(k_bicc_top, dim3(sweep), dim3(256), 0, s, n, a);

@@ -291,7 +291,7 @@ int components(const gmsx_graph *g, int source, const uint8_t *mask_in, int metr
             const int32_t *giant = nullptr;
             if (sample > 0) {
                 hipLaunchKernelGGL((k_rows<Op, 1>), dim3(sweep), dim3(256), 0, s, Op{src, 0, sample, nullptr, parent, g->adj, cc_walk_cap(n), &acc->error}, n,
-                                   g->off, (const int32_t *)nullptr, acc->count, int64_t(0), all, &acc->examined);
+                                   g->off, (const int32_t *)nullptr, acc->count, int64_t(0), int64_t(1), all, &acc->examined);
                 ++launches;
                 if (source == kSrcAll) {  // the skip is valid only where every kept edge is visible from both sides
                     if (int rc = flatten(n, parent, &acc->error, cus, s, &launches, nullptr)) return rc;

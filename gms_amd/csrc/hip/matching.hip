@@ -34,7 +34,7 @@
 // words, up to 3 (n / 2) words of pairs — O(n) words, DevBufs of the call.  The verifier: mate, the valid mate and a key word per vertex.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
-#include "frontier_rounds.hpp"  // wave_append, kGroup, kLongRow
+#include "frontier_rounds.hpp"  // wave_append
 #include "row_classes.hpp"
 #include "union_find.hpp"       // cc_find_in_row
 
@@ -293,42 +293,41 @@ __device__ __forceinline__ bool match_earlier(unsigned long long ka, int32_t a, 
 }
 
 // the verifier, per edge u < x that is not in the (valid) matching: both ends free = augmentable; no adjacent matching edge earlier in the
-// order = undominated.  WIDTH lanes per row: kGroup up to kLongRow entries, 64 beyond
-template <int WIDTH>
-__global__ __launch_bounds__(256) void k_match_check(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                     const int32_t *__restrict__ wgt, const int32_t *__restrict__ eff,
-                                                     const unsigned long long *__restrict__ vkey, MatchCheckAcc *__restrict__ acc) {
-    const int lane = threadIdx.x & (WIDTH - 1);
-    const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
-    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
-    unsigned long long augmentable = 0, undominated = 0;
-    for (int64_t u = row0; u < n; u += rows_step) {
-        const int64_t j0 = off[u], j1 = off[u + 1];
-        if ((j1 - j0 > kLongRow) != (WIDTH == 64)) continue;
+// order = undominated.  An Op of row_classes.hpp's two-width pass
+struct MatchCheck {
+    const int32_t *adj, *wgt, *eff;
+    const unsigned long long *vkey;
+    MatchCheckAcc *acc;
+    unsigned long long augmentable = 0, undominated = 0;  // this thread's sums: begin() sets them
+    __device__ __forceinline__ void begin() { augmentable = undominated = 0; }
+    template <int>
+    __device__ __forceinline__ unsigned long long row(int32_t u, int64_t j0, int64_t j1, int lane, int width) {
         const int32_t mu = eff[u];
         const unsigned long long ku = vkey[u];
-        for (int64_t j = j0 + lane; j < j1; j += WIDTH) {
+        for (int64_t j = j0 + lane; j < j1; j += width) {
             const int32_t x = adj[j];
-            if (int64_t(x) <= u || x == mu) continue;
+            if (x <= u || x == mu) continue;
             const int32_t mx = eff[x];
             if (mu < 0 && mx < 0) {
                 ++augmentable;
                 ++undominated;
                 continue;
             }
-            const unsigned long long k = match_key(int32_t(u), x, wgt ? ~uint32_t(wgt[j]) : 0u);
-            const bool dominated = (mu >= 0 && match_earlier(ku, int32_t(u), mu, k, int32_t(u), x)) ||
-                                   (mx >= 0 && match_earlier(vkey[x], x, mx, k, int32_t(u), x));
+            const unsigned long long k = match_key(u, x, wgt ? ~uint32_t(wgt[j]) : 0u);
+            const bool dominated = (mu >= 0 && match_earlier(ku, u, mu, k, u, x)) || (mx >= 0 && match_earlier(vkey[x], x, mx, k, u, x));
             undominated += !dominated;
         }
+        return 0;
     }
-    augmentable = wave_sum(augmentable);
-    undominated = wave_sum(undominated);
-    if ((threadIdx.x & 63) == 0 && undominated) {
-        atomicAdd(&acc->augmentable, augmentable);
-        atomicAdd(&acc->undominated, undominated);
+    __device__ __forceinline__ void finish() {
+        augmentable = wave_sum(augmentable);
+        undominated = wave_sum(undominated);
+        if ((threadIdx.x & 63) == 0 && undominated) {
+            atomicAdd(&acc->augmentable, augmentable);
+            atomicAdd(&acc->undominated, undominated);
+        }
     }
-}
+};
 
 int matching(const gmsx_graph *g, uint32_t flags, int32_t *mate_out, int32_t *edge_u, int32_t *edge_v, int32_t *edge_w, gmsx_matching_info *info,
              gmsx_stats *stats) {
@@ -382,7 +381,7 @@ int matching(const gmsx_graph *g, uint32_t flags, int32_t *mate_out, int32_t *ed
     GMSX_HIP(hipEventRecord(c.ev[1], s));
     int launches = 0;
     const unsigned per_vertex = unsigned((n + 255) / 256);
-    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    const unsigned sweep = row_grid(n, 1, cus, 16);
     hipLaunchKernelGGL(k_match_init, dim3(per_vertex), dim3(256), 0, s, n, mate, cand);
     ++launches;
     classify_rows<true>(g, bounds, l, ctrl->count[0], &ctrl->error, cus, s, &launches);
@@ -484,18 +483,10 @@ int matching_verify(const gmsx_graph *g, uint32_t flags, const int32_t *mate_in,
     GMSX_HIP(hipMemcpyAsync(d_mate.p, mate_in, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, s));
     GMSX_HIP(hipMemsetAsync(acc, 0, sizeof(MatchCheckAcc), s));
     GMSX_HIP(hipEventRecord(c.ev[1], s));
-    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
-    const unsigned grid16 = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
-    const unsigned grid64 = unsigned(std::min<int64_t>((n * 64 + 255) / 256, int64_t(cus) * 8));
-    const bool long_rows = g->max_deg > kLongRow;
-    hipLaunchKernelGGL(k_match_valid, dim3(sweep), dim3(256), 0, s, n, g->off, g->adj, wgt, d_mate.as<const int32_t>(), d_eff.as<int32_t>(),
+    int launches = 1;
+    hipLaunchKernelGGL(k_match_valid, dim3(row_grid(n, 1, cus, 16)), dim3(256), 0, s, n, g->off, g->adj, wgt, d_mate.as<const int32_t>(), d_eff.as<int32_t>(),
                        d_key.as<unsigned long long>(), acc);
-    hipLaunchKernelGGL((k_match_check<kGroup>), dim3(grid16), dim3(256), 0, s, n, g->off, g->adj, wgt, d_eff.as<const int32_t>(),
-                       d_key.as<const unsigned long long>(), acc);
-    if (long_rows)
-        hipLaunchKernelGGL((k_match_check<64>), dim3(grid64), dim3(256), 0, s, n, g->off, g->adj, wgt, d_eff.as<const int32_t>(),
-                           d_key.as<const unsigned long long>(), acc);
-    const int launches = long_rows ? 3 : 2;
+    launch_rows_two_width(MatchCheck{g->adj, wgt, d_eff.as<const int32_t>(), d_key.as<const unsigned long long>(), acc}, g, nullptr, cus, s, &launches);
     MatchCheckAcc a;
     GMSX_HIP(hipMemcpyAsync(&a, acc, sizeof a, hipMemcpyDeviceToHost, s));
     GMSX_HIP(hipEventRecord(c.ev[2], s));

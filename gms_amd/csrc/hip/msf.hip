@@ -33,15 +33,15 @@
 // and a cycle among one round's picks would need an edge that is not the first of the component that picked it.  Only (lo, hi) keeps unit
 // weights acyclic.  The union-find does not depend on it: a link inside one component changes nothing.
 //
-// AFTER THE ROUNDS.  k_msf_count: per row the marked `u < v` arcs (and, in the same pass, Σ w, min w, max w over them and the marked `u > v`
-// arcs, which must be as many); a scan of the counts; k_msf_fill: every row compacts its marked arcs chunk by chunk with a ballot, in CSR
-// order — the edge list ascends by (u, v) without a sort.  k_cc_sizes and k_msf_info give trees, isolated and largest_tree.  The host checks
-// edges == n - trees before anything is written.
+// AFTER THE ROUNDS.  MsfCount: per row the marked `u < v` arcs (and, in the same pass, Σ w, min w, max w over them and the marked `u > v`
+// arcs, which must be as many); a scan of the counts; MsfFill: every row compacts its marked arcs chunk by chunk with a ballot, in CSR
+// order — the edge list ascends by (u, v) without a sort.  Both are Ops of row_classes.hpp's two-width pass.  k_cc_sizes and k_msf_info give
+// trees, isolated and largest_tree.  The host checks edges == n - trees before anything is written.
 // STATE: parent, root, sizes, the live lists (2 x their capacities, at most 4 n + 6 entries) as 32-bit words, best, cpair, the row counts and
 // their scan as 64-bit words, cw, the nnz-byte mask, and up to 3 (n - 1) words of edges — O(n) words and a byte per arc, DevBufs of the call.
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
-#include "frontier_rounds.hpp"  // load_now, wave_append, append_checked, RowGroup, kGroup, kLongRow
+#include "frontier_rounds.hpp"  // load_now, wave_append, append_checked, RowGroup
 #include "row_classes.hpp"
 #include "union_find.hpp"
 
@@ -196,75 +196,78 @@ __global__ __launch_bounds__(256) void k_msf_apply(int64_t n, const int64_t *__r
     if ((threadIdx.x & 63) == 0 && picks) atomicAdd(&ctrl->picks, picks);
 }
 
-// per row the marked `u < v` arcs into cnt[u] (one writer); Σ w, min w, max w over them and the marked `u > v` arcs into acc.  WIDTH lanes
-// per row: kGroup up to kLongRow entries, 64 beyond
-template <int WIDTH>
-__global__ __launch_bounds__(256) void k_msf_count(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                   const int32_t *__restrict__ wgt, const uint8_t *__restrict__ mask, int64_t *__restrict__ cnt,
-                                                   MsfAcc *__restrict__ acc) {
-    const int lane = threadIdx.x & (WIDTH - 1);
-    const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
-    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
-    unsigned long long upper = 0, lower = 0, weight = 0;
-    uint32_t wmin = ~0u, wmax = 0;
-    for (int64_t u = row0; u < n; u += rows_step) {
-        const int64_t j0 = off[u], j1 = off[u + 1];
-        if ((j1 - j0 > kLongRow) != (WIDTH == 64)) continue;
+// per row the marked `u < v` arcs into cnt[u] (one writer); Σ w, min w, max w over them and the marked `u > v` arcs into acc.  An Op of
+// row_classes.hpp's two-width pass
+struct MsfCount {
+    const int32_t *adj, *wgt;
+    const uint8_t *mask;
+    int64_t *cnt;
+    MsfAcc *acc;
+    unsigned long long upper = 0, lower = 0, weight = 0;  // this thread's sums: begin() sets them
+    uint32_t wmin = 0, wmax = 0;
+    __device__ __forceinline__ void begin() { upper = lower = weight = 0; wmin = ~0u; wmax = 0; }
+    template <int kLanes>
+    __device__ __forceinline__ unsigned long long row(int32_t u, int64_t j0, int64_t j1, int lane, int width) {
         int64_t here = 0;
-        for (int64_t j = j0 + lane; j < j1; j += WIDTH) {
+        unsigned long long low = lower;  // (over the row in a local: counted in the member, the loop keeps a second copy of it, 34 VGPRs for 32)
+        for (int64_t j = j0 + lane; j < j1; j += width) {
             if (!mask[j]) continue;
-            if (int64_t(adj[j]) > u) {
+            if (adj[j] > u) {
                 const uint32_t w = uint32_t(wgt[j]);
                 ++here;
                 weight += w;
                 wmin = min(wmin, w);
                 wmax = max(wmax, w);
             } else {
-                ++lower;
+                ++low;
             }
         }
+        lower = low;
         upper += (unsigned long long)here;
-        here = wave_sum<WIDTH>(here);
+        here = wave_sum<kLanes>(here);
         if (lane == 0) cnt[u] = here;
+        return 0;
     }
-    upper = wave_sum(upper);
-    lower = wave_sum(lower);
-    weight = wave_sum(weight);
-    wmin = wave_min(wmin);
-    wmax = wave_max(wmax);
-    if ((threadIdx.x & 63) == 0 && (upper || lower)) {
-        atomicAdd(&acc->upper, upper);
-        atomicAdd(&acc->lower, lower);
-        atomicAdd(&acc->weight, weight);
-        atomicMin(&acc->wmin, wmin);
-        atomicMax(&acc->wmax, wmax);
+    __device__ __forceinline__ void finish() {
+        upper = wave_sum(upper);
+        lower = wave_sum(lower);
+        weight = wave_sum(weight);
+        wmin = wave_min(wmin);
+        wmax = wave_max(wmax);
+        if ((threadIdx.x & 63) == 0 && (upper || lower)) {
+            atomicAdd(&acc->upper, upper);
+            atomicAdd(&acc->lower, lower);
+            atomicAdd(&acc->weight, weight);
+            atomicMin(&acc->wmin, wmin);
+            atomicMax(&acc->wmax, wmax);
+        }
     }
-}
+};
 
-// the marked `u < v` arcs of row u to the positions pos[u], pos[u] + 1, … in CSR order: a ballot per chunk of the row
-template <int WIDTH>
-__global__ __launch_bounds__(256) void k_msf_fill(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                  const int32_t *__restrict__ wgt, const uint8_t *__restrict__ mask, const int64_t *__restrict__ pos,
-                                                  int64_t cap, int32_t *__restrict__ eu, int32_t *__restrict__ ev, int32_t *__restrict__ ew,
-                                                  MsfAcc *__restrict__ acc) {
-    const RowGroup<WIDTH> grp;
-    const int lane = grp.lane;
-    const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
-    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
-    for (int64_t u = row0; u < n; u += rows_step) {  // (uniform in the group: its lanes leave together)
-        const int64_t j0 = off[u], j1 = off[u + 1];
-        if ((j1 - j0 > kLongRow) != (WIDTH == 64)) continue;
+// the marked `u < v` arcs of row u to the positions pos[u], pos[u] + 1, … in CSR order: a ballot per chunk of the row.  An Op of the
+// two-width pass (the row's lanes leave together)
+struct MsfFill {
+    const int32_t *adj, *wgt;
+    const uint8_t *mask;
+    const int64_t *pos;
+    int64_t cap;
+    int32_t *eu, *ev, *ew;
+    MsfAcc *acc;
+    __device__ __forceinline__ void begin() {}
+    template <int kLanes>
+    __device__ __forceinline__ unsigned long long row(int32_t u, int64_t j0, int64_t j1, int lane, int width) {
+        const RowGroup<kLanes> grp;
         int64_t at = pos[u];
         const int64_t stop = pos[u + 1];
-        if (at == stop) continue;
-        for (int64_t c = j0; c < j1; c += WIDTH) {
+        if (at == stop) return 0;
+        for (int64_t c = j0; c < j1; c += width) {
             const int64_t j = c + lane;
-            const bool take = j < j1 && mask[j] && int64_t(adj[j]) > u;
+            const bool take = j < j1 && mask[j] && adj[j] > u;
             const unsigned long long hits = grp.ballot(take);
             if (take) {
                 const int64_t p = at + __popcll(hits & ((1ull << lane) - 1ull));
                 if (p < stop && p < cap) {
-                    eu[p] = int32_t(u);
+                    eu[p] = u;
                     ev[p] = adj[j];
                     ew[p] = wgt[j];
                 } else {
@@ -274,8 +277,10 @@ __global__ __launch_bounds__(256) void k_msf_fill(int64_t n, const int64_t *__re
             at += __popcll(hits);
         }
         if (at != stop && lane == 0) acc->error = 1;
+        return 0;
     }
-}
+    __device__ __forceinline__ void finish() {}
+};
 
 // per root: trees, isolated vertices (trees of one vertex), the largest tree.  A label that is no root raises the flag.
 __global__ __launch_bounds__(256) void k_msf_info(int64_t n, const int32_t *__restrict__ label, const int32_t *__restrict__ size, MsfAcc *__restrict__ acc) {
@@ -360,7 +365,7 @@ int msf(const gmsx_graph *g, uint32_t flags, int32_t *edge_u, int32_t *edge_v, i
     GMSX_HIP(hipEventRecord(c.ev[1], s));
     int launches = 0;
     const unsigned per_vertex = unsigned((n + 255) / 256);
-    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    const unsigned sweep = row_grid(n, 1, cus, 16);
     hipLaunchKernelGGL(k_msf_init, dim3(per_vertex), dim3(256), 0, s, n, parent, d_size.as<int32_t>());
     ++launches;
     classify_rows<true>(g, bounds, l, ctrl->count[0], &ctrl->error, cus, s, &launches);
@@ -404,23 +409,16 @@ int msf(const gmsx_graph *g, uint32_t flags, int32_t *edge_u, int32_t *edge_v, i
     }
     // ---- the edge list and the info reduction
     GMSX_HIP(hipEventRecord(c.ev[2], s));
-    const unsigned grid16 = unsigned(std::min<int64_t>((n * kGroup + 255) / 256, int64_t(cus) * 32));
-    const unsigned grid64 = unsigned(std::min<int64_t>((n * 64 + 255) / 256, int64_t(cus) * 8));
-    const bool long_rows = g->max_deg > kLongRow;
-    hipLaunchKernelGGL((k_msf_count<kGroup>), dim3(grid16), dim3(256), 0, s, n, g->off, g->adj, wgt, d_mask.as<const uint8_t>(), d_cnt.as<int64_t>(), acc);
-    if (long_rows)
-        hipLaunchKernelGGL((k_msf_count<64>), dim3(grid64), dim3(256), 0, s, n, g->off, g->adj, wgt, d_mask.as<const uint8_t>(), d_cnt.as<int64_t>(), acc);
+    launch_rows_two_width(MsfCount{g->adj, wgt, d_mask.as<const uint8_t>(), d_cnt.as<int64_t>(), acc}, g, nullptr, cus, s, &launches);
     hipLaunchKernelGGL(k_cc_sizes, dim3(sweep), dim3(256), 0, s, n, parent, d_size.as<int32_t>());
     hipLaunchKernelGGL(k_msf_info, dim3(sweep), dim3(256), 0, s, n, parent, d_size.as<const int32_t>(), acc);
-    launches += long_rows ? 4 : 3;
+    launches += 2;
     if (want_edges) {
         if (int rc = exclusive_scan_i64(d_cnt.as<const int64_t>(), d_pos.as<int64_t>(), n + 1, s)) return rc;
-        hipLaunchKernelGGL((k_msf_fill<kGroup>), dim3(grid16), dim3(256), 0, s, n, g->off, g->adj, wgt, d_mask.as<const uint8_t>(), d_pos.as<const int64_t>(),
-                           n - 1, d_eu.as<int32_t>(), d_ev.as<int32_t>(), d_ew.as<int32_t>(), acc);
-        if (long_rows)
-            hipLaunchKernelGGL((k_msf_fill<64>), dim3(grid64), dim3(256), 0, s, n, g->off, g->adj, wgt, d_mask.as<const uint8_t>(),
-                               d_pos.as<const int64_t>(), n - 1, d_eu.as<int32_t>(), d_ev.as<int32_t>(), d_ew.as<int32_t>(), acc);
-        launches += long_rows ? 3 : 2;
+        ++launches;
+        launch_rows_two_width(MsfFill{g->adj, wgt, d_mask.as<const uint8_t>(), d_pos.as<const int64_t>(), n - 1, d_eu.as<int32_t>(), d_ev.as<int32_t>(),
+                                      d_ew.as<int32_t>(), acc},
+                              g, nullptr, cus, s, &launches);
     }
     MsfAcc a;
     GMSX_HIP(hipMemcpyAsync(&a, acc, sizeof a, hipMemcpyDeviceToHost, s));

@@ -7,11 +7,16 @@
 // (a hub of 10^5 to 10^6 entries is not one wave's job).  wave_row and wg_row are options of each algorithm (row_bounds) and first guesses,
 // not tuned values.  A class above 0 is a vertex list that k_row_classify fills once per call; the order inside a list is the arrival order
 // of atomics and reaches no output.
-// TWO SHAPES OF USE.
+// THREE SHAPES OF USE.
 //   whole-graph passes (components, bicc): three lists in one buffer; class 0 is taken straight from the vertex range 0 .. n - 1 by its
 //       degree.  launch_rows runs k_rows<Op, WIDTH> once per class: Op::row<kLanes>(v, j0, j1, lane, width) is called by all WIDTH lanes of a
 //       non-empty row (kLanes of them share a wave) and returns the arcs this lane looked at; Op::begin() by every thread before its first
 //       row, Op::finish() after its last, both converged.
+//   two-width whole-graph passes (msf, matching, bicc, sssp): no list at all.  launch_rows_two_width runs the same k_rows twice over the
+//       vertex range: a kGroup-lane group per row of at most kLongRow entries, EMPTY ROWS INCLUDED (an Op with nothing to do there falls
+//       through its own loop), and, only where the graph has one, a wave per longer row.  Both widths fit a wave (kLanes == WIDTH), so a
+//       row's lanes may ballot (RowGroup<kLanes>) and keep its CSR order, or fold one result per row; the Op is the kernel's by-value
+//       argument: begin() sets its per-thread sums and does every read that belongs before the row loop, finish() folds and adds them.
 //   live-list rounds (msf, matching): four lists in each of two buffers, rows without an arc in none; a round reads buffer cur and may append
 //       to the other.  launch_live_rows runs k_live_rows<Op, WIDTH> over the non-empty classes: a wave (WIDTH = 256: the workgroup) takes
 //       its rows together and stays converged, so Op::row<WIDTH>(v, active, lane), called by every thread whether its row exists or not, may
@@ -44,6 +49,12 @@ inline RowBounds row_bounds(const char *wave_name, const char *wg_name) {
     const int64_t wave_row = std::max<long long>(1, std::min<long long>(opt_int(wave_name, kWaveRowDefault), INT_MAX));
     const int64_t wg_row = std::max<long long>(wave_row, std::min<long long>(opt_int(wg_name, kWgRowDefault), INT_MAX));
     return {std::min<int64_t>(kShortRow, wave_row), wave_row, wg_row};
+}
+
+// THE GRIDS: workgroups of 256 threads for `rows` rows of `width` lanes each, at most per_cu of them per compute unit.  In use: a lane per
+// row and 16, a kGroup-lane group and 32, a wave and 8 (whole-graph passes); kRowsPerCu (live lists).
+inline unsigned row_grid(int64_t rows, int width, int cus, int per_cu) {
+    return unsigned(std::min<int64_t>((rows * width + 255) / 256, int64_t(cus) * per_cu));
 }
 
 // the lists: list b of buffer i is buf[i] + base[b], at most cap[b] entries; count[b] (four device words per buffer, in the caller's control
@@ -95,16 +106,15 @@ __global__ __launch_bounds__(256) void k_row_classify(int64_t n, const int64_t *
 }
 template <bool kLaneList>
 void classify_rows(const gmsx_graph *g, const RowBounds &r, const RowLists &l, int32_t *count, int32_t *error, int cus, hipStream_t s, int *launches) {
-    const unsigned sweep = unsigned(std::min<int64_t>((g->n + 255) / 256, int64_t(cus) * 16));
-    hipLaunchKernelGGL(k_row_classify<kLaneList>, dim3(sweep), dim3(256), 0, s, g->n, g->off, r, l, count, error);
+    hipLaunchKernelGGL(k_row_classify<kLaneList>, dim3(row_grid(g->n, 1, cus, 16)), dim3(256), 0, s, g->n, g->off, r, l, count, error);
     ++*launches;
 }
 
-// A WHOLE-GRAPH ROW PASS: WIDTH lanes per row.  list == nullptr: the rows are the vertices 0 .. n - 1 with fewer than dmax entries; else
+// A WHOLE-GRAPH ROW PASS: WIDTH lanes per row of dmin <= entries < dmax.  list == nullptr: the rows are the vertices 0 .. n - 1; else
 // list[0 .. *count), clamped to list_cap.  The arcs looked at are added to *examined.
 template <class Op, int WIDTH>
 __global__ __launch_bounds__(256) void k_rows(Op op, int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ list,
-                                              const int32_t *__restrict__ count, int64_t list_cap, int64_t dmax,
+                                              const int32_t *__restrict__ count, int64_t list_cap, int64_t dmin, int64_t dmax,
                                               unsigned long long *__restrict__ examined_all) {
     constexpr int kLanes = WIDTH > 64 ? 64 : WIDTH;
     const int lane = threadIdx.x & (WIDTH - 1);
@@ -116,7 +126,7 @@ __global__ __launch_bounds__(256) void k_rows(Op op, int64_t n, const int64_t *_
     for (int64_t i = row0; i < rows; i += rows_step) {
         const int32_t v = list ? list[i] : int32_t(i);
         const int64_t j0 = off[v], j1 = off[v + 1];
-        if (j1 - j0 >= dmax || j1 == j0) continue;
+        if (j1 - j0 >= dmax || j1 - j0 < dmin) continue;
         examined += op.template row<kLanes>(v, j0, j1, lane, WIDTH);
     }
     op.finish();
@@ -128,14 +138,25 @@ template <class Op>
 void launch_rows(const Op &op, const gmsx_graph *g, const RowBounds &r, const RowLists &l, const int32_t *count, unsigned long long *examined, int cus,
                  hipStream_t s, int *launches) {
     const int64_t n = g->n;
-    const unsigned lanes = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
-    const unsigned grid = unsigned(cus) * 8;
-    const int64_t all = INT64_MAX;
-    hipLaunchKernelGGL((k_rows<Op, 1>), dim3(lanes), dim3(256), 0, s, op, n, g->off, (const int32_t *)nullptr, count, int64_t(0), r.short_row, examined);
-    hipLaunchKernelGGL((k_rows<Op, kGroup>), dim3(grid), dim3(256), 0, s, op, n, g->off, l.buf[0] + l.base[1], count + 1, l.cap[1], all, examined);
-    hipLaunchKernelGGL((k_rows<Op, 64>), dim3(grid), dim3(256), 0, s, op, n, g->off, l.buf[0] + l.base[2], count + 2, l.cap[2], all, examined);
-    hipLaunchKernelGGL((k_rows<Op, 256>), dim3(grid), dim3(256), 0, s, op, n, g->off, l.buf[0] + l.base[3], count + 3, l.cap[3], all, examined);
+    const unsigned lanes = row_grid(n, 1, cus, 16), grid = unsigned(cus) * 8;
+    const int64_t one = 1, all = INT64_MAX;
+    hipLaunchKernelGGL((k_rows<Op, 1>), dim3(lanes), dim3(256), 0, s, op, n, g->off, (const int32_t *)nullptr, count, int64_t(0), one, r.short_row, examined);
+    hipLaunchKernelGGL((k_rows<Op, kGroup>), dim3(grid), dim3(256), 0, s, op, n, g->off, l.buf[0] + l.base[1], count + 1, l.cap[1], one, all, examined);
+    hipLaunchKernelGGL((k_rows<Op, 64>), dim3(grid), dim3(256), 0, s, op, n, g->off, l.buf[0] + l.base[2], count + 2, l.cap[2], one, all, examined);
+    hipLaunchKernelGGL((k_rows<Op, 256>), dim3(grid), dim3(256), 0, s, op, n, g->off, l.buf[0] + l.base[3], count + 3, l.cap[3], one, all, examined);
     *launches += 4;
+}
+// THE TWO-WIDTH PLAN over the same kernel, no lists: a kGroup-lane group for every vertex with at most kLongRow entries, then — only where
+// the graph has such a row — a wave for every longer one.  An Op that counts no arcs returns 0 from row and may leave examined null.
+template <class Op>
+void launch_rows_two_width(const Op &op, const gmsx_graph *g, unsigned long long *examined, int cus, hipStream_t s, int *launches) {
+    const int64_t n = g->n, wide = int64_t(kLongRow) + 1;
+    hipLaunchKernelGGL((k_rows<Op, kGroup>), dim3(row_grid(n, kGroup, cus, 32)), dim3(256), 0, s, op, n, g->off, (const int32_t *)nullptr,
+                       (const int32_t *)nullptr, int64_t(0), int64_t(0), wide, examined);
+    if (g->max_deg > kLongRow)
+        hipLaunchKernelGGL((k_rows<Op, 64>), dim3(row_grid(n, 64, cus, 8)), dim3(256), 0, s, op, n, g->off, (const int32_t *)nullptr,
+                           (const int32_t *)nullptr, int64_t(0), wide, int64_t(INT64_MAX), examined);
+    *launches += g->max_deg > kLongRow ? 2 : 1;
 }
 
 // A LIVE-LIST ROW PASS: WIDTH lanes per row of list[0 .. *count), clamped to list_cap.  A wave takes 64 / WIDTH consecutive rows at a time and
@@ -164,7 +185,7 @@ template <int WIDTH, class Op>
 void launch_live_class(const Op &op, const RowLists &l, int cur, int b, const int32_t *count, int64_t rows, unsigned long long *examined, int cus,
                        hipStream_t s, int *launches) {
     if (rows <= 0) return;
-    const unsigned grid = unsigned(std::min<int64_t>((rows * WIDTH + 255) / 256, int64_t(cus) * kRowsPerCu[b]));
+    const unsigned grid = row_grid(rows, WIDTH, cus, kRowsPerCu[b]);
     hipLaunchKernelGGL((k_live_rows<Op, WIDTH>), dim3(grid), dim3(256), 0, s, op, l.buf[cur] + l.base[b], count + b, l.cap[b], examined);
     ++*launches;
 }

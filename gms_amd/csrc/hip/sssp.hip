@@ -35,6 +35,7 @@
 #include "device_buffer.hpp"
 #include "device_graph.hpp"
 #include "frontier_rounds.hpp"
+#include "row_classes.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -179,36 +180,36 @@ __global__ __launch_bounds__(256) void k_sssp_info(int64_t n, const int64_t *__r
     }
 }
 
-// THE PULL PASS over dist (int64, below 0 = unreached): WIDTH lanes per vertex (kGroup: rows up to kLongRow; 64: the longer ones) walk its
-// ascending row chunk by chunk, a ballot per chunk; the lowest lane of the first chunk with a tight entry holds the smallest-id tight
-// neighbour.  kCount = false (gmsx_sssp): out at that chunk, parent written by that lane (one writer per vertex), far = the smallest id at
-// max_dist.  kCount = true (gmsx_sssp_verify): the whole row, and the three counts.  Arc u→v is met in v's row: the weights are symmetric.
-template <int WIDTH, bool kCount>
-__global__ __launch_bounds__(256) void k_sssp_pull(int64_t n, const int64_t *__restrict__ off, const int32_t *__restrict__ adj,
-                                                   const int32_t *__restrict__ wgt, const long long *__restrict__ dist, int32_t source,
-                                                   int32_t *__restrict__ parent, SsspAcc *__restrict__ acc) {
-    const RowGroup<WIDTH> grp;
-    const int lane = grp.lane;
-    const int64_t row0 = (int64_t(blockIdx.x) * blockDim.x + threadIdx.x) / WIDTH;
-    const int64_t rows_step = (int64_t(gridDim.x) * blockDim.x) / WIDTH;
-    const unsigned long long max_dist = kCount ? 0ull : acc->max_dist;
-    unsigned long long violated = 0, untight = 0, wrong = 0;
-    for (int64_t v = row0; v < n; v += rows_step) {  // (uniform in the group: its lanes leave together)
-        const int64_t j0 = off[v], j1 = off[v + 1];
-        const bool is_long = j1 - j0 > kLongRow;
-        if (is_long != (WIDTH == 64)) continue;
+// THE PULL PASS over dist (int64, below 0 = unreached), an Op of row_classes.hpp's two-width pass: the lanes of a vertex walk its ascending
+// row chunk by chunk, a ballot per chunk; the lowest lane of the first chunk with a tight entry holds the smallest-id tight neighbour.
+// kCount = false (gmsx_sssp): out at that chunk, parent written by that lane (one writer per vertex), far = the smallest id at max_dist; an
+// unreached vertex and the source, with or without a row, are settled before the walk.  kCount = true (gmsx_sssp_verify): the whole row,
+// and the three counts.  Arc u→v is met in v's row: the weights are symmetric.
+template <bool kCount>
+struct SsspPull {
+    const int32_t *adj, *wgt;
+    const long long *dist;
+    int32_t source;
+    int32_t *parent;
+    SsspAcc *acc;
+    unsigned long long max_dist = 0;                          // acc->max_dist, read once before the first row
+    unsigned long long violated = 0, untight = 0, wrong = 0;  // this thread's sums: begin() sets them
+    __device__ __forceinline__ void begin() { max_dist = kCount ? 0ull : acc->max_dist; violated = untight = wrong = 0; }
+    template <int kLanes>
+    __device__ __forceinline__ unsigned long long row(int32_t v, int64_t j0, int64_t j1, int lane, int width) {
+        const RowGroup<kLanes> grp;
         const long long dv = dist[v];
-        const bool is_source = v == int64_t(source);
+        const bool is_source = v == source;
         if (!kCount) {
             if (dv < 0 || is_source) {
                 if (lane == 0) parent[v] = is_source && dv >= 0 ? source : -1;
-                if (lane == 0 && is_source && (unsigned long long)dv == max_dist) atomicMin(&acc->far, int32_t(v));
-                continue;
+                if (lane == 0 && is_source && (unsigned long long)dv == max_dist) atomicMin(&acc->far, v);
+                return 0;
             }
-            if (lane == 0 && (unsigned long long)dv == max_dist) atomicMin(&acc->far, int32_t(v));
+            if (lane == 0 && (unsigned long long)dv == max_dist) atomicMin(&acc->far, v);
         }
         bool found = false, neighbour_reached = false;
-        for (int64_t c = j0; c < j1; c += WIDTH) {
+        for (int64_t c = j0; c < j1; c += width) {
             const int64_t j = c + lane;
             bool tight = false;
             int32_t u = -1;
@@ -242,16 +243,19 @@ __global__ __launch_bounds__(256) void k_sssp_pull(int64_t n, const int64_t *__r
         } else if (!found && lane == 0) {
             ++untight;
         }
+        return 0;
     }
-    violated = wave_sum(violated);
-    untight = wave_sum(untight);
-    wrong = wave_sum(wrong);
-    if ((threadIdx.x & 63) == 0) {
-        if (violated) atomicAdd(&acc->violated, violated);
-        if (untight) atomicAdd(&acc->untight, untight);
-        if (wrong) atomicAdd(&acc->wrong_unreached, wrong);
+    __device__ __forceinline__ void finish() {
+        violated = wave_sum(violated);
+        untight = wave_sum(untight);
+        wrong = wave_sum(wrong);
+        if ((threadIdx.x & 63) == 0) {
+            if (violated) atomicAdd(&acc->violated, violated);
+            if (untight) atomicAdd(&acc->untight, untight);
+            if (wrong) atomicAdd(&acc->wrong_unreached, wrong);
+        }
     }
-}
+};
 
 // ---- attaching weights ---------------------------------------------------------------------------------------------------------------------
 
@@ -324,7 +328,7 @@ int sssp_run(const gmsx_graph *g, int32_t source, long long delta, long long wg_
     const int64_t n = g->n;
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
     const unsigned per_vertex = unsigned((n + 255) / 256);
-    const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+    const unsigned sweep = row_grid(n, 1, cus, 16);
     D *dist = b.dist.as<D>();
     SsspCtrl *ctrl = b.ctrl.as<SsspCtrl>();
     const FrontierBufs bufs = b.store.bufs();
@@ -385,21 +389,12 @@ int sssp_alloc(const gmsx_graph *g, bool wide, SsspBufs &b) {
     return GMSX_OK;
 }
 
-// the pull pass over `dist` (device, int64): both widths
+// the pull pass over `dist` (device, int64)
 template <bool kCount>
 void sssp_pull(const gmsx_graph *g, const long long *dist, int32_t source, int32_t *parent, SsspAcc *acc, int *launches) {
     Ctx &c = ctx();
     const int cus = c.compute_units > 0 ? c.compute_units : 256;
-    const unsigned grid16 = unsigned(std::min<int64_t>((g->n * kGroup + 255) / 256, int64_t(cus) * 32));
-    const unsigned grid64 = unsigned(std::min<int64_t>((g->n * 64 + 255) / 256, int64_t(cus) * 8));
-    hipLaunchKernelGGL((k_sssp_pull<kGroup, kCount>), dim3(grid16), dim3(256), 0, c.stream, g->n, g->off, g->adj, g->wgt.as<const int32_t>(), dist, source,
-                       parent, acc);
-    *launches += 1;
-    if (g->max_deg > kLongRow) {
-        hipLaunchKernelGGL((k_sssp_pull<64, kCount>), dim3(grid64), dim3(256), 0, c.stream, g->n, g->off, g->adj, g->wgt.as<const int32_t>(), dist,
-                           source, parent, acc);
-        *launches += 1;
-    }
+    launch_rows_two_width(SsspPull<kCount>{g->adj, g->wgt.as<const int32_t>(), dist, source, parent, acc}, g, nullptr, cus, c.stream, launches);
 }
 
 }  // namespace
@@ -485,7 +480,7 @@ int gmsx_sssp(const gmsx_graph *g, int32_t source, int64_t delta, int64_t *dist,
         if (int rc = wide ? sssp_run<long long>(g, source, d, wg_frontier, b, &run, &launches) : sssp_run<int32_t>(g, source, d, wg_frontier, b, &run, &launches))
             return rc;
         // ---- the info and the pull pass
-        const unsigned sweep = unsigned(std::min<int64_t>((n + 255) / 256, int64_t(cus) * 16));
+        const unsigned sweep = row_grid(n, 1, cus, 16);
         if (wide)
             hipLaunchKernelGGL(k_sssp_info<long long>, dim3(sweep), dim3(256), 0, s, n, g->off, b.dist.as<const long long>(), b.out.as<long long>(), acc);
         else
